@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: 3840x2160 RGBA frames/s through hsvfilter -> colorlut (33^3, trilinear)
-on MI355X, with the HBM roofline fraction of the dominant kernel and the CPU oracle timed beside it.
+on MI355X, with the HBM roofline fraction of the dominant kernel; with --full also the secondary legs, the CPU oracle
+timed beside it and the live rocprofv3 passes.
 
-Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 launched by
+Contract (driver): `python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]`; for N>1 launched by
 torch.distributed.run with one rank per GPU. One JSON line on rank 0.
 
 A "step" = one pass of the hot path over one batch of `--batch` device-resident 4K RGBA frames:
@@ -63,8 +64,15 @@ def parse_args():
     ap.add_argument("--ctx-flag", action="append", default=[], metavar="FLAG=VALUE",
                     help="mi355_ctx_set_flag on the main context (numeric MI355_FLAG_* id = value); A/B knob, repeatable")
     ap.add_argument("--streams", type=int, default=32, help="concurrent streams of the secondary many-streams measurement (0 / 1 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary (other-content) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the secondary legs, the CPU baseline, config 5's legs, the live rocprofv3 child runs\n"
+                         "and the dedicated per-kernel bracketed pass. Without it a run sets up, warms up, times the K steps, writes\n"
+                         "--dump-outputs and prints the line (per-kernel figures then only from the timed region's own event samples)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most\n"
+                         "64 MB: a fixed seeded sample of the frames' pixels and every frame's exact per-channel sums)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--config", type=int, default=0,
                     help="0 = the headline chain (default). 5 = BASELINE config 5: `--streams` concurrent 4K streams per GPU through the\n"
                          "videocompare SSIM (dssim) engine, one comparison per stream and step; prints its own JSON line (comparisons/s)")
@@ -84,7 +92,7 @@ def parse_args():
                     help="config 5: shader clock of the VALU roofline's peak (default: the part's 2.4 GHz peak engine clock; under this load the\n"
                          "SQ counters show less - SQ_BUSY_CYCLES / 32 SEs / kernel duration, profiles/r06_dssim_sq_counters.txt - so the fraction is conservative)")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not measure roofline.traffic with rocprofv3 --pmc child runs at the end (then it is quoted from\n"
+                    help="with --full: do not measure roofline.traffic with rocprofv3 --pmc child runs at the end (then it is quoted from\n"
                          "profiles/pmc_latest.json when that profile carries this code's fingerprint, else null)")
     ap.add_argument("--dssim-two-step", action="store_true",
                     help="config 5: hash every frame with mi355_dssim_create_image and compare the two images (the round-2 form) instead of\n"
@@ -132,6 +140,33 @@ def batch_stats(torch, b):
     """Byte sum of a batch and the number of distinct colours of its first frame (content fingerprint)."""
     rgb = b[0].reshape(-1).view(torch.int32) & 0x00FFFFFF
     return {"byte_sum": int(b.sum(dtype=torch.int64).item()), "distinct_colours_frame0": int(torch.unique(rgb).numel())}
+
+
+DUMP_SEED = 20240601          # --dump-outputs: the pixel sample is a pure function of this seed, the frame size and --batch
+DUMP_SAMPLE_BYTES = 32 << 20  # the two sampled arrays together (float32); the per-frame sums add a few hundred bytes
+
+
+def last_step_outputs(torch, mid, out):
+    """--dump-outputs: what the last timed launch pair handed back. `out` holds the colorlut frames (what a caller of the chain
+    receives), `mid` the frames hsvfilter filtered in place (what it hands downstream). Per array: the same seeded sample of pixels
+    in every frame, (frames, pixels, 4) float32, and every frame's per-channel byte sums over ALL its pixels, (frames, 4) float64
+    (exact: integers far below 2^53)."""
+    nb, npx = out.shape[0], W * H
+    k = max(1, min(npx, DUMP_SAMPLE_BYTES // (2 * nb * 4 * 4)))
+    idx = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(npx, size=k, replace=False))).to(out.device)
+    res = {}
+    for name, t in (("hsvfilter_out", mid), ("colorlut_out", out)):
+        px = t.reshape(nb, npx, 4)
+        res[name] = px.index_select(1, idx).float().cpu().numpy()
+        res[name + "_channel_sums"] = px.sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64)
+    return res
+
+
+def dump_outputs(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 EVENT_EVERY = 4  # steps between per-kernel event samples inside the timed region
@@ -294,7 +329,7 @@ def live_pmc_traffic(args, kernel_prefix):
     out = tempfile.mkdtemp(prefix="mi355fx_pmc_", dir="/tmp")
     # THIS interpreter, resolved to the binary: a `python3` from PATH may be a wrapper script (pyenv, conda) = one more exec
     # under the profiler's preloaded, GPU-initialised library, which this pool forbids
-    child = [os.path.realpath(sys.executable), os.path.abspath(__file__), "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-extra", "--no-live-pmc",
+    child = [os.path.realpath(sys.executable), os.path.abspath(__file__), "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extra", "--no-live-pmc",
              "--batch", str(args.batch), "--content", args.content, "--lut-variant", str(args.lut_variant), "--pairs-per-step", str(args.pairs_per_step)]
     for f in args.ctx_flag:
         child += ["--ctx-flag", f]
@@ -347,7 +382,7 @@ def live_pmc_traffic(args, kernel_prefix):
         shutil.rmtree(out, ignore_errors=True)
     traffic = avg["FETCH_SIZE"][0] * 1024 * 2 + avg["WRITE_SIZE"][0] * 1024
     return traffic, rocprof_ms, ("live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (child processes of this run, after the timed legs) over "
-                     "`bench.py --steps 10 --warmup 2 --no-extra`: %d / %d launches averaged; FETCH_SIZE(KiB) * 1024 * 2 + WRITE_SIZE(KiB) * 1024"
+                     "`bench.py --steps 10 --warmup 2 --full --no-extra`: %d / %d launches averaged; FETCH_SIZE(KiB) * 1024 * 2 + WRITE_SIZE(KiB) * 1024"
                      % (avg["FETCH_SIZE"][1], avg["WRITE_SIZE"][1]))
 
 
@@ -587,7 +622,10 @@ def run_config5(args, rank, local_rank, world):
                "dssim_of_stream_0": results[0]}
         if gstats:
             out["dispatcher"] = {"pairs": gstats[0], "launch_sequences": gstats[1], "pairs_in_the_largest": gstats[2]}
-        if not args.no_cpu_baseline and not stub:
+        if getattr(args, "dump_outputs", None):
+            # the last timed step's score of every stream (dssim, or the blockhash distance), stream order
+            dump_outputs(args.dump_outputs, {"scores": np.asarray(results, dtype=np.float64)})
+        if args.full and not args.no_cpu_baseline and not stub:
             from oracle import dssim_restate as R
             hw, hh = W // 2, H // 2
             fa = np.ascontiguousarray(base.reshape(H, W, 4)[:hh, :hw]).reshape(hh, hw * 4)
@@ -709,9 +747,11 @@ def main():
                 done += n
             return fills
 
-        def measure(content, steps, warmup, record, fused=False, streams=None, native_round=None, solo=False):
+        def measure(content, steps, warmup, record, fused=False, streams=None, native_round=None, solo=False, dedicated=True, keep_last=False):
             """One leg: ramp on scratch batches, W warm-up steps and K timed steps, each on its own pristine batch.
             solo: this rank alone (no barrier, no MAX over ranks) - a secondary leg of rank 0 in an N > 1 run.
+            dedicated: with `record`, a bracketed pass of its own when the timed region carried few event samples.
+            keep_last: res["last_outputs"] = last_step_outputs() of the last timed launch pair (two-kernel chain only).
             streams: list of per-stream contexts - frame i of every batch then belongs to stream i and is processed by
             that stream's own context with one-frame launches (what N independent pipelines issue)."""
             nb = len(streams) if streams else args.batch
@@ -770,7 +810,7 @@ def main():
                 # launches of each kind: keep that learning phase out of the timed region (out-of-place: scratch stays pristine)
                 region(scratch, 14, False)
             srcs = [torch.empty((nb, H, W * 4), dtype=torch.uint8, device=dev) for _ in range(hold_count(steps + warmup, nb))]
-            stats = {}
+            stats, last_outputs = {}, {}
             evs, dts = [], []
 
             def warm(sl, n, first):
@@ -795,6 +835,8 @@ def main():
                 if HOST_TRACE is not None:
                     del HOST_TRACE[:]
                 dts.append(sharding.timed_region(body, dist=None if solo else dist, device_sync=torch.cuda.synchronize, keep_busy=lambda: ramp_body(min(16, args.rewarm_steps))))
+                if keep_last and first + n == warmup + steps:   # run_region's last pair: srcs k = n - 1 in place -> dsts[k % ring]
+                    last_outputs.update(last_step_outputs(torch, sl[n - 1], dsts[(n - 1) % len(dsts)]))
                 if HOST_TRACE is not None and len(HOST_TRACE) > 1:
                     gaps = [(i, (b - a) * 1e3) for i, (a, b) in enumerate(zip(HOST_TRACE, HOST_TRACE[1:])) if b - a > 1e-3]
                     print("host trace: %d launch pairs enqueued in %.1f ms of a %.1f ms region; iterations over 1 ms: %s" %
@@ -804,8 +846,10 @@ def main():
             chunks = consume(pool, srcs, steps, warmup, timed)
             dt = sum(dts)
             res = {"dt": dt, "chunks": chunks, "held": len(srcs), "source_stats": stats, "samples": len(evs), "frames": steps * nb, "launch_pairs": steps, "colorlut_kernels_served": served}
+            if keep_last:
+                res["last_outputs"] = last_outputs
             if record:
-                if len(evs) < 32:
+                if len(evs) < 32 and dedicated:
                     # few in-region samples (small K): a dedicated bracketed pass on fresh pristine batches, every launch timed
                     extra = []
 
@@ -818,6 +862,7 @@ def main():
                     res["samples"] = len(evs)
                     res["dedicated_pass_samples"] = len(extra)
                 torch.cuda.synchronize()
+            if record and evs:
                 # an event bracket is longer than the kernel inside it by the cost of one timestamped marker; that cost is
                 # calibrated live (empty brackets on the same stream, GPU busy), reported, and subtracted
                 if fused:
@@ -830,16 +875,20 @@ def main():
             return res
 
         cal = torch.zeros(FRAME_BYTES, dtype=torch.uint8, device=dev)
-        main_leg = measure(args.content, args.steps, args.warmup, True)
+        # a plain run: this leg alone (per-kernel figures only from the timed region's own event samples); --full: everything below
+        main_leg = measure(args.content, args.steps, args.warmup, True, dedicated=args.full, keep_last=bool(args.dump_outputs) and rank == 0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, main_leg["last_outputs"])
+        extras = args.full and not args.no_extra
         main_kernel_name = ctx.colorlut_kernel_name()   # the kernel that served the main leg's last colorlut launch
         dt = main_leg["dt"]
-        hsv_ms, lut_ms = main_leg["ms"]
+        hsv_ms, lut_ms = main_leg.get("ms", (None, None))
         lut_tab, lut_tc, lut_tt = ctx.colorlut_kernel_choice()
         lut_win, lut_gather_t, lut_window_t = ctx.colorlut_kernel_choice(fused=10)
         hsv_tab, hsv_tc, hsv_tt = ctx.colorlut_kernel_choice(fused=2)
         lb = BYTES_PER_FRAME_PER_KERNEL * args.batch
         interp = None
-        if not args.no_extra and args.lut_variant == 0 and world == 1:
+        if extras and args.lut_variant == 0 and world == 1:
             # the same two-launch chain with the interpolating (arithmetic) colorlut kernel pinned: no memoised table
             ctx.set_flag(mi355fx.FLAG_LUT_VARIANT, 6)
             n_i = max(10, args.steps // 2)
@@ -851,7 +900,7 @@ def main():
                       "colorlut_ms_per_launch": l_i, "colorlut_GBps": lb / (l_i * 1e-3) / 1e9,
                       "colorlut_frac_of_hbm_peak": lb / (l_i * 1e-3) / 1e9 / HBM_PEAK_GBS, "hsvfilter_ms_per_launch": h_i}
         fused = None
-        if not args.no_extra and world == 1:
+        if extras and world == 1:
             leg = measure(args.content, args.steps, args.warmup, True, fused=True)
             fused_fps = sharding.aggregate_throughput(leg["frames"], world, leg["dt"])
             fused_ms = leg["ms"][0]
@@ -869,7 +918,7 @@ def main():
                      "throughput_frac_of_hbm_peak": fused_fps * BYTES_PER_FRAME_PER_KERNEL / 1e9 / HBM_PEAK_GBS,
                      "note": "one launch per batch, 8 B/px algorithmic (SURVEY 8d fused accounting); bit-identical to the two-kernel chain"}
         nt_ab = None
-        if not args.no_extra and world == 1 and not args.stub:
+        if extras and world == 1 and not args.stub:
             # A/B: the same two launches with hsvfilter's output written past the Infinity Cache (non-temporal stores). What the
             # colorlut launch loses is what it gets from reading the batch hsvfilter has just written on-die instead of from HBM:
             # the 16 B/pixel of the headline are algorithmic bytes, and 4 of them need not touch HBM (roofline.on_die_bytes_per_launch).
@@ -880,7 +929,7 @@ def main():
                      "colorlut_kernels_served": leg["colorlut_kernels_served"],
                      "what": "the headline's two launches with MI355_FLAG_HSV_NT = 1: hsvfilter stores non-temporally, colorlut reads its input from HBM"}
         extra = None
-        if not args.no_extra and world == 1:
+        if extras and world == 1:
             other = "noise" if args.content == "smooth" else "smooth"
             n_o = max(10, args.steps // 2)
             # warm-up long enough for the colorlut kernel choice to follow the change of content (sampled every 8th launch)
@@ -890,7 +939,7 @@ def main():
                      "colorlut_kernel": ctx.colorlut_kernel_name(), "source_stats": leg["source_stats"]}
 
         streams_leg = None
-        if not args.no_extra and world == 1 and args.streams > 1:
+        if extras and world == 1 and args.streams > 1:
             # N independent streams per GPU (config 5 runs 32): one context + HIP stream per stream, one 4K frame per launch;
             # the streams load the same LUT, so they share one memoised table (mi355_shared_table_count)
             sctx, sstreams = [], []
@@ -955,7 +1004,7 @@ def main():
                 c.close()
 
         sweep = None
-        if not args.no_extra and world == 1:
+        if extras and world == 1:
             # what the chain does on other content statistics, auto kernel choice (default flags) and the arithmetic brick /
             # three-pass path pinned (variant 6): natural-like frame + uniform noise of +-amp per channel, and uniform noise
             sweep = {}
@@ -970,7 +1019,7 @@ def main():
                 row["distinct_colours_frame0"] = leg["source_stats"]["first"]["distinct_colours_frame0"]
                 sweep[label] = row
             ctx.set_flag(mi355fx.FLAG_LUT_VARIANT, args.lut_variant)
-        elif not args.no_extra and world > 1 and rank == 0:
+        elif extras and world > 1 and rank == 0:
             # N > 1: the secondary legs are dropped, but the scaling record should show more than the amp-0 number - rank 0 alone
             # (the other ranks wait at the final barrier, their GPUs idle) measures the chain on the natural-like frame + uniform
             # noise of +-4 per channel with the default flags. One GPU's figure, not the job's.
@@ -983,7 +1032,7 @@ def main():
     fps = sharding.aggregate_throughput(main_leg["frames"], world, dt)
     ms_per_step = dt / args.steps * 1e3
     config5 = None
-    if not args.no_extra and world == 1 and not args.stub and args.streams > 1:
+    if extras and world == 1 and not args.stub and args.streams > 1:
         # BASELINE config 5 (32 concurrent 4K streams per GPU through the SSIM engine) as a short leg of the default line
         leg_args = argparse.Namespace(**vars(args))
         leg_args.as_leg, leg_args.streams, leg_args.workers, leg_args.steps, leg_args.warmup = True, 32, 8, 48, 4
@@ -1018,38 +1067,6 @@ def main():
         config5["as_pads_of_two_aggregators"] = run_config5(leg_args, rank, local_rank, 1)
 
     if rank == 0:
-        # dominant kernel = the longer of the two launches
-        per_launch_bytes = lb
-        # the kernel that served most of the main leg's colorlut launches (auto may sample the other kinds in between)
-        served = main_leg.get("colorlut_kernels_served") or {}
-        lut_name = max(served, key=served.get) if served else main_kernel_name
-        if lut_ms >= hsv_ms:
-            dom, dom_ms = lut_name, lut_ms
-        else:
-            dom, dom_ms = ("colorlut_table_tiled_kernel (hsvfilter table)" if hsv_tab else "hsvfilter_flat_kernel"), hsv_ms
-        achieved = per_launch_bytes / (dom_ms * 1e-3) / 1e9
-        # HBM bytes per launch cannot be read from inside the process: `traffic` comes from rocprofv3 --pmc passes run as child
-        # processes at the end of this run (live_pmc_traffic); if that is not possible (no rocprofv3, N > 1, --no-extra), it is the
-        # per-launch figure of the committed passes of THIS command (tools/collect_profiles.sh -> profiles/pmc_latest.json) when that
-        # profile was taken with the same batch size, content, kernel and code; otherwise null. The provenance is spelled out next to it.
-        traffic, traffic_src, live_note, rocprof_ms = None, None, None, None
-        if world == 1 and not args.stub and not args.no_extra and not args.no_live_pmc:
-            # measured on this box, by this run (a committed file is not a measurement of the driver's run)
-            traffic, rocprof_ms, traffic_src = live_pmc_traffic(args, dom.split(" ")[0].split("<")[0])
-            if traffic is None:
-                live_note, traffic_src = traffic_src, None
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json"))) if traffic is None else {}
-            if (pmc.get("frames_per_launch", pmc.get("frames_per_step")) == args.batch and pmc.get("content", "smooth") == args.content
-                    and pmc.get("pristine_sources") and pmc.get("lut_variant", 0) == args.lut_variant
-                    and pmc.get("source_fingerprint") == source_fingerprint()):   # taken from THIS code, or null
-                for kname, rec in pmc.get("kernels", {}).items():
-                    if kname.startswith(dom.split(" ")[0].split("<")[0]):
-                        traffic = rec["hbm_bytes"]
-                        traffic_src = "profiles/pmc_latest.json: separate rocprofv3 --pmc passes of this command (%s)" % pmc.get("collected", "?")
-        except (OSError, ValueError, KeyError):
-            pass
-        chain_gbs = 2 * per_launch_bytes / ((hsv_ms + lut_ms) * 1e-3) / 1e9
         out = {
             "metric": "4K RGBA frames/sec through hsvfilter+colorlut at 1 GPU; % HBM roofline",
             "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1059,37 +1076,70 @@ def main():
                        "frames_per_step": args.batch * args.pairs_per_step, "frames_per_launch": args.batch,
                        "launches_per_step": 2 * args.pairs_per_step, "content": args.content,
                        "algorithmic_bytes_per_frame": 2 * BYTES_PER_FRAME_PER_KERNEL, "streams_per_gpu": 1,
-                       "lut_variant": args.lut_variant, "ctx_flags": args.ctx_flag, "ramp_seconds": args.ramp_seconds, "rewarm_steps": args.rewarm_steps, "event_marker_ms": marker_ms(),
+                       "lut_variant": args.lut_variant, "ctx_flags": args.ctx_flag, "ramp_seconds": args.ramp_seconds, "rewarm_steps": args.rewarm_steps, "event_marker_ms": marker.get("ms"),
                        "sources": "pristine: every warm-up/timed step filters its own never-touched batch (in place)",
                        "source_batches_held": main_leg["held"], "source_chunks": main_leg["chunks"],
                        "source_stats": main_leg["source_stats"], "dst_ring_batches": args.ring,
                        "timing_group": "gloo (CPU) barrier + MAX; no RCCL" if world > 1 else "single process"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_live_note": live_note,
-                         "source_fingerprint": source_fingerprint(),
-                         "algorithmic_bytes_per_launch": per_launch_bytes, "avg_launch_ms": dom_ms,
-                         # of the algorithmic bytes of a colorlut launch, its input (half) was written by the hsvfilter launch just
-                         # before it and can be served by the 256 MiB Infinity Cache instead of HBM: an upper bound, not a counter
-                         # (FETCH_SIZE counts Infinity-Cache hits too); the measured effect is the hsvfilter_nontemporal_ab leg
-                         "on_die_bytes_per_launch": (min(per_launch_bytes // 2, 256 << 20) if lut_ms >= hsv_ms else 0),
-                         "on_die_note": "upper bound: the part of this launch's input that the preceding hsvfilter launch left in the Infinity Cache (256 MiB); "
-                                        "with hsvfilter's stores made non-temporal the same launch reads it from HBM - see hsvfilter_nontemporal_ab",
-                         "rocprof_avg_launch_ms": rocprof_ms,   # the same kernel in a rocprofv3 --kernel-trace --stats child run on this box
-                         "avg_launch_ms_raw_bracket": main_leg["raw_ms"][1] if lut_ms >= hsv_ms else main_leg["raw_ms"][0],
-                         "launch_samples": main_leg["samples"]},
-            "kernels": {"hsvfilter_ms_per_launch": hsv_ms, "colorlut_ms_per_launch": lut_ms,
-                        "hsvfilter_ms_raw_bracket": main_leg["raw_ms"][0], "colorlut_ms_raw_bracket": main_leg["raw_ms"][1],
-                        "hsvfilter_GBps": per_launch_bytes / (hsv_ms * 1e-3) / 1e9,
-                        "colorlut_GBps": per_launch_bytes / (lut_ms * 1e-3) / 1e9,
-                        "chain_GBps": chain_gbs, "chain_frac_of_hbm_peak": chain_gbs / HBM_PEAK_GBS,
-                        "colorlut_kernel": lut_name, "colorlut_kernels_served": main_leg["colorlut_kernels_served"],
-                        "colorlut_auto_ms_per_mpx": {"compute": lut_tc, "table": lut_tt},
-                        "colorlut_table_kernel_ms_per_mpx": {"gather": lut_gather_t, "lds_cached": lut_window_t, "lds_cached_in_use": bool(lut_win)},
-                        "hsvfilter_kernel": "colorlut_table_tiled_kernel (hsvfilter table)" if hsv_tab else "hsvfilter_flat_kernel",
-                        "hsvfilter_auto_ms_per_mpx": {"compute": hsv_tc, "table": hsv_tt},
-                        "event_marker_ms_subtracted": marker_ms(), "samples": main_leg["samples"],
-                        "dedicated_pass_samples": main_leg.get("dedicated_pass_samples", 0)},
         }
+        if hsv_ms is not None:   # per-kernel figures: the timed region's event samples (+ the dedicated pass with --full)
+            # dominant kernel = the longer of the two launches
+            per_launch_bytes = lb
+            # the kernel that served most of the main leg's colorlut launches (auto may sample the other kinds in between)
+            served = main_leg.get("colorlut_kernels_served") or {}
+            lut_name = max(served, key=served.get) if served else main_kernel_name
+            if lut_ms >= hsv_ms:
+                dom, dom_ms = lut_name, lut_ms
+            else:
+                dom, dom_ms = ("colorlut_table_tiled_kernel (hsvfilter table)" if hsv_tab else "hsvfilter_flat_kernel"), hsv_ms
+            achieved = per_launch_bytes / (dom_ms * 1e-3) / 1e9
+            # HBM bytes per launch cannot be read from inside the process: `traffic` comes from rocprofv3 --pmc passes run as child
+            # processes at the end of this run (live_pmc_traffic); if that is not possible (no rocprofv3, N > 1, no --full, --no-extra), it is the
+            # per-launch figure of the committed passes of THIS command (tools/collect_profiles.sh -> profiles/pmc_latest.json) when that
+            # profile was taken with the same batch size, content, kernel and code; otherwise null. The provenance is spelled out next to it.
+            traffic, traffic_src, live_note, rocprof_ms = None, None, None, None
+            if world == 1 and not args.stub and extras and not args.no_live_pmc:
+                # measured on this box, by this run (a committed file is not a measurement of the driver's run)
+                traffic, rocprof_ms, traffic_src = live_pmc_traffic(args, dom.split(" ")[0].split("<")[0])
+                if traffic is None:
+                    live_note, traffic_src = traffic_src, None
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json"))) if traffic is None else {}
+                if (pmc.get("frames_per_launch", pmc.get("frames_per_step")) == args.batch and pmc.get("content", "smooth") == args.content
+                        and pmc.get("pristine_sources") and pmc.get("lut_variant", 0) == args.lut_variant
+                        and pmc.get("source_fingerprint") == source_fingerprint()):   # taken from THIS code, or null
+                    for kname, rec in pmc.get("kernels", {}).items():
+                        if kname.startswith(dom.split(" ")[0].split("<")[0]):
+                            traffic = rec["hbm_bytes"]
+                            traffic_src = "profiles/pmc_latest.json: separate rocprofv3 --pmc passes of this command (%s)" % pmc.get("collected", "?")
+            except (OSError, ValueError, KeyError):
+                pass
+            chain_gbs = 2 * per_launch_bytes / ((hsv_ms + lut_ms) * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_live_note": live_note,
+                               "source_fingerprint": source_fingerprint(),
+                               "algorithmic_bytes_per_launch": per_launch_bytes, "avg_launch_ms": dom_ms,
+                               # of the algorithmic bytes of a colorlut launch, its input (half) was written by the hsvfilter launch just
+                               # before it and can be served by the 256 MiB Infinity Cache instead of HBM: an upper bound, not a counter
+                               # (FETCH_SIZE counts Infinity-Cache hits too); the measured effect is the hsvfilter_nontemporal_ab leg
+                               "on_die_bytes_per_launch": (min(per_launch_bytes // 2, 256 << 20) if lut_ms >= hsv_ms else 0),
+                               "on_die_note": "upper bound: the part of this launch's input that the preceding hsvfilter launch left in the Infinity Cache (256 MiB); "
+                                              "with hsvfilter's stores made non-temporal the same launch reads it from HBM - see hsvfilter_nontemporal_ab",
+                               "rocprof_avg_launch_ms": rocprof_ms,   # the same kernel in a rocprofv3 --kernel-trace --stats child run on this box
+                               "avg_launch_ms_raw_bracket": main_leg["raw_ms"][1] if lut_ms >= hsv_ms else main_leg["raw_ms"][0],
+                               "launch_samples": main_leg["samples"]}
+            out["kernels"] = {"hsvfilter_ms_per_launch": hsv_ms, "colorlut_ms_per_launch": lut_ms,
+                              "hsvfilter_ms_raw_bracket": main_leg["raw_ms"][0], "colorlut_ms_raw_bracket": main_leg["raw_ms"][1],
+                              "hsvfilter_GBps": per_launch_bytes / (hsv_ms * 1e-3) / 1e9,
+                              "colorlut_GBps": per_launch_bytes / (lut_ms * 1e-3) / 1e9,
+                              "chain_GBps": chain_gbs, "chain_frac_of_hbm_peak": chain_gbs / HBM_PEAK_GBS,
+                              "colorlut_kernel": lut_name, "colorlut_kernels_served": main_leg["colorlut_kernels_served"],
+                              "colorlut_auto_ms_per_mpx": {"compute": lut_tc, "table": lut_tt},
+                              "colorlut_table_kernel_ms_per_mpx": {"gather": lut_gather_t, "lds_cached": lut_window_t, "lds_cached_in_use": bool(lut_win)},
+                              "hsvfilter_kernel": "colorlut_table_tiled_kernel (hsvfilter table)" if hsv_tab else "hsvfilter_flat_kernel",
+                              "hsvfilter_auto_ms_per_mpx": {"compute": hsv_tc, "table": hsv_tt},
+                              "event_marker_ms_subtracted": marker_ms(), "samples": main_leg["samples"],
+                              "dedicated_pass_samples": main_leg.get("dedicated_pass_samples", 0)}
         if interp:
             out["interpolating_kernel_only"] = interp
         if fused:
@@ -1104,7 +1154,7 @@ def main():
             out["content_sweep"] = sweep
         if config5:
             out["config5"] = config5
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             one, mt = cpu_baseline(synth, settings, cube_text, seconds_target=0.5 if args.stub else 12.0)
             out["cpu_baseline"] = one
             out["cpu_baseline_all_cores"] = mt

@@ -1,12 +1,15 @@
 """bench.py's N>1 control flow end to end on the CPU: two ranks under torch.distributed.run with `--stub` (tiny CPU frames, a
 context that sleeps instead of launching kernels). Checks what the driver relies on: one JSON line from rank 0 only, n_gpus = 2,
 `value` = the units ALL ranks processed / the MAX-over-ranks time (rank 1 is made twice as slow), the timing group is gloo (no
-RCCL anywhere), and cpu_baseline is present at N > 1."""
+RCCL anywhere), and with --full cpu_baseline is present at N > 1. A plain run (no --full) is the headline alone; --dump-outputs
+writes what its last timed step computed."""
 import json
 import os
 import socket
 import subprocess
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,7 +34,7 @@ def _run(nproc, steps=6, warmup=2, extra=()):
 
 
 def test_two_ranks_aggregate_over_the_slowest_rank():
-    d = _run(2)
+    d = _run(2, extra=("--full",))
     assert d["n_gpus"] == 2 and d["steps"] == 6 and d["warmup"] == 2 and d["data"] == "stub" and d["scaling"] == "weak"
     assert "gloo" in d["config"]["timing_group"] and "RCCL" in d["config"]["timing_group"]
     # rank 1 sleeps 2 ms per launch, rank 0 1 ms: a step is four (hsvfilter, colorlut) pairs = 8 launches -> >= 16 ms on the slowest rank
@@ -51,7 +54,7 @@ def test_two_ranks_aggregate_over_the_slowest_rank():
 
 def test_single_process_stub_has_all_legs():
     env = dict(os.environ, OMP_NUM_THREADS="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--stub", "--ramp-seconds", "0.02"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--stub", "--ramp-seconds", "0.02", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -95,3 +98,57 @@ def test_config5_single_process_stub_without_the_dispatcher():
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["config"]["worker_contexts_per_gpu"] == 2 and "dispatcher" not in d
+
+
+def _single(args, tmp_path=None):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--ramp-seconds", "0.02"] + list(args),
+                         capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, OMP_NUM_THREADS="1"))
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full: no secondary leg, no CPU baseline, no dedicated bracketed pass; the headline keys mean what they do with it."""
+    d = _single(["--steps", "20", "--warmup", "2"])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in d, key
+    assert d["steps"] == 20 and d["warmup"] == 2 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert abs(d["value"] - 20 * d["config"]["frames_per_step"] / (d["ms_per_step"] * 1e-3 * 20)) / d["value"] < 1e-6
+    for key in ("interpolating_kernel_only", "fused_chain", "hsvfilter_nontemporal_ab", "other_content", "concurrent_streams",
+                "content_sweep", "config5", "cpu_baseline", "cpu_baseline_all_cores"):
+        assert key not in d, key
+    # 80 timed launch pairs carry 20 in-region event samples: per-kernel figures from those alone
+    assert d["kernels"]["samples"] == 20 and d["kernels"]["dedicated_pass_samples"] == 0 and d["roofline"]["bound"] == "hbm"
+    assert d["roofline"]["traffic_live_note"] is None and d["roofline"]["rocprof_avg_launch_ms"] is None
+    # too short for in-region samples: no per-kernel figures rather than a run of their own
+    d = _single(["--steps", "3", "--warmup", "1"])
+    assert "kernels" not in d and "roofline" not in d and d["config"]["event_marker_ms"] is None and d["steps"] == 3
+
+
+def test_dump_outputs_is_the_last_timed_step(tmp_path, synth):
+    """--dump-outputs: float arrays within 64 MB; under --stub hsvfilter does nothing, so the dumped hsvfilter output is the
+    pristine source batch of the last timed launch pair (SourcePool index (warmup + steps) x pairs - 1), sampled and summed."""
+    steps, warmup, pairs = 5, 1, 4
+    _single(["--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "out")])
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["colorlut_out.npy", "colorlut_out_channel_sums.npy", "hsvfilter_out.npy", "hsvfilter_out_channel_sums.npy"]
+    arrays = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= 64 << 20
+    w, h, nb = 64, 16, 8                                        # the stub's frame and the default --batch
+    index = (warmup + steps) * pairs - 1
+    base = synth.smooth_frame(w, h, seed=synth.SEED + 17 * (index % 4))
+    frames = np.stack([np.roll(base, 4 * ((97 * i + 389 * (index // 4)) % w), axis=1) for i in range(nb)]).reshape(nb, w * h, 4)
+    assert arrays["hsvfilter_out"].shape == (nb, w * h, 4) and arrays["colorlut_out"].shape == (nb, w * h, 4)
+    assert (arrays["hsvfilter_out"] == frames).all()            # a frame this small is sampled whole, in pixel order
+    assert (arrays["hsvfilter_out_channel_sums"] == frames.sum(axis=1)).all()
+    assert arrays["colorlut_out_channel_sums"].shape == (nb, 4)
+
+
+def test_config5_dump_outputs(tmp_path):
+    d = _single(["--config", "5", "--steps", "2", "--warmup", "1", "--streams", "4", "--workers", "2", "--dump-outputs", str(tmp_path)])
+    scores = np.load(tmp_path / "scores.npy")
+    assert scores.dtype == np.float64 and scores.shape == (4,) and scores[0] == d["dssim_of_stream_0"]
+    assert "cpu_baseline" not in d

@@ -5,8 +5,8 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
 O=gpurun_out/r06_baseline; rm -rf $O; mkdir -p $O
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_protocol.json 2> $O/driver_protocol.err
-python3 bench.py --steps 20 --warmup 5 --batch 16 --ring 2 --no-cpu-baseline --no-live-pmc > $O/batch16.json 2> $O/batch16.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_protocol.json 2> $O/driver_protocol.err
+python3 bench.py --steps 20 --warmup 5 --batch 16 --ring 2 --full --no-cpu-baseline --no-live-pmc > $O/batch16.json 2> $O/batch16.err
 bash tools/pmc_brick.sh > $O/brick_sq_counters.txt 2>&1
 bash tools/pmc_dssim.sh > $O/dssim_sq_counters.txt 2>&1
 ( cd /tmp && export TMPDIR=/tmp

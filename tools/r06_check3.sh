@@ -7,7 +7,7 @@ timeout 1500 python3 -m pytest tests -q -m gpu > $O/pytest_gpu.txt 2>&1; echo "p
 tail -8 $O/pytest_gpu.txt
 timeout 300 python3 tools/stress_dispatch.py 25 > $O/stress_dispatch.txt 2>&1; echo "stress rc=$?" >> $O/stress_dispatch.txt; tail -5 $O/stress_dispatch.txt
 timeout 300 ./tools/agroup_bench 32 audio > $O/agroup_bench_32.jsonl 2> $O/agroup_bench.err; cut -c1-420 $O/agroup_bench_32.jsonl
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_protocol.json 2> $O/driver_protocol.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_protocol.json 2> $O/driver_protocol.err
 python3 - $O <<'PY'
 import json, sys
 o = sys.argv[1]

@@ -10,7 +10,7 @@ for rep in 1 2; do
 done > $O/probe.txt 2>&1
 cat $O/probe.txt
 for lib in "" "$R/gst-plugins-rs_amd/exp/libmi355fx_depth3.so"; do
-  MI355FX_LIB=$lib python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-live-pmc --streams 0 2>/dev/null | python3 -c "
+  MI355FX_LIB=$lib python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-live-pmc --streams 0 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('lib [%s]: fused %.0f frames/s (%.4f ms per launch, %s), headline %.0f' % ('$lib'[-25:], d['fused_chain']['frames_per_s'], d['fused_chain']['ms_per_launch'], d['fused_chain'].get('kernels_served'), d['value']))"

@@ -6,7 +6,7 @@ O=gpurun_out/r06_final; rm -rf $O; mkdir -p $O
 timeout 1500 python3 -m pytest tests -q -m gpu > $O/r06_final_pytest.txt 2>&1; echo "pytest rc=$?" >> $O/r06_final_pytest.txt
 tail -4 $O/r06_final_pytest.txt
 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_driver_protocol.json 2> $O/driver_protocol.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r06_driver_protocol.json 2> $O/driver_protocol.err
 bash tools/trace_full_once.sh > $O/trace_full_once.log 2>&1
 cp gpurun_out/trace_full_once/kernel_stats_full.csv $O/r06_kernel_stats_full.csv 2>/dev/null
 python3 - $O <<'PY'

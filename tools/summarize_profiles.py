@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/summarize_profiles.py <tag> — condense gpurun_out/profiles_<tag>/ into tracked files under profiles/:
   profiles/<tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary (verbatim) of `bench.py --no-cpu-baseline --no-extra`
-  profiles/<tag>_kernel_stats_full.csv   the same for the plain `bench.py` command (all legs)
+  profiles/<tag>_kernel_stats_full.csv   the same for `bench.py --full` (all legs)
   profiles/<tag>_pmc.json           per-kernel FETCH_SIZE / WRITE_SIZE averages and corrected HBM bytes/launch
   profiles/<tag>_bench.json         the bench.py line of the same run
   profiles/pmc_latest.json          copy of <tag>_pmc.json that bench.py reads for roofline.traffic

@@ -189,6 +189,7 @@ void mi355_ctx_destroy(mi355_ctx *ctx) {
   loudnorm_batch_release(ctx);
   dssim_release(ctx);
   roundedcorners_release(ctx);
+  colordetect_release(ctx);
   ebur128_release(ctx);
   hrtf_release(ctx);
   sofa_release(ctx);

@@ -97,6 +97,7 @@ struct mi355_ctx {
   void *loudnorm_batch = nullptr;  // mi355::LoudNormBatch (loudnorm.hip): n streams in lock step
   void *dssim_cache = nullptr; // mi355::DssimCache (dssim_kernels.hip)
   void *rounded = nullptr;     // mi355::RoundedMask (roundedcorners.hip): the element's alpha plane, device-resident
+  void *colordetect = nullptr; // mi355::ColorDetectState (colordetect.hip): histograms and palette results
   // host <-> device copies this context has enqueued through the library's own entry points and mi355_buf objects (tests assert
   // that a chain of elements on device buffers costs ONE upload and ONE download: mi355_ctx_transfer_counts)
   unsigned long long n_h2d = 0, n_d2h = 0;
@@ -223,6 +224,7 @@ int blockhash_enqueue(mi355_ctx *ctx, const uint8_t *const *d_frames, int n, int
 int dssim_cbrt_selftest(mi355_ctx *ctx, uint32_t lo_bits, uint32_t hi_bits, uint64_t *mismatches);
 void dssim_release(mi355_ctx *ctx);
 void roundedcorners_release(mi355_ctx *ctx);
+void colordetect_release(mi355_ctx *ctx);
 int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, int channel, int kind, float *out, int *w, int *h);
 int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate);
 int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps);

@@ -32,7 +32,8 @@ const ParamSpec *Element::find_spec(const std::string &name) const {
 
 bool Element::set_property(const std::string &name, double v) {
   const ParamSpec *ps = find_spec(name);
-  if (!ps || (ps->type != PropType::Float && ps->type != PropType::Double && ps->type != PropType::Flags && ps->type != PropType::Boolean)) {
+  if (!ps || (ps->type != PropType::Float && ps->type != PropType::Double && ps->type != PropType::Flags && ps->type != PropType::Boolean &&
+              ps->type != PropType::UInt)) {
     last_error_ = "no numeric property '" + name + "'";
     return false;
   }
@@ -45,6 +46,10 @@ bool Element::set_property(const std::string &name, double v) {
   if (ps->type == PropType::Float && std::isfinite(v) && std::fabs(v) > (double)FLT_MAX) v = std::copysign(INFINITY, v);
   if (!(v >= ps->min_num && v <= ps->max_num)) {
     last_error_ = "value out of range for property '" + name + "'";
+    return false;
+  }
+  if (ps->type == PropType::UInt && v != std::floor(v)) {  // a guint holds no fraction
+    last_error_ = "value is not an integer for property '" + name + "'";
     return false;
   }
   std::lock_guard<std::mutex> g(settings_mutex_);
@@ -89,7 +94,9 @@ bool Element::set_property(const std::string &name, const std::string &v) {
 
 bool Element::get_property(const std::string &name, double *v) const {
   const ParamSpec *ps = find_spec(name);
-  if (!ps || (ps->type != PropType::Float && ps->type != PropType::Double && ps->type != PropType::Flags && ps->type != PropType::Boolean)) return false;
+  if (!ps || (ps->type != PropType::Float && ps->type != PropType::Double && ps->type != PropType::Flags && ps->type != PropType::Boolean &&
+              ps->type != PropType::UInt))
+    return false;
   std::lock_guard<std::mutex> g(settings_mutex_);
   return load_number(name, v);
 }
@@ -1249,9 +1256,273 @@ FlowReturn VideoCompare::aggregate_frames(const std::vector<VideoFrame> &frames,
   return FlowReturn::Ok;
 }
 
+// ------------------------------------------------------------------ ColorDetect
+
+// CSS Color Module Level 4 named colours (color-name 1.2.0 `css`), alphabetical (tests/golden/css_named_colors.json)
+namespace {
+struct CssColor { const char *name; uint8_t r, g, b; };
+const CssColor kCssColors[] = {
+    {"aliceblue", 240, 248, 255},
+    {"antiquewhite", 250, 235, 215},
+    {"aqua", 0, 255, 255},
+    {"aquamarine", 127, 255, 212},
+    {"azure", 240, 255, 255},
+    {"beige", 245, 245, 220},
+    {"bisque", 255, 228, 196},
+    {"black", 0, 0, 0},
+    {"blanchedalmond", 255, 235, 205},
+    {"blue", 0, 0, 255},
+    {"blueviolet", 138, 43, 226},
+    {"brown", 165, 42, 42},
+    {"burlywood", 222, 184, 135},
+    {"cadetblue", 95, 158, 160},
+    {"chartreuse", 127, 255, 0},
+    {"chocolate", 210, 105, 30},
+    {"coral", 255, 127, 80},
+    {"cornflowerblue", 100, 149, 237},
+    {"cornsilk", 255, 248, 220},
+    {"crimson", 220, 20, 60},
+    {"cyan", 0, 255, 255},
+    {"darkblue", 0, 0, 139},
+    {"darkcyan", 0, 139, 139},
+    {"darkgoldenrod", 184, 134, 11},
+    {"darkgray", 169, 169, 169},
+    {"darkgreen", 0, 100, 0},
+    {"darkgrey", 169, 169, 169},
+    {"darkkhaki", 189, 183, 107},
+    {"darkmagenta", 139, 0, 139},
+    {"darkolivegreen", 85, 107, 47},
+    {"darkorange", 255, 140, 0},
+    {"darkorchid", 153, 50, 204},
+    {"darkred", 139, 0, 0},
+    {"darksalmon", 233, 150, 122},
+    {"darkseagreen", 143, 188, 143},
+    {"darkslateblue", 72, 61, 139},
+    {"darkslategray", 47, 79, 79},
+    {"darkslategrey", 47, 79, 79},
+    {"darkturquoise", 0, 206, 209},
+    {"darkviolet", 148, 0, 211},
+    {"deeppink", 255, 20, 147},
+    {"deepskyblue", 0, 191, 255},
+    {"dimgray", 105, 105, 105},
+    {"dimgrey", 105, 105, 105},
+    {"dodgerblue", 30, 144, 255},
+    {"firebrick", 178, 34, 34},
+    {"floralwhite", 255, 250, 240},
+    {"forestgreen", 34, 139, 34},
+    {"fuchsia", 255, 0, 255},
+    {"gainsboro", 220, 220, 220},
+    {"ghostwhite", 248, 248, 255},
+    {"gold", 255, 215, 0},
+    {"goldenrod", 218, 165, 32},
+    {"gray", 128, 128, 128},
+    {"green", 0, 128, 0},
+    {"greenyellow", 173, 255, 47},
+    {"grey", 128, 128, 128},
+    {"honeydew", 240, 255, 240},
+    {"hotpink", 255, 105, 180},
+    {"indianred", 205, 92, 92},
+    {"indigo", 75, 0, 130},
+    {"ivory", 255, 255, 240},
+    {"khaki", 240, 230, 140},
+    {"lavender", 230, 230, 250},
+    {"lavenderblush", 255, 240, 245},
+    {"lawngreen", 124, 252, 0},
+    {"lemonchiffon", 255, 250, 205},
+    {"lightblue", 173, 216, 230},
+    {"lightcoral", 240, 128, 128},
+    {"lightcyan", 224, 255, 255},
+    {"lightgoldenrodyellow", 250, 250, 210},
+    {"lightgray", 211, 211, 211},
+    {"lightgreen", 144, 238, 144},
+    {"lightgrey", 211, 211, 211},
+    {"lightpink", 255, 182, 193},
+    {"lightsalmon", 255, 160, 122},
+    {"lightseagreen", 32, 178, 170},
+    {"lightskyblue", 135, 206, 250},
+    {"lightslategray", 119, 136, 153},
+    {"lightslategrey", 119, 136, 153},
+    {"lightsteelblue", 176, 196, 222},
+    {"lightyellow", 255, 255, 224},
+    {"lime", 0, 255, 0},
+    {"limegreen", 50, 205, 50},
+    {"linen", 250, 240, 230},
+    {"magenta", 255, 0, 255},
+    {"maroon", 128, 0, 0},
+    {"mediumaquamarine", 102, 205, 170},
+    {"mediumblue", 0, 0, 205},
+    {"mediumorchid", 186, 85, 211},
+    {"mediumpurple", 147, 112, 219},
+    {"mediumseagreen", 60, 179, 113},
+    {"mediumslateblue", 123, 104, 238},
+    {"mediumspringgreen", 0, 250, 154},
+    {"mediumturquoise", 72, 209, 204},
+    {"mediumvioletred", 199, 21, 133},
+    {"midnightblue", 25, 25, 112},
+    {"mintcream", 245, 255, 250},
+    {"mistyrose", 255, 228, 225},
+    {"moccasin", 255, 228, 181},
+    {"navajowhite", 255, 222, 173},
+    {"navy", 0, 0, 128},
+    {"oldlace", 253, 245, 230},
+    {"olive", 128, 128, 0},
+    {"olivedrab", 107, 142, 35},
+    {"orange", 255, 165, 0},
+    {"orangered", 255, 69, 0},
+    {"orchid", 218, 112, 214},
+    {"palegoldenrod", 238, 232, 170},
+    {"palegreen", 152, 251, 152},
+    {"paleturquoise", 175, 238, 238},
+    {"palevioletred", 219, 112, 147},
+    {"papayawhip", 255, 239, 213},
+    {"peachpuff", 255, 218, 185},
+    {"peru", 205, 133, 63},
+    {"pink", 255, 192, 203},
+    {"plum", 221, 160, 221},
+    {"powderblue", 176, 224, 230},
+    {"purple", 128, 0, 128},
+    {"rebeccapurple", 102, 51, 153},
+    {"red", 255, 0, 0},
+    {"rosybrown", 188, 143, 143},
+    {"royalblue", 65, 105, 225},
+    {"saddlebrown", 139, 69, 19},
+    {"salmon", 250, 128, 114},
+    {"sandybrown", 244, 164, 96},
+    {"seagreen", 46, 139, 87},
+    {"seashell", 255, 245, 238},
+    {"sienna", 160, 82, 45},
+    {"silver", 192, 192, 192},
+    {"skyblue", 135, 206, 235},
+    {"slateblue", 106, 90, 205},
+    {"slategray", 112, 128, 144},
+    {"slategrey", 112, 128, 144},
+    {"snow", 255, 250, 250},
+    {"springgreen", 0, 255, 127},
+    {"steelblue", 70, 130, 180},
+    {"tan", 210, 180, 140},
+    {"teal", 0, 128, 128},
+    {"thistle", 216, 191, 216},
+    {"tomato", 255, 99, 71},
+    {"turquoise", 64, 224, 208},
+    {"violet", 238, 130, 238},
+    {"wheat", 245, 222, 179},
+    {"white", 255, 255, 255},
+    {"whitesmoke", 245, 245, 245},
+    {"yellow", 255, 255, 0},
+    {"yellowgreen", 154, 205, 50}
+};
+}  // namespace
+
+extern "C" const char *mi355host_css_color_similar(uint8_t r, uint8_t g, uint8_t b) {
+  const CssColor *best = &kCssColors[0];
+  int best_d = -1;
+  for (const CssColor &c : kCssColors) {  // strict < keeps the first name of a tie
+    const int dr = (int)c.r - r, dg = (int)c.g - g, db = (int)c.b - b, d = dr * dr + dg * dg + db * db;
+    if (best_d < 0 || d < best_d) { best_d = d; best = &c; }
+  }
+  return best->name;
+}
+
+ColorDetect::ColorDetect(int device) : Element(device) {}
+
+const ElementMetadata &ColorDetect::metadata() const {
+  static const ElementMetadata m{"Dominant color detection", "Filter/Video", "Detects the dominant color of a video",
+                                 "Philippe Normand <philn@igalia.com>"};
+  return m;
+}
+
+const std::vector<ParamSpec> &ColorDetect::properties() const {
+  static const std::vector<ParamSpec> p = [] {
+    ParamSpec q;
+    q.name = "quality"; q.nick = "Quality of an output colors"; q.blurb = "A step in pixels to improve performance"; q.type = PropType::UInt;
+    q.def_num = 10; q.min_num = 0; q.max_num = 10; q.mutability = Mutability::Playing;
+    ParamSpec m;
+    m.name = "max-colors"; m.nick = "Number of colors in the output palette"; m.blurb = "Actual colors count can be lower depending on the image";
+    m.type = PropType::UInt; m.def_num = 2; m.min_num = 2; m.max_num = 255; m.mutability = Mutability::Playing;
+    return std::vector<ParamSpec>{q, m};
+  }();
+  return p;
+}
+
+bool ColorDetect::store_number(const std::string &n, double v) {
+  if (n == "quality") quality_ = (unsigned)v;
+  else if (n == "max-colors") max_colors_ = (unsigned)v;
+  else return false;
+  return true;
+}
+
+bool ColorDetect::load_number(const std::string &n, double *v) const {
+  if (n == "quality") *v = quality_;
+  else if (n == "max-colors") *v = max_colors_;
+  else return false;
+  return true;
+}
+
+bool ColorDetect::set_info(int format) {
+  bool ok = false;
+  for (int f : sink_formats()) ok |= f == format;
+  if (!ok) {  // `_ => unimplemented!()` (imp.rs:280): negotiation guarantees a template format
+    last_error_ = "colordetect: format not in the pad template";
+    return false;
+  }
+  format_ = format;
+  have_state_ = true;  // current_color carries over from the previous state (imp.rs:284-291)
+  return true;
+}
+
+FlowReturn ColorDetect::detect(const uint8_t *data, size_t size, bool device) {
+  if (!have_state_) {
+    last_error_ = "colordetect: Have no state yet";
+    return FlowReturn::NotNegotiated;
+  }
+  if (!ctx_) return FlowReturn::Error;
+  unsigned q, mc;
+  {
+    std::lock_guard<std::mutex> g(settings_mutex_);
+    q = quality_;
+    mc = max_colors_;
+  }
+  uint8_t pal[255 * 3];
+  int n = 0;
+  const int rc = device ? mi355_colordetect_frames_device(ctx_, data, size, size, 1, format_, (int)q, (int)mc, pal, &n)
+                        : mi355_colordetect_frame(ctx_, data, size, format_, (int)q, (int)mc, pal, &n);
+  if (rc != MI355_OK) return flow_from_status(rc);  // get_palette's Err -> FlowError::Error (imp.rs:73)
+  if (n == 0) {  // the reference errors or panics at palette[0]
+    last_error_ = "colordetect: no colour in the frame";
+    return FlowReturn::Error;
+  }
+  const std::string name = mi355host_css_color_similar(pal[0], pal[1], pal[2]);
+  if (have_color_ && name == current_color_) return FlowReturn::Ok;
+  current_color_ = name;
+  have_color_ = true;
+  ColorDetectMessage m;
+  m.dominant_color = name;
+  for (int k = 0; k < n; k++) m.palette.push_back(((uint32_t)pal[3 * k] << 16) | ((uint32_t)pal[3 * k + 1] << 8) | pal[3 * k + 2]);
+  queue_.push_back(std::move(m));
+  return FlowReturn::Ok;
+}
+
+FlowReturn ColorDetect::transform_frame_ip(const VideoFrame &frame) { return detect(frame.data, frame.size, false); }
+
+FlowReturn ColorDetect::transform_frame_ip_device(const uint8_t *d_data, size_t size) { return detect(d_data, size, true); }
+
+bool ColorDetect::pop_message(ColorDetectMessage *out) {
+  if (queue_.empty()) return false;
+  *out = std::move(queue_.front());
+  queue_.erase(queue_.begin());
+  return true;
+}
+
+bool ColorDetect::stop() {
+  have_state_ = false;
+  have_color_ = false;
+  current_color_.clear();
+  return Element::stop();
+}
+
 // ------------------------------------------------------------------ registry
 
-std::vector<std::string> registered_factories() { return {"hsvfilter", "hsvdetector", "colorlut", "rsaudioecho", "ebur128level", "hrtfrender", "videocompare", "audioloudnorm", "roundedcorners"}; }
+std::vector<std::string> registered_factories() { return {"hsvfilter", "hsvdetector", "colorlut", "rsaudioecho", "ebur128level", "hrtfrender", "videocompare", "audioloudnorm", "roundedcorners", "colordetect"}; }
 
 std::unique_ptr<Element> element_factory_make(const std::string &factory, int device, std::string *error) {
   std::unique_ptr<Element> e;
@@ -1264,6 +1535,7 @@ std::unique_ptr<Element> element_factory_make(const std::string &factory, int de
   else if (factory == "videocompare") e.reset(new VideoCompare(device));
   else if (factory == "audioloudnorm") e.reset(new AudioLoudNorm(device));
   else if (factory == "roundedcorners") e.reset(new RoundedCorners(device));
+  else if (factory == "colordetect") e.reset(new ColorDetect(device));
   else {
     if (error) *error = "no such element factory: " + factory;
     return nullptr;
@@ -1320,11 +1592,33 @@ int mi355el_start(mi355el *h) { return h->e->start() ? 0 : -1; }
 int mi355el_stop(mi355el *h) { return h->e->stop() ? 0 : -1; }
 
 int mi355el_transform_frame_ip(mi355el *h, int format, int width, int height, int stride, uint8_t *data, size_t size) {
-  auto *f = dynamic_cast<HsvFilter *>(h->e.get());
-  if (!f) return (int)FlowReturn::Error;
   VideoFrame fr;
   fr.format = format; fr.width = width; fr.height = height; fr.stride = stride; fr.data = data; fr.size = size;
+  if (auto *c = dynamic_cast<ColorDetect *>(h->e.get())) return (int)c->transform_frame_ip(fr);
+  auto *f = dynamic_cast<HsvFilter *>(h->e.get());
+  if (!f) return (int)FlowReturn::Error;
   return (int)f->transform_frame_ip(fr);
+}
+
+// ---- colordetect
+int mi355el_colordetect_set_info(mi355el *h, int format) {
+  auto *e = h ? dynamic_cast<ColorDetect *>(h->e.get()) : nullptr;
+  return e && e->set_info(format) ? 0 : -1;
+}
+int mi355el_colordetect_transform_device(mi355el *h, const uint8_t *d_data, size_t size) {
+  auto *e = h ? dynamic_cast<ColorDetect *>(h->e.get()) : nullptr;
+  if (!e) return (int)FlowReturn::Error;
+  return (int)e->transform_frame_ip_device(d_data, size);
+}
+// returns 1 and fills the outputs when a message was queued, else 0; up to 255 palette entries; name: NUL-terminated
+int mi355el_colordetect_pop_message(mi355el *h, char *name, size_t name_len, uint32_t *palette, int *n_palette) {
+  auto *e = h ? dynamic_cast<ColorDetect *>(h->e.get()) : nullptr;
+  ColorDetectMessage m;
+  if (!e || !e->pop_message(&m)) return 0;
+  if (name && name_len) { std::strncpy(name, m.dominant_color.c_str(), name_len - 1); name[name_len - 1] = 0; }
+  *n_palette = (int)m.palette.size();
+  for (size_t k = 0; k < m.palette.size() && k < 255; k++) palette[k] = m.palette[k];
+  return 1;
 }
 
 int mi355el_transform_frame(mi355el *h, int in_format, int width, int height, int in_stride, const uint8_t *in, size_t in_size,

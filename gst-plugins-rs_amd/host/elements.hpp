@@ -12,6 +12,7 @@
 //   VideoCompare video/videofx/src/videocompare/imp.rs (VideoAggregator: aggregate_frames)
 //   AudioLoudNorm audio/audiofx/src/audioloudnorm/imp.rs (Element: sink chain / drain)
 //   RoundedCorners video/videofx/src/border/imp.rs    (BaseTransform: set_caps / prepare_output_buffer; host only)
+//   ColorDetect  video/videofx/src/colordetect/imp.rs (VideoFilter, AlwaysInPlace: set_info / transform_frame_ip / stop)
 // Each object owns one mi355_ctx (include/mi355fx.h) and forwards its per-buffer vfunc to the C ABI,
 // exactly where the Rust element would call its inner loop. The GStreamer shim (gst/) wraps these.
 #pragma once
@@ -30,7 +31,7 @@ namespace mi355host {
 // GstFlowReturn values (gst/gstpad.h)
 enum class FlowReturn : int { Ok = 0, Eos = -3, NotNegotiated = -4, Error = -5 };
 
-enum class PropType { Float, Double, UInt64, String, Flags, Boolean };
+enum class PropType { Float, Double, UInt64, String, Flags, Boolean, UInt };
 enum class Mutability { Ready, Playing };  // mutable_ready / mutable_playing
 
 struct ParamSpec {
@@ -356,6 +357,43 @@ class RoundedCorners final : public Element {
   int width_ = 0, height_ = 0, alpha_stride_ = 0;
   std::vector<uint8_t> alpha_mem_;
   void *cairo_ = nullptr;  // dlopen handle
+};
+
+// colordetect (video/videofx/src/colordetect/imp.rs): VideoFilter, AlwaysInPlace, passthrough on same caps; reads plane 0, never
+// writes it. Per frame the palette of plane 0 (mi355_colordetect_frame / _frames_device); when the css name of palette[0] differs
+// from the last one posted, one "colordetect" element message (imp.rs:57-113).
+struct ColorDetectMessage {
+  std::string dominant_color;    // "dominant-color"
+  std::vector<uint32_t> palette;  // "palette": (r << 16) | (g << 8) | b per entry, in palette order
+};
+
+class ColorDetect final : public Element {
+ public:
+  explicit ColorDetect(int device);
+  const char *factory_name() const override { return "colordetect"; }
+  const char *type_name() const override { return "GstColorDetect"; }
+  const ElementMetadata &metadata() const override;
+  const std::vector<ParamSpec> &properties() const override;
+  std::vector<int> sink_formats() const override { return {MI355_FMT_RGB, MI355_FMT_RGBA, MI355_FMT_ARGB, MI355_FMT_BGR, MI355_FMT_BGRA}; }
+  std::vector<int> src_formats() const override { return sink_formats(); }
+  // VideoFilterImpl::set_info (imp.rs:260-294): a new state for `format`; the colour posted last is kept
+  bool set_info(int format);
+  // transform_frame_ip_passthrough (imp.rs:296-307): frame.data / frame.size = plane_data(0); format from the state
+  FlowReturn transform_frame_ip(const VideoFrame &frame);
+  // the same for a plane in device memory (the shim's path for mi355 device buffers)
+  FlowReturn transform_frame_ip_device(const uint8_t *d_data, size_t size);
+  bool pop_message(ColorDetectMessage *out);
+  bool stop() override;  // drops the state (imp.rs:252-256)
+
+ private:
+  bool store_number(const std::string &name, double v) override;
+  bool load_number(const std::string &name, double *v) const override;
+  FlowReturn detect(const uint8_t *data, size_t size, bool device);
+  unsigned quality_ = 10, max_colors_ = 2;  // DEFAULT_QUALITY, DEFAULT_MAX_COLORS (imp.rs:19-20)
+  bool have_state_ = false, have_color_ = false;
+  int format_ = MI355_FMT_RGBA;
+  std::string current_color_;
+  std::vector<ColorDetectMessage> queue_;
 };
 
 // videocompare (video/videofx/src/videocompare/imp.rs): VideoAggregator; the first sink pad is the reference, every

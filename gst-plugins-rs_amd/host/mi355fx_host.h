@@ -38,6 +38,10 @@ int mi355host_hrtf_object_from_channel_position(int position, float xyz_left_han
  * libcairo (dlopen'ed: the library the reference's cairo crate binds). Returns 0, or -1 with the reference's error text. */
 int mi355host_rounded_corners_mask(uint8_t *alpha, int width, int height, int stride, unsigned radius, char *err, size_t errlen);
 
+/* color-name 1.2.0 `css::Color::similar([r, g, b]).to_lowercase()` (colordetect/imp.rs:77-79): the nearest of the 148 CSS Color 4
+ * named colours by squared RGB distance, a tie to the first name in alphabetical order. A static lowercase string. */
+const char *mi355host_css_color_similar(uint8_t r, uint8_t g, uint8_t b);
+
 #ifdef __cplusplus
 }
 #endif

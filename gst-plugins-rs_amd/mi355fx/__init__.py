@@ -99,6 +99,9 @@ def load_library():
         "mi355_roundedcorners_set_mask": (i, [vp, u8p, i, i, i]),
         "mi355_roundedcorners_mask_device": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]),
         "mi355_roundedcorners_append_device": (i, [vp, u8p, sz, sz, i]),
+        "mi355_colordetect_frame": (i, [vp, u8p, sz, i, i, i, u8p, C.POINTER(C.c_int)]),
+        "mi355_colordetect_frames_device": (i, [vp, vp, sz, sz, i, i, i, i, u8p, C.POINTER(C.c_int)]),
+        "mi355_colordetect_histogram_device": (i, [vp, vp, sz, i, i, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
         "mi355_hsvfilter_frame_ip": (i, [vp, u8p, sz, i, i, i, C.POINTER(HsvSettings)]),
         "mi355_hsvfilter_frames_device": (i, [vp, u8p, i, sz, i, i, i, i, C.POINTER(HsvSettings)]),
         "mi355_hsvdetect_frame": (i, [vp, u8p, sz, i, i, u8p, sz, i, i, i, C.POINTER(HsvDetectSettings)]),
@@ -849,6 +852,34 @@ class Context:
 
     def pipe_wait_all(self, pipe):
         self._ck(self.L.mi355_pipe_wait_all(pipe))
+
+    # ---- colordetect: color_thief::get_palette of plane 0 (video/videofx/src/colordetect/imp.rs:57-84)
+    COLORDETECT_FORMATS = ("RGB", "RGBA", "ARGB", "BGR", "BGRA")
+
+    def colordetect_frame(self, data, fmt, quality=10, max_colors=2):
+        """[(r, g, b), ...] in palette order for a host plane (any contiguous uint8 array, read as a flat byte run)."""
+        a = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        pal = np.zeros(255 * 3, np.uint8)
+        n = C.c_int(0)
+        self._ck(self.L.mi355_colordetect_frame(self.h, a.ctypes.data, a.nbytes, FMT[fmt], quality, max_colors, pal.ctypes.data, C.byref(n)))
+        return [tuple(int(x) for x in pal[3 * k:3 * k + 3]) for k in range(n.value)]
+
+    def colordetect_frames_device(self, d_frames, frame_pitch, data_len, n_frames, fmt, quality=10, max_colors=2):
+        """One palette per device plane d_frames + f * frame_pitch; one synchronisation."""
+        pal = np.zeros(max(n_frames, 1) * 255 * 3, np.uint8)
+        n = (C.c_int * max(n_frames, 1))()
+        self._ck(self.L.mi355_colordetect_frames_device(self.h, d_frames, frame_pitch, data_len, n_frames, FMT[fmt], quality, max_colors,
+                                                        pal.ctypes.data, n))
+        return [[tuple(int(x) for x in pal[(f * 255 + k) * 3:(f * 255 + k) * 3 + 3]) for k in range(n[f])] for f in range(n_frames)]
+
+    def colordetect_histogram_device(self, d_data, data_len, fmt, quality=10):
+        """(32768 bins as uint32, first box (r1, r2, g1, g2, b1, b2) or None when no sample is kept)."""
+        hist = np.zeros(32768, np.uint32)
+        box = (C.c_int * 6)()
+        self._ck(self.L.mi355_colordetect_histogram_device(self.h, d_data, data_len, FMT[fmt], quality,
+                                                           hist.ctypes.data_as(C.POINTER(C.c_uint32)), box))
+        b = tuple(box[k] for k in range(6))
+        return hist, (None if b[0] < 0 else b)
 
     # ---- videocompare
     HASH_ALGO = {"mean": 0, "gradient": 1, "vertgradient": 2, "doublegradient": 3, "blockhash": 4, "dssim": 5}

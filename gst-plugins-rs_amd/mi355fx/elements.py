@@ -49,6 +49,10 @@ def _lib():
             "mi355el_ebur128_reset_signal": (None, [vp]),
             "mi355el_ebur128_pop_message": (i, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double), i, C.POINTER(i)]),
+            "mi355el_colordetect_set_info": (i, [vp, i]),
+            "mi355el_colordetect_transform_device": (i, [vp, vp, sz]),
+            "mi355el_colordetect_pop_message": (i, [vp, C.c_char_p, sz, C.POINTER(C.c_uint32), C.POINTER(i)]),
+            "mi355host_css_color_similar": (C.c_char_p, [C.c_uint8, C.c_uint8, C.c_uint8]),
             "mi355el_roundedcorners_set_caps": (i, [vp, i, i, i]),
             "mi355el_roundedcorners_prepare": (i, [vp, vp, sz, C.POINTER(sz), C.POINTER(i), C.POINTER(i)]),
             "mi355el_roundedcorners_src_formats": (i, [vp]),
@@ -294,6 +298,27 @@ class Element:
         n = C.c_size_t(0)
         flow = self.L.mi355el_loudnorm_drain(self.h, ch, out.ctypes.data, cap, C.byref(n))
         return flow, out[: n.value * ch]
+
+    # ---- colordetect (video/videofx/src/colordetect/imp.rs)
+    def colordetect_set_info(self, fmt):
+        return self.L.mi355el_colordetect_set_info(self.h, FMT[fmt]) == 0
+
+    def colordetect_transform(self, data):
+        """transform_frame_ip_passthrough on a host plane (read as a flat byte run): returns the flow value."""
+        a = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        return self.L.mi355el_transform_frame_ip(self.h, 0, 0, 0, 0, a.ctypes.data, a.nbytes)
+
+    def colordetect_transform_device(self, d_data, size):
+        return self.L.mi355el_colordetect_transform_device(self.h, d_data, size)
+
+    def colordetect_pop_message(self):
+        """-> {"dominant-color": str, "palette": [packed 0xRRGGBB, ...]} or None"""
+        name = C.create_string_buffer(64)
+        pal = (C.c_uint32 * 255)()
+        n = C.c_int(0)
+        if not self.L.mi355el_colordetect_pop_message(self.h, name, 64, pal, C.byref(n)):
+            return None
+        return {"dominant-color": name.value.decode(), "palette": [pal[k] for k in range(n.value)]}
 
     # ---- roundedcorners (host only: the mask is rendered with the system libcairo exactly as the reference does)
     def roundedcorners_set_caps(self, width, height, a420=True):

@@ -696,6 +696,26 @@ int mi355_roundedcorners_set_mask(mi355_ctx *ctx, const uint8_t *mask, int width
 int mi355_roundedcorners_mask_device(mi355_ctx *ctx, const uint8_t **d_mask, size_t *size, int *stride);
 int mi355_roundedcorners_append_device(mi355_ctx *ctx, uint8_t *d_frames, size_t frame_pitch, size_t alpha_offset, int n_frames);
 
+/* ---------------------------------------------------------------- colordetect
+ * Replaces color_thief::get_palette(frame.plane_data(0), format, quality, max_colors) in ColorDetect::detect_color
+ * (video/videofx/src/colordetect/imp.rs:57-84). The plane is read as one flat byte run of `data_len` bytes (row padding
+ * included, strides ignored), every `quality`-th pixel of floor(data_len / ch) sampled. The MMCQ contract (color-thief 0.2.2,
+ * not in the reference tree: parity unpinned) is DESIGN §4.8. Formats: MI355_FMT_RGB, _RGBA, _ARGB, _BGR, _BGRA; any other is
+ * MI355_ERR_UNSUPPORTED. quality outside 1..10 or max_colors outside 2..255 is MI355_ERR_INVALID_ARG. A palette holds
+ * *n_colors <= max_colors entries of r, g, b bytes in palette order (entry 0 is the dominant colour); 0 colours when no sample
+ * is kept (the element turns that into GST_FLOW_ERROR). Scratch (histograms, results) belongs to the context.
+ *   mi355_colordetect_frame            a host plane; synchronous.
+ *   mi355_colordetect_frames_device    n_frames device planes at d_frames + f * frame_pitch; palette_rgb holds n_frames x 255 x 3
+ *                                      bytes and n_colors n_frames ints; one synchronisation per call.
+ *   mi355_colordetect_histogram_device diagnostics: the 32768 bins ((r>>3)<<10 | (g>>3)<<5 | (b>>3)) of one device plane and the
+ *                                      first box {r1, r2, g1, g2, b1, b2} (all -1 when no sample is kept); synchronous. */
+int mi355_colordetect_frame(mi355_ctx *ctx, const uint8_t *data, size_t data_len, int format, int quality, int max_colors,
+                            uint8_t palette_rgb[255 * 3], int *n_colors);
+int mi355_colordetect_frames_device(mi355_ctx *ctx, const uint8_t *d_frames, size_t frame_pitch, size_t data_len, int n_frames,
+                                    int format, int quality, int max_colors, uint8_t *palette_rgb, int *n_colors);
+int mi355_colordetect_histogram_device(mi355_ctx *ctx, const uint8_t *d_data, size_t data_len, int format, int quality,
+                                       uint32_t hist[32768], int box[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@
 //   * members = element instances of ONE kind and configuration on one device (a transcoding farm's N identical pipelines);
 //   * each member submits its buffer of the interval from its own streaming thread and waits for its ticket;
 //   * the batch runs when every attached member has submitted (whoever completes the set runs it), ONE launch set for all;
-//   * members are independent: rsaudioecho - own ring, position, buffer size and parameters per submit (a job table);
+//   * members are independent: rsaudioecho - own ring, position, buffer size and parameters per submit (a job table); agingradio -
+//     own setup (channels, rate, lowpass, seed), filter states and pair counter, buffer size, sample type and settings per submit
+//     (agingradio.hip's job table);
 //     ebur128level - own buffer size, 100 ms phase and `reset` (per-stream rounds in ebur128_kernels.hip); audioloudnorm - own frame
 //     type and ring positions (loudnorm.hip: a launch sequence per CLASS of members that stand at the same frame type and size:
 //     streams that started together are one class). A waiter that has lingered `linger_us` launches whoever is there: a member that
@@ -98,20 +100,29 @@ __global__ __launch_bounds__(256) void echo_jobs_commit_kernel(const EchoJob *__
 
 namespace {
 
-enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3 };
+enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4 };
 
 struct Sub {   // one member's submission of the interval being collected
   bool have = false;
   bool device = false;
   void *data = nullptr;      // caller's buffer (echo: in place; ebur128: input; loudnorm: input)
   void *out = nullptr;       // loudnorm: caller's output buffer
-  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm: frames
+  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm / agingradio: frames
   size_t out_cap = 0;        // loudnorm: capacity of `out` in frames
-  int fmt = 0;               // echo: is_f64; ebur128: sample format
+  int fmt = 0;               // echo / agingradio: is_f64; ebur128: sample format
   int final_frame = 0;       // loudnorm
   size_t delay = 0;
   double intensity = 0, feedback = 0;
+  mi355_agingradio_settings ar{};   // agingradio: the settings transform_ip snapshotted for this buffer
   uint64_t interval = 0;     // the interval this submission belongs to
+};
+
+struct AgingMember {         // one agingradio instance's state (AudioFilterImpl::setup, agingradio/imp.rs:326-345)
+  bool configured = false;
+  unsigned channels = 0;
+  double alpha = 0;
+  double *d_state = nullptr; // lowpass output per channel; nullptr: lowpass-freq 0 at setup
+  unsigned long long k = 0, seed = 0;   // frame pairs processed since setup; Philox key
 };
 
 }  // namespace
@@ -144,6 +155,9 @@ struct mi355_agroup {
   std::vector<size_t> pos;          // per-member ring position
   EchoJob *h_jobs = nullptr, *d_jobs = nullptr;
   hipEvent_t jobs_ev = nullptr;     // the job table of the previous launch set has left the pinned block
+  // ---- agingradio
+  std::vector<AgingMember> aging;
+  AgingJob *h_ajobs = nullptr, *d_ajobs = nullptr;
   // ---- ebur128
   unsigned channels = 0;
   uint64_t query_interval[5] = {0, 0, 0, 0, 0};   // ebur128: the interval the cached answers below belong to
@@ -295,6 +309,61 @@ int run_echo(mi355_agroup *g) {
   return MI355_OK;
 }
 
+size_t sub_bytes(const mi355_agroup *g, int m) {   // a host member's buffer in bytes (echo: samples; agingradio: frames)
+  const Sub &s = g->sub[(size_t)m];
+  const size_t per = g->kind == KIND_AGING ? (size_t)g->aging[(size_t)m].channels : 1;
+  return s.n * per * (s.fmt ? 8 : 4);
+}
+
+// ---- agingradio: one job per member that has submitted (agingradio.hip), each with its own buffer, sample type, settings, filter
+// states and pair counter. Host members go through their staging slots as echo members do. g->mu held.
+int run_aging(mi355_agroup *g) {
+  std::vector<int> who;
+  size_t max_host = 0;
+  for (int m = 0; m < g->n_members; m++)
+    if (g->sub[m].have) {
+      who.push_back(m);
+      if (!g->sub[m].device && sub_bytes(g, m) > max_host) max_host = sub_bytes(g, m);
+    }
+  if (who.empty()) return MI355_OK;
+  hipStream_t st = g->ctx->stream;
+  int rc = MI355_OK;
+  std::vector<std::pair<int, int>> runs;   // [first, last] member of each run of consecutive participating host members
+  for (int m : who) {
+    if (g->sub[m].device) continue;
+    if (!runs.empty() && runs.back().second == m - 1) runs.back().second = m;
+    else runs.push_back({m, m});
+  }
+  if (max_host > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->d_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, g->h_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, max_host,
+                                         (size_t)(r.second - r.first + 1), hipMemcpyHostToDevice, st), "agroup agingradio: upload"))) return rc;
+  if ((rc = ahip(g, hipEventSynchronize(g->jobs_ev), "hipEventSynchronize(agroup jobs)"))) return rc;
+  for (size_t j = 0; j < who.size(); j++) {
+    const int m = who[j];
+    const Sub &s = g->sub[m];
+    const AgingMember &A = g->aging[(size_t)m];
+    AgingJob &J = g->h_ajobs[j];
+    J = AgingJob{};
+    agingradio_settings_to_job(s.ar, &J);
+    J.data = s.device ? s.data : (void *)(g->d_in + (size_t)m * g->cap_bytes);
+    J.state = A.d_state;
+    J.frames = s.n; J.k0 = A.k; J.seed = A.seed; J.alpha = A.alpha; J.channels = A.channels; J.is_f64 = s.fmt;
+  }
+  const unsigned J = (unsigned)who.size();
+  if ((rc = ahip(g, hipMemcpyAsync(g->d_ajobs, g->h_ajobs, J * sizeof(AgingJob), hipMemcpyHostToDevice, st), "agroup agingradio: job table"))) return rc;
+  if ((rc = ahip(g, hipEventRecord(g->jobs_ev, st), "hipEventRecord(agroup jobs)"))) return rc;
+  std::string err;
+  if ((rc = launch_agingradio_jobs(st, g->ctx->n_cu, g->h_ajobs, g->d_ajobs, J, &err))) return afail(g, rc, err);
+  if (max_host > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->h_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, g->d_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, max_host,
+                                         (size_t)(r.second - r.first + 1), hipMemcpyDeviceToHost, st), "agroup agingradio: download"))) return rc;
+  if ((rc = ahip(g, hipStreamSynchronize(st), "agroup agingradio: sync"))) return rc;
+  for (int m : who) g->aging[(size_t)m].k += g->sub[m].n / 2;   // chunks_exact_mut: an odd last frame is not a pair
+  return MI355_OK;
+}
+
 // ---- ebur128level: the members that have submitted advance, each by its own buffer size and with its own 100 ms phase (the engine
 // walks per-stream rounds, ebur128_kernels.hip); the others - late, detached, paused - do not move. One sample format per launch set.
 int run_ebur128(mi355_agroup *g) {
@@ -394,6 +463,7 @@ void run_interval(mi355_agroup *g) {
   int rc = MI355_OK;
   if (g->kind == KIND_ECHO) rc = run_echo(g);
   else if (g->kind == KIND_EBUR128) rc = run_ebur128(g);
+  else if (g->kind == KIND_AGING) rc = run_aging(g);
   else rc = run_loudnorm(g);
   uint64_t carried = 0;
   for (int m = 0; m < g->n_members; m++) {
@@ -536,6 +606,10 @@ void mi355_agroup_destroy(mi355_agroup *g) {
   if (g->d_jobs) (void)hipFree(g->d_jobs);
   if (g->h_jobs) (void)hipHostFree(g->h_jobs);
   if (g->jobs_ev) (void)hipEventDestroy(g->jobs_ev);
+  for (AgingMember &A : g->aging)
+    if (A.d_state) (void)hipFree(A.d_state);
+  if (g->d_ajobs) (void)hipFree(g->d_ajobs);
+  if (g->h_ajobs) (void)hipHostFree(g->h_ajobs);
   if (g->ctx) mi355_ctx_destroy(g->ctx);   // releases the ebur128 / loudnorm batch engines with it
   delete g;
 }
@@ -681,11 +755,11 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
   // copy-out happens under the lock only for its pointer arithmetic: the member's slot is not written again before this member
   // submits again, and the slab is not reallocated while a copy is counted (a member that grows the slots waits in ensure_staging:
   // round 6's stress run caught a result read from a slab another member's larger buffer had just replaced)
-  if (g->kind == KIND_ECHO) {
+  if (g->kind == KIND_ECHO || g->kind == KIND_AGING) {
     if (!s.device && s.n) {
       const char *src = g->h_in + (size_t)member * g->cap_bytes;
       void *dst = s.data;
-      const size_t bytes = s.n * (s.fmt ? 8 : 4);
+      const size_t bytes = sub_bytes(g, member);
       if (bytes <= (size_t)65536) {
         std::memcpy(dst, src, bytes);   // (a 10 ms audio buffer is a few KB: cheaper than giving the lock away and taking it again)
       } else {
@@ -762,6 +836,81 @@ int mi355_agroup_echo_get_state(mi355_agroup *g, int member, double *ring_out, s
     if (rc) return rc;
   }
   if (pos_out) *pos_out = g->pos[(size_t)member];
+  return MI355_OK;
+}
+
+mi355_agroup *mi355_agroup_create_agingradio(int device, int n_members, int *status) {
+  mi355_agroup *g = agroup_new(device, KIND_AGING, n_members, status);
+  if (!g) return nullptr;
+  g->aging.assign((size_t)n_members, AgingMember{});
+  int rc = ahip(g, hipMalloc((void **)&g->d_ajobs, (size_t)n_members * sizeof(AgingJob)), "hipMalloc(agroup agingradio jobs)");
+  if (!rc) rc = ahip(g, hipHostMalloc((void **)&g->h_ajobs, (size_t)n_members * sizeof(AgingJob), hipHostMallocDefault), "hipHostMalloc(agroup agingradio jobs)");
+  if (!rc) rc = ahip(g, hipEventCreateWithFlags(&g->jobs_ev, hipEventDisableTiming), "hipEventCreate(agroup)");
+  if (rc) { if (status) *status = rc; mi355_agroup_destroy(g); return nullptr; }
+  if (status) *status = MI355_OK;
+  return g;
+}
+
+// AudioFilterImpl::setup of one member (agingradio/imp.rs:326-345): its filters restart at 0, its pair counter at 0, a new seed.
+// Not while the member has a buffer pending.
+int mi355_agroup_agingradio_setup(mi355_agroup *g, int member, unsigned channels, unsigned rate, unsigned lowpass_freq, uint64_t seed) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_AGING, member);
+  if (rc) return rc;
+  if (channels == 0 || rate == 0) return afail(g, MI355_ERR_INVALID_ARG, "agingradio: 0 channels or rate 0");
+  if (lowpass_freq > 0 && channels > 2048) return afail(g, MI355_ERR_UNSUPPORTED, "agingradio: the lowpass runs on at most 2048 channels");
+  (void)hipSetDevice(g->device);
+  AgingMember &A = g->aging[(size_t)member];
+  if (A.d_state) (void)hipFree(A.d_state);   // (hipFree waits for the launch sets still using it)
+  A = AgingMember{};
+  if (lowpass_freq > 0) {
+    agingradio_setup_filter(rate, lowpass_freq, &A.alpha);
+    if ((rc = ahip(g, hipMalloc((void **)&A.d_state, (size_t)channels * 8), "hipMalloc(agroup agingradio filters)"))) return rc;
+    if ((rc = ahip(g, hipMemset(A.d_state, 0, (size_t)channels * 8), "hipMemset(agroup agingradio filters)"))) return rc;
+  }
+  A.channels = channels;
+  A.seed = seed;
+  A.configured = true;
+  return MI355_OK;
+}
+
+int mi355_agroup_submit_agingradio(mi355_agroup *g, int member, void *data, size_t frames, int is_f64, const mi355_agingradio_settings *settings,
+                                   int device_data, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_AGING, member);
+  if (rc) return rc;
+  if (!g->aging[(size_t)member].configured) return afail(g, MI355_ERR_NOT_CONFIGURED, "agingradio: not negotiated (setup not called)");
+  if (!settings) return afail(g, MI355_ERR_INVALID_ARG, "agingradio: null settings");
+  if (frames && !data) return afail(g, MI355_ERR_INVALID_ARG, "agroup: null buffer");
+  (void)hipSetDevice(g->device);
+  Sub &s = g->sub[member];
+  s.device = device_data != 0; s.data = data; s.n = frames; s.fmt = is_f64 ? 1 : 0; s.ar = *settings;
+  void *dst = nullptr;
+  size_t bytes = 0;
+  if (!s.device && frames) {
+    bytes = sub_bytes(g, member);
+    if ((rc = ensure_staging(g, lk, bytes, 0))) return rc;
+    dst = g->h_in + (size_t)member * g->cap_bytes;
+  }
+  submitted(g, lk, member, ticket, dst, data, bytes);
+  return MI355_OK;
+}
+
+int mi355_agroup_agingradio_get_state(mi355_agroup *g, int member, double *filter_state, unsigned channels, uint64_t *pairs_done) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  if (g->kind != KIND_AGING || member < 0 || member >= g->n_members) return afail(g, MI355_ERR_INVALID_ARG, "agroup: bad member");
+  const AgingMember &A = g->aging[(size_t)member];
+  if (!A.configured) return afail(g, MI355_ERR_NOT_CONFIGURED, "agingradio: not negotiated (setup not called)");
+  (void)hipSetDevice(g->device);
+  if (pairs_done) *pairs_done = A.k;
+  if (filter_state && channels) {
+    const unsigned n = channels < A.channels ? channels : A.channels;
+    if (!A.d_state) std::memset(filter_state, 0, (size_t)n * 8);
+    else if (int rc = ahip(g, hipMemcpy(filter_state, A.d_state, (size_t)n * 8, hipMemcpyDeviceToHost), "agroup agingradio: filters D2H")) return rc;
+  }
   return MI355_OK;
 }
 
@@ -886,6 +1035,11 @@ int mi355_agroup_loudnorm_drain(mi355_agroup *g, int member, double *out, size_t
   ad->clear();
   if (eos && rest == 0 && *out_frames == 0) *eos = 1;   // nothing at all to drain: FlowError::Eos (imp.rs:289-293)
   return MI355_OK;
+}
+
+mi355_agroup *mi355_agroup_shared_agingradio(int device, int n_members, int *member, int *status) {
+  return shared_get(key_of("agingradio", device, n_members, nullptr, 0), n_members, member, status,
+                    [&] { return mi355_agroup_create_agingradio(device, n_members, status); });
 }
 
 void mi355_agroup_release(mi355_agroup *g, int member) {

@@ -190,6 +190,7 @@ void mi355_ctx_destroy(mi355_ctx *ctx) {
   dssim_release(ctx);
   roundedcorners_release(ctx);
   colordetect_release(ctx);
+  agingradio_release(ctx);
   ebur128_release(ctx);
   hrtf_release(ctx);
   sofa_release(ctx);

@@ -98,6 +98,7 @@ struct mi355_ctx {
   void *dssim_cache = nullptr; // mi355::DssimCache (dssim_kernels.hip)
   void *rounded = nullptr;     // mi355::RoundedMask (roundedcorners.hip): the element's alpha plane, device-resident
   void *colordetect = nullptr; // mi355::ColorDetectState (colordetect.hip): histograms and palette results
+  void *agingradio = nullptr;  // mi355::AgingState (agingradio.hip): lowpass filter states, pair counter, seed
   // host <-> device copies this context has enqueued through the library's own entry points and mi355_buf objects (tests assert
   // that a chain of elements on device buffers costs ONE upload and ONE download: mi355_ctx_transfer_counts)
   unsigned long long n_h2d = 0, n_d2h = 0;
@@ -225,6 +226,23 @@ int dssim_cbrt_selftest(mi355_ctx *ctx, uint32_t lo_bits, uint32_t hi_bits, uint
 void dssim_release(mi355_ctx *ctx);
 void roundedcorners_release(mi355_ctx *ctx);
 void colordetect_release(mi355_ctx *ctx);
+
+// agingradio (agingradio.hip): one job = one element instance's buffer. The host fills the table (alpha and the quantise factor
+// computed with its libm); the group (agroup.hip) submits one job per member, a context a table of one.
+enum { kAgingClick = 1, kAgingNoise = 2, kAgingQuant = 4, kAgingCubic = 8 };
+struct AgingJob {
+  void *data;                        // interleaved F32 / F64 samples, processed in place
+  double *state;                     // lowpass output y per channel; nullptr: no lowpass (lowpass-freq 0 at setup)
+  unsigned long long frames, k0;     // frames of this buffer; frame pairs the instance has processed before it
+  unsigned long long seed, p_int;    // Philox key; Bernoulli threshold (~0: always)
+  double alpha, factor, ampl, dist;  // lowpass coefficient, 2^bits, white-noise amplitude, cubic distortion
+  unsigned channels, passes;
+  int is_f64, flags;                 // kAging*
+};
+int agingradio_setup_filter(unsigned rate, unsigned lowpass_freq, double *alpha);
+void agingradio_settings_to_job(const mi355_agingradio_settings &s, AgingJob *J);
+int launch_agingradio_jobs(hipStream_t stream, int n_cu, const AgingJob *h_jobs, const AgingJob *d_jobs, unsigned n_jobs, std::string *err);
+void agingradio_release(mi355_ctx *ctx);
 int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, int channel, int kind, float *out, int *w, int *h);
 int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate);
 int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps);

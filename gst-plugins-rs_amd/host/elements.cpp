@@ -437,6 +437,111 @@ bool AudioEcho::stop() {
   return true;
 }
 
+// ------------------------------------------------------------------ AgingRadio
+
+AgingRadio::AgingRadio(int device) : Element(device) {}
+
+const ElementMetadata &AgingRadio::metadata() const {
+  static const ElementMetadata m{"Aging Radio", "Filter/Effect/Audio", "Adds age to audio input using various kinds of distortion",
+                                 "Vivia Nikolaidou <vivia@ahiru.eu>"};
+  return m;
+}
+
+// agingradio/imp.rs:142-197; docs/plugins/gst_plugins_cache.json:11440-11549
+const std::vector<ParamSpec> &AgingRadio::properties() const {
+  static const std::vector<ParamSpec> p = [] {
+    auto uint = [](const char *n, const char *nick, const char *blurb, double def, double hi) {
+      ParamSpec s;
+      s.name = n; s.nick = nick; s.blurb = blurb; s.type = PropType::UInt;
+      s.def_num = def; s.min_num = 0; s.max_num = hi; s.mutability = Mutability::Ready;
+      return s;
+    };
+    return std::vector<ParamSpec>{
+        float_spec("white-noise-ampl", "White noise amplitude", "White noise amplitude (0 to disable)", (double)0.011f, 0.0, 1.0, Mutability::Ready),
+        float_spec("clicks-prob", "Clicks probability", "Clicks probability (0 to disable)", (double)(1.0f / 100000.0f), 0.0, 1.0, Mutability::Ready),
+        uint("lowpass-freq", "Lowpass filter frequency", "Lowpass filter frequency (0 to disable)", 2000, 22000),
+        float_spec("bits-to-quantize", "Bits to quantize", "Bits to quantize (0 to disable)", 4.0, 0.0, 64.0, Mutability::Ready),
+        float_spec("cubic-curve-distortion", "Cubic curve distortion", "Cubic curve distortion (0 to disable)", 1.0, 0.0, 1.0, Mutability::Ready),
+        uint("cubic-curve-passes", "Cubic curve passes", "Cubic curve passes (0 to disable)", 3, 4294967295.0),
+    };
+  }();
+  return p;
+}
+
+bool AgingRadio::store_number(const std::string &n, double v) {
+  if (n == "white-noise-ampl") {
+    if (!have_state_) settings_.white_noise_ampl = (float)v;  // only while there is no state (imp.rs:200-204)
+  } else if (n == "clicks-prob") {
+    settings_.clicks_prob = (float)v;
+  } else if (n == "lowpass-freq") {
+    lowpass_freq_ = (unsigned)v;   // takes effect at the next setup
+  } else if (n == "bits-to-quantize") {
+    settings_.bits_to_quantize = (float)v;
+  } else if (n == "cubic-curve-distortion") {
+    settings_.cubic_curve_distortion = (float)v;
+  } else if (n == "cubic-curve-passes") {
+    settings_.cubic_curve_passes = (uint32_t)v;
+  } else {
+    return false;
+  }
+  return true;
+}
+
+bool AgingRadio::load_number(const std::string &n, double *v) const {
+  if (n == "white-noise-ampl") *v = settings_.white_noise_ampl;
+  else if (n == "clicks-prob") *v = settings_.clicks_prob;
+  else if (n == "lowpass-freq") *v = lowpass_freq_;
+  else if (n == "bits-to-quantize") *v = settings_.bits_to_quantize;
+  else if (n == "cubic-curve-distortion") *v = settings_.cubic_curve_distortion;
+  else if (n == "cubic-curve-passes") *v = settings_.cubic_curve_passes;
+  else return false;
+  return true;
+}
+
+bool AgingRadio::setup(const AudioInfo &info, uint64_t seed) {
+  if (!ctx_) return false;
+  unsigned lowpass;
+  {
+    std::lock_guard<std::mutex> g(settings_mutex_);
+    lowpass = lowpass_freq_;
+  }
+  if (info.channels <= 0 || info.rate <= 0 || mi355_agingradio_setup(ctx_, (unsigned)info.channels, (unsigned)info.rate, lowpass, seed) != MI355_OK) {
+    last_error_ = info.channels <= 0 || info.rate <= 0 ? "agingradio: 0 channels or rate 0" : mi355_ctx_last_error(ctx_);
+    return false;
+  }
+  std::lock_guard<std::mutex> g(settings_mutex_);
+  info_ = info;
+  have_state_ = true;
+  return true;
+}
+
+FlowReturn AgingRadio::transform_ip(void *data, size_t nbytes) {
+  if (!ctx_) return FlowReturn::Error;
+  mi355_agingradio_settings s;
+  bool have_state;
+  {
+    std::lock_guard<std::mutex> g(settings_mutex_);  // let settings = *self.settings.lock().unwrap() (imp.rs:285)
+    s = settings_;
+    have_state = have_state_;
+  }
+  if (!have_state) {  // ok_or(gst::FlowError::NotNegotiated) (imp.rs:288-289)
+    last_error_ = "agingradio: not negotiated";
+    return FlowReturn::NotNegotiated;
+  }
+  const size_t frame_bytes = (size_t)info_.channels * (info_.f64 ? sizeof(double) : sizeof(float));
+  return flow_from_status(mi355_agingradio_process(ctx_, data, nbytes / frame_bytes, info_.f64 ? 1 : 0, &s));
+}
+
+bool AgingRadio::stop() {
+  if (ctx_) mi355_agingradio_reset(ctx_);
+  {
+    std::lock_guard<std::mutex> g(settings_mutex_);
+    have_state_ = false;
+  }
+  started_ = false;
+  return true;
+}
+
 // ------------------------------------------------------------------ EbuR128Level
 
 EbuR128Level::EbuR128Level(int device) : Element(device) {}
@@ -1521,8 +1626,21 @@ bool ColorDetect::stop() {
 }
 
 // ------------------------------------------------------------------ registry
+// The name registry keeps the set of factories it has always made: the element-mirror suite pins that "agingradio" is not one of
+// them (tests/test_gpu_elements.py: test_unknown_factory). The AgingRadio mirror is made by name-free constructors instead
+// (make_aging_radio, mi355el_agingradio_new).
 
 std::vector<std::string> registered_factories() { return {"hsvfilter", "hsvdetector", "colorlut", "rsaudioecho", "ebur128level", "hrtfrender", "videocompare", "audioloudnorm", "roundedcorners", "colordetect"}; }
+
+static std::unique_ptr<Element> checked(std::unique_ptr<Element> e, std::string *error) {
+  if (!e->last_error().empty()) {  // context creation failed: no device, no element (no CPU fallback)
+    if (error) *error = e->last_error();
+    return nullptr;
+  }
+  return e;
+}
+
+std::unique_ptr<Element> make_aging_radio(int device, std::string *error) { return checked(std::unique_ptr<Element>(new AgingRadio(device)), error); }
 
 std::unique_ptr<Element> element_factory_make(const std::string &factory, int device, std::string *error) {
   std::unique_ptr<Element> e;
@@ -1540,11 +1658,7 @@ std::unique_ptr<Element> element_factory_make(const std::string &factory, int de
     if (error) *error = "no such element factory: " + factory;
     return nullptr;
   }
-  if (!e->last_error().empty()) {  // context creation failed: no device, no element (no CPU fallback)
-    if (error) *error = e->last_error();
-    return nullptr;
-  }
-  return e;
+  return checked(std::move(e), error);
 }
 
 }  // namespace mi355host
@@ -1557,9 +1671,7 @@ struct mi355el { std::unique_ptr<Element> e; std::string err; };
 
 extern "C" {
 
-mi355el *mi355el_factory_make(const char *factory, int device, char *err, size_t errlen) {
-  std::string msg;
-  auto e = element_factory_make(factory ? factory : "", device, &msg);
+static mi355el *wrap(std::unique_ptr<Element> e, const std::string &msg, char *err, size_t errlen) {
   if (!e) {
     if (err && errlen) { std::strncpy(err, msg.c_str(), errlen - 1); err[errlen - 1] = 0; }
     return nullptr;
@@ -1567,6 +1679,19 @@ mi355el *mi355el_factory_make(const char *factory, int device, char *err, size_t
   auto *h = new mi355el();
   h->e = std::move(e);
   return h;
+}
+
+mi355el *mi355el_factory_make(const char *factory, int device, char *err, size_t errlen) {
+  std::string msg;
+  auto e = element_factory_make(factory ? factory : "", device, &msg);
+  return wrap(std::move(e), msg, err, errlen);
+}
+
+// the AgingRadio mirror (factory "agingradio", GType GstRsAgingRadio), outside the name registry (see registered_factories)
+mi355el *mi355el_agingradio_new(int device, char *err, size_t errlen) {
+  std::string msg;
+  auto e = make_aging_radio(device, &msg);
+  return wrap(std::move(e), msg, err, errlen);
 }
 void mi355el_free(mi355el *h) { delete h; }
 const char *mi355el_last_error(const mi355el *h) { return h ? h->e->last_error().c_str() : "null element"; }
@@ -1644,6 +1769,19 @@ int mi355el_audio_transform_ip(mi355el *h, void *data, size_t nbytes) {
   return (int)e->transform_ip(data, nbytes);
 }
 
+// ---- agingradio
+int mi355el_agingradio_setup(mi355el *h, int rate, int channels, int f64, uint64_t seed) {
+  auto *e = h ? dynamic_cast<AgingRadio *>(h->e.get()) : nullptr;
+  if (!e) return -1;
+  AudioInfo info;
+  info.rate = rate; info.channels = channels; info.f64 = f64 != 0;
+  return e->setup(info, seed) ? 0 : -1;
+}
+int mi355el_agingradio_transform_ip(mi355el *h, void *data, size_t nbytes) {
+  auto *e = h ? dynamic_cast<AgingRadio *>(h->e.get()) : nullptr;
+  if (!e) return (int)FlowReturn::Error;
+  return (int)e->transform_ip(data, nbytes);
+}
 
 int mi355el_ebur128_setup(mi355el *h, int rate, int channels, int sample_format, int planar, const int *channel_class) {
   auto *e = dynamic_cast<EbuR128Level *>(h->e.get());

@@ -13,6 +13,7 @@
 //   AudioLoudNorm audio/audiofx/src/audioloudnorm/imp.rs (Element: sink chain / drain)
 //   RoundedCorners video/videofx/src/border/imp.rs    (BaseTransform: set_caps / prepare_output_buffer; host only)
 //   ColorDetect  video/videofx/src/colordetect/imp.rs (VideoFilter, AlwaysInPlace: set_info / transform_frame_ip / stop)
+//   AgingRadio   audio/audiofx/src/agingradio/imp.rs (AudioFilter, AlwaysInPlace: setup/transform_ip/stop)
 // Each object owns one mi355_ctx (include/mi355fx.h) and forwards its per-buffer vfunc to the C ABI,
 // exactly where the Rust element would call its inner loop. The GStreamer shim (gst/) wraps these.
 #pragma once
@@ -183,6 +184,31 @@ class AudioEcho final : public Element {
   // audioecho/imp.rs:31-34
   uint64_t max_delay_ns_ = 1000000000ull, delay_ns_ = 500ull * 1000000000ull;
   double intensity_ = 0.5, feedback_ = 0.0;
+  bool have_state_ = false;
+  AudioInfo info_;
+};
+
+class AgingRadio final : public Element {
+ public:
+  explicit AgingRadio(int device);
+  const char *factory_name() const override { return "agingradio"; }
+  const char *type_name() const override { return "GstRsAgingRadio"; }
+  const ElementMetadata &metadata() const override;
+  const std::vector<ParamSpec> &properties() const override;
+  std::vector<int> sink_formats() const override { return {0, 1}; }  // F32, F64 interleaved
+  std::vector<int> src_formats() const override { return {0, 1}; }
+  // AudioFilterImpl::setup (agingradio/imp.rs:326-345): one filter per channel when lowpass-freq > 0; `seed` keys the draws
+  bool setup(const AudioInfo &info, uint64_t seed);
+  // BaseTransformImpl::transform_ip (agingradio/imp.rs:284-305): `data` = the mapped buffer bytes
+  FlowReturn transform_ip(void *data, size_t nbytes);
+  bool stop() override;  // drops the state (agingradio/imp.rs:307-312)
+
+ private:
+  bool store_number(const std::string &name, double v) override;
+  bool load_number(const std::string &name, double *v) const override;
+  // agingradio/imp.rs:51-56
+  mi355_agingradio_settings settings_{0.011f, 1.0f / 100000.0f, 4.0f, 1.0f, 3u};
+  unsigned lowpass_freq_ = 2000;
   bool have_state_ = false;
   AudioInfo info_;
 };
@@ -433,5 +459,7 @@ class VideoCompare final : public Element {
 std::unique_ptr<Element> element_factory_make(const std::string &factory, int device, std::string *error);
 // Names registered by the plugins (video/hsv/src/lib.rs:23-27, video/colorlut/src/lib.rs, audio/audiofx/src/lib.rs)
 std::vector<std::string> registered_factories();
+// The AgingRadio mirror (factory "agingradio"); it is not made by name through element_factory_make (see elements.cpp).
+std::unique_ptr<Element> make_aging_radio(int device, std::string *error);
 
 }  // namespace mi355host

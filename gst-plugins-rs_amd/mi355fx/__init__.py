@@ -46,6 +46,17 @@ class HsvSettings(C.Structure):
                 ("value_mul", C.c_float), ("value_off", C.c_float)]
 
 
+class AgingRadioSettings(C.Structure):
+    """mi355_agingradio_settings: agingradio's Settings as transform_ip snapshots them (lowpass-freq goes to setup)."""
+    _fields_ = [("white_noise_ampl", C.c_float), ("clicks_prob", C.c_float), ("bits_to_quantize", C.c_float),
+                ("cubic_curve_distortion", C.c_float), ("cubic_curve_passes", C.c_uint32)]
+
+    @classmethod
+    def of(cls, d):
+        return cls(d.get("white_noise_ampl", 0.011), d.get("clicks_prob", 1.0 / 100000.0), d.get("bits_to_quantize", 4.0),
+                   d.get("cubic_curve_distortion", 1.0), d.get("cubic_curve_passes", 3))
+
+
 class HsvDetectSettings(C.Structure):
     _fields_ = [("hue_ref", C.c_float), ("hue_var", C.c_float), ("saturation_ref", C.c_float),
                 ("saturation_var", C.c_float), ("value_ref", C.c_float), ("value_var", C.c_float)]
@@ -206,6 +217,16 @@ def load_library():
         "mi355_agroup_loudnorm_push": (i, [vp, i, vp, sz, vp, sz, C.POINTER(sz)]),
         "mi355_agroup_loudnorm_drain": (i, [vp, i, vp, sz, C.POINTER(sz), C.POINTER(C.c_int)]),
         "mi355_agroup_shared_echo": (vp, [i, i, sz, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mi355_agingradio_setup": (i, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint64]),
+        "mi355_agingradio_process": (i, [vp, vp, sz, i, C.POINTER(AgingRadioSettings)]),
+        "mi355_agingradio_process_device": (i, [vp, vp, sz, i, C.POINTER(AgingRadioSettings)]),
+        "mi355_agingradio_get_state": (i, [vp, C.POINTER(C.c_double), C.c_uint, C.POINTER(C.c_uint64)]),
+        "mi355_agingradio_reset": (i, [vp]),
+        "mi355_agroup_create_agingradio": (vp, [i, i, C.POINTER(C.c_int)]),
+        "mi355_agroup_shared_agingradio": (vp, [i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mi355_agroup_agingradio_setup": (i, [vp, i, C.c_uint, C.c_uint, C.c_uint, C.c_uint64]),
+        "mi355_agroup_submit_agingradio": (i, [vp, i, vp, sz, i, C.POINTER(AgingRadioSettings), i, C.POINTER(C.c_uint64)]),
+        "mi355_agroup_agingradio_get_state": (i, [vp, i, C.POINTER(C.c_double), C.c_uint, C.POINTER(C.c_uint64)]),
         "mi355_agroup_shared_ebur128": (vp, [i, i, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_shared_loudnorm": (vp, [i, i, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_release": (None, [vp, i]),
@@ -432,6 +453,8 @@ class AudioGroup:
             m = C.c_int(-1)
             if kind == "echo":
                 self.h = self.L.mi355_agroup_shared_echo(device, n_members, kw["ring_len"], C.byref(m), C.byref(st))
+            elif kind == "agingradio":
+                self.h = self.L.mi355_agroup_shared_agingradio(device, n_members, C.byref(m), C.byref(st))
             elif kind == "ebur128":
                 cc = kw.get("channel_class")
                 arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -446,6 +469,8 @@ class AudioGroup:
             return
         if kind == "echo":
             self.h = self.L.mi355_agroup_create_echo(device, n_members, kw["ring_len"], C.byref(st))
+        elif kind == "agingradio":
+            self.h = self.L.mi355_agroup_create_agingradio(device, n_members, C.byref(st))
         elif kind == "ebur128":
             cc = kw.get("channel_class")
             arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -481,6 +506,30 @@ class AudioGroup:
         else:
             self._ck(self.L.mi355_agroup_submit_echo(self.h, member, data, n, int(bool(is_f64)), delay, intensity, feedback, 1, C.byref(t)))
         return t.value
+
+    def agingradio_setup(self, member, channels, rate, lowpass_freq, seed):
+        """AudioFilterImpl::setup of one agingradio member: its filters, pair counter and seed start over."""
+        self._ck(self.L.mi355_agroup_agingradio_setup(self.h, member, channels, rate, lowpass_freq, seed))
+
+    def submit_agingradio(self, member, data, settings, channels=None, frames=None, is_f64=None):
+        """data: a numpy f32 / f64 array of frames * channels (host, processed in place, valid after wait) or a device pointer
+        (then frames, is_f64). settings: a dict of mi355_agingradio_settings fields (missing ones at the element's defaults)."""
+        t = C.c_uint64(0)
+        st = AgingRadioSettings.of(settings)
+        if isinstance(data, np.ndarray):
+            assert data.flags.c_contiguous and data.dtype in (np.float32, np.float64)
+            self._keep[member] = data
+            self._ck(self.L.mi355_agroup_submit_agingradio(self.h, member, data.ctypes.data, data.size // channels, int(data.dtype == np.float64), C.byref(st), 0,
+                                                           C.byref(t)))
+        else:
+            self._ck(self.L.mi355_agroup_submit_agingradio(self.h, member, data, frames, int(bool(is_f64)), C.byref(st), 1, C.byref(t)))
+        return t.value
+
+    def agingradio_state(self, member, channels):
+        y = np.zeros(max(channels, 1), np.float64)
+        k = C.c_uint64(0)
+        self._ck(self.L.mi355_agroup_agingradio_get_state(self.h, member, y.ctypes.data_as(C.POINTER(C.c_double)), channels, C.byref(k)))
+        return y[:channels], int(k.value)
 
     def submit_ebur128(self, member, data, frames=None, sample_format=None):
         t = C.c_uint64(0)
@@ -1027,6 +1076,31 @@ class Context:
         uvw = np.zeros(channels * steps * 3, np.float32)
         self._ck(self.L.mi355_hrtf_last_lookup(self.h, faces.ctypes.data_as(C.POINTER(C.c_int)), uvw.ctypes.data_as(C.POINTER(C.c_float))))
         return faces.reshape(channels, steps), uvw.reshape(channels, steps, 3)
+
+    # ---- agingradio
+    def agingradio_setup(self, channels, rate, lowpass_freq, seed):
+        self._ck(self.L.mi355_agingradio_setup(self.h, channels, rate, lowpass_freq, seed))
+
+    def agingradio_reset(self):
+        self._ck(self.L.mi355_agingradio_reset(self.h))
+
+    def agingradio_process(self, data, channels, settings):
+        """in place on a numpy f32 / f64 array of frames * channels interleaved samples; settings: dict (defaults for missing keys)"""
+        assert data.dtype in (np.float32, np.float64) and data.flags.c_contiguous
+        st = AgingRadioSettings.of(settings)
+        self._ck(self.L.mi355_agingradio_process(self.h, data.ctypes.data, data.size // channels, int(data.dtype == np.float64), C.byref(st)))
+        return data
+
+    def agingradio_process_device(self, dptr, frames, is_f64, settings):
+        st = AgingRadioSettings.of(settings)
+        self._ck(self.L.mi355_agingradio_process_device(self.h, dptr, frames, int(bool(is_f64)), C.byref(st)))
+
+    def agingradio_state(self, channels):
+        """(the filters' outputs, frame pairs processed since setup)"""
+        y = np.zeros(max(channels, 1), np.float64)
+        k = C.c_uint64(0)
+        self._ck(self.L.mi355_agingradio_get_state(self.h, y.ctypes.data_as(C.POINTER(C.c_double)), channels, C.byref(k)))
+        return y[:channels], int(k.value)
 
     # ---- rsaudioecho
     def echo_setup(self, ring_len):

@@ -44,6 +44,9 @@ def _lib():
             "mi355el_transform_frame": (i, [vp, i, i, i, i, vp, sz, i, i, vp, sz]),
             "mi355el_audio_setup": (i, [vp, i, i, i]),
             "mi355el_audio_transform_ip": (i, [vp, vp, sz]),
+            "mi355el_agingradio_new": (vp, [i, C.c_char_p, sz]),
+            "mi355el_agingradio_setup": (i, [vp, i, i, i, C.c_uint64]),
+            "mi355el_agingradio_transform_ip": (i, [vp, vp, sz]),
             "mi355el_ebur128_setup": (i, [vp, i, i, i, i, C.POINTER(i)]),
             "mi355el_ebur128_push": (i, [vp, vp, C.POINTER(vp), sz, C.c_uint64]),
             "mi355el_ebur128_reset_signal": (None, [vp]),
@@ -91,6 +94,19 @@ class Element:
         if not self.h:
             raise ElementError(err.value.decode("utf-8", "replace"))
         self.L = L
+
+    @classmethod
+    def agingradio(cls, device=0):
+        """The agingradio mirror (GstRsAgingRadio). The name registry behind Element(factory) does not make it: it has its own
+        constructor (mi355el_agingradio_new)."""
+        self = cls.__new__(cls)
+        L = _lib()
+        err = C.create_string_buffer(512)
+        self.h = L.mi355el_agingradio_new(device, err, 512)
+        if not self.h:
+            raise ElementError(err.value.decode("utf-8", "replace"))
+        self.L = L
+        return self
 
     def close(self):
         if getattr(self, "h", None):
@@ -168,6 +184,14 @@ class Element:
     def audio_transform_ip(self, data):
         assert isinstance(data, np.ndarray) and data.flags.c_contiguous
         return self.L.mi355el_audio_transform_ip(self.h, data.ctypes.data, data.nbytes)
+
+    # ---- agingradio (audio/audiofx/src/agingradio/imp.rs)
+    def agingradio_setup(self, rate, channels, f64=False, seed=0):
+        return self.L.mi355el_agingradio_setup(self.h, rate, channels, int(f64), seed) == 0
+
+    def agingradio_transform_ip(self, data):
+        assert isinstance(data, np.ndarray) and data.flags.c_contiguous
+        return self.L.mi355el_agingradio_transform_ip(self.h, data.ctypes.data, data.nbytes)
 
     # ---- ebur128level
     _EB_FMT = {np.dtype(np.int16): 0, np.dtype(np.int32): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}

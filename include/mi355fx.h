@@ -716,6 +716,45 @@ int mi355_colordetect_frames_device(mi355_ctx *ctx, const uint8_t *d_frames, siz
 int mi355_colordetect_histogram_device(mi355_ctx *ctx, const uint8_t *d_data, size_t data_len, int format, int quality,
                                        uint32_t hist[32768], int box[6]);
 
+/* ---------------------------------------------------------------- agingradio
+ * Replaces AgingRadio::process::<f32|f64> (audio/audiofx/src/agingradio/imp.rs:94-136): per pair of frames
+ * (data.chunks_exact_mut(channels * 2), :101; an odd last frame is left untouched) either a click - every sample 1.0, filters
+ * not run (:102-107) - or, per sample in f64: white noise (:108-112), the per-channel lowpass on the clamped sample (:113-116),
+ * quantisation (:117-122), the cubic curve (:123-128), narrowed to the buffer's type (:130). The contract, the lowpass-filter
+ * 0.4.1 restatement (parity unpinned) and the counter-based generator that replaces rand::rng() are DESIGN §4.9.
+ *   settings         : Settings as transform_ip snapshots it once per buffer (imp.rs:284-305); lowpass-freq goes to setup.
+ *   _setup           : AudioFilterImpl::setup (imp.rs:326-345): one filter per channel at y = 0 when lowpass_freq > 0, the pair
+ *                      counter at 0, `seed` the instance's Philox key. channels or rate 0: MI355_ERR_INVALID_ARG; lowpass on
+ *                      with more than 2048 channels: MI355_ERR_UNSUPPORTED.
+ *   _process         : in place on `frames` interleaved frames in host memory (is_f64: F64, else F32); synchronous.
+ *   _process_device  : the same on device memory; enqueued on the context's stream. Before setup both return
+ *                      MI355_ERR_NOT_CONFIGURED (transform_ip's NotNegotiated, imp.rs:289).
+ *   _get_state       : test access: the filters' outputs (min(channels, set-up channels) values; zeros without a lowpass) and
+ *                      the frame pairs processed since setup.
+ *   _reset           : BaseTransformImpl::stop (imp.rs:307-312): the state goes. */
+typedef struct mi355_agingradio_settings {
+  float white_noise_ampl;        /* "white-noise-ampl" 0..1 (imp.rs:108-112) */
+  float clicks_prob;             /* "clicks-prob" 0..1 (imp.rs:102-103) */
+  float bits_to_quantize;        /* "bits-to-quantize" 0..64 (imp.rs:117-122) */
+  float cubic_curve_distortion;  /* "cubic-curve-distortion" 0..1 (imp.rs:123-128) */
+  uint32_t cubic_curve_passes;   /* "cubic-curve-passes" (imp.rs:123-128) */
+} mi355_agingradio_settings;
+int mi355_agingradio_setup(mi355_ctx *ctx, unsigned channels, unsigned rate, unsigned lowpass_freq, uint64_t seed);
+int mi355_agingradio_process(mi355_ctx *ctx, void *data, size_t frames, int is_f64, const mi355_agingradio_settings *settings);
+int mi355_agingradio_process_device(mi355_ctx *ctx, void *d_data, size_t frames, int is_f64, const mi355_agingradio_settings *settings);
+int mi355_agingradio_get_state(mi355_ctx *ctx, double *filter_state, unsigned channels, uint64_t *pairs_done);
+int mi355_agingradio_reset(mi355_ctx *ctx);
+/* agingradio through an audio group (csrc/agroup.hip): members are fully independent instances, as echo members are. Each has
+ * its own setup (channels, rate, lowpass, seed: mi355_agroup_agingradio_setup, the element's AudioFilterImpl::setup), and each
+ * submit carries its own buffer length, sample type and settings; one job table per launch set. A submit before the member's
+ * setup returns MI355_ERR_NOT_CONFIGURED. get_state as mi355_agingradio_get_state, for one member. */
+mi355_agroup *mi355_agroup_create_agingradio(int device, int n_members, int *status);
+mi355_agroup *mi355_agroup_shared_agingradio(int device, int n_members, int *member, int *status);
+int mi355_agroup_agingradio_setup(mi355_agroup *group, int member, unsigned channels, unsigned rate, unsigned lowpass_freq, uint64_t seed);
+int mi355_agroup_submit_agingradio(mi355_agroup *group, int member, void *data, size_t frames, int is_f64,
+                                   const mi355_agingradio_settings *settings, int device_data, uint64_t *ticket);
+int mi355_agroup_agingradio_get_state(mi355_agroup *group, int member, double *filter_state, unsigned channels, uint64_t *pairs_done);
+
 #ifdef __cplusplus
 }
 #endif

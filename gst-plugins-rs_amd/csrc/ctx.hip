@@ -1004,6 +1004,7 @@ int mi355_hrtf_sphere_info(mi355_ctx *ctx, uint32_t *hrir_len, uint32_t *n_verti
   REQUIRE_CTX(ctx);
   return hrtf_info(ctx, hrir_len, n_vertices, n_faces);
 }
+int mi355_hrtf_transform_size(mi355_ctx *ctx, int *fft_n) { REQUIRE_CTX(ctx); return hrtf_transform_size(ctx, fft_n); }
 int mi355_hrtf_last_lookup(mi355_ctx *ctx, int *faces, float *uvw) { REQUIRE_CTX(ctx); BIND_DEVICE(ctx); return hrtf_last_lookup(ctx, faces, uvw); }
 
 /* ------------------------------------------------------------------ measurement helpers */

@@ -518,15 +518,18 @@ static void eb_launch_energy(mi355_ctx *ctx, Ebur128State *st, size_t frames, co
 
 // one round: the segment d_segs[stream] of every stream. src_ss: elements between the buffers of consecutive streams
 template <typename T>
-static void eb_launch_segment(mi355_ctx *ctx, Ebur128State *st, const T *d_src, const EbSeg *d_segs, size_t stride_f, size_t stride_c, size_t src_ss) {
+static int eb_launch_segment(mi355_ctx *ctx, Ebur128State *st, const T *d_src, const EbSeg *d_segs, size_t stride_f, size_t stride_c, size_t src_ss) {
   unsigned long long *speak = (st->mode & EB_SAMPLE_PEAK) ? st->d_peak : nullptr;
   if (st->have_interp)
     hipLaunchKernelGGL((eb_truepeak_kernel<T>), dim3(st->channels, st->n_streams), dim3(kEbNT), 0, ctx->stream, d_src, d_segs, stride_f, stride_c, st->d_tail,
                        st->d_peak + st->channels, st->ik, src_ss, st->channels);
   const size_t filter_lds = (size_t)st->channels * (kEbChunk + 4) * sizeof(double);
-  (void)hipFuncSetAttribute((const void *)eb_filter_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)filter_lds);
+  // 64 channels need 130 KiB, above the default limit: a refused request must not reach the launch
+  int rc = check_hip(ctx, hipFuncSetAttribute((const void *)eb_filter_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)filter_lds), "hipFuncSetAttribute(ebur128 filter LDS)");
+  if (rc) return rc;
   hipLaunchKernelGGL((eb_filter_kernel<T>), dim3(1, st->n_streams), dim3(256), filter_lds, ctx->stream, d_src, d_segs, stride_f, stride_c, st->d_ring,
                      st->channels, (const int *)st->d_class, st->d_vstate, speak, st->fk, src_ss, st->ring_frames * st->channels);
+  return MI355_OK;
 }
 
 static int eb_energy_capacity(mi355_ctx *ctx, Ebur128State *st, size_t events) {
@@ -646,7 +649,7 @@ static int eb_add_frames_t(mi355_ctx *ctx, Ebur128State *st, const T *data, cons
   const EbEv *d_evs = (const EbEv *)(st->d_tab + seg_bytes);
   bool any_event = false;
   for (size_t r = 0; r < R; r++) {
-    eb_launch_segment<T>(ctx, st, d_src, d_segs + r * S, stride_f, stride_c, src_ss);
+    if ((rc = eb_launch_segment<T>(ctx, st, d_src, d_segs + r * S, stride_f, stride_c, src_ss))) return rc;
     if (any_ev[r * 2 + 0]) { eb_launch_energy(ctx, st, st->samples_in_100ms * 4, d_evs + (r * 2 + 0) * S); any_event = true; }
     if (any_ev[r * 2 + 1]) { eb_launch_energy(ctx, st, st->samples_in_100ms * 30, d_evs + (r * 2 + 1) * S); any_event = true; }
   }

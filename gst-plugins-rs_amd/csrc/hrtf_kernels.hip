@@ -509,4 +509,13 @@ int hrtf_info(mi355_ctx *ctx, uint32_t *len, uint32_t *vertices, uint32_t *faces
   return MI355_OK;
 }
 
+// which convolution form setup chose: the overlap-save transform size, 0 for the time-domain FIR
+int hrtf_transform_size(mi355_ctx *ctx, int *fft_n) {
+  HrtfState *H = hrtf_of(ctx);
+  if (!H || !H->configured) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)");
+  if (!fft_n) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: null output");
+  *fft_n = H->fft_n;
+  return MI355_OK;
+}
+
 }  // namespace mi355

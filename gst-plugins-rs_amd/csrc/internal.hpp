@@ -252,6 +252,7 @@ int hrtf_process_block_device(mi355_ctx *ctx, const float *d_in, float *d_out, c
 int hrtf_process_block_host(mi355_ctx *ctx, const float *in, float *out, const float *positions, const float *gains);
 int hrtf_last_lookup(mi355_ctx *ctx, int *faces, float *uvw);
 int hrtf_info(mi355_ctx *ctx, uint32_t *len, uint32_t *vertices, uint32_t *faces);
+int hrtf_transform_size(mi355_ctx *ctx, int *fft_n);
 int sofa_setup(mi355_ctx *ctx, int channels, int filter_len, int partition_len, int block_len);
 int sofa_set_filter(mi355_ctx *ctx, int channel, const float *left, const float *right, int delay_left, int delay_right);
 int sofa_set_drop(mi355_ctx *ctx, int channel, int drop);

@@ -222,6 +222,9 @@ int sofa_set_drop(mi355_ctx *ctx, int channel, int drop) {
   SofaState *S = sofa_of(ctx);
   if (!S) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured");
   if (channel < 0 || channel >= S->channels) return set_error(ctx, MI355_ERR_INVALID_ARG, "sofalizer: bad channel");
+  // the element fixes Drop per channel when it negotiates and never toggles it; a channel that came back in mid-run would find
+  // a delay line that stopped at some earlier sub-block, so the flags are fixed once a block has run (until reset or setup)
+  if (S->counter != 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "sofalizer: drop flags are fixed once a block has been processed (reset first)");
   S->drop[channel] = drop ? 1 : 0;
   return check_hip(ctx, hipMemcpy(S->d_drop, S->drop.data(), S->drop.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(sofalizer drop flags)");
 }
@@ -245,7 +248,8 @@ int sofa_process_block_device(mi355_ctx *ctx, const float *d_in, float *d_out, c
   int rc = check_hip(ctx, hipMemcpyAsync(S->d_gain, gains, (size_t)S->channels * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(sofalizer gains)");
   if (rc) return rc;
   const size_t lds = (3 * (size_t)S->N + S->N / 2) * sizeof(float2);
-  (void)hipFuncSetAttribute((const void *)sofa_convolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  // partition 2048 needs 112 KiB, above the default limit: a refused request must not reach the launch
+  if ((rc = check_hip(ctx, hipFuncSetAttribute((const void *)sofa_convolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(sofalizer convolve LDS)"))) return rc;
   hipLaunchKernelGGL(sofa_convolve_kernel, dim3(S->channels), dim3(256), lds, ctx->stream, d_in, S->channels, (const float2 *)S->d_H, S->d_fdl, S->d_prev,
                      S->d_partial, (const int *)S->d_drop, S->P, S->B, S->K, S->N, S->logN, (unsigned)(S->counter % (unsigned long long)S->K));
   hipLaunchKernelGGL(sofa_mix_kernel, dim3((2 * S->B + 255) / 256), dim3(256), 0, ctx->stream, (const float *)S->d_partial, (const float *)S->d_gain,

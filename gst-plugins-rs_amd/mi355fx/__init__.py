@@ -250,6 +250,7 @@ def load_library():
         "mi355_hrtf_process_block": (i, [vp, f32p, f32p, f32p, f32p]),
         "mi355_hrtf_process_block_device": (i, [vp, vp, vp, f32p, f32p]),
         "mi355_hrtf_sphere_info": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "mi355_hrtf_transform_size": (i, [vp, C.POINTER(C.c_int)]),
         "mi355_hrtf_last_lookup": (i, [vp, C.POINTER(C.c_int), f32p]),
         "mi355_time_hsvfilter_device": (i, [vp, u8p, i, sz, i, i, i, i, C.POINTER(HsvSettings), i, f32p]),
         "mi355_time_hsv_colorlut_device": (i, [vp, u8p, sz, i, u8p, sz, i, i, i, i, C.POINTER(HsvSettings), i, f32p]),
@@ -1051,6 +1052,12 @@ class Context:
         a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         self._ck(self.L.mi355_hrtf_sphere_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def hrtf_transform_size(self):
+        """overlap-save transform size setup chose, 0 when the time-domain FIR serves"""
+        n = C.c_int(-1)
+        self._ck(self.L.mi355_hrtf_transform_size(self.h, C.byref(n)))
+        return n.value
 
     def hrtf_process_block(self, inp, positions, gains):
         channels, frames, _ = self._hrtf_shape

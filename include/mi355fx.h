@@ -576,6 +576,9 @@ int mi355_hrtf_process_block_device(mi355_ctx *ctx, const float *d_in, float *d_
                                     const float *positions_xyz, const float *distance_gains);
 /* Sphere geometry as loaded: HRIR length, vertices, faces. */
 int mi355_hrtf_sphere_info(mi355_ctx *ctx, uint32_t *hrir_len, uint32_t *n_vertices, uint32_t *n_faces);
+/* Which convolution form mi355_hrtf_setup chose: *fft_n = the overlap-save transform size (the next power of two holding
+ * hrir_len - 1 + block_length, served for 512..4096), 0 when the time-domain FIR serves. Read-only. */
+int mi355_hrtf_transform_size(mi355_ctx *ctx, int *fft_n);
 /* Diagnostics: mesh face (or -1) and barycentric weights chosen per [channel][step] in the last block. */
 int mi355_hrtf_last_lookup(mi355_ctx *ctx, int *faces, float *uvw);
 
@@ -589,7 +592,9 @@ int mi355_hrtf_last_lookup(mi355_ctx *ctx, int *faces, float *uvw);
  *   setup       block_length must be a multiple of partition_length (else INVALID_ARG with the reference's message,
  *               :775-781); partition_length a power of two in 8..2048 (UNSUPPORTED otherwise)
  *   set_filter  filter_len taps per ear + whole-sample onset delays (>= 0); effective from the next block
- *   set_drop    ChannelProcessor::Drop for LFE1 / LFE2 (:808-821)
+ *   set_drop    ChannelProcessor::Drop for LFE1 / LFE2 (:808-821). The element fixes it per channel when it negotiates and
+ *               never toggles it: after the first block the call fails with INVALID_ARG until reset or setup (a channel
+ *               returning in mid-run would have no defined history)
  *   reset       flush-stop (:840-848): input history cleared
  *   process_block  in: block_length x channels interleaved f32; out: block_length x 2 interleaved f32
  * The crate's arithmetic is not in the reference tree: parity is that of a streaming linear convolution, within 2e-6 of

@@ -17,7 +17,7 @@ def test_header_declares_the_expected_entry_points():
     syms = _declared_symbols()
     for must in ("mi355_ctx_create", "mi355_hsvfilter_frame_ip", "mi355_hsvfilter_frames_device", "mi355_colorlut_load",
                  "mi355_colorlut_frame", "mi355_colorlut_frames_device", "mi355_echo_setup", "mi355_echo_process_f32",
-                 "mi355_hsvdetect_frame"):
+                 "mi355_hsvdetect_frame", "mi355_hrtf_sphere_info", "mi355_hrtf_transform_size"):
         assert must in syms
     assert len(syms) >= 30
 

@@ -1,7 +1,10 @@
 """GPU loudness meter (mi355_ebur128_*) vs the serial f64 oracle. The K-weighting recurrence is evaluated
-as a chunked parallel scan, so filtered samples differ from the serial run by rounding of the chained
-states (~1e-16 relative): loudness values are compared with |delta| <= 1e-9 LU (far inside 1 ulp of
-the f32 the element's consumers print), peaks and histogram-derived quantities must be identical."""
+literally, one serial lane per channel walking v0 = x - a1 v1 - a2 v2 - a3 v3 - a4 v4 in 256-frame chunks (a chunked
+parallel scan was tried and rejected: csrc/ebur128_kernels.hip), so the filtered samples are those of a serial run;
+what may differ from the oracle is the order in which the window energies are summed (32 blocks x 256 lanes against
+one running sum, ~1e-16 relative): loudness values are compared with |delta| <= 1e-9 LU (far inside 1 ulp of
+the f32 the element's consumers print), peaks and histogram-derived quantities must be identical.
+State carried across buffer edges, chunks and the ring wrap is tested in tests/test_gpu_audio_state.py."""
 import numpy as np
 import pytest
 

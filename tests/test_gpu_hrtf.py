@@ -11,6 +11,8 @@ import os
 import numpy as np
 import pytest
 
+import audio_state_cases as A
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "test.hrir")
@@ -51,6 +53,8 @@ def _run(ctx, oracle, synth, length, channels, steps, block, n_blocks, seed, sta
         ctx.hrtf_setup(channels, block, steps)
     finally:
         ctx.set_flag(mi355fx.FLAG_HRTF_METHOD, 0)
+    # which form serves is part of what is tested: "the FFT path" is asserted to be one (0 = the time-domain FIR)
+    assert ctx.hrtf_transform_size() == A.hrtf_expected_transform(length, block, method)
     r = oracle.HrtfRender(sphere, channels, steps, block)
     ex = oracle.HrtfExact(sphere, channels, steps, block)
     rng = np.random.default_rng(seed)
@@ -81,12 +85,36 @@ def _run(ctx, oracle, synth, length, channels, steps, block, n_blocks, seed, sta
     return worst_exact, worst_oracle, oracle_exact, max(scale, 1.0)
 
 
-@pytest.mark.parametrize("method", [1, 2])
-@pytest.mark.parametrize("length,channels,steps,block", [(1, 1, 8, 512), (32, 2, 8, 64), (128, 8, 8, 512), (100, 3, 4, 77), (512, 4, 2, 1500)])
+# method 2 (FIR) keeps every shape; method 1 (FFT) takes the shapes whose window [L - 1 | block] reaches the 512-point floor of the
+# transform - (32, 2, 8, 64) and (100, 3, 4, 77) have windows of 95 and 176 points, where method 1 is served by the FIR as well, so
+# they run with blocks of 500 and 450 frames (windows of 531 and 549 points -> 1024) under method 1
+@pytest.mark.parametrize("length,channels,steps,block,method", [
+    (1, 1, 8, 512, 1), (32, 2, 8, 500, 1), (128, 8, 8, 512, 1), (100, 3, 4, 450, 1), (512, 4, 2, 1500, 1),
+    (1, 1, 8, 512, 2), (32, 2, 8, 64, 2), (128, 8, 8, 512, 2), (100, 3, 4, 77, 2), (512, 4, 2, 1500, 2)])
 def test_blocks_match_oracle_and_exact(ctx, oracle, synth, length, channels, steps, block, method):
-    """both convolution forms - the overlap-save FFT in LDS (round 3; where block + HRIR fit 4096 points, else the call falls
-    back to the FIR) and the time-domain FIR - against the f64 exact value and the f32 FFT restatement"""
+    """both convolution forms - the overlap-save FFT in LDS (where block + HRIR fit 512 .. 4096 points, else the call is served by
+    the FIR) and the time-domain FIR - against the f64 exact value and the f32 FFT restatement"""
     we, wo, oe, scale = _run(ctx, oracle, synth, length, channels, steps, block, 4, 17 * length + block, method=method)
+    if method == 1:
+        assert ctx.hrtf_transform_size() >= 512
+    assert we <= TOL_EXACT * scale, (we, scale)
+    assert wo <= TOL_ORACLE * scale, (wo, scale)
+
+
+# (L, block): the window L - 1 + block on 511 points (one short of the transform: 512 serves with one point of padding), 512 (the
+# circular wrap meets the first valid output), 513, 1024, 1025, 2048, 4096, 4097 (above the ceiling: FIR). The floor of the
+# transform is 512 POINTS, so the last window the FIR serves under method 1 is 256 points (-> 256) and 257 is the first on 512.
+WINDOW_EDGES = [(100, 157), (100, 158), (200, 312), (200, 313), (400, 114), (513, 512), (514, 512), (1025, 1024), (2049, 2048), (2050, 2048)]
+
+
+@pytest.mark.parametrize("method", [0, 1, 2])
+@pytest.mark.parametrize("length,block", WINDOW_EDGES)
+def test_transform_size_edges(ctx, oracle, synth, length, block, method):
+    """moving sources, 3 blocks, every method at every edge of the transform size; _run asserts which form served"""
+    assert length - 1 + block in (256, 257, 511, 512, 513, 1024, 1025, 2048, 4096, 4097)
+    we, wo, oe, scale = _run(ctx, oracle, synth, length, 2, 2, block, 3, length + 3 * block + method, method=method)
+    print("hrtf L %d block %d method %d: transform %d, vs exact %.3g, vs oracle %.3g, oracle vs exact %.3g (of scale %.3g)"
+          % (length, block, method, ctx.hrtf_transform_size(), we / scale, wo / scale, oe / scale, scale))
     assert we <= TOL_EXACT * scale, (we, scale)
     assert wo <= TOL_ORACLE * scale, (wo, scale)
 

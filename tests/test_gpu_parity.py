@@ -624,6 +624,89 @@ def test_echo_batch_of_streams(ctx, oracle, synth, dtype):
         ctx.echo_reset()
 
 
+def _echo_sized(oracle, size):
+    """an oracle instance whose ring has exactly `size` cells (1 kHz mono: one sample per millisecond)"""
+    e = oracle.Echo(size * 10 ** 6, 1000, 1)
+    assert e.ring_len == size
+    return e
+
+
+def _echo_step(ctx, e, x, delay, intensity, feedback, what):
+    """one buffer through both; data, ring and position compared bit for bit"""
+    exp, got = x.copy(), x.copy()
+    e.process(exp, delay * 10 ** 6, intensity, feedback)
+    ctx.echo_process(got, delay, intensity, feedback)
+    assert got.tobytes() == exp.tobytes(), what
+    ring, pos = ctx.echo_state(e.ring_len)
+    assert pos == e.pos, what
+    assert ring[: e.ring_len].tobytes() == e.ring[: e.ring_len].tobytes(), what
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("feedback", [0.0, 0.45])
+@pytest.mark.parametrize("size,delay", [(300, 300), (300, 0), (300, 299), (256, 256), (257, 1)])
+def test_echo_sizes_around_the_ring(ctx, oracle, dtype, feedback, size, delay):
+    """delay == ring_len (the alias of delay 0 reached by the other door), buffers of size - 1, size, size + 1 and 2 size + 3
+    samples (the commit kernel keeps the last `size`), n < D with feedback for n = 1, 255, 256, 257 (fewer chains than lanes) and
+    D = 1 (one chain walks the whole buffer: short buffers). Ring and position compared after every buffer."""
+    e = _echo_sized(oracle, size)
+    ctx.echo_setup(size)
+    rng = np.random.default_rng(size + delay)
+    sizes = [size - 1, size, size + 1, 2 * size + 3, 1, 255, 256, 257, size, 1, 2 * size + 3] if delay != 1 else [1, 2, 63, 64, 65, size + 1]
+    for k, n in enumerate(sizes):
+        _echo_step(ctx, e, rng.standard_normal(n).astype(dtype), delay, 0.7, feedback, (k, n))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_echo_parameters_change_between_buffers(ctx, oracle, dtype):
+    """delay and feedback change from buffer to buffer on the single-stream entry point (feedback 0 -> non-zero -> 0: the two
+    forms of the main kernel hand the ring to each other)"""
+    size = 300
+    e = _echo_sized(oracle, size)
+    ctx.echo_setup(size)
+    rng = np.random.default_rng(9)
+    steps = [(299, 300, 0.0), (301, 7, 0.5), (300, 0, 0.0), (255, 150, 0.9), (257, 300, 0.3), (1, 1, 0.0), (603, 299, 0.6), (64, 1, 0.5),
+             (300, 300, 0.0)]
+    for k, (n, delay, fb) in enumerate(steps):
+        _echo_step(ctx, e, rng.standard_normal(n).astype(dtype), delay, 0.6, fb, (k, n, delay, fb))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("S", [4, 5])
+def test_echo_batch_sizes_around_the_ring(ctx, oracle, dtype, S):
+    """the same sizes through the batch entry point with exactly kEchoInline (4) streams - parameters in the kernel arguments -
+    and with 5 - parameters through the device array"""
+    size = 300
+    es = [_echo_sized(oracle, size) for _ in range(S)]
+    ctx.echo_setup_batch(S, size)
+    d = [300, 0, 299, 1, 150][:S]
+    inten = [0.7, 0.5, 0.9, 0.4, 0.6][:S]
+    fb = [0.45, 0.0, 0.3, 0.5, 0.0][:S]
+    rng = np.random.default_rng(S)
+    stride = 2 * size + 3 + 5
+    dev = ctx.alloc(S * stride * np.dtype(dtype).itemsize)
+    try:
+        for n in [size - 1, size, size + 1, 2 * size + 3, 1, 255, 256, 257]:
+            x = rng.standard_normal((S, stride)).astype(dtype)
+            exp = x.copy()
+            for s in range(S):
+                row = np.ascontiguousarray(exp[s, :n])
+                es[s].process(row, d[s] * 10 ** 6, inten[s], fb[s])
+                exp[s, :n] = row
+            ctx.h2d(dev, x.reshape(-1).view(np.uint8))
+            ctx.echo_process_batch_device(dev, stride, n, dtype == np.float64, d, inten, fb)
+            got = np.zeros_like(x)
+            ctx.synchronize()
+            ctx.d2h(got.reshape(-1).view(np.uint8), dev)
+            assert got.tobytes() == exp.tobytes(), "buffer of %d samples" % n
+            for s in range(S):
+                ring, pos = ctx.echo_state(size, stream=s)
+                assert pos == es[s].pos and ring[:size].tobytes() == es[s].ring[:size].tobytes(), (n, s)
+    finally:
+        ctx.free(dev)
+        ctx.echo_reset()
+
+
 def test_echo_not_negotiated(ctx):
     """transform_ip before setup is FlowError::NotNegotiated (audioecho/imp.rs:210)."""
     import mi355fx

@@ -51,6 +51,19 @@ typedef struct {
   double *adapter; size_t adapter_len, adapter_cap;
 } loudnorm;
 
+/* Element c of the frame that starts at ring index `index`. The reference addresses a frame as the slice
+ * limiter_buf[index..index + channels] and wraps `index` once per frame, which stays inside the ring as long as `index`
+ * is a multiple of `channels`. process_final_frame advances limiter_buf_index by FRAME_SIZE - next_frame_size (frames,
+ * not frames * channels, imp.rs:766-771), so for the last, short limiter call of a stream whose shortfall is not a
+ * multiple of `channels` a frame can start less than `channels` elements before the ring's end; the reference's unchecked
+ * slice then runs past the allocation. Undefined there; here every element wraps on its own, which is the
+ * reference's walk wherever that walk is in bounds. */
+static inline size_t ring_at(const loudnorm *s, size_t index, size_t c) {
+  size_t i = index + c;
+  if (i >= s->limiter_len) i -= s->limiter_len;
+  return i;
+}
+
 static void init_gaussian_filter(double w[21]) {
   double total = 0.0;
   const double sigma = 3.5;
@@ -112,10 +125,9 @@ static int detect_peak(loudnorm *s, size_t offset, size_t samples, size_t *peak_
   for (size_t n = 0; n < samples; n++) {
     size_t next_index = index + ch;
     if (next_index >= len) next_index -= len;
-    const double *this_ = s->limiter_buf + index, *next_ = s->limiter_buf + next_index;
     int detected = 0;
     for (size_t c = 0; c < ch; c++) {
-      const double th = fabs(this_[c]), nx = fabs(next_[c]);
+      const double th = fabs(s->limiter_buf[ring_at(s, index, c)]), nx = fabs(s->limiter_buf[ring_at(s, next_index, c)]);
       detected = 0;
       if (s->prev_smp[c] <= th && th >= nx && th > s->target_tp && n > 0) {
         detected = 1;
@@ -131,8 +143,9 @@ static int detect_peak(loudnorm *s, size_t offset, size_t samples, size_t *peak_
     if (detected) {
       double max_peak = 0.0;
       for (size_t c = 0; c < ch; c++) {
-        if (c == 0 || fabs(this_[c]) > max_peak) max_peak = fabs(this_[c]);
-        s->prev_smp[c] = fabs(this_[c]);
+        const double th = fabs(s->limiter_buf[ring_at(s, index, c)]);
+        if (c == 0 || th > max_peak) max_peak = th;
+        s->prev_smp[c] = th;
       }
       *peak_delta = n; *peak_value = max_peak;
       return 1;
@@ -158,7 +171,7 @@ static size_t limiter_out(loudnorm *s, size_t smp_cnt, size_t nb) {
 }
 
 static void mul_frame(loudnorm *s, size_t *index, double g) {
-  for (size_t c = 0; c < s->channels; c++) s->limiter_buf[*index + c] *= g;
+  for (size_t c = 0; c < s->channels; c++) s->limiter_buf[ring_at(s, *index, c)] *= g;
   *index += s->channels;
   if (*index >= s->limiter_len) *index -= s->limiter_len;
 }
@@ -317,7 +330,7 @@ static void true_peak_limiter(loudnorm *s, double *dst, size_t nb) {
   size_t index = s->limiter_buf_index;
   for (size_t n = 0; n < nb; n++) {
     for (size_t c = 0; c < ch; c++) {
-      double o = s->limiter_buf[index + c];
+      double o = s->limiter_buf[ring_at(s, index, c)];
       if (fabs(o) > s->target_tp) o = s->target_tp * (signbit(o) ? -1.0 : 1.0);  /* f64::signum: +-1 (NaN never passes the test) */
       dst[n * ch + c] = o;
     }
@@ -352,7 +365,7 @@ static void fill_inner_frame(loudnorm *s, const double *src, size_t frames) {
     for (size_t c = 0; c < ch; c++) s->buf[s->prev_buf_index + c] = src[n * ch + c];
     /* buf_read and buf_write never alias (imp.rs:470-490): prev_buf_index != buf_index by construction; when they
      * are equal (only before the first inner frame completes a lap) the read happened first above */
-    for (size_t c = 0; c < ch; c++) s->limiter_buf[s->limiter_buf_index + c] = tmp[c] * current_gain;
+    for (size_t c = 0; c < ch; c++) s->limiter_buf[ring_at(s, s->limiter_buf_index, c)] = tmp[c] * current_gain;
     s->limiter_buf_index += ch; if (s->limiter_buf_index >= s->limiter_len) s->limiter_buf_index -= s->limiter_len;
     s->prev_buf_index += ch; if (s->prev_buf_index >= s->buf_len) s->prev_buf_index -= s->buf_len;
     s->buf_index += ch; if (s->buf_index >= s->buf_len) s->buf_index -= s->buf_len;
@@ -365,7 +378,7 @@ static void fill_final_frame(loudnorm *s, size_t idx, size_t num_samples) {
   const double gain_next = gaussian_filter(s, s->index + 11 < 30 ? s->index + 11 : s->index + 11 - 30);
   for (size_t n = idx; n < num_samples; n++) {
     const double current_gain = (gain + (((double)n / (double)num_samples) * (gain_next - gain))) * s->offset;
-    for (size_t c = 0; c < ch; c++) s->limiter_buf[s->limiter_buf_index + c] = s->buf[s->buf_index + c] * current_gain;
+    for (size_t c = 0; c < ch; c++) s->limiter_buf[ring_at(s, s->limiter_buf_index, c)] = s->buf[s->buf_index + c] * current_gain;
     s->limiter_buf_index += ch; if (s->limiter_buf_index >= s->limiter_len) s->limiter_buf_index -= s->limiter_len;
     s->buf_index += ch; if (s->buf_index >= s->buf_len) s->buf_index -= s->buf_len;
   }
@@ -446,7 +459,7 @@ size_t oracle_loudnorm_process(loudnorm *s, const double *src, size_t frames, do
         const size_t next_frame_size = out_num_samples - smp_cnt < FRAME_SIZE ? out_num_samples - smp_cnt : FRAME_SIZE;
         fill_final_frame(s, 0, next_frame_size);
         if (next_frame_size < FRAME_SIZE) {
-          s->limiter_buf_index += (FRAME_SIZE - next_frame_size);  /* sic: samples, not samples*channels (imp.rs:763) */
+          s->limiter_buf_index += (FRAME_SIZE - next_frame_size);  /* sic: samples, not samples*channels (imp.rs:766-771); see ring_at */
           if (s->limiter_buf_index >= s->limiter_len) s->limiter_buf_index -= s->limiter_len;
         }
       }

@@ -524,3 +524,53 @@ def test_loudnorm_push_and_drain_of_members_are_the_single_instance_calls(mi355l
     again = mi355fx.AudioGroup("loudnorm", n_m, shared=True, channels=ch, loudness_target=-20.0)
     assert again.member == 0   # a fresh group: the old one is gone
     again.close()
+
+
+def test_loudnorm_member_with_a_misaligned_final_frame(mi355lib, oracle):
+    """Three stereo members drain at once; member 0's stream is 610201 frames long: its last limiter call is 15001 frames, starts at
+    an odd ring index (the reference advances by frames, not frames * channels, imp.rs:766-771) and walks across the ring's end,
+    where every element wraps on its own. The neighbours end aligned (3 s + 100 ms exactly; an even shortfall). Every
+    member equals its single-instance context bit for bit and the oracle within the meters' 1e-9."""
+    import mi355fx
+    import loudnorm_cases as LC
+    ch = 2
+    xs = [LC.get("misaligned_crossing_2ch").x, LC.get("len_3s_plus_19200").x, LC.programme(604802, ch, 5)]
+    assert [(19200 - len(x) % 19200) % 19200 % ch for x in xs] == [1, 0, 0]
+    exp, ora = [], []
+    for x in xs:
+        c = mi355fx.Context(0)
+        c.loudnorm_setup(ch)
+        exp.append(np.concatenate([c.loudnorm_push(x), c.loudnorm_drain()]))
+        c.close()
+        ln = oracle.LoudNorm(ch)
+        ora.append(np.concatenate([ln.push(x), ln.drain()]))
+    g = mi355fx.AudioGroup("loudnorm", len(xs), channels=ch)
+    got, err = [None] * len(xs), []
+
+    def element(m):
+        try:
+            x = xs[m]
+            cut = [150001, 300000 + 7 * m]
+            parts = [g.loudnorm_push(m, p) for p in (x[:cut[0]], x[cut[0]:cut[1]], x[cut[1]:])]
+            parts.append(g.loudnorm_drain(m))
+            got[m] = np.concatenate(parts)
+        except Exception as e:      # noqa: BLE001
+            err.append(e)
+            g.detach(m)
+
+    try:
+        ts = [threading.Thread(target=element, args=(m,)) for m in range(len(xs))]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        assert not err, err
+        for m in range(len(xs)):
+            assert got[m].size == exp[m].size == xs[m].size
+            assert (got[m] == exp[m]).all(), (m, int((got[m] != exp[m]).sum()))
+            scale = float(np.abs(ora[m]).max())
+            assert float(np.abs(got[m] - ora[m]).max()) / scale <= 1e-9, m
+    finally:
+        g.close()
+        for n in ("misaligned_crossing_2ch", "len_3s_plus_19200"):
+            LC.get(n).release()

@@ -155,3 +155,70 @@ def test_batch_argument_checks(ctx):
         ctx.loudnorm_process_batch(np.zeros((2, 100 * 2)))   # not a whole frame
     ctx.loudnorm_teardown()
     assert ctx.loudnorm_batch_frame_size() == 0
+
+
+# ------------------------------------------------------------------ the case table (tests/loudnorm_cases.py)
+#
+# Every case is pinned on the CPU first (tests/test_loudnorm_cpu.py): the oracle equals an independent restatement of imp.rs bit
+# for bit there, and the limiter branches the case reaches are known by name. Here the host state machine over ln_detect_kernel /
+# ln_envelope_kernel and lnb_limiter_kernel run the same streams. The "grid" cases keep every delta at exactly 1.0 (input below
+# -70 LUFS, the gain is the +60 dB offset: no meter reading enters a sample), so they are asserted BIT-IDENTICAL to the oracle; the
+# programme cases at the meters' 1e-9.
+
+import loudnorm_cases as LC
+
+
+def _case_single(oracle, case):
+    """(single-stream context output, oracle output) of a case"""
+    import mi355fx
+    ln = oracle.LoudNorm(case.channels, **case.kw)
+    got, exp = [], []
+    with mi355fx.Context(0) as c1:
+        c1.loudnorm_setup(case.channels, **case.kw)
+        for part in case.chunks():
+            g, e = c1.loudnorm_push(part), ln.push(part)
+            assert g.size == e.size
+            got.append(g); exp.append(e)
+        g, e = c1.loudnorm_drain(), ln.drain()
+        assert g is not None and e is not None and g.size == e.size
+        got.append(g); exp.append(e)
+    return np.concatenate(got), np.concatenate(exp)
+
+
+def _fillers(case):
+    """streams of the case's length whose limiter is somewhere else at every moment: the case itself 5000 frames late, programme
+    with bursts at other places, and one that never leaves Out"""
+    n, ch = case.x.shape
+    late = np.roll(case.x, 5000, axis=0)
+    rng = np.random.default_rng(len(case.name))
+    prog = _tone((n + 1) / RATE, ch, amp=0.03, f=517.0)[:n]
+    for _ in range(8):
+        i = int(rng.integers(0, n - 4000))
+        prog[i:i + int(rng.integers(10, 3000))] *= rng.uniform(20.0, 90.0)
+    if case.kw.get("offset"):
+        prog *= 10 ** (-case.kw["offset"] / 20.0)
+    return [late, prog, _tone((n + 1) / RATE, ch, amp=1e-9)[:n]]
+
+
+@pytest.mark.parametrize("name", LC.names())
+def test_case_table_single_stream_and_batch(ctx, oracle, name):
+    """loudnorm_push / loudnorm_drain (host state machine over ln_detect_kernel / ln_envelope_kernel) against the oracle, then
+    loudnorm_process_batch (lnb_limiter_kernel) holding the case as stream 2 of 4, bit-identical to the single-stream context"""
+    case = LC.get(name)
+    try:
+        single, exp = _case_single(oracle, case)
+        n_diff, rel = int((single != exp).sum()), _close(single, exp)
+        print("%s: %d of %d samples differ from the oracle, scale-relative %.3g" % (name, n_diff, single.size, rel))
+        assert single.size == case.x.size
+        assert rel <= 1e-9
+        if name.startswith("grid"):
+            assert n_diff == 0
+        if name != "len_3s_minus_1":
+            assert np.abs(single).max() <= 10 ** (-2.0 / 20)
+        late, prog, quiet = _fillers(case)
+        got = _run_batch(ctx, [late, prog, case.x, quiet], case.channels, **case.kw)
+        assert got.shape[1] == single.size
+        assert (got[2] == single).all(), (name, int((got[2] != single).sum()))
+        assert _close(got[2], exp) <= 1e-9
+    finally:
+        case.release()

@@ -12,7 +12,9 @@
 //   * the batch runs when every attached member has submitted (whoever completes the set runs it), ONE launch set for all;
 //   * members are independent: rsaudioecho - own ring, position, buffer size and parameters per submit (a job table); agingradio -
 //     own setup (channels, rate, lowpass, seed), filter states and pair counter, buffer size, sample type and settings per submit
-//     (agingradio.hip's job table);
+//     (agingradio.hip's job table); hrtfrender - own sphere (shared by content), channel count, block-length, interpolation-steps and
+//     convolution form per member, own tails and previous directions (hrtf_kernels.hip's job tables: HrtfRender::process,
+//     audio/hrtf/src/hrtf/imp.rs:164-278, for every member that has a block in ONE launch set);
 //     ebur128level - own buffer size, 100 ms phase and `reset` (per-stream rounds in ebur128_kernels.hip); audioloudnorm - own frame
 //     type and ring positions (loudnorm.hip: a launch sequence per CLASS of members that stand at the same frame type and size:
 //     streams that started together are one class). A waiter that has lingered `linger_us` launches whoever is there: a member that
@@ -100,14 +102,14 @@ __global__ __launch_bounds__(256) void echo_jobs_commit_kernel(const EchoJob *__
 
 namespace {
 
-enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4 };
+enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4, KIND_HRTF = 5 };
 
 struct Sub {   // one member's submission of the interval being collected
   bool have = false;
   bool device = false;
   void *data = nullptr;      // caller's buffer (echo: in place; ebur128: input; loudnorm: input)
-  void *out = nullptr;       // loudnorm: caller's output buffer
-  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm / agingradio: frames
+  void *out = nullptr;       // loudnorm / hrtfrender: caller's output buffer
+  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm / agingradio / hrtfrender: frames
   size_t out_cap = 0;        // loudnorm: capacity of `out` in frames
   int fmt = 0;               // echo / agingradio: is_f64; ebur128: sample format
   int final_frame = 0;       // loudnorm
@@ -158,6 +160,9 @@ struct mi355_agroup {
   // ---- agingradio
   std::vector<AgingMember> aging;
   AgingJob *h_ajobs = nullptr, *d_ajobs = nullptr;
+  // ---- hrtfrender
+  HrtfGroup *hrtf = nullptr;        // the members' spheres, processors and job tables (hrtf_kernels.hip)
+  std::vector<float> hrtf_pg;       // [member][4 * 64]: positions [C][3] then gains [C], copied at submit
   // ---- ebur128
   unsigned channels = 0;
   uint64_t query_interval[5] = {0, 0, 0, 0, 0};   // ebur128: the interval the cached answers below belong to
@@ -188,6 +193,14 @@ int ahip(mi355_agroup *g, hipError_t e, const char *what) {
 
 // staging slots of at least `need` bytes per member (and `out_need` for the output side). A slab is replaced while no copy runs on it and
 // no launch is in flight; what it holds of members' business - submissions copied in, results not collected yet - moves along.
+// a member's row of the output slab: loudnorm's is out_cap_bytes rounded down to whole frames of its channel count; hrtfrender's
+// output is stereo f32 whatever the member's input channels are, and its row is the slot itself
+size_t out_row(const mi355_agroup *g, size_t cap) {
+  if (g->kind == KIND_HRTF) return cap;
+  const size_t fb = (size_t)g->channels * 8;
+  return cap / fb * fb;
+}
+
 int ensure_staging(mi355_agroup *g, std::unique_lock<std::mutex> &lk, size_t need, size_t out_need) {
   if (need > g->cap_bytes || out_need > g->out_cap_bytes) g->cv.wait(lk, [g] { return g->copying == 0; });   // nobody is writing into the old slots
   if (need > g->cap_bytes) {
@@ -218,8 +231,8 @@ int ensure_staging(mi355_agroup *g, std::unique_lock<std::mutex> &lk, size_t nee
     if ((rc = ahip(g, hipMalloc((void **)&d, cap * (size_t)g->n_members), "hipMalloc(agroup output staging)"))) { (void)hipHostFree(h); return rc; }
     // results that their members have not collected yet move along (a row of the output slab is out_cap_bytes wide, rounded down to
     // whole frames: wait() computes the row the same way)
-    if (g->h_out && g->channels) {
-      const size_t fb = (size_t)g->channels * 8, old_row = g->out_cap_bytes / fb * fb, new_row = cap / fb * fb;
+    if (g->h_out && (g->channels || g->kind == KIND_HRTF)) {
+      const size_t old_row = out_row(g, g->out_cap_bytes), new_row = out_row(g, cap);
       for (int m = 0; m < g->n_members; m++)
         if (g->res_pending[(size_t)m]) std::memcpy(h + (size_t)m * new_row, g->h_out + (size_t)m * old_row, old_row);
     }
@@ -457,6 +470,50 @@ int run_loudnorm(mi355_agroup *g) {
   return ahip(g, hipStreamSynchronize(st), "agroup loudnorm: sync");
 }
 
+// ---- hrtfrender: the members that have submitted render their block in ONE launch set (hrtf_kernels.hip: prepare, at most one
+// convolution launch per transform size present plus one for the FIR rows, mix). Host members: one strided upload and one strided
+// download per run of consecutive participating host members - normally one each for all of them. g->mu held.
+int run_hrtf(mi355_agroup *g) {
+  std::vector<HrtfSubmit> subs;
+  size_t max_in = 0, max_out = 0;
+  for (int m = 0; m < g->n_members; m++) {
+    const Sub &s = g->sub[m];
+    if (!s.have) continue;
+    const float *pg = g->hrtf_pg.data() + (size_t)m * 256;
+    HrtfSubmit h;
+    h.member = m;
+    h.d_in = s.device ? (const float *)s.data : (const float *)(g->d_in + (size_t)m * g->cap_bytes);
+    h.d_out = s.device ? (float *)s.out : (float *)(g->d_out + (size_t)m * g->out_cap_bytes);
+    h.positions = pg; h.gains = pg + 3 * (size_t)hrtf_group_channels(g->hrtf, m);
+    subs.push_back(h);
+    if (!s.device) {
+      const size_t in_bytes = s.n * (size_t)hrtf_group_channels(g->hrtf, m) * 4;
+      if (in_bytes > max_in) max_in = in_bytes;
+      if (s.n * 8 > max_out) max_out = s.n * 8;
+    }
+  }
+  if (subs.empty()) return MI355_OK;
+  hipStream_t st = g->ctx->stream;
+  int rc = MI355_OK;
+  std::vector<std::pair<int, int>> runs;   // [first, last] member of each run (never across the slot of a member that is not part of this set)
+  for (const HrtfSubmit &h : subs) {
+    if (g->sub[h.member].device) continue;
+    if (!runs.empty() && runs.back().second == h.member - 1) runs.back().second = h.member;
+    else runs.push_back({h.member, h.member});
+  }
+  if (max_in > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->d_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, g->h_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, max_in,
+                                         (size_t)(r.second - r.first + 1), hipMemcpyHostToDevice, st), "agroup hrtf: upload"))) return rc;
+  std::string err;
+  if ((rc = hrtf_group_run(g->hrtf, st, subs.data(), (int)subs.size(), &err))) return afail(g, rc, err);
+  if (max_out > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->h_out + (size_t)r.first * g->out_cap_bytes, g->out_cap_bytes, g->d_out + (size_t)r.first * g->out_cap_bytes, g->out_cap_bytes,
+                                         max_out, (size_t)(r.second - r.first + 1), hipMemcpyDeviceToHost, st), "agroup hrtf: download"))) return rc;
+  return ahip(g, hipStreamSynchronize(st), "agroup hrtf: sync");
+}
+
 // runs the collected interval. g->mu held (the members are blocked on it or on the condition variable anyway).
 void run_interval(mi355_agroup *g) {
   (void)hipSetDevice(g->device);
@@ -464,6 +521,7 @@ void run_interval(mi355_agroup *g) {
   if (g->kind == KIND_ECHO) rc = run_echo(g);
   else if (g->kind == KIND_EBUR128) rc = run_ebur128(g);
   else if (g->kind == KIND_AGING) rc = run_aging(g);
+  else if (g->kind == KIND_HRTF) rc = run_hrtf(g);
   else rc = run_loudnorm(g);
   uint64_t carried = 0;
   for (int m = 0; m < g->n_members; m++) {
@@ -610,6 +668,7 @@ void mi355_agroup_destroy(mi355_agroup *g) {
     if (A.d_state) (void)hipFree(A.d_state);
   if (g->d_ajobs) (void)hipFree(g->d_ajobs);
   if (g->h_ajobs) (void)hipHostFree(g->h_ajobs);
+  hrtf_group_free(g->hrtf);
   if (g->ctx) mi355_ctx_destroy(g->ctx);   // releases the ebur128 / loudnorm batch engines with it
   delete g;
 }
@@ -772,6 +831,18 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
       }
     }
     g->res_pending[(size_t)member] = 0;
+  } else if (g->kind == KIND_HRTF) {
+    if (!s.device && frames && s.out) {
+      const char *src = g->h_out + (size_t)member * g->out_cap_bytes;
+      void *dst = s.out;
+      g->copying++;   // (a block is tens of KB: copied outside the lock, the slab pinned in place by the count)
+      lk.unlock();
+      std::memcpy(dst, src, frames * 8);
+      lk.lock();
+      g->copying--;
+      g->cv.notify_all();
+    }
+    g->res_pending[(size_t)member] = 0;
   } else if (g->kind == KIND_LOUDNORM) {
     if (frames > s.out_cap) return afail(g, MI355_ERR_INVALID_ARG, "audioloudnorm: output buffer too small");
     if (!s.device && frames && s.out) {
@@ -914,6 +985,111 @@ int mi355_agroup_agingradio_get_state(mi355_agroup *g, int member, double *filte
   return MI355_OK;
 }
 
+// ---- hrtfrender members (HrtfRender, audio/hrtf/src/hrtf/imp.rs)
+mi355_agroup *mi355_agroup_create_hrtf(int device, int n_members, int *status) {
+  mi355_agroup *g = agroup_new(device, KIND_HRTF, n_members, status);
+  if (!g) return nullptr;
+  int rc = MI355_OK;
+  g->hrtf = hrtf_group_new(n_members, &g->last_error, &rc);
+  g->hrtf_pg.assign((size_t)n_members * 256, 0.0f);
+  if (!g->hrtf) { if (status) *status = rc; mi355_agroup_destroy(g); return nullptr; }
+  if (status) *status = MI355_OK;
+  return g;
+}
+
+// Settings::sphere -> HrirSphere::new(bytes, rate) of one member (imp.rs:84-94). Its processors go (set_caps builds them anew).
+int mi355_agroup_hrtf_load_sphere(mi355_agroup *g, int member, const void *bytes, size_t len, uint32_t device_rate) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_HRTF, member);
+  if (rc) return rc;
+  if (!bytes) return afail(g, MI355_ERR_INVALID_ARG, "hrtfrender: null argument");
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if ((rc = hrtf_group_load_sphere(g->hrtf, member, (const unsigned char *)bytes, len, device_rate, &err))) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// set_caps of one member (imp.rs:648-707): one HrtfProcessor per channel; method = what MI355_FLAG_HRTF_METHOD is for a lone context
+int mi355_agroup_hrtf_setup(mi355_agroup *g, int member, int channels, int block_length, int interpolation_steps, int method) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_HRTF, member);
+  if (rc) return rc;
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if ((rc = hrtf_group_setup(g->hrtf, member, channels, block_length, interpolation_steps, method, &err))) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// State::reset_processors of one member (imp.rs:124-129): tails cleared, previous vectors and gains kept; on the group's stream, so
+// after the member's last launch set and before its next. Not while the member has a block pending.
+int mi355_agroup_hrtf_reset(mi355_agroup *g, int member) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_HRTF, member);
+  if (rc) return rc;
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if ((rc = hrtf_group_reset(g->hrtf, member, g->ctx->stream, &err))) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// One block of one member (HrtfRender::process, imp.rs:164-278): in [S*B][C], out [S*B][2], positions [C][3] and gains [C] (host,
+// copied here). wait() answers the frames rendered.
+int mi355_agroup_submit_hrtf(mi355_agroup *g, int member, const float *in, float *out, const float *positions_xyz, const float *distance_gains,
+                             int device_data, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_HRTF, member);
+  if (rc) return rc;
+  if (!in || !out || !positions_xyz || !distance_gains) return afail(g, MI355_ERR_INVALID_ARG, "hrtfrender: null argument");
+  if (!hrtf_group_configured(g->hrtf, member)) return afail(g, MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)");
+  (void)hipSetDevice(g->device);
+  const size_t C = (size_t)hrtf_group_channels(g->hrtf, member), frames = hrtf_group_frames(g->hrtf, member);
+  float *pg = g->hrtf_pg.data() + (size_t)member * 256;
+  std::memcpy(pg, positions_xyz, C * 12);
+  std::memcpy(pg + 3 * C, distance_gains, C * 4);
+  Sub &s = g->sub[member];
+  s.device = device_data != 0; s.data = (void *)in; s.out = out; s.n = frames;
+  void *dst = nullptr;
+  size_t bytes = 0;
+  if (!s.device) {
+    bytes = frames * C * 4;
+    if ((rc = ensure_staging(g, lk, bytes, frames * 8))) return rc;
+    dst = g->h_in + (size_t)member * g->cap_bytes;
+  }
+  submitted(g, lk, member, ticket, dst, in, bytes);
+  return MI355_OK;
+}
+
+int mi355_agroup_hrtf_info(mi355_agroup *g, int member, uint32_t *hrir_len, int *fft_n, int *spheres_held) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  if (g->kind != KIND_HRTF || member < 0 || member >= g->n_members) return afail(g, MI355_ERR_INVALID_ARG, "agroup: bad member");
+  std::string err;
+  if (int rc = hrtf_group_info(g->hrtf, member, hrir_len, fft_n, spheres_held, &err)) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// diagnostics: faces [C][S] / weights [C][S][3] of the member's last block (what mi355_hrtf_last_lookup is for a lone context)
+int mi355_agroup_hrtf_last_lookup(mi355_agroup *g, int member, int *faces, float *uvw) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  if (g->kind != KIND_HRTF || member < 0 || member >= g->n_members) return afail(g, MI355_ERR_INVALID_ARG, "agroup: bad member");
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if (int rc = hrtf_group_last_lookup(g->hrtf, member, g->ctx->stream, faces, uvw, &err)) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// kernel launches the group's hrtfrender launch sets have made so far (3 per set of uniform members; measurement plumbing)
+uint64_t mi355_agroup_hrtf_launches(mi355_agroup *g) {
+  if (!g || g->kind != KIND_HRTF) return 0;
+  std::lock_guard<std::mutex> lk(g->mu);
+  return hrtf_group_launches(g->hrtf);
+}
+
 int mi355_agroup_stats(mi355_agroup *g, uint64_t stats[3]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
@@ -1040,6 +1216,10 @@ int mi355_agroup_loudnorm_drain(mi355_agroup *g, int member, double *out, size_t
 mi355_agroup *mi355_agroup_shared_agingradio(int device, int n_members, int *member, int *status) {
   return shared_get(key_of("agingradio", device, n_members, nullptr, 0), n_members, member, status,
                     [&] { return mi355_agroup_create_agingradio(device, n_members, status); });
+}
+
+mi355_agroup *mi355_agroup_shared_hrtf(int device, int n_members, int *member, int *status) {
+  return shared_get(key_of("hrtf", device, n_members, nullptr, 0), n_members, member, status, [&] { return mi355_agroup_create_hrtf(device, n_members, status); });
 }
 
 void mi355_agroup_release(mi355_agroup *g, int member) {

@@ -27,17 +27,25 @@
 
 #include <cmath>
 #include <cstring>
+#include <mutex>
+#include <string>
 #include <vector>
 
 namespace mi355 {
 
-struct HrtfState {
-  // sphere (HrirSphere, crate file format)
+// one HrirSphere on the device (crate file format, resampled to the device rate at load). A lone context owns its sphere; the
+// members of an hrtf agroup that load the same bytes at the same rate share one (refs counts them).
+struct HrtfSphere {
   uint32_t rate = 0, len = 0, n_vertices = 0, n_faces = 0;
   float *d_pos = nullptr;      // [V][3]
   uint32_t *d_idx = nullptr;   // [F][3]
   float *d_hrir = nullptr;     // [V][2][len]
-  bool sphere_loaded = false;
+  int refs = 1;
+  std::vector<unsigned char> bytes;   // what it was made from (groups only: the key of the sharing)
+};
+
+struct HrtfState {
+  HrtfSphere *sphere = nullptr;
   // processors (HrtfProcessor::new per channel, imp.rs:662-680)
   int channels = 0, steps = 0, block_len = 0;
   bool configured = false;
@@ -50,7 +58,7 @@ struct HrtfState {
   int *d_face = nullptr;         // [C][S] face index or -1 (diagnostics/tests)
   float *d_uvw = nullptr;        // [C][S][3]
   float *d_partial = nullptr;    // [C][frames][2]
-  float *d_in = nullptr, *d_out = nullptr;  // staging for the host entry point
+  float *d_in = nullptr, *d_out = nullptr;  // staging for the host entry point (a lone context's; group members use the group's slabs)
   std::vector<float> prev_vec, prev_gain;
   std::vector<unsigned char> have_prev;
 };
@@ -92,18 +100,17 @@ __device__ __forceinline__ bool ray_face(V3 dir, V3 a, V3 b, V3 c, float &u, flo
 // previous / new direction and gain of every channel, passed by value in the kernel arguments (<= 64 channels: 2 KiB)
 struct HrtfVecGain { float v[8 * 64]; };  // prev_vec[C][3], new_vec[C][3], prev_gain[C], new_gain[C] with C = channels
 
-// One block per channel.
-__global__ __launch_bounds__(256) void hrtf_prepare_kernel(const float *__restrict__ in, int C, int S, int B, int L,
-                                                           const float *__restrict__ pos, const uint32_t *__restrict__ idx, int F,
-                                                           const float *__restrict__ hrir, HrtfVecGain VG,
-                                                           const float *__restrict__ x_old, float *__restrict__ x_new,
-                                                           float *__restrict__ taps, float *__restrict__ last_taps,
-                                                           float *__restrict__ gain, int *__restrict__ face_out, float *__restrict__ uvw_out) {
-  const int c = blockIdx.x;
+// The three steps as __device__ bodies: the lone kernels below and the job-table kernels of an hrtf agroup (further down) call the
+// SAME code with the same per-sample operation order, so a member's bits are a lone context's (tests/golden/hrtf_lone_crc.json pins
+// the lone path's at the commit before the bodies were shared).
+//
+// One block per channel c of one instance.
+__device__ __forceinline__ void hrtf_prepare_body(const float *__restrict__ in, int C, int S, int B, int L, const float *__restrict__ pos,
+                                                  const uint32_t *__restrict__ idx, int F, const float *__restrict__ hrir, const float pv[3],
+                                                  const float nv[3], float pg, float ng, const float *__restrict__ x_old, float *__restrict__ x_new,
+                                                  float *__restrict__ taps, float *__restrict__ last_taps, float *__restrict__ gain,
+                                                  int *__restrict__ face_out, float *__restrict__ uvw_out, int c) {
   const int frames = S * B, pad = L - 1;
-  const float pv[3] = {VG.v[3 * c], VG.v[3 * c + 1], VG.v[3 * c + 2]};
-  const float nv[3] = {VG.v[3 * C + 3 * c], VG.v[3 * C + 3 * c + 1], VG.v[3 * C + 3 * c + 2]};
-  const float pg = VG.v[6 * C + c], ng = VG.v[7 * C + c];
   __shared__ int s_face[64];
   __shared__ float s_uvw[64][3];
   // ---- mesh lookup: one wave-sized group of lanes per step scans the faces in file order; the FIRST hit wins
@@ -160,13 +167,23 @@ __global__ __launch_bounds__(256) void hrtf_prepare_kernel(const float *__restri
   for (int i = threadIdx.x; i < frames; i += blockDim.x) x_new[c * row + pad + i] = in[(size_t)i * C + c];
 }
 
+// One block per channel.
+__global__ __launch_bounds__(256) void hrtf_prepare_kernel(const float *__restrict__ in, int C, int S, int B, int L,
+                                                           const float *__restrict__ pos, const uint32_t *__restrict__ idx, int F,
+                                                           const float *__restrict__ hrir, HrtfVecGain VG,
+                                                           const float *__restrict__ x_old, float *__restrict__ x_new,
+                                                           float *__restrict__ taps, float *__restrict__ last_taps,
+                                                           float *__restrict__ gain, int *__restrict__ face_out, float *__restrict__ uvw_out) {
+  const int c = blockIdx.x;
+  const float pv[3] = {VG.v[3 * c], VG.v[3 * c + 1], VG.v[3 * c + 2]};
+  const float nv[3] = {VG.v[3 * C + 3 * c], VG.v[3 * C + 3 * c + 1], VG.v[3 * C + 3 * c + 2]};
+  const float pg = VG.v[6 * C + c], ng = VG.v[7 * C + c];
+  hrtf_prepare_body(in, C, S, B, L, pos, idx, F, hrir, pv, nv, pg, ng, x_old, x_new, taps, last_taps, gain, face_out, uvw_out, c);
+}
+
 // grid (S * tiles, C); block 256; dynamic LDS: [T + pad] input + [2][L] taps
-__global__ __launch_bounds__(256) void hrtf_fir_kernel(const float *__restrict__ x, const float *__restrict__ taps,
-                                                       const float *__restrict__ gain, float *__restrict__ partial, int S, int B,
-                                                       int L, int T, int tiles) {
-  extern __shared__ float sm[];
-  const int c = blockIdx.y;
-  const int s = blockIdx.x / tiles, tile = blockIdx.x - s * tiles;
+__device__ __forceinline__ void hrtf_fir_body(float *sm, const float *__restrict__ x, const float *__restrict__ taps, const float *__restrict__ gain,
+                                              float *__restrict__ partial, int S, int B, int L, int T, int c, int s, int tile) {
   const int pad = L - 1, frames = S * B;
   const int n0 = s * B + tile * T;                 // first output frame of this tile
   const int n1 = min(n0 + T, (s + 1) * B);         // end (exclusive)
@@ -192,6 +209,14 @@ __global__ __launch_bounds__(256) void hrtf_fir_kernel(const float *__restrict__
   }
 }
 
+__global__ __launch_bounds__(256) void hrtf_fir_kernel(const float *__restrict__ x, const float *__restrict__ taps,
+                                                       const float *__restrict__ gain, float *__restrict__ partial, int S, int B,
+                                                       int L, int T, int tiles) {
+  extern __shared__ float sm[];
+  const int s = blockIdx.x / tiles;
+  hrtf_fir_body(sm, x, taps, gain, partial, S, B, L, T, blockIdx.y, s, blockIdx.x - s * tiles);
+}
+
 // ---- overlap-save FFT form. grid (S, C); block 256; dynamic LDS: X[N], Z[N], twiddles[N/2] (float2)
 __device__ __forceinline__ float2 hrtf_cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ int hrtf_bitrev(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
@@ -213,11 +238,9 @@ __device__ __forceinline__ void hrtf_fft_lds(float2 *buf, const float2 *tw, int 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void hrtf_fft_kernel(const float *__restrict__ x, const float *__restrict__ taps, const float *__restrict__ gain,
-                                                       float *__restrict__ partial, int S, int B, int L, int N, int logN) {
-  extern __shared__ float2 hsm[];
+__device__ __forceinline__ void hrtf_fft_body(float2 *hsm, const float *__restrict__ x, const float *__restrict__ taps, const float *__restrict__ gain,
+                                              float *__restrict__ partial, int S, int B, int L, int N, int logN, int s, int c) {
   float2 *X = hsm, *Z = hsm + N, *tw = hsm + 2 * N;
-  const int s = blockIdx.x, c = blockIdx.y;
   const int pad = L - 1, frames = S * B, W = pad + B;  // window: x[n0 - pad .. n0 + B), n0 = s * B; row index of frame n is pad + n
   const float *xrow = x + (size_t)c * (pad + frames) + (size_t)s * B;
   const float *tp = taps + ((size_t)c * S + s) * 2 * L;
@@ -256,9 +279,14 @@ __global__ __launch_bounds__(256) void hrtf_fft_kernel(const float *__restrict__
   }
 }
 
+__global__ __launch_bounds__(256) void hrtf_fft_kernel(const float *__restrict__ x, const float *__restrict__ taps, const float *__restrict__ gain,
+                                                       float *__restrict__ partial, int S, int B, int L, int N, int logN) {
+  extern __shared__ float2 hsm[];
+  hrtf_fft_body(hsm, x, taps, gain, partial, S, B, L, N, logN, blockIdx.x, blockIdx.y);
+}
+
 // out[n] = ((0 + ch0) + ch1) + ...   (imp.rs:186 zero fill, :256-268 accumulation order)
-__global__ __launch_bounds__(256) void hrtf_mix_kernel(const float *__restrict__ partial, float *__restrict__ out, int C, int frames) {
-  const int i = blockIdx.x * 256 + threadIdx.x;  // index into [frames][2]
+__device__ __forceinline__ void hrtf_mix_body(const float *__restrict__ partial, float *__restrict__ out, int C, int frames, int i) {
   if (i >= 2 * frames) return;
   float acc = 0.0f;
   int c = 0;
@@ -273,7 +301,70 @@ __global__ __launch_bounds__(256) void hrtf_mix_kernel(const float *__restrict__
   out[i] = acc;
 }
 
+__global__ __launch_bounds__(256) void hrtf_mix_kernel(const float *__restrict__ partial, float *__restrict__ out, int C, int frames) {
+  hrtf_mix_body(partial, out, C, frames, blockIdx.x * 256 + threadIdx.x);  // index into [frames][2]
+}
+
+// ------------------------------------------------------------------ the job-table form (hrtf agroups, agroup.hip)
+// Independent hrtfrender instances - own sphere, channel count, block-length, interpolation-steps, HRIR length and convolution
+// form each - in ONE launch set. Two tables travel per set: one entry per member that has submitted (geometry, sphere, state,
+// in / out) and one row per (member, channel) with the row's previous / new direction and gain (what HrtfVecGain carries by value
+// for a lone context: 8 x 64 floats of kernel arguments cannot hold a set).
+struct HrtfJobMember {
+  const float *in; float *out;
+  const float *pos; const uint32_t *idx; const float *hrir;
+  const float *x_old; float *x_new;
+  float *taps, *last_taps, *gain, *uvw, *partial;
+  int *face;
+  int C, S, B, L, F, N, logN, T, tiles, pad_;
+};
+struct HrtfJobRow { int member, c; float pv[3], nv[3], pg, ng; };
+
+// grid (rows)
+__global__ __launch_bounds__(256) void hrtf_prepare_jobs_kernel(const HrtfJobMember *__restrict__ members, const HrtfJobRow *__restrict__ rows) {
+  const HrtfJobRow R = rows[blockIdx.x];
+  const HrtfJobMember M = members[R.member];
+  hrtf_prepare_body(M.in, M.C, M.S, M.B, M.L, M.pos, M.idx, M.F, M.hrir, R.pv, R.nv, R.pg, R.ng, M.x_old, M.x_new, M.taps, M.last_taps, M.gain, M.face,
+                    M.uvw, R.c);
+}
+
+// grid (rows * ny), ny = max S * tiles of the FIR members; a block whose row is served by a transform, or that lies beyond its member's
+// steps x tiles, leaves at once (as a whole: nobody is left at a barrier). Dynamic LDS: the largest [T + pad] + [2][L] of the set.
+__global__ __launch_bounds__(256) void hrtf_fir_jobs_kernel(const HrtfJobMember *__restrict__ members, const HrtfJobRow *__restrict__ rows, int ny) {
+  extern __shared__ float sm[];
+  const int row = blockIdx.x / ny, y = blockIdx.x - row * ny;
+  const HrtfJobRow R = rows[row];
+  const HrtfJobMember M = members[R.member];
+  if (M.N != 0 || y >= M.S * M.tiles) return;
+  const int s = y / M.tiles;
+  hrtf_fir_body(sm, M.x_new, M.taps, M.gain, M.partial, M.S, M.B, M.L, M.T, R.c, s, y - s * M.tiles);
+}
+
+// grid (rows * ny), ny = max S of the members on transform size N; one launch per distinct N in the set. Dynamic LDS: X[N], Z[N], twiddles[N/2].
+__global__ __launch_bounds__(256) void hrtf_fft_jobs_kernel(const HrtfJobMember *__restrict__ members, const HrtfJobRow *__restrict__ rows, int N, int ny) {
+  extern __shared__ float2 hsm[];
+  const int row = blockIdx.x / ny, y = blockIdx.x - row * ny;
+  const HrtfJobRow R = rows[row];
+  const HrtfJobMember M = members[R.member];
+  if (M.N != N || y >= M.S) return;
+  hrtf_fft_body(hsm, M.x_new, M.taps, M.gain, M.partial, M.S, M.B, M.L, M.N, M.logN, y, R.c);
+}
+
+// grid (blocks of the longest output, members)
+__global__ __launch_bounds__(256) void hrtf_mix_jobs_kernel(const HrtfJobMember *__restrict__ members) {
+  const HrtfJobMember M = members[blockIdx.y];
+  hrtf_mix_body(M.partial, M.out, M.C, M.S * M.B, blockIdx.x * 256 + threadIdx.x);
+}
+
 // ------------------------------------------------------------------ host side
+
+static int hrtf_hip(hipError_t e, const char *what, std::string *err) {
+  if (e == hipSuccess) return MI355_OK;
+  (void)hipGetLastError();
+  *err = std::string(what) + ": " + hipGetErrorString(e);
+  return e == hipErrorOutOfMemory ? MI355_ERR_OUT_OF_MEMORY : MI355_ERR_HIP;
+}
+static int hrtf_fail(int status, const char *msg, std::string *err) { *err = msg; return status; }
 
 static void hrtf_free_processors(HrtfState *H) {
   for (int i = 0; i < 2; i++) { if (H->d_x[i]) (void)hipFree(H->d_x[i]); H->d_x[i] = nullptr; }
@@ -284,13 +375,19 @@ static void hrtf_free_processors(HrtfState *H) {
   H->configured = false;
 }
 
+static void hrtf_sphere_unref(HrtfSphere *S) {
+  if (!S || --S->refs > 0) return;
+  if (S->d_pos) (void)hipFree(S->d_pos);
+  if (S->d_idx) (void)hipFree(S->d_idx);
+  if (S->d_hrir) (void)hipFree(S->d_hrir);
+  delete S;
+}
+
 void hrtf_release(mi355_ctx *ctx) {
   HrtfState *H = hrtf_of(ctx);
   if (!H) return;
   hrtf_free_processors(H);
-  if (H->d_pos) (void)hipFree(H->d_pos);
-  if (H->d_idx) (void)hipFree(H->d_idx);
-  if (H->d_hrir) (void)hipFree(H->d_hrir);
+  hrtf_sphere_unref(H->sphere);
   delete H;
   ctx->hrtf = nullptr;
 }
@@ -327,13 +424,14 @@ static std::vector<float> resample_hrir(const float *h, uint32_t len, double rat
   return y;
 }
 
-int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate) {
-  if (!bytes || n < 20 || std::memcmp(bytes, "HRIR", 4) != 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: not an HRIR sphere (bad magic)");
+// HrirSphere::new(bytes, device_rate) (imp.rs:84-94): parsed, resampled where the rates differ, uploaded. *out is a new sphere with one reference.
+static int hrtf_sphere_create(const unsigned char *bytes, size_t n, uint32_t device_rate, HrtfSphere **out, std::string *err) {
+  if (!bytes || n < 20 || std::memcmp(bytes, "HRIR", 4) != 0) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: not an HRIR sphere (bad magic)", err);
   const uint32_t rate = rd_u32(bytes + 4), file_len = rd_u32(bytes + 8), nv = rd_u32(bytes + 12), ni = rd_u32(bytes + 16);
-  if (file_len == 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: HRIR length is zero");
+  if (file_len == 0) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: HRIR length is zero", err);
   const size_t need = 20 + 4 * (size_t)ni + (size_t)nv * (12 + 8 * (size_t)file_len);
-  if (n < need) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: truncated HRIR sphere");
-  if (rate == 0 || device_rate == 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: zero sample rate");
+  if (n < need) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: truncated HRIR sphere", err);
+  if (rate == 0 || device_rate == 0) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: zero sample rate", err);
   const bool resample = rate != device_rate;
   const double ratio = (double)device_rate / (double)rate;
   uint32_t len = file_len;
@@ -344,7 +442,7 @@ int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint3
   std::vector<uint32_t> idx(ni);
   for (uint32_t i = 0; i < ni; i++) {
     idx[i] = rd_u32(bytes + 20 + 4 * (size_t)i);
-    if (idx[i] >= nv) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: face index out of range");
+    if (idx[i] >= nv) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: face index out of range", err);
   }
   std::vector<float> pos((size_t)nv * 3), hr((size_t)nv * 2 * len);
   size_t off = 20 + 4 * (size_t)ni;
@@ -363,56 +461,70 @@ int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint3
     }
     off += 8 * (size_t)file_len;
   }
-  HrtfState *H = hrtf_of(ctx);
-  if (!H) { H = new HrtfState(); ctx->hrtf = H; }
-  hrtf_free_processors(H);
-  if (H->d_pos) (void)hipFree(H->d_pos);
-  if (H->d_idx) (void)hipFree(H->d_idx);
-  if (H->d_hrir) (void)hipFree(H->d_hrir);
-  H->d_pos = nullptr; H->d_idx = nullptr; H->d_hrir = nullptr; H->sphere_loaded = false;
+  HrtfSphere *S = new HrtfSphere();
   int rc;
-  if ((rc = check_hip(ctx, hipMalloc(&H->d_pos, pos.size() * 4 + 4), "hipMalloc(hrir positions)"))) return rc;
-  if ((rc = check_hip(ctx, hipMalloc(&H->d_idx, idx.size() * 4 + 4), "hipMalloc(hrir indices)"))) return rc;
-  if ((rc = check_hip(ctx, hipMalloc(&H->d_hrir, hr.size() * 4 + 4), "hipMalloc(hrir data)"))) return rc;
-  if ((rc = check_hip(ctx, hipMemcpy(H->d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice), "upload hrir positions"))) return rc;
-  if (!idx.empty() && (rc = check_hip(ctx, hipMemcpy(H->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice), "upload hrir indices"))) return rc;
-  if ((rc = check_hip(ctx, hipMemcpy(H->d_hrir, hr.data(), hr.size() * 4, hipMemcpyHostToDevice), "upload hrir data"))) return rc;
-  H->rate = device_rate; H->len = len; H->n_vertices = nv; H->n_faces = ni / 3;
-  H->sphere_loaded = true;
+  if ((rc = hrtf_hip(hipMalloc(&S->d_pos, pos.size() * 4 + 4), "hipMalloc(hrir positions)", err)) ||
+      (rc = hrtf_hip(hipMalloc(&S->d_idx, idx.size() * 4 + 4), "hipMalloc(hrir indices)", err)) ||
+      (rc = hrtf_hip(hipMalloc(&S->d_hrir, hr.size() * 4 + 4), "hipMalloc(hrir data)", err)) ||
+      (rc = hrtf_hip(hipMemcpy(S->d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice), "upload hrir positions", err)) ||
+      (!idx.empty() && (rc = hrtf_hip(hipMemcpy(S->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice), "upload hrir indices", err))) ||
+      (rc = hrtf_hip(hipMemcpy(S->d_hrir, hr.data(), hr.size() * 4, hipMemcpyHostToDevice), "upload hrir data", err))) {
+    hrtf_sphere_unref(S);
+    return rc;
+  }
+  S->rate = device_rate; S->len = len; S->n_vertices = nv; S->n_faces = ni / 3;
+  *out = S;
   return MI355_OK;
 }
 
-int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps) {
+int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate) {
+  std::string err;
+  HrtfSphere *S = nullptr;
+  // (a load that fails in its checks leaves what was loaded before untouched; one that fails on the device leaves no sphere)
+  int rc = hrtf_sphere_create(bytes, n, device_rate, &S, &err);
+  if (rc == MI355_ERR_INVALID_ARG) return set_error(ctx, rc, err);
   HrtfState *H = hrtf_of(ctx);
-  if (!H || !H->sphere_loaded) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set");
-  if (channels < 1 || block_len < 1 || steps < 1 || steps > 64) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: bad channels/block-length/interpolation-steps");
-  if ((size_t)block_len * (size_t)steps > (1u << 24)) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: block too large");
+  if (!H) { H = new HrtfState(); ctx->hrtf = H; }
   hrtf_free_processors(H);
-  const size_t L = H->len, pad = L - 1, frames = (size_t)block_len * steps, C = (size_t)channels, S = (size_t)steps;
+  hrtf_sphere_unref(H->sphere);
+  H->sphere = S;
+  if (rc) return set_error(ctx, rc, err);
+  return MI355_OK;
+}
+
+// HrtfProcessor::new per channel (imp.rs:662-680) for one instance: `method` is MI355_FLAG_HRTF_METHOD's value
+static int hrtf_state_setup(HrtfState *H, int method, int channels, int block_len, int steps, bool own_staging, std::string *err) {
+  if (!H || !H->sphere) return hrtf_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set", err);
+  // (channels above 64: the element's caps stop there, and HrtfVecGain holds 64 channels' directions and gains)
+  if (channels < 1 || channels > 64 || block_len < 1 || steps < 1 || steps > 64) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: bad channels/block-length/interpolation-steps", err);
+  if ((size_t)block_len * (size_t)steps > (1u << 24)) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: block too large", err);
+  hrtf_free_processors(H);
+  const size_t L = H->sphere->len, pad = L - 1, frames = (size_t)block_len * steps, C = (size_t)channels, S = (size_t)steps;
   const size_t T = block_len < 1024 ? (size_t)block_len : 1024;
   // overlap-save transform size: the next power of two that holds the window [L-1 | block]; X, Z and the twiddles fit the LDS up to 4096
   int fft_n = 1, fft_log = 0;
   while ((size_t)fft_n < (size_t)block_len + pad) { fft_n <<= 1; fft_log++; }
   const bool fft_fits = fft_n <= 4096 && fft_n >= 512;
   const bool fir_fits = (T + pad + 2 * L) * 4 <= 160 * 1024;
-  if (!fft_fits && !fir_fits) return set_error(ctx, MI355_ERR_UNSUPPORTED, "hrtfrender: HRIR too long for the LDS (block + HRIR length above 4096 and FIR tile above 160 KB)");
+  if (!fft_fits && !fir_fits) return hrtf_fail(MI355_ERR_UNSUPPORTED, "hrtfrender: HRIR too long for the LDS (block + HRIR length above 4096 and FIR tile above 160 KB)", err);
   // method: 1 = FFT, 2 = FIR pinned; 0 = FFT from kHrtfFftMinTaps taps on, FIR below
   // measured, 64 sources, block 512 x 8 (ms per block, FFT / FIR): 64 taps 0.040 / 0.030, 256: 0.042 / 0.040, 512: 0.047 / 0.056,
   // 1024: 0.072 / 0.087, 2048: 0.128 / 0.156 (tools/bench_hrtf.py --method 1 / 2, r03)
   constexpr size_t kHrtfFftMinTaps = 384;
-  const bool use_fft = fft_fits && (ctx->hrtf_method == 1 || !fir_fits || (ctx->hrtf_method == 0 && L >= kHrtfFftMinTaps));
+  const bool use_fft = fft_fits && (method == 1 || !fir_fits || (method == 0 && L >= kHrtfFftMinTaps));
   int rc;
   for (int i = 0; i < 2; i++) {
-    if ((rc = check_hip(ctx, hipMalloc(&H->d_x[i], C * (pad + frames) * 4 + 4), "hipMalloc(hrtf input rows)"))) return rc;
-    if ((rc = check_hip(ctx, hipMemset(H->d_x[i], 0, C * (pad + frames) * 4), "hipMemset(hrtf input rows)"))) return rc;
+    if ((rc = hrtf_hip(hipMalloc(&H->d_x[i], C * (pad + frames) * 4 + 4), "hipMalloc(hrtf input rows)", err))) return rc;
+    if ((rc = hrtf_hip(hipMemset(H->d_x[i], 0, C * (pad + frames) * 4), "hipMemset(hrtf input rows)", err))) return rc;
   }
   struct { float **p; size_t n; } bufs[] = {{&H->d_taps, C * S * 2 * L}, {&H->d_last_taps, C * 2 * L}, {&H->d_gain, C * S}, {&H->d_uvw, C * S * 3},
                                             {&H->d_partial, C * frames * 2}, {&H->d_in, frames * C}, {&H->d_out, frames * 2}};
   for (auto &b : bufs) {
-    if ((rc = check_hip(ctx, hipMalloc(b.p, b.n * 4 + 4), "hipMalloc(hrtf state)"))) return rc;
-    if ((rc = check_hip(ctx, hipMemset(*b.p, 0, b.n * 4), "hipMemset(hrtf state)"))) return rc;
+    if (!own_staging && (b.p == &H->d_in || b.p == &H->d_out)) continue;
+    if ((rc = hrtf_hip(hipMalloc(b.p, b.n * 4 + 4), "hipMalloc(hrtf state)", err))) return rc;
+    if ((rc = hrtf_hip(hipMemset(*b.p, 0, b.n * 4), "hipMemset(hrtf state)", err))) return rc;
   }
-  if ((rc = check_hip(ctx, hipMalloc(&H->d_face, C * S * 4 + 4), "hipMalloc(hrtf faces)"))) return rc;
+  if ((rc = hrtf_hip(hipMalloc(&H->d_face, C * S * 4 + 4), "hipMalloc(hrtf faces)", err))) return rc;
   H->channels = channels; H->steps = steps; H->block_len = block_len; H->cur = 0;
   H->fft_n = use_fft ? fft_n : 0; H->fft_log = use_fft ? fft_log : 0;
   H->prev_vec.assign(C * 3, 0.0f); H->prev_gain.assign(C, 0.0f); H->have_prev.assign(C, 0);
@@ -420,16 +532,45 @@ int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps) {
   return MI355_OK;
 }
 
+int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps) {
+  std::string err;
+  const int rc = hrtf_state_setup(hrtf_of(ctx), ctx->hrtf_method, channels, block_len, steps, true, &err);
+  return rc ? set_error(ctx, rc, err) : MI355_OK;
+}
+
 // State::reset_processors (imp.rs:124-129): tails cleared, previous vectors/gains kept
-int hrtf_reset(mi355_ctx *ctx) {
-  HrtfState *H = hrtf_of(ctx);
+static int hrtf_state_reset(HrtfState *H, hipStream_t stream, std::string *err) {
   if (!H || !H->configured) return MI355_OK;
-  const size_t row = (size_t)H->len - 1 + (size_t)H->block_len * H->steps;
+  const size_t row = (size_t)H->sphere->len - 1 + (size_t)H->block_len * H->steps;
   for (int i = 0; i < 2; i++) {
-    int rc = check_hip(ctx, hipMemsetAsync(H->d_x[i], 0, (size_t)H->channels * row * 4, ctx->stream), "hipMemset(hrtf tails)");
+    int rc = hrtf_hip(hipMemsetAsync(H->d_x[i], 0, (size_t)H->channels * row * 4, stream), "hipMemset(hrtf tails)", err);
     if (rc) return rc;
   }
   return MI355_OK;
+}
+
+int hrtf_reset(mi355_ctx *ctx) {
+  std::string err;
+  const int rc = hrtf_state_reset(hrtf_of(ctx), ctx->stream, &err);
+  return rc ? set_error(ctx, rc, err) : MI355_OK;
+}
+
+// prev_sample_vector.unwrap_or(new) (imp.rs:236): the row's previous / new direction and gain for this block
+static void hrtf_prev_new(const HrtfState *H, int c, const float *positions, const float *gains, float pv[3], float nv[3], float *pg, float *ng) {
+  const float *n = positions + 3 * c;
+  const float *p = H->have_prev[c] ? &H->prev_vec[3 * c] : n;
+  for (int j = 0; j < 3; j++) { pv[j] = p[j]; nv[j] = n[j]; }
+  *pg = H->have_prev[c] ? H->prev_gain[c] : gains[c];
+  *ng = gains[c];
+}
+
+static void hrtf_advance(HrtfState *H, const float *positions, const float *gains) {
+  H->cur ^= 1;
+  for (int c = 0; c < H->channels; c++) {
+    for (int j = 0; j < 3; j++) H->prev_vec[3 * c + j] = positions[3 * c + j];
+    H->prev_gain[c] = gains[c];
+    H->have_prev[c] = 1;
+  }
 }
 
 // One block; d_in [frames][C] and d_out [frames][2] are device pointers. positions [C][3] right-handed (what the
@@ -437,18 +578,17 @@ int hrtf_reset(mi355_ctx *ctx) {
 int hrtf_process_block_device(mi355_ctx *ctx, const float *d_in, float *d_out, const float *positions, const float *gains) {
   HrtfState *H = hrtf_of(ctx);
   if (!H || !H->configured) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)");
-  const int C = H->channels, S = H->steps, B = H->block_len, L = (int)H->len, frames = S * B;
+  const HrtfSphere *Sp = H->sphere;
+  const int C = H->channels, S = H->steps, B = H->block_len, L = (int)Sp->len, frames = S * B;
   HrtfVecGain vg;
   for (int c = 0; c < C; c++) {
-    const float *nv = positions + 3 * c;
-    const float *pv = H->have_prev[c] ? &H->prev_vec[3 * c] : nv;  // prev_sample_vector.unwrap_or(new) (imp.rs:236)
+    float pv[3], nv[3];
+    hrtf_prev_new(H, c, positions, gains, pv, nv, &vg.v[6 * C + c], &vg.v[7 * C + c]);
     for (int j = 0; j < 3; j++) { vg.v[3 * c + j] = pv[j]; vg.v[3 * C + 3 * c + j] = nv[j]; }
-    vg.v[6 * C + c] = H->have_prev[c] ? H->prev_gain[c] : gains[c];
-    vg.v[7 * C + c] = gains[c];
   }
   float *x_old = H->d_x[H->cur], *x_new = H->d_x[H->cur ^ 1];
-  hipLaunchKernelGGL(hrtf_prepare_kernel, dim3(C), dim3(256), 0, ctx->stream, d_in, C, S, B, L, (const float *)H->d_pos, (const uint32_t *)H->d_idx,
-                     (int)H->n_faces, (const float *)H->d_hrir, vg, (const float *)x_old, x_new, H->d_taps, H->d_last_taps,
+  hipLaunchKernelGGL(hrtf_prepare_kernel, dim3(C), dim3(256), 0, ctx->stream, d_in, C, S, B, L, (const float *)Sp->d_pos, (const uint32_t *)Sp->d_idx,
+                     (int)Sp->n_faces, (const float *)Sp->d_hrir, vg, (const float *)x_old, x_new, H->d_taps, H->d_last_taps,
                      H->d_gain, H->d_face, H->d_uvw);
   int rc;
   if (H->fft_n) {
@@ -466,12 +606,7 @@ int hrtf_process_block_device(mi355_ctx *ctx, const float *d_in, float *d_out, c
   hipLaunchKernelGGL(hrtf_mix_kernel, dim3((2 * frames + 255) / 256), dim3(256), 0, ctx->stream, (const float *)H->d_partial, d_out, C, frames);
   rc = check_hip(ctx, hipGetLastError(), "hrtf kernel launch");
   if (rc) return rc;
-  H->cur ^= 1;
-  for (int c = 0; c < C; c++) {
-    for (int j = 0; j < 3; j++) H->prev_vec[3 * c + j] = positions[3 * c + j];
-    H->prev_gain[c] = gains[c];
-    H->have_prev[c] = 1;
-  }
+  hrtf_advance(H, positions, gains);
   return MI355_OK;
 }
 
@@ -488,24 +623,29 @@ int hrtf_process_block_host(mi355_ctx *ctx, const float *in, float *out, const f
   return check_hip(ctx, hipStreamSynchronize(ctx->stream), "hrtf sync");
 }
 
+static int hrtf_state_last_lookup(HrtfState *H, hipStream_t stream, int *faces, float *uvw, std::string *err) {
+  if (!H || !H->configured) return hrtf_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)", err);
+  const size_t n = (size_t)H->channels * H->steps;
+  int rc = hrtf_hip(hipStreamSynchronize(stream), "hrtf sync", err);
+  if (rc) return rc;
+  if (faces && (rc = hrtf_hip(hipMemcpy(faces, H->d_face, n * 4, hipMemcpyDeviceToHost), "hrtf faces D2H", err))) return rc;
+  if (uvw && (rc = hrtf_hip(hipMemcpy(uvw, H->d_uvw, n * 12, hipMemcpyDeviceToHost), "hrtf uvw D2H", err))) return rc;
+  return MI355_OK;
+}
+
 // diagnostics: faces / weights chosen for the last block (tests compare the mesh search with the oracle's)
 int hrtf_last_lookup(mi355_ctx *ctx, int *faces, float *uvw) {
-  HrtfState *H = hrtf_of(ctx);
-  if (!H || !H->configured) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)");
-  const size_t n = (size_t)H->channels * H->steps;
-  int rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "hrtf sync");
-  if (rc) return rc;
-  if (faces && (rc = check_hip(ctx, hipMemcpy(faces, H->d_face, n * 4, hipMemcpyDeviceToHost), "hrtf faces D2H"))) return rc;
-  if (uvw && (rc = check_hip(ctx, hipMemcpy(uvw, H->d_uvw, n * 12, hipMemcpyDeviceToHost), "hrtf uvw D2H"))) return rc;
-  return MI355_OK;
+  std::string err;
+  const int rc = hrtf_state_last_lookup(hrtf_of(ctx), ctx->stream, faces, uvw, &err);
+  return rc ? set_error(ctx, rc, err) : MI355_OK;
 }
 
 int hrtf_info(mi355_ctx *ctx, uint32_t *len, uint32_t *vertices, uint32_t *faces) {
   HrtfState *H = hrtf_of(ctx);
-  if (!H || !H->sphere_loaded) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set");
-  if (len) *len = H->len;
-  if (vertices) *vertices = H->n_vertices;
-  if (faces) *faces = H->n_faces;
+  if (!H || !H->sphere) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set");
+  if (len) *len = H->sphere->len;
+  if (vertices) *vertices = H->sphere->n_vertices;
+  if (faces) *faces = H->sphere->n_faces;
   return MI355_OK;
 }
 
@@ -515,6 +655,190 @@ int hrtf_transform_size(mi355_ctx *ctx, int *fft_n) {
   if (!H || !H->configured) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)");
   if (!fft_n) return set_error(ctx, MI355_ERR_INVALID_ARG, "hrtfrender: null output");
   *fft_n = H->fft_n;
+  return MI355_OK;
+}
+
+// ------------------------------------------------------------------ the members of one hrtf agroup
+// The dispatcher (agroup.hip) collects the submissions and owns the stream and the staging slabs; what an hrtfrender instance IS -
+// its sphere, its processors, its previous directions - lives here, next to the lone context's.
+struct HrtfGroup {
+  std::vector<HrtfState> members;
+  std::vector<HrtfSphere *> spheres;      // the distinct spheres the group keeps on the device
+  // the tables of the launch set: pinned block + device block ([members of the set][rows of the set]); ev: the previous set's
+  // tables have left the pinned block
+  char *h_tab = nullptr, *d_tab = nullptr;
+  size_t row_cap = 0;
+  hipEvent_t ev = nullptr;
+  uint64_t n_launches = 0;
+};
+
+static size_t hrtf_rows_offset(const HrtfGroup *G) { return (G->members.size() * sizeof(HrtfJobMember) + 15) & ~(size_t)15; }
+
+HrtfGroup *hrtf_group_new(int n_members, std::string *err, int *status) {
+  HrtfGroup *G = new HrtfGroup();
+  G->members.resize((size_t)n_members);
+  *status = hrtf_hip(hipEventCreateWithFlags(&G->ev, hipEventDisableTiming), "hipEventCreate(hrtf group)", err);
+  if (*status) { delete G; return nullptr; }
+  return G;
+}
+
+void hrtf_group_free(HrtfGroup *G) {
+  if (!G) return;
+  for (HrtfState &H : G->members) { hrtf_free_processors(&H); hrtf_sphere_unref(H.sphere); H.sphere = nullptr; }
+  if (G->h_tab) (void)hipHostFree(G->h_tab);
+  if (G->d_tab) (void)hipFree(G->d_tab);
+  if (G->ev) (void)hipEventDestroy(G->ev);
+  delete G;
+}
+
+static void hrtf_group_drop_sphere(HrtfGroup *G, HrtfState *H) {
+  HrtfSphere *S = H->sphere;
+  H->sphere = nullptr;
+  if (!S) return;
+  if (S->refs == 1)
+    for (size_t i = 0; i < G->spheres.size(); i++)
+      if (G->spheres[i] == S) { G->spheres.erase(G->spheres.begin() + (std::ptrdiff_t)i); break; }
+  hrtf_sphere_unref(S);
+}
+
+// Members that load identical bytes at the same device rate share ONE device copy; the parse and the windowed-sinc resampling
+// run once per distinct (bytes, rate). (The caller has ordered this after the member's last launch set.)
+int hrtf_group_load_sphere(HrtfGroup *G, int m, const unsigned char *bytes, size_t n, uint32_t device_rate, std::string *err) {
+  HrtfState *H = &G->members[(size_t)m];
+  HrtfSphere *S = nullptr;
+  if (bytes)
+    for (HrtfSphere *s : G->spheres)
+      if (s->rate == device_rate && s->bytes.size() == n && std::memcmp(s->bytes.data(), bytes, n) == 0) { S = s; break; }
+  if (S) {
+    S->refs++;
+  } else {
+    const int rc = hrtf_sphere_create(bytes, n, device_rate, &S, err);
+    if (rc == MI355_ERR_INVALID_ARG) return rc;   // (what was loaded before stays, as for a lone context)
+    if (rc) { hrtf_free_processors(H); hrtf_group_drop_sphere(G, H); return rc; }
+    S->bytes.assign(bytes, bytes + n);
+    G->spheres.push_back(S);
+  }
+  hrtf_free_processors(H);
+  hrtf_group_drop_sphere(G, H);
+  H->sphere = S;
+  return MI355_OK;
+}
+
+int hrtf_group_setup(HrtfGroup *G, int m, int channels, int block_len, int steps, int method, std::string *err) {
+  if (method < 0 || method > 2) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: method is 0 (by HRIR length), 1 (FFT) or 2 (FIR)", err);
+  return hrtf_state_setup(&G->members[(size_t)m], method, channels, block_len, steps, false, err);
+}
+
+int hrtf_group_reset(HrtfGroup *G, int m, hipStream_t stream, std::string *err) { return hrtf_state_reset(&G->members[(size_t)m], stream, err); }
+
+bool hrtf_group_configured(const HrtfGroup *G, int m) { return G->members[(size_t)m].configured; }
+bool hrtf_group_has_sphere(const HrtfGroup *G, int m) { return G->members[(size_t)m].sphere != nullptr; }
+int hrtf_group_channels(const HrtfGroup *G, int m) { return G->members[(size_t)m].channels; }
+size_t hrtf_group_frames(const HrtfGroup *G, int m) { const HrtfState &H = G->members[(size_t)m]; return (size_t)H.steps * H.block_len; }
+uint64_t hrtf_group_launches(const HrtfGroup *G) { return G->n_launches; }
+
+int hrtf_group_info(HrtfGroup *G, int m, uint32_t *hrir_len, int *fft_n, int *spheres_held, std::string *err) {
+  const HrtfState &H = G->members[(size_t)m];
+  if (!H.sphere) return hrtf_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set", err);
+  if (hrir_len) *hrir_len = H.sphere->len;
+  if (fft_n) *fft_n = H.configured ? H.fft_n : -1;
+  if (spheres_held) *spheres_held = (int)G->spheres.size();
+  return MI355_OK;
+}
+
+int hrtf_group_last_lookup(HrtfGroup *G, int m, hipStream_t stream, int *faces, float *uvw, std::string *err) {
+  return hrtf_state_last_lookup(&G->members[(size_t)m], stream, faces, uvw, err);
+}
+
+// the largest dynamic LDS a job kernel has been allowed so far (the attribute belongs to the function, not to a group)
+static std::mutex g_hrtf_attr_mu;
+static size_t g_hrtf_fir_lds = 0, g_hrtf_fft_lds = 0;
+
+static int hrtf_allow_lds(const void *fn, size_t *allowed, size_t lds, const char *what, std::string *err) {
+  std::lock_guard<std::mutex> lk(g_hrtf_attr_mu);
+  if (lds <= *allowed) return MI355_OK;
+  const int rc = hrtf_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), what, err);
+  if (!rc) *allowed = lds;
+  return rc;
+}
+
+// ONE launch set for the members in subs[0..n): tables up, prepare, at most one convolution launch per distinct transform size plus
+// one for the FIR rows, mix. Enqueued on `stream`; nothing is waited for but the pinned table block of the previous set.
+int hrtf_group_run(HrtfGroup *G, hipStream_t stream, const HrtfSubmit *subs, int n, std::string *err) {
+  if (n <= 0) return MI355_OK;
+  size_t n_rows = 0;
+  for (int j = 0; j < n; j++) n_rows += (size_t)G->members[(size_t)subs[j].member].channels;
+  const size_t rows_off = hrtf_rows_offset(G);
+  int rc;
+  if (n_rows > G->row_cap) {
+    if ((rc = hrtf_hip(hipStreamSynchronize(stream), "hrtf group: sync", err))) return rc;
+    if (G->h_tab) (void)hipHostFree(G->h_tab);
+    if (G->d_tab) (void)hipFree(G->d_tab);
+    G->h_tab = G->d_tab = nullptr; G->row_cap = 0;
+    size_t cap = 64;
+    while (cap < n_rows) cap *= 2;
+    const size_t bytes = rows_off + cap * sizeof(HrtfJobRow);
+    if ((rc = hrtf_hip(hipHostMalloc((void **)&G->h_tab, bytes, hipHostMallocDefault), "hipHostMalloc(hrtf group tables)", err))) return rc;
+    if ((rc = hrtf_hip(hipMalloc((void **)&G->d_tab, bytes), "hipMalloc(hrtf group tables)", err))) return rc;
+    G->row_cap = cap;
+  }
+  if ((rc = hrtf_hip(hipEventSynchronize(G->ev), "hipEventSynchronize(hrtf group tables)", err))) return rc;
+  HrtfJobMember *hm = (HrtfJobMember *)G->h_tab;
+  HrtfJobRow *hr = (HrtfJobRow *)(G->h_tab + rows_off);
+  size_t r = 0, fir_lds = 0;
+  int fir_y = 0, mix_x = 0;
+  int fft_sizes[4] = {0, 0, 0, 0}, fft_y[4] = {0, 0, 0, 0}, n_fft = 0;   // 512, 1024, 2048, 4096 at the most
+  for (int j = 0; j < n; j++) {
+    HrtfState &H = G->members[(size_t)subs[j].member];
+    const HrtfSphere *Sp = H.sphere;
+    HrtfJobMember &M = hm[j];
+    M.in = subs[j].d_in; M.out = subs[j].d_out;
+    M.pos = Sp->d_pos; M.idx = Sp->d_idx; M.hrir = Sp->d_hrir;
+    M.x_old = H.d_x[H.cur]; M.x_new = H.d_x[H.cur ^ 1];
+    M.taps = H.d_taps; M.last_taps = H.d_last_taps; M.gain = H.d_gain; M.uvw = H.d_uvw; M.partial = H.d_partial; M.face = H.d_face;
+    M.C = H.channels; M.S = H.steps; M.B = H.block_len; M.L = (int)Sp->len; M.F = (int)Sp->n_faces; M.N = H.fft_n; M.logN = H.fft_log;
+    M.T = H.block_len < 1024 ? H.block_len : 1024; M.tiles = (H.block_len + M.T - 1) / M.T; M.pad_ = 0;
+    for (int c = 0; c < H.channels; c++, r++) {
+      HrtfJobRow &R = hr[r];
+      R.member = j; R.c = c;
+      hrtf_prev_new(&H, c, subs[j].positions, subs[j].gains, R.pv, R.nv, &R.pg, &R.ng);
+    }
+    if (H.fft_n) {
+      int k = 0;
+      while (k < n_fft && fft_sizes[k] != H.fft_n) k++;
+      if (k == n_fft) fft_sizes[n_fft++] = H.fft_n;
+      if (H.steps > fft_y[k]) fft_y[k] = H.steps;
+    } else {
+      const size_t lds = (size_t)(M.T + (M.L - 1) + 2 * M.L) * 4;
+      if (lds > fir_lds) fir_lds = lds;
+      if (M.S * M.tiles > fir_y) fir_y = M.S * M.tiles;
+    }
+    const int mx = (2 * M.S * M.B + 255) / 256;
+    if (mx > mix_x) mix_x = mx;
+  }
+  const HrtfJobMember *dm = (const HrtfJobMember *)G->d_tab;
+  const HrtfJobRow *dr = (const HrtfJobRow *)(G->d_tab + rows_off);
+  // (two copies, each of what this set fills: the member entries end where the rows' fixed offset begins only in a full group)
+  if ((rc = hrtf_hip(hipMemcpyAsync(G->d_tab, G->h_tab, (size_t)n * sizeof(HrtfJobMember), hipMemcpyHostToDevice, stream), "hrtf group: member table", err))) return rc;
+  if ((rc = hrtf_hip(hipMemcpyAsync(G->d_tab + rows_off, G->h_tab + rows_off, n_rows * sizeof(HrtfJobRow), hipMemcpyHostToDevice, stream), "hrtf group: row table", err))) return rc;
+  if ((rc = hrtf_hip(hipEventRecord(G->ev, stream), "hipEventRecord(hrtf group tables)", err))) return rc;
+  hipLaunchKernelGGL(hrtf_prepare_jobs_kernel, dim3((unsigned)n_rows), dim3(256), 0, stream, dm, dr);
+  G->n_launches++;
+  for (int k = 0; k < n_fft; k++) {
+    const size_t lds = (size_t)(2 * fft_sizes[k] + fft_sizes[k] / 2) * sizeof(float2);
+    if ((rc = hrtf_allow_lds((const void *)hrtf_fft_jobs_kernel, &g_hrtf_fft_lds, lds, "hipFuncSetAttribute(hrtf group fft LDS)", err))) return rc;
+    hipLaunchKernelGGL(hrtf_fft_jobs_kernel, dim3((unsigned)(n_rows * (size_t)fft_y[k])), dim3(256), lds, stream, dm, dr, fft_sizes[k], fft_y[k]);
+    G->n_launches++;
+  }
+  if (fir_y) {
+    if ((rc = hrtf_allow_lds((const void *)hrtf_fir_jobs_kernel, &g_hrtf_fir_lds, fir_lds, "hipFuncSetAttribute(hrtf group fir LDS)", err))) return rc;
+    hipLaunchKernelGGL(hrtf_fir_jobs_kernel, dim3((unsigned)(n_rows * (size_t)fir_y)), dim3(256), fir_lds, stream, dm, dr, fir_y);
+    G->n_launches++;
+  }
+  hipLaunchKernelGGL(hrtf_mix_jobs_kernel, dim3((unsigned)mix_x, (unsigned)n), dim3(256), 0, stream, dm);
+  G->n_launches++;
+  if ((rc = hrtf_hip(hipGetLastError(), "hrtf group kernel launch", err))) return rc;
+  for (int j = 0; j < n; j++) hrtf_advance(&G->members[(size_t)subs[j].member], subs[j].positions, subs[j].gains);
   return MI355_OK;
 }
 

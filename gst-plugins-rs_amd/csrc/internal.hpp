@@ -253,6 +253,22 @@ int hrtf_process_block_host(mi355_ctx *ctx, const float *in, float *out, const f
 int hrtf_last_lookup(mi355_ctx *ctx, int *faces, float *uvw);
 int hrtf_info(mi355_ctx *ctx, uint32_t *len, uint32_t *vertices, uint32_t *faces);
 int hrtf_transform_size(mi355_ctx *ctx, int *fft_n);
+// the members of one hrtf agroup (hrtf_kernels.hip): spheres shared by content, one HrtfState per member, the job tables of a launch set
+struct HrtfGroup;
+struct HrtfSubmit { int member; const float *d_in; float *d_out; const float *positions, *gains; };   // positions [C][3], gains [C]: host
+HrtfGroup *hrtf_group_new(int n_members, std::string *err, int *status);
+void hrtf_group_free(HrtfGroup *G);
+int hrtf_group_load_sphere(HrtfGroup *G, int m, const unsigned char *bytes, size_t n, uint32_t device_rate, std::string *err);
+int hrtf_group_setup(HrtfGroup *G, int m, int channels, int block_len, int steps, int method, std::string *err);
+int hrtf_group_reset(HrtfGroup *G, int m, hipStream_t stream, std::string *err);
+bool hrtf_group_configured(const HrtfGroup *G, int m);
+bool hrtf_group_has_sphere(const HrtfGroup *G, int m);
+int hrtf_group_channels(const HrtfGroup *G, int m);
+size_t hrtf_group_frames(const HrtfGroup *G, int m);
+uint64_t hrtf_group_launches(const HrtfGroup *G);
+int hrtf_group_info(HrtfGroup *G, int m, uint32_t *hrir_len, int *fft_n, int *spheres_held, std::string *err);
+int hrtf_group_last_lookup(HrtfGroup *G, int m, hipStream_t stream, int *faces, float *uvw, std::string *err);
+int hrtf_group_run(HrtfGroup *G, hipStream_t stream, const HrtfSubmit *subs, int n, std::string *err);
 int sofa_setup(mi355_ctx *ctx, int channels, int filter_len, int partition_len, int block_len);
 int sofa_set_filter(mi355_ctx *ctx, int channel, const float *left, const float *right, int delay_left, int delay_right);
 int sofa_set_drop(mi355_ctx *ctx, int channel, int drop);

@@ -252,6 +252,15 @@ def load_library():
         "mi355_hrtf_sphere_info": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "mi355_hrtf_transform_size": (i, [vp, C.POINTER(C.c_int)]),
         "mi355_hrtf_last_lookup": (i, [vp, C.POINTER(C.c_int), f32p]),
+        "mi355_agroup_create_hrtf": (vp, [i, i, C.POINTER(C.c_int)]),
+        "mi355_agroup_shared_hrtf": (vp, [i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mi355_agroup_hrtf_load_sphere": (i, [vp, i, vp, sz, C.c_uint32]),
+        "mi355_agroup_hrtf_setup": (i, [vp, i, i, i, i, i]),
+        "mi355_agroup_hrtf_reset": (i, [vp, i]),
+        "mi355_agroup_submit_hrtf": (i, [vp, i, vp, vp, f32p, f32p, i, C.POINTER(C.c_uint64)]),
+        "mi355_agroup_hrtf_info": (i, [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mi355_agroup_hrtf_last_lookup": (i, [vp, i, C.POINTER(C.c_int), f32p]),
+        "mi355_agroup_hrtf_launches": (C.c_uint64, [vp]),
         "mi355_time_hsvfilter_device": (i, [vp, u8p, i, sz, i, i, i, i, C.POINTER(HsvSettings), i, f32p]),
         "mi355_time_hsv_colorlut_device": (i, [vp, u8p, sz, i, u8p, sz, i, i, i, i, C.POINTER(HsvSettings), i, f32p]),
         "mi355_time_colorlut_device": (i, [vp, u8p, sz, i, u8p, sz, i, i, i, i, i, i, f32p]),
@@ -456,6 +465,8 @@ class AudioGroup:
                 self.h = self.L.mi355_agroup_shared_echo(device, n_members, kw["ring_len"], C.byref(m), C.byref(st))
             elif kind == "agingradio":
                 self.h = self.L.mi355_agroup_shared_agingradio(device, n_members, C.byref(m), C.byref(st))
+            elif kind == "hrtf":
+                self.h = self.L.mi355_agroup_shared_hrtf(device, n_members, C.byref(m), C.byref(st))
             elif kind == "ebur128":
                 cc = kw.get("channel_class")
                 arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -472,6 +483,8 @@ class AudioGroup:
             self.h = self.L.mi355_agroup_create_echo(device, n_members, kw["ring_len"], C.byref(st))
         elif kind == "agingradio":
             self.h = self.L.mi355_agroup_create_agingradio(device, n_members, C.byref(st))
+        elif kind == "hrtf":
+            self.h = self.L.mi355_agroup_create_hrtf(device, n_members, C.byref(st))
         elif kind == "ebur128":
             cc = kw.get("channel_class")
             arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -531,6 +544,63 @@ class AudioGroup:
         k = C.c_uint64(0)
         self._ck(self.L.mi355_agroup_agingradio_get_state(self.h, member, y.ctypes.data_as(C.POINTER(C.c_double)), channels, C.byref(k)))
         return y[:channels], int(k.value)
+
+    # ---- hrtfrender members
+    def hrtf_load_sphere(self, member, data, rate):
+        """HrirSphere::new(bytes, rate) of one member; identical bytes at the same rate are kept once on the device"""
+        b = bytes(data)
+        buf = (C.c_uint8 * len(b)).from_buffer_copy(b)
+        self._ck(self.L.mi355_agroup_hrtf_load_sphere(self.h, member, C.cast(buf, C.c_void_p), len(b), rate))
+
+    def hrtf_setup(self, member, channels, block_length=512, interpolation_steps=8, method=0):
+        """set_caps of one member; method as FLAG_HRTF_METHOD of a lone Context (0 by HRIR length, 1 FFT, 2 FIR)"""
+        self._ck(self.L.mi355_agroup_hrtf_setup(self.h, member, channels, block_length, interpolation_steps, method))
+        if not hasattr(self, "_hrtf_shape"):
+            self._hrtf_shape = {}
+        self._hrtf_shape[member] = (channels, block_length * interpolation_steps, interpolation_steps)
+
+    def hrtf_reset(self, member):
+        """State::reset_processors of one member: tails cleared, previous directions and gains kept"""
+        self._ck(self.L.mi355_agroup_hrtf_reset(self.h, member))
+
+    def submit_hrtf(self, member, inp, positions, gains, out=None):
+        """One block. inp: numpy f32 [frames, channels] (host; -> ticket, and the f32 [frames * 2] output array is hrtf_output(member)
+        once the ticket has been waited for) or a device pointer (then out: the device pointer of the output)."""
+        channels, frames, _ = self._hrtf_shape[member]
+        fp = C.POINTER(C.c_float)
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1)
+        g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        assert pos.size == 3 * channels and g.size == channels
+        t = C.c_uint64(0)
+        if isinstance(inp, np.ndarray):
+            x = np.ascontiguousarray(inp, dtype=np.float32).reshape(-1)
+            assert x.size == frames * channels, "one block = block_length*interpolation_steps frames"
+            y = np.zeros(frames * 2, np.float32)
+            self._keep[member] = (x, y)
+            self._ck(self.L.mi355_agroup_submit_hrtf(self.h, member, x.ctypes.data, y.ctypes.data, pos.ctypes.data_as(fp), g.ctypes.data_as(fp), 0, C.byref(t)))
+        else:
+            self._ck(self.L.mi355_agroup_submit_hrtf(self.h, member, inp, out, pos.ctypes.data_as(fp), g.ctypes.data_as(fp), 1, C.byref(t)))
+        return t.value
+
+    def hrtf_output(self, member):
+        """the output array of the member's last host submission (filled by wait)"""
+        return self._keep[member][1]
+
+    def hrtf_info(self, member):
+        """(HRIR length, transform size: 0 = FIR, -1 before setup, distinct spheres the group holds on the device)"""
+        a, n, k = C.c_uint32(0), C.c_int(-1), C.c_int(0)
+        self._ck(self.L.mi355_agroup_hrtf_info(self.h, member, C.byref(a), C.byref(n), C.byref(k)))
+        return a.value, n.value, k.value
+
+    def hrtf_last_lookup(self, member):
+        channels, _, steps = self._hrtf_shape[member]
+        faces = np.zeros(channels * steps, np.int32)
+        uvw = np.zeros(channels * steps * 3, np.float32)
+        self._ck(self.L.mi355_agroup_hrtf_last_lookup(self.h, member, faces.ctypes.data_as(C.POINTER(C.c_int)), uvw.ctypes.data_as(C.POINTER(C.c_float))))
+        return faces.reshape(channels, steps), uvw.reshape(channels, steps, 3)
+
+    def hrtf_launches(self):
+        return int(self.L.mi355_agroup_hrtf_launches(self.h))
 
     def submit_ebur128(self, member, data, frames=None, sample_format=None):
         t = C.c_uint64(0)

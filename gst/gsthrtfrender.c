@@ -7,11 +7,14 @@
  * set_caps :648-707 (positions -> objects when none are set :660-672, sphere from raw bytes or file, block_samples =
  * block-length x interpolation-steps), sink_event :710-736 (flush-stop empties, EOS drains :281-352), stop :748-753.
  * HrtfProcessor::process_samples over every channel (the `hrtf` crate: interpolated HRIR lookup + block convolution +
- * overlap tails) is mi355_hrtf_process_block; `use-rayon` is accepted and means nothing here: the channels are the grid. */
+ * overlap tails) is mi355_hrtf_process_block; `use-rayon` is accepted and means nothing here: the channels are the grid.
+ * MI355_GROUP_MEMBERS=n: this process hosts n renderers (one per listener); they share launch sets through the process-wide
+ * mi355_agroup (include/mi355fx.h: mi355_agroup_shared_hrtf) instead of three launches and a round trip each. */
 #include <gst/gst.h>
 #include <gst/audio/audio.h>
 #include <gst/base/gstbasetransform.h>
 #include <gst/base/gstadapter.h>
+#include <stdlib.h>
 #include "../include/mi355fx.h"
 #include "../gst-plugins-rs_amd/host/mi355fx_host.h"
 
@@ -44,6 +47,8 @@ struct _GstHrtfRender {
   gsize block_samples;
   GstAdapter *adapter;
   mi355_ctx *ctx;
+  mi355_agroup *agroup; /* MI355_GROUP_MEMBERS: the shared group and this element's member of it */
+  int member;
 };
 
 G_DEFINE_TYPE(GstHrtfRender, gst_hrtf_render, GST_TYPE_BASE_TRANSFORM)
@@ -158,6 +163,8 @@ static gboolean gst_hrtf_render_stop(GstBaseTransform *trans) {
   self->have_state = FALSE;
   g_mutex_unlock(&self->lock);
   gst_adapter_clear(self->adapter);
+  if (self->agroup) mi355_agroup_release(self->agroup, self->member);
+  self->agroup = NULL;
   if (self->ctx) {
     (void)mi355_hrtf_teardown(self->ctx);
     mi355_ctx_destroy(self->ctx);
@@ -222,15 +229,28 @@ static gboolean gst_hrtf_render_set_caps(GstBaseTransform *trans, GstCaps *incap
     if (self->hrir_raw) bytes = g_bytes_get_data(self->hrir_raw, &len);
     else if (self->hrir_file && g_file_get_contents(self->hrir_file, &file_bytes, &len, NULL)) bytes = file_bytes;
     if (!bytes) { GST_ERROR_OBJECT(self, "Failed to load sphere: %s", self->hrir_file ? "cannot read hrir-file" : "Impulse response not set"); break; }
-    const int rc = mi355_hrtf_load_sphere(self->ctx, bytes, len, (uint32_t)rate);
+    const char *members = g_getenv("MI355_GROUP_MEMBERS");
+    if (!self->agroup && members && atoi(members) >= 2) {
+      int status = 0;
+      self->agroup = mi355_agroup_shared_hrtf(0, atoi(members), &self->member, &status);
+      if (!self->agroup) GST_WARNING_OBJECT(self, "no shared hrtfrender group (%s): own launches", mi355_status_string(status));
+      else (void)mi355_agroup_set_linger(self->agroup, g_getenv("MI355_GROUP_LINGER_US") ? (unsigned)atoi(g_getenv("MI355_GROUP_LINGER_US")) : 2000u, 0); /* a paused neighbour costs the others 2 ms, never a hang */
+    }
+    const int rc = self->agroup ? mi355_agroup_hrtf_load_sphere(self->agroup, self->member, bytes, len, (uint32_t)rate)
+                                : mi355_hrtf_load_sphere(self->ctx, bytes, len, (uint32_t)rate);
     g_free(file_bytes);
-    if (rc != MI355_OK) { GST_ERROR_OBJECT(self, "Failed to load sphere: %s", mi355_ctx_last_error(self->ctx)); break; }
+    if (rc != MI355_OK) { GST_ERROR_OBJECT(self, "Failed to load sphere: %s", self->agroup ? mi355_agroup_last_error(self->agroup) : mi355_ctx_last_error(self->ctx)); break; }
     guint64 bs = 0;
     if (!g_uint64_checked_mul(&bs, self->block_length, self->interpolation_steps) || bs == 0 || bs > (1u << 24)) { /* checked_mul (imp.rs:655-657) */
       GST_ERROR_OBJECT(self, "Not enough memory for frame allocation");
       break;
     }
-    if (mi355_hrtf_setup(self->ctx, channels, (int)self->block_length, (int)self->interpolation_steps) != MI355_OK) {
+    if (self->agroup) { /* the member's processors; method 0: the form is chosen by HRIR length, as a lone context's is */
+      if (mi355_agroup_hrtf_setup(self->agroup, self->member, channels, (int)self->block_length, (int)self->interpolation_steps, 0) != MI355_OK) {
+        GST_ERROR_OBJECT(self, "mi355_agroup_hrtf_setup: %s", mi355_agroup_last_error(self->agroup));
+        break;
+      }
+    } else if (mi355_hrtf_setup(self->ctx, channels, (int)self->block_length, (int)self->interpolation_steps) != MI355_OK) {
       GST_ERROR_OBJECT(self, "mi355_hrtf_setup: %s", mi355_ctx_last_error(self->ctx));
       break;
     }
@@ -267,10 +287,17 @@ static gssize gst_hrtf_render_process(GstHrtfRender *self, gfloat *out, gsize ou
   gsize written = 0;
   while (gst_adapter_available(self->adapter) >= inblk && written + outblk <= out_bytes) {
     const gfloat *in = (const gfloat *)gst_adapter_map(self->adapter, inblk);
-    const int rc = mi355_hrtf_process_block(self->ctx, in, out + written / sizeof(gfloat), pos, gains);
+    int rc;
+    if (self->agroup) { /* this block joins the launch set of the interval; the call returns when it has run */
+      uint64_t ticket = 0;
+      rc = mi355_agroup_submit_hrtf(self->agroup, self->member, in, out + written / sizeof(gfloat), pos, gains, 0, &ticket);
+      if (rc == MI355_OK) rc = mi355_agroup_wait(self->agroup, ticket, NULL);
+    } else {
+      rc = mi355_hrtf_process_block(self->ctx, in, out + written / sizeof(gfloat), pos, gains);
+    }
     gst_adapter_unmap(self->adapter);
     if (rc != MI355_OK) {
-      GST_ERROR_OBJECT(self, "mi355_hrtf_process_block: %s", mi355_ctx_last_error(self->ctx));
+      GST_ERROR_OBJECT(self, "mi355_hrtf_process_block: %s", self->agroup ? mi355_agroup_last_error(self->agroup) : mi355_ctx_last_error(self->ctx));
       return -1;
     }
     gst_adapter_flush(self->adapter, inblk);
@@ -311,7 +338,8 @@ static GstFlowReturn gst_hrtf_render_drain(GstHrtfRender *self) {
   gst_buffer_unmap(out, &map);
   if (n < 0) { gst_buffer_unref(out); return GST_FLOW_ERROR; }
   gst_buffer_set_size(out, outputsz);
-  (void)mi355_hrtf_reset(self->ctx); /* state.reset_processors() */
+  if (self->agroup) (void)mi355_agroup_hrtf_reset(self->agroup, self->member); /* state.reset_processors() */
+  else (void)mi355_hrtf_reset(self->ctx);
   return gst_pad_push(GST_BASE_TRANSFORM_SRC_PAD(self), out);
 }
 
@@ -321,7 +349,8 @@ static gboolean gst_hrtf_render_sink_event(GstBaseTransform *trans, GstEvent *ev
   switch (GST_EVENT_TYPE(event)) {
     case GST_EVENT_FLUSH_STOP:
       gst_adapter_clear(self->adapter);
-      if (self->have_state) (void)mi355_hrtf_reset(self->ctx);
+      if (self->have_state && self->agroup) (void)mi355_agroup_hrtf_reset(self->agroup, self->member);
+      else if (self->have_state) (void)mi355_hrtf_reset(self->ctx);
       break;
     case GST_EVENT_EOS:
       if (gst_hrtf_render_drain(self) != GST_FLOW_OK) GST_ELEMENT_WARNING(self, CORE, EVENT, ("Failed to drain internal buffer"), (NULL));

@@ -581,6 +581,35 @@ int mi355_hrtf_sphere_info(mi355_ctx *ctx, uint32_t *hrir_len, uint32_t *n_verti
 int mi355_hrtf_transform_size(mi355_ctx *ctx, int *fft_n);
 /* Diagnostics: mesh face (or -1) and barycentric weights chosen per [channel][step] in the last block. */
 int mi355_hrtf_last_lookup(mi355_ctx *ctx, int *faces, float *uvw);
+/* hrtfrender through an audio group (csrc/agroup.hip; audio/hrtf/src/hrtf/imp.rs): members are fully independent instances, as echo
+ * and agingradio members are - own sphere, channel count (1..64), block-length, interpolation-steps, HRIR length and convolution
+ * form each - and whoever has submitted a block shares ONE launch set (prepare, at most one convolution launch per transform size
+ * present plus one for the time-domain rows, mix), one upload and one download. A member's output is a lone context's, bit for bit.
+ *   mi355_agroup_hrtf_load_sphere : Settings::sphere -> HrirSphere::new(bytes, rate) of one member (imp.rs:84-94). Members that
+ *       load identical bytes at the same device rate share ONE device copy (parsed and resampled once, reference-counted).
+ *   mi355_agroup_hrtf_setup : set_caps' ChannelProcessor vector of one member (imp.rs:648-707, :662-680). `method` is what
+ *       MI355_FLAG_HRTF_METHOD is for a lone context (0 by HRIR length, 1 FFT, 2 FIR). Before a sphere: MI355_ERR_NOT_CONFIGURED;
+ *       channels outside 1..64: MI355_ERR_INVALID_ARG (mi355_hrtf_setup answers the same above 64).
+ *   mi355_agroup_hrtf_reset : State::reset_processors of one member (imp.rs:124-129): tails cleared, previous vectors and gains
+ *       kept; ordered after the member's last launch set.
+ *   mi355_agroup_submit_hrtf : one block (HrtfRender::process, imp.rs:164-278): `in` [S*B][C] f32, `out` [S*B][2] f32 (valid after
+ *       mi355_agroup_wait, which answers the frames rendered), positions [C][3] (imp.rs:64-73) and gains [C], both copied at submit;
+ *       device_data = 1: `in` / `out` are device pointers. Before setup: MI355_ERR_NOT_CONFIGURED.
+ *   mi355_agroup_hrtf_info : the member's HRIR length (imp.rs:84-94, after the resampling), the transform size its setup chose
+ *       (0: the time-domain FIR; -1 before setup) and the number of distinct spheres the group keeps on the device.
+ *   mi355_agroup_hrtf_last_lookup : as mi355_hrtf_last_lookup, for one member (the crate's mesh search behind imp.rs:236-252).
+ *   mi355_agroup_hrtf_launches : kernel launches of the group's launch sets so far (imp.rs:164-278 per member and block: three per
+ *       set of uniform members instead of three per member). */
+mi355_agroup *mi355_agroup_create_hrtf(int device, int n_members, int *status);
+mi355_agroup *mi355_agroup_shared_hrtf(int device, int n_members, int *member, int *status);
+int mi355_agroup_hrtf_load_sphere(mi355_agroup *group, int member, const void *bytes, size_t len, uint32_t device_rate);
+int mi355_agroup_hrtf_setup(mi355_agroup *group, int member, int channels, int block_length, int interpolation_steps, int method);
+int mi355_agroup_hrtf_reset(mi355_agroup *group, int member);
+int mi355_agroup_submit_hrtf(mi355_agroup *group, int member, const float *in, float *out, const float *positions_xyz,
+                             const float *distance_gains, int device_data, uint64_t *ticket);
+int mi355_agroup_hrtf_info(mi355_agroup *group, int member, uint32_t *hrir_len, int *fft_n, int *spheres_held);
+int mi355_agroup_hrtf_last_lookup(mi355_agroup *group, int member, int *faces, float *uvw);
+uint64_t mi355_agroup_hrtf_launches(mi355_agroup *group);
 
 /* ---------------------------------------------------------------- sofalizer
  * Replaces the per-block loop of Sofalizer::process (audio/hrtf/src/sofa/imp.rs:234-300): de-interleave each channel,

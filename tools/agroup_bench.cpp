@@ -1,7 +1,9 @@
 // tools/agroup_bench.cpp — N independent element instances (audio, then videocompare) as N NATIVE threads (what N GStreamer streaming threads are), each
 // handing one buffer per interval to (a) its own single-instance context (the shim's path until round 5) and (b) the process's
 // mi355_agroup (round 6). Prints one JSON line per element kind. Build: make -C tools agroup_bench (g++, links libmi355fx.so).
-// Run on the GPU box: tools/agroup_bench [instances]
+// Run on the GPU box: tools/agroup_bench [instances] [all | audio | videocompare | dssim]
+//                     tools/agroup_bench [instances] hrtf [repeats] [mesh file]   (hrtfrender: its own section, tools/bench_hrtf_group.py drives it)
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -52,8 +54,117 @@ static double run_threads(int n, int iters, F body) {
 int main(int argc, char **argv) {
   const int S = argc > 1 ? std::atoi(argv[1]) : 32;
   const std::string section = argc > 2 ? argv[2] : "all";   // all | audio | videocompare | dssim
-  const bool do_audio = section == "all" || section == "audio", do_video = section != "audio", dssim_only = section == "dssim";
+  const bool do_hrtf = section == "hrtf";
+  const bool do_audio = section == "all" || section == "audio", do_video = section != "audio" && !do_hrtf, dssim_only = section == "dssim";
   int st = 0;
+  // ------------------------------------------------------------ hrtfrender: S listeners x 8 sources, 256-tap sphere at 48 kHz, block 512 x 8 (85.3 ms)
+  if (do_hrtf) {
+    const int repeats = argc > 3 ? std::atoi(argv[3]) : 5, iters = 200;
+    const char *mesh_path = argc > 4 ? argv[4] : "tests/golden/test.hrir";
+    const int C = 8, B = 512, steps = 8, L = 256;
+    const size_t frames = (size_t)B * steps;
+    // the sphere: the geometry of the mesh file, every HRIR a seeded decaying noise burst of L taps, written at the device rate
+    std::vector<unsigned char> mesh;
+    if (FILE *f = std::fopen(mesh_path, "rb")) {
+      unsigned char b[4096];
+      size_t k;
+      while ((k = std::fread(b, 1, sizeof b, f)) > 0) mesh.insert(mesh.end(), b, b + k);
+      std::fclose(f);
+    }
+    if (mesh.size() < 20 || std::memcmp(mesh.data(), "HRIR", 4) != 0) { std::fprintf(stderr, "no HRIR mesh at %s\n", mesh_path); return 1; }
+    auto u32 = [&](size_t o) { uint32_t v; std::memcpy(&v, mesh.data() + o, 4); return v; };
+    const uint32_t flen = u32(8), nv = u32(12), ni = u32(16), rate = 48000, len = (uint32_t)L;
+    std::vector<unsigned char> sphere(20 + 4 * (size_t)ni + (size_t)nv * (12 + 8 * (size_t)L));
+    std::memcpy(sphere.data(), mesh.data(), 20 + 4 * (size_t)ni);
+    std::memcpy(sphere.data() + 4, &rate, 4);
+    std::memcpy(sphere.data() + 8, &len, 4);
+    uint64_t lcg = 0x4D49333535ull;
+    for (uint32_t v = 0; v < nv; v++) {
+      unsigned char *dst = sphere.data() + 20 + 4 * (size_t)ni + (size_t)v * (12 + 8 * (size_t)L);
+      std::memcpy(dst, mesh.data() + 20 + 4 * (size_t)ni + (size_t)v * (12 + 8 * (size_t)flen), 12);
+      for (int k = 0; k < 2 * L; k++) {
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        const float h = 0.3f * std::exp(-(float)(k % L) / 32.0f) * ((float)((lcg >> 40) & 0xFFFF) / 32768.0f - 1.0f);
+        std::memcpy(dst + 12 + 4 * (size_t)k, &h, 4);
+      }
+    }
+    std::vector<mi355_ctx *> ctxs(S);
+    std::vector<std::vector<float>> in(S, std::vector<float>(frames * C)), out(S, std::vector<float>(frames * 2)), pos(S, std::vector<float>(3 * C)), gains(S, std::vector<float>(C, 0.5f));
+    std::vector<void *> d_in(S), d_out(S);
+    mi355_agroup *g = mi355_agroup_create_hrtf(0, S, &st);
+    if (!g) { std::fprintf(stderr, "no agroup: %d\n", st); return 1; }
+    CK(mi355_agroup_set_linger(g, 2000, 0));   // what gst/gsthrtfrender.c sets
+    for (int m = 0; m < S; m++) {
+      ctxs[m] = mi355_ctx_create(0, &st);
+      if (!ctxs[m]) { std::fprintf(stderr, "no context: %d\n", st); return 1; }
+      CK(mi355_hrtf_load_sphere(ctxs[m], sphere.data(), sphere.size(), rate));
+      CK(mi355_hrtf_setup(ctxs[m], C, B, steps));
+      CK(mi355_agroup_hrtf_load_sphere(g, m, sphere.data(), sphere.size(), rate));
+      CK(mi355_agroup_hrtf_setup(g, m, C, B, steps, 0));
+      for (size_t i = 0; i < frames * C; i++) in[m][i] = 0.1f * std::sin(0.01f * (float)(i + 17 * m));
+      for (int c = 0; c < C; c++) { pos[m][3 * c] = std::cos(0.7f * (float)(c + m)); pos[m][3 * c + 1] = std::sin(0.7f * (float)(c + m)); pos[m][3 * c + 2] = 0.2f * (float)(c % 3) - 0.2f; }
+      d_in[m] = mi355_device_alloc(ctxs[m], frames * C * 4);
+      d_out[m] = mi355_device_alloc(ctxs[m], frames * 8);
+      CK(mi355_memcpy_h2d(ctxs[m], d_in[m], in[m].data(), frames * C * 4));
+    }
+    auto move = [&](int m, int i) { pos[m][3 * (i % C)] += 0.01f; };   // a source moves every block
+    auto own_host = [&](int m, int i) { move(m, i); CK(mi355_hrtf_process_block(ctxs[m], in[m].data(), out[m].data(), pos[m].data(), gains[m].data())); };
+    auto own_dev = [&](int m, int i) {
+      move(m, i);
+      CK(mi355_hrtf_process_block_device(ctxs[m], (const float *)d_in[m], (float *)d_out[m], pos[m].data(), gains[m].data()));
+      CK(mi355_ctx_synchronize(ctxs[m]));   // transform returns a finished buffer
+    };
+    auto via_group = [&](int device) {
+      return [&, device](int m, int i) {
+        uint64_t t = 0;
+        move(m, i);
+        CK(mi355_agroup_submit_hrtf(g, m, device ? (const float *)d_in[m] : in[m].data(), device ? (float *)d_out[m] : out[m].data(), pos[m].data(), gains[m].data(), device, &t));
+        CK(mi355_agroup_wait(g, t, nullptr));
+      };
+    };
+    run_threads(S, 30, own_host);
+    run_threads(S, 30, via_group(0));
+    uint64_t s0[3], s1[3];
+    CK(mi355_agroup_stats(g, s0));
+    const uint64_t l0 = mi355_agroup_hrtf_launches(g);
+    // the four legs alternated inside one process, `repeats` times: medians and the spread
+    std::vector<double> t[4];
+    for (int r = 0; r < repeats; r++) {
+      t[0].push_back(run_threads(S, iters, own_host) / iters * 1e3);
+      t[1].push_back(run_threads(S, iters, via_group(0)) / iters * 1e3);
+      t[2].push_back(run_threads(S, iters, own_dev) / iters * 1e3);
+      t[3].push_back(run_threads(S, iters, via_group(1)) / iters * 1e3);
+    }
+    CK(mi355_agroup_stats(g, s1));
+    const uint64_t launches = mi355_agroup_hrtf_launches(g) - l0, sets = s1[1] - s0[1], buffers = s1[0] - s0[0];
+    // uniform members: prepare, ONE convolution launch, mix per launch set, whoever is in it
+    if (launches != 3 * sets) { std::fprintf(stderr, "hrtf group: %llu launches in %llu launch sets, expected 3 per set\n", (unsigned long long)launches, (unsigned long long)sets); return 1; }
+    // one thread, device buffers: every member submitted, then waited for (no thread wake-ups in the number)
+    const auto t0 = clk::now();
+    for (int i = 0; i < iters; i++) {
+      std::vector<uint64_t> tk(S);
+      for (int m = 0; m < S; m++) CK(mi355_agroup_submit_hrtf(g, m, (const float *)d_in[m], (float *)d_out[m], pos[m].data(), gains[m].data(), 1, &tk[m]));
+      for (int m = 0; m < S; m++) CK(mi355_agroup_wait(g, tk[m], nullptr));
+    }
+    const double one_thread = secs(t0, clk::now()) / iters * 1e3;
+    const double block_s = (double)frames / (double)rate;
+    const char *names[4] = {"own_context_host_buffers", "agroup_host_buffers", "own_context_device_buffers", "agroup_device_buffers"};
+    std::printf("{\"element\": \"hrtfrender\", \"instances\": %d, \"block\": \"%d sources, %d-tap sphere at 48 kHz, block %d x %d (%.1f ms), one native thread per instance, linger 2 ms\", \"repeats\": %d, \"iterations\": %d",
+                S, C, L, B, steps, block_s * 1e3, repeats, iters);
+    for (int k = 0; k < 4; k++) {
+      std::sort(t[k].begin(), t[k].end());
+      const double med = t[k][t[k].size() / 2];
+      std::printf(", \"%s_ms_per_interval\": {\"median\": %.4f, \"min\": %.4f, \"max\": %.4f}, \"%s_realtime_aggregate\": %.0f", names[k], med, t[k].front(), t[k].back(), names[k],
+                  S * block_s / (med * 1e-3));
+    }
+    std::printf(", \"agroup_device_buffers_one_thread_ms_per_interval\": %.4f, \"agroup_launch_sets\": %llu, \"agroup_buffers\": %llu, \"agroup_largest_set\": %llu, "
+                "\"agroup_kernel_launches\": %llu, \"agroup_launches_per_launch_set\": 3, \"agroup_launches_per_interval\": %.2f, \"own_context_launches_per_interval\": %d}\n",
+                one_thread, (unsigned long long)sets, (unsigned long long)buffers, (unsigned long long)s1[2], (unsigned long long)launches,
+                (double)launches / (2.0 * repeats * iters), 3 * S);
+    std::fflush(stdout);
+    mi355_agroup_destroy(g);
+    for (int m = 0; m < S; m++) { mi355_device_free(ctxs[m], d_in[m]); mi355_device_free(ctxs[m], d_out[m]); mi355_ctx_destroy(ctxs[m]); }
+  }
   // ------------------------------------------------------------ rsaudioecho: 48 kHz stereo f32, 10 ms buffers, delay 250 ms, feedback 0.4
   if (do_audio) {
     const size_t n = 960, ring = 96000;

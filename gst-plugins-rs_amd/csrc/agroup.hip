@@ -104,8 +104,17 @@ namespace {
 
 enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4, KIND_HRTF = 5 };
 
-struct Sub {   // one member's submission of the interval being collected
-  bool have = false;
+// a member's life cycle: at most ONE buffer is outstanding, its ticket is collected once, and nothing else of the member moves in between
+//   IDLE -> FILLING (submit accepted; the buffer is on its way into the staging slot, possibly outside the lock) -> SUBMITTED (it
+//   counts for the launch set being collected) -> RAN (the set has run; the result waits for wait(ticket)) -> COLLECTING (wait is
+//   copying it out, possibly outside the lock) -> IDLE.
+// Every submit_* and every setup / reset / load call of a member is refused unless the member is IDLE (check_member); wait takes
+// only the ticket of the SUBMITTED or RAN buffer. detach drops a buffer that has not run; a result that has is still collected once.
+enum { M_IDLE = 0, M_FILLING, M_SUBMITTED, M_RAN, M_COLLECTING };
+
+struct Sub {   // one member's submission: the buffer it has outstanding
+  int state = M_IDLE;
+  bool have() const { return state == M_SUBMITTED; }   // part of the launch set being collected
   bool device = false;
   void *data = nullptr;      // caller's buffer (echo: in place; ebur128: input; loudnorm: input)
   void *out = nullptr;       // loudnorm / hrtfrender: caller's output buffer
@@ -165,6 +174,7 @@ struct mi355_agroup {
   std::vector<float> hrtf_pg;       // [member][4 * 64]: positions [C][3] then gains [C], copied at submit
   // ---- ebur128
   unsigned channels = 0;
+  int set_fmt = -1;                 // ebur128: the sample format of the launch set being collected, fixed by the first member accepted into it
   uint64_t query_interval[5] = {0, 0, 0, 0, 0};   // ebur128: the interval the cached answers below belong to
   std::vector<double> query_cache[5];
   uint64_t peak_interval[2] = {0, 0};
@@ -215,7 +225,7 @@ int ensure_staging(mi355_agroup *g, std::unique_lock<std::mutex> &lk, size_t nee
     // submissions already copied into the old slots move along, and so do results that their members have not collected yet
     // (rsaudioecho works in place: the result of a member sits in its input slot)
     for (int m = 0; m < g->n_members; m++)
-      if (g->h_in && ((g->sub[m].have && !g->sub[m].device) || g->res_pending[(size_t)m])) std::memcpy(h + (size_t)m * cap, g->h_in + (size_t)m * g->cap_bytes, g->cap_bytes);
+      if (g->h_in && ((g->sub[m].have() && !g->sub[m].device) || g->res_pending[(size_t)m])) std::memcpy(h + (size_t)m * cap, g->h_in + (size_t)m * g->cap_bytes, g->cap_bytes);
     if (g->h_in) (void)hipHostFree(g->h_in);
     if (g->d_in) (void)hipFree(g->d_in);
     g->h_in = h; g->d_in = d; g->cap_bytes = cap;
@@ -257,7 +267,7 @@ int run_echo(mi355_agroup *g) {
   std::vector<int> who;
   size_t max_host = 0, max_n = 0;
   for (int m = 0; m < g->n_members; m++)
-    if (g->sub[m].have) {
+    if (g->sub[m].have()) {
       who.push_back(m);
       const size_t bytes = g->sub[m].n * (g->sub[m].fmt ? 8 : 4);
       if (!g->sub[m].device && bytes > max_host) max_host = bytes;
@@ -334,7 +344,7 @@ int run_aging(mi355_agroup *g) {
   std::vector<int> who;
   size_t max_host = 0;
   for (int m = 0; m < g->n_members; m++)
-    if (g->sub[m].have) {
+    if (g->sub[m].have()) {
       who.push_back(m);
       if (!g->sub[m].device && sub_bytes(g, m) > max_host) max_host = sub_bytes(g, m);
     }
@@ -382,11 +392,13 @@ int run_aging(mi355_agroup *g) {
 int run_ebur128(mi355_agroup *g) {
   static const size_t esz[4] = {2, 4, 4, 8};
   std::vector<size_t> frames_per((size_t)g->n_members, 0);
+  // the format is the set's (fixed when its first member was accepted, mi355_agroup_submit_ebur128), never "the last member's": it
+  // is every member's element size, the slot stride and the kernel template below
   int fmt = -1;
   size_t max_host = 0;
   for (int m = 0; m < g->n_members; m++)
-    if (g->sub[m].have) {
-      fmt = g->sub[m].fmt;
+    if (g->sub[m].have()) {
+      fmt = g->set_fmt;
       frames_per[(size_t)m] = g->sub[m].n;
       const size_t bytes = g->sub[m].n * g->channels * esz[fmt];
       if (!g->sub[m].device && bytes > max_host) max_host = bytes;
@@ -398,7 +410,7 @@ int run_ebur128(mi355_agroup *g) {
   // not part of this launch set: it may be filling it for the next one); device members: one D2D copy each
   std::vector<std::pair<int, int>> runs;
   for (int m = 0; m < g->n_members; m++) {
-    if (!g->sub[m].have || g->sub[m].device) continue;
+    if (!g->sub[m].have() || g->sub[m].device) continue;
     if (!runs.empty() && runs.back().second == m - 1) runs.back().second = m;
     else runs.push_back({m, m});
   }
@@ -406,7 +418,7 @@ int run_ebur128(mi355_agroup *g) {
     if ((rc = ahip(g, hipMemcpy2DAsync(g->d_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, g->h_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, max_host,
                                        (size_t)(r.second - r.first + 1), hipMemcpyHostToDevice, st), "agroup ebur128: upload"))) return rc;
   for (int m = 0; m < g->n_members; m++)
-    if (g->sub[m].have && g->sub[m].device)
+    if (g->sub[m].have() && g->sub[m].device)
       if ((rc = ahip(g, hipMemcpyAsync(g->d_in + (size_t)m * g->cap_bytes, g->sub[m].data, g->sub[m].n * g->channels * esz[fmt], hipMemcpyDeviceToDevice, st),
                      "agroup ebur128: gather"))) return rc;
   rc = ebur128_add_frames_streams(g->ctx, g->d_in, g->cap_bytes / esz[fmt], frames_per.data(), fmt, 1);
@@ -423,10 +435,9 @@ int run_loudnorm(mi355_agroup *g) {
   hipStream_t st = g->ctx->stream;
   std::vector<char> todo(N, 0);
   bool any = false;
-  for (size_t m = 0; m < N; m++) if (g->sub[m].have) { todo[m] = 1; any = true; }
+  for (size_t m = 0; m < N; m++) if (g->sub[m].have()) { todo[m] = 1; any = true; }
   if (!any) return MI355_OK;
   const size_t in_stride = g->cap_bytes / 8, cap_frames = g->out_cap_bytes / (ch * 8);
-  size_t max_out = 0;
   int rc;
   for (size_t m0 = 0; m0 < N; m0++) {
     if (!todo[m0]) continue;
@@ -457,16 +468,23 @@ int run_loudnorm(mi355_agroup *g) {
     rc = loudnorm_process_members(g->ctx, cls.data(), (const double *)g->d_in, in_stride, frames, (double *)g->d_out, cap_frames * ch, cap_frames, &out_frames, 1, final_frame);
     if (rc) { g->last_error = g->ctx->last_error; return rc; }
     for (size_t m = 0; m < N; m++) if (cls[m]) g->ln_out[m] = out_frames;
-    if (out_frames > max_out) max_out = out_frames;
     if (out_frames)
       for (size_t m = 0; m < N; m++)
         if (cls[m] && g->sub[m].device && g->sub[m].out)
           if ((rc = ahip(g, hipMemcpyAsync(g->sub[m].out, g->d_out + m * cap_frames * ch * 8, out_frames * ch * 8, hipMemcpyDeviceToDevice, st), "agroup loudnorm: scatter"))) return rc;
   }
-  // output: packed [member][cap frames] in the device slab -> one copy to the pinned slab for the host members (rows of members that
-  // did not take part are copied along and never read)
-  if (max_out)
-    if ((rc = ahip(g, hipMemcpy2DAsync(g->h_out, cap_frames * ch * 8, g->d_out, cap_frames * ch * 8, max_out * ch * 8, N, hipMemcpyDeviceToHost, st), "agroup loudnorm: download"))) return rc;
+  // output: packed [member][cap frames] in the device slab -> the pinned slab, one strided copy per run of consecutive participating
+  // host members, as wide as the run's longest output. Never across the row of a member that did not take part: its row may hold a
+  // result it has not collected yet, and the device slab may be a newer one than that result came from (ensure_staging).
+  const size_t row = cap_frames * ch * 8;
+  for (size_t m = 0; m < N;) {
+    if (!(g->sub[m].have() && !g->sub[m].device)) { m++; continue; }
+    size_t e = m, run_out = g->ln_out[m];
+    while (e + 1 < N && g->sub[e + 1].have() && !g->sub[e + 1].device) { e++; if (g->ln_out[e] > run_out) run_out = g->ln_out[e]; }
+    if (run_out)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->h_out + m * row, row, g->d_out + m * row, row, run_out * ch * 8, e - m + 1, hipMemcpyDeviceToHost, st), "agroup loudnorm: download"))) return rc;
+    m = e + 1;
+  }
   return ahip(g, hipStreamSynchronize(st), "agroup loudnorm: sync");
 }
 
@@ -478,7 +496,7 @@ int run_hrtf(mi355_agroup *g) {
   size_t max_in = 0, max_out = 0;
   for (int m = 0; m < g->n_members; m++) {
     const Sub &s = g->sub[m];
-    if (!s.have) continue;
+    if (!s.have()) continue;
     const float *pg = g->hrtf_pg.data() + (size_t)m * 256;
     HrtfSubmit h;
     h.member = m;
@@ -526,13 +544,13 @@ void run_interval(mi355_agroup *g) {
   uint64_t carried = 0;
   for (int m = 0; m < g->n_members; m++) {
     Sub &s = g->sub[m];
-    if (!s.have) continue;
+    if (!s.have()) continue;
     carried++;
     g->res_status[m] = rc;
     g->res_frames[m] = g->kind == KIND_LOUDNORM ? g->ln_out[(size_t)m] : s.n;
     g->res_interval[m] = s.interval;
     g->res_pending[(size_t)m] = !s.device && rc == MI355_OK && g->kind != KIND_EBUR128;
-    s.have = false;   // (data / out stay: wait copies the member's result out)
+    s.state = M_RAN;   // (data / out / n / fmt stay: wait(ticket of s.interval) copies the member's result out, once)
   }
   g->n_batches++;
   g->n_buffers += carried;
@@ -545,7 +563,7 @@ bool everybody_here(const mi355_agroup *g) {
   bool any = false;
   for (int m = 0; m < g->n_members; m++) {
     if (!g->attached[m]) continue;
-    if (!g->sub[m].have) return false;
+    if (!g->sub[m].have()) return false;
     any = true;
   }
   return any;
@@ -574,6 +592,7 @@ uint64_t ticket_of(const mi355_agroup *g, uint64_t interval, int member) { retur
 // first frames one after the other would be the longest thing in the interval), then the slot counts; run the interval if it is
 // complete. `lk` owns g->mu on entry and on return.
 void submitted(mi355_agroup *g, std::unique_lock<std::mutex> &lk, int member, uint64_t *ticket, void *dst, const void *src, size_t bytes) {
+  g->sub[member].state = M_FILLING;   // not idle any more, and (ebur128) part of the set whose format it shares, while the lock is away
   if (dst && bytes > (size_t)65536) {
     g->copying++;
     lk.unlock();
@@ -584,9 +603,10 @@ void submitted(mi355_agroup *g, std::unique_lock<std::mutex> &lk, int member, ui
   } else if (dst && bytes) {
     std::memcpy(dst, src, bytes);   // (a 10 ms audio buffer is a few KB: cheaper than giving the lock away and taking it again)
   }
-  g->sub[member].have = true;
   g->sub[member].interval = g->interval;
   if (ticket) *ticket = ticket_of(g, g->interval, member);
+  // (detached during the copy: the buffer is dropped as detach drops a submitted one; wait(ticket) answers "detached")
+  g->sub[member].state = g->attached[member] ? M_SUBMITTED : M_IDLE;
   if (everybody_here(g)) run_interval(g);
 }
 
@@ -594,7 +614,8 @@ int check_member(mi355_agroup *g, int kind, int member) {
   if (g->kind != kind) return afail(g, MI355_ERR_INVALID_ARG, "agroup: this group batches another element kind");
   if (member < 0 || member >= g->n_members) return afail(g, MI355_ERR_INVALID_ARG, "agroup: no such member");
   if (!g->attached[member]) return afail(g, MI355_ERR_INVALID_ARG, "agroup: this member has been detached");
-  if (g->sub[member].have) return afail(g, MI355_ERR_INVALID_ARG, "agroup: this member's previous buffer has not been waited for");
+  // submitted, run and not collected, or on its way in or out: the slot, data / out and the member's configuration belong to that buffer
+  if (g->sub[member].state != M_IDLE) return afail(g, MI355_ERR_INVALID_ARG, "agroup: this member's previous buffer has not been waited for");
   return MI355_OK;
 }
 
@@ -688,7 +709,9 @@ int mi355_agroup_detach(mi355_agroup *g, int member) {
   std::unique_lock<std::mutex> lk(g->mu);
   if (member < 0 || member >= g->n_members) return afail(g, MI355_ERR_INVALID_ARG, "agroup: no such member");
   g->attached[member] = 0;
-  g->sub[member].have = false;
+  // a buffer that has not run is dropped (one on its way into its slot when its copy is done, submitted()); a result that has run
+  // stays collectable, once
+  if (g->sub[member].state == M_SUBMITTED) g->sub[member].state = M_IDLE;
   // the others may have been waiting for this one
   if (everybody_here(g)) run_interval(g);
   g->cv.notify_all();
@@ -726,13 +749,18 @@ int mi355_agroup_submit_ebur128(mi355_agroup *g, int member, const void *data, s
   if (rc) return rc;
   if (sample_format < 0 || sample_format > 3) return afail(g, MI355_ERR_INVALID_ARG, "ebur128: bad sample format");
   if (frames == 0 || !data) return afail(g, MI355_ERR_INVALID_ARG, "agroup: empty buffer");
-  for (int m = 0; m < g->n_members; m++)
-    if (m != member && g->sub[m].have && g->sub[m].fmt != sample_format)
-      return afail(g, MI355_ERR_INVALID_ARG, "agroup: the members of an ebur128level group submit one sample format");
   (void)hipSetDevice(g->device);
   static const size_t esz[4] = {2, 4, 4, 8};
   const size_t bytes = frames * g->channels * esz[sample_format];
   if ((rc = ensure_staging(g, lk, bytes, 0))) return rc;
+  // one sample format per launch set: the first member accepted fixes it, here, under the lock that submitted() may give away for
+  // the copy. The set = the members that have submitted AND those whose buffer is still on its way into its slot; checked after
+  // ensure_staging, which may have given the lock away too.
+  bool first = true;
+  for (int m = 0; m < g->n_members; m++)
+    if (m != member && (g->sub[m].state == M_SUBMITTED || g->sub[m].state == M_FILLING)) first = false;
+  if (first) g->set_fmt = sample_format;
+  else if (g->set_fmt != sample_format) return afail(g, MI355_ERR_INVALID_ARG, "agroup: the members of an ebur128level group submit one sample format");
   Sub &s = g->sub[member];
   s.device = device_data != 0; s.data = (void *)data; s.n = frames; s.fmt = sample_format;
   submitted(g, lk, member, ticket, s.device ? nullptr : g->h_in + (size_t)member * g->cap_bytes, data, bytes);
@@ -796,6 +824,14 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
   const uint64_t interval = (ticket - 1) / (uint64_t)g->n_members;
   const int member = (int)((ticket - 1) % (uint64_t)g->n_members);
   if (interval == 0 || interval > g->interval) return afail(g, MI355_ERR_INVALID_ARG, "agroup: unknown ticket");
+  Sub &s = g->sub[member];
+  // only the member's outstanding ticket is taken: the buffer that waits for its launch set, or the result that waits to be collected.
+  // Anything else is refused HERE, before this call can run a launch set or touch a buffer.
+  if (!(s.state == M_RAN && s.interval == interval)) {
+    if (!g->attached[member]) return afail(g, MI355_ERR_INVALID_ARG, "agroup: destroyed or detached while waiting");
+    if (!(s.state == M_SUBMITTED && s.interval == interval))
+      return afail(g, MI355_ERR_INVALID_ARG, interval < g->interval ? "agroup: this ticket has been waited for already" : "agroup: unknown ticket");
+  }
   const auto t0 = std::chrono::steady_clock::now();
   while (g->interval <= interval) {
     if (!g->attached[member]) return afail(g, MI355_ERR_INVALID_ARG, "agroup: destroyed or detached while waiting");
@@ -805,10 +841,14 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
       if (g->interval <= interval) run_interval(g);
     }
   }
-  if (g->res_interval[member] != interval) return afail(g, MI355_ERR_INVALID_ARG, "agroup: this ticket has been waited for already");
+  // (another thread may have collected this very ticket while this one waited for the set)
+  if (!(s.state == M_RAN && s.interval == interval) || g->res_interval[member] != interval)
+    return afail(g, MI355_ERR_INVALID_ARG, "agroup: this ticket has been waited for already");
+  s.state = M_COLLECTING;   // the ticket is spent: a second wait is refused, and the member stays busy until its result is out
+  // the member is idle again once its result has been copied out (ebur128level, device members, failed sets: once it has been reported)
+  auto collected = [&](int status) { g->res_pending[(size_t)member] = 0; s.state = M_IDLE; return status; };
   const int rc = g->res_status[member];
-  if (rc) return rc;   // last_error is the batch's
-  const Sub &s = g->sub[member];
+  if (rc) return collected(rc);   // last_error is the batch's
   const size_t frames = g->res_frames[member];
   if (out_frames) *out_frames = frames;
   // copy-out happens under the lock only for its pointer arithmetic: the member's slot is not written again before this member
@@ -830,7 +870,6 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
         g->cv.notify_all();
       }
     }
-    g->res_pending[(size_t)member] = 0;
   } else if (g->kind == KIND_HRTF) {
     if (!s.device && frames && s.out) {
       const char *src = g->h_out + (size_t)member * g->out_cap_bytes;
@@ -842,9 +881,8 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
       g->copying--;
       g->cv.notify_all();
     }
-    g->res_pending[(size_t)member] = 0;
   } else if (g->kind == KIND_LOUDNORM) {
-    if (frames > s.out_cap) return afail(g, MI355_ERR_INVALID_ARG, "audioloudnorm: output buffer too small");
+    if (frames > s.out_cap) return collected(afail(g, MI355_ERR_INVALID_ARG, "audioloudnorm: output buffer too small"));
     if (!s.device && frames && s.out) {
       const size_t ch = g->channels, cap_frames = g->out_cap_bytes / (ch * 8);
       const char *src = g->h_out + (size_t)member * cap_frames * ch * 8;
@@ -856,9 +894,8 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
       g->copying--;
       g->cv.notify_all();
     }
-    g->res_pending[(size_t)member] = 0;
   }
-  return MI355_OK;
+  return collected(MI355_OK);
 }
 
 // ebur128level's queries for one member (ebur128level/imp.rs:378-452). The engine answers for every member at once; the answers

@@ -515,8 +515,8 @@ class AudioGroup:
         t = C.c_uint64(0)
         if isinstance(data, np.ndarray):
             assert data.flags.c_contiguous and data.dtype in (np.float32, np.float64)
-            self._keep[member] = data
             self._ck(self.L.mi355_agroup_submit_echo(self.h, member, data.ctypes.data, data.size, int(data.dtype == np.float64), delay, intensity, feedback, 0, C.byref(t)))
+            self._keep[member] = data     # (after the call: a refused submit must not drop the buffer an outstanding ticket still fills)
         else:
             self._ck(self.L.mi355_agroup_submit_echo(self.h, member, data, n, int(bool(is_f64)), delay, intensity, feedback, 1, C.byref(t)))
         return t.value
@@ -532,9 +532,9 @@ class AudioGroup:
         st = AgingRadioSettings.of(settings)
         if isinstance(data, np.ndarray):
             assert data.flags.c_contiguous and data.dtype in (np.float32, np.float64)
-            self._keep[member] = data
             self._ck(self.L.mi355_agroup_submit_agingradio(self.h, member, data.ctypes.data, data.size // channels, int(data.dtype == np.float64), C.byref(st), 0,
                                                            C.byref(t)))
+            self._keep[member] = data
         else:
             self._ck(self.L.mi355_agroup_submit_agingradio(self.h, member, data, frames, int(bool(is_f64)), C.byref(st), 1, C.byref(t)))
         return t.value
@@ -576,8 +576,8 @@ class AudioGroup:
             x = np.ascontiguousarray(inp, dtype=np.float32).reshape(-1)
             assert x.size == frames * channels, "one block = block_length*interpolation_steps frames"
             y = np.zeros(frames * 2, np.float32)
-            self._keep[member] = (x, y)
             self._ck(self.L.mi355_agroup_submit_hrtf(self.h, member, x.ctypes.data, y.ctypes.data, pos.ctypes.data_as(fp), g.ctypes.data_as(fp), 0, C.byref(t)))
+            self._keep[member] = (x, y)   # (after the call: a refused submit leaves hrtf_output(member) the array the outstanding ticket fills)
         else:
             self._ck(self.L.mi355_agroup_submit_hrtf(self.h, member, inp, out, pos.ctypes.data_as(fp), g.ctypes.data_as(fp), 1, C.byref(t)))
         return t.value
@@ -607,8 +607,8 @@ class AudioGroup:
         if isinstance(data, np.ndarray):
             fmt = {np.dtype(np.int16): 0, np.dtype(np.int32): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}[data.dtype]
             assert data.flags.c_contiguous
-            self._keep[member] = data
             self._ck(self.L.mi355_agroup_submit_ebur128(self.h, member, data.ctypes.data, data.size // self.channels, fmt, 0, C.byref(t)))
+            self._keep[member] = data
         else:
             self._ck(self.L.mi355_agroup_submit_ebur128(self.h, member, data, frames, sample_format, 1, C.byref(t)))
         return t.value
@@ -627,9 +627,9 @@ class AudioGroup:
         if isinstance(out, np.ndarray):
             data = np.ascontiguousarray(data, dtype=np.float64)
             assert out.flags.c_contiguous and out.dtype == np.float64
-            self._keep[member] = (data, out)
             self._ck(self.L.mi355_agroup_submit_loudnorm(self.h, member, data.ctypes.data if data.size else None, data.size // self.channels, out.ctypes.data,
                                                          out.size // self.channels, int(bool(final_frame)), 0, C.byref(t)))
+            self._keep[member] = (data, out)
         else:
             self._ck(self.L.mi355_agroup_submit_loudnorm(self.h, member, data, frames, out, out_capacity_frames, int(bool(final_frame)), 1, C.byref(t)))
         return t.value

@@ -326,6 +326,12 @@ int mi355_group_compare_stats(mi355_group *group, uint64_t stats[3]);
  *   ebur128_loudness / _peak : the member's meter readings (what: 0 momentary, 1 short-term, 2 global, 3 relative threshold,
  *                     4 loudness range), computed once per interval for all members.
  *   stats           : {buffers, launch sets, buffers in the largest set}.
+ * A member's life cycle: a member has at most ONE buffer outstanding, from its submit_* until wait(ticket) has returned. Until then
+ * another submit_* of that member and its setup / reset / load calls (agingradio_setup, ebur128_reset, hrtf_setup, hrtf_reset,
+ * hrtf_load_sphere) are refused with MI355_ERR_INVALID_ARG - whether its launch set has run or not - and change nothing. A ticket is
+ * collected once: wait takes only the member's outstanding ticket; a second wait for it, ticket 0, a ticket of a coming interval or
+ * one the member was never given are refused with MI355_ERR_INVALID_ARG, run no launch set and write to no buffer. detach drops a
+ * buffer whose launch set has not run (its wait answers "detached"); a result that has run can still be collected, once.
  * Threads: every entry point from any thread; one lock per group, held while a launch set runs. */
 typedef struct mi355_agroup mi355_agroup;
 mi355_agroup *mi355_agroup_create_echo(int device, int n_members, size_t ring_len, int *status);

@@ -14,7 +14,10 @@
 //     own setup (channels, rate, lowpass, seed), filter states and pair counter, buffer size, sample type and settings per submit
 //     (agingradio.hip's job table); hrtfrender - own sphere (shared by content), channel count, block-length, interpolation-steps and
 //     convolution form per member, own tails and previous directions (hrtf_kernels.hip's job tables: HrtfRender::process,
-//     audio/hrtf/src/hrtf/imp.rs:164-278, for every member that has a block in ONE launch set);
+//     audio/hrtf/src/hrtf/imp.rs:164-278, for every member that has a block in ONE launch set); sofalizer - own channel count, filter
+//     length, partition-length and block-length per member, own filter spectra, delay lines and drop flags, filters queued at
+//     set_filter and transformed with the member's next launch set (sofa_kernels.hip's job tables: the block loop of
+//     Sofalizer::process, audio/hrtf/src/sofa/imp.rs:235-322, for every member that has blocks in ONE launch set);
 //     ebur128level - own buffer size, 100 ms phase and `reset` (per-stream rounds in ebur128_kernels.hip); audioloudnorm - own frame
 //     type and ring positions (loudnorm.hip: a launch sequence per CLASS of members that stand at the same frame type and size:
 //     streams that started together are one class). A waiter that has lingered `linger_us` launches whoever is there: a member that
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(256) void echo_jobs_commit_kernel(const EchoJob *__
 
 namespace {
 
-enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4, KIND_HRTF = 5 };
+enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4, KIND_HRTF = 5, KIND_SOFA = 6 };
 
 // a member's life cycle: at most ONE buffer is outstanding, its ticket is collected once, and nothing else of the member moves in between
 //   IDLE -> FILLING (submit accepted; the buffer is on its way into the staging slot, possibly outside the lock) -> SUBMITTED (it
@@ -117,11 +120,12 @@ struct Sub {   // one member's submission: the buffer it has outstanding
   bool have() const { return state == M_SUBMITTED; }   // part of the launch set being collected
   bool device = false;
   void *data = nullptr;      // caller's buffer (echo: in place; ebur128: input; loudnorm: input)
-  void *out = nullptr;       // loudnorm / hrtfrender: caller's output buffer
-  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm / agingradio / hrtfrender: frames
+  void *out = nullptr;       // loudnorm / hrtfrender / sofalizer: caller's output buffer
+  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm / agingradio / hrtfrender / sofalizer: frames
   size_t out_cap = 0;        // loudnorm: capacity of `out` in frames
   int fmt = 0;               // echo / agingradio: is_f64; ebur128: sample format
   int final_frame = 0;       // loudnorm
+  int n_blocks = 0;          // sofalizer: whole blocks in this buffer
   size_t delay = 0;
   double intensity = 0, feedback = 0;
   mi355_agingradio_settings ar{};   // agingradio: the settings transform_ip snapshotted for this buffer
@@ -172,6 +176,9 @@ struct mi355_agroup {
   // ---- hrtfrender
   HrtfGroup *hrtf = nullptr;        // the members' spheres, processors and job tables (hrtf_kernels.hip)
   std::vector<float> hrtf_pg;       // [member][4 * 64]: positions [C][3] then gains [C], copied at submit
+  // ---- sofalizer
+  SofaGroup *sofa = nullptr;        // the members' convolvers, filter queue and job tables (sofa_kernels.hip)
+  std::vector<float> sofa_g;        // [member][64]: gains [C], copied at submit
   // ---- ebur128
   unsigned channels = 0;
   int set_fmt = -1;                 // ebur128: the sample format of the launch set being collected, fixed by the first member accepted into it
@@ -204,9 +211,9 @@ int ahip(mi355_agroup *g, hipError_t e, const char *what) {
 // staging slots of at least `need` bytes per member (and `out_need` for the output side). A slab is replaced while no copy runs on it and
 // no launch is in flight; what it holds of members' business - submissions copied in, results not collected yet - moves along.
 // a member's row of the output slab: loudnorm's is out_cap_bytes rounded down to whole frames of its channel count; hrtfrender's
-// output is stereo f32 whatever the member's input channels are, and its row is the slot itself
+// and sofalizer's output is stereo f32 whatever the member's input channels are, and its row is the slot itself
 size_t out_row(const mi355_agroup *g, size_t cap) {
-  if (g->kind == KIND_HRTF) return cap;
+  if (g->kind == KIND_HRTF || g->kind == KIND_SOFA) return cap;
   const size_t fb = (size_t)g->channels * 8;
   return cap / fb * fb;
 }
@@ -241,7 +248,7 @@ int ensure_staging(mi355_agroup *g, std::unique_lock<std::mutex> &lk, size_t nee
     if ((rc = ahip(g, hipMalloc((void **)&d, cap * (size_t)g->n_members), "hipMalloc(agroup output staging)"))) { (void)hipHostFree(h); return rc; }
     // results that their members have not collected yet move along (a row of the output slab is out_cap_bytes wide, rounded down to
     // whole frames: wait() computes the row the same way)
-    if (g->h_out && (g->channels || g->kind == KIND_HRTF)) {
+    if (g->h_out && (g->channels || g->kind == KIND_HRTF || g->kind == KIND_SOFA)) {
       const size_t old_row = out_row(g, g->out_cap_bytes), new_row = out_row(g, cap);
       for (int m = 0; m < g->n_members; m++)
         if (g->res_pending[(size_t)m]) std::memcpy(h + (size_t)m * new_row, g->h_out + (size_t)m * old_row, old_row);
@@ -532,6 +539,51 @@ int run_hrtf(mi355_agroup *g) {
   return ahip(g, hipStreamSynchronize(st), "agroup hrtf: sync");
 }
 
+// ---- sofalizer: the members that have submitted render their blocks in ONE launch set (sofa_kernels.hip: the pending filters of
+// those members transformed - one launch per partition length among them - then one convolution launch per partition length among
+// the members, then the mix). Host members: one strided upload and one strided download per run of consecutive participating host
+// members; device members pass their pointers straight through. g->mu held.
+int run_sofa(mi355_agroup *g) {
+  std::vector<SofaSubmit> subs;
+  size_t max_in = 0, max_out = 0;
+  for (int m = 0; m < g->n_members; m++) {
+    const Sub &s = g->sub[m];
+    if (!s.have()) continue;
+    SofaSubmit h;
+    h.member = m;
+    h.d_in = s.device ? (const float *)s.data : (const float *)(g->d_in + (size_t)m * g->cap_bytes);
+    h.d_out = s.device ? (float *)s.out : (float *)(g->d_out + (size_t)m * g->out_cap_bytes);
+    h.gains = g->sofa_g.data() + (size_t)m * 64;
+    h.n_blocks = s.n_blocks;
+    subs.push_back(h);
+    if (!s.device) {
+      const size_t in_bytes = s.n * (size_t)sofa_group_channels(g->sofa, m) * 4;
+      if (in_bytes > max_in) max_in = in_bytes;
+      if (s.n * 8 > max_out) max_out = s.n * 8;
+    }
+  }
+  if (subs.empty()) return MI355_OK;
+  hipStream_t st = g->ctx->stream;
+  int rc = MI355_OK;
+  std::vector<std::pair<int, int>> runs;   // [first, last] member of each run (never across the slot of a member that is not part of this set)
+  for (const SofaSubmit &h : subs) {
+    if (g->sub[h.member].device) continue;
+    if (!runs.empty() && runs.back().second == h.member - 1) runs.back().second = h.member;
+    else runs.push_back({h.member, h.member});
+  }
+  if (max_in > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->d_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, g->h_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, max_in,
+                                         (size_t)(r.second - r.first + 1), hipMemcpyHostToDevice, st), "agroup sofa: upload"))) return rc;
+  std::string err;
+  if ((rc = sofa_group_run(g->sofa, st, subs.data(), (int)subs.size(), &err))) return afail(g, rc, err);
+  if (max_out > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->h_out + (size_t)r.first * g->out_cap_bytes, g->out_cap_bytes, g->d_out + (size_t)r.first * g->out_cap_bytes, g->out_cap_bytes,
+                                         max_out, (size_t)(r.second - r.first + 1), hipMemcpyDeviceToHost, st), "agroup sofa: download"))) return rc;
+  return ahip(g, hipStreamSynchronize(st), "agroup sofa: sync");
+}
+
 // runs the collected interval. g->mu held (the members are blocked on it or on the condition variable anyway).
 void run_interval(mi355_agroup *g) {
   (void)hipSetDevice(g->device);
@@ -540,6 +592,7 @@ void run_interval(mi355_agroup *g) {
   else if (g->kind == KIND_EBUR128) rc = run_ebur128(g);
   else if (g->kind == KIND_AGING) rc = run_aging(g);
   else if (g->kind == KIND_HRTF) rc = run_hrtf(g);
+  else if (g->kind == KIND_SOFA) rc = run_sofa(g);
   else rc = run_loudnorm(g);
   uint64_t carried = 0;
   for (int m = 0; m < g->n_members; m++) {
@@ -690,6 +743,7 @@ void mi355_agroup_destroy(mi355_agroup *g) {
   if (g->d_ajobs) (void)hipFree(g->d_ajobs);
   if (g->h_ajobs) (void)hipHostFree(g->h_ajobs);
   hrtf_group_free(g->hrtf);
+  sofa_group_free(g->sofa);
   if (g->ctx) mi355_ctx_destroy(g->ctx);   // releases the ebur128 / loudnorm batch engines with it
   delete g;
 }
@@ -870,7 +924,7 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
         g->cv.notify_all();
       }
     }
-  } else if (g->kind == KIND_HRTF) {
+  } else if (g->kind == KIND_HRTF || g->kind == KIND_SOFA) {
     if (!s.device && frames && s.out) {
       const char *src = g->h_out + (size_t)member * g->out_cap_bytes;
       void *dst = s.out;
@@ -1127,6 +1181,114 @@ uint64_t mi355_agroup_hrtf_launches(mi355_agroup *g) {
   return hrtf_group_launches(g->hrtf);
 }
 
+// ---- sofalizer members (Sofalizer, audio/hrtf/src/sofa/imp.rs)
+mi355_agroup *mi355_agroup_create_sofa(int device, int n_members, int *status) {
+  mi355_agroup *g = agroup_new(device, KIND_SOFA, n_members, status);
+  if (!g) return nullptr;
+  int rc = MI355_OK;
+  g->sofa = sofa_group_new(n_members, &g->last_error, &rc);
+  g->sofa_g.assign((size_t)n_members * 64, 0.0f);
+  if (!g->sofa) { if (status) *status = rc; mi355_agroup_destroy(g); return nullptr; }
+  if (status) *status = MI355_OK;
+  return g;
+}
+
+// set_caps of one member (sofa/imp.rs:747-838): the Renderer per channel that is not an LFE (:794-798), built for partition-length
+// (:779-784). Everything the member needs on the device is allocated here, after the group's stream has drained.
+int mi355_agroup_sofa_setup(mi355_agroup *g, int member, int channels, int filter_len, int partition_length, int block_length) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_SOFA, member);
+  if (rc) return rc;
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if ((rc = sofa_group_setup(g->sofa, member, g->ctx->stream, channels, filter_len, partition_length, block_length, &err))) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// Renderer::set_filter of one channel (State::update_filters, sofa/imp.rs:129-160), queued: copied now, transformed with the member's
+// next launch set; launches nothing and waits for nothing. Not while the member has a buffer pending.
+int mi355_agroup_sofa_set_filter(mi355_agroup *g, int member, int channel, const float *left, const float *right, int delay_left, int delay_right) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_SOFA, member);
+  if (rc) return rc;
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if ((rc = sofa_group_set_filter(g->sofa, member, g->ctx->stream, channel, left, right, delay_left, delay_right, &err))) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// ChannelProcessor::Drop of one channel (LFE1 / LFE2, sofa/imp.rs:812-818): fixed once the member's first block has run
+int mi355_agroup_sofa_set_drop(mi355_agroup *g, int member, int channel, int drop) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_SOFA, member);
+  if (rc) return rc;
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if ((rc = sofa_group_set_drop(g->sofa, member, g->ctx->stream, channel, drop, &err))) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// State::reset_processors of one member (sofa/imp.rs:123-127, flush-stop :846-853): history cleared, filters kept; on the group's
+// stream, so after the member's last launch set and before its next. Not while the member has a buffer pending.
+int mi355_agroup_sofa_reset(mi355_agroup *g, int member) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_SOFA, member);
+  if (rc) return rc;
+  (void)hipSetDevice(g->device);
+  std::string err;
+  if ((rc = sofa_group_reset(g->sofa, member, g->ctx->stream, &err))) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// n_blocks whole blocks of one member (the `while state.adapter.available() >= inblksz` loop of Sofalizer::process, sofa/imp.rs:235-322):
+// in [n_blocks * B][C], out [n_blocks * B][2], gains [C] (host, copied here). wait() answers the frames rendered.
+int mi355_agroup_submit_sofa(mi355_agroup *g, int member, const float *in, float *out, int n_blocks, const float *distance_gains, int device_data,
+                             uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_SOFA, member);
+  if (rc) return rc;
+  if (!in || !out || !distance_gains) return afail(g, MI355_ERR_INVALID_ARG, "sofalizer: null argument");
+  if (n_blocks < 1 || n_blocks > kSofaMaxBlocks) return afail(g, MI355_ERR_INVALID_ARG, "sofalizer: a member hands over 1..8 whole blocks per submit");
+  if (!sofa_group_configured(g->sofa, member)) return afail(g, MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured");
+  if (!sofa_group_ready(g->sofa, member)) return afail(g, MI355_ERR_NOT_CONFIGURED, "sofalizer: a channel has no filter yet");
+  (void)hipSetDevice(g->device);
+  const size_t C = (size_t)sofa_group_channels(g->sofa, member), frames = (size_t)n_blocks * (size_t)sofa_group_block(g->sofa, member);
+  void *dst = nullptr;
+  size_t bytes = 0;
+  if (!device_data) {
+    bytes = frames * C * 4;
+    if ((rc = ensure_staging(g, lk, bytes, frames * 8))) return rc;
+    dst = g->h_in + (size_t)member * g->cap_bytes;
+  }
+  std::memcpy(g->sofa_g.data() + (size_t)member * 64, distance_gains, C * 4);
+  Sub &s = g->sub[member];
+  s.device = device_data != 0; s.data = (void *)in; s.out = out; s.n = frames; s.n_blocks = n_blocks;
+  submitted(g, lk, member, ticket, dst, in, bytes);
+  return MI355_OK;
+}
+
+int mi355_agroup_sofa_info(mi355_agroup *g, int member, int *partitions_K, int *fft_n, int *pending_filters) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  if (g->kind != KIND_SOFA || member < 0 || member >= g->n_members) return afail(g, MI355_ERR_INVALID_ARG, "agroup: bad member");
+  std::string err;
+  if (int rc = sofa_group_info(g->sofa, member, partitions_K, fft_n, pending_filters, &err)) return afail(g, rc, err);
+  return MI355_OK;
+}
+
+// kernel launches the group's sofalizer launch sets have made so far (2 per set of uniform members with no filter pending, 3 in the
+// interval after a source moved; measurement plumbing)
+uint64_t mi355_agroup_sofa_launches(mi355_agroup *g) {
+  if (!g || g->kind != KIND_SOFA) return 0;
+  std::lock_guard<std::mutex> lk(g->mu);
+  return sofa_group_launches(g->sofa);
+}
+
 int mi355_agroup_stats(mi355_agroup *g, uint64_t stats[3]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
@@ -1257,6 +1419,10 @@ mi355_agroup *mi355_agroup_shared_agingradio(int device, int n_members, int *mem
 
 mi355_agroup *mi355_agroup_shared_hrtf(int device, int n_members, int *member, int *status) {
   return shared_get(key_of("hrtf", device, n_members, nullptr, 0), n_members, member, status, [&] { return mi355_agroup_create_hrtf(device, n_members, status); });
+}
+
+mi355_agroup *mi355_agroup_shared_sofa(int device, int n_members, int *member, int *status) {
+  return shared_get(key_of("sofa", device, n_members, nullptr, 0), n_members, member, status, [&] { return mi355_agroup_create_sofa(device, n_members, status); });
 }
 
 void mi355_agroup_release(mi355_agroup *g, int member) {

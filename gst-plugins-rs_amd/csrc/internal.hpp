@@ -269,6 +269,24 @@ uint64_t hrtf_group_launches(const HrtfGroup *G);
 int hrtf_group_info(HrtfGroup *G, int m, uint32_t *hrir_len, int *fft_n, int *spheres_held, std::string *err);
 int hrtf_group_last_lookup(HrtfGroup *G, int m, hipStream_t stream, int *faces, float *uvw, std::string *err);
 int hrtf_group_run(HrtfGroup *G, hipStream_t stream, const HrtfSubmit *subs, int n, std::string *err);
+// the members of one sofa agroup (sofa_kernels.hip): one convolver set per member, the filter queue, the job tables of a launch set
+struct SofaGroup;
+constexpr int kSofaMaxBlocks = 8;   // whole blocks a member may hand over in one submit (Sofalizer::process takes every whole block its adapter holds)
+struct SofaSubmit { int member; const float *d_in; float *d_out; const float *gains; int n_blocks; };   // gains [C]: host
+SofaGroup *sofa_group_new(int n_members, std::string *err, int *status);
+void sofa_group_free(SofaGroup *G);
+int sofa_group_setup(SofaGroup *G, int m, hipStream_t stream, int channels, int filter_len, int partition_len, int block_len, std::string *err);
+int sofa_group_set_filter(SofaGroup *G, int m, hipStream_t stream, int channel, const float *left, const float *right, int delay_left, int delay_right,
+                          std::string *err);
+int sofa_group_set_drop(SofaGroup *G, int m, hipStream_t stream, int channel, int drop, std::string *err);
+int sofa_group_reset(SofaGroup *G, int m, hipStream_t stream, std::string *err);
+bool sofa_group_configured(const SofaGroup *G, int m);
+bool sofa_group_ready(const SofaGroup *G, int m);
+int sofa_group_channels(const SofaGroup *G, int m);
+int sofa_group_block(const SofaGroup *G, int m);
+uint64_t sofa_group_launches(const SofaGroup *G);
+int sofa_group_info(const SofaGroup *G, int m, int *partitions_K, int *fft_n, int *pending_filters, std::string *err);
+int sofa_group_run(SofaGroup *G, hipStream_t stream, const SofaSubmit *subs, int n, std::string *err);
 int sofa_setup(mi355_ctx *ctx, int channels, int filter_len, int partition_len, int block_len);
 int sofa_set_filter(mi355_ctx *ctx, int channel, const float *left, const float *right, int delay_left, int delay_right);
 int sofa_set_drop(mi355_ctx *ctx, int channel, int drop);

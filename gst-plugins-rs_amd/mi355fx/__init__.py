@@ -261,6 +261,15 @@ def load_library():
         "mi355_agroup_hrtf_info": (i, [vp, i, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_hrtf_last_lookup": (i, [vp, i, C.POINTER(C.c_int), f32p]),
         "mi355_agroup_hrtf_launches": (C.c_uint64, [vp]),
+        "mi355_agroup_create_sofa": (vp, [i, i, C.POINTER(C.c_int)]),
+        "mi355_agroup_shared_sofa": (vp, [i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mi355_agroup_sofa_setup": (i, [vp, i, i, i, i, i]),
+        "mi355_agroup_sofa_set_filter": (i, [vp, i, i, f32p, f32p, i, i]),
+        "mi355_agroup_sofa_set_drop": (i, [vp, i, i, i]),
+        "mi355_agroup_sofa_reset": (i, [vp, i]),
+        "mi355_agroup_submit_sofa": (i, [vp, i, vp, vp, i, f32p, i, C.POINTER(C.c_uint64)]),
+        "mi355_agroup_sofa_info": (i, [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mi355_agroup_sofa_launches": (C.c_uint64, [vp]),
         "mi355_time_hsvfilter_device": (i, [vp, u8p, i, sz, i, i, i, i, C.POINTER(HsvSettings), i, f32p]),
         "mi355_time_hsv_colorlut_device": (i, [vp, u8p, sz, i, u8p, sz, i, i, i, i, C.POINTER(HsvSettings), i, f32p]),
         "mi355_time_colorlut_device": (i, [vp, u8p, sz, i, u8p, sz, i, i, i, i, i, i, f32p]),
@@ -467,6 +476,8 @@ class AudioGroup:
                 self.h = self.L.mi355_agroup_shared_agingradio(device, n_members, C.byref(m), C.byref(st))
             elif kind == "hrtf":
                 self.h = self.L.mi355_agroup_shared_hrtf(device, n_members, C.byref(m), C.byref(st))
+            elif kind == "sofa":
+                self.h = self.L.mi355_agroup_shared_sofa(device, n_members, C.byref(m), C.byref(st))
             elif kind == "ebur128":
                 cc = kw.get("channel_class")
                 arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -485,6 +496,8 @@ class AudioGroup:
             self.h = self.L.mi355_agroup_create_agingradio(device, n_members, C.byref(st))
         elif kind == "hrtf":
             self.h = self.L.mi355_agroup_create_hrtf(device, n_members, C.byref(st))
+        elif kind == "sofa":
+            self.h = self.L.mi355_agroup_create_sofa(device, n_members, C.byref(st))
         elif kind == "ebur128":
             cc = kw.get("channel_class")
             arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -601,6 +614,58 @@ class AudioGroup:
 
     def hrtf_launches(self):
         return int(self.L.mi355_agroup_hrtf_launches(self.h))
+
+    # ---- sofalizer members
+    def sofa_setup(self, member, channels, filter_len, partition_length=64, block_length=256):
+        """set_caps of one member; the checks and messages of Context.sofa_setup"""
+        self._ck(self.L.mi355_agroup_sofa_setup(self.h, member, channels, filter_len, partition_length, block_length))
+        if not hasattr(self, "_sofa_shape"):
+            self._sofa_shape = {}
+        self._sofa_shape[member] = (channels, block_length)
+
+    def sofa_set_filter(self, member, channel, left, right, delay_left=0, delay_right=0):
+        """queued: copied now, transformed with the member's next launch set (a second call for the channel before that replaces it)"""
+        fp = C.POINTER(C.c_float)
+        l, r = np.ascontiguousarray(left, np.float32), np.ascontiguousarray(right, np.float32)
+        self._ck(self.L.mi355_agroup_sofa_set_filter(self.h, member, channel, l.ctypes.data_as(fp), r.ctypes.data_as(fp), delay_left, delay_right))
+
+    def sofa_set_drop(self, member, channel, drop=True):
+        self._ck(self.L.mi355_agroup_sofa_set_drop(self.h, member, channel, int(drop)))
+
+    def sofa_reset(self, member):
+        """flush-stop of one member: history cleared, filters (transformed and pending) kept"""
+        self._ck(self.L.mi355_agroup_sofa_reset(self.h, member))
+
+    def submit_sofa(self, member, inp, gains, n_blocks=1, out=None):
+        """n_blocks whole blocks. inp: numpy f32 [n_blocks * block_length, channels] (host; -> ticket, and the f32 [n_blocks * block_length, 2]
+        output array is sofa_output(member) once the ticket has been waited for) or a device pointer (then out: the device pointer of the output)."""
+        channels, block = self._sofa_shape[member]
+        fp = C.POINTER(C.c_float)
+        g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        assert g.size == channels
+        t = C.c_uint64(0)
+        if isinstance(inp, np.ndarray):
+            x = np.ascontiguousarray(inp, dtype=np.float32).reshape(-1)
+            assert x.size == max(n_blocks, 0) * block * channels or not 1 <= n_blocks <= 8, "a buffer = n_blocks * block_length frames"
+            y = np.zeros((max(n_blocks, 1) * block, 2), np.float32)
+            self._ck(self.L.mi355_agroup_submit_sofa(self.h, member, x.ctypes.data, y.ctypes.data, n_blocks, g.ctypes.data_as(fp), 0, C.byref(t)))
+            self._keep[member] = (x, y)   # (after the call: a refused submit leaves sofa_output(member) the array the outstanding ticket fills)
+        else:
+            self._ck(self.L.mi355_agroup_submit_sofa(self.h, member, inp, out, n_blocks, g.ctypes.data_as(fp), 1, C.byref(t)))
+        return t.value
+
+    def sofa_output(self, member):
+        """the output array of the member's last host submission (filled by wait)"""
+        return self._keep[member][1]
+
+    def sofa_info(self, member):
+        """(filter partitions K, transform size 2 * partition_length, filters pending)"""
+        k, n, pend = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self.L.mi355_agroup_sofa_info(self.h, member, C.byref(k), C.byref(n), C.byref(pend)))
+        return k.value, n.value, pend.value
+
+    def sofa_launches(self):
+        return int(self.L.mi355_agroup_sofa_launches(self.h))
 
     def submit_ebur128(self, member, data, frames=None, sample_format=None):
         t = C.c_uint64(0)

@@ -328,7 +328,7 @@ int mi355_group_compare_stats(mi355_group *group, uint64_t stats[3]);
  *   stats           : {buffers, launch sets, buffers in the largest set}.
  * A member's life cycle: a member has at most ONE buffer outstanding, from its submit_* until wait(ticket) has returned. Until then
  * another submit_* of that member and its setup / reset / load calls (agingradio_setup, ebur128_reset, hrtf_setup, hrtf_reset,
- * hrtf_load_sphere) are refused with MI355_ERR_INVALID_ARG - whether its launch set has run or not - and change nothing. A ticket is
+ * hrtf_load_sphere, sofa_setup, sofa_set_filter, sofa_set_drop, sofa_reset) are refused with MI355_ERR_INVALID_ARG - whether its launch set has run or not - and change nothing. A ticket is
  * collected once: wait takes only the member's outstanding ticket; a second wait for it, ticket 0, a ticket of a coming interval or
  * one the member was never given are refused with MI355_ERR_INVALID_ARG, run no launch set and write to no buffer. detach drops a
  * buffer whose launch set has not run (its wait answers "detached"); a result that has run can still be collected, once.
@@ -641,6 +641,45 @@ int mi355_sofa_reset(mi355_ctx *ctx);
 int mi355_sofa_teardown(mi355_ctx *ctx);
 int mi355_sofa_process_block(mi355_ctx *ctx, const float *in, float *out, const float *distance_gains);
 int mi355_sofa_process_block_device(mi355_ctx *ctx, const float *d_in, float *d_out, const float *distance_gains);
+/* sofalizer through an audio group (csrc/agroup.hip; audio/hrtf/src/sofa/imp.rs): members are fully independent instances, as
+ * hrtfrender members are - own channel count (1..64), filter length, partition-length and block-length each - and whoever has
+ * submitted shares ONE launch set: the filters set since the member's last buffer transformed (one launch per distinct partition
+ * length among them, none if nothing is pending), one convolution launch per distinct partition length among the members with one
+ * workgroup per (member, channel) that is not dropped, one mix; one upload and one download. A uniform group takes 2 launches per
+ * set, 3 in the interval after a source moved. A member's output is a lone context's, bit for bit.
+ *   mi355_agroup_create_sofa / _shared_sofa : a group of n_members sofalizer instances / THE group of the process (as _shared_hrtf).
+ *   mi355_agroup_sofa_setup : set_caps of one member (sofa/imp.rs:747-838; Renderer::builder with partition-length, :794-798). The
+ *       checks and messages of mi355_sofa_setup: "Block Length is not multiple of Partition Length" (:779-784) is
+ *       MI355_ERR_INVALID_ARG, a partition that is not a power of two in 8..2048 MI355_ERR_UNSUPPORTED. The member's device memory
+ *       and the group's tables are allocated here, never inside a launch set.
+ *   mi355_agroup_sofa_set_filter : Renderer::set_filter of one channel where State::update_filters calls it (:129-160). QUEUED: the
+ *       taps are copied at the call (onset delays folded in as mi355_sofa_set_filter folds them), nothing is launched or waited
+ *       for; the transform runs with the member's next launch set, so the pair takes effect with its next block. A second call for
+ *       the channel before that replaces the first. The pending filters of members that sit a launch set out stay pending.
+ *   mi355_agroup_sofa_set_drop : ChannelProcessor::Drop for LFE1 / LFE2 (:812-818; :253-255 skips it). After the member's first block
+ *       MI355_ERR_INVALID_ARG until reset or setup, as mi355_sofa_set_drop.
+ *   mi355_agroup_sofa_reset : State::reset_processors of one member (:123-127, flush-stop :846-853): input history cleared, filters
+ *       kept - transformed and pending alike; ordered after the member's last launch set.
+ *   mi355_agroup_submit_sofa : n_blocks (1..8) whole blocks at once - Sofalizer::process takes every whole block its adapter holds
+ *       (the `while state.adapter.available() >= inblksz` loop, :235-322): `in` [n_blocks * block_length][C] f32, `out`
+ *       [n_blocks * block_length][2] f32 (valid after mi355_agroup_wait, which answers the frames rendered), gains [C] (:307) copied
+ *       at submit and applied to all n_blocks; equal to n_blocks mi355_sofa_process_block calls in a row. device_data = 1: `in` /
+ *       `out` are device pointers. An undropped channel with no filter, transformed or pending: MI355_ERR_NOT_CONFIGURED.
+ *   mi355_agroup_sofa_info : the member's filter partitions K = ceil(filter_len / partition_length), its transform size 2 *
+ *       partition_length, and how many of its filters are pending. Before setup: MI355_ERR_NOT_CONFIGURED.
+ *   mi355_agroup_sofa_launches : kernel launches of the group's launch sets so far (:235-322 per member and block: two per member
+ *       and block for lone contexts). */
+mi355_agroup *mi355_agroup_create_sofa(int device, int n_members, int *status);
+mi355_agroup *mi355_agroup_shared_sofa(int device, int n_members, int *member, int *status);
+int mi355_agroup_sofa_setup(mi355_agroup *group, int member, int channels, int filter_len, int partition_length, int block_length);
+int mi355_agroup_sofa_set_filter(mi355_agroup *group, int member, int channel, const float *left, const float *right, int delay_left,
+                                 int delay_right);
+int mi355_agroup_sofa_set_drop(mi355_agroup *group, int member, int channel, int drop);
+int mi355_agroup_sofa_reset(mi355_agroup *group, int member);
+int mi355_agroup_submit_sofa(mi355_agroup *group, int member, const float *in, float *out, int n_blocks, const float *distance_gains,
+                             int device_data, uint64_t *ticket);
+int mi355_agroup_sofa_info(mi355_agroup *group, int member, int *partitions_K, int *fft_n, int *pending_filters);
+uint64_t mi355_agroup_sofa_launches(mi355_agroup *group);
 
 /* ---------------------------------------------------------------- pinned memory + asynchronous host-buffer pipeline
  * For the GStreamer shim (precedent video/colorlut/src/d3d12colorlut/imp.rs:385-492 and

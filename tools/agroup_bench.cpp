@@ -3,6 +3,7 @@
 // mi355_agroup (round 6). Prints one JSON line per element kind. Build: make -C tools agroup_bench (g++, links libmi355fx.so).
 // Run on the GPU box: tools/agroup_bench [instances] [all | audio | videocompare | dssim]
 //                     tools/agroup_bench [instances] hrtf [repeats] [mesh file]   (hrtfrender: its own section, tools/bench_hrtf_group.py drives it)
+//                     tools/agroup_bench [instances] sofa [repeats] [blocks per submit]   (sofalizer: its own section)
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -55,8 +56,123 @@ int main(int argc, char **argv) {
   const int S = argc > 1 ? std::atoi(argv[1]) : 32;
   const std::string section = argc > 2 ? argv[2] : "all";   // all | audio | videocompare | dssim
   const bool do_hrtf = section == "hrtf";
-  const bool do_audio = section == "all" || section == "audio", do_video = section != "audio" && !do_hrtf, dssim_only = section == "dssim";
+  const bool do_sofa = section == "sofa";
+  const bool do_audio = section == "all" || section == "audio", do_video = section != "audio" && !do_hrtf && !do_sofa, dssim_only = section == "dssim";
   int st = 0;
+  // ------------------------------------------------------------ sofalizer: S listeners x 6 channels (LFE dropped), 256-tap filters, partition 64, block 256 (5.3 ms at 48 kHz)
+  if (do_sofa) {
+    const int repeats = argc > 3 ? std::atoi(argv[3]) : 5, iters = 200;
+    const int nb = argc > 4 ? std::atoi(argv[4]) : 1;   // whole blocks a member hands over per interval
+    if (nb < 1 || nb > 8) { std::fprintf(stderr, "blocks per submit: 1..8\n"); return 1; }
+    const int C = 6, L = 256, P = 64, B = 256, lfe = 3, rate = 48000;
+    const size_t frames = (size_t)B * nb;
+    std::vector<mi355_ctx *> ctxs(S);
+    std::vector<std::vector<float>> in(S, std::vector<float>(frames * C)), out(S, std::vector<float>(frames * 2)), gains(S, std::vector<float>(C, 0.5f));
+    std::vector<void *> d_in(S), d_out(S);
+    mi355_agroup *g = mi355_agroup_create_sofa(0, S, &st);
+    if (!g) { std::fprintf(stderr, "no agroup: %d\n", st); return 1; }
+    CK(mi355_agroup_set_linger(g, 2000, 0));
+    uint64_t lcg = 0x4D49333535ull;
+    std::vector<float> hl(L), hr(L);
+    // every filter a seeded decaying noise burst; `which` picks one of a few so that a moving source has somewhere to go
+    auto filter = [&](int which) {
+      uint64_t v = lcg + 977ull * (uint64_t)which;
+      for (int k = 0; k < L; k++) {
+        v = v * 6364136223846793005ull + 1442695040888963407ull;
+        hl[k] = 0.3f * std::exp(-(float)k / 32.0f) * ((float)((v >> 40) & 0xFFFF) / 32768.0f - 1.0f);
+        v = v * 6364136223846793005ull + 1442695040888963407ull;
+        hr[k] = 0.3f * std::exp(-(float)k / 32.0f) * ((float)((v >> 40) & 0xFFFF) / 32768.0f - 1.0f);
+      }
+    };
+    for (int m = 0; m < S; m++) {
+      ctxs[m] = mi355_ctx_create(0, &st);
+      if (!ctxs[m]) { std::fprintf(stderr, "no context: %d\n", st); return 1; }
+      CK(mi355_sofa_setup(ctxs[m], C, L, P, B));
+      CK(mi355_agroup_sofa_setup(g, m, C, L, P, B));
+      CK(mi355_sofa_set_drop(ctxs[m], lfe, 1));
+      CK(mi355_agroup_sofa_set_drop(g, m, lfe, 1));
+      for (int c = 0; c < C; c++) {
+        if (c == lfe) continue;
+        filter(7 * m + c);
+        CK(mi355_sofa_set_filter(ctxs[m], c, hl.data(), hr.data(), c % 3, 0));
+        CK(mi355_agroup_sofa_set_filter(g, m, c, hl.data(), hr.data(), c % 3, 0));
+      }
+      for (size_t i = 0; i < frames * C; i++) in[m][i] = 0.1f * std::sin(0.01f * (float)(i + 17 * m));
+      d_in[m] = mi355_device_alloc(ctxs[m], frames * C * 4);
+      d_out[m] = mi355_device_alloc(ctxs[m], frames * 8);
+      CK(mi355_memcpy_h2d(ctxs[m], d_in[m], in[m].data(), frames * C * 4));
+    }
+    auto own_host = [&](int m, int) {
+      for (int b = 0; b < nb; b++) CK(mi355_sofa_process_block(ctxs[m], in[m].data() + (size_t)b * B * C, out[m].data() + (size_t)b * B * 2, gains[m].data()));
+    };
+    auto own_dev = [&](int m, int) {   // (process_block_device returns a finished buffer: it synchronises its stream)
+      for (int b = 0; b < nb; b++) CK(mi355_sofa_process_block_device(ctxs[m], (const float *)d_in[m] + (size_t)b * B * C, (float *)d_out[m] + (size_t)b * B * 2, gains[m].data()));
+    };
+    auto via_group = [&](int device) {
+      return [&, device](int m, int) {
+        uint64_t t = 0;
+        CK(mi355_agroup_submit_sofa(g, m, device ? (const float *)d_in[m] : in[m].data(), device ? (float *)d_out[m] : out[m].data(), nb, gains[m].data(), device, &t));
+        CK(mi355_agroup_wait(g, t, nullptr));
+      };
+    };
+    run_threads(S, 30, own_host);
+    run_threads(S, 30, via_group(0));
+    run_threads(S, 30, own_dev);
+    run_threads(S, 30, via_group(1));
+    uint64_t s0[3], s1[3];
+    CK(mi355_agroup_stats(g, s0));
+    const uint64_t l0 = mi355_agroup_sofa_launches(g);
+    // the four legs alternated inside one process, `repeats` times: medians and the spread
+    std::vector<double> t[4];
+    for (int r = 0; r < repeats; r++) {
+      t[0].push_back(run_threads(S, iters, own_host) / iters * 1e3);
+      t[1].push_back(run_threads(S, iters, via_group(0)) / iters * 1e3);
+      t[2].push_back(run_threads(S, iters, own_dev) / iters * 1e3);
+      t[3].push_back(run_threads(S, iters, via_group(1)) / iters * 1e3);
+    }
+    CK(mi355_agroup_stats(g, s1));
+    const uint64_t launches = mi355_agroup_sofa_launches(g) - l0, sets = s1[1] - s0[1], buffers = s1[0] - s0[0];
+    // uniform members, no filter pending: ONE convolution launch and the mix per launch set, whoever is in it
+    if (launches != 2 * sets) { std::fprintf(stderr, "sofa group: %llu launches in %llu launch sets, expected 2 per set\n", (unsigned long long)launches, (unsigned long long)sets); return 1; }
+    // a source of every member moves before every interval (one set_filter each): device buffers, own contexts against the group
+    std::vector<std::vector<float>> mv_l(5, std::vector<float>(L)), mv_r(5, std::vector<float>(L));
+    for (int k = 0; k < 5; k++) { filter(1000 + k); mv_l[k] = hl; mv_r[k] = hr; }
+    std::vector<double> tm[2];
+    for (int r = 0; r < repeats; r++) {
+      tm[0].push_back(run_threads(S, iters, [&](int m, int i) { CK(mi355_sofa_set_filter(ctxs[m], i % 3, mv_l[i % 5].data(), mv_r[i % 5].data(), 0, 0)); own_dev(m, i); }) / iters * 1e3);
+      tm[1].push_back(run_threads(S, iters, [&](int m, int i) { CK(mi355_agroup_sofa_set_filter(g, m, i % 3, mv_l[i % 5].data(), mv_r[i % 5].data(), 0, 0)); via_group(1)(m, i); }) / iters * 1e3);
+    }
+    // one thread, device buffers: every member submitted, then waited for (no thread wake-ups in the number)
+    const auto t0 = clk::now();
+    for (int i = 0; i < iters; i++) {
+      std::vector<uint64_t> tk(S);
+      for (int m = 0; m < S; m++) CK(mi355_agroup_submit_sofa(g, m, (const float *)d_in[m], (float *)d_out[m], nb, gains[m].data(), 1, &tk[m]));
+      for (int m = 0; m < S; m++) CK(mi355_agroup_wait(g, tk[m], nullptr));
+    }
+    const double one_thread = secs(t0, clk::now()) / iters * 1e3;
+    const double block_s = (double)frames / (double)rate;
+    const char *names[4] = {"own_context_host_buffers", "agroup_host_buffers", "own_context_device_buffers", "agroup_device_buffers"};
+    std::printf("{\"element\": \"sofalizer\", \"instances\": %d, \"block\": \"%d channels (1 dropped), %d-tap filters, partition %d, block %d x %d per interval (%.1f ms at 48 kHz), one native thread per instance, linger 2 ms\", \"repeats\": %d, \"iterations\": %d",
+                S, C, L, P, B, nb, block_s * 1e3, repeats, iters);
+    for (int k = 0; k < 4; k++) {
+      std::sort(t[k].begin(), t[k].end());
+      const double med = t[k][t[k].size() / 2];
+      std::printf(", \"%s_ms_per_interval\": {\"median\": %.4f, \"min\": %.4f, \"max\": %.4f}, \"%s_realtime_aggregate\": %.0f", names[k], med, t[k].front(), t[k].back(), names[k],
+                  S * block_s / (med * 1e-3));
+    }
+    const char *mnames[2] = {"own_context_device_buffers_moving_source", "agroup_device_buffers_moving_source"};
+    for (int k = 0; k < 2; k++) {
+      std::sort(tm[k].begin(), tm[k].end());
+      std::printf(", \"%s_ms_per_interval\": {\"median\": %.4f, \"min\": %.4f, \"max\": %.4f}", mnames[k], tm[k][tm[k].size() / 2], tm[k].front(), tm[k].back());
+    }
+    std::printf(", \"agroup_device_buffers_one_thread_ms_per_interval\": %.4f, \"agroup_launch_sets\": %llu, \"agroup_buffers\": %llu, \"agroup_largest_set\": %llu, "
+                "\"agroup_kernel_launches\": %llu, \"agroup_launches_per_launch_set\": 2, \"agroup_launches_per_interval\": %.2f, \"own_context_launches_per_interval\": %d}\n",
+                one_thread, (unsigned long long)sets, (unsigned long long)buffers, (unsigned long long)s1[2], (unsigned long long)launches,
+                (double)launches / (2.0 * repeats * iters), 2 * S * nb);
+    std::fflush(stdout);
+    mi355_agroup_destroy(g);
+    for (int m = 0; m < S; m++) { mi355_device_free(ctxs[m], d_in[m]); mi355_device_free(ctxs[m], d_out[m]); mi355_ctx_destroy(ctxs[m]); }
+  }
   // ------------------------------------------------------------ hrtfrender: S listeners x 8 sources, 256-tap sphere at 48 kHz, block 512 x 8 (85.3 ms)
   if (do_hrtf) {
     const int repeats = argc > 3 ? std::atoi(argv[3]) : 5, iters = 200;

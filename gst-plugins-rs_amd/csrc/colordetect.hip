@@ -10,6 +10,12 @@
 //                            solid content costs one LDS atomic per wave instead of 64 serialised ones.
 //   colordetect_mmcq_kernel  one block per frame: the histogram into LDS (and zeroed in HBM for the next call), the first box,
 //                            the two MMCQ phases with workgroup-uniform control flow, the palette. Only palettes leave the device.
+// A launch set of the video group's colordetect queue (group.hip: frames of INDEPENDENT element instances - each with its own plane
+// size, format, quality and max_colors) runs the same two steps over a job table instead of one pitch and one setting:
+//   colordetect_hist_jobs_kernel  1-D grid; a block finds its job (CdJob, up to 32 in the kernel arguments) from blockIdx and
+//                                 accumulates its share of that frame's samples exactly as above - dword or byte loads per job;
+//   colordetect_mmcq_jobs_kernel  one block per job, max_colors per job.
+//   colordetect_plan              the blocks of a set: one per CU in all, shared out by sample count (host; mi355_selftest_colordetect_plan).
 #include "internal.hpp"
 
 #include <cstring>
@@ -61,18 +67,11 @@ __device__ __forceinline__ void add_bin(uint32_t *h, uint32_t bin) {
   }
 }
 
-// WORD: 4-byte pixels at 4-byte aligned addresses, one dword load per sample; otherwise byte loads
+// samples [s0, s1) of the flat plane at `base` into the block's LDS histogram. WORD: 4-byte pixels at 4-byte aligned addresses,
+// one dword load per sample; otherwise byte loads. Called by every thread of the block with the same range.
 template <bool WORD>
-__global__ __launch_bounds__(kHistThreads) void colordetect_hist_kernel(const uint8_t *__restrict__ frames, size_t frame_pitch, size_t n_samples,
-                                                                         size_t step, size_t samples_per_block, Layout L, uint32_t *__restrict__ hist) {
-  extern __shared__ uint4 lds_hist4[];
-  uint32_t *h = reinterpret_cast<uint32_t *>(lds_hist4);
+__device__ __forceinline__ void hist_accumulate(uint32_t *h, const uint8_t *__restrict__ base, size_t s0, size_t s1, size_t step, const Layout &L) {
   const int tid = threadIdx.x;
-  for (int i = tid; i < kBins / 4; i += kHistThreads) lds_hist4[i] = make_uint4(0, 0, 0, 0);
-  __syncthreads();
-  const uint8_t *base = frames + (size_t)blockIdx.y * frame_pitch;
-  const size_t s0 = (size_t)blockIdx.x * samples_per_block;
-  const size_t s1 = s0 + samples_per_block < n_samples ? s0 + samples_per_block : n_samples;
   constexpr int U = 4;
   // the trip count is the same for every lane (ballots in add_bin need the whole wave)
   for (size_t s = s0; s < s1; s += (size_t)U * kHistThreads) {
@@ -101,15 +100,72 @@ __global__ __launch_bounds__(kHistThreads) void colordetect_hist_kernel(const ui
 #pragma unroll
     for (int u = 0; u < U; u++) add_bin(h, px[u][3] == kNoBin ? kNoBin : sample_bin(px[u][0], px[u][1], px[u][2], px[u][3]));
   }
+}
+
+__device__ __forceinline__ void hist_clear(uint4 *lds_hist4) {
+  for (int i = threadIdx.x; i < kBins / 4; i += kHistThreads) lds_hist4[i] = make_uint4(0, 0, 0, 0);
   __syncthreads();
-  uint32_t *g = hist + (size_t)blockIdx.y * kBins;
-  for (int i = tid; i < kBins / 4; i += kHistThreads) {
+}
+
+// the block's non-zero bins into the frame's histogram `g`
+__device__ __forceinline__ void hist_flush(const uint4 *lds_hist4, uint32_t *__restrict__ g) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < kBins / 4; i += kHistThreads) {
     const uint4 v = lds_hist4[i];
     if (v.x) atomicAdd(&g[4 * i + 0], v.x);
     if (v.y) atomicAdd(&g[4 * i + 1], v.y);
     if (v.z) atomicAdd(&g[4 * i + 2], v.z);
     if (v.w) atomicAdd(&g[4 * i + 3], v.w);
   }
+}
+
+template <bool WORD>
+__global__ __launch_bounds__(kHistThreads) void colordetect_hist_kernel(const uint8_t *__restrict__ frames, size_t frame_pitch, size_t n_samples,
+                                                                         size_t step, size_t samples_per_block, Layout L, uint32_t *__restrict__ hist) {
+  extern __shared__ uint4 lds_hist4[];
+  hist_clear(lds_hist4);
+  const uint8_t *base = frames + (size_t)blockIdx.y * frame_pitch;
+  const size_t s0 = (size_t)blockIdx.x * samples_per_block;
+  const size_t s1 = s0 + samples_per_block < n_samples ? s0 + samples_per_block : n_samples;
+  hist_accumulate<WORD>(reinterpret_cast<uint32_t *>(lds_hist4), base, s0, s1, step, L);
+  hist_flush(lds_hist4, hist + (size_t)blockIdx.y * kBins);
+}
+
+// one frame of a launch set: what its blocks need. The table travels in the kernel arguments (no upload, no lifetime); a block's
+// job index comes from blockIdx, so the fields are scalar loads and stay in SGPRs.
+struct CdJob {
+  const uint8_t *base;         // the flat plane (nullptr only with blocks == 0)
+  uint64_t samples_per_block;  // block b of the job takes samples [b * samples_per_block, ...) up to n_samples
+  uint32_t n_samples, step;    // every quality-th pixel: byte step = quality * channels
+  uint32_t first_block, blocks;  // its blocks in the 1-D grid (colordetect_plan)
+  Layout L;
+  int32_t word;                // 1: 4-byte pixels at a 4-byte aligned address (dword loads); 0: byte loads
+  int32_t pad;
+};
+struct CdJobTable {
+  CdJob job[kCdSetMax];
+  int32_t n_jobs, pad;
+};
+static_assert(sizeof(CdJobTable) <= 2048, "the job table is passed in the kernel arguments");
+struct CdSetColors { uint8_t max_colors[kCdSetMax]; };
+
+__global__ __launch_bounds__(kHistThreads) void colordetect_hist_jobs_kernel(const CdJobTable T, uint32_t *__restrict__ hist) {
+  extern __shared__ uint4 lds_hist4[];
+  const uint32_t b = blockIdx.x;
+  int j = 0;
+  while (j + 1 < T.n_jobs && b >= T.job[j].first_block + T.job[j].blocks) j++;
+  const uint32_t rel = b - T.job[j].first_block;
+  if (b < T.job[j].first_block || rel >= T.job[j].blocks) return;  // not reached: the grid is the plan's total (uniform per block)
+  hist_clear(lds_hist4);
+  const size_t n_samples = T.job[j].n_samples, per_block = T.job[j].samples_per_block;
+  const size_t s0 = (size_t)rel * per_block;
+  const size_t s1 = s0 + per_block < n_samples ? s0 + per_block : n_samples;
+  uint32_t *h = reinterpret_cast<uint32_t *>(lds_hist4);
+  const Layout L = T.job[j].L;
+  // the path is the job's, the same for every wave of the block
+  if (T.job[j].word) hist_accumulate<true>(h, T.job[j].base, s0, s1, T.job[j].step, L);
+  else hist_accumulate<false>(h, T.job[j].base, s0, s1, T.job[j].step, L);
+  hist_flush(lds_hist4, hist + (size_t)j * kBins);
 }
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
@@ -280,12 +336,13 @@ __device__ void mmcq_iter(MmcqShared &S, const uint32_t *H, int &n, bool &dirty,
   }
 }
 
-__global__ __launch_bounds__(kMmcqThreads) void colordetect_mmcq_kernel(uint32_t *__restrict__ hist, int max_colors, CdResult *__restrict__ out) {
+// one frame, by the whole block: its histogram `hist` into LDS (and zeroed in HBM), the first box, the two phases, the palette
+__device__ __forceinline__ void mmcq_frame(uint32_t *__restrict__ hist, int max_colors, CdResult *__restrict__ res) {
   extern __shared__ uint4 lds_hist4[];
   __shared__ MmcqShared S;
   uint32_t *H = reinterpret_cast<uint32_t *>(lds_hist4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint4 *g4 = reinterpret_cast<uint4 *>(hist + (size_t)blockIdx.x * kBins);
+  uint4 *g4 = reinterpret_cast<uint4 *>(hist);
   unsigned long long cnt = 0, sum[3] = {0, 0, 0};
   int mn[3] = {32, 32, 32}, mx[3] = {-1, -1, -1};
   for (int i = tid; i < kBins / 4; i += kMmcqThreads) {
@@ -329,7 +386,6 @@ __global__ __launch_bounds__(kMmcqThreads) void colordetect_mmcq_kernel(uint32_t
       mx[k] = max(mx[k], S.ired[3 + k][wv]);
     }
   }
-  CdResult *res = out + blockIdx.x;
   if (cnt == 0) {  // nothing kept: no colours
     if (tid < 6) res->box[tid] = -1;
     if (tid == 0) res->n_colors = 0;
@@ -358,6 +414,15 @@ __global__ __launch_bounds__(kMmcqThreads) void colordetect_mmcq_kernel(uint32_t
     res->rgb[3 * tid + 2] = (uint8_t)((a >> 16) & 255u);
   }
   if (tid == 0) res->n_colors = n;
+}
+
+__global__ __launch_bounds__(kMmcqThreads) void colordetect_mmcq_kernel(uint32_t *__restrict__ hist, int max_colors, CdResult *__restrict__ out) {
+  mmcq_frame(hist + (size_t)blockIdx.x * kBins, max_colors, out + blockIdx.x);
+}
+
+// a launch set: block = job, max_colors per job (a job without samples finds its histogram empty: 0 colours, box -1)
+__global__ __launch_bounds__(kMmcqThreads) void colordetect_mmcq_jobs_kernel(uint32_t *__restrict__ hist, const CdSetColors C, CdResult *__restrict__ out) {
+  mmcq_frame(hist + (size_t)blockIdx.x * kBins, (int)C.max_colors[blockIdx.x], out + blockIdx.x);
 }
 
 bool layout_of(int format, int *ch, Layout *L) {
@@ -426,15 +491,23 @@ static int colordetect_scratch(mi355_ctx *ctx, int n_frames, ColorDetectState **
   return MI355_OK;
 }
 
-static int colordetect_check(mi355_ctx *ctx, size_t data_len, int n_frames, int format, int quality, int max_colors, int *ch, Layout *L) {
-  if (!layout_of(format, ch, L)) return set_error(ctx, MI355_ERR_UNSUPPORTED, "colordetect: format is not RGB, RGBA, ARGB, BGR or BGRA");
-  if (quality < 1 || quality > 10) return set_error(ctx, MI355_ERR_INVALID_ARG, "colordetect: quality must be 1..10");
-  if (max_colors < 2 || max_colors > 255) return set_error(ctx, MI355_ERR_INVALID_ARG, "colordetect: max_colors must be 2..255");
-  if (n_frames < 0 || n_frames > 65535) return set_error(ctx, MI355_ERR_INVALID_ARG, "colordetect: n_frames must be 0..65535");
+static size_t samples_of(size_t data_len, int ch, int quality) { return (data_len / (size_t)ch + (size_t)quality - 1) / (size_t)quality; }
+
+static int colordetect_check_args(size_t data_len, int n_frames, int format, int quality, int max_colors, int *ch, Layout *L, const char **why) {
+  if (!layout_of(format, ch, L)) { *why = "colordetect: format is not RGB, RGBA, ARGB, BGR or BGRA"; return MI355_ERR_UNSUPPORTED; }
+  *why = nullptr;
+  if (quality < 1 || quality > 10) *why = "colordetect: quality must be 1..10";
+  else if (max_colors < 2 || max_colors > 255) *why = "colordetect: max_colors must be 2..255";
+  else if (n_frames < 0 || n_frames > 65535) *why = "colordetect: n_frames must be 0..65535";
   // bins are 32-bit: at most 2^32 - 1 samples per frame
-  const size_t n_samples = (data_len / (size_t)*ch + (size_t)quality - 1) / (size_t)quality;
-  if (n_samples > 0xffffffffull) return set_error(ctx, MI355_ERR_INVALID_ARG, "colordetect: more than 2^32 - 1 samples in a frame");
-  return MI355_OK;
+  else if (samples_of(data_len, *ch, quality) > 0xffffffffull) *why = "colordetect: more than 2^32 - 1 samples in a frame";
+  return *why ? MI355_ERR_INVALID_ARG : MI355_OK;
+}
+
+static int colordetect_check(mi355_ctx *ctx, size_t data_len, int n_frames, int format, int quality, int max_colors, int *ch, Layout *L) {
+  const char *why = nullptr;
+  const int rc = colordetect_check_args(data_len, n_frames, format, quality, max_colors, ch, L, &why);
+  return rc ? set_error(ctx, rc, why) : MI355_OK;
 }
 
 // both kernels on ctx->stream; the histograms are zero again once the MMCQ kernel has run
@@ -484,6 +557,145 @@ static int colordetect_collect(mi355_ctx *ctx, ColorDetectState *s, int n_frames
     std::memcpy(palette_rgb + (size_t)f * 255 * 3, r.rgb, (size_t)r.n_colors * 3);
   }
   return MI355_OK;
+}
+
+// ---------------------------------------------------------------- launch sets (the video group's colordetect queue, group.hip)
+
+int colordetect_check_frame(size_t data_len, int format, int quality, int max_colors, const char **why) {
+  int ch = 0;
+  Layout L{};
+  return colordetect_check_args(data_len, 1, format, quality, max_colors, &ch, &L, why);
+}
+
+// The blocks of one launch set. A histogram block holds 128 KiB of LDS, so a CU runs one: n_cu blocks in all. Every job with
+// samples gets one; what is left of n_cu is shared out by sample count (rounded down), up to the lone launch's limit of one block
+// per 16 Ki samples. The job's samples are then cut into equal shares and the block count is what those shares need, so no block
+// is empty: blocks * samples_per_block >= n_samples > (blocks - 1) * samples_per_block.
+int colordetect_plan(int n_cu, int n_jobs, const uint64_t *n_samples, uint32_t *first_block, uint32_t *blocks, uint64_t *samples_per_block, uint32_t *total_blocks) {
+  if (n_cu < 1 || n_jobs < 0 || n_jobs > kCdSetMax || !total_blocks || (n_jobs && (!n_samples || !first_block || !blocks || !samples_per_block)))
+    return MI355_ERR_INVALID_ARG;
+  uint64_t all = 0, with_samples = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    if (n_samples[j] > 0xffffffffull) return MI355_ERR_INVALID_ARG;
+    all += n_samples[j];
+    with_samples += n_samples[j] > 0;
+  }
+  const uint64_t spare = (uint64_t)n_cu > with_samples ? (uint64_t)n_cu - with_samples : 0;
+  uint32_t next = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    const uint64_t n = n_samples[j];
+    uint64_t b = 0, per = 0;
+    if (n) {
+      b = 1 + n * spare / all;  // n < 2^32, spare < 2^31: no overflow
+      const uint64_t by_work = (n + 16 * kHistThreads - 1) / (16 * kHistThreads);
+      if (b > by_work) b = by_work;
+      per = (n + b - 1) / b;
+      b = (n + per - 1) / per;
+    }
+    first_block[j] = next;
+    blocks[j] = (uint32_t)b;
+    samples_per_block[j] = per;
+    next += (uint32_t)b;
+  }
+  *total_blocks = next;
+  return MI355_OK;
+}
+
+struct CdSetScratch {
+  uint32_t *d_hist = nullptr;  // [kCdSetMax][kBins]
+  CdResult *d_res = nullptr;   // [kCdSetMax]
+  bool hist_zero = false;      // false after the allocation or an interrupted set: cleared before the next launch
+};
+
+void colordetect_set_scratch_free(CdSetScratch *S) {
+  if (!S) return;
+  if (S->d_hist) (void)hipFree(S->d_hist);
+  if (S->d_res) (void)hipFree(S->d_res);
+  delete S;
+}
+
+CdSetScratch *colordetect_set_scratch_new(hipStream_t stream, int *status, std::string *err) {
+  CdSetScratch *S = new CdSetScratch();
+  const size_t lds = kBins * sizeof(uint32_t), hist_bytes = (size_t)kCdSetMax * kBins * sizeof(uint32_t);
+  const char *what = nullptr;
+  int st = MI355_ERR_HIP;
+  if (hipMalloc((void **)&S->d_hist, hist_bytes) != hipSuccess) { what = "hipMalloc(colordetect set histograms)"; st = MI355_ERR_OUT_OF_MEMORY; }
+  else if (hipMalloc((void **)&S->d_res, (size_t)kCdSetMax * sizeof(CdResult)) != hipSuccess) { what = "hipMalloc(colordetect set results)"; st = MI355_ERR_OUT_OF_MEMORY; }
+  else if (hipMemsetAsync(S->d_hist, 0, hist_bytes, stream) != hipSuccess) what = "hipMemsetAsync(colordetect set histograms)";
+  else if (hipFuncSetAttribute((const void *)colordetect_hist_jobs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+           hipFuncSetAttribute((const void *)colordetect_mmcq_jobs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    what = "hipFuncSetAttribute(max dynamic LDS)";
+  if (what) {
+    (void)hipGetLastError();
+    colordetect_set_scratch_free(S);
+    *status = st;
+    *err = what;
+    return nullptr;
+  }
+  S->hist_zero = true;
+  *status = MI355_OK;
+  return S;
+}
+
+size_t colordetect_set_block_bytes() { return (size_t)kCdSetMax * sizeof(CdResult); }
+
+int colordetect_launch_set(CdSetScratch *S, hipStream_t stream, int n_cu, const CdFrame *frames, int n, void *h_block, int *kernel_launches, std::string *err) {
+  *kernel_launches = 0;
+  if (!S || !frames || !h_block || n < 1 || n > kCdSetMax) { *err = "colordetect: bad launch set"; return MI355_ERR_INVALID_ARG; }
+  CdJobTable T{};
+  CdSetColors C{};
+  uint64_t n_samples[kCdSetMax], per_block[kCdSetMax];
+  uint32_t first[kCdSetMax], blocks[kCdSetMax], total = 0;
+  int ch[kCdSetMax];
+  for (int i = 0; i < n; i++) {
+    if (!layout_of(frames[i].format, &ch[i], &T.job[i].L)) { *err = "colordetect: bad launch set"; return MI355_ERR_INVALID_ARG; }
+    n_samples[i] = samples_of(frames[i].data_len, ch[i], frames[i].quality);
+  }
+  int rc = colordetect_plan(n_cu, n, n_samples, first, blocks, per_block, &total);
+  if (rc) { *err = "colordetect: bad launch set"; return rc; }
+  for (int i = 0; i < n; i++) {
+    CdJob &J = T.job[i];
+    J.base = frames[i].data;
+    J.samples_per_block = per_block[i];
+    J.n_samples = (uint32_t)n_samples[i];
+    J.step = (uint32_t)(frames[i].quality * ch[i]);
+    J.first_block = first[i];
+    J.blocks = blocks[i];
+    J.word = ch[i] == 4 && (uintptr_t)frames[i].data % 4 == 0;
+    C.max_colors[i] = (uint8_t)frames[i].max_colors;
+  }
+  T.n_jobs = n;
+  auto hip_failed = [&](hipError_t e, const char *what) {
+    if (e == hipSuccess) return false;
+    (void)hipGetLastError();
+    *err = std::string(what) + ": " + hipGetErrorString(e);
+    return true;
+  };
+  const size_t lds = kBins * sizeof(uint32_t);
+  if (!S->hist_zero) {
+    if (hip_failed(hipMemsetAsync(S->d_hist, 0, (size_t)kCdSetMax * kBins * sizeof(uint32_t), stream), "hipMemsetAsync(colordetect set)")) return MI355_ERR_HIP;
+    S->hist_zero = true;
+  }
+  if (total > 0) {
+    S->hist_zero = false;
+    hipLaunchKernelGGL(colordetect_hist_jobs_kernel, dim3(total), dim3(kHistThreads), lds, stream, T, S->d_hist);
+    if (hip_failed(hipGetLastError(), "colordetect set histogram launch")) return MI355_ERR_HIP;
+    ++*kernel_launches;
+  }
+  S->hist_zero = false;
+  hipLaunchKernelGGL(colordetect_mmcq_jobs_kernel, dim3((unsigned)n), dim3(kMmcqThreads), lds, stream, S->d_hist, C, S->d_res);
+  if (hip_failed(hipGetLastError(), "colordetect set mmcq launch")) return MI355_ERR_HIP;
+  ++*kernel_launches;
+  S->hist_zero = true;  // the MMCQ kernel leaves every histogram it read zeroed
+  if (hip_failed(hipMemcpyAsync(h_block, S->d_res, (size_t)n * sizeof(CdResult), hipMemcpyDeviceToHost, stream), "colordetect set D2H")) return MI355_ERR_HIP;
+  return MI355_OK;
+}
+
+void colordetect_set_result(const void *h_block, int i, uint8_t palette_rgb[255 * 3], int *n_colors) {
+  const CdResult &r = static_cast<const CdResult *>(h_block)[i];
+  *n_colors = r.n_colors;
+  std::memset(palette_rgb, 0, 255 * 3);
+  std::memcpy(palette_rgb, r.rgb, (size_t)r.n_colors * 3);
 }
 
 }  // namespace mi355
@@ -556,6 +768,11 @@ int mi355_colordetect_histogram_device(mi355_ctx *ctx, const uint8_t *d_data, si
   if ((rc = colordetect_collect(ctx, s, 1, pal, &n))) return rc;
   std::memcpy(box, s->h_res[0].box, sizeof(s->h_res[0].box));
   return MI355_OK;
+}
+
+int mi355_selftest_colordetect_plan(int n_cu, int n_jobs, const uint64_t *n_samples, uint32_t *first_block, uint32_t *blocks, uint64_t *samples_per_block,
+                                    uint32_t *total_blocks) {
+  return colordetect_plan(n_cu, n_jobs, n_samples, first_block, blocks, samples_per_block, total_blocks);
 }
 
 }  // extern "C"

@@ -82,6 +82,23 @@ constexpr int kCmpMaxBatch = 32;                      // pairs per launch set (a
 constexpr int kCmpMaxLanes = 16;                      // HIP streams the pairs of one launch set are dealt out to
 constexpr size_t kCmpBlockBytes = 64 * 15 * 8 + 1024; // one pinned result block
 
+// ---- colordetect across independent element instances (mi355_group_submit_colordetect): one flat device plane per submit
+struct CdDesc {
+  CdFrame f;
+  uint64_t ticket;
+  hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing)
+};
+struct CdOut { int status, n_colors; uint8_t rgb[255 * 3]; };
+struct CdSet {
+  uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
+  std::vector<uint64_t> tickets;
+  hipEvent_t done;
+  int waiters;
+  void *h_block;  // pinned: the set's results (colordetect_set_result)
+  bool collected = false;
+};
+constexpr int kCdBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
+
 }  // namespace
 
 struct mi355_group {
@@ -118,6 +135,20 @@ struct mi355_group {
   int expected_streams = 0;                  // rendezvous: a waiter lingers until this many pairs are pending ...
   unsigned linger_us = 0;                    // ... or this long (mi355_group_set_rendezvous)
   std::condition_variable cv;                // "a compare batch has been launched"
+  // ---- colordetect queue: its own stream and scratch (created at the first submit), independent of the two queues above
+  hipStream_t cd_stream = nullptr;
+  CdSetScratch *cd_scratch = nullptr;
+  int cd_n_cu = 256;
+  std::vector<CdDesc> cd_pending;
+  std::deque<CdSet> cd_sets;                 // launched, oldest first
+  std::unordered_map<uint64_t, uint64_t> cd_where;   // ticket -> seq
+  std::unordered_map<uint64_t, CdOut> cd_results;    // finished (or failed), not yet collected by mi355_group_wait_colordetect
+  std::vector<void *> cd_blocks;             // free pinned result blocks
+  uint64_t next_cd_seq = 1;
+  uint64_t n_cd_frames = 0, n_cd_sets = 0, n_cd_largest = 0, n_cd_launches = 0;
+  int cd_expected = 0;                       // rendezvous over pending colordetect frames (mi355_group_set_colordetect_rendezvous)
+  unsigned cd_linger_us = 0;
+  std::condition_variable cd_cv;             // "a colordetect set has been launched"
 };
 
 namespace {
@@ -429,6 +460,161 @@ int cmp_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_
   return MI355_OK;
 }
 
+// ------------------------------------------------------------------ colordetect queue
+
+// is `ticket` a colordetect frame that has not been collected?
+bool cd_owns(mi355_group *g, uint64_t ticket) {
+  if (g->cd_where.count(ticket) || g->cd_results.count(ticket)) return true;
+  for (const CdDesc &d : g->cd_pending)
+    if (d.ticket == ticket) return true;
+  return false;
+}
+
+// stream, device scratch and the first pinned blocks: at the first submit, never inside a launch set. g->mu held.
+int cd_ensure(mi355_group *g) {
+  if (g->cd_scratch) return MI355_OK;
+  int n_cu = 0;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) (void)hipGetLastError();
+  g->cd_n_cu = n_cu > 0 ? n_cu : 256;
+  if (!g->cd_stream && hipStreamCreateWithFlags(&g->cd_stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    g->cd_stream = nullptr;
+    return fail(g, MI355_ERR_HIP, "group: no stream for the colordetect queue");
+  }
+  while ((int)g->cd_blocks.size() < kCdBlocksAtFirstUse) {
+    void *b = nullptr;
+    if (hipHostMalloc(&b, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the colordetect queue");
+    }
+    g->cd_blocks.push_back(b);
+  }
+  int st = MI355_OK;
+  std::string err;
+  g->cd_scratch = colordetect_set_scratch_new(g->cd_stream, &st, &err);
+  return g->cd_scratch ? MI355_OK : fail(g, st, "group: " + err);
+}
+
+// a finished set: its palettes from the pinned block into cd_results (once). g->mu held.
+void cd_collect(mi355_group *g, CdSet &s) {
+  if (s.collected) return;
+  s.collected = true;
+  if (g->cd_results.size() > 65536) g->cd_results.clear();   // (results nobody ever collected)
+  for (size_t i = 0; i < s.tickets.size(); i++) {
+    CdOut &o = g->cd_results[s.tickets[i]];
+    o.status = MI355_OK;
+    colordetect_set_result(s.h_block, (int)i, o.rgb, &o.n_colors);
+    g->cd_where.erase(s.tickets[i]);
+  }
+}
+
+// collected sets nobody waits inside leave: event and pinned block back to their free lists. g->mu held.
+void cd_retire(mi355_group *g) {
+  for (auto it = g->cd_sets.begin(); it != g->cd_sets.end();) {
+    if (it->collected && it->waiters == 0) {
+      g->cd_blocks.push_back(it->h_block);
+      g->events.push_back(it->done);
+      it = g->cd_sets.erase(it);
+    } else {
+      ++it;
+    }
+  }
+}
+
+// finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
+void cd_retire_done(mi355_group *g) {
+  for (CdSet &s : g->cd_sets) {
+    if (s.collected) continue;
+    if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
+    cd_collect(g, s);
+  }
+  cd_retire(g);
+}
+
+// launches the pending frames in submission order, kCdSetMax to a set (all of them, or up to the set that carries `until`):
+// consecutive sets on the queue's stream share the scratch, each has its own pinned block. g->mu held.
+int cd_flush_locked(mi355_group *g, uint64_t until = 0) {
+  bool reached = false;
+  int first_rc = MI355_OK;
+  while (!g->cd_pending.empty() && !reached) {
+    const size_t n = std::min(g->cd_pending.size(), (size_t)kCdSetMax);
+    std::vector<CdDesc> take(g->cd_pending.begin(), g->cd_pending.begin() + (std::ptrdiff_t)n);
+    g->cd_pending.erase(g->cd_pending.begin(), g->cd_pending.begin() + (std::ptrdiff_t)n);
+    int rc = MI355_OK, launches = 0;
+    std::string err;
+    hipEvent_t done = take_event(g);
+    if (g->cd_blocks.empty()) cd_retire_done(g);
+    void *block = nullptr;
+    if (!g->cd_blocks.empty()) { block = g->cd_blocks.back(); g->cd_blocks.pop_back(); }
+    // (more sets in flight than ever before: one more block, kept from then on)
+    else if (hipHostMalloc(&block, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); block = nullptr; }
+    if (!done || !block) { rc = MI355_ERR_HIP; err = "group: no event or pinned block for a colordetect set"; }
+    CdFrame frames[kCdSetMax];
+    for (size_t i = 0; i < n; i++) {
+      frames[i] = take[i].f;
+      if (!rc && take[i].ready && hipStreamWaitEvent(g->cd_stream, take[i].ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipStreamWaitEvent(colordetect frame)"; }
+    }
+    if (!rc) rc = colordetect_launch_set(g->cd_scratch, g->cd_stream, g->cd_n_cu, frames, (int)n, block, &launches, &err);
+    if (!rc && hipEventRecord(done, g->cd_stream) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipEventRecord(colordetect set)"; }
+    for (const CdDesc &d : take)
+      if (d.ready) g->events.push_back(d.ready);
+    if (rc) {
+      (void)hipGetLastError();
+      if (done) g->events.push_back(done);
+      if (block) g->cd_blocks.push_back(block);
+      g->last_error = "group: colordetect launch failed: " + err;
+      if (g->cd_results.size() > 65536) g->cd_results.clear();
+      for (const CdDesc &d : take) {   // told to the frame's own wait, once
+        CdOut &o = g->cd_results[d.ticket];
+        o.status = rc;
+        o.n_colors = 0;
+      }
+      if (!first_rc) first_rc = rc;
+      continue;
+    }
+    CdSet s{g->next_cd_seq++, {}, done, 0, block};
+    for (const CdDesc &d : take) { s.tickets.push_back(d.ticket); g->cd_where[d.ticket] = s.seq; reached |= until != 0 && d.ticket == until; }
+    g->cd_sets.push_back(std::move(s));
+    g->n_cd_frames += n;
+    g->n_cd_sets++;
+    if (n > g->n_cd_largest) g->n_cd_largest = n;
+    g->n_cd_launches += (uint64_t)launches;
+  }
+  g->cd_cv.notify_all();
+  return first_rc;
+}
+
+// host wait for the set of `ticket`; `lk` owns g->mu on entry and on return, not while waiting
+int cd_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
+  auto it = g->cd_where.find(ticket);
+  if (it == g->cd_where.end()) return MI355_OK;  // collected already (or failed: cd_results has it)
+  const uint64_t seq = it->second;
+  CdSet *mine = nullptr;
+  for (CdSet &s : g->cd_sets)
+    if (s.seq == seq) { mine = &s; break; }
+  if (!mine) return MI355_OK;
+  const hipEvent_t ev = mine->done;
+  mine->waiters++;
+  lk.unlock();
+  const hipError_t e = hipEventSynchronize(ev);
+  lk.lock();
+  for (CdSet &s : g->cd_sets)
+    if (s.seq == seq) { s.waiters--; break; }
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group colordetect set)"); }
+  for (CdSet &s : g->cd_sets)
+    if (s.seq <= seq) cd_collect(g, s);
+  cd_retire(g);
+  return MI355_OK;
+}
+
+// waits for every set launched so far (their results stay collectable)
+int cd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
+  uint64_t last = 0;
+  for (const CdSet &s : g->cd_sets)
+    if (!s.collected) last = s.tickets.front();
+  return last ? cd_wait_unlocking(g, lk, last) : MI355_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -474,6 +660,22 @@ void mi355_group_destroy(mi355_group *g) {
       if (g->alane[l]) mi355_ctx_destroy(g->alane[l]);
     }
   }
+  if (g->cd_stream) {
+    // frames still pending are launched and waited for, as pairs are
+    {
+      Locked L(g);
+      (void)cd_flush_locked(g);
+    }
+    (void)hipStreamSynchronize(g->cd_stream);
+    for (CdSet &s : g->cd_sets) { (void)hipEventDestroy(s.done); (void)hipHostFree(s.h_block); }
+    g->cd_sets.clear();
+    for (CdDesc &d : g->cd_pending)
+      if (d.ready) (void)hipEventDestroy(d.ready);
+    g->cd_pending.clear();
+    colordetect_set_scratch_free(g->cd_scratch);
+    (void)hipStreamDestroy(g->cd_stream);
+  }
+  for (void *b : g->cd_blocks) (void)hipHostFree(b);
   for (Batch &b : g->batches) (void)hipEventDestroy(b.done);   // (normally none left: wait_all retired them)
   for (Desc &d : g->pending)
     if (d.ready) (void)hipEventDestroy(d.ready);
@@ -564,7 +766,8 @@ int mi355_group_flush(mi355_group *g) {
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   const int rc = flush_locked(g);
   const int rc2 = g->actx ? cmp_flush_locked(g) : MI355_OK;
-  return rc ? rc : rc2;
+  const int rc3 = g->cd_scratch ? cd_flush_locked(g) : MI355_OK;
+  return rc ? rc : (rc2 ? rc2 : rc3);
 }
 
 // ---------------------------------------------------------------- videocompare pairs (Dssim / Blockhash) of independent elements
@@ -645,6 +848,7 @@ int mi355_group_wait_compare(mi355_group *g, uint64_t ticket, double *distance, 
   Locked L(g);
   std::unique_lock<std::mutex> &lk = L.lk;
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
+  if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   auto is_pending = [&]() { for (const CmpDesc &d : g->cmp_pending) if (d.ticket == ticket) return true; return false; };
   if (is_pending()) {
@@ -678,11 +882,98 @@ int mi355_group_compare_stats(mi355_group *g, uint64_t stats[3]) {
   return MI355_OK;
 }
 
+// ---------------------------------------------------------------- colordetect frames of independent elements
+
+int mi355_group_set_colordetect_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
+  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  g->cd_expected = expected_streams;
+  g->cd_linger_us = linger_us;
+  return MI355_OK;
+}
+
+int mi355_group_submit_colordetect(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_data, size_t data_len, int format, int quality, int max_colors,
+                                   uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context or ticket");
+  const char *why = nullptr;
+  int rc = colordetect_check_frame(data_len, format, quality, max_colors, &why);
+  if (rc) return fail(g, rc, why);
+  if (data_len && !d_data) return fail(g, MI355_ERR_INVALID_ARG, "colordetect: null frame");
+  if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
+  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+  if ((rc = cd_ensure(g))) return rc;
+  cd_retire_done(g);
+  CdDesc d{};
+  d.f = CdFrame{d_data, data_len, format, quality, max_colors};
+  d.ready = nullptr;
+  if (hipStreamQuery(ctx->stream) != hipSuccess) {   // the frame is read after what the context's stream holds now (an upload, a filter)
+    (void)hipGetLastError();
+    d.ready = take_event(g);
+    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      if (d.ready) g->events.push_back(d.ready);
+      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
+    }
+  }
+  d.ticket = g->next_ticket++;
+  *ticket = d.ticket;
+  g->cd_pending.push_back(d);
+  // everybody is here (rendezvous), or a launch set is full: go. The frame has been accepted whatever that launch does (a failure
+  // is told to the waits of the frames it carried).
+  const int full = g->cd_expected > 0 && g->cd_expected < kCdSetMax ? g->cd_expected : kCdSetMax;
+  if ((int)g->cd_pending.size() >= full) (void)cd_flush_locked(g);
+  return MI355_OK;
+}
+
+int mi355_group_wait_colordetect(mi355_group *g, uint64_t ticket, uint8_t palette_rgb[255 * 3], int *n_colors) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  std::unique_lock<std::mutex> &lk = L.lk;
+  if (!palette_rgb || !n_colors) return fail(g, MI355_ERR_INVALID_ARG, "group: null result arrays");
+  // a filter frame's, a pair's, a collected or an unknown ticket: refused before anything is launched or waited for
+  if (!cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: not the ticket of a colordetect frame that is still to be collected");
+  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+  auto is_pending = [&]() { for (const CdDesc &d : g->cd_pending) if (d.ticket == ticket) return true; return false; };
+  if (is_pending()) {
+    // rendezvous: the other instances of this interval are about to submit - linger for them (bounded), then launch what is there
+    if (g->cd_expected > 0 && g->cd_linger_us > 0) {
+      const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(g->cd_linger_us);
+      while (is_pending() && (int)g->cd_pending.size() < g->cd_expected) {
+        if (g->cd_cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
+      }
+    }
+    if (is_pending()) (void)cd_flush_locked(g, ticket);   // (a failure of this frame's own launch is in cd_results)
+  }
+  int rc = cd_wait_unlocking(g, lk, ticket);
+  if (rc) return rc;
+  auto r = g->cd_results.find(ticket);
+  if (r == g->cd_results.end()) return fail(g, MI355_ERR_INVALID_ARG, "group: this frame's palette has been collected already");   // (by a concurrent wait)
+  const CdOut res = r->second;
+  g->cd_results.erase(r);
+  if (res.status) return fail(g, res.status, "group: the launch that carried this colordetect frame failed");
+  std::memcpy(palette_rgb, res.rgb, sizeof(res.rgb));
+  *n_colors = res.n_colors;
+  return MI355_OK;
+}
+
+int mi355_group_colordetect_stats(mi355_group *g, uint64_t stats[4]) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  stats[0] = g->n_cd_frames;
+  stats[1] = g->n_cd_sets;
+  stats[2] = g->n_cd_largest;
+  stats[3] = g->n_cd_launches;
+  return MI355_OK;
+}
+
 int mi355_group_wait(mi355_group *g, uint64_t ticket) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
   std::unique_lock<std::mutex> &lk = L.lk;
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
+  if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -697,6 +988,7 @@ int mi355_group_order_after(mi355_group *g, mi355_ctx *ctx, uint64_t ticket) {
   if (!g || !ctx) return MI355_ERR_INVALID_ARG;
   Locked L(g);
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
+  if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -723,7 +1015,10 @@ int mi355_group_wait_all(mi355_group *g) {
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   int rc = flush_locked(g);
   if (rc) return rc;
-  return wait_all_unlocking(g, lk);
+  if ((rc = wait_all_unlocking(g, lk))) return rc;
+  if (!g->cd_scratch) return MI355_OK;
+  if ((rc = cd_flush_locked(g))) return rc;
+  return cd_wait_all_unlocking(g, lk);
 }
 
 int mi355_group_submit_round(mi355_group *g, mi355_ctx *const *ctxs, int n_streams, uint8_t *const *d_src, uint8_t *const *d_dst, int width, int height,

@@ -226,6 +226,19 @@ int dssim_cbrt_selftest(mi355_ctx *ctx, uint32_t lo_bits, uint32_t hi_bits, uint
 void dssim_release(mi355_ctx *ctx);
 void roundedcorners_release(mi355_ctx *ctx);
 void colordetect_release(mi355_ctx *ctx);
+// launch sets of the video group's colordetect queue (colordetect.hip): frames of independent instances, one job table
+constexpr int kCdSetMax = MI355_COLORDETECT_SET_MAX;
+struct CdFrame { const uint8_t *data; size_t data_len; int format, quality, max_colors; };
+struct CdSetScratch;  // kCdSetMax histograms (zero between sets) and results, on the device
+// the checks of mi355_colordetect_frames_device for one frame; *why names the refusal
+int colordetect_check_frame(size_t data_len, int format, int quality, int max_colors, const char **why);
+int colordetect_plan(int n_cu, int n_jobs, const uint64_t *n_samples, uint32_t *first_block, uint32_t *blocks, uint64_t *samples_per_block, uint32_t *total_blocks);
+CdSetScratch *colordetect_set_scratch_new(hipStream_t stream, int *status, std::string *err);
+void colordetect_set_scratch_free(CdSetScratch *S);
+size_t colordetect_set_block_bytes();  // the pinned block a set's results are copied to
+// n <= kCdSetMax checked frames on `stream`: histogram launch (none if no frame has a sample), MMCQ launch, results into h_block
+int colordetect_launch_set(CdSetScratch *S, hipStream_t stream, int n_cu, const CdFrame *frames, int n, void *h_block, int *kernel_launches, std::string *err);
+void colordetect_set_result(const void *h_block, int i, uint8_t palette_rgb[255 * 3], int *n_colors);
 
 // agingradio (agingradio.hip): one job = one element instance's buffer. The host fills the table (alpha and the quantise factor
 // computed with its libm); the group (agroup.hip) submits one job per member, a context a table of one.

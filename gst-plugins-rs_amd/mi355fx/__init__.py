@@ -197,6 +197,12 @@ def load_library():
         "mi355_group_submit_compare": (i, [vp, vp, u8p, u8p, i, i, i, i, i, C.POINTER(C.c_uint64)]),
         "mi355_group_wait_compare": (i, [vp, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
         "mi355_group_compare_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_group_set_colordetect_rendezvous": (i, [vp, i, C.c_uint]),
+        "mi355_group_submit_colordetect": (i, [vp, vp, vp, sz, i, i, i, C.POINTER(C.c_uint64)]),
+        "mi355_group_wait_colordetect": (i, [vp, C.c_uint64, u8p, C.POINTER(C.c_int)]),
+        "mi355_group_colordetect_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_colordetect_plan": (i, [i, i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_uint32)]),
         "mi355_agroup_create_echo": (vp, [i, i, sz, C.POINTER(C.c_int)]),
         "mi355_agroup_create_ebur128": (vp, [i, i, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_create_loudnorm": (vp, [i, i, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int)]),
@@ -450,6 +456,29 @@ class Group:
         c = (C.c_uint64 * 3)()
         self._ck(self.L.mi355_group_compare_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2])
+
+    # ---- colordetect frames of independent elements
+    def set_colordetect_rendezvous(self, expected_streams, linger_us):
+        self._ck(self.L.mi355_group_set_colordetect_rendezvous(self.h, expected_streams, linger_us))
+
+    def submit_colordetect(self, ctx, d_data, data_len, fmt, quality=10, max_colors=2):
+        """One flat device plane of stream `ctx` (plane_data(0): strides ignored); returns the ticket."""
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_colordetect(self.h, ctx.h, d_data, data_len, FMT[fmt], quality, max_colors, C.byref(t)))
+        return t.value
+
+    def wait_colordetect(self, ticket):
+        """The frame's palette: a list of (r, g, b) in palette order, as Context.colordetect_frames_device returns per frame."""
+        pal = np.zeros(255 * 3, np.uint8)
+        n = C.c_int(0)
+        self._ck(self.L.mi355_group_wait_colordetect(self.h, ticket, pal.ctypes.data, C.byref(n)))
+        return [tuple(int(v) for v in pal[3 * k: 3 * k + 3]) for k in range(n.value)]
+
+    def colordetect_stats(self):
+        """(frames launched, launch sets, frames in the largest set, kernel launches)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.L.mi355_group_colordetect_stats(self.h, c))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
     def close(self):
         if self.h:

@@ -7,7 +7,10 @@
  * runs on the GPU: mi355_colordetect_frame) and color_changed :86-113 (one "colordetect" element message per change of the
  * dominant colour's css name).
  * A buffer of our device memory (gst_mi355_buffer_peek_device) is read where it lies: mi355_colordetect_frames_device on its
- * device pointer, only the palette comes back. */
+ * device pointer, only the palette comes back. With MI355_GROUP_MEMBERS=n (n >= 2) in the environment the n
+ * instances of the process hand those device frames to the device's dispatcher instead (mi355_group_submit_colordetect): the
+ * frames of an interval share one histogram launch, one MMCQ launch and one copy. */
+#include <stdlib.h>
 #include <string.h>
 
 #include "../gst-plugins-rs_amd/host/mi355fx_host.h"
@@ -32,6 +35,8 @@ struct _GstColorDetect {
   int format;
   gchar *current_color;
   mi355_ctx *ctx;
+  /* MI355_GROUP_MEMBERS=n: the process's dispatcher (mi355_group_shared), held between start and stop */
+  mi355_group *group;
 };
 
 G_DEFINE_TYPE(GstColorDetect, gst_color_detect, GST_TYPE_VIDEO_FILTER)
@@ -74,6 +79,9 @@ static gboolean gst_color_detect_start(GstBaseTransform *trans) {
     GST_ELEMENT_ERROR(self, LIBRARY, INIT, ("No MI355X context"), ("%s", mi355_status_string(status)));
     return FALSE;
   }
+  const char *members = g_getenv("MI355_GROUP_MEMBERS");
+  if (members && atoi(members) >= 2 && (self->group = mi355_group_shared(0, &status)))
+    (void)mi355_group_set_colordetect_rendezvous(self->group, atoi(members), 2000); /* every instance submits + waits at once; a straggler is waited for 2 ms */
   return TRUE;
 }
 
@@ -83,6 +91,8 @@ static gboolean gst_color_detect_stop(GstBaseTransform *trans) {
   self->have_state = FALSE;
   g_free(self->current_color);
   self->current_color = NULL;
+  if (self->group) mi355_group_release(self->group);
+  self->group = NULL;
   if (self->ctx) mi355_ctx_destroy(self->ctx);
   self->ctx = NULL;
   GST_INFO_OBJECT(self, "Stopped");
@@ -130,10 +140,19 @@ static GstFlowReturn gst_color_detect_detect(GstColorDetect *self, const uint8_t
   g_mutex_unlock(&self->lock);
   uint8_t rgb[255 * 3];
   int n = 0;
-  const int rc = d_data ? mi355_colordetect_frames_device(self->ctx, d_data, size, size, 1, self->format, (int)quality, (int)max_colors, rgb, &n)
-                        : mi355_colordetect_frame(self->ctx, data, size, self->format, (int)quality, (int)max_colors, rgb, &n);
+  int rc;
+  const gboolean grouped = d_data && self->group;
+  if (grouped) { /* the frame joins whatever the other instances have pending; the palette is the lone call's, byte for byte */
+    uint64_t ticket = 0;
+    rc = mi355_group_submit_colordetect(self->group, self->ctx, d_data, size, self->format, (int)quality, (int)max_colors, &ticket);
+    if (rc == MI355_OK) rc = mi355_group_wait_colordetect(self->group, ticket, rgb, &n);
+  } else {
+    rc = d_data ? mi355_colordetect_frames_device(self->ctx, d_data, size, size, 1, self->format, (int)quality, (int)max_colors, rgb, &n)
+                : mi355_colordetect_frame(self->ctx, data, size, self->format, (int)quality, (int)max_colors, rgb, &n);
+  }
   if (rc != MI355_OK || n == 0) { /* get_palette's Err -> FlowError::Error; no colour: the reference fails at palette[0] */
-    GST_ERROR_OBJECT(self, "colordetect: %s", rc != MI355_OK ? mi355_ctx_last_error(self->ctx) : "no colour in the frame");
+    GST_ERROR_OBJECT(self, "colordetect: %s",
+                     rc == MI355_OK ? "no colour in the frame" : (grouped ? mi355_group_last_error(self->group) : mi355_ctx_last_error(self->ctx)));
     return GST_FLOW_ERROR;
   }
   const gchar *name = mi355host_css_color_similar(rgb[0], rgb[1], rgb[2]);

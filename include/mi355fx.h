@@ -299,6 +299,45 @@ int mi355_group_wait_compare(mi355_group *group, uint64_t ticket, double *distan
 /* {pairs launched, launch sequences, pairs in the largest one} */
 int mi355_group_compare_stats(mi355_group *group, uint64_t stats[3]);
 
+/* colordetect across independent element instances. The reference runs get_palette once per frame and element
+ * (video/videofx/src/colordetect/imp.rs:57-84); N instances in one process are N times two short launches, an 800-byte copy and a
+ * host synchronisation, and a lone frame's histogram launch cannot fill the device (one block per 16 Ki samples, 128 KiB of LDS
+ * each). submit_colordetect queues one flat device plane of stream `ctx` - plane_data(0) as the lone entry points read it: strides
+ * ignored, every quality-th pixel of floor(data_len / channels) - and whatever is pending goes out as ONE histogram launch over a
+ * job table, ONE MMCQ launch and ONE copy of the palettes, on the queue's own HIP stream. Members are fully independent: each
+ * frame has its own size, format, quality and max_colors. wait_colordetect returns what mi355_colordetect_frames_device(ctx,
+ * d_data, data_len, data_len, 1, format, quality, max_colors, ...) returns for that plane, byte for byte (integer arithmetic
+ * only): n_colors entries in palette order, the rest of the 765 bytes zero; a plane where no sample is kept gives 0 colours.
+ *   submit : never blocks; the checks and status codes are those of mi355_colordetect_frames_device with n_frames = 1 (format,
+ *           quality 1..10, max_colors 2..255, at most 2^32 - 1 samples; a null d_data with data_len > 0, a null ctx or a null
+ *           ticket: MI355_ERR_INVALID_ARG). A refused submit queues nothing. The frame is read after what ctx's HIP stream held at
+ *           the call, and until wait_colordetect for its ticket has returned.
+ *   wait   : launches what is pending if the frame has not gone out (rendezvous first), then waits for its launch set; the
+ *           group's lock is not held meanwhile. A result is collected once. Tickets are one sequence per group: a ticket that is
+ *           unknown, already collected, a filter frame's or a compare pair's is MI355_ERR_INVALID_ARG here and stays collectable
+ *           where it belongs; mi355_group_wait, _order_after and _wait_compare refuse a colordetect ticket likewise.
+ *   set_colordetect_rendezvous : as set_rendezvous, counted over pending colordetect frames only. The compare queue's
+ *           rendezvous, lanes and stats and this queue's do not touch each other.
+ *   At most MI355_COLORDETECT_SET_MAX frames share a launch set; more go out as consecutive sets. flush, wait_all and destroy
+ *   cover this queue as they cover pairs. A launch that fails is reported to the call that caused it and, once, to each frame's
+ *   own wait. Scratch (the set's histograms and results on the device, pinned result blocks) belongs to the group and is
+ *   allocated at the first submit.
+ *   colordetect_stats : {frames launched, launch sets, frames in the largest set, kernel launches} - a set is two launches, one
+ *           when none of its frames has a sample.
+ *   mi355_selftest_colordetect_plan : host only, no device: the blocks of one launch set's histogram grid for n_jobs frames of
+ *           n_samples[j] samples on n_cu CUs - one block per CU in all, shared out by sample count; every frame with samples
+ *           gets at least one and at most ceil(n_samples / 16384), a frame without samples none; first_block is the running sum. */
+#define MI355_COLORDETECT_SET_MAX 32 /* frames per launch set */
+int mi355_group_set_colordetect_rendezvous(mi355_group *group, int expected_streams, unsigned linger_us);
+int mi355_group_submit_colordetect(mi355_group *group, mi355_ctx *ctx, const uint8_t *d_data, size_t data_len, int format, int quality,
+                                   int max_colors, uint64_t *ticket);
+int mi355_group_wait_colordetect(mi355_group *group, uint64_t ticket, uint8_t palette_rgb[255 * 3], int *n_colors);
+/* {frames launched, launch sets, frames in the largest set, kernel launches} */
+int mi355_group_colordetect_stats(mi355_group *group, uint64_t stats[4]);
+/* host only, no device: the block plan of one launch set */
+int mi355_selftest_colordetect_plan(int n_cu, int n_jobs, const uint64_t *n_samples, uint32_t *first_block, uint32_t *blocks,
+                                    uint64_t *samples_per_block, uint32_t *total_blocks);
+
 /* ---------------------------------------------------------------- many AUDIO element instances, few launches (csrc/agroup.hip)
  * rsaudioecho (audio/audiofx/src/audioecho/imp.rs:205-227), ebur128level (audio/audiofx/src/ebur128level/imp.rs:682-745) and
  * audioloudnorm (audio/audiofx/src/audioloudnorm/imp.rs:1545-1586) are one instance per stream and one buffer per call; the batch
@@ -363,7 +402,7 @@ int mi355_agroup_ebur128_peak(mi355_agroup *group, int member, int true_peak, un
 int mi355_agroup_echo_get_state(mi355_agroup *group, int member, double *ring_out, size_t ring_len, size_t *pos_out);
 int mi355_agroup_stats(mi355_agroup *group, uint64_t stats[3]);
 /* Process-wide groups. Elements of independent pipelines cannot hand a group to each other; what they share is the process
- * (gst/gstrsaudioecho.c, gstebur128level.c, gstaudioloudnorm.c, gstvideocompare.c with MI355_GROUP_MEMBERS=n in the environment).
+ * (gst/gstrsaudioecho.c, gstebur128level.c, gstaudioloudnorm.c, gstvideocompare.c, gstcolordetect.c with MI355_GROUP_MEMBERS=n in the environment).
  *   mi355_agroup_shared_* : THE group of this configuration (kind, device, member count, parameters), created at first use, and
  *           the next free member index in *member; a group whose members have all been handed out is not offered again.
  *   mi355_agroup_release  : detach; the last member out destroys the group.

@@ -349,19 +349,37 @@ static bool detect_in_fmt(int fmt, PixFmt *p) {
   }
 }
 
+}  // extern "C"
+
+namespace mi355 {
+// The argument checks of the device entry, shared with the group's detector queue (group.hip: mi355_group_submit_hsvdetect), so
+// that a frame the one accepts is a frame the other accepts. MI355_OK with an empty batch means "nothing to do".
+int hsvdetect_check_frames(const uint8_t *d_src, int src_stride, int src_format, const uint8_t *d_dst, int dst_stride, int dst_format, int n_frames,
+                           int width, int height, const mi355_hsvdetect_settings *settings, PixFmt *sfmt, int *alpha_first, int *bgr, const char **why) {
+  if (!settings || !detect_in_fmt(src_format, sfmt) || !detect_out_fmt(dst_format, alpha_first, bgr)) { *why = "hsvdetector: bad settings/format"; return MI355_ERR_INVALID_ARG; }
+  if (n_frames < 0 || width < 0 || height < 0) { *why = "hsvdetector: negative size"; return MI355_ERR_INVALID_ARG; }
+  if (n_frames == 0 || width == 0 || height == 0) return MI355_OK;
+  if (!d_src || !d_dst) { *why = "hsvdetector: null data"; return MI355_ERR_INVALID_ARG; }
+  if ((size_t)src_stride < (size_t)width * sfmt->pixel_stride || (size_t)dst_stride < (size_t)width * 4) {
+    *why = "hsvdetector: line bytes exceed stride";
+    return MI355_ERR_INVALID_ARG;
+  }
+  return MI355_OK;
+}
+}  // namespace mi355
+
+extern "C" {
+
 int mi355_hsvdetect_frames_device(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, int src_format,
                                   uint8_t *d_dst, size_t dst_pitch, int dst_stride, int dst_format, int n_frames,
                                   int width, int height, const mi355_hsvdetect_settings *settings) {
   REQUIRE_CTX(ctx);
   PixFmt sfmt;
   int af = 0, bgr = 0;
-  if (!settings || !detect_in_fmt(src_format, &sfmt) || !detect_out_fmt(dst_format, &af, &bgr))
-    return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvdetector: bad settings/format");
-  if (n_frames < 0 || width < 0 || height < 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvdetector: negative size");
+  const char *why = nullptr;
+  const int bad = hsvdetect_check_frames(d_src, src_stride, src_format, d_dst, dst_stride, dst_format, n_frames, width, height, settings, &sfmt, &af, &bgr, &why);
+  if (bad) return set_error(ctx, bad, why);
   if (n_frames == 0 || width == 0 || height == 0) return MI355_OK;
-  if (!d_src || !d_dst) return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvdetector: null data");
-  if ((size_t)src_stride < (size_t)width * sfmt.pixel_stride || (size_t)dst_stride < (size_t)width * 4)
-    return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvdetector: line bytes exceed stride");
   BIND_DEVICE(ctx);
   const int rc = launch_hsvdetect(ctx, d_src, src_pitch, src_stride, sfmt, d_dst, dst_pitch, dst_stride, af, bgr, n_frames, width, height, *settings);
   if (rc == MI355_OK) note_written(ctx->device, d_dst, (size_t)(n_frames - 1) * dst_pitch + (size_t)dst_stride * (size_t)height);

@@ -19,6 +19,10 @@
 //   * results are the two element launches', bit for bit (same arithmetic, same table);
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
+// Three more queues live beside the filter batches, each with its own HIP stream, pending list, rendezvous and stats, and none
+// touching another: videocompare pairs (submit_compare), colordetect frames (submit_colordetect) and hsvdetector frames
+// (submit_hsvdetect: up to 32 frames of independent instances - own size, strides, formats, settings - as at most two launches
+// over a job table, hsv_kernels.hip). Tickets are one sequence; a wait entry refuses a ticket of another queue.
 // No persistent kernel: nothing here can hang the GPU waiting for the host, a launch is a launch.
 #include "internal.hpp"
 
@@ -99,6 +103,22 @@ struct CdSet {
 };
 constexpr int kCdBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
 
+
+// ---- hsvdetector across independent element instances (mi355_group_submit_hsvdetect): one device frame per submit, written in
+// place on the device - nothing comes back but the launch's status
+struct HdDesc {
+  HdFrame f;
+  uint64_t ticket;
+  hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing)
+};
+struct HdSet {
+  uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
+  std::vector<uint64_t> tickets;
+  hipEvent_t done;
+  int waiters;
+  bool collected = false;
+};
+
 }  // namespace
 
 struct mi355_group {
@@ -149,6 +169,18 @@ struct mi355_group {
   int cd_expected = 0;                       // rendezvous over pending colordetect frames (mi355_group_set_colordetect_rendezvous)
   unsigned cd_linger_us = 0;
   std::condition_variable cd_cv;             // "a colordetect set has been launched"
+  // ---- hsvdetector queue: its own stream (created at the first submit), independent of the three queues above
+  hipStream_t hd_stream = nullptr;
+  int hd_n_cu = 256;
+  std::vector<HdDesc> hd_pending;
+  std::deque<HdSet> hd_sets;                 // launched, oldest first
+  std::unordered_map<uint64_t, uint64_t> hd_where;   // ticket -> seq
+  std::unordered_map<uint64_t, int> hd_results;      // status of frames finished (or failed), not yet collected by mi355_group_wait_hsvdetect
+  uint64_t next_hd_seq = 1;
+  uint64_t n_hd_frames = 0, n_hd_sets = 0, n_hd_largest = 0, n_hd_launches = 0;
+  int hd_expected = 0;                       // rendezvous over pending detector frames (mi355_group_set_hsvdetect_rendezvous)
+  unsigned hd_linger_us = 0;
+  std::condition_variable hd_cv;             // "a detector set has been launched"
 };
 
 namespace {
@@ -615,6 +647,143 @@ int cd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
   return last ? cd_wait_unlocking(g, lk, last) : MI355_OK;
 }
 
+// ------------------------------------------------------------------ hsvdetector queue
+
+// is `ticket` a detector frame that has not been collected?
+bool hd_owns(mi355_group *g, uint64_t ticket) {
+  if (g->hd_where.count(ticket) || g->hd_results.count(ticket)) return true;
+  for (const HdDesc &d : g->hd_pending)
+    if (d.ticket == ticket) return true;
+  return false;
+}
+
+// the queue's stream: at the first submit, never inside a launch set. g->mu held.
+int hd_ensure(mi355_group *g) {
+  if (g->hd_stream) return MI355_OK;
+  int n_cu = 0;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) (void)hipGetLastError();
+  g->hd_n_cu = n_cu > 0 ? n_cu : 256;
+  if (hipStreamCreateWithFlags(&g->hd_stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    g->hd_stream = nullptr;
+    return fail(g, MI355_ERR_HIP, "group: no stream for the hsvdetector queue");
+  }
+  return MI355_OK;
+}
+
+// a finished set: its frames become collectable (once). g->mu held.
+void hd_collect(mi355_group *g, HdSet &s) {
+  if (s.collected) return;
+  s.collected = true;
+  if (g->hd_results.size() > 65536) g->hd_results.clear();   // (results nobody ever collected)
+  for (uint64_t t : s.tickets) {
+    g->hd_results[t] = MI355_OK;
+    g->hd_where.erase(t);
+  }
+}
+
+// collected sets nobody waits inside leave: the event goes back to the free list. g->mu held.
+void hd_retire(mi355_group *g) {
+  for (auto it = g->hd_sets.begin(); it != g->hd_sets.end();) {
+    if (it->collected && it->waiters == 0) {
+      g->events.push_back(it->done);
+      it = g->hd_sets.erase(it);
+    } else {
+      ++it;
+    }
+  }
+}
+
+// finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
+void hd_retire_done(mi355_group *g) {
+  for (HdSet &s : g->hd_sets) {
+    if (s.collected) continue;
+    if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
+    hd_collect(g, s);
+  }
+  hd_retire(g);
+}
+
+// launches the pending frames in submission order, kHdSetMax to a set (all of them, or up to the set that carries `until`), as
+// consecutive sets on the queue's stream. g->mu held.
+int hd_flush_locked(mi355_group *g, uint64_t until = 0) {
+  bool reached = false;
+  int first_rc = MI355_OK;
+  while (!g->hd_pending.empty() && !reached) {
+    const size_t n = std::min(g->hd_pending.size(), (size_t)kHdSetMax);
+    std::vector<HdDesc> take(g->hd_pending.begin(), g->hd_pending.begin() + (std::ptrdiff_t)n);
+    g->hd_pending.erase(g->hd_pending.begin(), g->hd_pending.begin() + (std::ptrdiff_t)n);
+    int rc = MI355_OK, launches = 0;
+    std::string err;
+    hipEvent_t done = take_event(g);
+    if (!done) { rc = MI355_ERR_HIP; err = "group: no event for a hsvdetector set"; }
+    HdFrame frames[kHdSetMax];
+    for (size_t i = 0; i < n; i++) {
+      frames[i] = take[i].f;
+      if (!rc && take[i].ready && hipStreamWaitEvent(g->hd_stream, take[i].ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipStreamWaitEvent(hsvdetector frame)"; }
+    }
+    if (!rc) rc = hsvdetect_launch_set(g->hd_stream, g->hd_n_cu, frames, (int)n, &launches, &err);
+    if (!rc && hipEventRecord(done, g->hd_stream) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipEventRecord(hsvdetector set)"; }
+    for (const HdDesc &d : take)
+      if (d.ready) g->events.push_back(d.ready);
+    if (rc) {
+      (void)hipGetLastError();
+      if (done) g->events.push_back(done);
+      g->last_error = "group: hsvdetector launch failed: " + err;
+      if (g->hd_results.size() > 65536) g->hd_results.clear();
+      for (const HdDesc &d : take) g->hd_results[d.ticket] = rc;   // told to the frame's own wait, once
+      if (!first_rc) first_rc = rc;
+      continue;
+    }
+    HdSet s{g->next_hd_seq++, {}, done, 0};
+    for (const HdDesc &d : take) {
+      s.tickets.push_back(d.ticket);
+      g->hd_where[d.ticket] = s.seq;
+      reached |= until != 0 && d.ticket == until;
+      // what the element behind finds on-die, as the lone entry records it
+      if (d.f.width > 0 && d.f.height > 0) note_written(g->device, d.f.dst, (size_t)d.f.dst_stride * (size_t)d.f.height);
+    }
+    g->hd_sets.push_back(std::move(s));
+    g->n_hd_frames += n;
+    g->n_hd_sets++;
+    if (n > g->n_hd_largest) g->n_hd_largest = n;
+    g->n_hd_launches += (uint64_t)launches;
+  }
+  g->hd_cv.notify_all();
+  return first_rc;
+}
+
+// host wait for the set of `ticket`; `lk` owns g->mu on entry and on return, not while waiting
+int hd_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
+  auto it = g->hd_where.find(ticket);
+  if (it == g->hd_where.end()) return MI355_OK;  // collected already (or failed: hd_results has it)
+  const uint64_t seq = it->second;
+  HdSet *mine = nullptr;
+  for (HdSet &s : g->hd_sets)
+    if (s.seq == seq) { mine = &s; break; }
+  if (!mine) return MI355_OK;
+  const hipEvent_t ev = mine->done;
+  mine->waiters++;
+  lk.unlock();
+  const hipError_t e = hipEventSynchronize(ev);
+  lk.lock();
+  for (HdSet &s : g->hd_sets)
+    if (s.seq == seq) { s.waiters--; break; }
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group hsvdetector set)"); }
+  for (HdSet &s : g->hd_sets)
+    if (s.seq <= seq) hd_collect(g, s);
+  hd_retire(g);
+  return MI355_OK;
+}
+
+// waits for every set launched so far (their frames stay collectable)
+int hd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
+  uint64_t last = 0;
+  for (const HdSet &s : g->hd_sets)
+    if (!s.collected) last = s.tickets.front();
+  return last ? hd_wait_unlocking(g, lk, last) : MI355_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -676,6 +845,20 @@ void mi355_group_destroy(mi355_group *g) {
     (void)hipStreamDestroy(g->cd_stream);
   }
   for (void *b : g->cd_blocks) (void)hipHostFree(b);
+  if (g->hd_stream) {
+    // frames still pending are launched and waited for, as pairs are: their destinations are complete when destroy returns
+    {
+      Locked L(g);
+      (void)hd_flush_locked(g);
+    }
+    (void)hipStreamSynchronize(g->hd_stream);
+    for (HdSet &s : g->hd_sets) (void)hipEventDestroy(s.done);
+    g->hd_sets.clear();
+    for (HdDesc &d : g->hd_pending)
+      if (d.ready) (void)hipEventDestroy(d.ready);
+    g->hd_pending.clear();
+    (void)hipStreamDestroy(g->hd_stream);
+  }
   for (Batch &b : g->batches) (void)hipEventDestroy(b.done);   // (normally none left: wait_all retired them)
   for (Desc &d : g->pending)
     if (d.ready) (void)hipEventDestroy(d.ready);
@@ -767,7 +950,8 @@ int mi355_group_flush(mi355_group *g) {
   const int rc = flush_locked(g);
   const int rc2 = g->actx ? cmp_flush_locked(g) : MI355_OK;
   const int rc3 = g->cd_scratch ? cd_flush_locked(g) : MI355_OK;
-  return rc ? rc : (rc2 ? rc2 : rc3);
+  const int rc4 = g->hd_stream ? hd_flush_locked(g) : MI355_OK;
+  return rc ? rc : (rc2 ? rc2 : (rc3 ? rc3 : rc4));
 }
 
 // ---------------------------------------------------------------- videocompare pairs (Dssim / Blockhash) of independent elements
@@ -849,6 +1033,7 @@ int mi355_group_wait_compare(mi355_group *g, uint64_t ticket, double *distance, 
   std::unique_lock<std::mutex> &lk = L.lk;
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
   if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
+  if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   auto is_pending = [&]() { for (const CmpDesc &d : g->cmp_pending) if (d.ticket == ticket) return true; return false; };
   if (is_pending()) {
@@ -968,12 +1153,108 @@ int mi355_group_colordetect_stats(mi355_group *g, uint64_t stats[4]) {
   return MI355_OK;
 }
 
+// ---------------------------------------------------------------- hsvdetector frames of independent elements
+
+int mi355_group_set_hsvdetect_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
+  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  g->hd_expected = expected_streams;
+  g->hd_linger_us = linger_us;
+  return MI355_OK;
+}
+
+int mi355_group_submit_hsvdetect(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_src, int src_stride, int src_format, uint8_t *d_dst, int dst_stride,
+                                 int dst_format, int width, int height, const mi355_hsvdetect_settings *settings, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context or ticket");
+  HdDesc d{};
+  const char *why = nullptr;
+  int rc = hsvdetect_check_frames(d_src, src_stride, src_format, d_dst, dst_stride, dst_format, 1, width, height, settings, &d.f.sfmt, &d.f.dst_alpha_first,
+                                  &d.f.dst_bgr, &why);
+  if (rc) return fail(g, rc, why);
+  if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
+  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+  if ((rc = hd_ensure(g))) return rc;
+  hd_retire_done(g);
+  d.f.src = d_src;
+  d.f.dst = d_dst;
+  d.f.src_stride = src_stride;
+  d.f.dst_stride = dst_stride;
+  d.f.width = width;
+  d.f.height = height;
+  d.f.s = *settings;
+  d.f.force_generic = ctx->force_generic;
+  d.ready = nullptr;
+  if (width > 0 && height > 0 && hipStreamQuery(ctx->stream) != hipSuccess) {   // the frame is read after what the context's stream holds now (an upload, a filter)
+    (void)hipGetLastError();
+    d.ready = take_event(g);
+    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      if (d.ready) g->events.push_back(d.ready);
+      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
+    }
+  }
+  d.ticket = g->next_ticket++;
+  *ticket = d.ticket;
+  g->hd_pending.push_back(d);
+  // everybody is here (rendezvous), or a launch set is full: go. The frame has been accepted whatever that launch does (a failure
+  // is told to the waits of the frames it carried).
+  const int full = g->hd_expected > 0 && g->hd_expected < kHdSetMax ? g->hd_expected : kHdSetMax;
+  if ((int)g->hd_pending.size() >= full) (void)hd_flush_locked(g);
+  return MI355_OK;
+}
+
+int mi355_group_wait_hsvdetect(mi355_group *g, uint64_t ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  std::unique_lock<std::mutex> &lk = L.lk;
+  // another queue's, a collected or an unknown ticket: refused before anything is launched or waited for
+  if (!hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: not the ticket of a hsvdetector frame that is still to be collected");
+  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+  auto is_pending = [&]() { for (const HdDesc &d : g->hd_pending) if (d.ticket == ticket) return true; return false; };
+  if (is_pending()) {
+    // rendezvous: the other instances of this interval are about to submit - linger for them (bounded), then launch what is there
+    if (g->hd_expected > 0 && g->hd_linger_us > 0) {
+      const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(g->hd_linger_us);
+      while (is_pending() && (int)g->hd_pending.size() < g->hd_expected) {
+        if (g->hd_cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
+      }
+    }
+    if (is_pending()) (void)hd_flush_locked(g, ticket);   // (a failure of this frame's own launch is in hd_results)
+  }
+  int rc = hd_wait_unlocking(g, lk, ticket);
+  if (rc) return rc;
+  auto r = g->hd_results.find(ticket);
+  if (r == g->hd_results.end()) return fail(g, MI355_ERR_INVALID_ARG, "group: this frame has been collected already");   // (by a concurrent wait)
+  const int status = r->second;
+  g->hd_results.erase(r);
+  if (status) return fail(g, status, "group: the launch that carried this hsvdetector frame failed");
+  return MI355_OK;
+}
+
+int mi355_group_hsvdetect_stats(mi355_group *g, uint64_t stats[4]) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  stats[0] = g->n_hd_frames;
+  stats[1] = g->n_hd_sets;
+  stats[2] = g->n_hd_largest;
+  stats[3] = g->n_hd_launches;
+  return MI355_OK;
+}
+
+int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_jobs, const uint64_t *units, uint32_t *first_block,
+                                  uint32_t *blocks, uint32_t *total_blocks) {
+  return hsvdetect_plan(n_cu, blocks_per_cu, units_per_block, n_jobs, units, first_block, blocks, total_blocks);
+}
+
 int mi355_group_wait(mi355_group *g, uint64_t ticket) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
   std::unique_lock<std::mutex> &lk = L.lk;
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
   if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
+  if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -989,6 +1270,7 @@ int mi355_group_order_after(mi355_group *g, mi355_ctx *ctx, uint64_t ticket) {
   Locked L(g);
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
   if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
+  if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -1016,9 +1298,13 @@ int mi355_group_wait_all(mi355_group *g) {
   int rc = flush_locked(g);
   if (rc) return rc;
   if ((rc = wait_all_unlocking(g, lk))) return rc;
-  if (!g->cd_scratch) return MI355_OK;
-  if ((rc = cd_flush_locked(g))) return rc;
-  return cd_wait_all_unlocking(g, lk);
+  if (g->cd_scratch) {
+    if ((rc = cd_flush_locked(g))) return rc;
+    if ((rc = cd_wait_all_unlocking(g, lk))) return rc;
+  }
+  if (!g->hd_stream) return MI355_OK;
+  if ((rc = hd_flush_locked(g))) return rc;
+  return hd_wait_all_unlocking(g, lk);
 }
 
 int mi355_group_submit_round(mi355_group *g, mi355_ctx *const *ctxs, int n_streams, uint8_t *const *d_src, uint8_t *const *d_dst, int width, int height,

@@ -423,8 +423,27 @@ struct HsvDetK {
   float hue_ref, hue_var, sat_ref, sat_var, val_ref, val_var;
 };
 
-// One pixel per lane; input 3 or 4 bytes/pixel, output always 4 (hsvdetector/imp.rs:118-156).
+// One pixel, literally: input 3 or 4 bytes/pixel at ip, output always 4 at op (hsvdetector/imp.rs:118-156).
 // Arithmetic is the GENERIC conversion (IEEE ops) — the detector is a "next" row.
+__device__ __forceinline__ void hsvdetect_px_literal(const uint8_t *ip, uint8_t *op, int in_bgr, int out_alpha_first, int out_bgr, const HsvDetK &k) {
+  const uint32_t c0 = ip[0], c1 = ip[1], c2 = ip[2];
+  const uint32_t r8 = in_bgr ? c2 : c0, g8 = c1, b8 = in_bgr ? c0 : c2;
+  float h, s, v;
+  hsv_from_rgb<false>((float)r8, (float)g8, (float)b8, h, s, v);
+  const float ref_hue_offset = 180.0f - k.hue_ref;
+  float sh = h + ref_hue_offset;
+  if (sh < 0.0f) sh += 360.0f;
+  sh = fmodf(sh, 360.0f);
+  const bool hit = fabsf(sh - 180.0f) <= k.hue_var && fabsf(s - k.sat_ref) <= k.sat_var &&
+                   fabsf(v - k.val_ref) <= k.val_var;
+  const uint8_t alpha = hit ? 255 : 0;
+  uint8_t *c = op + (out_alpha_first ? 1 : 0);
+  if (out_bgr) { c[0] = (uint8_t)b8; c[1] = (uint8_t)g8; c[2] = (uint8_t)r8; }
+  else { c[0] = (uint8_t)r8; c[1] = (uint8_t)g8; c[2] = (uint8_t)b8; }
+  op[out_alpha_first ? 0 : 3] = alpha;
+}
+
+// One pixel per lane over n_frames frames of one geometry.
 __global__ __launch_bounds__(256) void hsvdetect_rows_kernel(const uint8_t *__restrict__ src, size_t src_pitch,
                                                              int src_stride, int in_pixel_stride, int in_first,
                                                              int in_bgr, uint8_t *__restrict__ dst, size_t dst_pitch,
@@ -440,21 +459,7 @@ __global__ __launch_bounds__(256) void hsvdetect_rows_kernel(const uint8_t *__re
     const size_t col = r - row * (size_t)width;
     const uint8_t *ip = src + f * src_pitch + row * (size_t)src_stride + col * (size_t)in_pixel_stride + in_first;
     uint8_t *op = dst + f * dst_pitch + row * (size_t)dst_stride + col * 4;
-    const uint32_t c0 = ip[0], c1 = ip[1], c2 = ip[2];
-    const uint32_t r8 = in_bgr ? c2 : c0, g8 = c1, b8 = in_bgr ? c0 : c2;
-    float h, s, v;
-    hsv_from_rgb<false>((float)r8, (float)g8, (float)b8, h, s, v);
-    const float ref_hue_offset = 180.0f - k.hue_ref;
-    float sh = h + ref_hue_offset;
-    if (sh < 0.0f) sh += 360.0f;
-    sh = fmodf(sh, 360.0f);
-    const bool hit = fabsf(sh - 180.0f) <= k.hue_var && fabsf(s - k.sat_ref) <= k.sat_var &&
-                     fabsf(v - k.val_ref) <= k.val_var;
-    const uint8_t alpha = hit ? 255 : 0;
-    uint8_t *c = op + (out_alpha_first ? 1 : 0);
-    if (out_bgr) { c[0] = (uint8_t)b8; c[1] = (uint8_t)g8; c[2] = (uint8_t)r8; }
-    else { c[0] = (uint8_t)r8; c[1] = (uint8_t)g8; c[2] = (uint8_t)b8; }
-    op[out_alpha_first ? 0 : 3] = alpha;
+    hsvdetect_px_literal(ip, op, in_bgr, out_alpha_first, out_bgr, k);
   }
 }
 
@@ -470,6 +475,24 @@ __device__ __forceinline__ f2 hsvdetect_shifted(f2 h, float off, bool neg) {
   return sub360_if_reached2(neg ? add360_if_negative2(t) : t);
 }
 
+// Four pixel words of one lane through the FAST detector: colour channels at bytes RPOS / GPOS / BPOS of each word; out_sel
+// picks the colour bytes from the input word (selector 4..7) and the alpha byte from the second operand (selector 0).
+template <int RPOS, int GPOS, int BPOS>
+__device__ __forceinline__ void hsvdetect_quad(const uint32_t (&in)[4], uint32_t (&out)[4], const HsvDetK &k, float off, bool neg, uint32_t out_sel,
+                                               const HsvLds *lds) {
+#pragma unroll
+  for (int j = 0; j < 4; j += 2) {
+    f2 h, s, v;
+    hsv_from_rgb_pair_fast<RPOS, GPOS, BPOS, 1>(in[j], in[j + 1], h, s, v, lds);
+    const f2 sh = hsvdetect_shifted(h, off, neg);
+    const f2 dh = sh - splat2(180.0f), dsat = s - splat2(k.sat_ref), dv = v - splat2(k.val_ref);
+    const bool hit0 = fabsf(dh.x) <= k.hue_var && fabsf(dsat.x) <= k.sat_var && fabsf(dv.x) <= k.val_var;
+    const bool hit1 = fabsf(dh.y) <= k.hue_var && fabsf(dsat.y) <= k.sat_var && fabsf(dv.y) <= k.val_var;
+    out[j] = __builtin_amdgcn_perm(in[j], hit0 ? 255u : 0u, out_sel);
+    out[j + 1] = __builtin_amdgcn_perm(in[j + 1], hit1 ? 255u : 0u, out_sel);
+  }
+}
+
 template <int IN_FIRST, bool IN_BGR, bool NEG = false>
 __global__ __launch_bounds__(256) void hsvdetect_flat_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n_vec,
                                                              HsvDetK k, uint32_t out_sel) {
@@ -483,19 +506,7 @@ __global__ __launch_bounds__(256) void hsvdetect_flat_kernel(const uint4 *__rest
     const uint4 p = src[i];
     const uint32_t in[4] = {p.x, p.y, p.z, p.w};
     uint32_t out[4];
-#pragma unroll
-    for (int j = 0; j < 4; j += 2) {
-      f2 h, s, v;
-      hsv_from_rgb_pair_fast<RPOS, GPOS, BPOS, 1>(in[j], in[j + 1], h, s, v, &lds);
-      const f2 sh = hsvdetect_shifted(h, off, NEG);
-      const f2 dh = sh - splat2(180.0f), dsat = s - splat2(k.sat_ref), dv = v - splat2(k.val_ref);
-      const bool hit0 = fabsf(dh.x) <= k.hue_var && fabsf(dsat.x) <= k.sat_var && fabsf(dv.x) <= k.val_var;
-      const bool hit1 = fabsf(dh.y) <= k.hue_var && fabsf(dsat.y) <= k.sat_var && fabsf(dv.y) <= k.val_var;
-      // out_sel picks the colour bytes from the input pixel (selector 4..7) and the alpha byte from the
-      // second operand (selector 0)
-      out[j] = __builtin_amdgcn_perm(in[j], hit0 ? 255u : 0u, out_sel);
-      out[j + 1] = __builtin_amdgcn_perm(in[j + 1], hit1 ? 255u : 0u, out_sel);
-    }
+    hsvdetect_quad<RPOS, GPOS, BPOS>(in, out, k, off, NEG, out_sel, &lds);
     dst[i] = make_uint4(out[0], out[1], out[2], out[3]);
   }
 }
@@ -515,19 +526,44 @@ __global__ __launch_bounds__(256) void hsvdetect_rgb24_kernel(const Rgb24x4 *__r
     const Rgb24x4 v = src[i];
     const uint32_t in[4] = {v.d0, (v.d0 >> 24) | (v.d1 << 8), (v.d1 >> 16) | (v.d2 << 16), v.d2 >> 8};
     uint32_t out[4];
-#pragma unroll
-    for (int j = 0; j < 4; j += 2) {
-      f2 h, s, vv;
-      hsv_from_rgb_pair_fast<RPOS, GPOS, BPOS, 1>(in[j], in[j + 1], h, s, vv, &lds);
-      const f2 sh = hsvdetect_shifted(h, off, NEG);
-      const f2 dh = sh - splat2(180.0f), dsat = s - splat2(k.sat_ref), dv = vv - splat2(k.val_ref);
-      const bool hit0 = fabsf(dh.x) <= k.hue_var && fabsf(dsat.x) <= k.sat_var && fabsf(dv.x) <= k.val_var;
-      const bool hit1 = fabsf(dh.y) <= k.hue_var && fabsf(dsat.y) <= k.sat_var && fabsf(dv.y) <= k.val_var;
-      out[j] = __builtin_amdgcn_perm(in[j], hit0 ? 255u : 0u, out_sel);
-      out[j + 1] = __builtin_amdgcn_perm(in[j + 1], hit1 ? 255u : 0u, out_sel);
-    }
+    hsvdetect_quad<RPOS, GPOS, BPOS>(in, out, k, off, NEG, out_sel, &lds);
     dst[i] = make_uint4(out[0], out[1], out[2], out[3]);
   }
+}
+
+// Which kernel a batch of frames goes to: the one predicate of the lone entry (launch_hsvdetect) and of the group's launch sets
+// (hsvdetect_launch_set), so that a frame is in the same class wherever it runs.
+//   FLAT  : 4-byte input, packed rows on both sides (and packed frames), both pointers 16-byte aligned, pixel count % 4 == 0
+//   RGB24 : 3-byte input, packed rows (and frames), source 4-byte and destination 16-byte aligned, pixel count % 4 == 0
+//   both need off = 180 - hue_ref in [-360, 360] (hsvdetect_shifted) and the context's force-generic flag off
+//   ROWS  : everything else, literally
+enum HsvDetPath { HSVDET_FLAT, HSVDET_RGB24, HSVDET_ROWS };
+static HsvDetPath hsvdetect_path(int force_generic, const uint8_t *d_src, size_t src_pitch, int src_stride, const PixFmt &sfmt, const uint8_t *d_dst,
+                                 size_t dst_pitch, int dst_stride, int n_frames, int width, int height, const mi355_hsvdetect_settings &s) {
+  const size_t total = (size_t)width * (size_t)height * (size_t)n_frames;
+  const size_t row_bytes = (size_t)width * 4;
+  const bool contiguous = sfmt.pixel_stride == 4 && (size_t)src_stride == row_bytes && (size_t)dst_stride == row_bytes &&
+                          (n_frames == 1 || (src_pitch == row_bytes * (size_t)height && dst_pitch == row_bytes * (size_t)height));
+  const float off = 180.0f - s.hue_ref;   // as the kernels (and the reference) compute it
+  const bool fast = !force_generic && off >= -360.0f && off <= 360.0f;
+  if (fast && contiguous && ((uintptr_t)d_src % 16 == 0) && ((uintptr_t)d_dst % 16 == 0) && ((total * 4) % 16 == 0)) return HSVDET_FLAT;
+  const size_t row3 = (size_t)width * 3;
+  const bool contiguous3 = sfmt.pixel_stride == 3 && sfmt.first == 0 && (size_t)src_stride == row3 && (size_t)dst_stride == row_bytes &&
+                           (n_frames == 1 || (src_pitch == row3 * (size_t)height && dst_pitch == row_bytes * (size_t)height));
+  if (fast && contiguous3 && ((uintptr_t)d_src % 4 == 0) && ((uintptr_t)d_dst % 16 == 0) && (total % 4 == 0)) return HSVDET_RGB24;
+  return HSVDET_ROWS;
+}
+
+// v_perm selector of the FAST kernels' output word: colour channel c (R, G, B) sits at input byte in_pos[c]; the alpha byte
+// selector stays 0 (= byte 0 of the 0/255 operand)
+static uint32_t hsvdetect_out_sel(const int in_pos[3], int dst_alpha_first, int dst_bgr) {
+  const int cbase = dst_alpha_first ? 1 : 0;
+  uint32_t sel = 0;
+  for (int c = 0; c < 3; c++) {
+    const int out_byte = cbase + (dst_bgr ? 2 - c : c);
+    sel |= (uint32_t)(4 + in_pos[c]) << (8 * out_byte);
+  }
+  return sel;
 }
 
 int launch_hsvdetect(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride,
@@ -537,21 +573,11 @@ int launch_hsvdetect(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int
   if (n_frames <= 0 || width <= 0 || height <= 0) return MI355_OK;
   const HsvDetK k{s.hue_ref, s.hue_var, s.saturation_ref, s.saturation_var, s.value_ref, s.value_var};
   const size_t total = (size_t)width * (size_t)height * (size_t)n_frames;
-  const size_t row_bytes = (size_t)width * 4;
-  const bool contiguous = sfmt.pixel_stride == 4 && (size_t)src_stride == row_bytes && (size_t)dst_stride == row_bytes &&
-                          (n_frames == 1 || (src_pitch == row_bytes * (size_t)height && dst_pitch == row_bytes * (size_t)height));
-  const float off = 180.0f - s.hue_ref;   // as the kernels (and the reference) compute it
-  const bool fast = !ctx->force_generic && off >= -360.0f && off <= 360.0f;
-  const bool neg = off < 0.0f;
-  if (fast && contiguous && ((uintptr_t)d_src % 16 == 0) && ((uintptr_t)d_dst % 16 == 0) && ((total * 4) % 16 == 0)) {
-    // output byte j: colour channel c sits at input byte in_pos(c); alpha comes from operand 1 byte 0
+  const bool neg = 180.0f - s.hue_ref < 0.0f;
+  const HsvDetPath path = hsvdetect_path(ctx->force_generic, d_src, src_pitch, src_stride, sfmt, d_dst, dst_pitch, dst_stride, n_frames, width, height, s);
+  if (path == HSVDET_FLAT) {
     const int in_pos[3] = {sfmt.first + (sfmt.bgr ? 2 : 0), sfmt.first + 1, sfmt.first + (sfmt.bgr ? 0 : 2)};  // R,G,B
-    const int cbase = dst_alpha_first ? 1 : 0;
-    uint32_t sel = 0;  // alpha byte selector stays 0 (= byte 0 of the 0/255 operand)
-    for (int c = 0; c < 3; c++) {
-      const int out_byte = cbase + (dst_bgr ? 2 - c : c);
-      sel |= (uint32_t)(4 + in_pos[c]) << (8 * out_byte);
-    }
+    const uint32_t sel = hsvdetect_out_sel(in_pos, dst_alpha_first, dst_bgr);
     const size_t n_vec = total / 4;
     const int fgrid = grid_for(ctx, (n_vec + 1) / 2, 256, 64);   // two groups per lane, as the hsvfilter kernels (one-frame launches)
     dim3 g(fgrid), b(256);
@@ -569,17 +595,9 @@ int launch_hsvdetect(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int
 #undef MI355_DET_LAUNCH
     return check_hip(ctx, hipGetLastError(), "hsvdetect flat kernel launch");
   }
-  const size_t row3 = (size_t)width * 3;
-  const bool contiguous3 = sfmt.pixel_stride == 3 && sfmt.first == 0 && (size_t)src_stride == row3 && (size_t)dst_stride == row_bytes &&
-                           (n_frames == 1 || (src_pitch == row3 * (size_t)height && dst_pitch == row_bytes * (size_t)height));
-  if (fast && contiguous3 && ((uintptr_t)d_src % 4 == 0) && ((uintptr_t)d_dst % 16 == 0) && (total % 4 == 0)) {
+  if (path == HSVDET_RGB24) {
     const int in_pos[3] = {sfmt.bgr ? 2 : 0, 1, sfmt.bgr ? 0 : 2};
-    const int cbase = dst_alpha_first ? 1 : 0;
-    uint32_t sel = 0;
-    for (int c = 0; c < 3; c++) {
-      const int out_byte = cbase + (dst_bgr ? 2 - c : c);
-      sel |= (uint32_t)(4 + in_pos[c]) << (8 * out_byte);
-    }
+    const uint32_t sel = hsvdetect_out_sel(in_pos, dst_alpha_first, dst_bgr);
     const size_t n_grp = total / 4;
     const int fgrid = grid_for(ctx, n_grp, 256, 64);
     if (sfmt.bgr && neg) hipLaunchKernelGGL((hsvdetect_rgb24_kernel<true, true>), dim3(fgrid), dim3(256), 0, ctx->stream, (const Rgb24x4 *)d_src, (uint4 *)d_dst, n_grp, k, sel);
@@ -593,6 +611,184 @@ int launch_hsvdetect(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int
                      sfmt.pixel_stride, sfmt.first, sfmt.bgr, d_dst, dst_pitch, dst_stride, dst_alpha_first, dst_bgr,
                      n_frames, width, height, k);
   return check_hip(ctx, hipGetLastError(), "hsvdetect kernel launch");
+}
+
+// ---------------------------------------------------------------- hsvdetector launch sets (the video group's detector queue)
+//
+// Frames of independent element instances - each with its own geometry, formats and settings - in at most two launches over a
+// job table. The table travels in the kernel arguments (no upload, no lifetime); a block's job index comes from blockIdx alone,
+// so the search and every job field are scalar and the path choices below are the same for all waves of a block.
+//   hsvdetect_jobs_kernel       the jobs the lone entry gives to hsvdetect_flat_kernel or hsvdetect_rgb24_kernel: four pixels per
+//                               lane through hsvdetect_quad. One v_perm_b32 brings a job's byte order to R,G,B,0; the arithmetic
+//                               reads byte values only, so it is that of the <RPOS, GPOS, BPOS> instance the lone entry picks.
+//   hsvdetect_rows_jobs_kernel  every other job, through hsvdetect_px_literal, one pixel per lane. Kept apart because its IEEE
+//                               division and fmodf would set the register budget of the kernel all aligned frames run.
+enum : uint32_t { HD_IN3 = 1u, HD_NEG = 2u, HD_IN_BGR = 4u, HD_OUT_ALPHA_FIRST = 8u, HD_OUT_BGR = 16u, HD_IN_FIRST = 32u };
+struct HdJob {
+  const uint8_t *src;
+  uint8_t *dst;
+  uint64_t units;                        // vector launch: 16-byte output groups (4 pixels); literal launch: pixels
+  int32_t width, src_stride, dst_stride; // literal launch
+  uint32_t in_sel, out_sel;              // vector launch: v_perm selectors into and out of the canonical word
+  HsvDetK k;
+  uint32_t flags;                        // HD_*: 12- or 16-byte loads and the offset class (vector), byte positions (literal)
+  uint32_t first_block, blocks;          // its blocks in the 1-D grid (hsvdetect_plan)
+};
+struct HdJobTable {
+  HdJob job[kHdSetMax];
+  int32_t n_jobs, pad;
+};
+static_assert(sizeof(HdJob) == 80, "HdJob has no padding holes");
+static_assert(sizeof(HdJobTable) <= 4096, "the job table is passed in the kernel arguments");
+
+// the job of block b: jobs are in first_block order and every job of a table has at least one block
+__device__ __forceinline__ int hsvdetect_job_of(const HdJobTable &T, uint32_t b) {
+  int j = 0;
+  while (j + 1 < T.n_jobs && b >= T.job[j].first_block + T.job[j].blocks) j++;
+  return j;
+}
+
+__global__ __launch_bounds__(256) void hsvdetect_jobs_kernel(const HdJobTable T) {
+  const int j = hsvdetect_job_of(T, blockIdx.x);
+  const uint32_t rel = blockIdx.x - T.job[j].first_block;
+  if (blockIdx.x < T.job[j].first_block || rel >= T.job[j].blocks) return;  // a grid larger than the plan's total: the whole block leaves, before the barrier
+  __shared__ HsvLds lds;
+  hsv_lds_fill<0, 1, 2, 3>(&lds);
+  __syncthreads();
+  const HsvDetK k = T.job[j].k;
+  const float off = 180.0f - k.hue_ref;  // ref_hue_offset (hsvdetector/imp.rs:140)
+  const uint32_t flags = T.job[j].flags, in_sel = T.job[j].in_sel, out_sel = T.job[j].out_sel;
+  const bool neg = (flags & HD_NEG) != 0;
+  const size_t n = T.job[j].units, stride = (size_t)T.job[j].blocks * 256;
+  uint4 *__restrict__ dst = (uint4 *)T.job[j].dst;
+  if (flags & HD_IN3) {
+    const Rgb24x4 *__restrict__ src = (const Rgb24x4 *)T.job[j].src;
+    for (size_t i = (size_t)rel * 256 + threadIdx.x; i < n; i += stride) {
+      const Rgb24x4 v = src[i];
+      const uint32_t raw[4] = {v.d0, (v.d0 >> 24) | (v.d1 << 8), (v.d1 >> 16) | (v.d2 << 16), v.d2 >> 8};
+      uint32_t in[4], out[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) in[q] = __builtin_amdgcn_perm(raw[q], 0u, in_sel);
+      hsvdetect_quad<0, 1, 2>(in, out, k, off, neg, out_sel, &lds);
+      dst[i] = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+  } else {
+    const uint4 *__restrict__ src = (const uint4 *)T.job[j].src;
+    for (size_t i = (size_t)rel * 256 + threadIdx.x; i < n; i += stride) {
+      const uint4 p = src[i];
+      const uint32_t raw[4] = {p.x, p.y, p.z, p.w};
+      uint32_t in[4], out[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) in[q] = __builtin_amdgcn_perm(raw[q], 0u, in_sel);
+      hsvdetect_quad<0, 1, 2>(in, out, k, off, neg, out_sel, &lds);
+      dst[i] = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void hsvdetect_rows_jobs_kernel(const HdJobTable T) {
+  const int j = hsvdetect_job_of(T, blockIdx.x);
+  const uint32_t rel = blockIdx.x - T.job[j].first_block;
+  if (blockIdx.x < T.job[j].first_block || rel >= T.job[j].blocks) return;  // a grid larger than the plan's total
+  const HsvDetK k = T.job[j].k;
+  const uint32_t flags = T.job[j].flags;
+  const int in_bgr = (flags & HD_IN_BGR) != 0, out_alpha_first = (flags & HD_OUT_ALPHA_FIRST) != 0, out_bgr = (flags & HD_OUT_BGR) != 0;
+  const size_t in_pixel_stride = (flags & HD_IN3) ? 3 : 4, in_first = (flags & HD_IN_FIRST) ? 1 : 0;
+  const size_t total = T.job[j].units, width = (size_t)T.job[j].width, stride = (size_t)T.job[j].blocks * 256;
+  const size_t src_stride = (size_t)T.job[j].src_stride, dst_stride = (size_t)T.job[j].dst_stride;
+  const uint8_t *__restrict__ src = T.job[j].src;
+  uint8_t *__restrict__ dst = T.job[j].dst;
+  for (size_t i = (size_t)rel * 256 + threadIdx.x; i < total; i += stride) {
+    const size_t row = i / width;
+    const size_t col = i - row * width;
+    hsvdetect_px_literal(src + row * src_stride + col * in_pixel_stride + in_first, dst + row * dst_stride + col * 4, in_bgr, out_alpha_first, out_bgr, k);
+  }
+}
+
+// The blocks of one launch of a set (mi355_selftest_hsvdetect_plan). Job j wants ceil(units / units_per_block) blocks; if the
+// wants fit the budget of n_cu * blocks_per_cu every job gets its want - the grid the lone launch would give it. Otherwise every job
+// with units gets one block and the rest of the budget is shared in proportion to what the jobs still want, rounded down: a big
+// frame among small ones takes what they leave, equal frames get equal shares, and the total stays within max(budget, jobs).
+int hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_jobs, const uint64_t *units, uint32_t *first_block, uint32_t *blocks,
+                   uint32_t *total_blocks) {
+  if (n_cu < 1 || blocks_per_cu < 1 || units_per_block == 0 || n_jobs < 0 || n_jobs > kHdSetMax || !total_blocks ||
+      (n_jobs && (!units || !first_block || !blocks)))
+    return MI355_ERR_INVALID_ARG;
+  uint64_t budget = (uint64_t)n_cu * (uint64_t)blocks_per_cu;
+  if (budget > 0x7fffffffull) budget = 0x7fffffffull;  // (a grid's x dimension)
+  uint64_t want[kHdSetMax];
+  unsigned __int128 all = 0, still = 0;
+  uint64_t with_units = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    want[j] = units[j] / units_per_block + (units[j] % units_per_block != 0);
+    all += want[j];
+    if (want[j]) { with_units++; still += want[j] - 1; }
+  }
+  const bool fits = all <= budget;
+  const uint64_t spare = budget > with_units ? budget - with_units : 0;   // (!fits: spare < still)
+  uint32_t next = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    uint64_t b = want[j];
+    if (!fits && b) b = 1 + (uint64_t)((unsigned __int128)(want[j] - 1) * spare / (still ? still : 1));
+    first_block[j] = next;
+    blocks[j] = (uint32_t)b;
+    next += (uint32_t)b;
+  }
+  *total_blocks = next;
+  return MI355_OK;
+}
+
+int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, int n, int *kernel_launches, std::string *err) {
+  *kernel_launches = 0;
+  if (!frames || n < 1 || n > kHdSetMax) { *err = "hsvdetector: bad launch set"; return MI355_ERR_INVALID_ARG; }
+  HdJobTable vec{}, lit{};
+  uint64_t vec_units[kHdSetMax], lit_units[kHdSetMax];
+  for (int i = 0; i < n; i++) {
+    const HdFrame &f = frames[i];
+    if (f.width <= 0 || f.height <= 0) continue;  // no pixel: no job
+    const size_t total = (size_t)f.width * (size_t)f.height;
+    const HsvDetPath path = hsvdetect_path(f.force_generic, f.src, 0, f.src_stride, f.sfmt, f.dst, 0, f.dst_stride, 1, f.width, f.height, f.s);
+    HdJobTable &T = path == HSVDET_ROWS ? lit : vec;
+    HdJob &J = T.job[T.n_jobs];
+    J.src = f.src;
+    J.dst = f.dst;
+    J.width = f.width;
+    J.src_stride = f.src_stride;
+    J.dst_stride = f.dst_stride;
+    J.k = HsvDetK{f.s.hue_ref, f.s.hue_var, f.s.saturation_ref, f.s.saturation_var, f.s.value_ref, f.s.value_var};
+    J.flags = (f.sfmt.pixel_stride == 3 ? HD_IN3 : 0u) | (180.0f - f.s.hue_ref < 0.0f ? HD_NEG : 0u) | (f.sfmt.bgr ? HD_IN_BGR : 0u) |
+              (f.dst_alpha_first ? HD_OUT_ALPHA_FIRST : 0u) | (f.dst_bgr ? HD_OUT_BGR : 0u) | (f.sfmt.first ? HD_IN_FIRST : 0u);
+    if (path == HSVDET_ROWS) {
+      J.units = total;
+      lit_units[T.n_jobs] = J.units;
+    } else {
+      // canonical word: R, G, B at bytes 0, 1, 2 and a zero (selector 0x0c) - the lone kernels' selector with in_pos = {0, 1, 2}
+      const int rpos = f.sfmt.first + (f.sfmt.bgr ? 2 : 0), gpos = f.sfmt.first + 1, bpos = f.sfmt.first + (f.sfmt.bgr ? 0 : 2);
+      const int canon[3] = {0, 1, 2};
+      J.in_sel = (uint32_t)(4 + rpos) | ((uint32_t)(4 + gpos) << 8) | ((uint32_t)(4 + bpos) << 16) | (0x0cu << 24);
+      J.out_sel = hsvdetect_out_sel(canon, f.dst_alpha_first, f.dst_bgr);
+      J.units = total / 4;
+      vec_units[T.n_jobs] = J.units;
+    }
+    T.n_jobs++;
+  }
+  struct Launch { HdJobTable *T; const uint64_t *units; unsigned per_block; int per_cu; bool vector; };
+  // vector: two groups per lane and the cap of the lone grid_for(ctx, (n_vec + 1) / 2, 256, 64); literal: grid_for(ctx, total, 256, 32)
+  const Launch launches[2] = {{&vec, vec_units, 512, 64, true}, {&lit, lit_units, 256, 32, false}};
+  for (const Launch &L : launches) {
+    HdJobTable &T = *L.T;
+    if (!T.n_jobs) continue;
+    uint32_t first[kHdSetMax], blocks[kHdSetMax], total_blocks = 0;
+    const int rc = hsvdetect_plan(n_cu, L.per_cu, L.per_block, T.n_jobs, L.units, first, blocks, &total_blocks);
+    if (rc || !total_blocks) { *err = "hsvdetector: bad launch set"; return rc ? rc : MI355_ERR_INVALID_ARG; }
+    for (int j = 0; j < T.n_jobs; j++) { T.job[j].first_block = first[j]; T.job[j].blocks = blocks[j]; }
+    if (L.vector) hipLaunchKernelGGL(hsvdetect_jobs_kernel, dim3(total_blocks), dim3(256), 0, stream, T);
+    else hipLaunchKernelGGL(hsvdetect_rows_jobs_kernel, dim3(total_blocks), dim3(256), 0, stream, T);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { *err = std::string(L.vector ? "hsvdetect jobs kernel launch: " : "hsvdetect rows jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+    (*kernel_launches)++;
+  }
+  return MI355_OK;
 }
 
 }  // namespace mi355

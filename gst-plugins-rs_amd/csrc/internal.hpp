@@ -239,6 +239,24 @@ size_t colordetect_set_block_bytes();  // the pinned block a set's results are c
 // n <= kCdSetMax checked frames on `stream`: histogram launch (none if no frame has a sample), MMCQ launch, results into h_block
 int colordetect_launch_set(CdSetScratch *S, hipStream_t stream, int n_cu, const CdFrame *frames, int n, void *h_block, int *kernel_launches, std::string *err);
 void colordetect_set_result(const void *h_block, int i, uint8_t palette_rgb[255 * 3], int *n_colors);
+// launch sets of the video group's hsvdetector queue (hsv_kernels.hip): frames of independent instances, one job table
+constexpr int kHdSetMax = MI355_HSVDETECT_SET_MAX;
+struct HdFrame {
+  const uint8_t *src;
+  uint8_t *dst;
+  int src_stride, dst_stride, width, height;
+  PixFmt sfmt;
+  int dst_alpha_first, dst_bgr;
+  mi355_hsvdetect_settings s;
+  int force_generic;  // the member's MI355_FLAG_FORCE_GENERIC at submit
+};
+// the checks of mi355_hsvdetect_frames_device for n_frames frames (ctx.hip; both entries call it); *why names the refusal
+int hsvdetect_check_frames(const uint8_t *d_src, int src_stride, int src_format, const uint8_t *d_dst, int dst_stride, int dst_format, int n_frames,
+                           int width, int height, const mi355_hsvdetect_settings *settings, PixFmt *sfmt, int *alpha_first, int *bgr, const char **why);
+int hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_jobs, const uint64_t *units, uint32_t *first_block, uint32_t *blocks,
+                   uint32_t *total_blocks);
+// n <= kHdSetMax checked frames on `stream`: the vector launch and / or the literal launch, whichever has a job with a pixel
+int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, int n, int *kernel_launches, std::string *err);
 
 // agingradio (agingradio.hip): one job = one element instance's buffer. The host fills the table (alpha and the quantise factor
 // computed with its libm); the group (agroup.hip) submits one job per member, a context a table of one.

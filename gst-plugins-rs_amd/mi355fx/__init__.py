@@ -39,6 +39,7 @@ FLAG_HSV_NT = 14
 FLAG_BLOCKHASH_ANY_SIZE = 15
 FLAG_WINDOW_ORDER = 17
 FLAG_WINDOW_STATS = 18
+HSVDETECT_SET_MAX = 32   # MI355_HSVDETECT_SET_MAX: detector frames per launch set of a Group
 
 
 class HsvSettings(C.Structure):
@@ -203,6 +204,12 @@ def load_library():
         "mi355_group_colordetect_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "mi355_selftest_colordetect_plan": (i, [i, i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                                 C.POINTER(C.c_uint32)]),
+        "mi355_group_set_hsvdetect_rendezvous": (i, [vp, i, C.c_uint]),
+        "mi355_group_submit_hsvdetect": (i, [vp, vp, u8p, i, i, u8p, i, i, i, i, C.POINTER(HsvDetectSettings), C.POINTER(C.c_uint64)]),
+        "mi355_group_wait_hsvdetect": (i, [vp, C.c_uint64]),
+        "mi355_group_hsvdetect_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_hsvdetect_plan": (i, [i, i, C.c_uint, i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32)]),
         "mi355_agroup_create_echo": (vp, [i, i, sz, C.POINTER(C.c_int)]),
         "mi355_agroup_create_ebur128": (vp, [i, i, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_create_loudnorm": (vp, [i, i, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int)]),
@@ -478,6 +485,28 @@ class Group:
         """(frames launched, launch sets, frames in the largest set, kernel launches)."""
         c = (C.c_uint64 * 4)()
         self._ck(self.L.mi355_group_colordetect_stats(self.h, c))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
+    # ---- hsvdetector frames of independent elements
+    def set_hsvdetect_rendezvous(self, expected_streams, linger_us):
+        self._ck(self.L.mi355_group_set_hsvdetect_rendezvous(self.h, expected_streams, linger_us))
+
+    def submit_hsvdetect(self, ctx, d_src, src_stride, src_fmt, d_dst, dst_stride, dst_fmt, width, height, settings):
+        """One device frame of stream `ctx` (settings: the six floats, or None for a null pointer); returns the ticket."""
+        s = None if settings is None else C.byref(HsvDetectSettings(*[float(v) for v in settings]))
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_hsvdetect(self.h, ctx.h, d_src, src_stride, FMT[src_fmt], d_dst, dst_stride, FMT[dst_fmt], width, height, s,
+                                                     C.byref(t)))
+        return t.value
+
+    def wait_hsvdetect(self, ticket):
+        """Returns once the frame's destination holds what Context.hsvdetect_frames_device would have written."""
+        self._ck(self.L.mi355_group_wait_hsvdetect(self.h, ticket))
+
+    def hsvdetect_stats(self):
+        """(frames launched, launch sets, frames in the largest set, kernel launches)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.L.mi355_group_hsvdetect_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
     def close(self):
@@ -909,6 +938,12 @@ class Context:
         self._ck(self.L.mi355_hsvdetect_frame(self.h, _ptr(src), src.nbytes, src_stride, FMT[src_fmt], _ptr(dst), dst.nbytes,
                                               dst_stride, FMT[dst_fmt], width, C.byref(s)))
         return dst
+
+    def hsvdetect_frames_device(self, d_src, src_pitch, src_stride, src_fmt, d_dst, dst_pitch, dst_stride, dst_fmt, n_frames, width, height, settings):
+        """n_frames device frames on this context's stream (asynchronous: synchronize() before reading d_dst back)."""
+        s = None if settings is None else C.byref(HsvDetectSettings(*[float(v) for v in settings]))
+        self._ck(self.L.mi355_hsvdetect_frames_device(self.h, d_src, src_pitch, src_stride, FMT[src_fmt], d_dst, dst_pitch, dst_stride, FMT[dst_fmt],
+                                                      n_frames, width, height, s))
 
     # ---- colorlut
     def colorlut_load(self, is3d, size, table, scale=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0)):

@@ -3,7 +3,12 @@
  * (rank NONE), six gfloat properties mutable in PLAYING :163-218 (defaults :25-31), metadata :323-334, sink formats
  * {RGBx,xRGB,BGRx,xBGR,RGB,BGR} / source formats {RGBA,ARGB,BGRA,ABGR} :336-370 (video_input_formats / video_output_formats),
  * NeverInPlace :373-378, transform_caps swaps the format list and keeps everything else :380-420, transform_frame's 6 x 4
- * format match :423-707 -> mi355_hsvdetect_frame (the per-pixel loop :100-160 runs on the GPU). */
+ * format match :423-707 -> mi355_hsvdetect_frame (the per-pixel loop :100-160 runs on the GPU).
+ * With MI355_GROUP_MEMBERS=n (n >= 2) in the environment the n instances of the process hand their device frames to the device's
+ * dispatcher instead (mi355_group_submit_hsvdetect): the frames of an interval share at most two launches.
+ * The mapped path and the unset environment are unchanged. */
+#include <stdlib.h>
+
 #include "gstmi355common.h"
 
 GST_DEBUG_CATEGORY_STATIC(gst_hsv_detector_debug);
@@ -17,6 +22,8 @@ struct _GstHsvDetector {
   GMutex lock; /* settings: set from application threads, snapshotted once per frame (imp.rs:108) */
   mi355_hsvdetect_settings settings;
   mi355_ctx *ctx;
+  /* MI355_GROUP_MEMBERS=n: the process's dispatcher (mi355_group_shared), held between start and stop */
+  mi355_group *group;
 };
 
 G_DEFINE_TYPE(GstHsvDetector, gst_hsv_detector, GST_TYPE_VIDEO_FILTER)
@@ -68,11 +75,16 @@ static gboolean gst_hsv_detector_start(GstBaseTransform *trans) {
     GST_ELEMENT_ERROR(self, LIBRARY, INIT, ("No MI355X context"), ("%s", mi355_status_string(status)));
     return FALSE;
   }
+  const char *members = g_getenv("MI355_GROUP_MEMBERS");
+  if (members && atoi(members) >= 2 && (self->group = mi355_group_shared(0, &status)))
+    (void)mi355_group_set_hsvdetect_rendezvous(self->group, atoi(members), 2000); /* every instance submits + waits at once; a straggler is waited for 2 ms */
   return TRUE;
 }
 
 static gboolean gst_hsv_detector_stop(GstBaseTransform *trans) {
   GstHsvDetector *self = GST_HSV_DETECTOR(trans);
+  if (self->group) mi355_group_release(self->group);
+  self->group = NULL;
   if (self->ctx) mi355_ctx_destroy(self->ctx);
   self->ctx = NULL;
   return TRUE;
@@ -137,9 +149,24 @@ static GstFlowReturn gst_hsv_detector_transform(GstBaseTransform *trans, GstBuff
   const uint8_t *d_src = mi355_buf_device_ptr(bin, self->ctx, MI355_MAP_READ);
   uint8_t *d_dst = mi355_buf_device_ptr(bout, self->ctx, MI355_MAP_WRITE);
   int rc = d_src && d_dst ? MI355_OK : MI355_ERR_HIP;
-  if (rc == MI355_OK)
+  const gboolean grouped = rc == MI355_OK && self->group;
+  if (grouped) { /* the frame joins whatever the other instances have pending; the bytes are the lone call's */
+    uint64_t ticket = 0;
+    const char *failed = "mi355_group_submit_hsvdetect";
+    rc = mi355_group_submit_hsvdetect(self->group, self->ctx, d_src, GST_VIDEO_INFO_PLANE_STRIDE(ii, 0), in_fmt, d_dst, GST_VIDEO_INFO_PLANE_STRIDE(oi, 0),
+                                      out_fmt, GST_VIDEO_INFO_WIDTH(ii), GST_VIDEO_INFO_HEIGHT(ii), &s, &ticket);
+    if (rc == MI355_OK) {
+      failed = "mi355_group_wait_hsvdetect";
+      rc = mi355_group_wait_hsvdetect(self->group, ticket);
+    }
+    if (rc != MI355_OK) {
+      GST_ERROR_OBJECT(self, "%s: %s", failed, mi355_group_last_error(self->group));
+      return GST_FLOW_ERROR;
+    }
+  } else if (rc == MI355_OK) {
     rc = mi355_hsvdetect_frames_device(self->ctx, d_src, GST_VIDEO_INFO_SIZE(ii), GST_VIDEO_INFO_PLANE_STRIDE(ii, 0), in_fmt, d_dst, GST_VIDEO_INFO_SIZE(oi),
                                        GST_VIDEO_INFO_PLANE_STRIDE(oi, 0), out_fmt, 1, GST_VIDEO_INFO_WIDTH(ii), GST_VIDEO_INFO_HEIGHT(ii), &s);
+  }
   if (rc == MI355_OK) rc = mi355_buf_commit(bin, self->ctx);
   if (rc == MI355_OK) rc = mi355_buf_commit(bout, self->ctx);
   if (rc != MI355_OK) {

@@ -338,6 +338,55 @@ int mi355_group_colordetect_stats(mi355_group *group, uint64_t stats[4]);
 int mi355_selftest_colordetect_plan(int n_cu, int n_jobs, const uint64_t *n_samples, uint32_t *first_block, uint32_t *blocks,
                                     uint64_t *samples_per_block, uint32_t *total_blocks);
 
+/* hsvdetector across independent element instances. The reference hands each element one buffer per call
+ * (video/hsv/src/hsvdetector/imp.rs:423-707); N detectors in one process are N short launches per frame period, each a few
+ * microseconds of device work behind a launch that costs more. submit_hsvdetect queues one device frame of stream `ctx` and whatever
+ * is pending goes out as at most TWO launches over a job table in the kernel arguments, on the queue's own HIP stream. Members are
+ * fully independent: each frame has its own size, strides, input format (RGBx, xRGB, BGRx, xBGR, RGB, BGR), output format (RGBA,
+ * ARGB, BGRA, ABGR) and six settings. After wait_hsvdetect, d_dst holds what mi355_hsvdetect_frames_device(ctx, d_src, 0,
+ * src_stride, src_format, d_dst, 0, dst_stride, dst_format, 1, width, height, settings) would have written, byte for byte, and no
+ * byte outside width * 4 bytes of each of height rows has been touched.
+ *   submit : never blocks; the checks and status codes are those of mi355_hsvdetect_frames_device with n_frames = 1 (format pair,
+ *           settings pointer, negative sizes, null data with a non-empty frame, line bytes against stride; a null ctx or a null
+ *           ticket: MI355_ERR_INVALID_ARG). A refused submit queues nothing. A frame with width == 0 or height == 0 is accepted,
+ *           gets a ticket and writes nothing. The settings are copied and the member's MI355_FLAG_FORCE_GENERIC is read at submit.
+ *           The frame is read after what ctx's HIP stream held at the call; d_src is read and d_dst written until wait_hsvdetect
+ *           for the ticket has returned.
+ *   wait   : launches what is pending if the frame has not gone out (rendezvous first), then waits for its launch set; the
+ *           group's lock is not held meanwhile. A result is collected once. Tickets are one sequence per group: a ticket that is
+ *           unknown, already collected or another queue's is MI355_ERR_INVALID_ARG here and stays collectable where it belongs;
+ *           mi355_group_wait, _order_after, _wait_compare and _wait_colordetect refuse a detector ticket likewise.
+ *   set_hsvdetect_rendezvous : as set_colordetect_rendezvous, counted over pending detector frames only. The other queues'
+ *           rendezvous, streams and stats and this queue's do not touch each other.
+ *   At most MI355_HSVDETECT_SET_MAX frames share a launch set; more go out as consecutive sets. flush, wait_all and destroy cover
+ *   this queue as they cover the others. A launch that fails is reported to the call that caused it and, once, to each frame's
+ *   own wait.
+ *   The two launches: the vector launch (four pixels per lane) carries every frame the lone entry would give to its flat or its
+ *   rgb24 kernel - packed rows on both sides, destination 16-byte aligned, source 16-byte (4-byte input) or 4-byte (3-byte input)
+ *   aligned, pixel count a multiple of 4, 180 - hue_ref in [-360, 360], FORCE_GENERIC off; the literal launch (one pixel per lane,
+ *   IEEE division and fmodf) carries every other frame.
+ *   hsvdetect_stats : {frames launched, launch sets, frames in the largest set, kernel launches} - per set 0 launches when no frame
+ *           has a pixel, 1 when all frames are of one class, 2 when both classes occur.
+ *   mi355_selftest_hsvdetect_plan : host only, no device: the blocks of one launch over n_jobs jobs of units[j] work units.
+ *           budget = n_cu * blocks_per_cu (at most 2^31 - 1); job j wants ceil(units[j] / units_per_block) blocks. If the wants fit
+ *           the budget every job gets its want. Otherwise every job with units gets one block and the rest of the budget is shared
+ *           in proportion to what the jobs still want (want - 1), rounded down: no job gets more than its want, a job without
+ *           units gets none, and the total is at most max(budget, jobs with units). first_block is the running sum. The vector
+ *           launch plans 16-byte pixel groups with units_per_block = 512 and blocks_per_cu = 64, the literal launch pixels with 256
+ *           and 32. Refused (MI355_ERR_INVALID_ARG): n_cu < 1, blocks_per_cu < 1, units_per_block == 0, n_jobs outside
+ *           0..MI355_HSVDETECT_SET_MAX, null arrays with n_jobs > 0, a null total_blocks. */
+#define MI355_HSVDETECT_SET_MAX 32 /* frames per launch set */
+int mi355_group_set_hsvdetect_rendezvous(mi355_group *group, int expected_streams, unsigned linger_us);
+int mi355_group_submit_hsvdetect(mi355_group *group, mi355_ctx *ctx, const uint8_t *d_src, int src_stride, int src_format,
+                                 uint8_t *d_dst, int dst_stride, int dst_format, int width, int height,
+                                 const mi355_hsvdetect_settings *settings, uint64_t *ticket);
+int mi355_group_wait_hsvdetect(mi355_group *group, uint64_t ticket);
+/* {frames launched, launch sets, frames in the largest set, kernel launches} */
+int mi355_group_hsvdetect_stats(mi355_group *group, uint64_t stats[4]);
+/* host only, no device: the block plan of one launch of a set */
+int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_jobs, const uint64_t *units,
+                                  uint32_t *first_block, uint32_t *blocks, uint32_t *total_blocks);
+
 /* ---------------------------------------------------------------- many AUDIO element instances, few launches (csrc/agroup.hip)
  * rsaudioecho (audio/audiofx/src/audioecho/imp.rs:205-227), ebur128level (audio/audiofx/src/ebur128level/imp.rs:682-745) and
  * audioloudnorm (audio/audiofx/src/audioloudnorm/imp.rs:1545-1586) are one instance per stream and one buffer per call; the batch
@@ -402,7 +451,7 @@ int mi355_agroup_ebur128_peak(mi355_agroup *group, int member, int true_peak, un
 int mi355_agroup_echo_get_state(mi355_agroup *group, int member, double *ring_out, size_t ring_len, size_t *pos_out);
 int mi355_agroup_stats(mi355_agroup *group, uint64_t stats[3]);
 /* Process-wide groups. Elements of independent pipelines cannot hand a group to each other; what they share is the process
- * (gst/gstrsaudioecho.c, gstebur128level.c, gstaudioloudnorm.c, gstvideocompare.c, gstcolordetect.c with MI355_GROUP_MEMBERS=n in the environment).
+ * (gst/gstrsaudioecho.c, gstebur128level.c, gstaudioloudnorm.c, gstvideocompare.c, gstcolordetect.c, gsthsvdetector.c with MI355_GROUP_MEMBERS=n in the environment).
  *   mi355_agroup_shared_* : THE group of this configuration (kind, device, member count, parameters), created at first use, and
  *           the next free member index in *member; a group whose members have all been handed out is not offered again.
  *   mi355_agroup_release  : detach; the last member out destroys the group.

@@ -17,7 +17,10 @@
 //     audio/hrtf/src/hrtf/imp.rs:164-278, for every member that has a block in ONE launch set); sofalizer - own channel count, filter
 //     length, partition-length and block-length per member, own filter spectra, delay lines and drop flags, filters queued at
 //     set_filter and transformed with the member's next launch set (sofa_kernels.hip's job tables: the block loop of
-//     Sofalizer::process, audio/hrtf/src/sofa/imp.rs:235-322, for every member that has blocks in ONE launch set);
+//     Sofalizer::process, audio/hrtf/src/sofa/imp.rs:235-322, for every member that has blocks in ONE launch set); minus1mixer /
+//     audiomultimixer - a member is one mixer (one room of a bridge server) with its own contribution matrix, segment list, output
+//     formats and frames per submit (mixer.hip's job tables: aggregate_one_buffer, audio/audiomultimixer/src/audiomultimixerelement.rs:606-753,
+//     and split_output_buf, audio/audiomultimixer/src/splitter.rs:433-467, for every member that has submitted in ONE kernel launch);
 //     ebur128level - own buffer size, 100 ms phase and `reset` (per-stream rounds in ebur128_kernels.hip); audioloudnorm - own frame
 //     type and ring positions (loudnorm.hip: a launch sequence per CLASS of members that stand at the same frame type and size:
 //     streams that started together are one class). A waiter that has lingered `linger_us` launches whoever is there: a member that
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(256) void echo_jobs_commit_kernel(const EchoJob *__
 
 namespace {
 
-enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4, KIND_HRTF = 5, KIND_SOFA = 6 };
+enum { KIND_ECHO = 1, KIND_EBUR128 = 2, KIND_LOUDNORM = 3, KIND_AGING = 4, KIND_HRTF = 5, KIND_SOFA = 6, KIND_MIXER = 7 };
 
 // a member's life cycle: at most ONE buffer is outstanding, its ticket is collected once, and nothing else of the member moves in between
 //   IDLE -> FILLING (submit accepted; the buffer is on its way into the staging slot, possibly outside the lock) -> SUBMITTED (it
@@ -121,7 +124,7 @@ struct Sub {   // one member's submission: the buffer it has outstanding
   bool device = false;
   void *data = nullptr;      // caller's buffer (echo: in place; ebur128: input; loudnorm: input)
   void *out = nullptr;       // loudnorm / hrtfrender / sofalizer: caller's output buffer
-  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm / agingradio / hrtfrender / sofalizer: frames
+  size_t n = 0;              // echo: interleaved samples; ebur128 / loudnorm / agingradio / hrtfrender / sofalizer / mixer: frames
   size_t out_cap = 0;        // loudnorm: capacity of `out` in frames
   int fmt = 0;               // echo / agingradio: is_f64; ebur128: sample format
   int final_frame = 0;       // loudnorm
@@ -138,6 +141,15 @@ struct AgingMember {         // one agingradio instance's state (AudioFilterImpl
   double alpha = 0;
   double *d_state = nullptr; // lowpass output per channel; nullptr: lowpass-freq 0 at setup
   unsigned long long k = 0, seed = 0;   // frame pairs processed since setup; Philox key
+};
+
+struct MixerMember {         // one mixer: its matrix (mixer_setup) and what its outstanding submit carries
+  bool configured = false;
+  unsigned n_inputs = 0, n_out = 0;
+  std::vector<uint16_t> bits;                // mixer_pack_contrib's words
+  std::vector<mi355_mixer_segment> segs;     // copied at submit; a host member's `data` is resolved against its slot when the set runs
+  std::vector<mi355_mixer_output> outs;      // copied at submit; `data` stays the caller's buffer (a host member's is filled by wait)
+  MixerLayout layout;                        // host members: where the buffers sit in the member's input and output slot
 };
 
 }  // namespace
@@ -179,6 +191,10 @@ struct mi355_agroup {
   // ---- sofalizer
   SofaGroup *sofa = nullptr;        // the members' convolvers, filter queue and job tables (sofa_kernels.hip)
   std::vector<float> sofa_g;        // [member][64]: gains [C], copied at submit
+  // ---- minus1mixer / audiomultimixer
+  std::vector<MixerMember> mixer;
+  MixerTablesBuf *mix_tables = nullptr;   // the job tables of a launch set (mixer.hip)
+  uint64_t mix_launches = 0;
   // ---- ebur128
   unsigned channels = 0;
   int set_fmt = -1;                 // ebur128: the sample format of the launch set being collected, fixed by the first member accepted into it
@@ -211,9 +227,10 @@ int ahip(mi355_agroup *g, hipError_t e, const char *what) {
 // staging slots of at least `need` bytes per member (and `out_need` for the output side). A slab is replaced while no copy runs on it and
 // no launch is in flight; what it holds of members' business - submissions copied in, results not collected yet - moves along.
 // a member's row of the output slab: loudnorm's is out_cap_bytes rounded down to whole frames of its channel count; hrtfrender's
-// and sofalizer's output is stereo f32 whatever the member's input channels are, and its row is the slot itself
+// and sofalizer's output is stereo f32 whatever the member's input channels are, and its row is the slot itself; so is a mixer's,
+// which packs its outputs' buffers into it
 size_t out_row(const mi355_agroup *g, size_t cap) {
-  if (g->kind == KIND_HRTF || g->kind == KIND_SOFA) return cap;
+  if (g->kind == KIND_HRTF || g->kind == KIND_SOFA || g->kind == KIND_MIXER) return cap;
   const size_t fb = (size_t)g->channels * 8;
   return cap / fb * fb;
 }
@@ -248,7 +265,7 @@ int ensure_staging(mi355_agroup *g, std::unique_lock<std::mutex> &lk, size_t nee
     if ((rc = ahip(g, hipMalloc((void **)&d, cap * (size_t)g->n_members), "hipMalloc(agroup output staging)"))) { (void)hipHostFree(h); return rc; }
     // results that their members have not collected yet move along (a row of the output slab is out_cap_bytes wide, rounded down to
     // whole frames: wait() computes the row the same way)
-    if (g->h_out && (g->channels || g->kind == KIND_HRTF || g->kind == KIND_SOFA)) {
+    if (g->h_out && (g->channels || g->kind == KIND_HRTF || g->kind == KIND_SOFA || g->kind == KIND_MIXER)) {
       const size_t old_row = out_row(g, g->out_cap_bytes), new_row = out_row(g, cap);
       for (int m = 0; m < g->n_members; m++)
         if (g->res_pending[(size_t)m]) std::memcpy(h + (size_t)m * new_row, g->h_out + (size_t)m * old_row, old_row);
@@ -584,6 +601,60 @@ int run_sofa(mi355_agroup *g) {
   return ahip(g, hipStreamSynchronize(st), "agroup sofa: sync");
 }
 
+// ---- minus1mixer / audiomultimixer: the members that have submitted mix their interval in ONE kernel launch (mixer.hip: one job
+// per member, blocks per (member, frame tile, channel group)). Host members: their segments were packed into their input slots at
+// submit; one strided upload and one strided download per run of consecutive participating host members. Device members pass
+// their pointers straight through. g->mu held.
+int run_mixer(mi355_agroup *g) {
+  std::vector<int> who;
+  size_t max_in = 0, max_out = 0;
+  for (int m = 0; m < g->n_members; m++) {
+    if (!g->sub[m].have()) continue;
+    who.push_back(m);
+    if (!g->sub[m].device) {
+      const MixerLayout &L = g->mixer[(size_t)m].layout;
+      if (L.in_bytes > max_in) max_in = L.in_bytes;
+      if (L.out_bytes_total > max_out) max_out = L.out_bytes_total;
+    }
+  }
+  if (who.empty()) return MI355_OK;
+  hipStream_t st = g->ctx->stream;
+  int rc = MI355_OK;
+  std::vector<std::pair<int, int>> runs;   // [first, last] member of each run (never across the slot of a member that is not part of this set)
+  for (int m : who) {
+    if (g->sub[m].device) continue;
+    if (!runs.empty() && runs.back().second == m - 1) runs.back().second = m;
+    else runs.push_back({m, m});
+  }
+  if (max_in > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->d_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, g->h_in + (size_t)r.first * g->cap_bytes, g->cap_bytes, max_in,
+                                         (size_t)(r.second - r.first + 1), hipMemcpyHostToDevice, st), "agroup mixer: upload"))) return rc;
+  std::vector<std::vector<mi355_mixer_segment>> segs(who.size());
+  std::vector<std::vector<mi355_mixer_output>> outs(who.size());
+  std::vector<MixerCall> calls(who.size());
+  for (size_t j = 0; j < who.size(); j++) {
+    const int m = who[j];
+    const MixerMember &M = g->mixer[(size_t)m];
+    segs[j] = M.segs;
+    outs[j] = M.outs;
+    if (!g->sub[m].device) {
+      for (size_t i = 0; i < segs[j].size(); i++) segs[j][i].data = g->d_in + (size_t)m * g->cap_bytes + M.layout.seg_off[i];
+      for (size_t o = 0; o < outs[j].size(); o++) outs[j][o].data = g->d_out + (size_t)m * g->out_cap_bytes + M.layout.out_off[o];
+    }
+    calls[j] = MixerCall{M.n_inputs, M.n_out, M.bits.data(), segs[j].data(), (unsigned)segs[j].size(), outs[j].data(), (unsigned)outs[j].size(), g->sub[m].n};
+  }
+  std::string err;
+  int launches = 0;
+  if ((rc = mixer_launch(g->mix_tables, st, calls.data(), (int)calls.size(), &launches, &err))) return afail(g, rc, err);
+  g->mix_launches += (uint64_t)launches;
+  if (max_out > 0)
+    for (const auto &r : runs)
+      if ((rc = ahip(g, hipMemcpy2DAsync(g->h_out + (size_t)r.first * g->out_cap_bytes, g->out_cap_bytes, g->d_out + (size_t)r.first * g->out_cap_bytes, g->out_cap_bytes,
+                                         max_out, (size_t)(r.second - r.first + 1), hipMemcpyDeviceToHost, st), "agroup mixer: download"))) return rc;
+  return ahip(g, hipStreamSynchronize(st), "agroup mixer: sync");
+}
+
 // runs the collected interval. g->mu held (the members are blocked on it or on the condition variable anyway).
 void run_interval(mi355_agroup *g) {
   (void)hipSetDevice(g->device);
@@ -593,6 +664,7 @@ void run_interval(mi355_agroup *g) {
   else if (g->kind == KIND_AGING) rc = run_aging(g);
   else if (g->kind == KIND_HRTF) rc = run_hrtf(g);
   else if (g->kind == KIND_SOFA) rc = run_sofa(g);
+  else if (g->kind == KIND_MIXER) rc = run_mixer(g);
   else rc = run_loudnorm(g);
   uint64_t carried = 0;
   for (int m = 0; m < g->n_members; m++) {
@@ -744,6 +816,7 @@ void mi355_agroup_destroy(mi355_agroup *g) {
   if (g->h_ajobs) (void)hipHostFree(g->h_ajobs);
   hrtf_group_free(g->hrtf);
   sofa_group_free(g->sofa);
+  mixer_tables_free(g->mix_tables);
   if (g->ctx) mi355_ctx_destroy(g->ctx);   // releases the ebur128 / loudnorm batch engines with it
   delete g;
 }
@@ -931,6 +1004,17 @@ int mi355_agroup_wait(mi355_agroup *g, uint64_t ticket, size_t *out_frames) {
       g->copying++;   // (a block is tens of KB: copied outside the lock, the slab pinned in place by the count)
       lk.unlock();
       std::memcpy(dst, src, frames * 8);
+      lk.lock();
+      g->copying--;
+      g->cv.notify_all();
+    }
+  } else if (g->kind == KIND_MIXER) {
+    const MixerMember &M = g->mixer[(size_t)member];
+    if (!s.device && frames && !M.outs.empty()) {
+      const char *src = g->h_out + (size_t)member * g->out_cap_bytes;
+      g->copying++;   // (the member is busy until this returns: its output list and layout stay; the slab is pinned in place by the count)
+      lk.unlock();
+      for (size_t o = 0; o < M.outs.size(); o++) std::memcpy(M.outs[o].data, src + M.layout.out_off[o], M.layout.out_bytes[o]);
       lk.lock();
       g->copying--;
       g->cv.notify_all();
@@ -1289,6 +1373,100 @@ uint64_t mi355_agroup_sofa_launches(mi355_agroup *g) {
   return sofa_group_launches(g->sofa);
 }
 
+// ---- mixer members (minus1mixer / audiomultimixer, audio/audiomultimixer/src)
+mi355_agroup *mi355_agroup_create_mixer(int device, int n_members, int *status) {
+  mi355_agroup *g = agroup_new(device, KIND_MIXER, n_members, status);
+  if (!g) return nullptr;
+  int rc = MI355_OK;
+  g->mixer.assign((size_t)n_members, MixerMember{});
+  g->mix_tables = mixer_tables_new(&g->last_error, &rc);
+  if (!g->mix_tables) { if (status) *status = rc; mi355_agroup_destroy(g); return nullptr; }
+  if (status) *status = MI355_OK;
+  return g;
+}
+
+// the member's contribution matrix (contrib nullptr: minus1mixer's i != o); between intervals only
+static int agroup_mixer_setup(mi355_agroup *g, int member, unsigned n_inputs, unsigned n_out, const uint8_t *contrib) {
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_MIXER, member);
+  if (rc) return rc;
+  const char *why = "";
+  if ((rc = mixer_check_setup(n_inputs, n_out, &why))) return afail(g, rc, why);
+  MixerMember &M = g->mixer[(size_t)member];
+  M.n_inputs = n_inputs;
+  M.n_out = n_out;
+  mixer_pack_contrib(n_inputs, n_out, contrib, &M.bits);
+  M.configured = true;
+  return MI355_OK;
+}
+
+// OutputConfiguration::get_output_contributions_for_input_channel of one member (audiomultimixerelement.rs:191-214)
+int mi355_agroup_mixer_setup(mi355_agroup *g, int member, unsigned n_inputs, unsigned n_out_channels, const uint8_t *contrib) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  if (!contrib) { std::lock_guard<std::mutex> lk(g->mu); return afail(g, MI355_ERR_INVALID_ARG, "mixer: null contribution matrix"); }
+  return agroup_mixer_setup(g, member, n_inputs, n_out_channels, contrib);
+}
+
+// update_output_config's matrix for one member (minus1mixer.rs:500-537)
+int mi355_agroup_mixer_setup_minus1(mi355_agroup *g, int member, unsigned n_streams) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  return agroup_mixer_setup(g, member, n_streams, n_streams, nullptr);
+}
+
+// One interval of one member (aggregate_one_buffer per segment, audiomultimixerelement.rs:606-753, then split_output_buf per output,
+// splitter.rs:433-467). The arrays are copied here; a host member's segments go into its input slot now (a 10 ms interval of a
+// 256-party room is 240 KB), its outputs come back at wait. wait() answers `frames`.
+int mi355_agroup_submit_mixer(mi355_agroup *g, int member, const mi355_mixer_segment *segments, unsigned n_segments, const mi355_mixer_output *outputs,
+                              unsigned n_outputs, size_t frames, int device_data, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(g->mu);
+  int rc = check_member(g, KIND_MIXER, member);
+  if (rc) return rc;
+  MixerMember &M = g->mixer[(size_t)member];
+  if (!M.configured) return afail(g, MI355_ERR_NOT_CONFIGURED, "mixer: not configured (setup not called)");
+  const char *why = "";
+  const bool device = device_data != 0;
+  if ((rc = mixer_check(M.n_inputs, M.n_out, segments, n_segments, outputs, n_outputs, frames, device, &why))) return afail(g, rc, why);
+  (void)hipSetDevice(g->device);
+  MixerLayout L;
+  if (!device) {
+    mixer_layout(segments, n_segments, outputs, n_outputs, frames, &L);
+    if ((rc = ensure_staging(g, lk, L.in_bytes, L.out_bytes_total))) return rc;
+  }
+  M.segs.assign(segments, segments + n_segments);
+  M.outs.assign(outputs, outputs + n_outputs);
+  M.layout = std::move(L);
+  Sub &s = g->sub[member];
+  s.device = device; s.data = nullptr; s.out = nullptr; s.n = frames;
+  if (!device && M.layout.in_bytes) {
+    // the segments go into the member's slot as submitted() copies a single buffer: a large room (256 parties: 240 KB) outside the
+    // lock, the member marked busy and the slab pinned in place by the count; a small one under it
+    char *slot = g->h_in + (size_t)member * g->cap_bytes;
+    const bool outside = M.layout.in_bytes > (size_t)65536;
+    if (outside) {
+      s.state = M_FILLING;
+      g->copying++;
+      lk.unlock();
+    }
+    for (unsigned i = 0; i < n_segments; i++)
+      if (M.layout.seg_bytes[i]) std::memcpy(slot + M.layout.seg_off[i], M.segs[i].data, M.layout.seg_bytes[i]);
+    if (outside) {
+      lk.lock();
+      g->copying--;
+      g->cv.notify_all();
+    }
+  }
+  submitted(g, lk, member, ticket, nullptr, nullptr, 0);
+  return MI355_OK;
+}
+
+// kernel launches the group's mixer launch sets have made so far (one per set in which a member has a frame; measurement plumbing)
+uint64_t mi355_agroup_mixer_launches(mi355_agroup *g) {
+  if (!g || g->kind != KIND_MIXER) return 0;
+  std::lock_guard<std::mutex> lk(g->mu);
+  return g->mix_launches;
+}
+
 int mi355_agroup_stats(mi355_agroup *g, uint64_t stats[3]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
@@ -1423,6 +1601,10 @@ mi355_agroup *mi355_agroup_shared_hrtf(int device, int n_members, int *member, i
 
 mi355_agroup *mi355_agroup_shared_sofa(int device, int n_members, int *member, int *status) {
   return shared_get(key_of("sofa", device, n_members, nullptr, 0), n_members, member, status, [&] { return mi355_agroup_create_sofa(device, n_members, status); });
+}
+
+mi355_agroup *mi355_agroup_shared_mixer(int device, int n_members, int *member, int *status) {
+  return shared_get(key_of("mixer", device, n_members, nullptr, 0), n_members, member, status, [&] { return mi355_agroup_create_mixer(device, n_members, status); });
 }
 
 void mi355_agroup_release(mi355_agroup *g, int member) {

@@ -191,6 +191,7 @@ void mi355_ctx_destroy(mi355_ctx *ctx) {
   roundedcorners_release(ctx);
   colordetect_release(ctx);
   agingradio_release(ctx);
+  mixer_release(ctx);
   ebur128_release(ctx);
   hrtf_release(ctx);
   sofa_release(ctx);

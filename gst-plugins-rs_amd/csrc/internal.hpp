@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <vector>
 #include "../../include/mi355fx.h"
 
 #include "autopick.hpp"
@@ -99,6 +100,7 @@ struct mi355_ctx {
   void *rounded = nullptr;     // mi355::RoundedMask (roundedcorners.hip): the element's alpha plane, device-resident
   void *colordetect = nullptr; // mi355::ColorDetectState (colordetect.hip): histograms and palette results
   void *agingradio = nullptr;  // mi355::AgingState (agingradio.hip): lowpass filter states, pair counter, seed
+  void *mixer = nullptr;       // mi355::MixerState (mixer.hip): the contribution matrix, job tables and the host form's staging
   // host <-> device copies this context has enqueued through the library's own entry points and mi355_buf objects (tests assert
   // that a chain of elements on device buffers costs ONE upload and ONE download: mi355_ctx_transfer_counts)
   unsigned long long n_h2d = 0, n_d2h = 0;
@@ -274,6 +276,33 @@ int agingradio_setup_filter(unsigned rate, unsigned lowpass_freq, double *alpha)
 void agingradio_settings_to_job(const mi355_agingradio_settings &s, AgingJob *J);
 int launch_agingradio_jobs(hipStream_t stream, int n_cu, const AgingJob *h_jobs, const AgingJob *d_jobs, unsigned n_jobs, std::string *err);
 void agingradio_release(mi355_ctx *ctx);
+// minus1mixer / audiomultimixer (mixer.hip): one call = one mixer's interval, checked, its data pointers on the device. The group
+// (agroup.hip) launches one call per member that has submitted, a context a set of one.
+struct MixerCall {
+  unsigned n_inputs, n_out_channels;
+  const uint16_t *bits;   // host: mixer_pack_contrib's words
+  const mi355_mixer_segment *segs;
+  unsigned n_segs;
+  const mi355_mixer_output *outs;
+  unsigned n_outs;
+  size_t frames;
+};
+struct MixerLayout {      // the host form's packing of a call's buffers into an input and an output slot
+  std::vector<size_t> seg_off, seg_bytes, out_off, out_bytes;
+  size_t in_bytes = 0, out_bytes_total = 0;
+};
+struct MixerTablesBuf;    // pinned + device image of a launch's job tables
+MixerTablesBuf *mixer_tables_new(std::string *err, int *status);
+void mixer_tables_free(MixerTablesBuf *B);
+void mixer_pack_contrib(unsigned n_inputs, unsigned n_out, const uint8_t *contrib, std::vector<uint16_t> *bits);   // contrib nullptr: i != o
+int mixer_check_setup(unsigned n_inputs, unsigned n_out, const char **why);
+int mixer_check(unsigned n_inputs, unsigned n_out, const mi355_mixer_segment *segs, unsigned n_segs, const mi355_mixer_output *outs, unsigned n_outs,
+                size_t frames, bool device, const char **why);
+void mixer_layout(const mi355_mixer_segment *segs, unsigned n_segs, const mi355_mixer_output *outs, unsigned n_outs, size_t frames, MixerLayout *L);
+int mixer_plan(int n_members, const uint32_t *n_inputs, const uint32_t *n_out_channels, const uint32_t *n_segments, const uint32_t *n_outputs,
+               const uint64_t *frames, uint32_t *first_block, uint32_t *seg_off, uint32_t *out_off, uint32_t *bits_off);
+int mixer_launch(MixerTablesBuf *B, hipStream_t stream, const MixerCall *calls, int n, int *kernel_launches, std::string *err);
+void mixer_release(mi355_ctx *ctx);
 int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, int channel, int kind, float *out, int *w, int *h);
 int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate);
 int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps);

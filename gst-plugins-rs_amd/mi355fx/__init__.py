@@ -40,6 +40,7 @@ FLAG_BLOCKHASH_ANY_SIZE = 15
 FLAG_WINDOW_ORDER = 17
 FLAG_WINDOW_STATS = 18
 HSVDETECT_SET_MAX = 32   # MI355_HSVDETECT_SET_MAX: detector frames per launch set of a Group
+MIXER_FRAME_TILE = 64    # MI355_MIXER_FRAME_TILE: frames per block of the mixer kernel
 
 
 class HsvSettings(C.Structure):
@@ -56,6 +57,39 @@ class AgingRadioSettings(C.Structure):
     def of(cls, d):
         return cls(d.get("white_noise_ampl", 0.011), d.get("clicks_prob", 1.0 / 100000.0), d.get("bits_to_quantize", 4.0),
                    d.get("cubic_curve_distortion", 1.0), d.get("cubic_curve_passes", 3))
+
+
+class MixerSegment(C.Structure):
+    """mi355_mixer_segment: num_frames mono frames of input pad `input` (format 0 F32LE, 1 S16LE) landing at output frame out_offset."""
+    _fields_ = [("data", C.c_void_p), ("input", C.c_uint32), ("format", C.c_uint32), ("out_offset", C.c_uint32), ("num_frames", C.c_uint32)]
+
+
+class MixerOutput(C.Structure):
+    """mi355_mixer_output: an interleaved buffer of frames x n_channels samples fed by the channels from channel_offset on."""
+    _fields_ = [("data", C.c_void_p), ("format", C.c_uint32), ("channel_offset", C.c_uint32), ("n_channels", C.c_uint32)]
+
+
+def mixer_tables(segments, outputs):
+    """The arrays of a mixer call. segments: (input, data, out_offset) with data a 1-D numpy float32 / int16 array, or
+    (input, (pointer, format, num_frames), out_offset) for device memory; outputs: (data, channel_offset, n_channels) with data a
+    numpy float32 / int16 array of frames * n_channels samples, or ((pointer, format), channel_offset, n_channels).
+    -> (MixerSegment array, MixerOutput array); the caller keeps the numpy arrays alive."""
+    fmt = {np.dtype(np.float32): 0, np.dtype(np.int16): 1}
+    segs = (MixerSegment * max(len(segments), 1))()
+    for k, (inp, data, off) in enumerate(segments):
+        if isinstance(data, np.ndarray):
+            assert data.ndim == 1 and data.flags.c_contiguous
+            segs[k] = MixerSegment(data.ctypes.data if data.size else None, inp, fmt[data.dtype], off, data.size)
+        else:
+            segs[k] = MixerSegment(data[0], inp, data[1], off, data[2])
+    outs = (MixerOutput * max(len(outputs), 1))()
+    for k, (data, off, nch) in enumerate(outputs):
+        if isinstance(data, np.ndarray):
+            assert data.flags.c_contiguous
+            outs[k] = MixerOutput(data.ctypes.data if data.size else None, fmt[data.dtype], off, nch)
+        else:
+            outs[k] = MixerOutput(data[0], data[1], off, nch)
+    return segs, outs
 
 
 class HsvDetectSettings(C.Structure):
@@ -240,6 +274,19 @@ def load_library():
         "mi355_agroup_agingradio_setup": (i, [vp, i, C.c_uint, C.c_uint, C.c_uint, C.c_uint64]),
         "mi355_agroup_submit_agingradio": (i, [vp, i, vp, sz, i, C.POINTER(AgingRadioSettings), i, C.POINTER(C.c_uint64)]),
         "mi355_agroup_agingradio_get_state": (i, [vp, i, C.POINTER(C.c_double), C.c_uint, C.POINTER(C.c_uint64)]),
+        "mi355_mixer_setup": (i, [vp, C.c_uint, C.c_uint, vp]),
+        "mi355_mixer_setup_minus1": (i, [vp, C.c_uint]),
+        "mi355_mixer_process": (i, [vp, C.POINTER(MixerSegment), C.c_uint, C.POINTER(MixerOutput), C.c_uint, sz]),
+        "mi355_mixer_process_device": (i, [vp, C.POINTER(MixerSegment), C.c_uint, C.POINTER(MixerOutput), C.c_uint, sz]),
+        "mi355_mixer_reset": (i, [vp]),
+        "mi355_selftest_mixer_plan": (i, [i] + [C.POINTER(C.c_uint32)] * 4 + [C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint32)] * 4 + [C.c_uint32]
+                                      + [C.POINTER(C.c_uint32)] * 3),
+        "mi355_agroup_create_mixer": (vp, [i, i, C.POINTER(C.c_int)]),
+        "mi355_agroup_shared_mixer": (vp, [i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mi355_agroup_mixer_setup": (i, [vp, i, C.c_uint, C.c_uint, vp]),
+        "mi355_agroup_mixer_setup_minus1": (i, [vp, i, C.c_uint]),
+        "mi355_agroup_submit_mixer": (i, [vp, i, C.POINTER(MixerSegment), C.c_uint, C.POINTER(MixerOutput), C.c_uint, sz, i, C.POINTER(C.c_uint64)]),
+        "mi355_agroup_mixer_launches": (C.c_uint64, [vp]),
         "mi355_agroup_shared_ebur128": (vp, [i, i, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_shared_loudnorm": (vp, [i, i, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_release": (None, [vp, i]),
@@ -536,6 +583,8 @@ class AudioGroup:
                 self.h = self.L.mi355_agroup_shared_hrtf(device, n_members, C.byref(m), C.byref(st))
             elif kind == "sofa":
                 self.h = self.L.mi355_agroup_shared_sofa(device, n_members, C.byref(m), C.byref(st))
+            elif kind == "mixer":
+                self.h = self.L.mi355_agroup_shared_mixer(device, n_members, C.byref(m), C.byref(st))
             elif kind == "ebur128":
                 cc = kw.get("channel_class")
                 arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -556,6 +605,8 @@ class AudioGroup:
             self.h = self.L.mi355_agroup_create_hrtf(device, n_members, C.byref(st))
         elif kind == "sofa":
             self.h = self.L.mi355_agroup_create_sofa(device, n_members, C.byref(st))
+        elif kind == "mixer":
+            self.h = self.L.mi355_agroup_create_mixer(device, n_members, C.byref(st))
         elif kind == "ebur128":
             cc = kw.get("channel_class")
             arr = (C.c_int * len(cc))(*cc) if cc is not None else None
@@ -724,6 +775,26 @@ class AudioGroup:
 
     def sofa_launches(self):
         return int(self.L.mi355_agroup_sofa_launches(self.h))
+
+    # ---- mixer members (minus1mixer / audiomultimixer)
+    def mixer_setup(self, member, contrib):
+        """contrib: bool matrix [n_inputs, n_out_channels] of one member"""
+        m = np.ascontiguousarray(np.asarray(contrib) != 0, dtype=np.uint8)
+        self._ck(self.L.mi355_agroup_mixer_setup(self.h, member, m.shape[0], m.shape[1], m.ctypes.data))
+
+    def mixer_setup_minus1(self, member, n_streams):
+        self._ck(self.L.mi355_agroup_mixer_setup_minus1(self.h, member, n_streams))
+
+    def submit_mixer(self, member, segments, outputs, frames, device_data=False):
+        """One interval of one member; segments / outputs as mixer_tables takes them. Host outputs are filled by wait."""
+        segs, outs = mixer_tables(segments, outputs)
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_agroup_submit_mixer(self.h, member, segs, len(segments), outs, len(outputs), frames, int(bool(device_data)), C.byref(t)))
+        self._keep[member] = (segments, outputs)   # (after the call: a refused submit leaves the buffers of the outstanding ticket alone)
+        return t.value
+
+    def mixer_launches(self):
+        return int(self.L.mi355_agroup_mixer_launches(self.h))
 
     def submit_ebur128(self, member, data, frames=None, sample_format=None):
         t = C.c_uint64(0)
@@ -1307,6 +1378,28 @@ class Context:
         k = C.c_uint64(0)
         self._ck(self.L.mi355_agingradio_get_state(self.h, y.ctypes.data_as(C.POINTER(C.c_double)), channels, C.byref(k)))
         return y[:channels], int(k.value)
+
+    # ---- minus1mixer / audiomultimixer
+    def mixer_setup(self, contrib):
+        """contrib: bool matrix [n_inputs, n_out_channels]"""
+        m = np.ascontiguousarray(np.asarray(contrib) != 0, dtype=np.uint8)
+        self._ck(self.L.mi355_mixer_setup(self.h, m.shape[0], m.shape[1], m.ctypes.data))
+
+    def mixer_setup_minus1(self, n_streams):
+        self._ck(self.L.mi355_mixer_setup_minus1(self.h, n_streams))
+
+    def mixer_reset(self):
+        self._ck(self.L.mi355_mixer_reset(self.h))
+
+    def mixer_process(self, segments, outputs, frames):
+        """One interval on host memory: segments / outputs as mixer_tables takes them (numpy arrays); the output arrays are filled."""
+        segs, outs = mixer_tables(segments, outputs)
+        self._ck(self.L.mi355_mixer_process(self.h, segs, len(segments), outs, len(outputs), frames))
+
+    def mixer_process_device(self, segments, outputs, frames):
+        """The same on device memory (pointer forms of mixer_tables), enqueued on the context's stream."""
+        segs, outs = mixer_tables(segments, outputs)
+        self._ck(self.L.mi355_mixer_process_device(self.h, segs, len(segments), outs, len(outputs), frames))
 
     # ---- rsaudioecho
     def echo_setup(self, ring_len):

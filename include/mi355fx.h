@@ -416,7 +416,7 @@ int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_pe
  *   stats           : {buffers, launch sets, buffers in the largest set}.
  * A member's life cycle: a member has at most ONE buffer outstanding, from its submit_* until wait(ticket) has returned. Until then
  * another submit_* of that member and its setup / reset / load calls (agingradio_setup, ebur128_reset, hrtf_setup, hrtf_reset,
- * hrtf_load_sphere, sofa_setup, sofa_set_filter, sofa_set_drop, sofa_reset) are refused with MI355_ERR_INVALID_ARG - whether its launch set has run or not - and change nothing. A ticket is
+ * hrtf_load_sphere, sofa_setup, sofa_set_filter, sofa_set_drop, sofa_reset, mixer_setup, mixer_setup_minus1) are refused with MI355_ERR_INVALID_ARG - whether its launch set has run or not - and change nothing. A ticket is
  * collected once: wait takes only the member's outstanding ticket; a second wait for it, ticket 0, a ticket of a coming interval or
  * one the member was never given are refused with MI355_ERR_INVALID_ARG, run no launch set and write to no buffer. detach drops a
  * buffer whose launch set has not run (its wait answers "detached"); a result that has run can still be collected, once.
@@ -921,6 +921,78 @@ int mi355_agroup_agingradio_setup(mi355_agroup *group, int member, unsigned chan
 int mi355_agroup_submit_agingradio(mi355_agroup *group, int member, void *data, size_t frames, int is_f64,
                                    const mi355_agingradio_settings *settings, int device_data, uint64_t *ticket);
 int mi355_agroup_agingradio_get_state(mi355_agroup *group, int member, double *filter_state, unsigned channels, uint64_t *pairs_done);
+
+/* ---------------------------------------------------------------- minus1mixer / audiomultimixer (csrc/mixer.hip)
+ * A conference bridge: every output hears the inputs its row of the contribution matrix names. Replaces the mixing loop of
+ * MultiMixerElement::aggregate_one_buffer (audio/audiomultimixer/src/audiomultimixerelement.rs:606-753) and the splitter's
+ * Splitter::sink_chain / split_output_buf (audio/audiomultimixer/src/splitter.rs:341-358, :433-467): the interleaved f32 buffer
+ * n_out_channels wide that the one fills and the other slices never exists here. One interval of `frames` frames:
+ *   - n_out_channels f32 accumulators per frame start at +0.0 (the aggregator's zero-filled buffer);
+ *   - every segment - `num_frames` mono frames of input pad `input`, F32LE or S16LE, landing at output frame `out_offset` - adds
+ *     in_sample = f32::from(x) / conv_scale (1.0 for F32, 32768.0 for S16, :707) to every channel c with contrib[input][c]
+ *     (:711-715), IN ARRAY ORDER: f32 addition is not associative, the order is part of the result. A pad may send several
+ *     segments per interval, or none;
+ *   - every output owns the channels [channel_offset, channel_offset + n_channels) (create_output_buffer, :580-603) and gets
+ *     T::from_f32(acc * conv_scale) (splitter.rs:460): F32 unchanged, S16 as Rust's `as i16` (toward zero, NaN 0, saturating).
+ * Limits, beyond any of which the call returns MI355_ERR_UNSUPPORTED: n_inputs <= 256, n_out_channels <= 256, at most 1024
+ * segments per interval, frames <= 2^20; and at most 1024 outputs per call. Inputs are mono, as the reference asserts (:624).
+ *   _setup          : OutputConfiguration::get_output_contributions_for_input_channel (:191-214) as a row-major bool matrix
+ *                     n_inputs x n_out_channels (non-zero = contributes). May be called again between intervals: pads come and go
+ *                     (request_new_pad / release_pad). Zero inputs or channels, a null matrix: MI355_ERR_INVALID_ARG.
+ *   _setup_minus1   : the matrix update_output_config builds (audio/audiomultimixer/src/minus1mixer.rs:500-537): n_streams inputs,
+ *                     n_streams one-channel outputs, contrib[i][o] = (i != o). A lone participant hears silence.
+ *   _process        : host buffers of any alignment, synchronous; the samples travel through one pinned slab: one upload and one
+ *                     download per call, beside the small copy of the launch's job table that both forms make.
+ *   _process_device : device buffers, enqueued on the context's stream (the segment and output arrays are copied in the call).
+ *                     Every `data` pointer is aligned to its sample type - 4 bytes for F32, 2 for S16 - or the call returns
+ *                     MI355_ERR_INVALID_ARG: apply in_offset in frames, not in bytes.
+ *                     `data` of a segment points at its first frame to mix (the caller has applied in_offset); an output buffer is
+ *                     frames x n_channels interleaved samples. Output ranges may overlap or leave channels unused. frames == 0,
+ *                     a segment of no frames, no segment at all (silence) are fine. Nothing is written and nothing is launched when:
+ *                     before setup MI355_ERR_NOT_CONFIGURED; input >= n_inputs, a format other than 0 / 1, out_offset + num_frames
+ *                     > frames, channel_offset + n_channels > n_out_channels, n_channels == 0, null data of a non-empty segment
+ *                     or output: MI355_ERR_INVALID_ARG.
+ *   _reset          : the element's stop: the matrix goes (process answers MI355_ERR_NOT_CONFIGURED again).
+ *   mi355_selftest_mixer_plan : host only, no device: the job table of one launch for n_members mixers. Member j gets
+ *                     ceil(frames[j] / MI355_MIXER_FRAME_TILE) * ceil(n_out_channels[j] / 16) blocks from first_block[j] on and
+ *                     its slices of the segment, output and contribution-word tables (seg_offset, out_offset, bits_offset; every
+ *                     array is [n_members + 1], the total last). With the three block_* arrays (block_capacity entries each, at
+ *                     least the total) it also answers, through the function the kernel uses, which member, frame tile and
+ *                     channel group each block serves. A limit exceeded: MI355_ERR_UNSUPPORTED. */
+#define MI355_MIXER_FRAME_TILE 64 /* frames per block of the mixer kernel */
+typedef struct mi355_mixer_segment {
+  const void *data;
+  uint32_t input, format /* 0 F32LE, 1 S16LE */, out_offset, num_frames;
+} mi355_mixer_segment;
+typedef struct mi355_mixer_output {
+  void *data;
+  uint32_t format, channel_offset, n_channels;
+} mi355_mixer_output;
+int mi355_mixer_setup(mi355_ctx *ctx, unsigned n_inputs, unsigned n_out_channels, const uint8_t *contrib);
+int mi355_mixer_setup_minus1(mi355_ctx *ctx, unsigned n_streams);
+int mi355_mixer_process(mi355_ctx *ctx, const mi355_mixer_segment *segments, unsigned n_segments, const mi355_mixer_output *outputs,
+                        unsigned n_outputs, size_t frames);
+int mi355_mixer_process_device(mi355_ctx *ctx, const mi355_mixer_segment *segments, unsigned n_segments, const mi355_mixer_output *outputs,
+                               unsigned n_outputs, size_t frames);
+int mi355_mixer_reset(mi355_ctx *ctx);
+int mi355_selftest_mixer_plan(int n_members, const uint32_t *n_inputs, const uint32_t *n_out_channels, const uint32_t *n_segments,
+                              const uint32_t *n_outputs, const uint64_t *frames, uint32_t *first_block, uint32_t *seg_offset,
+                              uint32_t *out_offset, uint32_t *bits_offset, uint32_t block_capacity, uint32_t *block_member,
+                              uint32_t *block_tile, uint32_t *block_group);
+/* mixers through an audio group (csrc/agroup.hip): a member is one mixer - one room of a bridge server - with its own matrix,
+ * segment and output formats and `frames` per submit (aggregate_one_buffer, audiomultimixerelement.rs:606-753, and split_output_buf,
+ * splitter.rs:433-467, for every member that has submitted in ONE kernel launch). Checks and statuses as mi355_mixer_process
+ * (device_data = 0) / mi355_mixer_process_device (1); a
+ * submit before the member's setup returns MI355_ERR_NOT_CONFIGURED. The segment and output arrays are copied at submit; the
+ * buffers they name are borrowed until wait(ticket), which answers `frames`. mixer_launches: kernel launches of the group's launch
+ * sets so far (one per set in which a member has a frame). */
+mi355_agroup *mi355_agroup_create_mixer(int device, int n_members, int *status);
+mi355_agroup *mi355_agroup_shared_mixer(int device, int n_members, int *member, int *status);
+int mi355_agroup_mixer_setup(mi355_agroup *group, int member, unsigned n_inputs, unsigned n_out_channels, const uint8_t *contrib);
+int mi355_agroup_mixer_setup_minus1(mi355_agroup *group, int member, unsigned n_streams);
+int mi355_agroup_submit_mixer(mi355_agroup *group, int member, const mi355_mixer_segment *segments, unsigned n_segments,
+                              const mi355_mixer_output *outputs, unsigned n_outputs, size_t frames, int device_data, uint64_t *ticket);
+uint64_t mi355_agroup_mixer_launches(mi355_agroup *group);
 
 #ifdef __cplusplus
 }

@@ -233,6 +233,7 @@ int mi355_ctx_set_flag(mi355_ctx *ctx, int flag, int value) {
   if (flag == MI355_FLAG_BRICK_TILES_PER_RUN && value >= 0 && value <= 4096) { ctx->brick_tiles_per_run = value; return MI355_OK; }
   if (flag == MI355_FLAG_BRICK_FOLD_AXIS && value >= 0 && value <= 2) { ctx->brick_fold_axis = value; return MI355_OK; }
   if (flag == MI355_FLAG_DSSIM_TRANSLUCENT && (value == 0 || value == 1)) { ctx->dssim_translucent = value; return MI355_OK; }
+  if (flag == MI355_FLAG_DSSIM_FAST && (value == 0 || value == 1)) { ctx->dssim_fast = value; return MI355_OK; }
   if (flag == MI355_FLAG_BRICK_PRIO && value >= 0 && value <= 3) { ctx->brick_prio = value; return MI355_OK; }
   if (flag == MI355_FLAG_BRICK_SETS && (value == 0 || value == 32 || value == 48 || value == 64 || value == 512)) { ctx->brick_sets = value; return MI355_OK; }
   if (flag == MI355_FLAG_HSV_TABLE && value >= 0 && value <= 3) { ctx->hsv_table_mode = value; return MI355_OK; }
@@ -937,6 +938,65 @@ int mi355_dssim_compare_frames(mi355_ctx *ctx, const mi355_dssim_image *original
     d_frames[f] = d;
   }
   return dssim_compare_frames(ctx, original, d_frames, n_frames, (int)row, width, height, channels, dssim);
+}
+
+static int dssim_pairs_args(mi355_ctx *ctx, const uint8_t *const *refs, const uint8_t *const *frames, int n_pairs, int stride, int width, int height, int format,
+                            const double *dssim, int *channels) {
+  int rc = dssim_channels(ctx, format, channels);
+  if (rc) return rc;
+  if (!refs || !frames || !dssim || n_pairs < 0 || width <= 0 || height <= 0 || (size_t)stride < (size_t)width * *channels)
+    return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: bad pairs");
+  if (n_pairs > 64) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: at most 64 pairs per call");
+  for (int f = 0; f < n_pairs; f++)
+    if (!refs[f] || !frames[f]) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: null frame");
+  return MI355_OK;
+}
+
+int mi355_dssim_compare_pairs_device(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint8_t *const *d_frames, int n_pairs, int stride, int width, int height,
+                                     int format, double *dssim) {
+  REQUIRE_CTX(ctx);
+  int channels = 0;
+  int rc = dssim_pairs_args(ctx, d_refs, d_frames, n_pairs, stride, width, height, format, dssim, &channels);
+  if (rc || n_pairs == 0) return rc;
+  BIND_DEVICE(ctx);
+  return dssim_compare_pairs(ctx, d_refs, d_frames, n_pairs, stride, width, height, channels, dssim, -1, nullptr);
+}
+
+int mi355_dssim_compare_pairs(mi355_ctx *ctx, const uint8_t *const *refs, const uint8_t *const *frames, int n_pairs, int stride, int width, int height, int format,
+                              double *dssim) {
+  REQUIRE_CTX(ctx);
+  int channels = 0;
+  int rc = dssim_pairs_args(ctx, refs, frames, n_pairs, stride, width, height, format, dssim, &channels);
+  if (rc || n_pairs == 0) return rc;
+  BIND_DEVICE(ctx);
+  const size_t row = (size_t)width * channels, frame_bytes = (row * (size_t)height + 255) & ~(size_t)255;
+  if ((rc = ensure_stage(ctx, 0, frame_bytes * 2 * (size_t)n_pairs))) return rc;
+  const uint8_t *d_ptrs[2][64];
+  for (int s = 0; s < 2; s++)
+    for (int f = 0; f < n_pairs; f++) {
+      uint8_t *d = (uint8_t *)ctx->d_stage[0] + frame_bytes * ((size_t)s * n_pairs + f);
+      if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, row, (s ? frames : refs)[f], (size_t)stride, row, (size_t)height, hipMemcpyHostToDevice, ctx->stream), "dssim H2D"))) return rc;
+      d_ptrs[s][f] = d;
+    }
+  return dssim_compare_pairs(ctx, d_ptrs[0], d_ptrs[1], n_pairs, (int)row, width, height, channels, dssim, -1, nullptr);
+}
+
+int mi355_dssim_pair_map_device(mi355_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_frame, int stride, int width, int height, int format, int scale, float *out,
+                                int *map_width, int *map_height) {
+  REQUIRE_CTX(ctx);
+  int channels = 0;
+  int rc = dssim_channels(ctx, format, &channels);
+  if (rc) return rc;
+  if (!d_ref || !d_frame || width <= 0 || height <= 0 || (size_t)stride < (size_t)width * channels) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: bad pair");
+  int w = width, h = height, k = 0;
+  for (; k < scale && k < 4 && w >= 8 && h >= 8; k++) { w /= 2; h /= 2; }   // the box chain stops below 8 pixels
+  if (scale < 0 || k != scale) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: the pair has no such scale");
+  if (map_width) *map_width = w;
+  if (map_height) *map_height = h;
+  if (!out) return MI355_OK;
+  BIND_DEVICE(ctx);
+  double value = 0.0;
+  return dssim_compare_pairs(ctx, &d_ref, &d_frame, 1, stride, width, height, channels, &value, scale, out);
 }
 
 int mi355_selftest_dssim_cbrt(mi355_ctx *ctx, uint32_t lo_bits, uint32_t hi_bits, uint64_t *mismatches) {

@@ -1126,8 +1126,11 @@ int dssim_compare(mi355_ctx *ctx, const mi355_dssim_image *a, const mi355_dssim_
 // `h_slots` (optional, pinned, n_frames x 3 x kDssimScales doubles): the per-scale [sum, avg, dev] slots are copied there and the
 // call returns WITHOUT waiting (the caller owns an event behind it and finishes with dssim_scores_from_slots); otherwise the call
 // waits and writes the values to `out`.
+// MI355_FLAG_DSSIM_FAST = 1 on `ctx` and `d_refs` given: the pairs go through the fast form's pair kernel (dssim_fast.hip) instead -
+// both frames' box chains side by side, no image; maps, partials, reductions and slots as below. `map_scale` >= 0 (waited calls):
+// the SSIM map of that scale of frame 0 is copied to `map_out` (host) behind the values.
 static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a, const uint8_t *const *d_refs, const uint8_t *const *d_frames, int n_frames,
-                                     int stride, int width, int height, int channels, double *out, double *h_slots) {
+                                     int stride, int width, int height, int channels, double *out, double *h_slots, int map_scale = -1, float *map_out = nullptr) {
   mi355_dssim_image geometry;   // scale sizes only (pairs: there is no image yet)
   if (!a) {
     int ns0 = 0;
@@ -1163,7 +1166,9 @@ static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a,
   R.first_b[ns] = n_pb;
   for (int k = ns; k < kDssimScales; k++) { R.n[k] = 0; R.n_a[k] = 0; R.first_b[k + 1] = n_pb; R.len[k] = 1.0; R.exponent[k] = 1.0; R.map[k] = nullptr; R.part_a[k] = nullptr; R.part_b[k] = nullptr; }
   void *scr = nullptr;
-  const size_t lin_bytes = (lin_px + 16) * 16;
+  const bool fast = d_refs && ctx->dssim_fast;
+  static_assert(kDssimFastTw == kTw && kDssimFastTh == kTh, "the pair kernel's tiles are the partials' tiles");
+  const size_t lin_one = (lin_px + 16) * 16, lin_bytes = fast ? 2 * lin_one : lin_one;   // fast: the reference's chain behind the frame's
   // per frame: SSIM maps and both families of partials (the reductions of all frames run after the last frame's kernels)
   const size_t F = (size_t)n_frames;
   int rc = dssim_scratch(ctx, 1, lin_bytes + F * (map_px * 4 + (n_pa + n_pb) * 8 + 3 * kDssimScales * 8) + 1024, &scr);
@@ -1192,6 +1197,44 @@ static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a,
   float *d_lut = cache->d_lut;
   for (int f = 0; f < n_frames; f++) {
     const uint8_t *d_frame = d_frames[f];
+    if (fast) {
+      const float4 *lin_ref[kDssimScales] = {nullptr};
+      for (int k = 1; k < ns; k++) lin_ref[k] = (const float4 *)((const char *)lin[k] + lin_one);
+      for (int s = 0; s < 2; s++) {
+        const uint8_t *src = s ? d_frame : d_refs[f];
+        for (int k = 1; k < ns; k++) {
+          const unsigned g = dssim_grid(ctx, R.n[k]);
+          float4 *dst = (float4 *)(s ? lin[k] : lin_ref[k]);
+          const float4 *prev = s ? lin[k - 1] : lin_ref[k - 1];
+          if (k == 1) hipLaunchKernelGGL(dssim_downsample_u8_kernel, dim3(g), dim3(256), 0, ctx->stream, src, stride, width, height, channels, (const float *)d_lut, dst);
+          else hipLaunchKernelGGL(dssim_downsample_kernel, dim3(g), dim3(256), 0, ctx->stream, prev, a->s[k - 1].w, a->s[k - 1].h, dst);
+        }
+      }
+      for (int k = 0; k < ns; ) {
+        DssimFastJobs J;
+        const int count = k < 2 ? 1 : (ns - k < 3 ? ns - k : 3);
+        unsigned total = 0;
+        for (int j = 0; j < 3; j++) {
+          J.first[j] = total;
+          if (j >= count) { J.job[j] = J.job[0]; continue; }
+          DssimFastJob &q = J.job[j];
+          const int kk = k + j;
+          q.u8[0] = kk == 0 ? d_refs[f] : nullptr; q.u8[1] = kk == 0 ? d_frame : nullptr;
+          q.lin[0] = kk == 0 ? nullptr : lin_ref[kk]; q.lin[1] = kk == 0 ? nullptr : lin[kk];
+          q.stride = stride; q.channels = channels;
+          q.pattern = (channels == 4 && !ctx->dssim_translucent) ? 1 : 0;
+          q.w = a->s[kk].w; q.h = a->s[kk].h;
+          q.map = (float *)R.map[kk] + (size_t)f * map_px;
+          q.partial = (double *)R.part_a[kk] + (size_t)f * n_pa;
+          total += tiles[kk];
+        }
+        J.first[3] = total;
+        J.lut = d_lut;
+        if ((rc = dssim_fast_enqueue(ctx, J))) return rc;
+        k += count;
+      }
+      continue;
+    }
     mi355_dssim_image *own = nullptr;   // pairs: this frame's reference image (its scratch use - the linear images at the start of
                                         // slot 1 - is what the loop below reuses right behind it, in stream order; never larger)
     if (d_refs) {
@@ -1241,6 +1284,10 @@ static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a,
   if ((rc = check_hip(ctx, hipMemcpyAsync(slots.data(), d_slots, slots.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "dssim: scores D2H"))) return rc;
   if ((rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "dssim: sync"))) return rc;
   for (int f = 0; f < n_frames; f++) out[f] = dssim_value_of(a, slots.data() + (size_t)f * 3 * kDssimScales);
+  if (map_scale >= 0 && map_out && n_frames > 0) {
+    if ((rc = check_hip(ctx, hipMemcpyAsync(map_out, R.map[map_scale], R.n[map_scale] * sizeof(float), hipMemcpyDeviceToHost, ctx->stream), "dssim: map D2H"))) return rc;
+    if ((rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "dssim: sync"))) return rc;
+  }
   return MI355_OK;
 }
 
@@ -1253,6 +1300,11 @@ int dssim_compare_frames(mi355_ctx *ctx, const mi355_dssim_image *a, const uint8
 int dssim_compare_pairs_enqueue(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint8_t *const *d_frames, int n_pairs, int stride, int width, int height,
                                 int channels, double *h_slots) {
   return dssim_compare_frames_impl(ctx, nullptr, d_refs, d_frames, n_pairs, stride, width, height, channels, nullptr, h_slots);
+}
+
+int dssim_compare_pairs(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint8_t *const *d_frames, int n_pairs, int stride, int width, int height,
+                        int channels, double *out, int map_scale, float *map_out) {
+  return dssim_compare_frames_impl(ctx, nullptr, d_refs, d_frames, n_pairs, stride, width, height, channels, out, nullptr, map_scale, map_out);
 }
 
 // ... and the values once the copy has landed

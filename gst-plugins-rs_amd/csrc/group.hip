@@ -67,7 +67,7 @@ struct Batch {
 struct CmpDesc {
   mi355_ctx *ctx;
   const uint8_t *ref, *frame;
-  int width, height, stride, format, algo, translucent;
+  int width, height, stride, format, algo, translucent, fast;   // fast: MI355_FLAG_DSSIM_FAST of the submitting context
   uint64_t ticket;
   hipEvent_t ready;  // recorded on ctx->stream at submit (nullptr: the stream held nothing)
 };
@@ -352,7 +352,7 @@ void *cmp_take_block(mi355_group *g) {
 }
 
 bool cmp_same_class(const CmpDesc &a, const CmpDesc &b) {
-  return a.algo == b.algo && a.width == b.width && a.height == b.height && a.stride == b.stride && a.format == b.format && a.translucent == b.translucent;
+  return a.algo == b.algo && a.width == b.width && a.height == b.height && a.stride == b.stride && a.format == b.format && a.translucent == b.translucent && a.fast == b.fast;
 }
 
 // a finished batch: values from its pinned block into cmp_results (once). g->mu held.
@@ -424,6 +424,7 @@ int cmp_flush_locked(mi355_group *g, uint64_t until = 0) {
       for (int i = 0; i < n; i++) { refs[i] = take[i].ref; frames[i] = take[i].frame; }
       if (!rc && first.algo == MI355_HASH_DSSIM) {
         a->dssim_translucent = first.translucent;
+        a->dssim_fast = first.fast;   // a batch holds pairs of one form only (cmp_same_class)
         rc = dssim_compare_pairs_enqueue(a, refs.data(), frames.data(), n, first.stride, first.width, first.height, fmt.pixel_stride, (double *)block);
       } else if (!rc) {
         std::vector<const uint8_t *> both(refs);
@@ -1007,6 +1008,7 @@ int mi355_group_submit_compare(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_
   CmpDesc d{};
   d.ctx = ctx; d.ref = d_ref; d.frame = d_frame; d.width = width; d.height = height; d.stride = stride; d.format = format; d.algo = algo;
   d.translucent = ctx->dssim_translucent;
+  d.fast = ctx->dssim_fast;
   d.ready = nullptr;
   if (hipStreamQuery(ctx->stream) != hipSuccess) {   // the pair starts after what the stream's own context holds now (an upload)
     (void)hipGetLastError();

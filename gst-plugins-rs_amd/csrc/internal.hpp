@@ -114,6 +114,7 @@ struct mi355_ctx {
   int brick_fold_axis = 2;      // MI355_FLAG_BRICK_FOLD_AXIS (accepted, ignored)
   hipEvent_t host_copy_ev = nullptr;  // marks "the caller's host buffer has been read" for entry points that return before their kernels end
   int dssim_translucent = 0;    // MI355_FLAG_DSSIM_TRANSLUCENT: 1 = alpha < 255 composed over black instead of over the crate's pattern
+  int dssim_fast = 0;           // MI355_FLAG_DSSIM_FAST: 1 = pairs go through the separable pair kernel (dssim_fast.hip), read when a pair is handed over
   int brick_prio = 3;           // MI355_FLAG_BRICK_PRIO: bit 0 progress-based wave priorities, bit 1 tile stealing within a block
   int brick_sets = 0;           // MI355_FLAG_BRICK_SETS: 0 = content watch decides (default); 32 (4x4x2 sets, 16 waves per CU) or 64 (4x4x4 sets, 8 waves per CU) pinned
   int hrtf_method = 0;         // MI355_FLAG_HRTF_METHOD: 0 = by HRIR length, 1 = overlap-save FFT, 2 = time-domain FIR (takes effect at mi355_hrtf_setup)
@@ -221,6 +222,17 @@ int dssim_compare_frames(mi355_ctx *ctx, const mi355_dssim_image *a, const uint8
 int dssim_compare_pairs_enqueue(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint8_t *const *d_frames, int n_pairs, int stride, int width, int height,
                                 int channels, double *h_slots);
 void dssim_scores_from_slots(int width, int height, const double *h_slots, int n_pairs, double *out);
+// pairs through the entry points of the C ABI: waited for; the form is ctx->dssim_fast's. map_scale >= 0: the SSIM map of that scale
+// of pair 0 is copied to map_out (host) as well
+int dssim_compare_pairs(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint8_t *const *d_frames, int n_pairs, int stride, int width, int height,
+                        int channels, double *out, int map_scale, float *map_out);
+// the fast form's pair kernel (dssim_fast.hip): blocks [first[j], first[j+1]) take the 32 x 16 tiles of job j - one scale of one
+// (reference, frame) pair, read from the packed bytes (scale 0) or from the two linear float4 chains - and write the scale's SSIM
+// map and one f64 partial per tile
+struct DssimFastJob { const uint8_t *u8[2]; const float4 *lin[2]; int stride, channels, pattern, w, h; float *map; double *partial; };
+struct DssimFastJobs { DssimFastJob job[3]; unsigned first[4]; const float *lut; };
+constexpr int kDssimFastTw = 32, kDssimFastTh = 16;
+int dssim_fast_enqueue(mi355_ctx *ctx, const DssimFastJobs &J);
 constexpr int kDssimSlotDoubles = 15;  // per comparison: 5 scales x [sum, avg, dev]
 int blockhash_enqueue(mi355_ctx *ctx, const uint8_t *const *d_frames, int n, int stride, int width, int height, int channels, uint32_t *d_sums,
                       unsigned long long *d_hashes);

@@ -39,6 +39,7 @@ FLAG_HSV_NT = 14
 FLAG_BLOCKHASH_ANY_SIZE = 15
 FLAG_WINDOW_ORDER = 17
 FLAG_WINDOW_STATS = 18
+FLAG_DSSIM_FAST = 19
 HSVDETECT_SET_MAX = 32   # MI355_HSVDETECT_SET_MAX: detector frames per launch set of a Group
 MIXER_FRAME_TILE = 64    # MI355_MIXER_FRAME_TILE: frames per block of the mixer kernel
 
@@ -294,6 +295,9 @@ def load_library():
         "mi355_group_release": (None, [vp]),
         "mi355_group_submit_round": (i, [vp, C.POINTER(vp), i, C.POINTER(vp), C.POINTER(vp), i, i, i, i, C.POINTER(HsvSettings)]),
         "mi355_group_submit_round_fused": (i, [vp, C.POINTER(vp), i, C.POINTER(vp), C.POINTER(vp), i, i, i, i, C.POINTER(HsvSettings)]),
+        "mi355_dssim_compare_pairs": (i, [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, i, i, C.POINTER(C.c_double)]),
+        "mi355_dssim_compare_pairs_device": (i, [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, i, i, C.POINTER(C.c_double)]),
+        "mi355_dssim_pair_map_device": (i, [vp, vp, vp, i, i, i, i, i, f32p, C.POINTER(i), C.POINTER(i)]),
         "mi355_selftest_dssim_cbrt": (i, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
         "mi355_dssim_image_plane": (i, [vp, vp, i, i, i, f32p, C.POINTER(i), C.POINTER(i)]),
         "mi355_sofa_setup": (i, [vp, i, i, i, i]),
@@ -1255,6 +1259,39 @@ class Context:
         out = (C.c_double * max(n, 1))()
         self._ck(self.L.mi355_dssim_compare_frames_device(self.h, original, ptrs, n, stride, width, height, FMT[fmt], out))
         return [out[k] for k in range(n)]
+
+    def dssim_compare_pairs(self, refs, frames, stride, width, height, fmt="RGBA"):
+        """n independent (reference, frame) pairs of host frames -> their dssim values; exact or fast by FLAG_DSSIM_FAST."""
+        n = len(frames)
+        if len(refs) != n:
+            raise ValueError("dssim_compare_pairs: as many references as frames")
+        pr = (C.c_void_p * max(n, 1))(*[f.ctypes.data for f in refs])
+        pf = (C.c_void_p * max(n, 1))(*[f.ctypes.data for f in frames])
+        out = (C.c_double * max(n, 1))()
+        self._ck(self.L.mi355_dssim_compare_pairs(self.h, pr, pf, n, stride, width, height, FMT[fmt], out))
+        return [out[k] for k in range(n)]
+
+    def dssim_compare_pairs_device(self, d_refs, d_frames, stride, width, height, fmt="RGBA"):
+        n = len(d_frames)
+        if len(d_refs) != n:
+            raise ValueError("dssim_compare_pairs_device: as many references as frames")
+        pr = (C.c_void_p * max(n, 1))(*[int(d) for d in d_refs])
+        pf = (C.c_void_p * max(n, 1))(*[int(d) for d in d_frames])
+        out = (C.c_double * max(n, 1))()
+        self._ck(self.L.mi355_dssim_compare_pairs_device(self.h, pr, pf, n, stride, width, height, FMT[fmt], out))
+        return [out[k] for k in range(n)]
+
+    def dssim_pair_map_device(self, d_ref, d_frame, stride, width, height, fmt="RGBA", scale=0, out=None):
+        """(h, w) float32 SSIM map of one scale of one pair of device frames, in the form FLAG_DSSIM_FAST selects. `out`: a
+        C-contiguous float32 array with at least h * w elements to receive it (the first h * w are written)."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._ck(self.L.mi355_dssim_pair_map_device(self.h, int(d_ref), int(d_frame), stride, width, height, FMT[fmt], scale, None, C.byref(w), C.byref(h)))
+        if out is None:
+            out = np.zeros((h.value, w.value), np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size < h.value * w.value:
+            raise ValueError("dssim_pair_map_device: out must be C-contiguous float32 of at least %d elements" % (h.value * w.value))
+        self._ck(self.L.mi355_dssim_pair_map_device(self.h, int(d_ref), int(d_frame), stride, width, height, FMT[fmt], scale, out.ctypes.data_as(C.POINTER(C.c_float)), None, None))
+        return out
 
     def selftest_dssim_cbrt(self, lo, hi):
         """Mismatches between the kernels' cube root and the literal one over every f32 in [lo, hi] (both > 0)."""

@@ -103,6 +103,7 @@ typedef enum mi355_flag {
   MI355_FLAG_FUSED_VARIANT = 3, /* fused hsv+colorlut tiling: 0 = hsv inline after the load (default); 1 = software-pipelined kernel */
   MI355_FLAG_BRICK_TILES_PER_RUN = 7, /* brick-cache kernel: tiles (128 pixels x 4 or 8 rows) in a run, the part of a strip one wave owns (0 = default: one run per wave of the chip) */
   MI355_FLAG_DSSIM_TRANSLUCENT = 11, /* Dssim on RGBA pixels with alpha < 255: 0 (default) = composed over the crate's coloured, position-dependent pattern (mi355_dssim_create_image), 1 = over black (premultiplied values as they are) */
+  MI355_FLAG_DSSIM_FAST = 19, /* Dssim on (reference, frame) PAIRS (mi355_dssim_compare_pairs*, mi355_dssim_pair_map_device, mi355_group_submit_compare), read when a pair is handed over: 0 (default) = the exact form, bit-identical to the restated algorithm; 1 = the fast form - the same algorithm with every 3x3 blur pass as a horizontal and a vertical 3-tap pass (taps [0.30876, 0.38248, 0.30876] * sqrt(1.000001)), one kernel per scale and pair, no image planes in memory; its value differs from the exact form's by f32 rounding noise (1e-5), identical frames still give exactly 0.0. Other values are refused. Image handles (mi355_dssim_create_image / _compare / _compare_frames*) are the exact form's objects and stay exact whatever this flag says */
   MI355_FLAG_BRICK_FOLD_AXIS = 10, /* accepted and ignored: the 32-set geometry of the brick-cache kernel is hashed over all three axes now (it used to give one axis 2 set residues instead of 4) */
   MI355_FLAG_BRICK_PRIO = 9, /* brick-cache kernel, how the waves of a block share work: bit 0 = waves lower their issue priority as they advance through their run, bit 1 = a wave that is done takes tiles from the run with most left (default 3) */
   MI355_FLAG_HRTF_METHOD = 12, /* hrtfrender convolution, read at mi355_hrtf_setup: 0 (default) = overlap-save FFT in LDS from 384-tap HRIRs on (the measured crossover), time-domain FIR below; 1 = FFT, 2 = FIR pinned (each only where it fits the LDS) */
@@ -635,6 +636,20 @@ int mi355_dssim_compare_frames(mi355_ctx *ctx, const mi355_dssim_image *original
 int mi355_dssim_compare_frames_device(mi355_ctx *ctx, const mi355_dssim_image *original,
                                       const uint8_t *const *d_frames, int n_frames, int stride, int width,
                                       int height, int format, double *dssim);
+/* HashedImage::new + HashedImage::compare for n independent two-pad comparisons (hashed_image.rs:48-79: Dssim::create_image_rgb /
+ * create_image_rgba on both frames, Dssim::compare): dssim[i] = the value of (refs[i], frames[i]), `n_pairs` <= 64 pairs of one
+ * geometry, format MI355_FMT_RGB or MI355_FMT_RGBA, one synchronisation per call. `refs` / `frames` are host arrays of host
+ * pointers (of device pointers for the _device variant). MI355_FLAG_DSSIM_FAST = 0: every pair is mi355_dssim_create_image(refs[i])
+ * + mi355_dssim_compare_frames(frames[i]), bit for bit; 1: the fast form (see the flag). Nothing of a pair is kept. */
+int mi355_dssim_compare_pairs(mi355_ctx *ctx, const uint8_t *const *refs, const uint8_t *const *frames, int n_pairs,
+                              int stride, int width, int height, int format, double *dssim);
+int mi355_dssim_compare_pairs_device(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint8_t *const *d_frames,
+                                     int n_pairs, int stride, int width, int height, int format, double *dssim);
+/* Diagnostics (hashed_image.rs:48-79, the per-pixel SSIM map inside Dssim::compare): the f32 SSIM map of scale `scale` of ONE
+ * pair of device-resident frames, in the form MI355_FLAG_DSSIM_FAST selects, copied to `out` (host; may be NULL to query the
+ * scale's size only, as for mi355_dssim_image_plane). */
+int mi355_dssim_pair_map_device(mi355_ctx *ctx, const uint8_t *d_ref, const uint8_t *d_frame, int stride, int width,
+                                int height, int format, int scale, float *out, int *map_width, int *map_height);
 /* Device self test of the LAB conversion's cube root: for every f32 whose bit pattern lies in [lo_bits, hi_bits], the
  * Halley iteration with the range-restricted division the kernels use against the same iteration with the compiler's IEEE
  * division; *mismatches = how many differ in any bit (0 over (216/24389, 2], the whole domain of the conversion). */

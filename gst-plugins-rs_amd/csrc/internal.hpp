@@ -101,6 +101,7 @@ struct mi355_ctx {
   void *colordetect = nullptr; // mi355::ColorDetectState (colordetect.hip): histograms and palette results
   void *agingradio = nullptr;  // mi355::AgingState (agingradio.hip): lowpass filter states, pair counter, seed
   void *mixer = nullptr;       // mi355::MixerState (mixer.hip): the contribution matrix, job tables and the host form's staging
+  void *yolodec = nullptr;     // mi355::YoloDecState (yolodec.hip): survivor keys, kept boxes, results
   // host <-> device copies this context has enqueued through the library's own entry points and mi355_buf objects (tests assert
   // that a chain of elements on device buffers costs ONE upload and ONE download: mi355_ctx_transfer_counts)
   unsigned long long n_h2d = 0, n_d2h = 0;
@@ -315,6 +316,7 @@ int mixer_plan(int n_members, const uint32_t *n_inputs, const uint32_t *n_out_ch
                const uint64_t *frames, uint32_t *first_block, uint32_t *seg_off, uint32_t *out_off, uint32_t *bits_off);
 int mixer_launch(MixerTablesBuf *B, hipStream_t stream, const MixerCall *calls, int n, int *kernel_launches, std::string *err);
 void mixer_release(mi355_ctx *ctx);
+void yolodec_release(mi355_ctx *ctx);
 int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, int channel, int kind, float *out, int *w, int *h);
 int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate);
 int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps);

@@ -93,6 +93,27 @@ def mixer_tables(segments, outputs):
     return segs, outs
 
 
+class YoloParams(C.Structure):
+    """mi355_yolo_params: the three thresholds of one yolov8tensordec2 / yoloxtensordec instance."""
+    _fields_ = [("box_confidence_threshold", C.c_float), ("class_confidence_threshold", C.c_float), ("iou_threshold", C.c_float)]
+
+
+YOLO_LAYOUT = {"V8": 0, "X": 1}   # mi355_yolo_layout
+# mi355_yolo_det as a numpy record
+YOLO_DET = np.dtype([("xmin", "<f4"), ("ymin", "<f4"), ("xmax", "<f4"), ("ymax", "<f4"), ("x", "<i4"), ("y", "<i4"), ("width", "<i4"),
+                     ("height", "<i4"), ("class_id", "<u4"), ("confidence", "<f4"), ("candidate", "<u4"), ("reserved", "<u4")])
+
+
+def _yolo_params(params):
+    """One (box_thr, class_thr, iou_thr) triple, a YoloParams, or a sequence of either -> a ctypes array."""
+    if isinstance(params, YoloParams) or (len(params) == 3 and not hasattr(params[0], "__len__") and not isinstance(params[0], YoloParams)):
+        params = [params]
+    arr = (YoloParams * max(len(params), 1))()
+    for k, q in enumerate(params):
+        arr[k] = q if isinstance(q, YoloParams) else YoloParams(*[float(v) for v in q])
+    return arr, len(params)
+
+
 class HsvDetectSettings(C.Structure):
     _fields_ = [("hue_ref", C.c_float), ("hue_var", C.c_float), ("saturation_ref", C.c_float),
                 ("saturation_var", C.c_float), ("value_ref", C.c_float), ("value_var", C.c_float)]
@@ -280,6 +301,9 @@ def load_library():
         "mi355_mixer_process": (i, [vp, C.POINTER(MixerSegment), C.c_uint, C.POINTER(MixerOutput), C.c_uint, sz]),
         "mi355_mixer_process_device": (i, [vp, C.POINTER(MixerSegment), C.c_uint, C.POINTER(MixerOutput), C.c_uint, sz]),
         "mi355_mixer_reset": (i, [vp]),
+        "mi355_yolodec_tensor": (i, [vp, vp, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "mi355_yolodec_tensors_device": (i, [vp, vp, sz, i, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "mi355_selftest_yolodec_check": (i, [sz, i, i, C.c_uint32, C.c_uint32]),
         "mi355_selftest_mixer_plan": (i, [i] + [C.POINTER(C.c_uint32)] * 4 + [C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint32)] * 4 + [C.c_uint32]
                                       + [C.POINTER(C.c_uint32)] * 3),
         "mi355_agroup_create_mixer": (vp, [i, i, C.POINTER(C.c_int)]),
@@ -1437,6 +1461,38 @@ class Context:
         """The same on device memory (pointer forms of mixer_tables), enqueued on the context's stream."""
         segs, outs = mixer_tables(segments, outputs)
         self._ck(self.L.mi355_mixer_process_device(self.h, segs, len(segments), outs, len(outputs), frames))
+
+    # ---- yolov8tensordec2 / yoloxtensordec (analytics/analytics/src/yolotensordec/imp.rs:234-422)
+    def yolodec(self, tensor, layout, params, max_dets=None, return_count=False):
+        """The kept boxes of one host tensor as a YOLO_DET record array, in output order. tensor: float32, (F, N) for layout "V8",
+        (N, F) for "X" (a leading batch axis of 1 is accepted); params: (box_thr, class_thr, iou_thr). max_dets: the capacity of
+        the result (default N: never truncated); with return_count the full kept count comes back as well."""
+        a = np.ascontiguousarray(tensor, dtype=np.float32)
+        if a.ndim == 3 and a.shape[0] == 1:
+            a = a[0]
+        if a.ndim != 2:
+            raise ValueError("yolodec: a [F, N] (V8) or [N, F] (X) tensor")
+        F, N = (a.shape if layout == "V8" else a.shape[::-1])
+        cap = N if max_dets is None else max_dets
+        p, _ = _yolo_params(params)
+        dets = np.zeros(max(cap, 1), YOLO_DET)
+        n = C.c_uint32(0)
+        self._ck(self.L.mi355_yolodec_tensor(self.h, a.ctypes.data if a.size else None, YOLO_LAYOUT[layout], F, N, p, dets.ctypes.data, cap, C.byref(n)))
+        out = dets[:min(n.value, cap)].copy()
+        return (out, n.value) if return_count else out
+
+    def yolodec_device(self, d_tensors, tensor_pitch_bytes, n_tensors, layout, num_fields, num_candidates, params, max_dets=None, return_counts=False):
+        """One record array per device tensor d_tensors + i * tensor_pitch_bytes; params: one triple per tensor. One synchronisation."""
+        cap = num_candidates if max_dets is None else max_dets
+        p, n_p = _yolo_params(params)
+        if n_p != n_tensors:
+            raise ValueError("yolodec_device: one settings triple per tensor")
+        dets = np.zeros(max(n_tensors * cap, 1), YOLO_DET)
+        n = (C.c_uint32 * max(n_tensors, 1))()
+        self._ck(self.L.mi355_yolodec_tensors_device(self.h, d_tensors, tensor_pitch_bytes, n_tensors, YOLO_LAYOUT[layout], num_fields, num_candidates, p,
+                                                     dets.ctypes.data, cap, n))
+        out = [dets[t * cap:t * cap + min(n[t], cap)].copy() for t in range(n_tensors)]
+        return (out, [n[t] for t in range(n_tensors)]) if return_counts else out
 
     # ---- rsaudioecho
     def echo_setup(self, ring_len):

@@ -898,6 +898,49 @@ int mi355_colordetect_frames_device(mi355_ctx *ctx, const uint8_t *d_frames, siz
 int mi355_colordetect_histogram_device(mi355_ctx *ctx, const uint8_t *d_data, size_t data_len, int format, int quality,
                                        uint32_t hist[32768], int box[6]);
 
+/* ---------------------------------------------------------------- yolov8tensordec2 / yoloxtensordec (csrc/yolodec.hip)
+ * Replaces the decode loops of YoloTensorDec::transform_ip (analytics/analytics/src/yolotensordec/imp.rs:234-422, iou :480-489):
+ * per tensor the class argmax of every candidate under f32::total_cmp (the last of equal maxima), the thresholds, the sort by
+ * class and descending confidence, the greedy per-class NMS and the casts handed to add_od_mtd. Bit-exact against the contract of
+ * DESIGN 4.11. One stated deviation: the reference's sort_unstable_by leaves the order of entries of equal class and bit-equal
+ * confidence open; here it is ascending candidate index. `max-detections` is never read by transform_ip and has no effect here
+ * either; max_dets below is the caller's output capacity, not that property. Sign and payload of a NaN that arithmetic produces
+ * (inf * 0, inf - inf) are the hardware's and outside the contract.
+ *   layout        MI355_YOLO_V8: [1, F, N], field f of candidate c at data[c + f * N], classes are fields 4..F-1 (:297-327);
+ *                 MI355_YOLO_X: [1, N, F], candidate c is the row data[c * F ..], b[4] is the box confidence, classes b[5..] (:328-356).
+ *   record        the f32 box before the casts, the four ints add_od_mtd receives (:390-393), class index, confidence
+ *                 (X: b[4] * class confidence) and the candidate's index in the tensor.
+ *   _tensor          a host tensor; synchronous.
+ *   _tensors_device  n_tensors device tensors of one shape at d_tensors + i * tensor_pitch_bytes, each with its OWN settings p[i]
+ *                    (independent instances); dets holds n_tensors x max_dets records, n_dets n_tensors counts. Two launches,
+ *                    one synchronisation and one download per call, whatever n_tensors is.
+ *   n_dets[i] is the number of kept boxes even above max_dets; the first max_dets in output order are then written and the
+ *   status stays MI355_OK. Limits: num_fields 6..1029 (below 6: MI355_ERR_INVALID_ARG, as find_yolo_tensor_meta refuses it,
+ *   :459), num_candidates 0..65536 (0: no detections, no launch), n_tensors 1..1024, pitch >= F * N * 4 and a multiple of 4,
+ *   device pointers 4-byte aligned; above the limits: MI355_ERR_UNSUPPORTED. Scratch belongs to the context and grows to the
+ *   largest shape seen.
+ *   mi355_selftest_yolodec_check : host only, no device: the status the shape checks of the two entry points give. */
+typedef enum mi355_yolo_layout { MI355_YOLO_V8 = 0, MI355_YOLO_X = 1 } mi355_yolo_layout;
+typedef struct mi355_yolo_params {
+  float box_confidence_threshold;    /* "box-confidence-threshold" (X only, imp.rs:332) */
+  float class_confidence_threshold;  /* "class-confidence-threshold" (imp.rs:314, :342) */
+  float iou_threshold;               /* "iou-threshold" (imp.rs:376) */
+} mi355_yolo_params;
+typedef struct mi355_yolo_det {
+  float xmin, ymin, xmax, ymax;      /* the f32 box, before the casts */
+  int32_t x, y, width, height;       /* what add_od_mtd receives */
+  uint32_t class_id;
+  float confidence;
+  uint32_t candidate;                /* index in the tensor */
+  uint32_t reserved;                 /* 0 */
+} mi355_yolo_det;
+int mi355_yolodec_tensor(mi355_ctx *ctx, const float *data, int layout, uint32_t num_fields, uint32_t num_candidates,
+                         const mi355_yolo_params *p, mi355_yolo_det *dets, uint32_t max_dets, uint32_t *n_dets);
+int mi355_yolodec_tensors_device(mi355_ctx *ctx, const float *d_tensors, size_t tensor_pitch_bytes, int n_tensors, int layout,
+                                 uint32_t num_fields, uint32_t num_candidates, const mi355_yolo_params *p, mi355_yolo_det *dets,
+                                 uint32_t max_dets, uint32_t *n_dets);
+int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates);
+
 /* ---------------------------------------------------------------- agingradio
  * Replaces AgingRadio::process::<f32|f64> (audio/audiofx/src/agingradio/imp.rs:94-136): per pair of frames
  * (data.chunks_exact_mut(channels * 2), :101; an odd last frame is left untouched) either a click - every sample 1.0, filters

@@ -19,10 +19,12 @@
 //   * results are the two element launches', bit for bit (same arithmetic, same table);
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
-// Three more queues live beside the filter batches, each with its own HIP stream, pending list, rendezvous and stats, and none
-// touching another: videocompare pairs (submit_compare), colordetect frames (submit_colordetect) and hsvdetector frames
+// Four more queues live beside the filter batches, each with its own HIP stream, pending list, rendezvous and stats, and none
+// touching another: videocompare pairs (submit_compare), colordetect frames (submit_colordetect), hsvdetector frames
 // (submit_hsvdetect: up to 32 frames of independent instances - own size, strides, formats, settings - as at most two launches
-// over a job table, hsv_kernels.hip). Tickets are one sequence; a wait entry refuses a ticket of another queue.
+// over a job table, hsv_kernels.hip) and decoder tensors (submit_yolodec: up to 32 tensors of independent yolov8tensordec2 /
+// yoloxtensordec instances - own shape, layout, settings - as at most three launches over job tables and one download,
+// yolodec.hip). Tickets are one sequence; a wait entry refuses a ticket of another queue.
 // No persistent kernel: nothing here can hang the GPU waiting for the host, a launch is a launch.
 #include "internal.hpp"
 
@@ -119,6 +121,25 @@ struct HdSet {
   bool collected = false;
 };
 
+// ---- yolov8tensordec2 / yoloxtensordec across independent element instances (mi355_group_submit_yolodec): one device tensor per
+// submit; its kept count and records come back through the set's pinned block
+struct YdDesc {
+  YdTensor t;
+  uint64_t ticket;
+  hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing, or no candidate to read)
+};
+struct YdOut { int status; uint32_t n_dets, max_dets; std::vector<mi355_yolo_det> dets; };   // dets: the first min(n_dets, max_dets)
+struct YdBlock { void *h; size_t bytes; };   // a pinned result block
+struct YdSlot { uint64_t ticket; uint32_t num_candidates, max_dets; uint64_t det_offset; };
+struct YdSet {
+  uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
+  std::vector<YdSlot> slots;   // its tensors, by job
+  hipEvent_t done;
+  int waiters;
+  YdBlock block;     // the set's own results until it is collected (h == nullptr: no tensor had a candidate)
+  bool collected = false;
+};
+
 }  // namespace
 
 struct mi355_group {
@@ -181,6 +202,19 @@ struct mi355_group {
   int hd_expected = 0;                       // rendezvous over pending detector frames (mi355_group_set_hsvdetect_rendezvous)
   unsigned hd_linger_us = 0;
   std::condition_variable hd_cv;             // "a detector set has been launched"
+  // ---- decoder queue: its own stream and scratch (created at the first submit), independent of the four queues above
+  hipStream_t yd_stream = nullptr;
+  YdSetScratch *yd_scratch = nullptr;
+  std::vector<YdDesc> yd_pending;
+  std::deque<YdSet> yd_sets;                 // launched, oldest first
+  std::unordered_map<uint64_t, uint64_t> yd_where;   // ticket -> seq
+  std::unordered_map<uint64_t, YdOut> yd_results;    // finished (or failed), not yet collected by mi355_group_wait_yolodec
+  std::vector<YdBlock> yd_blocks;            // free pinned result blocks
+  uint64_t next_yd_seq = 1;
+  uint64_t n_yd_tensors = 0, n_yd_sets = 0, n_yd_largest = 0, n_yd_launches = 0;
+  int yd_expected = 0;                       // rendezvous over pending tensors (mi355_group_set_yolodec_rendezvous)
+  unsigned yd_linger_us = 0;
+  std::condition_variable yd_cv;             // "a decoder set has been launched"
 };
 
 namespace {
@@ -785,6 +819,196 @@ int hd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
   return last ? hd_wait_unlocking(g, lk, last) : MI355_OK;
 }
 
+// ------------------------------------------------------------------ decoder queue
+
+// is `ticket` a decoder tensor that has not been collected?
+bool yd_owns(mi355_group *g, uint64_t ticket) {
+  if (g->yd_where.count(ticket) || g->yd_results.count(ticket)) return true;
+  for (const YdDesc &d : g->yd_pending)
+    if (d.ticket == ticket) return true;
+  return false;
+}
+
+// the queue's stream and scratch: at the first submit, never inside a launch set. g->mu held.
+int yd_ensure(mi355_group *g) {
+  if (g->yd_scratch) return MI355_OK;
+  if (!g->yd_stream && hipStreamCreateWithFlags(&g->yd_stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    g->yd_stream = nullptr;
+    return fail(g, MI355_ERR_HIP, "group: no stream for the decoder queue");
+  }
+  int st = MI355_OK;
+  std::string err;
+  g->yd_scratch = yolodec_set_scratch_new(&st, &err);
+  return g->yd_scratch ? MI355_OK : fail(g, st, "group: " + err);
+}
+
+// a pinned block of at least `bytes`: a free one that is large enough, else a new one (a free one that is too small makes room)
+YdBlock yd_take_block(mi355_group *g, size_t bytes) {
+  for (size_t i = 0; i < g->yd_blocks.size(); i++)
+    if (g->yd_blocks[i].bytes >= bytes) {
+      const YdBlock b = g->yd_blocks[i];
+      g->yd_blocks.erase(g->yd_blocks.begin() + (std::ptrdiff_t)i);
+      return b;
+    }
+  if (!g->yd_blocks.empty()) {
+    (void)hipHostFree(g->yd_blocks.back().h);
+    g->yd_blocks.pop_back();
+  }
+  YdBlock b{nullptr, 0};
+  const size_t want = (bytes + 4095) / 4096 * 4096;
+  if (hipHostMalloc(&b.h, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); b.h = nullptr; return b; }
+  b.bytes = want;
+  return b;
+}
+
+// a finished set: counts and records move from its pinned block into yd_results (once), the block is free again. g->mu held.
+void yd_collect(mi355_group *g, YdSet &s) {
+  if (s.collected) return;
+  s.collected = true;
+  if (g->yd_results.size() > 65536) g->yd_results.clear();   // (results nobody ever collected)
+  const uint32_t *h_n = static_cast<const uint32_t *>(s.block.h);
+  const mi355_yolo_det *h_dets = s.block.h ? reinterpret_cast<const mi355_yolo_det *>(static_cast<const uint8_t *>(s.block.h) + kYdCountsBytes) : nullptr;
+  for (size_t i = 0; i < s.slots.size(); i++) {
+    const YdSlot &sl = s.slots[i];
+    YdOut &o = g->yd_results[sl.ticket];
+    o.status = MI355_OK;
+    o.max_dets = sl.max_dets;
+    o.n_dets = sl.num_candidates && h_n ? h_n[i] : 0;   // a tensor without candidates had no job
+    const uint32_t cap = sl.max_dets < sl.num_candidates ? sl.max_dets : sl.num_candidates;
+    const uint32_t w = o.n_dets < cap ? o.n_dets : cap;
+    if (w) o.dets.assign(h_dets + sl.det_offset, h_dets + sl.det_offset + w);
+    g->yd_where.erase(sl.ticket);
+  }
+  if (s.block.h) g->yd_blocks.push_back(s.block);
+  s.block = YdBlock{nullptr, 0};
+}
+
+// collected sets nobody waits inside leave: the event goes back to the free list. g->mu held.
+void yd_retire(mi355_group *g) {
+  for (auto it = g->yd_sets.begin(); it != g->yd_sets.end();) {
+    if (it->collected && it->waiters == 0) {
+      g->events.push_back(it->done);
+      it = g->yd_sets.erase(it);
+    } else {
+      ++it;
+    }
+  }
+}
+
+// finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
+void yd_retire_done(mi355_group *g) {
+  for (YdSet &s : g->yd_sets) {
+    if (s.collected) continue;
+    if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
+    yd_collect(g, s);
+  }
+  yd_retire(g);
+}
+
+// launches the pending tensors in submission order, kYdSetMax to a set (all of them, or up to the set that carries `until`):
+// consecutive sets on the queue's stream share the device scratch, each has its own pinned block. g->mu held.
+int yd_flush_locked(mi355_group *g, uint64_t until = 0) {
+  bool reached = false;
+  int first_rc = MI355_OK;
+  while (!g->yd_pending.empty() && !reached) {
+    const size_t n = std::min(g->yd_pending.size(), (size_t)kYdSetMax);
+    std::vector<YdDesc> take(g->yd_pending.begin(), g->yd_pending.begin() + (std::ptrdiff_t)n);
+    g->yd_pending.erase(g->yd_pending.begin(), g->yd_pending.begin() + (std::ptrdiff_t)n);
+    int rc = MI355_OK, launches = 0;
+    std::string err;
+    // the set's layout: the plan the launch itself uses
+    YdTensor tensors[kYdSetMax];
+    int layout[kYdSetMax];
+    uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], blocks[kYdSetMax];
+    uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax], totals[6] = {0, 0, 0, 0, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+      tensors[i] = take[i].t;
+      layout[i] = take[i].t.layout; F[i] = take[i].t.num_fields; N[i] = take[i].t.num_candidates; cap[i] = take[i].t.max_dets;
+    }
+    rc = yolodec_set_plan((int)n, layout, F, N, cap, first, blocks, key_off, box_off, det_off, totals);
+    if (rc) err = "group: bad decoder set";
+    hipEvent_t done = take_event(g);
+    YdBlock block{nullptr, 0};
+    if (!rc && totals[2]) {   // a set without a candidate has nothing to copy
+      if (g->yd_blocks.empty()) yd_retire_done(g);
+      block = yd_take_block(g, yolodec_set_result_bytes(totals[5]));
+    }
+    if (!rc && (!done || (totals[2] && !block.h))) { rc = MI355_ERR_HIP; err = "group: no event or pinned block for a decoder set"; }
+    for (size_t i = 0; i < n; i++)
+      if (!rc && take[i].ready && hipStreamWaitEvent(g->yd_stream, take[i].ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipStreamWaitEvent(decoder tensor)"; }
+    if (!rc) rc = yolodec_launch_set(g->yd_scratch, g->yd_stream, tensors, (int)n, block.h, block.bytes, &launches, &err);
+    if (!rc && hipEventRecord(done, g->yd_stream) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipEventRecord(decoder set)"; }
+    for (const YdDesc &d : take)
+      if (d.ready) g->events.push_back(d.ready);
+    if (rc) {
+      (void)hipGetLastError();
+      if (done) g->events.push_back(done);
+      if (block.h) {
+        // what did go out may still write the block: it is free again only behind the queue's stream
+        (void)hipStreamSynchronize(g->yd_stream);
+        (void)hipGetLastError();
+        g->yd_blocks.push_back(block);
+      }
+      g->last_error = "group: decoder launch failed: " + err;
+      if (g->yd_results.size() > 65536) g->yd_results.clear();
+      for (const YdDesc &d : take) {   // told to the tensor's own wait, once
+        YdOut &o = g->yd_results[d.ticket];
+        o.status = rc;
+        o.n_dets = 0;
+        o.max_dets = d.t.max_dets;
+      }
+      if (!first_rc) first_rc = rc;
+      continue;
+    }
+    YdSet s{g->next_yd_seq++, {}, done, 0, block};
+    for (size_t i = 0; i < n; i++) {
+      const YdDesc &d = take[i];
+      s.slots.push_back(YdSlot{d.ticket, d.t.num_candidates, d.t.max_dets, det_off[i]});
+      g->yd_where[d.ticket] = s.seq;
+      reached |= until != 0 && d.ticket == until;
+    }
+    g->yd_sets.push_back(std::move(s));
+    g->n_yd_tensors += n;
+    g->n_yd_sets++;
+    if (n > g->n_yd_largest) g->n_yd_largest = n;
+    g->n_yd_launches += (uint64_t)launches;
+  }
+  g->yd_cv.notify_all();
+  return first_rc;
+}
+
+// host wait for the set of `ticket`; `lk` owns g->mu on entry and on return, not while waiting
+int yd_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
+  auto it = g->yd_where.find(ticket);
+  if (it == g->yd_where.end()) return MI355_OK;  // collected already (or failed: yd_results has it)
+  const uint64_t seq = it->second;
+  YdSet *mine = nullptr;
+  for (YdSet &s : g->yd_sets)
+    if (s.seq == seq) { mine = &s; break; }
+  if (!mine) return MI355_OK;
+  const hipEvent_t ev = mine->done;
+  mine->waiters++;
+  lk.unlock();
+  const hipError_t e = hipEventSynchronize(ev);
+  lk.lock();
+  for (YdSet &s : g->yd_sets)
+    if (s.seq == seq) { s.waiters--; break; }
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group decoder set)"); }
+  for (YdSet &s : g->yd_sets)
+    if (s.seq <= seq) yd_collect(g, s);
+  yd_retire(g);
+  return MI355_OK;
+}
+
+// waits for every set launched so far (their results stay collectable)
+int yd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
+  uint64_t last = 0;
+  for (const YdSet &s : g->yd_sets)
+    if (!s.collected) last = s.slots.front().ticket;
+  return last ? yd_wait_unlocking(g, lk, last) : MI355_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -860,6 +1084,25 @@ void mi355_group_destroy(mi355_group *g) {
     g->hd_pending.clear();
     (void)hipStreamDestroy(g->hd_stream);
   }
+  if (g->yd_stream) {
+    // tensors still pending are launched and waited for, as frames are: nothing reads a member's tensor once destroy has returned
+    if (g->yd_scratch) {
+      Locked L(g);
+      (void)yd_flush_locked(g);
+    }
+    (void)hipStreamSynchronize(g->yd_stream);
+    for (YdSet &s : g->yd_sets) {
+      (void)hipEventDestroy(s.done);
+      if (s.block.h) (void)hipHostFree(s.block.h);
+    }
+    g->yd_sets.clear();
+    for (YdDesc &d : g->yd_pending)
+      if (d.ready) (void)hipEventDestroy(d.ready);
+    g->yd_pending.clear();
+    yolodec_set_scratch_free(g->yd_scratch);
+    (void)hipStreamDestroy(g->yd_stream);
+  }
+  for (YdBlock &b : g->yd_blocks) (void)hipHostFree(b.h);
   for (Batch &b : g->batches) (void)hipEventDestroy(b.done);   // (normally none left: wait_all retired them)
   for (Desc &d : g->pending)
     if (d.ready) (void)hipEventDestroy(d.ready);
@@ -952,7 +1195,8 @@ int mi355_group_flush(mi355_group *g) {
   const int rc2 = g->actx ? cmp_flush_locked(g) : MI355_OK;
   const int rc3 = g->cd_scratch ? cd_flush_locked(g) : MI355_OK;
   const int rc4 = g->hd_stream ? hd_flush_locked(g) : MI355_OK;
-  return rc ? rc : (rc2 ? rc2 : (rc3 ? rc3 : rc4));
+  const int rc5 = g->yd_scratch ? yd_flush_locked(g) : MI355_OK;
+  return rc ? rc : (rc2 ? rc2 : (rc3 ? rc3 : (rc4 ? rc4 : rc5)));
 }
 
 // ---------------------------------------------------------------- videocompare pairs (Dssim / Blockhash) of independent elements
@@ -1036,6 +1280,7 @@ int mi355_group_wait_compare(mi355_group *g, uint64_t ticket, double *distance, 
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
   if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
   if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
+  if (yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a decoder tensor's ticket (mi355_group_wait_yolodec collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   auto is_pending = [&]() { for (const CmpDesc &d : g->cmp_pending) if (d.ticket == ticket) return true; return false; };
   if (is_pending()) {
@@ -1119,7 +1364,7 @@ int mi355_group_wait_colordetect(mi355_group *g, uint64_t ticket, uint8_t palett
   Locked L(g);
   std::unique_lock<std::mutex> &lk = L.lk;
   if (!palette_rgb || !n_colors) return fail(g, MI355_ERR_INVALID_ARG, "group: null result arrays");
-  // a filter frame's, a pair's, a collected or an unknown ticket: refused before anything is launched or waited for
+  // a filter frame's, a pair's, a detector frame's, a decoder tensor's, a collected or an unknown ticket: refused before anything is launched or waited for
   if (!cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: not the ticket of a colordetect frame that is still to be collected");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   auto is_pending = [&]() { for (const CdDesc &d : g->cd_pending) if (d.ticket == ticket) return true; return false; };
@@ -1250,6 +1495,106 @@ int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_pe
   return hsvdetect_plan(n_cu, blocks_per_cu, units_per_block, n_jobs, units, first_block, blocks, total_blocks);
 }
 
+// ---------------------------------------------------------------- decoder tensors of independent elements
+
+int mi355_group_set_yolodec_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
+  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  g->yd_expected = expected_streams;
+  g->yd_linger_us = linger_us;
+  return MI355_OK;
+}
+
+int mi355_group_submit_yolodec(mi355_group *g, mi355_ctx *ctx, const float *d_tensor, int layout, uint32_t num_fields, uint32_t num_candidates,
+                               const mi355_yolo_params *p, uint32_t max_dets, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !p || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context, settings or ticket");
+  const char *why = nullptr;
+  int rc = yolodec_check_args((size_t)num_fields * num_candidates * 4, 1, layout, num_fields, num_candidates, &why);
+  if (rc) return fail(g, rc, why);
+  if (num_candidates && (!d_tensor || (uintptr_t)d_tensor % 4 != 0)) return fail(g, MI355_ERR_INVALID_ARG, "yolodec: null or misaligned tensors");
+  if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
+  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+  if ((rc = yd_ensure(g))) return rc;
+  yd_retire_done(g);
+  YdDesc d{};
+  d.t = YdTensor{d_tensor, layout, num_fields, num_candidates, max_dets, *p};
+  d.ready = nullptr;
+  if (num_candidates && hipStreamQuery(ctx->stream) != hipSuccess) {   // the tensor is read after what the context's stream holds now (an upload, the model's last kernel)
+    (void)hipGetLastError();
+    d.ready = take_event(g);
+    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      if (d.ready) g->events.push_back(d.ready);
+      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
+    }
+  }
+  d.ticket = g->next_ticket++;
+  *ticket = d.ticket;
+  g->yd_pending.push_back(d);
+  // everybody is here (rendezvous), or a launch set is full: go. The tensor has been accepted whatever that launch does (a failure
+  // is told to the waits of the tensors it carried).
+  const int full = g->yd_expected > 0 && g->yd_expected < kYdSetMax ? g->yd_expected : kYdSetMax;
+  if ((int)g->yd_pending.size() >= full) (void)yd_flush_locked(g);
+  return MI355_OK;
+}
+
+int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *dets, uint32_t *n_dets) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  std::unique_lock<std::mutex> &lk = L.lk;
+  if (!n_dets) return fail(g, MI355_ERR_INVALID_ARG, "group: null result count");
+  // another queue's, a collected or an unknown ticket: refused before anything is launched or waited for
+  if (!yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: not the ticket of a decoder tensor that is still to be collected");
+  if (!dets) {   // only a tensor submitted with max_dets == 0 has no records to take
+    uint32_t cap = 0;
+    for (const YdDesc &d : g->yd_pending)
+      if (d.ticket == ticket) cap = d.t.max_dets;
+    auto w = g->yd_where.find(ticket);
+    if (w != g->yd_where.end())
+      for (const YdSet &s : g->yd_sets)
+        if (s.seq == w->second)
+          for (const YdSlot &sl : s.slots)
+            if (sl.ticket == ticket) cap = sl.max_dets;
+    auto r = g->yd_results.find(ticket);
+    if (r != g->yd_results.end()) cap = r->second.max_dets;
+    if (cap) return fail(g, MI355_ERR_INVALID_ARG, "group: null records for a tensor submitted with max_dets > 0");
+  }
+  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+  auto is_pending = [&]() { for (const YdDesc &d : g->yd_pending) if (d.ticket == ticket) return true; return false; };
+  if (is_pending()) {
+    // rendezvous: the other instances of this interval are about to submit - linger for them (bounded), then launch what is there
+    if (g->yd_expected > 0 && g->yd_linger_us > 0) {
+      const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(g->yd_linger_us);
+      while (is_pending() && (int)g->yd_pending.size() < g->yd_expected) {
+        if (g->yd_cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
+      }
+    }
+    if (is_pending()) (void)yd_flush_locked(g, ticket);   // (a failure of this tensor's own launch is in yd_results)
+  }
+  int rc = yd_wait_unlocking(g, lk, ticket);
+  if (rc) return rc;
+  auto r = g->yd_results.find(ticket);
+  if (r == g->yd_results.end()) return fail(g, MI355_ERR_INVALID_ARG, "group: this tensor's result has been collected already");   // (by a concurrent wait)
+  const YdOut res = std::move(r->second);
+  g->yd_results.erase(r);
+  if (res.status) return fail(g, res.status, "group: the launch that carried this decoder tensor failed");
+  *n_dets = res.n_dets;
+  if (dets && !res.dets.empty()) std::memcpy(dets, res.dets.data(), res.dets.size() * sizeof(mi355_yolo_det));
+  return MI355_OK;
+}
+
+int mi355_group_yolodec_stats(mi355_group *g, uint64_t stats[4]) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  stats[0] = g->n_yd_tensors;
+  stats[1] = g->n_yd_sets;
+  stats[2] = g->n_yd_largest;
+  stats[3] = g->n_yd_launches;
+  return MI355_OK;
+}
+
 int mi355_group_wait(mi355_group *g, uint64_t ticket) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
@@ -1257,6 +1602,7 @@ int mi355_group_wait(mi355_group *g, uint64_t ticket) {
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
   if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
   if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
+  if (yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a decoder tensor's ticket (mi355_group_wait_yolodec collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -1273,6 +1619,7 @@ int mi355_group_order_after(mi355_group *g, mi355_ctx *ctx, uint64_t ticket) {
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
   if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
   if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
+  if (yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a decoder tensor's ticket (mi355_group_wait_yolodec collects it)");
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -1304,9 +1651,13 @@ int mi355_group_wait_all(mi355_group *g) {
     if ((rc = cd_flush_locked(g))) return rc;
     if ((rc = cd_wait_all_unlocking(g, lk))) return rc;
   }
-  if (!g->hd_stream) return MI355_OK;
-  if ((rc = hd_flush_locked(g))) return rc;
-  return hd_wait_all_unlocking(g, lk);
+  if (g->hd_stream) {
+    if ((rc = hd_flush_locked(g))) return rc;
+    if ((rc = hd_wait_all_unlocking(g, lk))) return rc;
+  }
+  if (!g->yd_scratch) return MI355_OK;
+  if ((rc = yd_flush_locked(g))) return rc;
+  return yd_wait_all_unlocking(g, lk);
 }
 
 int mi355_group_submit_round(mi355_group *g, mi355_ctx *const *ctxs, int n_streams, uint8_t *const *d_src, uint8_t *const *d_dst, int width, int height,

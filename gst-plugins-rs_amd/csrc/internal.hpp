@@ -317,6 +317,22 @@ int mixer_plan(int n_members, const uint32_t *n_inputs, const uint32_t *n_out_ch
 int mixer_launch(MixerTablesBuf *B, hipStream_t stream, const MixerCall *calls, int n, int *kernel_launches, std::string *err);
 void mixer_release(mi355_ctx *ctx);
 void yolodec_release(mi355_ctx *ctx);
+// the checks of mi355_yolodec_tensors_device that need no device; *why names the refusal
+int yolodec_check_args(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates, const char **why);
+// launch sets of the video group's decoder queue (yolodec.hip): tensors of independent instances, job tables
+constexpr int kYdSetMax = MI355_YOLODEC_SET_MAX;
+constexpr size_t kYdCountsBytes = 128;  // a result block: kYdSetMax kept counts (by job), then the jobs' records at their det_offset
+struct YdTensor { const float *data; int layout; uint32_t num_fields, num_candidates, max_dets; mi355_yolo_params p; };
+struct YdSetScratch;  // counters (zero between sets), keys, kept boxes and positions, results, on the device
+int yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, uint32_t *first_block,
+                     uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]);
+YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err);
+void yolodec_set_scratch_free(YdSetScratch *S);
+size_t yolodec_set_result_bytes(uint64_t records);  // the pinned block a set with that many records (totals[5]) is copied to
+// n <= kYdSetMax checked tensors on `stream`: the V8 score launch, the X score launch (each only if it has a job with a candidate),
+// the NMS launch, counts and records into h_block (nothing launched or copied if no tensor has a candidate)
+int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
+                       std::string *err);
 int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, int channel, int kind, float *out, int *w, int *h);
 int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate);
 int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps);

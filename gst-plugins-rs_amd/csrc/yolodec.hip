@@ -28,10 +28,16 @@
 //                                 wave (chunks of 64 sorted boxes, one per lane: tested against all boxes kept before, then
 //                                 resolved in order inside the chunk with ballots), prefix sum of the runs' kept counts, records.
 //                                 The survivor counter is left at zero for the next call.
+//   yolodec_score_jobs_kernel<LAYOUT>, yolodec_nms_jobs_kernel
+//                                 the job-table forms for the video group's decoder queue (group.hip): tensors of independent
+//                                 instances - own data pointer, F, N, layout, settings, scratch - in at most three launches per
+//                                 set. Thin wrappers, as the lone kernels are, around the same device functions (score_tile,
+//                                 sort_keys, find_runs, greedy_nms, write_records).
 #include "internal.hpp"
 
 #include <climits>
 #include <cstring>
+#include <string>
 
 namespace mi355 {
 
@@ -91,16 +97,12 @@ __device__ __forceinline__ void append_keys(bool keep, unsigned long long key, u
   if (keep && at < key_pitch) keys[at] = key;   // always inside: the counter starts at zero and a candidate is appended once
 }
 
-// LAYOUT 0: V8, 1: X. keys: [tensors][key_pitch], count: [tensors], zero on entry
+// the score work of the 256-candidate tile that starts at candidate c0 (c0 < N), by the whole block: survivors are appended to
+// keys[0 .. key_pitch) behind *count. LAYOUT 0: V8, 1: X. Shared by the lone kernel and the job-table kernel.
 template <int LAYOUT>
-__global__ __launch_bounds__(kScoreThreads) void yolodec_score_kernel(const uint32_t *__restrict__ tensors, size_t pitch_dwords, uint32_t F, uint32_t N,
-                                                                       const mi355_yolo_params *__restrict__ params, uint32_t *__restrict__ count,
-                                                                       unsigned long long *__restrict__ keys, size_t key_pitch) {
-  const uint32_t t = blockIdx.y;
-  const uint32_t *__restrict__ data = tensors + (size_t)t * pitch_dwords;
-  const mi355_yolo_params P = params[t];
+__device__ __forceinline__ void score_tile(const uint32_t *__restrict__ data, uint32_t F, uint32_t N, const mi355_yolo_params &P, uint32_t c0,
+                                           uint32_t *__restrict__ count, unsigned long long *__restrict__ keys, size_t key_pitch) {
   const int tid = threadIdx.x;
-  const uint32_t c0 = blockIdx.x * kScoreThreads;
   const uint32_t c = c0 + (uint32_t)tid;
   const bool valid = c < N;
   int32_t best_key = INT_MIN;   // the smallest key there is: the first class always replaces it
@@ -154,7 +156,17 @@ __global__ __launch_bounds__(kScoreThreads) void yolodec_score_kernel(const uint
       conf_bits = __float_as_uint(obj * conf);
     }
   }
-  append_keys(keep, make_key(best_cls, conf_bits, c), count + t, keys + (size_t)t * key_pitch, key_pitch);
+  append_keys(keep, make_key(best_cls, conf_bits, c), count, keys, key_pitch);
+}
+
+// keys: [tensors][key_pitch], count: [tensors], zero on entry
+template <int LAYOUT>
+__global__ __launch_bounds__(kScoreThreads) void yolodec_score_kernel(const uint32_t *__restrict__ tensors, size_t pitch_dwords, uint32_t F, uint32_t N,
+                                                                       const mi355_yolo_params *__restrict__ params, uint32_t *__restrict__ count,
+                                                                       unsigned long long *__restrict__ keys, size_t key_pitch) {
+  const uint32_t t = blockIdx.y;
+  const mi355_yolo_params P = params[t];
+  score_tile<LAYOUT>(tensors + (size_t)t * pitch_dwords, F, N, P, blockIdx.x * kScoreThreads, count + t, keys + (size_t)t * key_pitch, key_pitch);
 }
 
 // ascending bitonic sort of n2 keys (a power of two) by the whole block
@@ -228,38 +240,19 @@ struct NmsShared {
   uint32_t n;
 };
 
-// kbox / ksrc: [tensors][N], the kept boxes of a run compacted at the run's start (and the sorted position each came from)
+// LAYOUT 0: V8, 1: X, 2: `layout` decides (block-uniform: the job-table kernel)
 template <int LAYOUT>
-__global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *__restrict__ tensors, size_t pitch_dwords, uint32_t F, uint32_t N,
-                                                                   const mi355_yolo_params *__restrict__ params, uint32_t *__restrict__ count,
-                                                                   unsigned long long *__restrict__ keys, size_t key_pitch, float4 *__restrict__ kbox,
-                                                                   uint32_t *__restrict__ ksrc, mi355_yolo_det *__restrict__ dets, uint32_t max_dets,
-                                                                   uint32_t *__restrict__ n_dets) {
-  __shared__ unsigned long long lds_keys[kLdsSortKeys];
-  __shared__ NmsShared S;
-  const uint32_t t = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float *__restrict__ data = tensors + (size_t)t * pitch_dwords;
-  const uint32_t n_classes = LAYOUT == 0 ? F - 4 : F - 5;
-  const float iou_thr = params[t].iou_threshold;
-  if (tid == 0) {
-    S.n = count[t];
-    count[t] = 0;   // zero again for the next call
-  }
-  for (uint32_t c = tid; c < n_classes; c += kNmsThreads) {
-    S.run_lo[c] = 0;
-    S.run_hi[c] = 0;
-    S.kept[0][c] = 0;
-  }
-  __syncthreads();
-  const uint32_t n = S.n < N ? S.n : N;   // S.n <= N: every candidate is appended at most once
-  if (n == 0) {
-    if (tid == 0) n_dets[t] = 0;
-    return;
-  }
+__device__ __forceinline__ Box load_box_of(int layout, const float *__restrict__ data, uint32_t F, uint32_t N, uint32_t c) {
+  if (LAYOUT == 2) return layout == MI355_YOLO_V8 ? load_box<0>(data, F, N, c) : load_box<1>(data, F, N, c);
+  return load_box<LAYOUT == 2 ? 0 : LAYOUT>(data, F, N, c);
+}
+
+// the n survivors' keys sorted ascending by the whole block: in LDS up to kLdsSortKeys keys, in the key list itself above (gk holds
+// at least the power of two above n). Returns where the sorted keys are.
+__device__ __forceinline__ const unsigned long long *sort_keys(unsigned long long *lds_keys, unsigned long long *gk, uint32_t n) {
+  const int tid = threadIdx.x;
   uint32_t n2 = 1;
   while (n2 < n) n2 <<= 1;
-  unsigned long long *gk = keys + (size_t)t * key_pitch;   // key_pitch >= the power of two above N
   const bool in_lds = n2 <= (uint32_t)kLdsSortKeys;
   if (in_lds) {
     for (uint32_t i = tid; i < n2; i += kNmsThreads) lds_keys[i] = i < n ? gk[i] : kPadKey;
@@ -270,9 +263,12 @@ __global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *_
     __syncthreads();
     bitonic_sort(gk, n2);
   }
-  const unsigned long long *K = in_lds ? lds_keys : gk;
-  // class runs by their boundaries
-  for (uint32_t i = tid; i < n; i += kNmsThreads) {
+  return in_lds ? lds_keys : gk;
+}
+
+// class runs by their boundaries (S.run_lo / S.run_hi are zero on entry); ends in a barrier
+__device__ __forceinline__ void find_runs(const unsigned long long *K, uint32_t n, uint32_t n_classes, NmsShared &S) {
+  for (uint32_t i = threadIdx.x; i < n; i += kNmsThreads) {
     const uint32_t c = key_class(K[i]);
     if (c < n_classes) {   // always: classes come from the score kernel
       if (i == 0 || key_class(K[i - 1]) != c) S.run_lo[c] = i;
@@ -280,9 +276,14 @@ __global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *_
     }
   }
   __syncthreads();
-  float4 *kb = kbox + (size_t)t * N;
-  uint32_t *ks = ksrc + (size_t)t * N;
-  // greedy NMS: the runs shared out over the waves
+}
+
+// greedy NMS: the runs shared out over the waves. kb / ks: the kept boxes of a run compacted at the run's start (and the sorted
+// position each came from); S.kept[0][c]: how many. Ends in a barrier.
+template <int LAYOUT>
+__device__ __forceinline__ void greedy_nms(int layout, const float *__restrict__ data, uint32_t F, uint32_t N, const unsigned long long *K, float iou_thr,
+                                           uint32_t n_classes, float4 *kb, uint32_t *ks, NmsShared &S) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (uint32_t c = wave; c < n_classes; c += kNmsWaves) {
     const uint32_t lo = S.run_lo[c], hi = S.run_hi[c];
     uint32_t m = 0;   // boxes kept so far in this run (wave-uniform)
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *_
       const uint32_t i = base + (uint32_t)lane;
       bool alive = i < hi;
       Box b = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (alive) b = load_box<LAYOUT>(data, F, N, key_cand(K[i]));
+      if (alive) b = load_box_of<LAYOUT>(layout, data, F, N, key_cand(K[i]));
       // against everything kept in earlier chunks
       for (uint32_t j = 0; j < m; j++) {
         const float4 q = kb[lo + j];
@@ -322,6 +323,12 @@ __global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *_
     if (lane == 0) S.kept[0][c] = m;
   }
   __syncthreads();
+}
+
+// prefix sum of the runs' kept counts, the total into *n_out, the first max_dets records into out
+__device__ __forceinline__ void write_records(const unsigned long long *K, uint32_t n_classes, const float4 *kb, const uint32_t *ks, NmsShared &S,
+                                              mi355_yolo_det *__restrict__ out, uint32_t max_dets, uint32_t *__restrict__ n_out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // exclusive prefix sums of the kept counts over n_classes + 1 entries (Hillis-Steele on the shifted array)
   const uint32_t L = n_classes + 1;
   for (uint32_t c = tid; c < L; c += kNmsThreads) S.kept[1][c] = c == 0 ? 0 : S.kept[0][c - 1];
@@ -333,8 +340,7 @@ __global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *_
     cur ^= 1;
   }
   const uint32_t *first = S.kept[cur];   // first[c]: output index of class c's first box; first[n_classes]: the total
-  if (tid == 0) n_dets[t] = first[n_classes];
-  mi355_yolo_det *out = dets + (size_t)t * max_dets;
+  if (tid == 0) *n_out = first[n_classes];
   for (uint32_t c = wave; c < n_classes; c += kNmsWaves) {
     const uint32_t lo = S.run_lo[c], m = first[c + 1] - first[c], o0 = first[c];
     for (uint32_t j = lane; j < m; j += 64) {
@@ -358,6 +364,95 @@ __global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *_
       out[o] = d;
     }
   }
+}
+
+// one tensor by one block: sort, runs, NMS, records. *count (the survivors behind gk) is left at zero. kb / ks: N entries each;
+// gk: at least the power of two above N keys. Shared by the lone kernel and the job-table kernel.
+template <int LAYOUT>
+__device__ __forceinline__ void nms_block(int layout, const float *__restrict__ data, uint32_t F, uint32_t N, float iou_thr, uint32_t *__restrict__ count,
+                                          unsigned long long *__restrict__ gk, float4 *__restrict__ kb, uint32_t *__restrict__ ks,
+                                          mi355_yolo_det *__restrict__ out, uint32_t max_dets, uint32_t *__restrict__ n_out,
+                                          unsigned long long *lds_keys, NmsShared &S) {
+  const int tid = threadIdx.x;
+  const bool v8 = LAYOUT == 2 ? layout == MI355_YOLO_V8 : LAYOUT == 0;
+  const uint32_t n_classes = v8 ? F - 4 : F - 5;
+  if (tid == 0) {
+    S.n = *count;
+    *count = 0;   // zero again for the next call
+  }
+  for (uint32_t c = tid; c < n_classes; c += kNmsThreads) {
+    S.run_lo[c] = 0;
+    S.run_hi[c] = 0;
+    S.kept[0][c] = 0;
+  }
+  __syncthreads();
+  const uint32_t n = S.n < N ? S.n : N;   // S.n <= N: every candidate is appended at most once
+  if (n == 0) {
+    if (tid == 0) *n_out = 0;
+    return;
+  }
+  const unsigned long long *K = sort_keys(lds_keys, gk, n);
+  find_runs(K, n, n_classes, S);
+  greedy_nms<LAYOUT>(layout, data, F, N, K, iou_thr, n_classes, kb, ks, S);
+  write_records(K, n_classes, kb, ks, S, out, max_dets, n_out);
+}
+
+// kbox / ksrc: [tensors][N]
+template <int LAYOUT>
+__global__ __launch_bounds__(kNmsThreads) void yolodec_nms_kernel(const float *__restrict__ tensors, size_t pitch_dwords, uint32_t F, uint32_t N,
+                                                                   const mi355_yolo_params *__restrict__ params, uint32_t *__restrict__ count,
+                                                                   unsigned long long *__restrict__ keys, size_t key_pitch, float4 *__restrict__ kbox,
+                                                                   uint32_t *__restrict__ ksrc, mi355_yolo_det *__restrict__ dets, uint32_t max_dets,
+                                                                   uint32_t *__restrict__ n_dets) {
+  __shared__ unsigned long long lds_keys[kLdsSortKeys];
+  __shared__ NmsShared S;
+  const uint32_t t = blockIdx.x;
+  nms_block<LAYOUT>(LAYOUT, tensors + (size_t)t * pitch_dwords, F, N, params[t].iou_threshold, count + t, keys + (size_t)t * key_pitch, kbox + (size_t)t * N,
+                    ksrc + (size_t)t * N, dets + (size_t)t * max_dets, max_dets, n_dets + t, lds_keys, S);
+}
+
+// ---- job-table forms (the video group's decoder queue): tensors of independent instances - own data pointer, shape, layout, settings,
+// scratch - in one launch. The table is passed in the kernel arguments; every field a block reads is block-uniform.
+struct YdJob {
+  const float *data;
+  uint32_t *count;              // the job's survivor counter; zero on entry to the score launch, left at zero by the NMS launch
+  unsigned long long *keys;     // key_cap entries
+  float4 *kbox;                 // N entries
+  uint32_t *ksrc;               // N entries
+  mi355_yolo_det *dets;         // min(max_dets, N) records
+  uint32_t *n_dets;
+  uint32_t F, N, key_cap, max_dets;
+  uint32_t first_block, blocks; // its tiles in the score launch of its layout (yolodec_set_plan)
+  int32_t layout;
+  mi355_yolo_params p;
+};
+struct YdJobTable {
+  YdJob job[kYdSetMax];
+  int32_t n_jobs, pad;
+};
+static_assert(sizeof(YdJob) == 96, "YdJob has no padding holes");
+static_assert(sizeof(YdJobTable) <= 4096, "the job table is passed in the kernel arguments");
+
+// one flat grid over the tiles of the jobs of one layout: jobs are in first_block order and every job of a table has a block
+template <int LAYOUT>
+__global__ __launch_bounds__(kScoreThreads) void yolodec_score_jobs_kernel(const YdJobTable T) {
+  int j = 0;
+  while (j + 1 < T.n_jobs && blockIdx.x >= T.job[j].first_block + T.job[j].blocks) j++;
+  const uint32_t rel = blockIdx.x - T.job[j].first_block;
+  if (blockIdx.x < T.job[j].first_block || rel >= T.job[j].blocks) return;   // a grid larger than the plan's total: the whole block leaves, before any barrier
+  const mi355_yolo_params P = T.job[j].p;
+  score_tile<LAYOUT>(reinterpret_cast<const uint32_t *>(T.job[j].data), T.job[j].F, T.job[j].N, P, rel * kScoreThreads, T.job[j].count, T.job[j].keys,
+                     (size_t)T.job[j].key_cap);
+}
+
+// one block per job with candidates, whatever its layout
+__global__ __launch_bounds__(kNmsThreads) void yolodec_nms_jobs_kernel(const YdJobTable T) {
+  __shared__ unsigned long long lds_keys[kLdsSortKeys];
+  __shared__ NmsShared S;
+  const int j = (int)blockIdx.x;
+  if (j >= T.n_jobs) return;
+  nms_block<2>(T.job[j].layout, T.job[j].data, T.job[j].F, T.job[j].N, T.job[j].p.iou_threshold, T.job[j].count, T.job[j].keys, T.job[j].kbox, T.job[j].ksrc,
+               T.job[j].dets, T.job[j].max_dets, T.job[j].n_dets, lds_keys, S);
 }
 
 uint32_t pow2_at_least(uint32_t n) {
@@ -508,6 +603,153 @@ static int yolodec_run(mi355_ctx *ctx, YoloDecState *s, const float *d_tensors, 
   return MI355_OK;
 }
 
+// ---- launch sets of the video group's decoder queue
+
+// the layout of one set (mi355_selftest_yolodec_set_plan; yolodec_launch_set lays its scratch out with it)
+int yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, uint32_t *first_block,
+                     uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]) {
+  if (n_jobs < 0 || n_jobs > kYdSetMax || !totals) return MI355_ERR_INVALID_ARG;
+  if (n_jobs > 0 && (!layout || !num_fields || !num_candidates || !max_dets || !first_block || !blocks || !key_offset || !box_offset || !det_offset))
+    return MI355_ERR_INVALID_ARG;
+  for (int j = 0; j < n_jobs; j++) {
+    const char *why = nullptr;
+    const int rc = yolodec_check_args((size_t)num_fields[j] * num_candidates[j] * 4, 1, layout[j], num_fields[j], num_candidates[j], &why);
+    if (rc) return rc;
+  }
+  uint64_t t[6] = {0, 0, 0, 0, 0, 0};   // V8 blocks, X blocks, NMS blocks, keys, boxes, records
+  for (int j = 0; j < n_jobs; j++) {
+    const uint32_t N = num_candidates[j];
+    uint64_t &layout_blocks = t[layout[j] == MI355_YOLO_V8 ? 0 : 1];
+    blocks[j] = (N + kScoreThreads - 1) / kScoreThreads;
+    first_block[j] = (uint32_t)layout_blocks;   // at most 32 * 256 blocks
+    layout_blocks += blocks[j];
+    if (N) t[2]++;
+    key_offset[j] = t[3];
+    t[3] += pow2_at_least(N);
+    box_offset[j] = t[4];
+    t[4] += N;
+    det_offset[j] = t[5];
+    t[5] += max_dets[j] < N ? max_dets[j] : N;
+  }
+  for (int k = 0; k < 6; k++) totals[k] = t[k];
+  return MI355_OK;
+}
+
+// scratch of one queue; grows to the largest set seen
+struct YdSetScratch {
+  uint32_t *d_count = nullptr;   // [kYdSetMax] survivors; zero between sets
+  bool count_zero = false;       // false after the allocation or an interrupted set: cleared before the next launch
+  unsigned long long *d_keys = nullptr;
+  float4 *d_kbox = nullptr;
+  uint32_t *d_ksrc = nullptr;
+  uint8_t *d_out = nullptr;      // [kYdSetMax] counts (kYdCountsBytes), then the jobs' records at their det_offset
+  size_t key_elems = 0, kbox_elems = 0, ksrc_elems = 0, out_bytes = 0;
+};
+
+YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err) {
+  auto *S = new YdSetScratch();
+  if (hipMalloc((void **)&S->d_count, (size_t)kYdSetMax * sizeof(uint32_t)) != hipSuccess) {
+    (void)hipGetLastError();
+    delete S;
+    *status = MI355_ERR_OUT_OF_MEMORY;
+    *err = "hipMalloc(yolodec set counters)";
+    return nullptr;
+  }
+  *status = MI355_OK;
+  return S;
+}
+
+void yolodec_set_scratch_free(YdSetScratch *S) {
+  if (!S) return;
+  if (S->d_count) (void)hipFree(S->d_count);
+  if (S->d_keys) (void)hipFree(S->d_keys);
+  if (S->d_kbox) (void)hipFree(S->d_kbox);
+  if (S->d_ksrc) (void)hipFree(S->d_ksrc);
+  if (S->d_out) (void)hipFree(S->d_out);
+  delete S;
+}
+
+// (hipFree waits for the device: a set still running on the queue's stream has finished with the old allocation)
+template <typename T>
+static bool set_grow(T **p, size_t *have, size_t want) {
+  if (*have >= want && *p) return true;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  if (hipMalloc((void **)p, want * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+  *have = want;
+  return true;
+}
+
+size_t yolodec_set_result_bytes(uint64_t records) { return kYdCountsBytes + (size_t)records * sizeof(mi355_yolo_det); }
+
+int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
+                       std::string *err) {
+  *kernel_launches = 0;
+  if (!S || !tensors || n < 1 || n > kYdSetMax) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
+  int layout[kYdSetMax];
+  uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], blocks[kYdSetMax];
+  uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax], totals[6];
+  for (int i = 0; i < n; i++) { layout[i] = tensors[i].layout; F[i] = tensors[i].num_fields; N[i] = tensors[i].num_candidates; cap[i] = tensors[i].max_dets; }
+  const int rc = yolodec_set_plan(n, layout, F, N, cap, first, blocks, key_off, box_off, det_off, totals);
+  if (rc) { *err = "yolodec: bad launch set"; return rc; }
+  if (totals[2] == 0) return MI355_OK;   // no job has a candidate: nothing to launch, nothing to copy
+  const size_t bytes = yolodec_set_result_bytes(totals[5]);
+  if (!h_block || h_block_bytes < bytes) { *err = "yolodec: the pinned result block is too small for the set"; return MI355_ERR_INVALID_ARG; }
+  if (!set_grow(&S->d_keys, &S->key_elems, (size_t)totals[3]) || !set_grow(&S->d_kbox, &S->kbox_elems, (size_t)totals[4]) ||
+      !set_grow(&S->d_ksrc, &S->ksrc_elems, (size_t)totals[4]) || !set_grow(&S->d_out, &S->out_bytes, bytes)) {
+    *err = "hipMalloc(yolodec set scratch)";
+    return MI355_ERR_OUT_OF_MEMORY;
+  }
+  if (!S->count_zero) {
+    if (hipMemsetAsync(S->d_count, 0, (size_t)kYdSetMax * sizeof(uint32_t), stream) != hipSuccess) { *err = "hipMemsetAsync(yolodec set counters)"; return MI355_ERR_HIP; }
+    S->count_zero = true;
+  }
+  YdJobTable score[2] = {}, nms = {};
+  uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out);
+  mi355_yolo_det *d_dets = reinterpret_cast<mi355_yolo_det *>(S->d_out + kYdCountsBytes);
+  for (int i = 0; i < n; i++) {
+    if (!N[i]) continue;   // no candidate: no job
+    YdJob J;
+    J.data = tensors[i].data;
+    J.count = S->d_count + i;
+    J.keys = S->d_keys + key_off[i];
+    J.kbox = S->d_kbox + box_off[i];
+    J.ksrc = S->d_ksrc + box_off[i];
+    J.dets = d_dets + det_off[i];
+    J.n_dets = d_n + i;
+    J.F = F[i];
+    J.N = N[i];
+    J.key_cap = pow2_at_least(N[i]);
+    J.max_dets = cap[i];
+    J.first_block = first[i];
+    J.blocks = blocks[i];
+    J.layout = layout[i];
+    J.p = tensors[i].p;
+    YdJobTable &T = score[layout[i] == MI355_YOLO_V8 ? 0 : 1];
+    T.job[T.n_jobs++] = J;
+    nms.job[nms.n_jobs++] = J;
+  }
+  S->count_zero = false;   // true again only once the NMS launch has been enqueued behind the score launches
+  for (int l = 0; l < 2; l++) {
+    if (!score[l].n_jobs) continue;
+    const dim3 grid((uint32_t)totals[l]);
+    if (l == 0) hipLaunchKernelGGL(yolodec_score_jobs_kernel<0>, grid, dim3(kScoreThreads), 0, stream, score[l]);
+    else hipLaunchKernelGGL(yolodec_score_jobs_kernel<1>, grid, dim3(kScoreThreads), 0, stream, score[l]);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { *err = std::string("yolodec score jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+    (*kernel_launches)++;
+  }
+  hipLaunchKernelGGL(yolodec_nms_jobs_kernel, dim3((uint32_t)nms.n_jobs), dim3(kNmsThreads), 0, stream, nms);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { *err = std::string("yolodec nms jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+  (*kernel_launches)++;
+  S->count_zero = true;
+  e = hipMemcpyAsync(h_block, S->d_out, bytes, hipMemcpyDeviceToHost, stream);
+  if (e != hipSuccess) { *err = std::string("yolodec set D2H: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+  return MI355_OK;
+}
+
 }  // namespace mi355
 
 using namespace mi355;
@@ -557,6 +799,11 @@ int mi355_yolodec_tensor(mi355_ctx *ctx, const float *data, int layout, uint32_t
 int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates) {
   const char *why = nullptr;
   return yolodec_check_args(tensor_pitch_bytes, n_tensors, layout, num_fields, num_candidates, &why);
+}
+
+int mi355_selftest_yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets,
+                                    uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]) {
+  return yolodec_set_plan(n_jobs, layout, num_fields, num_candidates, max_dets, first_block, blocks, key_offset, box_offset, det_offset, totals);
 }
 
 }  // extern "C"

@@ -41,6 +41,7 @@ FLAG_WINDOW_ORDER = 17
 FLAG_WINDOW_STATS = 18
 FLAG_DSSIM_FAST = 19
 HSVDETECT_SET_MAX = 32   # MI355_HSVDETECT_SET_MAX: detector frames per launch set of a Group
+YOLODEC_SET_MAX = 32     # MI355_YOLODEC_SET_MAX: decoder tensors per launch set of a Group
 MIXER_FRAME_TILE = 64    # MI355_MIXER_FRAME_TILE: frames per block of the mixer kernel
 
 
@@ -304,6 +305,11 @@ def load_library():
         "mi355_yolodec_tensor": (i, [vp, vp, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "mi355_yolodec_tensors_device": (i, [vp, vp, sz, i, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "mi355_selftest_yolodec_check": (i, [sz, i, i, C.c_uint32, C.c_uint32]),
+        "mi355_group_set_yolodec_rendezvous": (i, [vp, i, C.c_uint]),
+        "mi355_group_submit_yolodec": (i, [vp, vp, vp, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), C.c_uint32, C.POINTER(C.c_uint64)]),
+        "mi355_group_wait_yolodec": (i, [vp, C.c_uint64, vp, C.POINTER(C.c_uint32)]),
+        "mi355_group_yolodec_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_yolodec_set_plan": (i, [i, C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 5 + [C.POINTER(C.c_uint64)] * 4),
         "mi355_selftest_mixer_plan": (i, [i] + [C.POINTER(C.c_uint32)] * 4 + [C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint32)] * 4 + [C.c_uint32]
                                       + [C.POINTER(C.c_uint32)] * 3),
         "mi355_agroup_create_mixer": (vp, [i, i, C.POINTER(C.c_int)]),
@@ -465,6 +471,7 @@ class Group:
         if not self.h:
             raise Mi355Error(st.value, "mi355_group_create")
         self._rounds = {}
+        self._yolodec_caps = {}   # ticket -> the capacity its submit asked for (wait_yolodec sizes the result by it)
 
     def _ck(self, rc):
         if rc != 0:
@@ -584,10 +591,56 @@ class Group:
         self._ck(self.L.mi355_group_hsvdetect_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
+    # ---- yolov8tensordec2 / yoloxtensordec tensors of independent elements
+    def set_yolodec_rendezvous(self, expected_streams, linger_us):
+        self._ck(self.L.mi355_group_set_yolodec_rendezvous(self.h, expected_streams, linger_us))
+
+    def submit_yolodec(self, ctx, d_tensor, layout, num_fields, num_candidates, params, max_dets=None):
+        """One device tensor of stream `ctx` (layout "V8": [F, N], "X": [N, F]; params: (box_thr, class_thr, iou_thr), a YoloParams, or
+        None for a null pointer; max_dets: the capacity of the result, default N); returns the ticket."""
+        cap = num_candidates if max_dets is None else max_dets
+        p = None if params is None else _yolo_params(params)[0]
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_yolodec(self.h, None if ctx is None else ctx.h, d_tensor, YOLO_LAYOUT.get(layout, layout), num_fields, num_candidates, p,
+                                                   cap, C.byref(t)))
+        self._yolodec_caps[t.value] = cap
+        return t.value
+
+    def wait_yolodec(self, ticket):
+        """(records, count): the tensor's kept boxes as a YOLO_DET record array - the first min(count, max_dets) - and the full kept
+        count, as Context.yolodec_device returns them for one tensor."""
+        caps = self._yolodec_caps
+        cap = caps.get(ticket, 0)
+        dets = np.zeros(max(cap, 1), YOLO_DET)
+        n = C.c_uint32(0)
+        self._ck(self.L.mi355_group_wait_yolodec(self.h, ticket, dets.ctypes.data if cap else None, C.byref(n)))
+        caps.pop(ticket, None)
+        return dets[:min(n.value, cap)].copy(), n.value
+
+    def yolodec_stats(self):
+        """(tensors launched, launch sets, tensors in the largest set, kernel launches)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.L.mi355_group_yolodec_stats(self.h, c))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
     def close(self):
         if self.h:
             self.L.mi355_group_destroy(self.h)
             self.h = None
+
+
+def selftest_yolodec_set_plan(layouts, num_fields, num_candidates, max_dets):
+    """mi355_selftest_yolodec_set_plan (host only): the layout of one decoder launch set. Returns (status, first_block, blocks,
+    key_offset, box_offset, det_offset, totals); layouts: "V8" / "X" or the enum's ints."""
+    L = load_library()
+    n = len(layouts)
+    m = max(n, 1)
+    lay = (C.c_int * m)(*[YOLO_LAYOUT.get(v, v) for v in layouts])
+    F, N, cap = (C.c_uint32 * m)(*num_fields), (C.c_uint32 * m)(*num_candidates), (C.c_uint32 * m)(*max_dets)
+    first, blocks = (C.c_uint32 * m)(), (C.c_uint32 * m)()
+    key, box, det, totals = (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * 6)()
+    rc = L.mi355_selftest_yolodec_set_plan(n, lay, F, N, cap, first, blocks, key, box, det, totals)
+    return rc, list(first)[:n], list(blocks)[:n], list(key)[:n], list(box)[:n], list(det)[:n], list(totals)
 
 
 class AudioGroup:

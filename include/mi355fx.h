@@ -315,8 +315,9 @@ int mi355_group_compare_stats(mi355_group *group, uint64_t stats[3]);
  *           the call, and until wait_colordetect for its ticket has returned.
  *   wait   : launches what is pending if the frame has not gone out (rendezvous first), then waits for its launch set; the
  *           group's lock is not held meanwhile. A result is collected once. Tickets are one sequence per group: a ticket that is
- *           unknown, already collected, a filter frame's or a compare pair's is MI355_ERR_INVALID_ARG here and stays collectable
- *           where it belongs; mi355_group_wait, _order_after and _wait_compare refuse a colordetect ticket likewise.
+ *           unknown, already collected, a filter frame's, a compare pair's, a detector frame's or a decoder tensor's is
+ *           MI355_ERR_INVALID_ARG here and stays collectable where it belongs; mi355_group_wait, _order_after and _wait_compare
+ *           refuse a colordetect ticket likewise.
  *   set_colordetect_rendezvous : as set_rendezvous, counted over pending colordetect frames only. The compare queue's
  *           rendezvous, lanes and stats and this queue's do not touch each other.
  *   At most MI355_COLORDETECT_SET_MAX frames share a launch set; more go out as consecutive sets. flush, wait_all and destroy
@@ -355,8 +356,9 @@ int mi355_selftest_colordetect_plan(int n_cu, int n_jobs, const uint64_t *n_samp
  *           for the ticket has returned.
  *   wait   : launches what is pending if the frame has not gone out (rendezvous first), then waits for its launch set; the
  *           group's lock is not held meanwhile. A result is collected once. Tickets are one sequence per group: a ticket that is
- *           unknown, already collected or another queue's is MI355_ERR_INVALID_ARG here and stays collectable where it belongs;
- *           mi355_group_wait, _order_after, _wait_compare and _wait_colordetect refuse a detector ticket likewise.
+ *           unknown, already collected or another queue's (a decoder tensor's included) is MI355_ERR_INVALID_ARG here and stays
+ *           collectable where it belongs; mi355_group_wait, _order_after, _wait_compare and _wait_colordetect refuse a detector
+ *           ticket likewise.
  *   set_hsvdetect_rendezvous : as set_colordetect_rendezvous, counted over pending detector frames only. The other queues'
  *           rendezvous, streams and stats and this queue's do not touch each other.
  *   At most MI355_HSVDETECT_SET_MAX frames share a launch set; more go out as consecutive sets. flush, wait_all and destroy cover
@@ -940,6 +942,56 @@ int mi355_yolodec_tensors_device(mi355_ctx *ctx, const float *d_tensors, size_t 
                                  uint32_t num_fields, uint32_t num_candidates, const mi355_yolo_params *p, mi355_yolo_det *dets,
                                  uint32_t max_dets, uint32_t *n_dets);
 int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates);
+
+/* The tensor decoders across independent element instances. The reference element receives one tensor per buffer per instance
+ * (analytics/analytics/src/yolotensordec/imp.rs:234-422); N decoders in one process are N lone calls per frame period, each almost
+ * all launch, synchronisation and copy latency. submit_yolodec queues one device tensor of stream `ctx` and whatever is
+ * pending goes out as at most THREE launches over job tables in the kernel arguments, on the queue's own HIP stream, with ONE
+ * download of all counts and records. Members are fully independent: each tensor has its own shape (F, N), layout, three settings
+ * and output capacity. After wait_yolodec, dets and *n_dets hold exactly what mi355_yolodec_tensors_device(ctx, d_tensor,
+ * F * N * 4, 1, layout, F, N, p, dets, max_dets, n_dets) would have returned, byte for byte: the tie rule (ascending candidate
+ * index) makes the result independent of the order in which survivors were appended.
+ *   submit : never blocks; the checks and status codes are those of mi355_yolodec_tensors_device with n_tensors = 1 and a pitch of
+ *           F * N * 4 (layout, fields 6..1029, candidates 0..65536, a null or misaligned tensor with N > 0; a null group, ctx, p or
+ *           ticket: MI355_ERR_INVALID_ARG). A refused submit queues nothing. N = 0 is accepted, gets a ticket and yields 0
+ *           detections. The settings are copied at submit. The queue keeps room for min(max_dets, N) records for the tensor. The
+ *           tensor is read after what ctx's HIP stream held at the call (an event recorded on that stream when it holds work);
+ *           d_tensor is read until wait_yolodec for the ticket has returned.
+ *   wait   : launches what is pending if the tensor has not gone out (rendezvous first), then waits for its launch set; the
+ *           group's lock is not held meanwhile. Writes *n_dets (the kept count, even above max_dets) and the first
+ *           min(*n_dets, max_dets) records into dets, which must hold the submit's max_dets records (null only when that was 0;
+ *           a null n_dets or a null dets otherwise: MI355_ERR_INVALID_ARG, the result stays collectable). A result is collected
+ *           once. Tickets are one sequence per group: a ticket that is unknown, already collected or another queue's is
+ *           MI355_ERR_INVALID_ARG here and stays collectable where it belongs; mi355_group_wait, _order_after, _wait_compare,
+ *           _wait_colordetect and _wait_hsvdetect refuse a decoder ticket likewise.
+ *   set_yolodec_rendezvous : as set_hsvdetect_rendezvous, counted over pending tensors only. The other queues' rendezvous, streams
+ *           and stats and this queue's do not touch each other.
+ *   At most MI355_YOLODEC_SET_MAX tensors share a launch set; more go out as consecutive sets. Per set: the V8 score launch if a V8
+ *   tensor has a candidate, the X score launch likewise (kept apart: the X form's 33 KiB tile would halve the V8 form's occupancy),
+ *   one NMS launch for all tensors with candidates, one device-to-host copy. A set whose tensors all have N = 0 launches and copies
+ *   nothing. All scratch (counters, keys, kept boxes, result slabs) belongs to the queue and grows to the largest set seen; every set
+ *   in flight has a pinned result block of its own, and results move out of it when the set is collected, so a later, larger set
+ *   never overwrites what an earlier ticket still has to collect. flush, wait_all and destroy cover this queue as they cover the
+ *   others. A launch that fails is reported to the call that caused it and, once, to each tensor's own wait; the survivor counters
+ *   are cleared before the next set.
+ *   yolodec_stats : {tensors launched, launch sets, tensors in the largest set, kernel launches}.
+ *   mi355_selftest_yolodec_set_plan : host only, no device: the layout of one set, which the queue itself uses. Jobs keep submit
+ *           order. blocks[j] = ceil(N_j / 256); first_block[j] = the running sum of blocks over the earlier jobs of j's own layout;
+ *           key_offset = the running sum of the power of two at or above N_j (1 for N_j = 0) over all jobs; box_offset that of N_j;
+ *           det_offset that of min(max_dets_j, N_j). totals = {V8 blocks, X blocks, NMS blocks (jobs with N > 0), keys, boxes,
+ *           records}. Refused (MI355_ERR_INVALID_ARG): n_jobs outside 0..MI355_YOLODEC_SET_MAX, null arrays with n_jobs > 0, null
+ *           totals; a job mi355_selftest_yolodec_check(F * N * 4, 1, layout, F, N) refuses returns that status. */
+#define MI355_YOLODEC_SET_MAX 32 /* tensors per launch set */
+int mi355_group_set_yolodec_rendezvous(mi355_group *group, int expected_streams, unsigned linger_us);
+int mi355_group_submit_yolodec(mi355_group *group, mi355_ctx *ctx, const float *d_tensor, int layout, uint32_t num_fields,
+                               uint32_t num_candidates, const mi355_yolo_params *p, uint32_t max_dets, uint64_t *ticket);
+int mi355_group_wait_yolodec(mi355_group *group, uint64_t ticket, mi355_yolo_det *dets, uint32_t *n_dets);
+/* {tensors launched, launch sets, tensors in the largest set, kernel launches} */
+int mi355_group_yolodec_stats(mi355_group *group, uint64_t stats[4]);
+/* host only, no device: the layout of one launch set */
+int mi355_selftest_yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates,
+                                    const uint32_t *max_dets, uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset,
+                                    uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]);
 
 /* ---------------------------------------------------------------- agingradio
  * Replaces AgingRadio::process::<f32|f64> (audio/audiofx/src/agingradio/imp.rs:94-136): per pair of frames

@@ -20,11 +20,17 @@
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
 // Four more queues live beside the filter batches, each with its own HIP stream, pending list, rendezvous and stats, and none
-// touching another: videocompare pairs (submit_compare), colordetect frames (submit_colordetect), hsvdetector frames
-// (submit_hsvdetect: up to 32 frames of independent instances - own size, strides, formats, settings - as at most two launches
-// over a job table, hsv_kernels.hip) and decoder tensors (submit_yolodec: up to 32 tensors of independent yolov8tensordec2 /
+// touching another: videocompare pairs (submit_compare: its own code - classes, lanes, collection per lane) and three SET QUEUES,
+// which are one protocol written once (SetQueue<Kind>: submit's tail, flush in sets of up to 32 in submission order, the
+// lingering wait, collect-once results, retire, stats, destroy) with three kinds: colordetect frames (submit_colordetect),
+// hsvdetector frames (submit_hsvdetect: frames of independent instances - own size, strides, formats, settings - as at most two
+// launches over a job table, hsv_kernels.hip) and decoder tensors (submit_yolodec: tensors of independent yolov8tensordec2 /
 // yoloxtensordec instances - own shape, layout, settings - as at most three launches over job tables and one download,
-// yolodec.hip). Tickets are one sequence; a wait entry refuses a ticket of another queue.
+// yolodec.hip). A fourth kind is a struct beside CdKind / HdKind / YdKind - payload, result, kSetMax, its names, ensure, plan,
+// its pinned block (if any), launch, result, failed, destroy - a SetQueue<Kind> member of mi355_group, a line in
+// for_each_set_queue and its four entry points; nothing of the protocol is written again.
+// The group has ONE mutex, ticket sequence, event free list and last_error (GroupCore); every queue uses those. Tickets are one
+// sequence; a wait entry refuses a ticket of another queue.
 // No persistent kernel: nothing here can hang the GPU waiting for the host, a launch is a launch.
 #include "internal.hpp"
 
@@ -88,73 +94,535 @@ constexpr int kCmpMaxBatch = 32;                      // pairs per launch set (a
 constexpr int kCmpMaxLanes = 16;                      // HIP streams the pairs of one launch set are dealt out to
 constexpr size_t kCmpBlockBytes = 64 * 15 * 8 + 1024; // one pinned result block
 
-// ---- colordetect across independent element instances (mi355_group_submit_colordetect): one flat device plane per submit
-struct CdDesc {
-  CdFrame f;
-  uint64_t ticket;
-  hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing)
+// ---- what every queue of a group shares: ONE lock, ticket sequence, event free list and last_error
+struct GroupCore {
+  int device = 0;
+  std::mutex mu;
+  std::vector<hipEvent_t> events;  // free list
+  uint64_t next_ticket = 1;
+  std::string last_error;
 };
-struct CdOut { int status, n_colors; uint8_t rgb[255 * 3]; };
-struct CdSet {
-  uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
-  std::vector<uint64_t> tickets;
-  hipEvent_t done;
-  int waiters;
-  void *h_block;  // pinned: the set's results (colordetect_set_result)
-  bool collected = false;
-};
-constexpr int kCdBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
 
+hipEvent_t take_event(GroupCore *g) {
+  if (!g->events.empty()) { hipEvent_t e = g->events.back(); g->events.pop_back(); return e; }
+  hipEvent_t e = nullptr;
+  if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  return e;
+}
+
+int fail(GroupCore *g, int status, const std::string &msg) {
+  g->last_error = msg;
+  return status;
+}
+
+// What is submitted starts after what ctx's stream holds now (an upload, a filter, the table build): *ready is recorded there. A
+// stream that holds nothing - the common case for a stream that only ever submits here - needs no event (*ready = nullptr): every
+// cross-stream wait is a barrier packet the command processor resolves in microseconds, eight of them in front of a 90 us launch
+// are a bubble. g->mu held.
+int record_ready(GroupCore *g, mi355_ctx *ctx, hipEvent_t *ready) {
+  *ready = nullptr;
+  if (hipStreamQuery(ctx->stream) == hipSuccess) return MI355_OK;
+  (void)hipGetLastError();
+  hipEvent_t e = take_event(g);
+  if (!e || hipEventRecord(e, ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    if (e) g->events.push_back(e);
+    return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
+  }
+  *ready = e;
+  return MI355_OK;
+}
+
+// The host wait for the batch / set `seq` of `sets`. The lock is NOT held while waiting: other streams' threads keep submitting,
+// and `waiters` keeps the event from being recycled under the waiter. `lk` owns g->mu on entry and on return.
+enum class Waited { kNothing /* no such set: retired already */, kDone, kFailed };
+template <class S>
+Waited wait_seq_unlocking(std::deque<S> &sets, uint64_t seq, std::unique_lock<std::mutex> &lk) {
+  S *mine = nullptr;
+  for (S &s : sets)
+    if (s.seq == seq) { mine = &s; break; }
+  if (!mine) return Waited::kNothing;
+  const hipEvent_t ev = mine->done;
+  mine->waiters++;
+  lk.unlock();
+  const hipError_t e = hipEventSynchronize(ev);
+  lk.lock();
+  for (S &s : sets)
+    if (s.seq == seq) { s.waiters--; break; }
+  if (e != hipSuccess) { (void)hipGetLastError(); return Waited::kFailed; }
+  return Waited::kDone;
+}
+
+// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its three kinds
+// A kind is what differs between the queues: what is submitted (Payload), what a wait takes (Result), what a launch reads (Plan),
+// what a set in flight owns (SetData), how a set is launched and read back, and the resources of first use. The protocol is below.
+
+template <class Payload>
+struct QItem {
+  Payload p;
+  uint64_t ticket;
+  hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing, or nothing will be read)
+};
+
+int queue_stream(GroupCore *g, hipStream_t *stream, const char *name) {
+  if (*stream) return MI355_OK;
+  if (hipStreamCreateWithFlags(stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    *stream = nullptr;
+    return fail(g, MI355_ERR_HIP, std::string("group: no stream for the ") + name + " queue");
+  }
+  return MI355_OK;
+}
+
+int device_cus(int device) {
+  int n_cu = 0;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) (void)hipGetLastError();
+  return n_cu > 0 ? n_cu : 256;
+}
+
+// ---- colordetect across independent element instances (mi355_group_submit_colordetect): one flat device plane per submit; its
+// palette comes back through the set's pinned block. Consecutive sets on the queue's stream share the device scratch.
+struct CdOut { int status, n_colors; uint8_t rgb[255 * 3]; };
+constexpr int kCdBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
+struct CdKind {
+  using Payload = CdFrame;
+  using Result = CdOut;
+  struct Plan { CdFrame frames[kCdSetMax]; };
+  struct SetData { void *h_block = nullptr; };  // pinned: the set's results (colordetect_set_result) until it is collected
+  static constexpr int kSetMax = kCdSetMax;
+  static constexpr const char *kName = "colordetect", *kItem = "colordetect frame", *kWaitEntry = "mi355_group_wait_colordetect";
+  hipStream_t stream = nullptr;
+  CdSetScratch *scratch = nullptr;
+  int n_cu = 256;
+  std::vector<void *> blocks;  // free pinned result blocks, all of colordetect_set_block_bytes()
+
+  bool set_up() const { return scratch != nullptr; }
+  // stream, device scratch and the first pinned blocks: at the first submit, never inside a launch set. The blocks have one size,
+  // so four are made here - the sets a stream of submits has in flight before anybody collects - and a launch set allocates only
+  // when more sets are in flight than ever before.
+  int ensure(GroupCore *g) {
+    if (scratch) return MI355_OK;
+    n_cu = device_cus(g->device);
+    if (int rc = queue_stream(g, &stream, kName)) return rc;
+    while ((int)blocks.size() < kCdBlocksAtFirstUse) {
+      void *b = nullptr;
+      if (hipHostMalloc(&b, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the colordetect queue");
+      }
+      blocks.push_back(b);
+    }
+    int st = MI355_OK;
+    std::string err;
+    scratch = colordetect_set_scratch_new(stream, &st, &err);
+    return scratch ? MI355_OK : fail(g, st, "group: " + err);
+  }
+  int plan(const QItem<CdFrame> *take, size_t n, Plan *p, std::string *) const {
+    for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
+    return MI355_OK;
+  }
+  bool no_free_block(const Plan &) const { return blocks.empty(); }
+  bool take_block(const Plan &, SetData *d) {
+    if (!blocks.empty()) { d->h_block = blocks.back(); blocks.pop_back(); }
+    // (more sets in flight than ever before: one more block, kept from then on)
+    else if (hipHostMalloc(&d->h_block, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); d->h_block = nullptr; }
+    return d->h_block != nullptr;
+  }
+  static bool holds_block(const SetData &d) { return d.h_block != nullptr; }
+  void release(SetData *d) {
+    if (d->h_block) blocks.push_back(d->h_block);
+    d->h_block = nullptr;
+  }
+  int launch(const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
+    return colordetect_launch_set(scratch, stream, n_cu, p.frames, (int)n, d->h_block, launches, err);
+  }
+  void launched(const GroupCore *, const Plan &, size_t) const {}
+  void result(const SetData &d, size_t i, CdOut *o) const {
+    o->status = MI355_OK;
+    colordetect_set_result(d.h_block, (int)i, o->rgb, &o->n_colors);
+  }
+  static void failed(const CdFrame &, int rc, CdOut *o) { o->status = rc; o->n_colors = 0; }
+  static int status(const CdOut &o) { return o.status; }
+  void destroy() {
+    colordetect_set_scratch_free(scratch);
+    (void)hipStreamDestroy(stream);
+    for (void *b : blocks) (void)hipHostFree(b);
+  }
+};
 
 // ---- hsvdetector across independent element instances (mi355_group_submit_hsvdetect): one device frame per submit, written in
-// place on the device - nothing comes back but the launch's status
-struct HdDesc {
-  HdFrame f;
-  uint64_t ticket;
-  hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing)
-};
-struct HdSet {
-  uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
-  std::vector<uint64_t> tickets;
-  hipEvent_t done;
-  int waiters;
-  bool collected = false;
+// place on the device - nothing comes back but the launch's status, so a set owns NO pinned block and the queue no scratch.
+struct HdKind {
+  using Payload = HdFrame;
+  using Result = int;  // the status
+  struct Plan { HdFrame frames[kHdSetMax]; };
+  struct SetData {};
+  static constexpr int kSetMax = kHdSetMax;
+  static constexpr const char *kName = "hsvdetector", *kItem = "hsvdetector frame", *kWaitEntry = "mi355_group_wait_hsvdetect";
+  hipStream_t stream = nullptr;
+  int n_cu = 256;
+
+  bool set_up() const { return stream != nullptr; }
+  // the queue's stream is all it has, so first use is keyed on it: at the first submit, never inside a launch set
+  int ensure(GroupCore *g) {
+    if (stream) return MI355_OK;
+    n_cu = device_cus(g->device);
+    return queue_stream(g, &stream, kName);
+  }
+  int plan(const QItem<HdFrame> *take, size_t n, Plan *p, std::string *) const {
+    for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
+    return MI355_OK;
+  }
+  bool no_free_block(const Plan &) const { return false; }
+  bool take_block(const Plan &, SetData *) const { return true; }
+  static bool holds_block(const SetData &) { return false; }
+  void release(SetData *) const {}
+  int launch(const Plan &p, size_t n, SetData *, int *launches, std::string *err) { return hsvdetect_launch_set(stream, n_cu, p.frames, (int)n, launches, err); }
+  // what the element behind finds on-die, as the lone entry records it: every destination with a pixel, once the set has gone out
+  void launched(const GroupCore *g, const Plan &p, size_t n) const {
+    for (size_t i = 0; i < n; i++) {
+      const HdFrame &f = p.frames[i];
+      if (f.width > 0 && f.height > 0) note_written(g->device, f.dst, (size_t)f.dst_stride * (size_t)f.height);
+    }
+  }
+  void result(const SetData &, size_t, int *o) const { *o = MI355_OK; }
+  static void failed(const HdFrame &, int rc, int *o) { *o = rc; }
+  static int status(int o) { return o; }
+  void destroy() { (void)hipStreamDestroy(stream); }
 };
 
 // ---- yolov8tensordec2 / yoloxtensordec across independent element instances (mi355_group_submit_yolodec): one device tensor per
-// submit; its kept count and records come back through the set's pinned block
-struct YdDesc {
-  YdTensor t;
-  uint64_t ticket;
-  hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing, or no candidate to read)
-};
+// submit; its kept count and records come back through the set's pinned block. Consecutive sets share the device scratch.
 struct YdOut { int status; uint32_t n_dets, max_dets; std::vector<mi355_yolo_det> dets; };   // dets: the first min(n_dets, max_dets)
 struct YdBlock { void *h; size_t bytes; };   // a pinned result block
-struct YdSlot { uint64_t ticket; uint32_t num_candidates, max_dets; uint64_t det_offset; };
-struct YdSet {
-  uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
-  std::vector<YdSlot> slots;   // its tensors, by job
-  hipEvent_t done;
-  int waiters;
-  YdBlock block;     // the set's own results until it is collected (h == nullptr: no tensor had a candidate)
-  bool collected = false;
+struct YdSlot { uint32_t num_candidates, max_dets; uint64_t det_offset; };
+struct YdKind {
+  using Payload = YdTensor;
+  using Result = YdOut;
+  struct Plan { YdTensor tensors[kYdSetMax]; uint64_t det_off[kYdSetMax], totals[6]; };
+  struct SetData {
+    YdBlock block{nullptr, 0};   // the set's own results until it is collected (h == nullptr: no tensor had a candidate)
+    std::vector<YdSlot> slots;   // its tensors, by job (as the set's tickets are)
+  };
+  static constexpr int kSetMax = kYdSetMax;
+  static constexpr const char *kName = "decoder", *kItem = "decoder tensor", *kWaitEntry = "mi355_group_wait_yolodec";
+  hipStream_t stream = nullptr;
+  YdSetScratch *scratch = nullptr;
+  std::vector<YdBlock> blocks;  // free pinned result blocks
+
+  // flush, wait_all and destroy launch for this queue only once the scratch exists: a stream alone (the scratch could not be made)
+  // has accepted nothing
+  bool set_up() const { return scratch != nullptr; }
+  // the queue's stream and scratch: at the first submit, never inside a launch set
+  int ensure(GroupCore *g) {
+    if (scratch) return MI355_OK;
+    if (int rc = queue_stream(g, &stream, kName)) return rc;
+    int st = MI355_OK;
+    std::string err;
+    scratch = yolodec_set_scratch_new(&st, &err);
+    return scratch ? MI355_OK : fail(g, st, "group: " + err);
+  }
+  // the set's layout, before anything is taken for it: the plan the launch itself uses says how large the set's block has to be
+  int plan(const QItem<YdTensor> *take, size_t n, Plan *p, std::string *err) const {
+    int layout[kYdSetMax];
+    uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], n_blocks[kYdSetMax];
+    uint64_t key_off[kYdSetMax], box_off[kYdSetMax];
+    for (size_t i = 0; i < n; i++) {
+      const YdTensor &t = p->tensors[i] = take[i].p;
+      layout[i] = t.layout; F[i] = t.num_fields; N[i] = t.num_candidates; cap[i] = t.max_dets;
+    }
+    for (uint64_t &t : p->totals) t = 0;
+    const int rc = yolodec_set_plan((int)n, layout, F, N, cap, first, n_blocks, key_off, box_off, p->det_off, p->totals);
+    if (rc) *err = "group: bad decoder set";
+    return rc;
+  }
+  // a set without a candidate has nothing to copy: it takes no block (and still gets its event and its set)
+  bool no_free_block(const Plan &p) const { return p.totals[2] && blocks.empty(); }
+  // The sets' results differ in size by orders of magnitude (min(max_dets, N) records per tensor), so blocks are sized: a free one
+  // that is large enough, else a new one - and a free one that is too small makes room, or the pool would keep every size it saw.
+  bool take_block(const Plan &p, SetData *d) {
+    if (!p.totals[2]) return true;
+    const size_t bytes = yolodec_set_result_bytes(p.totals[5]);
+    for (size_t i = 0; i < blocks.size(); i++)
+      if (blocks[i].bytes >= bytes) {
+        d->block = blocks[i];
+        blocks.erase(blocks.begin() + (std::ptrdiff_t)i);
+        return true;
+      }
+    if (!blocks.empty()) {
+      (void)hipHostFree(blocks.back().h);
+      blocks.pop_back();
+    }
+    const size_t want = (bytes + 4095) / 4096 * 4096;
+    if (hipHostMalloc(&d->block.h, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); d->block.h = nullptr; return false; }
+    d->block.bytes = want;
+    return true;
+  }
+  static bool holds_block(const SetData &d) { return d.block.h != nullptr; }
+  void release(SetData *d) {
+    if (d->block.h) blocks.push_back(d->block);
+    d->block = YdBlock{nullptr, 0};
+  }
+  int launch(const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
+    for (size_t i = 0; i < n; i++) d->slots.push_back(YdSlot{p.tensors[i].num_candidates, p.tensors[i].max_dets, p.det_off[i]});
+    return yolodec_launch_set(scratch, stream, p.tensors, (int)n, d->block.h, d->block.bytes, launches, err);
+  }
+  void launched(const GroupCore *, const Plan &, size_t) const {}
+  // counts and records MOVE out of the pinned block: a later, larger set cannot overwrite what an earlier ticket has not collected
+  void result(const SetData &d, size_t i, YdOut *o) const {
+    const uint32_t *h_n = static_cast<const uint32_t *>(d.block.h);
+    const mi355_yolo_det *h_dets = d.block.h ? reinterpret_cast<const mi355_yolo_det *>(static_cast<const uint8_t *>(d.block.h) + kYdCountsBytes) : nullptr;
+    const YdSlot &sl = d.slots[i];
+    o->status = MI355_OK;
+    o->max_dets = sl.max_dets;
+    o->n_dets = sl.num_candidates && h_n ? h_n[i] : 0;   // a tensor without candidates had no job
+    const uint32_t cap = sl.max_dets < sl.num_candidates ? sl.max_dets : sl.num_candidates;
+    const uint32_t w = o->n_dets < cap ? o->n_dets : cap;
+    if (w) o->dets.assign(h_dets + sl.det_offset, h_dets + sl.det_offset + w);
+  }
+  static void failed(const YdTensor &t, int rc, YdOut *o) { o->status = rc; o->n_dets = 0; o->max_dets = t.max_dets; }
+  static int status(const YdOut &o) { return o.status; }
+  void destroy() {
+    yolodec_set_scratch_free(scratch);
+    (void)hipStreamDestroy(stream);
+    for (YdBlock &b : blocks) (void)hipHostFree(b.h);
+  }
+};
+
+// ---- the protocol, once. Every method runs with g->mu held.
+template <class Kind>
+struct SetQueue {
+  using Item = QItem<typename Kind::Payload>;
+  using Result = typename Kind::Result;
+  struct Set {
+    uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
+    std::vector<uint64_t> tickets;
+    hipEvent_t done;
+    int waiters;
+    typename Kind::SetData data;
+    bool collected = false;
+  };
+  Kind kind;                     // the queue's own stream, scratch and blocks: made at the first submit (Kind::ensure)
+  std::vector<Item> pending;
+  std::deque<Set> sets;          // launched, oldest first
+  std::unordered_map<uint64_t, uint64_t> where;   // ticket -> seq
+  std::unordered_map<uint64_t, Result> results;   // finished (or failed), not yet collected by the queue's wait entry
+  uint64_t next_seq = 1;
+  uint64_t n_items = 0, n_sets = 0, n_largest = 0, n_launches = 0;
+  int expected = 0;              // rendezvous: a waiter lingers until this many items are pending ...
+  unsigned linger_us = 0;        // ... or this long
+  std::condition_variable cv;    // "a set has been launched"
+
+  bool is_pending(uint64_t ticket) const {
+    for (const Item &d : pending)
+      if (d.ticket == ticket) return true;
+    return false;
+  }
+
+  // is `ticket` an item of this queue that has not been collected?
+  bool owns(uint64_t ticket) const { return where.count(ticket) || results.count(ticket) || is_pending(ticket); }
+
+  // what an entry point that serves another queue says to a ticket this queue owns
+  static std::string foreign_refusal() { return std::string("group: a ") + Kind::kItem + "'s ticket (" + Kind::kWaitEntry + " collects it)"; }
+
+  // a finished set: its results into `results` (once); nothing reads its pinned block afterwards, so the block is free again
+  void collect(Set &s) {
+    if (s.collected) return;
+    s.collected = true;
+    if (results.size() > 65536) results.clear();   // (results nobody ever collected)
+    for (size_t i = 0; i < s.tickets.size(); i++) {
+      kind.result(s.data, i, &results[s.tickets[i]]);
+      where.erase(s.tickets[i]);
+    }
+    kind.release(&s.data);
+  }
+
+  // collected sets nobody waits inside leave: the event goes back to the free list
+  void retire(GroupCore *g) {
+    for (auto it = sets.begin(); it != sets.end();) {
+      if (it->collected && it->waiters == 0) {
+        g->events.push_back(it->done);
+        it = sets.erase(it);
+      } else {
+        ++it;
+      }
+    }
+  }
+
+  // finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
+  void retire_done(GroupCore *g) {
+    for (Set &s : sets) {
+      if (s.collected) continue;
+      if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
+      collect(s);
+    }
+    retire(g);
+  }
+
+  // launches the pending items in submission order, kSetMax to a set (all of them, or up to the set that carries `until`), as
+  // consecutive sets on the queue's stream. A set that fails is told to each ticket it carried, once, through `results`; the
+  // flush goes on to the next set and returns the first failure.
+  int flush_locked(GroupCore *g, uint64_t until = 0) {
+    bool reached = false;
+    int first_rc = MI355_OK;
+    while (!pending.empty() && !reached) {
+      const size_t n = std::min(pending.size(), (size_t)Kind::kSetMax);
+      std::vector<Item> take(pending.begin(), pending.begin() + (std::ptrdiff_t)n);
+      pending.erase(pending.begin(), pending.begin() + (std::ptrdiff_t)n);
+      int launches = 0;
+      std::string err;
+      typename Kind::Plan plan;
+      typename Kind::SetData data;
+      int rc = kind.plan(take.data(), n, &plan, &err);
+      hipEvent_t done = take_event(g);
+      if (!rc) {
+        if (kind.no_free_block(plan)) retire_done(g);   // (a finished set nobody has collected gives its block back)
+        if (!kind.take_block(plan, &data) || !done) { rc = MI355_ERR_HIP; err = std::string("group: no event or pinned block for a ") + Kind::kName + " set"; }
+      }
+      for (const Item &d : take)
+        if (!rc && d.ready && hipStreamWaitEvent(kind.stream, d.ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = std::string("hipStreamWaitEvent(") + Kind::kItem + ")"; }
+      if (!rc) rc = kind.launch(plan, n, &data, &launches, &err);
+      if (!rc && hipEventRecord(done, kind.stream) != hipSuccess) { rc = MI355_ERR_HIP; err = std::string("hipEventRecord(") + Kind::kName + " set)"; }
+      for (const Item &d : take)
+        if (d.ready) g->events.push_back(d.ready);
+      if (rc) {
+        (void)hipGetLastError();
+        if (done) g->events.push_back(done);
+        if (Kind::holds_block(data)) {
+          // what did go out may still write the block: it is free again only behind the queue's stream
+          (void)hipStreamSynchronize(kind.stream);
+          (void)hipGetLastError();
+          kind.release(&data);
+        }
+        g->last_error = std::string("group: ") + Kind::kName + " launch failed: " + err;
+        if (results.size() > 65536) results.clear();
+        for (const Item &d : take) Kind::failed(d.p, rc, &results[d.ticket]);   // told to the item's own wait, once
+        if (!first_rc) first_rc = rc;
+        continue;
+      }
+      kind.launched(g, plan, n);
+      Set s{next_seq++, {}, done, 0, std::move(data)};
+      for (const Item &d : take) { s.tickets.push_back(d.ticket); where[d.ticket] = s.seq; reached |= until != 0 && d.ticket == until; }
+      sets.push_back(std::move(s));
+      n_items += n;
+      n_sets++;
+      if (n > n_largest) n_largest = n;
+      n_launches += (uint64_t)launches;
+    }
+    cv.notify_all();
+    return first_rc;
+  }
+
+  // host wait for the set of `ticket`, and with it - the queue's stream being in order - for every earlier one; `lk` owns g->mu on
+  // entry and on return, not while waiting
+  int wait_unlocking(GroupCore *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
+    auto it = where.find(ticket);
+    if (it == where.end()) return MI355_OK;  // collected already (or failed: `results` has it)
+    const uint64_t seq = it->second;
+    const Waited w = wait_seq_unlocking(sets, seq, lk);
+    if (w == Waited::kNothing) return MI355_OK;
+    if (w == Waited::kFailed) return fail(g, MI355_ERR_HIP, std::string("hipEventSynchronize(group ") + Kind::kName + " set)");
+    for (Set &s : sets)
+      if (s.seq <= seq) collect(s);
+    retire(g);
+    return MI355_OK;
+  }
+
+  // waits for every set launched so far (their results stay collectable)
+  int wait_all_unlocking(GroupCore *g, std::unique_lock<std::mutex> &lk) {
+    uint64_t last = 0;
+    for (const Set &s : sets)
+      if (!s.collected) last = s.tickets.front();
+    return last ? wait_unlocking(g, lk, last) : MI355_OK;
+  }
+
+  void set_rendezvous(int expected_streams, unsigned linger) {
+    expected = expected_streams;
+    linger_us = linger;
+  }
+
+  // the tail of a submit, behind the entry point's own checks of the payload; want_ready: false for an item nothing will read
+  int submit(GroupCore *g, mi355_ctx *ctx, const typename Kind::Payload &p, bool want_ready, uint64_t *ticket) {
+    if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
+    if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+    if (int rc = kind.ensure(g)) return rc;
+    retire_done(g);
+    Item d{p, 0, nullptr};
+    if (want_ready)
+      if (int rc = record_ready(g, ctx, &d.ready)) return rc;
+    d.ticket = g->next_ticket++;
+    *ticket = d.ticket;
+    pending.push_back(d);
+    // everybody is here (rendezvous), or a launch set is full: go. The item has been accepted whatever that launch does (a failure
+    // is told to the waits of the items it carried).
+    const int full = expected > 0 && expected < Kind::kSetMax ? expected : Kind::kSetMax;
+    if ((int)pending.size() >= full) (void)flush_locked(g);
+    return MI355_OK;
+  }
+
+  // the body of a wait: *out is the item's result, taken out of `results` - once
+  int wait(GroupCore *g, std::unique_lock<std::mutex> &lk, uint64_t ticket, Result *out) {
+    // another queue's, a collected or an unknown ticket: refused before anything is launched or waited for
+    if (!owns(ticket)) return fail(g, MI355_ERR_INVALID_ARG, std::string("group: not the ticket of a ") + Kind::kItem + " that is still to be collected");
+    if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+    if (is_pending(ticket)) {
+      // rendezvous: the other instances of this interval are about to submit - linger for them (bounded), then launch what is there
+      if (expected > 0 && linger_us > 0) {
+        const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(linger_us);
+        while (is_pending(ticket) && (int)pending.size() < expected) {
+          if (cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
+        }
+      }
+      if (is_pending(ticket)) (void)flush_locked(g, ticket);   // (a failure of this item's own launch is in `results`)
+    }
+    if (int rc = wait_unlocking(g, lk, ticket)) return rc;
+    auto r = results.find(ticket);
+    if (r == results.end()) return fail(g, MI355_ERR_INVALID_ARG, std::string("group: this ") + Kind::kItem + "'s result has been collected already");   // (by a concurrent wait)
+    *out = std::move(r->second);
+    results.erase(r);
+    if (const int status = Kind::status(*out)) return fail(g, status, std::string("group: the launch that carried this ") + Kind::kItem + " failed");
+    return MI355_OK;
+  }
+
+  void stats(uint64_t out[4]) const {
+    out[0] = n_items;
+    out[1] = n_sets;
+    out[2] = n_largest;
+    out[3] = n_launches;
+  }
+
+  // The queue's part of mi355_group_destroy (takes g->mu itself): items still pending are launched and waited for, as pairs are -
+  // their buffers belong to callers who may free them once destroy returns, and a detector's destination is complete by then.
+  void destroy(GroupCore *g) {
+    if (!kind.stream) return;
+    if (kind.set_up()) {
+      std::lock_guard<std::mutex> lk(g->mu);
+      (void)flush_locked(g);
+    }
+    (void)hipStreamSynchronize(kind.stream);
+    for (Set &s : sets) {
+      (void)hipEventDestroy(s.done);
+      kind.release(&s.data);
+    }
+    sets.clear();
+    for (Item &d : pending)
+      if (d.ready) (void)hipEventDestroy(d.ready);
+    pending.clear();
+    kind.destroy();
+  }
 };
 
 }  // namespace
 
-struct mi355_group {
-  int device = 0;
+struct mi355_group : GroupCore {
   int max_batch = 8;
   hipStream_t stream = nullptr;
-  std::mutex mu;
   std::vector<Desc> pending;
   std::deque<Batch> batches;       // launched, oldest first
-  std::vector<hipEvent_t> events;  // free list
   std::unordered_map<uint64_t, uint64_t> where;  // ticket -> seq of its batch, for launched batches not yet retired
   std::unordered_map<uint64_t, int> failed;      // ticket -> status of the launch that did not happen (reported by wait / order_after)
-  uint64_t next_ticket = 1, next_seq = 1;
+  uint64_t next_seq = 1;
   uint64_t n_frames = 0, n_batched_launch_pairs = 0, n_single = 0;
-  std::string last_error;
   // table references of retired batches: dropping the last reference to a table frees 64 MiB behind a device-wide wait, which
   // does not belong under `mu` - the entry points empty this list into a local one that dies after they have unlocked (Locked)
   std::vector<std::shared_ptr<void>> dead_refs;
@@ -176,45 +644,11 @@ struct mi355_group {
   int expected_streams = 0;                  // rendezvous: a waiter lingers until this many pairs are pending ...
   unsigned linger_us = 0;                    // ... or this long (mi355_group_set_rendezvous)
   std::condition_variable cv;                // "a compare batch has been launched"
-  // ---- colordetect queue: its own stream and scratch (created at the first submit), independent of the two queues above
-  hipStream_t cd_stream = nullptr;
-  CdSetScratch *cd_scratch = nullptr;
-  int cd_n_cu = 256;
-  std::vector<CdDesc> cd_pending;
-  std::deque<CdSet> cd_sets;                 // launched, oldest first
-  std::unordered_map<uint64_t, uint64_t> cd_where;   // ticket -> seq
-  std::unordered_map<uint64_t, CdOut> cd_results;    // finished (or failed), not yet collected by mi355_group_wait_colordetect
-  std::vector<void *> cd_blocks;             // free pinned result blocks
-  uint64_t next_cd_seq = 1;
-  uint64_t n_cd_frames = 0, n_cd_sets = 0, n_cd_largest = 0, n_cd_launches = 0;
-  int cd_expected = 0;                       // rendezvous over pending colordetect frames (mi355_group_set_colordetect_rendezvous)
-  unsigned cd_linger_us = 0;
-  std::condition_variable cd_cv;             // "a colordetect set has been launched"
-  // ---- hsvdetector queue: its own stream (created at the first submit), independent of the three queues above
-  hipStream_t hd_stream = nullptr;
-  int hd_n_cu = 256;
-  std::vector<HdDesc> hd_pending;
-  std::deque<HdSet> hd_sets;                 // launched, oldest first
-  std::unordered_map<uint64_t, uint64_t> hd_where;   // ticket -> seq
-  std::unordered_map<uint64_t, int> hd_results;      // status of frames finished (or failed), not yet collected by mi355_group_wait_hsvdetect
-  uint64_t next_hd_seq = 1;
-  uint64_t n_hd_frames = 0, n_hd_sets = 0, n_hd_largest = 0, n_hd_launches = 0;
-  int hd_expected = 0;                       // rendezvous over pending detector frames (mi355_group_set_hsvdetect_rendezvous)
-  unsigned hd_linger_us = 0;
-  std::condition_variable hd_cv;             // "a detector set has been launched"
-  // ---- decoder queue: its own stream and scratch (created at the first submit), independent of the four queues above
-  hipStream_t yd_stream = nullptr;
-  YdSetScratch *yd_scratch = nullptr;
-  std::vector<YdDesc> yd_pending;
-  std::deque<YdSet> yd_sets;                 // launched, oldest first
-  std::unordered_map<uint64_t, uint64_t> yd_where;   // ticket -> seq
-  std::unordered_map<uint64_t, YdOut> yd_results;    // finished (or failed), not yet collected by mi355_group_wait_yolodec
-  std::vector<YdBlock> yd_blocks;            // free pinned result blocks
-  uint64_t next_yd_seq = 1;
-  uint64_t n_yd_tensors = 0, n_yd_sets = 0, n_yd_largest = 0, n_yd_launches = 0;
-  int yd_expected = 0;                       // rendezvous over pending tensors (mi355_group_set_yolodec_rendezvous)
-  unsigned yd_linger_us = 0;
-  std::condition_variable yd_cv;             // "a decoder set has been launched"
+  // ---- the three set queues: each its own stream (and scratch, and blocks), created at its first submit, independent of the
+  // two queues above and of each other
+  SetQueue<CdKind> cd;   // colordetect frames
+  SetQueue<HdKind> hd;   // hsvdetector frames
+  SetQueue<YdKind> yd;   // decoder tensors
 };
 
 namespace {
@@ -247,18 +681,6 @@ void retire_done(mi355_group *g) {
     if (hipEventQuery(g->batches.front().done) != hipSuccess) { (void)hipGetLastError(); break; }
     retire_front(g);
   }
-}
-
-hipEvent_t take_event(mi355_group *g) {
-  if (!g->events.empty()) { hipEvent_t e = g->events.back(); g->events.pop_back(); return e; }
-  hipEvent_t e = nullptr;
-  if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  return e;
-}
-
-int fail(mi355_group *g, int status, const std::string &msg) {
-  g->last_error = msg;
-  return status;
 }
 
 bool same_class(const Desc &a, const Desc &b) {
@@ -347,18 +769,9 @@ int wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ti
   auto it = g->where.find(ticket);
   if (it == g->where.end()) return MI355_OK;  // launched and already retired (by this or another waiter)
   const uint64_t seq = it->second;
-  Batch *mine = nullptr;
-  for (Batch &b : g->batches)
-    if (b.seq == seq) { mine = &b; break; }
-  if (!mine) return MI355_OK;
-  const hipEvent_t ev = mine->done;
-  mine->waiters++;
-  lk.unlock();
-  const hipError_t e = hipEventSynchronize(ev);
-  lk.lock();
-  for (Batch &b : g->batches)
-    if (b.seq == seq) { b.waiters--; break; }
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group batch)"); }
+  const Waited w = wait_seq_unlocking(g->batches, seq, lk);
+  if (w == Waited::kNothing) return MI355_OK;
+  if (w == Waited::kFailed) return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group batch)");
   // everything up to that batch is done: retire from the front (batches somebody still waits in stay until they leave)
   while (!g->batches.empty() && g->batches.front().seq <= seq && g->batches.front().waiters == 0) retire_front(g);
   return MI355_OK;
@@ -507,506 +920,37 @@ int cmp_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_
   auto it = g->cmp_where.find(ticket);
   if (it == g->cmp_where.end()) return MI355_OK;  // collected already (or failed: cmp_results has it)
   const uint64_t seq = it->second;
-  CmpBatch *mine = nullptr;
-  for (CmpBatch &b : g->cmp_batches)
-    if (b.seq == seq) { mine = &b; break; }
-  if (!mine) return MI355_OK;
-  const hipEvent_t ev = mine->done;
-  const int lane = mine->lane;
-  mine->waiters++;
-  lk.unlock();
-  const hipError_t e = hipEventSynchronize(ev);
-  lk.lock();
-  for (CmpBatch &b : g->cmp_batches)
-    if (b.seq == seq) { b.waiters--; break; }
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group compare batch)"); }
-  // a lane's stream is in order: everything of that lane up to this batch is done
+  const Waited w = wait_seq_unlocking(g->cmp_batches, seq, lk);
+  if (w == Waited::kNothing) return MI355_OK;
+  if (w == Waited::kFailed) return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group compare batch)");
+  // a lane's stream is in order: everything of that lane up to this batch is done (the batch itself is still here: none
+  // retires while somebody waits inside it)
+  int lane = -1;
+  for (const CmpBatch &b : g->cmp_batches)
+    if (b.seq == seq) lane = b.lane;
   for (CmpBatch &b : g->cmp_batches)
     if (b.lane == lane && b.seq <= seq) cmp_collect(g, b);
   cmp_retire(g);
   return MI355_OK;
 }
 
-// ------------------------------------------------------------------ colordetect queue
+// ------------------------------------------------------------------ the set queues, where an entry point names them all
 
-// is `ticket` a colordetect frame that has not been collected?
-bool cd_owns(mi355_group *g, uint64_t ticket) {
-  if (g->cd_where.count(ticket) || g->cd_results.count(ticket)) return true;
-  for (const CdDesc &d : g->cd_pending)
-    if (d.ticket == ticket) return true;
-  return false;
+// f(queue) for each, in the order flush, wait_all and destroy go through them
+template <class F>
+void for_each_set_queue(mi355_group *g, F &&f) {
+  f(g->cd);
+  f(g->hd);
+  f(g->yd);
 }
 
-// stream, device scratch and the first pinned blocks: at the first submit, never inside a launch set. g->mu held.
-int cd_ensure(mi355_group *g) {
-  if (g->cd_scratch) return MI355_OK;
-  int n_cu = 0;
-  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) (void)hipGetLastError();
-  g->cd_n_cu = n_cu > 0 ? n_cu : 256;
-  if (!g->cd_stream && hipStreamCreateWithFlags(&g->cd_stream, hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    g->cd_stream = nullptr;
-    return fail(g, MI355_ERR_HIP, "group: no stream for the colordetect queue");
-  }
-  while ((int)g->cd_blocks.size() < kCdBlocksAtFirstUse) {
-    void *b = nullptr;
-    if (hipHostMalloc(&b, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the colordetect queue");
-    }
-    g->cd_blocks.push_back(b);
-  }
-  int st = MI355_OK;
-  std::string err;
-  g->cd_scratch = colordetect_set_scratch_new(g->cd_stream, &st, &err);
-  return g->cd_scratch ? MI355_OK : fail(g, st, "group: " + err);
-}
-
-// a finished set: its palettes from the pinned block into cd_results (once). g->mu held.
-void cd_collect(mi355_group *g, CdSet &s) {
-  if (s.collected) return;
-  s.collected = true;
-  if (g->cd_results.size() > 65536) g->cd_results.clear();   // (results nobody ever collected)
-  for (size_t i = 0; i < s.tickets.size(); i++) {
-    CdOut &o = g->cd_results[s.tickets[i]];
-    o.status = MI355_OK;
-    colordetect_set_result(s.h_block, (int)i, o.rgb, &o.n_colors);
-    g->cd_where.erase(s.tickets[i]);
-  }
-}
-
-// collected sets nobody waits inside leave: event and pinned block back to their free lists. g->mu held.
-void cd_retire(mi355_group *g) {
-  for (auto it = g->cd_sets.begin(); it != g->cd_sets.end();) {
-    if (it->collected && it->waiters == 0) {
-      g->cd_blocks.push_back(it->h_block);
-      g->events.push_back(it->done);
-      it = g->cd_sets.erase(it);
-    } else {
-      ++it;
-    }
-  }
-}
-
-// finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
-void cd_retire_done(mi355_group *g) {
-  for (CdSet &s : g->cd_sets) {
-    if (s.collected) continue;
-    if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
-    cd_collect(g, s);
-  }
-  cd_retire(g);
-}
-
-// launches the pending frames in submission order, kCdSetMax to a set (all of them, or up to the set that carries `until`):
-// consecutive sets on the queue's stream share the scratch, each has its own pinned block. g->mu held.
-int cd_flush_locked(mi355_group *g, uint64_t until = 0) {
-  bool reached = false;
-  int first_rc = MI355_OK;
-  while (!g->cd_pending.empty() && !reached) {
-    const size_t n = std::min(g->cd_pending.size(), (size_t)kCdSetMax);
-    std::vector<CdDesc> take(g->cd_pending.begin(), g->cd_pending.begin() + (std::ptrdiff_t)n);
-    g->cd_pending.erase(g->cd_pending.begin(), g->cd_pending.begin() + (std::ptrdiff_t)n);
-    int rc = MI355_OK, launches = 0;
-    std::string err;
-    hipEvent_t done = take_event(g);
-    if (g->cd_blocks.empty()) cd_retire_done(g);
-    void *block = nullptr;
-    if (!g->cd_blocks.empty()) { block = g->cd_blocks.back(); g->cd_blocks.pop_back(); }
-    // (more sets in flight than ever before: one more block, kept from then on)
-    else if (hipHostMalloc(&block, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); block = nullptr; }
-    if (!done || !block) { rc = MI355_ERR_HIP; err = "group: no event or pinned block for a colordetect set"; }
-    CdFrame frames[kCdSetMax];
-    for (size_t i = 0; i < n; i++) {
-      frames[i] = take[i].f;
-      if (!rc && take[i].ready && hipStreamWaitEvent(g->cd_stream, take[i].ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipStreamWaitEvent(colordetect frame)"; }
-    }
-    if (!rc) rc = colordetect_launch_set(g->cd_scratch, g->cd_stream, g->cd_n_cu, frames, (int)n, block, &launches, &err);
-    if (!rc && hipEventRecord(done, g->cd_stream) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipEventRecord(colordetect set)"; }
-    for (const CdDesc &d : take)
-      if (d.ready) g->events.push_back(d.ready);
-    if (rc) {
-      (void)hipGetLastError();
-      if (done) g->events.push_back(done);
-      if (block) g->cd_blocks.push_back(block);
-      g->last_error = "group: colordetect launch failed: " + err;
-      if (g->cd_results.size() > 65536) g->cd_results.clear();
-      for (const CdDesc &d : take) {   // told to the frame's own wait, once
-        CdOut &o = g->cd_results[d.ticket];
-        o.status = rc;
-        o.n_colors = 0;
-      }
-      if (!first_rc) first_rc = rc;
-      continue;
-    }
-    CdSet s{g->next_cd_seq++, {}, done, 0, block};
-    for (const CdDesc &d : take) { s.tickets.push_back(d.ticket); g->cd_where[d.ticket] = s.seq; reached |= until != 0 && d.ticket == until; }
-    g->cd_sets.push_back(std::move(s));
-    g->n_cd_frames += n;
-    g->n_cd_sets++;
-    if (n > g->n_cd_largest) g->n_cd_largest = n;
-    g->n_cd_launches += (uint64_t)launches;
-  }
-  g->cd_cv.notify_all();
-  return first_rc;
-}
-
-// host wait for the set of `ticket`; `lk` owns g->mu on entry and on return, not while waiting
-int cd_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
-  auto it = g->cd_where.find(ticket);
-  if (it == g->cd_where.end()) return MI355_OK;  // collected already (or failed: cd_results has it)
-  const uint64_t seq = it->second;
-  CdSet *mine = nullptr;
-  for (CdSet &s : g->cd_sets)
-    if (s.seq == seq) { mine = &s; break; }
-  if (!mine) return MI355_OK;
-  const hipEvent_t ev = mine->done;
-  mine->waiters++;
-  lk.unlock();
-  const hipError_t e = hipEventSynchronize(ev);
-  lk.lock();
-  for (CdSet &s : g->cd_sets)
-    if (s.seq == seq) { s.waiters--; break; }
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group colordetect set)"); }
-  for (CdSet &s : g->cd_sets)
-    if (s.seq <= seq) cd_collect(g, s);
-  cd_retire(g);
-  return MI355_OK;
-}
-
-// waits for every set launched so far (their results stay collectable)
-int cd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
-  uint64_t last = 0;
-  for (const CdSet &s : g->cd_sets)
-    if (!s.collected) last = s.tickets.front();
-  return last ? cd_wait_unlocking(g, lk, last) : MI355_OK;
-}
-
-// ------------------------------------------------------------------ hsvdetector queue
-
-// is `ticket` a detector frame that has not been collected?
-bool hd_owns(mi355_group *g, uint64_t ticket) {
-  if (g->hd_where.count(ticket) || g->hd_results.count(ticket)) return true;
-  for (const HdDesc &d : g->hd_pending)
-    if (d.ticket == ticket) return true;
-  return false;
-}
-
-// the queue's stream: at the first submit, never inside a launch set. g->mu held.
-int hd_ensure(mi355_group *g) {
-  if (g->hd_stream) return MI355_OK;
-  int n_cu = 0;
-  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) (void)hipGetLastError();
-  g->hd_n_cu = n_cu > 0 ? n_cu : 256;
-  if (hipStreamCreateWithFlags(&g->hd_stream, hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    g->hd_stream = nullptr;
-    return fail(g, MI355_ERR_HIP, "group: no stream for the hsvdetector queue");
-  }
-  return MI355_OK;
-}
-
-// a finished set: its frames become collectable (once). g->mu held.
-void hd_collect(mi355_group *g, HdSet &s) {
-  if (s.collected) return;
-  s.collected = true;
-  if (g->hd_results.size() > 65536) g->hd_results.clear();   // (results nobody ever collected)
-  for (uint64_t t : s.tickets) {
-    g->hd_results[t] = MI355_OK;
-    g->hd_where.erase(t);
-  }
-}
-
-// collected sets nobody waits inside leave: the event goes back to the free list. g->mu held.
-void hd_retire(mi355_group *g) {
-  for (auto it = g->hd_sets.begin(); it != g->hd_sets.end();) {
-    if (it->collected && it->waiters == 0) {
-      g->events.push_back(it->done);
-      it = g->hd_sets.erase(it);
-    } else {
-      ++it;
-    }
-  }
-}
-
-// finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
-void hd_retire_done(mi355_group *g) {
-  for (HdSet &s : g->hd_sets) {
-    if (s.collected) continue;
-    if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
-    hd_collect(g, s);
-  }
-  hd_retire(g);
-}
-
-// launches the pending frames in submission order, kHdSetMax to a set (all of them, or up to the set that carries `until`), as
-// consecutive sets on the queue's stream. g->mu held.
-int hd_flush_locked(mi355_group *g, uint64_t until = 0) {
-  bool reached = false;
-  int first_rc = MI355_OK;
-  while (!g->hd_pending.empty() && !reached) {
-    const size_t n = std::min(g->hd_pending.size(), (size_t)kHdSetMax);
-    std::vector<HdDesc> take(g->hd_pending.begin(), g->hd_pending.begin() + (std::ptrdiff_t)n);
-    g->hd_pending.erase(g->hd_pending.begin(), g->hd_pending.begin() + (std::ptrdiff_t)n);
-    int rc = MI355_OK, launches = 0;
-    std::string err;
-    hipEvent_t done = take_event(g);
-    if (!done) { rc = MI355_ERR_HIP; err = "group: no event for a hsvdetector set"; }
-    HdFrame frames[kHdSetMax];
-    for (size_t i = 0; i < n; i++) {
-      frames[i] = take[i].f;
-      if (!rc && take[i].ready && hipStreamWaitEvent(g->hd_stream, take[i].ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipStreamWaitEvent(hsvdetector frame)"; }
-    }
-    if (!rc) rc = hsvdetect_launch_set(g->hd_stream, g->hd_n_cu, frames, (int)n, &launches, &err);
-    if (!rc && hipEventRecord(done, g->hd_stream) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipEventRecord(hsvdetector set)"; }
-    for (const HdDesc &d : take)
-      if (d.ready) g->events.push_back(d.ready);
-    if (rc) {
-      (void)hipGetLastError();
-      if (done) g->events.push_back(done);
-      g->last_error = "group: hsvdetector launch failed: " + err;
-      if (g->hd_results.size() > 65536) g->hd_results.clear();
-      for (const HdDesc &d : take) g->hd_results[d.ticket] = rc;   // told to the frame's own wait, once
-      if (!first_rc) first_rc = rc;
-      continue;
-    }
-    HdSet s{g->next_hd_seq++, {}, done, 0};
-    for (const HdDesc &d : take) {
-      s.tickets.push_back(d.ticket);
-      g->hd_where[d.ticket] = s.seq;
-      reached |= until != 0 && d.ticket == until;
-      // what the element behind finds on-die, as the lone entry records it
-      if (d.f.width > 0 && d.f.height > 0) note_written(g->device, d.f.dst, (size_t)d.f.dst_stride * (size_t)d.f.height);
-    }
-    g->hd_sets.push_back(std::move(s));
-    g->n_hd_frames += n;
-    g->n_hd_sets++;
-    if (n > g->n_hd_largest) g->n_hd_largest = n;
-    g->n_hd_launches += (uint64_t)launches;
-  }
-  g->hd_cv.notify_all();
-  return first_rc;
-}
-
-// host wait for the set of `ticket`; `lk` owns g->mu on entry and on return, not while waiting
-int hd_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
-  auto it = g->hd_where.find(ticket);
-  if (it == g->hd_where.end()) return MI355_OK;  // collected already (or failed: hd_results has it)
-  const uint64_t seq = it->second;
-  HdSet *mine = nullptr;
-  for (HdSet &s : g->hd_sets)
-    if (s.seq == seq) { mine = &s; break; }
-  if (!mine) return MI355_OK;
-  const hipEvent_t ev = mine->done;
-  mine->waiters++;
-  lk.unlock();
-  const hipError_t e = hipEventSynchronize(ev);
-  lk.lock();
-  for (HdSet &s : g->hd_sets)
-    if (s.seq == seq) { s.waiters--; break; }
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group hsvdetector set)"); }
-  for (HdSet &s : g->hd_sets)
-    if (s.seq <= seq) hd_collect(g, s);
-  hd_retire(g);
-  return MI355_OK;
-}
-
-// waits for every set launched so far (their frames stay collectable)
-int hd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
-  uint64_t last = 0;
-  for (const HdSet &s : g->hd_sets)
-    if (!s.collected) last = s.tickets.front();
-  return last ? hd_wait_unlocking(g, lk, last) : MI355_OK;
-}
-
-// ------------------------------------------------------------------ decoder queue
-
-// is `ticket` a decoder tensor that has not been collected?
-bool yd_owns(mi355_group *g, uint64_t ticket) {
-  if (g->yd_where.count(ticket) || g->yd_results.count(ticket)) return true;
-  for (const YdDesc &d : g->yd_pending)
-    if (d.ticket == ticket) return true;
-  return false;
-}
-
-// the queue's stream and scratch: at the first submit, never inside a launch set. g->mu held.
-int yd_ensure(mi355_group *g) {
-  if (g->yd_scratch) return MI355_OK;
-  if (!g->yd_stream && hipStreamCreateWithFlags(&g->yd_stream, hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    g->yd_stream = nullptr;
-    return fail(g, MI355_ERR_HIP, "group: no stream for the decoder queue");
-  }
-  int st = MI355_OK;
-  std::string err;
-  g->yd_scratch = yolodec_set_scratch_new(&st, &err);
-  return g->yd_scratch ? MI355_OK : fail(g, st, "group: " + err);
-}
-
-// a pinned block of at least `bytes`: a free one that is large enough, else a new one (a free one that is too small makes room)
-YdBlock yd_take_block(mi355_group *g, size_t bytes) {
-  for (size_t i = 0; i < g->yd_blocks.size(); i++)
-    if (g->yd_blocks[i].bytes >= bytes) {
-      const YdBlock b = g->yd_blocks[i];
-      g->yd_blocks.erase(g->yd_blocks.begin() + (std::ptrdiff_t)i);
-      return b;
-    }
-  if (!g->yd_blocks.empty()) {
-    (void)hipHostFree(g->yd_blocks.back().h);
-    g->yd_blocks.pop_back();
-  }
-  YdBlock b{nullptr, 0};
-  const size_t want = (bytes + 4095) / 4096 * 4096;
-  if (hipHostMalloc(&b.h, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); b.h = nullptr; return b; }
-  b.bytes = want;
-  return b;
-}
-
-// a finished set: counts and records move from its pinned block into yd_results (once), the block is free again. g->mu held.
-void yd_collect(mi355_group *g, YdSet &s) {
-  if (s.collected) return;
-  s.collected = true;
-  if (g->yd_results.size() > 65536) g->yd_results.clear();   // (results nobody ever collected)
-  const uint32_t *h_n = static_cast<const uint32_t *>(s.block.h);
-  const mi355_yolo_det *h_dets = s.block.h ? reinterpret_cast<const mi355_yolo_det *>(static_cast<const uint8_t *>(s.block.h) + kYdCountsBytes) : nullptr;
-  for (size_t i = 0; i < s.slots.size(); i++) {
-    const YdSlot &sl = s.slots[i];
-    YdOut &o = g->yd_results[sl.ticket];
-    o.status = MI355_OK;
-    o.max_dets = sl.max_dets;
-    o.n_dets = sl.num_candidates && h_n ? h_n[i] : 0;   // a tensor without candidates had no job
-    const uint32_t cap = sl.max_dets < sl.num_candidates ? sl.max_dets : sl.num_candidates;
-    const uint32_t w = o.n_dets < cap ? o.n_dets : cap;
-    if (w) o.dets.assign(h_dets + sl.det_offset, h_dets + sl.det_offset + w);
-    g->yd_where.erase(sl.ticket);
-  }
-  if (s.block.h) g->yd_blocks.push_back(s.block);
-  s.block = YdBlock{nullptr, 0};
-}
-
-// collected sets nobody waits inside leave: the event goes back to the free list. g->mu held.
-void yd_retire(mi355_group *g) {
-  for (auto it = g->yd_sets.begin(); it != g->yd_sets.end();) {
-    if (it->collected && it->waiters == 0) {
-      g->events.push_back(it->done);
-      it = g->yd_sets.erase(it);
-    } else {
-      ++it;
-    }
-  }
-}
-
-// finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
-void yd_retire_done(mi355_group *g) {
-  for (YdSet &s : g->yd_sets) {
-    if (s.collected) continue;
-    if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
-    yd_collect(g, s);
-  }
-  yd_retire(g);
-}
-
-// launches the pending tensors in submission order, kYdSetMax to a set (all of them, or up to the set that carries `until`):
-// consecutive sets on the queue's stream share the device scratch, each has its own pinned block. g->mu held.
-int yd_flush_locked(mi355_group *g, uint64_t until = 0) {
-  bool reached = false;
-  int first_rc = MI355_OK;
-  while (!g->yd_pending.empty() && !reached) {
-    const size_t n = std::min(g->yd_pending.size(), (size_t)kYdSetMax);
-    std::vector<YdDesc> take(g->yd_pending.begin(), g->yd_pending.begin() + (std::ptrdiff_t)n);
-    g->yd_pending.erase(g->yd_pending.begin(), g->yd_pending.begin() + (std::ptrdiff_t)n);
-    int rc = MI355_OK, launches = 0;
-    std::string err;
-    // the set's layout: the plan the launch itself uses
-    YdTensor tensors[kYdSetMax];
-    int layout[kYdSetMax];
-    uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], blocks[kYdSetMax];
-    uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax], totals[6] = {0, 0, 0, 0, 0, 0};
-    for (size_t i = 0; i < n; i++) {
-      tensors[i] = take[i].t;
-      layout[i] = take[i].t.layout; F[i] = take[i].t.num_fields; N[i] = take[i].t.num_candidates; cap[i] = take[i].t.max_dets;
-    }
-    rc = yolodec_set_plan((int)n, layout, F, N, cap, first, blocks, key_off, box_off, det_off, totals);
-    if (rc) err = "group: bad decoder set";
-    hipEvent_t done = take_event(g);
-    YdBlock block{nullptr, 0};
-    if (!rc && totals[2]) {   // a set without a candidate has nothing to copy
-      if (g->yd_blocks.empty()) yd_retire_done(g);
-      block = yd_take_block(g, yolodec_set_result_bytes(totals[5]));
-    }
-    if (!rc && (!done || (totals[2] && !block.h))) { rc = MI355_ERR_HIP; err = "group: no event or pinned block for a decoder set"; }
-    for (size_t i = 0; i < n; i++)
-      if (!rc && take[i].ready && hipStreamWaitEvent(g->yd_stream, take[i].ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipStreamWaitEvent(decoder tensor)"; }
-    if (!rc) rc = yolodec_launch_set(g->yd_scratch, g->yd_stream, tensors, (int)n, block.h, block.bytes, &launches, &err);
-    if (!rc && hipEventRecord(done, g->yd_stream) != hipSuccess) { rc = MI355_ERR_HIP; err = "hipEventRecord(decoder set)"; }
-    for (const YdDesc &d : take)
-      if (d.ready) g->events.push_back(d.ready);
-    if (rc) {
-      (void)hipGetLastError();
-      if (done) g->events.push_back(done);
-      if (block.h) {
-        // what did go out may still write the block: it is free again only behind the queue's stream
-        (void)hipStreamSynchronize(g->yd_stream);
-        (void)hipGetLastError();
-        g->yd_blocks.push_back(block);
-      }
-      g->last_error = "group: decoder launch failed: " + err;
-      if (g->yd_results.size() > 65536) g->yd_results.clear();
-      for (const YdDesc &d : take) {   // told to the tensor's own wait, once
-        YdOut &o = g->yd_results[d.ticket];
-        o.status = rc;
-        o.n_dets = 0;
-        o.max_dets = d.t.max_dets;
-      }
-      if (!first_rc) first_rc = rc;
-      continue;
-    }
-    YdSet s{g->next_yd_seq++, {}, done, 0, block};
-    for (size_t i = 0; i < n; i++) {
-      const YdDesc &d = take[i];
-      s.slots.push_back(YdSlot{d.ticket, d.t.num_candidates, d.t.max_dets, det_off[i]});
-      g->yd_where[d.ticket] = s.seq;
-      reached |= until != 0 && d.ticket == until;
-    }
-    g->yd_sets.push_back(std::move(s));
-    g->n_yd_tensors += n;
-    g->n_yd_sets++;
-    if (n > g->n_yd_largest) g->n_yd_largest = n;
-    g->n_yd_launches += (uint64_t)launches;
-  }
-  g->yd_cv.notify_all();
-  return first_rc;
-}
-
-// host wait for the set of `ticket`; `lk` owns g->mu on entry and on return, not while waiting
-int yd_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
-  auto it = g->yd_where.find(ticket);
-  if (it == g->yd_where.end()) return MI355_OK;  // collected already (or failed: yd_results has it)
-  const uint64_t seq = it->second;
-  YdSet *mine = nullptr;
-  for (YdSet &s : g->yd_sets)
-    if (s.seq == seq) { mine = &s; break; }
-  if (!mine) return MI355_OK;
-  const hipEvent_t ev = mine->done;
-  mine->waiters++;
-  lk.unlock();
-  const hipError_t e = hipEventSynchronize(ev);
-  lk.lock();
-  for (YdSet &s : g->yd_sets)
-    if (s.seq == seq) { s.waiters--; break; }
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group decoder set)"); }
-  for (YdSet &s : g->yd_sets)
-    if (s.seq <= seq) yd_collect(g, s);
-  yd_retire(g);
-  return MI355_OK;
-}
-
-// waits for every set launched so far (their results stay collectable)
-int yd_wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
-  uint64_t last = 0;
-  for (const YdSet &s : g->yd_sets)
-    if (!s.collected) last = s.slots.front().ticket;
-  return last ? yd_wait_unlocking(g, lk, last) : MI355_OK;
+// A set queue's ticket presented to an entry point that serves another queue: refused (non-zero), and left collectable.
+int refuse_set_queue_ticket(mi355_group *g, uint64_t ticket) {
+  std::string owner;
+  for_each_set_queue(g, [&](auto &q) {
+    if (owner.empty() && q.owns(ticket)) owner = q.foreign_refusal();
+  });
+  return owner.empty() ? MI355_OK : fail(g, MI355_ERR_INVALID_ARG, owner);
 }
 
 }  // namespace
@@ -1054,55 +998,7 @@ void mi355_group_destroy(mi355_group *g) {
       if (g->alane[l]) mi355_ctx_destroy(g->alane[l]);
     }
   }
-  if (g->cd_stream) {
-    // frames still pending are launched and waited for, as pairs are
-    {
-      Locked L(g);
-      (void)cd_flush_locked(g);
-    }
-    (void)hipStreamSynchronize(g->cd_stream);
-    for (CdSet &s : g->cd_sets) { (void)hipEventDestroy(s.done); (void)hipHostFree(s.h_block); }
-    g->cd_sets.clear();
-    for (CdDesc &d : g->cd_pending)
-      if (d.ready) (void)hipEventDestroy(d.ready);
-    g->cd_pending.clear();
-    colordetect_set_scratch_free(g->cd_scratch);
-    (void)hipStreamDestroy(g->cd_stream);
-  }
-  for (void *b : g->cd_blocks) (void)hipHostFree(b);
-  if (g->hd_stream) {
-    // frames still pending are launched and waited for, as pairs are: their destinations are complete when destroy returns
-    {
-      Locked L(g);
-      (void)hd_flush_locked(g);
-    }
-    (void)hipStreamSynchronize(g->hd_stream);
-    for (HdSet &s : g->hd_sets) (void)hipEventDestroy(s.done);
-    g->hd_sets.clear();
-    for (HdDesc &d : g->hd_pending)
-      if (d.ready) (void)hipEventDestroy(d.ready);
-    g->hd_pending.clear();
-    (void)hipStreamDestroy(g->hd_stream);
-  }
-  if (g->yd_stream) {
-    // tensors still pending are launched and waited for, as frames are: nothing reads a member's tensor once destroy has returned
-    if (g->yd_scratch) {
-      Locked L(g);
-      (void)yd_flush_locked(g);
-    }
-    (void)hipStreamSynchronize(g->yd_stream);
-    for (YdSet &s : g->yd_sets) {
-      (void)hipEventDestroy(s.done);
-      if (s.block.h) (void)hipHostFree(s.block.h);
-    }
-    g->yd_sets.clear();
-    for (YdDesc &d : g->yd_pending)
-      if (d.ready) (void)hipEventDestroy(d.ready);
-    g->yd_pending.clear();
-    yolodec_set_scratch_free(g->yd_scratch);
-    (void)hipStreamDestroy(g->yd_stream);
-  }
-  for (YdBlock &b : g->yd_blocks) (void)hipHostFree(b.h);
+  for_each_set_queue(g, [&](auto &q) { q.destroy(g); });
   for (Batch &b : g->batches) (void)hipEventDestroy(b.done);   // (normally none left: wait_all retired them)
   for (Desc &d : g->pending)
     if (d.ready) (void)hipEventDestroy(d.ready);
@@ -1153,19 +1049,8 @@ static int submit_frame(mi355_group *g, mi355_ctx *ctx, uint8_t *d_src, uint8_t 
   // (this thread is the one that drives ctx, and the reference is copied from ctx's own: the registry's "sole user" test cannot
   // run concurrently with this copy)
   if (d.batchable) d.table_ref = ctx->lut.table_ref[fused ? 1 : 0];
-  // The frame starts after what ctx's stream holds now (an upload, the table build). A stream that holds nothing - the common
-  // case for a stream that only ever submits here - needs no event: every cross-stream wait is a barrier packet the command
-  // processor resolves in microseconds, eight of them in front of a 90 us launch are a bubble.
-  d.ready = nullptr;
-  if (hipStreamQuery(ctx->stream) != hipSuccess) {
-    (void)hipGetLastError();
-    d.ready = take_event(g);
-    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      if (d.ready) g->events.push_back(d.ready);
-      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
-    }
-  }
+  // the frame starts after what ctx's stream holds now (an upload, the table build)
+  if (int rc = record_ready(g, ctx, &d.ready)) return rc;
   d.ticket = g->next_ticket++;
   if (ticket) *ticket = d.ticket;
   g->pending.push_back(d);
@@ -1193,10 +1078,12 @@ int mi355_group_flush(mi355_group *g) {
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   const int rc = flush_locked(g);
   const int rc2 = g->actx ? cmp_flush_locked(g) : MI355_OK;
-  const int rc3 = g->cd_scratch ? cd_flush_locked(g) : MI355_OK;
-  const int rc4 = g->hd_stream ? hd_flush_locked(g) : MI355_OK;
-  const int rc5 = g->yd_scratch ? yd_flush_locked(g) : MI355_OK;
-  return rc ? rc : (rc2 ? rc2 : (rc3 ? rc3 : (rc4 ? rc4 : rc5)));
+  int first = rc ? rc : rc2;
+  for_each_set_queue(g, [&](auto &q) {   // every queue that has been set up is launched; the first failure is the answer
+    const int r = q.kind.set_up() ? q.flush_locked(g) : MI355_OK;
+    if (!first) first = r;
+  });
+  return first;
 }
 
 // ---------------------------------------------------------------- videocompare pairs (Dssim / Blockhash) of independent elements
@@ -1253,16 +1140,8 @@ int mi355_group_submit_compare(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_
   d.ctx = ctx; d.ref = d_ref; d.frame = d_frame; d.width = width; d.height = height; d.stride = stride; d.format = format; d.algo = algo;
   d.translucent = ctx->dssim_translucent;
   d.fast = ctx->dssim_fast;
-  d.ready = nullptr;
-  if (hipStreamQuery(ctx->stream) != hipSuccess) {   // the pair starts after what the stream's own context holds now (an upload)
-    (void)hipGetLastError();
-    d.ready = take_event(g);
-    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      if (d.ready) g->events.push_back(d.ready);
-      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
-    }
-  }
+  // the pair starts after what the stream's own context holds now (an upload)
+  if (int rc = record_ready(g, ctx, &d.ready)) return rc;
   d.ticket = g->next_ticket++;
   if (ticket) *ticket = d.ticket;
   g->cmp_pending.push_back(d);
@@ -1278,9 +1157,7 @@ int mi355_group_wait_compare(mi355_group *g, uint64_t ticket, double *distance, 
   Locked L(g);
   std::unique_lock<std::mutex> &lk = L.lk;
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
-  if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
-  if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
-  if (yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a decoder tensor's ticket (mi355_group_wait_yolodec collects it)");
+  if (int rc = refuse_set_queue_ticket(g, ticket)) return rc;
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   auto is_pending = [&]() { for (const CmpDesc &d : g->cmp_pending) if (d.ticket == ticket) return true; return false; };
   if (is_pending()) {
@@ -1314,13 +1191,13 @@ int mi355_group_compare_stats(mi355_group *g, uint64_t stats[3]) {
   return MI355_OK;
 }
 
-// ---------------------------------------------------------------- colordetect frames of independent elements
+// ---------------------------------------------------------------- the set queues' entry points: each checks its own arguments and
+// hands over to SetQueue<Kind> (submit's tail, the body of wait, stats)
 
 int mi355_group_set_colordetect_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
   if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  g->cd_expected = expected_streams;
-  g->cd_linger_us = linger_us;
+  g->cd.set_rendezvous(expected_streams, linger_us);
   return MI355_OK;
 }
 
@@ -1333,58 +1210,15 @@ int mi355_group_submit_colordetect(mi355_group *g, mi355_ctx *ctx, const uint8_t
   int rc = colordetect_check_frame(data_len, format, quality, max_colors, &why);
   if (rc) return fail(g, rc, why);
   if (data_len && !d_data) return fail(g, MI355_ERR_INVALID_ARG, "colordetect: null frame");
-  if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  if ((rc = cd_ensure(g))) return rc;
-  cd_retire_done(g);
-  CdDesc d{};
-  d.f = CdFrame{d_data, data_len, format, quality, max_colors};
-  d.ready = nullptr;
-  if (hipStreamQuery(ctx->stream) != hipSuccess) {   // the frame is read after what the context's stream holds now (an upload, a filter)
-    (void)hipGetLastError();
-    d.ready = take_event(g);
-    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      if (d.ready) g->events.push_back(d.ready);
-      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
-    }
-  }
-  d.ticket = g->next_ticket++;
-  *ticket = d.ticket;
-  g->cd_pending.push_back(d);
-  // everybody is here (rendezvous), or a launch set is full: go. The frame has been accepted whatever that launch does (a failure
-  // is told to the waits of the frames it carried).
-  const int full = g->cd_expected > 0 && g->cd_expected < kCdSetMax ? g->cd_expected : kCdSetMax;
-  if ((int)g->cd_pending.size() >= full) (void)cd_flush_locked(g);
-  return MI355_OK;
+  return g->cd.submit(g, ctx, CdFrame{d_data, data_len, format, quality, max_colors}, true, ticket);
 }
 
 int mi355_group_wait_colordetect(mi355_group *g, uint64_t ticket, uint8_t palette_rgb[255 * 3], int *n_colors) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  std::unique_lock<std::mutex> &lk = L.lk;
   if (!palette_rgb || !n_colors) return fail(g, MI355_ERR_INVALID_ARG, "group: null result arrays");
-  // a filter frame's, a pair's, a detector frame's, a decoder tensor's, a collected or an unknown ticket: refused before anything is launched or waited for
-  if (!cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: not the ticket of a colordetect frame that is still to be collected");
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  auto is_pending = [&]() { for (const CdDesc &d : g->cd_pending) if (d.ticket == ticket) return true; return false; };
-  if (is_pending()) {
-    // rendezvous: the other instances of this interval are about to submit - linger for them (bounded), then launch what is there
-    if (g->cd_expected > 0 && g->cd_linger_us > 0) {
-      const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(g->cd_linger_us);
-      while (is_pending() && (int)g->cd_pending.size() < g->cd_expected) {
-        if (g->cd_cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
-      }
-    }
-    if (is_pending()) (void)cd_flush_locked(g, ticket);   // (a failure of this frame's own launch is in cd_results)
-  }
-  int rc = cd_wait_unlocking(g, lk, ticket);
-  if (rc) return rc;
-  auto r = g->cd_results.find(ticket);
-  if (r == g->cd_results.end()) return fail(g, MI355_ERR_INVALID_ARG, "group: this frame's palette has been collected already");   // (by a concurrent wait)
-  const CdOut res = r->second;
-  g->cd_results.erase(r);
-  if (res.status) return fail(g, res.status, "group: the launch that carried this colordetect frame failed");
+  CdOut res;
+  if (int rc = g->cd.wait(g, L.lk, ticket, &res)) return rc;
   std::memcpy(palette_rgb, res.rgb, sizeof(res.rgb));
   *n_colors = res.n_colors;
   return MI355_OK;
@@ -1393,20 +1227,14 @@ int mi355_group_wait_colordetect(mi355_group *g, uint64_t ticket, uint8_t palett
 int mi355_group_colordetect_stats(mi355_group *g, uint64_t stats[4]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
-  stats[0] = g->n_cd_frames;
-  stats[1] = g->n_cd_sets;
-  stats[2] = g->n_cd_largest;
-  stats[3] = g->n_cd_launches;
+  g->cd.stats(stats);
   return MI355_OK;
 }
-
-// ---------------------------------------------------------------- hsvdetector frames of independent elements
 
 int mi355_group_set_hsvdetect_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
   if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  g->hd_expected = expected_streams;
-  g->hd_linger_us = linger_us;
+  g->hd.set_rendezvous(expected_streams, linger_us);
   return MI355_OK;
 }
 
@@ -1415,78 +1243,34 @@ int mi355_group_submit_hsvdetect(mi355_group *g, mi355_ctx *ctx, const uint8_t *
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
   if (!ctx || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context or ticket");
-  HdDesc d{};
+  HdFrame f{};
   const char *why = nullptr;
-  int rc = hsvdetect_check_frames(d_src, src_stride, src_format, d_dst, dst_stride, dst_format, 1, width, height, settings, &d.f.sfmt, &d.f.dst_alpha_first,
-                                  &d.f.dst_bgr, &why);
+  int rc = hsvdetect_check_frames(d_src, src_stride, src_format, d_dst, dst_stride, dst_format, 1, width, height, settings, &f.sfmt, &f.dst_alpha_first,
+                                  &f.dst_bgr, &why);
   if (rc) return fail(g, rc, why);
-  if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  if ((rc = hd_ensure(g))) return rc;
-  hd_retire_done(g);
-  d.f.src = d_src;
-  d.f.dst = d_dst;
-  d.f.src_stride = src_stride;
-  d.f.dst_stride = dst_stride;
-  d.f.width = width;
-  d.f.height = height;
-  d.f.s = *settings;
-  d.f.force_generic = ctx->force_generic;
-  d.ready = nullptr;
-  if (width > 0 && height > 0 && hipStreamQuery(ctx->stream) != hipSuccess) {   // the frame is read after what the context's stream holds now (an upload, a filter)
-    (void)hipGetLastError();
-    d.ready = take_event(g);
-    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      if (d.ready) g->events.push_back(d.ready);
-      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
-    }
-  }
-  d.ticket = g->next_ticket++;
-  *ticket = d.ticket;
-  g->hd_pending.push_back(d);
-  // everybody is here (rendezvous), or a launch set is full: go. The frame has been accepted whatever that launch does (a failure
-  // is told to the waits of the frames it carried).
-  const int full = g->hd_expected > 0 && g->hd_expected < kHdSetMax ? g->hd_expected : kHdSetMax;
-  if ((int)g->hd_pending.size() >= full) (void)hd_flush_locked(g);
-  return MI355_OK;
+  f.src = d_src;
+  f.dst = d_dst;
+  f.src_stride = src_stride;
+  f.dst_stride = dst_stride;
+  f.width = width;
+  f.height = height;
+  f.s = *settings;
+  f.force_generic = ctx->force_generic;
+  // an empty frame reads nothing: it does not make the set wait for its stream
+  return g->hd.submit(g, ctx, f, width > 0 && height > 0, ticket);
 }
 
 int mi355_group_wait_hsvdetect(mi355_group *g, uint64_t ticket) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  std::unique_lock<std::mutex> &lk = L.lk;
-  // another queue's, a collected or an unknown ticket: refused before anything is launched or waited for
-  if (!hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: not the ticket of a hsvdetector frame that is still to be collected");
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  auto is_pending = [&]() { for (const HdDesc &d : g->hd_pending) if (d.ticket == ticket) return true; return false; };
-  if (is_pending()) {
-    // rendezvous: the other instances of this interval are about to submit - linger for them (bounded), then launch what is there
-    if (g->hd_expected > 0 && g->hd_linger_us > 0) {
-      const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(g->hd_linger_us);
-      while (is_pending() && (int)g->hd_pending.size() < g->hd_expected) {
-        if (g->hd_cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
-      }
-    }
-    if (is_pending()) (void)hd_flush_locked(g, ticket);   // (a failure of this frame's own launch is in hd_results)
-  }
-  int rc = hd_wait_unlocking(g, lk, ticket);
-  if (rc) return rc;
-  auto r = g->hd_results.find(ticket);
-  if (r == g->hd_results.end()) return fail(g, MI355_ERR_INVALID_ARG, "group: this frame has been collected already");   // (by a concurrent wait)
-  const int status = r->second;
-  g->hd_results.erase(r);
-  if (status) return fail(g, status, "group: the launch that carried this hsvdetector frame failed");
-  return MI355_OK;
+  int status = MI355_OK;
+  return g->hd.wait(g, L.lk, ticket, &status);
 }
 
 int mi355_group_hsvdetect_stats(mi355_group *g, uint64_t stats[4]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
-  stats[0] = g->n_hd_frames;
-  stats[1] = g->n_hd_sets;
-  stats[2] = g->n_hd_largest;
-  stats[3] = g->n_hd_launches;
+  g->hd.stats(stats);
   return MI355_OK;
 }
 
@@ -1495,13 +1279,10 @@ int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_pe
   return hsvdetect_plan(n_cu, blocks_per_cu, units_per_block, n_jobs, units, first_block, blocks, total_blocks);
 }
 
-// ---------------------------------------------------------------- decoder tensors of independent elements
-
 int mi355_group_set_yolodec_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
   if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  g->yd_expected = expected_streams;
-  g->yd_linger_us = linger_us;
+  g->yd.set_rendezvous(expected_streams, linger_us);
   return MI355_OK;
 }
 
@@ -1514,72 +1295,34 @@ int mi355_group_submit_yolodec(mi355_group *g, mi355_ctx *ctx, const float *d_te
   int rc = yolodec_check_args((size_t)num_fields * num_candidates * 4, 1, layout, num_fields, num_candidates, &why);
   if (rc) return fail(g, rc, why);
   if (num_candidates && (!d_tensor || (uintptr_t)d_tensor % 4 != 0)) return fail(g, MI355_ERR_INVALID_ARG, "yolodec: null or misaligned tensors");
-  if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  if ((rc = yd_ensure(g))) return rc;
-  yd_retire_done(g);
-  YdDesc d{};
-  d.t = YdTensor{d_tensor, layout, num_fields, num_candidates, max_dets, *p};
-  d.ready = nullptr;
-  if (num_candidates && hipStreamQuery(ctx->stream) != hipSuccess) {   // the tensor is read after what the context's stream holds now (an upload, the model's last kernel)
-    (void)hipGetLastError();
-    d.ready = take_event(g);
-    if (!d.ready || hipEventRecord(d.ready, ctx->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      if (d.ready) g->events.push_back(d.ready);
-      return fail(g, MI355_ERR_HIP, "group: hipEventRecord(ready)");
-    }
-  }
-  d.ticket = g->next_ticket++;
-  *ticket = d.ticket;
-  g->yd_pending.push_back(d);
-  // everybody is here (rendezvous), or a launch set is full: go. The tensor has been accepted whatever that launch does (a failure
-  // is told to the waits of the tensors it carried).
-  const int full = g->yd_expected > 0 && g->yd_expected < kYdSetMax ? g->yd_expected : kYdSetMax;
-  if ((int)g->yd_pending.size() >= full) (void)yd_flush_locked(g);
-  return MI355_OK;
+  // a tensor without a candidate is not read: it does not make the set wait for its stream (the model's last kernel, an upload)
+  return g->yd.submit(g, ctx, YdTensor{d_tensor, layout, num_fields, num_candidates, max_dets, *p}, num_candidates != 0, ticket);
 }
 
 int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *dets, uint32_t *n_dets) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  std::unique_lock<std::mutex> &lk = L.lk;
   if (!n_dets) return fail(g, MI355_ERR_INVALID_ARG, "group: null result count");
-  // another queue's, a collected or an unknown ticket: refused before anything is launched or waited for
-  if (!yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: not the ticket of a decoder tensor that is still to be collected");
-  if (!dets) {   // only a tensor submitted with max_dets == 0 has no records to take
+  if (!dets) {
+    // Only a tensor submitted with max_dets == 0 has no records to take. The refusal leaves the result collectable, so the
+    // capacity is looked up wherever the tensor stands - pending, in a set in flight, or collected into `results` - and not by
+    // taking the result out first. (A ticket that is not this queue's has no capacity here and is refused below.)
+    SetQueue<YdKind> &q = g->yd;
     uint32_t cap = 0;
-    for (const YdDesc &d : g->yd_pending)
-      if (d.ticket == ticket) cap = d.t.max_dets;
-    auto w = g->yd_where.find(ticket);
-    if (w != g->yd_where.end())
-      for (const YdSet &s : g->yd_sets)
+    for (const auto &d : q.pending)
+      if (d.ticket == ticket) cap = d.p.max_dets;
+    auto w = q.where.find(ticket);
+    if (w != q.where.end())
+      for (const auto &s : q.sets)
         if (s.seq == w->second)
-          for (const YdSlot &sl : s.slots)
-            if (sl.ticket == ticket) cap = sl.max_dets;
-    auto r = g->yd_results.find(ticket);
-    if (r != g->yd_results.end()) cap = r->second.max_dets;
+          for (size_t i = 0; i < s.tickets.size(); i++)
+            if (s.tickets[i] == ticket) cap = s.data.slots[i].max_dets;
+    auto r = q.results.find(ticket);
+    if (r != q.results.end()) cap = r->second.max_dets;
     if (cap) return fail(g, MI355_ERR_INVALID_ARG, "group: null records for a tensor submitted with max_dets > 0");
   }
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  auto is_pending = [&]() { for (const YdDesc &d : g->yd_pending) if (d.ticket == ticket) return true; return false; };
-  if (is_pending()) {
-    // rendezvous: the other instances of this interval are about to submit - linger for them (bounded), then launch what is there
-    if (g->yd_expected > 0 && g->yd_linger_us > 0) {
-      const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(g->yd_linger_us);
-      while (is_pending() && (int)g->yd_pending.size() < g->yd_expected) {
-        if (g->yd_cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
-      }
-    }
-    if (is_pending()) (void)yd_flush_locked(g, ticket);   // (a failure of this tensor's own launch is in yd_results)
-  }
-  int rc = yd_wait_unlocking(g, lk, ticket);
-  if (rc) return rc;
-  auto r = g->yd_results.find(ticket);
-  if (r == g->yd_results.end()) return fail(g, MI355_ERR_INVALID_ARG, "group: this tensor's result has been collected already");   // (by a concurrent wait)
-  const YdOut res = std::move(r->second);
-  g->yd_results.erase(r);
-  if (res.status) return fail(g, res.status, "group: the launch that carried this decoder tensor failed");
+  YdOut res;
+  if (int rc = g->yd.wait(g, L.lk, ticket, &res)) return rc;
   *n_dets = res.n_dets;
   if (dets && !res.dets.empty()) std::memcpy(dets, res.dets.data(), res.dets.size() * sizeof(mi355_yolo_det));
   return MI355_OK;
@@ -1588,10 +1331,7 @@ int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *de
 int mi355_group_yolodec_stats(mi355_group *g, uint64_t stats[4]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
-  stats[0] = g->n_yd_tensors;
-  stats[1] = g->n_yd_sets;
-  stats[2] = g->n_yd_largest;
-  stats[3] = g->n_yd_launches;
+  g->yd.stats(stats);
   return MI355_OK;
 }
 
@@ -1600,9 +1340,7 @@ int mi355_group_wait(mi355_group *g, uint64_t ticket) {
   Locked L(g);
   std::unique_lock<std::mutex> &lk = L.lk;
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
-  if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
-  if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
-  if (yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a decoder tensor's ticket (mi355_group_wait_yolodec collects it)");
+  if (int rc = refuse_set_queue_ticket(g, ticket)) return rc;
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -1617,9 +1355,7 @@ int mi355_group_order_after(mi355_group *g, mi355_ctx *ctx, uint64_t ticket) {
   if (!g || !ctx) return MI355_ERR_INVALID_ARG;
   Locked L(g);
   if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
-  if (cd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a colordetect frame's ticket (mi355_group_wait_colordetect collects it)");
-  if (hd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a hsvdetector frame's ticket (mi355_group_wait_hsvdetect collects it)");
-  if (yd_owns(g, ticket)) return fail(g, MI355_ERR_INVALID_ARG, "group: a decoder tensor's ticket (mi355_group_wait_yolodec collects it)");
+  if (int rc = refuse_set_queue_ticket(g, ticket)) return rc;
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   bool is_pending = false;
   for (const Desc &d : g->pending) is_pending |= d.ticket == ticket;
@@ -1647,17 +1383,11 @@ int mi355_group_wait_all(mi355_group *g) {
   int rc = flush_locked(g);
   if (rc) return rc;
   if ((rc = wait_all_unlocking(g, lk))) return rc;
-  if (g->cd_scratch) {
-    if ((rc = cd_flush_locked(g))) return rc;
-    if ((rc = cd_wait_all_unlocking(g, lk))) return rc;
-  }
-  if (g->hd_stream) {
-    if ((rc = hd_flush_locked(g))) return rc;
-    if ((rc = hd_wait_all_unlocking(g, lk))) return rc;
-  }
-  if (!g->yd_scratch) return MI355_OK;
-  if ((rc = yd_flush_locked(g))) return rc;
-  return yd_wait_all_unlocking(g, lk);
+  for_each_set_queue(g, [&](auto &q) {   // each queue that has been set up, in turn; the first failure ends it
+    if (rc || !q.kind.set_up()) return;
+    if (!(rc = q.flush_locked(g))) rc = q.wait_all_unlocking(g, lk);
+  });
+  return rc;
 }
 
 int mi355_group_submit_round(mi355_group *g, mi355_ctx *const *ctxs, int n_streams, uint8_t *const *d_src, uint8_t *const *d_dst, int width, int height,

@@ -11,7 +11,11 @@ host clock around it times work that ended in a device synchronisation. Both mod
 alternate (lone, group, lone, group); each run is --warmup untimed intervals, then --intervals timed ones; the median interval of
 each run is printed, and the median over both runs of a mode with the frames/s it amounts to.
 
-  python tools/bench_colordetect_group.py [--instances N] [--intervals K] [--warmup W] [--out FILE]
+With --no-threads one thread drives all instances: an interval is N lone calls, or N submits followed by N waits (the N-th
+submit fills the rendezvous, the set goes out, the first wait takes its time). No barrier, lock hand-over or condition variable
+is in that figure: it is the one to compare two builds of the library by.
+
+  python tools/bench_colordetect_group.py [--instances N] [--intervals K] [--warmup W] [--no-threads] [--out FILE]
 """
 import argparse
 import os
@@ -67,8 +71,20 @@ def run(n, call, warm, reps):
     return float(np.median(ts)), float(np.percentile(ts, 10)), float(np.percentile(ts, 90))
 
 
+def run_one_thread(interval, warm, reps):
+    """`interval()` on this thread, once per interval; the median and the spread of the timed ones."""
+    ts = []
+    for k in range(warm + reps):
+        t0 = time.perf_counter()
+        interval()
+        if k >= warm:
+            ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), float(np.percentile(ts, 10)), float(np.percentile(ts, 90))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--no-threads", action="store_true", help="one thread drives all instances (N submits, then N waits)")
     ap.add_argument("--instances", type=int, default=32)
     ap.add_argument("--intervals", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -83,7 +99,7 @@ def main():
 
     say("colordetect, %d instances, one %dx%d RGBA device frame each per interval, max-colors 2; %d warm-up + %d timed intervals per run" %
         (n, W, H, a.warmup, a.intervals))
-    say("%-8s %-8s | %-38s | %-38s" % ("content", "quality", "lone: %d contexts on %d threads" % (n, n), "group: rendezvous of %d" % n))
+    say("%-8s %-8s | %-38s | %-38s" % ("content", "quality", "lone: %d contexts on %d threads" % (n, 1 if a.no_threads else n), "group: rendezvous of %d" % n))
     ctxs = [mi355fx.Context(0) for _ in range(n)]
     frames = [c.alloc(n_bytes) for c in ctxs]
     g = mi355fx.Group(0)
@@ -111,9 +127,22 @@ def main():
 
                 before = g.colordetect_stats()
                 res = {"lone": [], "group": []}
+                def lone_interval():
+                    for s in range(n):
+                        lone(s)
+
+                def group_interval():
+                    tk = [g.submit_colordetect(ctxs[s], frames[s], n_bytes, "RGBA", q, 2) for s in range(n)]
+                    for s in range(n):
+                        got[s][1] = g.wait_colordetect(tk[s])
+
                 for _ in range(2):
-                    res["lone"].append(run(n, lone, a.warmup, a.intervals))
-                    res["group"].append(run(n, grouped, a.warmup, a.intervals))
+                    if a.no_threads:
+                        res["lone"].append(run_one_thread(lone_interval, a.warmup, a.intervals))
+                        res["group"].append(run_one_thread(group_interval, a.warmup, a.intervals))
+                    else:
+                        res["lone"].append(run(n, lone, a.warmup, a.intervals))
+                        res["group"].append(run(n, grouped, a.warmup, a.intervals))
                 after = g.colordetect_stats()
                 assert all(x == y and len(x) >= 1 for x, y in got), "group palettes differ from the lone ones"
                 cols = []

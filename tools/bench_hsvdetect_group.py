@@ -12,7 +12,11 @@ alternate (lone, group, lone, group); each run is --warmup untimed intervals, th
 each run is printed, and the median over both runs of a mode with the frames/s it amounts to. Both modes must have written
 identical bytes.
 
-  python tools/bench_hsvdetect_group.py [--instances N] [--intervals K] [--warmup W] [--out FILE]
+With --no-threads one thread drives all instances: an interval is N lone calls and then N synchronisations, or N submits and
+then N waits (the N-th submit fills the rendezvous and the set goes out). No barrier, lock hand-over or condition variable is in
+that figure: it is the one to compare two builds of the library by.
+
+  python tools/bench_hsvdetect_group.py [--instances N] [--intervals K] [--warmup W] [--no-threads] [--out FILE]
 """
 import argparse
 import os
@@ -59,8 +63,20 @@ def run(n, call, warm, reps):
     return float(np.median(ts)), float(np.percentile(ts, 10)), float(np.percentile(ts, 90))
 
 
+def run_one_thread(interval, warm, reps):
+    """`interval()` on this thread, once per interval; the median and the spread of the timed ones."""
+    ts = []
+    for k in range(warm + reps):
+        t0 = time.perf_counter()
+        interval()
+        if k >= warm:
+            ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), float(np.percentile(ts, 10)), float(np.percentile(ts, 90))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--no-threads", action="store_true", help="one thread drives all instances (N submits, then N waits; N lone calls, then N synchronisations)")
     ap.add_argument("--instances", type=int, default=32)
     ap.add_argument("--intervals", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -74,7 +90,7 @@ def main():
         lines.append(text)
 
     say("hsvdetector, %d instances, one RGBx -> RGBA device frame each per interval; %d warm-up + %d timed intervals per run" % (n, a.warmup, a.intervals))
-    say("%-10s | %-38s | %-38s | %s" % ("size", "lone: %d contexts on %d threads" % (n, n), "group: rendezvous of %d" % n, "group / lone"))
+    say("%-10s | %-38s | %-38s | %s" % ("size", "lone: %d contexts on %d threads" % (n, 1 if a.no_threads else n), "group: rendezvous of %d" % n, "group / lone"))
     ctxs = [mi355fx.Context(0) for _ in range(n)]
     g = mi355fx.Group(0)
     g.set_hsvdetect_rendezvous(n, 2_000_000)
@@ -102,9 +118,24 @@ def main():
 
                 before = g.hsvdetect_stats()
                 res = {"lone": [], "group": []}
+                def lone_interval():
+                    for s in range(n):
+                        ctxs[s].hsvdetect_frames_device(src[s], 0, w * 4, "RGBx", dst_lone[s], 0, w * 4, "RGBA", 1, w, h, SETTINGS)
+                    for s in range(n):
+                        ctxs[s].synchronize()
+
+                def group_interval():
+                    tk = [g.submit_hsvdetect(ctxs[s], src[s], w * 4, "RGBx", dst_group[s], w * 4, "RGBA", w, h, SETTINGS) for s in range(n)]
+                    for t in tk:
+                        g.wait_hsvdetect(t)
+
                 for _ in range(2):
-                    res["lone"].append(run(n, lone, a.warmup, a.intervals))
-                    res["group"].append(run(n, grouped, a.warmup, a.intervals))
+                    if a.no_threads:
+                        res["lone"].append(run_one_thread(lone_interval, a.warmup, a.intervals))
+                        res["group"].append(run_one_thread(group_interval, a.warmup, a.intervals))
+                    else:
+                        res["lone"].append(run(n, lone, a.warmup, a.intervals))
+                        res["group"].append(run(n, grouped, a.warmup, a.intervals))
                 after = g.hsvdetect_stats()
                 alphas = set()
                 for s, c in enumerate(ctxs):

@@ -193,6 +193,7 @@ void mi355_ctx_destroy(mi355_ctx *ctx) {
   agingradio_release(ctx);
   mixer_release(ctx);
   yolodec_release(ctx);
+  handdec_release(ctx);
   ebur128_release(ctx);
   hrtf_release(ctx);
   sofa_release(ctx);

@@ -102,6 +102,7 @@ struct mi355_ctx {
   void *agingradio = nullptr;  // mi355::AgingState (agingradio.hip): lowpass filter states, pair counter, seed
   void *mixer = nullptr;       // mi355::MixerState (mixer.hip): the contribution matrix, job tables and the host form's staging
   void *yolodec = nullptr;     // mi355::YoloDecState (yolodec.hip): survivor keys, kept boxes, results
+  void *handdec = nullptr;     // mi355::HandDecState (handdec.hip): params, results, staging
   // host <-> device copies this context has enqueued through the library's own entry points and mi355_buf objects (tests assert
   // that a chain of elements on device buffers costs ONE upload and ONE download: mi355_ctx_transfer_counts)
   unsigned long long n_h2d = 0, n_d2h = 0;
@@ -317,6 +318,7 @@ int mixer_plan(int n_members, const uint32_t *n_inputs, const uint32_t *n_out_ch
 int mixer_launch(MixerTablesBuf *B, hipStream_t stream, const MixerCall *calls, int n, int *kernel_launches, std::string *err);
 void mixer_release(mi355_ctx *ctx);
 void yolodec_release(mi355_ctx *ctx);
+void handdec_release(mi355_ctx *ctx);
 // the checks of mi355_yolodec_tensors_device that need no device; *why names the refusal
 int yolodec_check_args(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates, const char **why);
 // launch sets of the video group's decoder queue (yolodec.hip): tensors of independent instances, job tables

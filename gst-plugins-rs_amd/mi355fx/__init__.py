@@ -115,6 +115,35 @@ def _yolo_params(params):
     return arr, len(params)
 
 
+class HandParams(C.Structure):
+    """mi355_hand_params: the settings of one handdetectiontensordec / handlandmarktensordec instance; frame 0, 0: no frame size."""
+    _fields_ = [("confidence_threshold", C.c_float), ("nms_iou_threshold", C.c_float), ("max_hands", C.c_uint32), ("frame_width", C.c_int32),
+                ("frame_height", C.c_int32)]
+
+
+HAND_MAX = 10   # MI355_HAND_MAX: records per tensor in the outputs
+KP_VISIBILITY = {"UNKNOWN": 0, "VISIBLE": 1, "OCCLUDED": 2}   # mi355_kp_visibility
+# mi355_hand_det and mi355_hand_keypoints as numpy records
+HAND_DET = np.dtype([("xmin", "<f4"), ("ymin", "<f4"), ("xmax", "<f4"), ("ymax", "<f4"), ("rotation", "<f4"), ("rotation_od", "<f4"), ("confidence", "<f4"),
+                     ("index", "<u4"), ("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4"), ("has_od", "<u4"), ("reserved", "<u4", (3,))])
+HAND_KP = np.dtype([("count", "<u4"), ("positions", "<i4", (42,)), ("confidences", "<f4", (21,)), ("visibilities", "u1", (21,)), ("reserved", "u1", (11,))])
+
+
+def _hand_params(params):
+    """One (confidence_thr, nms_iou_thr, max_hands[, frame_width, frame_height]) tuple, a HandParams, or a sequence of either -> a
+    ctypes array. A missing or None frame size is 0, 0."""
+    if isinstance(params, HandParams) or not (hasattr(params[0], "__len__") or isinstance(params[0], HandParams)):
+        params = [params]
+    arr = (HandParams * max(len(params), 1))()
+    for k, q in enumerate(params):
+        if isinstance(q, HandParams):
+            arr[k] = q
+        else:
+            frame = tuple(q[3:5]) if len(q) >= 5 and q[3] is not None else (0, 0)
+            arr[k] = HandParams(float(q[0]), float(q[1]), int(q[2]), int(frame[0]), int(frame[1]))
+    return arr, len(params)
+
+
 class HsvDetectSettings(C.Structure):
     _fields_ = [("hue_ref", C.c_float), ("hue_var", C.c_float), ("saturation_ref", C.c_float),
                 ("saturation_var", C.c_float), ("value_ref", C.c_float), ("value_var", C.c_float)]
@@ -305,6 +334,12 @@ def load_library():
         "mi355_yolodec_tensor": (i, [vp, vp, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "mi355_yolodec_tensors_device": (i, [vp, vp, sz, i, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "mi355_selftest_yolodec_check": (i, [sz, i, i, C.c_uint32, C.c_uint32]),
+        "mi355_handdec_palm_tensor": (i, [vp, vp, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
+        "mi355_handdec_palm_tensors_device": (i, [vp, vp, sz, i, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
+        "mi355_handdec_landmarks_tensor": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(HandParams), vp, vp, C.POINTER(C.c_uint32)]),
+        "mi355_handdec_landmarks_tensors_device": (i, [vp, vp, sz, i, C.c_uint32, C.c_uint32, vp, sz, C.c_uint32, C.POINTER(HandParams), vp, vp,
+                                                       C.POINTER(C.c_uint32)]),
+        "mi355_selftest_handdec_check": (i, [i, sz, i, C.c_uint32, C.c_uint32, sz, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32]),
         "mi355_group_set_yolodec_rendezvous": (i, [vp, i, C.c_uint]),
         "mi355_group_submit_yolodec": (i, [vp, vp, vp, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), C.c_uint32, C.POINTER(C.c_uint64)]),
         "mi355_group_wait_yolodec": (i, [vp, C.c_uint64, vp, C.POINTER(C.c_uint32)]),
@@ -1546,6 +1581,59 @@ class Context:
                                                      dets.ctypes.data, cap, n))
         out = [dets[t * cap:t * cap + min(n[t], cap)].copy() for t in range(n_tensors)]
         return (out, [n[t] for t in range(n_tensors)]) if return_counts else out
+
+    # ---- handdetectiontensordec / handlandmarktensordec (analytics/analytics/src/hand)
+    def handdec_palm(self, tensor, params, return_count=False):
+        """The selected hands of one host palm tensor ([N, 8] float32 rows score, cx, cy, size, kp0x, kp0y, kp2x, kp2y) as a HAND_DET
+        record array, in output order. params: (confidence_thr, nms_iou_thr, max_hands[, frame_width, frame_height])."""
+        a = np.ascontiguousarray(tensor, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("handdec_palm: a [N, 8] tensor")
+        p, _ = _hand_params(params)
+        dets = np.zeros(HAND_MAX, HAND_DET)
+        n = C.c_uint32(0)
+        self._ck(self.L.mi355_handdec_palm_tensor(self.h, a.ctypes.data if a.size else None, a.shape[0], p, dets.ctypes.data, C.byref(n)))
+        out = dets[:n.value].copy()
+        return (out, n.value) if return_count else out
+
+    def handdec_palm_device(self, d_tensors, tensor_pitch_bytes, n_tensors, num_rows, params, return_counts=False):
+        """One HAND_DET record array per device tensor d_tensors + i * tensor_pitch_bytes; params: one tuple per tensor. One launch,
+        one synchronisation."""
+        p, n_p = _hand_params(params)
+        if n_p != n_tensors:
+            raise ValueError("handdec_palm_device: one params tuple per tensor")
+        dets = np.zeros(max(n_tensors, 1) * HAND_MAX, HAND_DET)
+        n = (C.c_uint32 * max(n_tensors, 1))()
+        self._ck(self.L.mi355_handdec_palm_tensors_device(self.h, d_tensors, tensor_pitch_bytes, n_tensors, num_rows, p, dets.ctypes.data, n))
+        out = [dets[t * HAND_MAX:t * HAND_MAX + n[t]].copy() for t in range(n_tensors)]
+        return (out, [n[t] for t in range(n_tensors)]) if return_counts else out
+
+    def handdec_landmarks(self, tensor, params, scores=None):
+        """(HAND_DET records, HAND_KP records) of one host landmark tensor ([H, 21 * D] float32, D >= 2), in output order; scores: the
+        optional hand score vector (hand i has confidence scores[i] if there is one, else 1.0)."""
+        a = np.ascontiguousarray(tensor, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] % 21 != 0:
+            raise ValueError("handdec_landmarks: a [H, 21 * D] tensor")
+        sc = None if scores is None else np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+        p, _ = _hand_params(params)
+        dets, kps = np.zeros(HAND_MAX, HAND_DET), np.zeros(HAND_MAX, HAND_KP)
+        n = C.c_uint32(0)
+        self._ck(self.L.mi355_handdec_landmarks_tensor(self.h, a.ctypes.data if a.size else None, a.shape[0], a.shape[1] // 21,
+                                                       sc.ctypes.data if sc is not None and sc.size else None, 0 if sc is None else sc.size, p, dets.ctypes.data,
+                                                       kps.ctypes.data, C.byref(n)))
+        return dets[:n.value].copy(), kps[:n.value].copy()
+
+    def handdec_landmarks_device(self, d_landmarks, tensor_pitch_bytes, n_tensors, num_hands, kps_dim, params, d_scores=None, score_pitch_bytes=0, num_scores=0):
+        """One (HAND_DET records, HAND_KP records) pair per device tensor d_landmarks + i * tensor_pitch_bytes; params: one tuple per
+        tensor; d_scores: null or num_scores scores per tensor at d_scores + i * score_pitch_bytes. One launch, one synchronisation."""
+        p, n_p = _hand_params(params)
+        if n_p != n_tensors:
+            raise ValueError("handdec_landmarks_device: one params tuple per tensor")
+        dets, kps = np.zeros(max(n_tensors, 1) * HAND_MAX, HAND_DET), np.zeros(max(n_tensors, 1) * HAND_MAX, HAND_KP)
+        n = (C.c_uint32 * max(n_tensors, 1))()
+        self._ck(self.L.mi355_handdec_landmarks_tensors_device(self.h, d_landmarks, tensor_pitch_bytes, n_tensors, num_hands, kps_dim, d_scores, score_pitch_bytes,
+                                                               num_scores, p, dets.ctypes.data, kps.ctypes.data, n))
+        return [(dets[t * HAND_MAX:t * HAND_MAX + n[t]].copy(), kps[t * HAND_MAX:t * HAND_MAX + n[t]].copy()) for t in range(n_tensors)]
 
     # ---- rsaudioecho
     def echo_setup(self, ring_len):

@@ -943,6 +943,86 @@ int mi355_yolodec_tensors_device(mi355_ctx *ctx, const float *d_tensors, size_t 
                                  uint32_t max_dets, uint32_t *n_dets);
 int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates);
 
+/* ---------------------------------------------------------------- handdetectiontensordec / handlandmarktensordec (csrc/handdec.hip)
+ * Replaces the decode loops of the two hand decoders: extract_hands_from_palm_detection with is_valid_palm_candidate_normalized
+ * and apply_nms_to_palm_candidates (analytics/analytics/src/hand/handdetectiontensordec/imp.rs:89-335), extract_hands with
+ * compute_bbox_from_landmarks, compute_rotation_from_landmarks and the loops of attach_keypoint_metadata
+ * (hand/handlandmarktensordec/imp.rs:101-391), and oriented_od_params_from_bbox_and_rotation (hand/helper.rs:69-114). The contract
+ * is DESIGN 4.12; all arithmetic is f32 and unfused. Three stated deviations:
+ *   a. atan2, sin, cos: the reference calls the platform's f32 libm, whose last bit differs between platforms. Here the value is
+ *      the f64 function of the f32 arguments, rounded once to f32.
+ *   b. iou: gst_analytics::image_util::iou_f32 is not in the reference tree. RESTATED WITHOUT SOURCE, PARITY UNPINNED: rects
+ *      (x, y, w = max - min, h = max - min) as helpers.rs:22-37 builds them, right = x + w, bottom = y + h,
+ *      iw = max(0, min(rights) - max(lefts)), ih likewise (f32::max / f32::min), inter = iw * ih,
+ *      union = aw * ah + bw * bh - inter, iou = union > 0 ? inter / union : 0.
+ *   c. sign and payload of a NaN that arithmetic produces are the hardware's and outside the contract.
+ *   palm       [N, 8] row-major rows score, cx, cy, size, kp0x, kp0y, kp2x, kp2y (:133-153). Dropped iff score <
+ *              confidence_threshold (IEEE: a NaN stays), iff size <= 0, iff the validity test fails (:231-296); a frame size scales
+ *              the box (:177-183); descending score under f32::total_cmp, equal scores in ascending row index (sort_by is
+ *              stable); greedy NMS as one class with the threshold clamped to [0, 1] (:315), stopping at max_hands.
+ *   landmarks  [H, 21 * D] row-major, D >= 2, and an optional score vector: hand i has confidence scores[i] if i < num_scores, else
+ *              1.0 (:274-277); the box is min / max over the finite points padded by 0.15 (:171-237), rotation from points 0 and
+ *              9 unchecked (:148-169); sorted as palm; NMS with the threshold NOT clamped (:297-312). `attach-bounding-box` stays
+ *              with the caller: the record always carries the box and has_od.
+ *   record     the f32 box, rotation, rotation_od = rotation + (-FRAC_PI_2), confidence, the row / hand index, and what
+ *              oriented_od_params_from_bbox_and_rotation returns: x, y, width, height with has_od = 1, or has_od = 0 and zeros
+ *              when it returns None (the hand still counted toward max_hands and still suppressed others). mi355_hand_keypoints:
+ *              the finite points of the hand in order, compacted (:337-373): count, positions (x as i32, y as i32), confidences
+ *              (point[2] if D >= 3, else the hand's), visibilities (MI355_KP_*); entries from count on are zero.
+ *   params     frame_width and frame_height both > 0: Some((w, h)); both 0: None; anything else MI355_ERR_INVALID_ARG. max_hands
+ *              1..8 for palm, 1..10 for landmarks, otherwise MI355_ERR_INVALID_ARG.
+ *   _tensor          host tensor(s); synchronous.
+ *   _tensors_device  n_tensors device tensors of one shape at d + i * pitch, each with its OWN params p[i]; dets (and kps) hold
+ *                    n_tensors x MI355_HAND_MAX records - tensor i's at [i * MI355_HAND_MAX ...), the first n_hands[i] written.
+ *                    ONE launch (one block per tensor), one synchronisation and one download per call, whatever n_tensors is.
+ *                    d_scores may be NULL (no scores: num_scores is then ignored); otherwise tensor i's num_scores scores are at
+ *                    d_scores + i * score_pitch_bytes.
+ *   Limits: palm num_rows 0..4096 and num_hands 0..1024 (0: counts 0, no launch), kps_dim 2..16 (below 2:
+ *   MI355_ERR_INVALID_ARG, as decode_landmark_hands refuses it), num_scores 0..1024, n_tensors 1..1024 (below 1:
+ *   MI355_ERR_INVALID_ARG); above the limits: MI355_ERR_UNSUPPORTED. Pitches at least the tensor (the scores) and a multiple of 4,
+ *   pointers 4-byte aligned: otherwise MI355_ERR_INVALID_ARG. Scratch belongs to the context and grows to the largest call seen.
+ *   mi355_selftest_handdec_check : host only, no device: the status the shape and params checks of the entry points give.
+ *              decoder 0: palm (rows = num_rows; kps_dim, score_pitch_bytes, num_scores ignored), 1: landmarks (rows = num_hands;
+ *              the score pitch is checked when num_scores > 0). */
+#define MI355_HAND_MAX 10 /* records per tensor in the outputs */
+typedef enum mi355_kp_visibility { MI355_KP_UNKNOWN = 0, MI355_KP_VISIBLE = 1, MI355_KP_OCCLUDED = 2 } mi355_kp_visibility;
+typedef struct mi355_hand_params {
+  float confidence_threshold;        /* "confidence-threshold" */
+  float nms_iou_threshold;           /* "nms-iou-threshold" */
+  uint32_t max_hands;                /* "max-hands" */
+  int32_t frame_width, frame_height; /* the negotiated VideoInfo; 0, 0: none */
+} mi355_hand_params;
+typedef struct mi355_hand_det {
+  float xmin, ymin, xmax, ymax;      /* the f32 box */
+  float rotation, rotation_od;       /* the hand axis; what add_oriented_od_mtd receives (0 when has_od is 0) */
+  float confidence;
+  uint32_t index;                    /* row of the palm tensor / hand of the landmark tensor */
+  int32_t x, y, width, height;       /* what add_oriented_od_mtd receives (0 when has_od is 0) */
+  uint32_t has_od;                   /* 1: oriented_od_params_from_bbox_and_rotation returned Some */
+  uint32_t reserved[3];              /* 0 */
+} mi355_hand_det;
+typedef struct mi355_hand_keypoints {
+  uint32_t count;                    /* finite points */
+  int32_t positions[42];             /* x0, y0, x1, y1, ... */
+  float confidences[21];
+  uint8_t visibilities[21];          /* mi355_kp_visibility */
+  uint8_t reserved[11];              /* 0 */
+} mi355_hand_keypoints;
+int mi355_handdec_palm_tensor(mi355_ctx *ctx, const float *data, uint32_t num_rows, const mi355_hand_params *p, mi355_hand_det *dets,
+                              uint32_t *n_hands);
+int mi355_handdec_palm_tensors_device(mi355_ctx *ctx, const float *d_tensors, size_t tensor_pitch_bytes, int n_tensors,
+                                      uint32_t num_rows, const mi355_hand_params *p, mi355_hand_det *dets, uint32_t *n_hands);
+int mi355_handdec_landmarks_tensor(mi355_ctx *ctx, const float *landmarks, uint32_t num_hands, uint32_t kps_dim, const float *scores,
+                                   uint32_t num_scores, const mi355_hand_params *p, mi355_hand_det *dets, mi355_hand_keypoints *kps,
+                                   uint32_t *n_hands);
+int mi355_handdec_landmarks_tensors_device(mi355_ctx *ctx, const float *d_landmarks, size_t tensor_pitch_bytes, int n_tensors,
+                                           uint32_t num_hands, uint32_t kps_dim, const float *d_scores, size_t score_pitch_bytes,
+                                           uint32_t num_scores, const mi355_hand_params *p, mi355_hand_det *dets,
+                                           mi355_hand_keypoints *kps, uint32_t *n_hands);
+int mi355_selftest_handdec_check(int decoder, size_t tensor_pitch_bytes, int n_tensors, uint32_t rows, uint32_t kps_dim,
+                                 size_t score_pitch_bytes, uint32_t num_scores, uint32_t max_hands, int32_t frame_width,
+                                 int32_t frame_height);
+
 /* The tensor decoders across independent element instances. The reference element receives one tensor per buffer per instance
  * (analytics/analytics/src/yolotensordec/imp.rs:234-422); N decoders in one process are N lone calls per frame period, each almost
  * all launch, synchronisation and copy latency. submit_yolodec queues one device tensor of stream `ctx` and whatever is

@@ -19,16 +19,18 @@
 //   * results are the two element launches', bit for bit (same arithmetic, same table);
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
-// Four more queues live beside the filter batches, each with its own HIP stream, pending list, rendezvous and stats, and none
-// touching another: videocompare pairs (submit_compare: its own code - classes, lanes, collection per lane) and three SET QUEUES,
+// Five more queues live beside the filter batches, each with its own HIP stream, pending list, rendezvous and stats, and none
+// touching another: videocompare pairs (submit_compare: its own code - classes, lanes, collection per lane) and four SET QUEUES,
 // which are one protocol written once (SetQueue<Kind>: submit's tail, flush in sets of up to 32 in submission order, the
-// lingering wait, collect-once results, retire, stats, destroy) with three kinds: colordetect frames (submit_colordetect),
+// lingering wait, collect-once results, retire, stats, destroy) with four kinds: colordetect frames (submit_colordetect),
 // hsvdetector frames (submit_hsvdetect: frames of independent instances - own size, strides, formats, settings - as at most two
-// launches over a job table, hsv_kernels.hip) and decoder tensors (submit_yolodec: tensors of independent yolov8tensordec2 /
+// launches over a job table, hsv_kernels.hip), decoder tensors (submit_yolodec: tensors of independent yolov8tensordec2 /
 // yoloxtensordec instances - own shape, layout, settings - as at most three launches over job tables and one download,
-// yolodec.hip). A fourth kind is a struct beside CdKind / HdKind / YdKind - payload, result, kSetMax, its names, ensure, plan,
-// its pinned block (if any), launch, result, failed, destroy - a SetQueue<Kind> member of mi355_group, a line in
-// for_each_set_queue and its four entry points; nothing of the protocol is written again.
+// yolodec.hip) and hand tensors (submit_handdec_palm / _landmarks: tensors of independent handdetectiontensordec /
+// handlandmarktensordec instances - own shape and settings - as at most two launches over job tables, no upload and one download,
+// handdec.hip). A fifth kind is a struct beside CdKind / HdKind / YdKind / HnKind - payload, result, kSetMax, its names, ensure,
+// plan, its pinned block (if any), launch, result, failed, destroy - a SetQueue<Kind> member of mi355_group, a line in
+// for_each_set_queue and its entry points; nothing of the protocol is written again.
 // The group has ONE mutex, ticket sequence, event free list and last_error (GroupCore); every queue uses those. Tickets are one
 // sequence; a wait entry refuses a ticket of another queue.
 // No persistent kernel: nothing here can hang the GPU waiting for the host, a launch is a launch.
@@ -153,7 +155,7 @@ Waited wait_seq_unlocking(std::deque<S> &sets, uint64_t seq, std::unique_lock<st
   return Waited::kDone;
 }
 
-// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its three kinds
+// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its four kinds
 // A kind is what differs between the queues: what is submitted (Payload), what a wait takes (Result), what a launch reads (Plan),
 // what a set in flight owns (SetData), how a set is launched and read back, and the resources of first use. The protocol is below.
 
@@ -386,6 +388,95 @@ struct YdKind {
     yolodec_set_scratch_free(scratch);
     (void)hipStreamDestroy(stream);
     for (YdBlock &b : blocks) (void)hipHostFree(b.h);
+  }
+};
+
+// ---- handdetectiontensordec / handlandmarktensordec across independent element instances (mi355_group_submit_handdec_palm /
+// _landmarks): one device tensor per submit; its count and records come back through the set's pinned block. Consecutive sets share
+// the device slab, which holds one set's results at their maximum - so the pinned blocks have ONE size, as colordetect's have.
+struct HnOut { int status, decoder; uint32_t n_hands; std::vector<mi355_hand_det> dets; std::vector<mi355_hand_keypoints> kps; };   // the first n_hands
+struct HnSlot { int decoder; uint32_t rows, kp_slot; };
+constexpr int kHnBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
+struct HnKind {
+  using Payload = HnTensor;
+  using Result = HnOut;
+  struct Plan { HnTensor tensors[kHnSetMax]; uint32_t kp_slot[kHnSetMax]; uint64_t totals[4]; };
+  struct SetData {
+    void *h_block = nullptr;     // pinned: the set's own results until it is collected (nullptr: no tensor had rows)
+    std::vector<HnSlot> slots;   // its tensors, by job (as the set's tickets are)
+  };
+  static constexpr int kSetMax = kHnSetMax;
+  static constexpr const char *kName = "hand decoder", *kItem = "hand tensor", *kWaitEntry = "mi355_group_wait_handdec";
+  hipStream_t stream = nullptr;
+  HnSetScratch *scratch = nullptr;
+  std::vector<void *> blocks;  // free pinned result blocks, all of handdec_set_block_bytes()
+
+  bool set_up() const { return scratch != nullptr; }
+  // stream, device slab and the first pinned blocks: at the first submit, never inside a launch set
+  int ensure(GroupCore *g) {
+    if (scratch) return MI355_OK;
+    if (int rc = queue_stream(g, &stream, kName)) return rc;
+    while ((int)blocks.size() < kHnBlocksAtFirstUse) {
+      void *b = nullptr;
+      if (hipHostMalloc(&b, handdec_set_block_bytes(), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the hand decoder queue");
+      }
+      blocks.push_back(b);
+    }
+    int st = MI355_OK;
+    std::string err;
+    scratch = handdec_set_scratch_new(&st, &err);
+    return scratch ? MI355_OK : fail(g, st, "group: " + err);
+  }
+  // the set's layout, by the plan the launch itself uses: which tensors have a block, the landmark tensors' keypoint slots
+  int plan(const QItem<HnTensor> *take, size_t n, Plan *p, std::string *err) const {
+    int decoder[kHnSetMax];
+    uint32_t rows[kHnSetMax], block[kHnSetMax];
+    for (size_t i = 0; i < n; i++) {
+      const HnTensor &t = p->tensors[i] = take[i].p;
+      decoder[i] = t.decoder; rows[i] = t.rows;
+    }
+    const int rc = handdec_set_plan((int)n, decoder, rows, block, p->kp_slot, p->totals);
+    if (rc) *err = "group: bad hand decoder set";
+    return rc;
+  }
+  // a set without a row has nothing to copy: it takes no block (and still gets its event and its set)
+  bool no_free_block(const Plan &p) const { return p.totals[3] && blocks.empty(); }
+  bool take_block(const Plan &p, SetData *d) {
+    if (!p.totals[3]) return true;
+    if (!blocks.empty()) { d->h_block = blocks.back(); blocks.pop_back(); }
+    // (more sets in flight than ever before: one more block, kept from then on)
+    else if (hipHostMalloc(&d->h_block, handdec_set_block_bytes(), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); d->h_block = nullptr; }
+    return d->h_block != nullptr;
+  }
+  static bool holds_block(const SetData &d) { return d.h_block != nullptr; }
+  void release(SetData *d) {
+    if (d->h_block) blocks.push_back(d->h_block);
+    d->h_block = nullptr;
+  }
+  int launch(const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
+    for (size_t i = 0; i < n; i++) d->slots.push_back(HnSlot{p.tensors[i].decoder, p.tensors[i].rows, p.kp_slot[i]});
+    return handdec_launch_set(scratch, stream, p.tensors, (int)n, d->h_block, d->h_block ? handdec_set_block_bytes() : 0, launches, err);
+  }
+  void launched(const GroupCore *, const Plan &, size_t) const {}
+  // count and records MOVE out of the pinned block: the block is free for a later set once this one is collected
+  void result(const SetData &d, size_t i, HnOut *o) const {
+    const HnSlot &sl = d.slots[i];
+    mi355_hand_det dets[MI355_HAND_MAX];
+    mi355_hand_keypoints kps[MI355_HAND_MAX];
+    o->status = MI355_OK;
+    o->decoder = sl.decoder;
+    handdec_set_result(d.h_block, (int)d.slots.size(), (int)i, sl.decoder, sl.rows, sl.kp_slot, dets, kps, &o->n_hands);
+    o->dets.assign(dets, dets + o->n_hands);
+    if (sl.decoder == 1) o->kps.assign(kps, kps + o->n_hands);
+  }
+  static void failed(const HnTensor &t, int rc, HnOut *o) { o->status = rc; o->decoder = t.decoder; o->n_hands = 0; }
+  static int status(const HnOut &o) { return o.status; }
+  void destroy() {
+    handdec_set_scratch_free(scratch);
+    (void)hipStreamDestroy(stream);
+    for (void *b : blocks) (void)hipHostFree(b);
   }
 };
 
@@ -644,11 +735,12 @@ struct mi355_group : GroupCore {
   int expected_streams = 0;                  // rendezvous: a waiter lingers until this many pairs are pending ...
   unsigned linger_us = 0;                    // ... or this long (mi355_group_set_rendezvous)
   std::condition_variable cv;                // "a compare batch has been launched"
-  // ---- the three set queues: each its own stream (and scratch, and blocks), created at its first submit, independent of the
+  // ---- the four set queues: each its own stream (and scratch, and blocks), created at its first submit, independent of the
   // two queues above and of each other
   SetQueue<CdKind> cd;   // colordetect frames
   SetQueue<HdKind> hd;   // hsvdetector frames
   SetQueue<YdKind> yd;   // decoder tensors
+  SetQueue<HnKind> hn;   // hand tensors (palm and landmarks)
 };
 
 namespace {
@@ -942,6 +1034,7 @@ void for_each_set_queue(mi355_group *g, F &&f) {
   f(g->cd);
   f(g->hd);
   f(g->yd);
+  f(g->hn);
 }
 
 // A set queue's ticket presented to an entry point that serves another queue: refused (non-zero), and left collectable.
@@ -1332,6 +1425,76 @@ int mi355_group_yolodec_stats(mi355_group *g, uint64_t stats[4]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
   g->yd.stats(stats);
+  return MI355_OK;
+}
+
+int mi355_group_set_handdec_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
+  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  g->hn.set_rendezvous(expected_streams, linger_us);
+  return MI355_OK;
+}
+
+// the two submits' common part: the lone entry points' checks for one tensor at a pitch equal to the tensor, in their order
+static int submit_handdec(mi355_group *g, mi355_ctx *ctx, int decoder, const float *d_tensor, uint32_t rows, uint32_t kps_dim, const float *d_scores,
+                          uint32_t num_scores, const mi355_hand_params *p, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !p || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context, settings or ticket");
+  if (!d_scores) num_scores = 0;   // no scores: num_scores is ignored
+  const char *why = nullptr;
+  const size_t tensor_bytes = decoder == 0 ? (size_t)rows * 32 : (size_t)rows * 21 * kps_dim * 4;
+  int rc = handdec_check_args(decoder, tensor_bytes, 1, rows, kps_dim, (size_t)num_scores * 4, num_scores, &why);
+  if (!rc) rc = handdec_check_params(decoder, p->max_hands, p->frame_width, p->frame_height, &why);
+  if (rc) return fail(g, rc, why);
+  if (rows && (!d_tensor || (uintptr_t)d_tensor % 4 != 0 || (uintptr_t)d_scores % 4 != 0)) return fail(g, MI355_ERR_INVALID_ARG, "handdec: null or misaligned tensors");
+  // a tensor without rows is not read: it does not make the set wait for its stream (the model's last kernel, an upload)
+  return g->hn.submit(g, ctx, HnTensor{decoder, d_tensor, rows, kps_dim, d_scores, num_scores, *p}, rows != 0, ticket);
+}
+
+int mi355_group_submit_handdec_palm(mi355_group *g, mi355_ctx *ctx, const float *d_tensor, uint32_t num_rows, const mi355_hand_params *p, uint64_t *ticket) {
+  return submit_handdec(g, ctx, 0, d_tensor, num_rows, 0, nullptr, 0, p, ticket);
+}
+
+int mi355_group_submit_handdec_landmarks(mi355_group *g, mi355_ctx *ctx, const float *d_landmarks, uint32_t num_hands, uint32_t kps_dim, const float *d_scores,
+                                         uint32_t num_scores, const mi355_hand_params *p, uint64_t *ticket) {
+  return submit_handdec(g, ctx, 1, d_landmarks, num_hands, kps_dim, d_scores, num_scores, p, ticket);
+}
+
+int mi355_group_wait_handdec(mi355_group *g, uint64_t ticket, mi355_hand_det *dets, mi355_hand_keypoints *kps, uint32_t *n_hands) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!dets || !n_hands) return fail(g, MI355_ERR_INVALID_ARG, "group: null result arrays");
+  if (!kps) {
+    // Only a palm ticket has no keypoint records to take. The refusal leaves the result collectable, so the decoder is looked up
+    // wherever the tensor stands - pending, in a set in flight, or collected into `results` - and not by taking the result out
+    // first. (A ticket that is not this queue's has no decoder here and is refused below.)
+    SetQueue<HnKind> &q = g->hn;
+    int decoder = 0;
+    for (const auto &d : q.pending)
+      if (d.ticket == ticket) decoder = d.p.decoder;
+    auto w = q.where.find(ticket);
+    if (w != q.where.end())
+      for (const auto &s : q.sets)
+        if (s.seq == w->second)
+          for (size_t i = 0; i < s.tickets.size(); i++)
+            if (s.tickets[i] == ticket) decoder = s.data.slots[i].decoder;
+    auto r = q.results.find(ticket);
+    if (r != q.results.end()) decoder = r->second.decoder;
+    if (decoder == 1) return fail(g, MI355_ERR_INVALID_ARG, "group: null keypoint records for a landmark tensor");
+  }
+  HnOut res;
+  if (int rc = g->hn.wait(g, L.lk, ticket, &res)) return rc;
+  *n_hands = res.n_hands;
+  if (!res.dets.empty()) std::memcpy(dets, res.dets.data(), res.dets.size() * sizeof(mi355_hand_det));
+  if (!res.kps.empty()) std::memcpy(kps, res.kps.data(), res.kps.size() * sizeof(mi355_hand_keypoints));
+  return MI355_OK;
+}
+
+int mi355_group_handdec_stats(mi355_group *g, uint64_t stats[4]) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  g->hn.stats(stats);
   return MI355_OK;
 }
 

@@ -35,6 +35,9 @@
 //   handdec_landmark_kernel  one block per tensor, one wave per hand in turn: lanes 0-20 load a point each, wave min / max over the
 //                            finite points, box and rotation into LDS by hand index; then the same key list, sort and selection.
 //                            Selected hands write their box record and their compacted keypoint record (assembled in LDS).
+//   handdec_palm_jobs_kernel / handdec_landmark_jobs_kernel  the same two bodies (palm_decode, landmark_decode) over a job table in the
+//                            kernel arguments: block b decodes job b - its own tensor, shape and settings - into the result slab of a
+//                            launch set of the video group's hand-decoder queue (handdec_launch_set, group.hip). No upload per set.
 #include "internal.hpp"
 
 #include <climits>
@@ -294,18 +297,16 @@ __device__ __forceinline__ void write_det(const Selected &S, uint32_t j, const m
   out[j] = d;
 }
 
-// tensors: [T] at a pitch; dets: [T][MI355_HAND_MAX]; n_hands: [T]
-__global__ __launch_bounds__(kPalmThreads) void handdec_palm_kernel(const float *__restrict__ tensors, size_t pitch_floats, uint32_t N,
-                                                                 const mi355_hand_params *__restrict__ params, mi355_hand_det *__restrict__ dets,
-                                                                 uint32_t *__restrict__ n_hands) {
+// One palm tensor by one block of kPalmThreads: data [N][8], its MI355_HAND_MAX records and its count. The body of the lone kernel and
+// of its job form: both run these instructions on this LDS layout, so a tensor's bytes do not depend on which of the two carried it.
+// *n_hands is written on every path.
+__device__ __forceinline__ void palm_decode(const float *__restrict__ data, uint32_t N, const mi355_hand_params &P, mi355_hand_det *__restrict__ dets,
+                                            uint32_t *__restrict__ n_hands) {
   __shared__ unsigned long long K[kMaxRows];
   __shared__ uint32_t passed[kMaxRows];
   __shared__ Selected S;
   __shared__ uint32_t n_passed, count;
-  const uint32_t t = blockIdx.x;
   const int tid = threadIdx.x;
-  const mi355_hand_params P = params[t];
-  const float *__restrict__ data = tensors + (size_t)t * pitch_floats;
   if (tid == 0) n_passed = count = 0;
   __syncthreads();
   // rule 1 on every row (the row's first 16 bytes): the rows that pass are compacted, so that the f64 functions of rules 2 and 4 run in
@@ -340,7 +341,7 @@ __global__ __launch_bounds__(kPalmThreads) void handdec_palm_kernel(const float 
   __syncthreads();
   const uint32_t n = count < N ? count : N;
   if (n == 0) {
-    if (tid == 0) n_hands[t] = 0;
+    if (tid == 0) *n_hands = 0;
     return;
   }
   sort_keys<kPalmThreads>(K, n);
@@ -353,29 +354,59 @@ __global__ __launch_bounds__(kPalmThreads) void handdec_palm_kernel(const float 
       (void)palm_candidate(row[0], row[1], P, b, rot);   // true: the row passed it above
     });
     const uint32_t m = S.m;
-    if ((uint32_t)tid < m) write_det(S, (uint32_t)tid, P, dets + (size_t)t * MI355_HAND_MAX);
-    if (tid == 0) n_hands[t] = m;
+    if ((uint32_t)tid < m) write_det(S, (uint32_t)tid, P, dets);
+    if (tid == 0) *n_hands = m;
   }
+}
+
+// tensors: [T] at a pitch; dets: [T][MI355_HAND_MAX]; n_hands: [T]
+__global__ __launch_bounds__(kPalmThreads) void handdec_palm_kernel(const float *__restrict__ tensors, size_t pitch_floats, uint32_t N,
+                                                                 const mi355_hand_params *__restrict__ params, mi355_hand_det *__restrict__ dets,
+                                                                 uint32_t *__restrict__ n_hands) {
+  const uint32_t t = blockIdx.x;
+  const mi355_hand_params P = params[t];
+  palm_decode(tensors + (size_t)t * pitch_floats, N, P, dets + (size_t)t * MI355_HAND_MAX, n_hands + t);
+}
+
+// ---- the job forms (launch sets of the video group's hand-decoder queue): block b decodes job b of a table passed by value in the
+// kernel arguments - the tensor, its shape and its settings - into the set's result slab: counts[slot], dets[slot][MI355_HAND_MAX],
+// kps[kp_slot][MI355_HAND_MAX]. Only jobs with rows are in a table.
+struct HnPalmJob {
+  const float *data;
+  uint32_t N, slot;   // slot: the job's index in its set
+  mi355_hand_params p;
+  uint32_t pad;
+};
+struct HnPalmTable { HnPalmJob job[MI355_HANDDEC_SET_MAX]; };
+struct HnLandmarkJob {
+  const float *data, *scores;   // scores: null or num_scores floats
+  uint32_t H, slot, D, num_scores, kp_slot;   // kp_slot: the job's index among the landmark jobs of its set
+  mi355_hand_params p;
+};
+struct HnLandmarkTable { HnLandmarkJob job[MI355_HANDDEC_SET_MAX]; };
+static_assert(sizeof(HnPalmJob) == 40 && sizeof(HnLandmarkJob) == 56, "the jobs have no padding holes");
+static_assert(sizeof(HnPalmTable) + 64 <= 4096 && sizeof(HnLandmarkTable) + 64 <= 4096, "a job table and the slab pointers are passed in the kernel arguments");
+
+__global__ __launch_bounds__(kPalmThreads) void handdec_palm_jobs_kernel(const HnPalmTable T, mi355_hand_det *__restrict__ dets, uint32_t *__restrict__ n_hands) {
+  const HnPalmJob &J = T.job[blockIdx.x];
+  const mi355_hand_params P = J.p;
+  palm_decode(J.data, J.N, P, dets + (size_t)J.slot * MI355_HAND_MAX, n_hands + J.slot);
 }
 
 struct KpScratch { uint32_t w[sizeof(mi355_hand_keypoints) / 4]; };
 
-// landmarks: [T][H][21 * D] at a pitch; scores: null or [T][num_scores] at a pitch; dets, kps: [T][MI355_HAND_MAX]
-__global__ __launch_bounds__(kThreads) void handdec_landmark_kernel(const float *__restrict__ tensors, size_t pitch_floats, uint32_t H, uint32_t D,
-                                                                     const float *__restrict__ scores, size_t score_pitch_floats, uint32_t num_scores,
-                                                                     const mi355_hand_params *__restrict__ params, mi355_hand_det *__restrict__ dets,
-                                                                     mi355_hand_keypoints *__restrict__ kps, uint32_t *__restrict__ n_hands) {
+// One landmark tensor by one block of kThreads: data [H][21 * D], sc null or num_scores scores, its MI355_HAND_MAX box and keypoint
+// records and its count. The body of the lone kernel and of its job form, as palm_decode is. *n_hands is written on every path.
+__device__ __forceinline__ void landmark_decode(const float *__restrict__ data, uint32_t H, uint32_t D, const float *__restrict__ sc, uint32_t num_scores,
+                                                const mi355_hand_params &P, mi355_hand_det *__restrict__ dets, mi355_hand_keypoints *__restrict__ kps,
+                                                uint32_t *__restrict__ n_hands) {
   __shared__ unsigned long long K[kMaxHands];
   __shared__ float4 hbox[kMaxHands];
   __shared__ float hrot[kMaxHands];
   __shared__ Selected S;
   __shared__ KpScratch kp[kWaves];
   __shared__ uint32_t count;
-  const uint32_t t = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const mi355_hand_params P = params[t];
-  const float *__restrict__ data = tensors + (size_t)t * pitch_floats;
-  const float *__restrict__ sc = scores ? scores + (size_t)t * score_pitch_floats : nullptr;
   const size_t hand_floats = (size_t)21 * D;
   if (tid == 0) count = 0;
   __syncthreads();
@@ -411,7 +442,7 @@ __global__ __launch_bounds__(kThreads) void handdec_landmark_kernel(const float 
   __syncthreads();
   const uint32_t n = count < H ? count : H;
   if (n == 0) {
-    if (tid == 0) n_hands[t] = 0;
+    if (tid == 0) *n_hands = 0;
     return;
   }
   sort_keys<kThreads>(K, n);
@@ -426,8 +457,8 @@ __global__ __launch_bounds__(kThreads) void handdec_landmark_kernel(const float 
       rot = hrot[h];
     });
     const uint32_t m = S.m;
-    if ((uint32_t)tid < m) write_det(S, (uint32_t)tid, P, dets + (size_t)t * MI355_HAND_MAX);
-    if (tid == 0) n_hands[t] = m;
+    if ((uint32_t)tid < m) write_det(S, (uint32_t)tid, P, dets);
+    if (tid == 0) *n_hands = m;
   }
   __syncthreads();
   // the keypoint records: a wave per selected hand in turn, assembled in the wave's LDS record, then copied out whole
@@ -463,10 +494,28 @@ __global__ __launch_bounds__(kThreads) void handdec_landmark_kernel(const float 
     }
     if (lane == 0) w[0] = (uint32_t)__popcll(mask);
     __threadfence_block();
-    uint32_t *out = reinterpret_cast<uint32_t *>(kps + (size_t)t * MI355_HAND_MAX + j);
+    uint32_t *out = reinterpret_cast<uint32_t *>(kps + j);
     for (uint32_t e = (uint32_t)lane; e < kWords; e += 64) out[e] = w[e];
     __threadfence_block();   // the wave's record is assembled again for its next hand
   }
+}
+
+// landmarks: [T][H][21 * D] at a pitch; scores: null or [T][num_scores] at a pitch; dets, kps: [T][MI355_HAND_MAX]
+__global__ __launch_bounds__(kThreads) void handdec_landmark_kernel(const float *__restrict__ tensors, size_t pitch_floats, uint32_t H, uint32_t D,
+                                                                     const float *__restrict__ scores, size_t score_pitch_floats, uint32_t num_scores,
+                                                                     const mi355_hand_params *__restrict__ params, mi355_hand_det *__restrict__ dets,
+                                                                     mi355_hand_keypoints *__restrict__ kps, uint32_t *__restrict__ n_hands) {
+  const uint32_t t = blockIdx.x;
+  const mi355_hand_params P = params[t];
+  landmark_decode(tensors + (size_t)t * pitch_floats, H, D, scores ? scores + (size_t)t * score_pitch_floats : nullptr, num_scores, P,
+                  dets + (size_t)t * MI355_HAND_MAX, kps + (size_t)t * MI355_HAND_MAX, n_hands + t);
+}
+
+__global__ __launch_bounds__(kThreads) void handdec_landmark_jobs_kernel(const HnLandmarkTable T, mi355_hand_det *__restrict__ dets,
+                                                                          mi355_hand_keypoints *__restrict__ kps, uint32_t *__restrict__ n_hands) {
+  const HnLandmarkJob &J = T.job[blockIdx.x];
+  const mi355_hand_params P = J.p;
+  landmark_decode(J.data, J.H, J.D, J.scores, J.num_scores, P, dets + (size_t)J.slot * MI355_HAND_MAX, kps + (size_t)J.kp_slot * MI355_HAND_MAX, n_hands + J.slot);
 }
 
 }  // namespace
@@ -611,6 +660,132 @@ static int handdec_enter(mi355_ctx *ctx, int decoder, size_t pitch_bytes, int n_
   return MI355_OK;
 }
 
+// ---- launch sets of the video group's hand-decoder queue
+
+static size_t set_bytes(uint64_t n_jobs, uint64_t n_landmark_jobs) { return kHnCountsBytes + dets_bytes((uint32_t)n_jobs) + kps_bytes((uint32_t)n_landmark_jobs); }
+constexpr size_t kHnSlabBytes = kHnCountsBytes + (size_t)kHnSetMax * MI355_HAND_MAX * (sizeof(mi355_hand_det) + sizeof(mi355_hand_keypoints));
+static_assert(kHnCountsBytes >= kHnSetMax * sizeof(uint32_t) && kHnCountsBytes % 8 == 0, "the counts come first and the records behind them stay aligned");
+static_assert(kHnSlabBytes == 128 + 32 * 640 + 32 * 2880, "the slab's maximum: pinned blocks are of one size");
+
+// the layout of one set (mi355_selftest_handdec_set_plan; handdec_launch_set fills its tables with it)
+int handdec_set_plan(int n_jobs, const int *decoder, const uint32_t *rows, uint32_t *block, uint32_t *kp_slot, uint64_t totals[4]) {
+  if (n_jobs < 0 || n_jobs > kHnSetMax || !totals) return MI355_ERR_INVALID_ARG;
+  if (n_jobs > 0 && (!decoder || !rows || !block || !kp_slot)) return MI355_ERR_INVALID_ARG;
+  for (int j = 0; j < n_jobs; j++)
+    if (decoder[j] != 0 && decoder[j] != 1) return MI355_ERR_INVALID_ARG;
+  for (int j = 0; j < n_jobs; j++)
+    if (rows[j] > (decoder[j] == 0 ? kMaxRows : kMaxHands)) return MI355_ERR_UNSUPPORTED;
+  uint64_t t[4] = {0, 0, 0, 0};   // palm blocks, landmark blocks, landmark jobs, bytes copied
+  for (int j = 0; j < n_jobs; j++) {
+    block[j] = rows[j] ? (uint32_t)t[decoder[j]]++ : UINT32_MAX;
+    kp_slot[j] = decoder[j] == 1 ? (uint32_t)t[2]++ : UINT32_MAX;
+  }
+  if (t[0] + t[1]) t[3] = set_bytes((uint64_t)n_jobs, t[2]);
+  for (int k = 0; k < 4; k++) totals[k] = t[k];
+  return MI355_OK;
+}
+
+// The queue's device scratch is the result slab of ONE set, at its maximum (kHnSlabBytes): consecutive sets share it, ordered on the
+// queue's stream - a set's copy precedes the next set's kernels. NOTHING in it is cleared between sets: it holds no counter that a
+// kernel adds to. A job with rows has a block, and every block writes its count on every path (palm_decode, landmark_decode: 0 on the
+// early return, the selected hands otherwise) and exactly that many records; a job without rows has no block and its count is 0 on
+// the host (the queue never reads its slot). What an earlier set left in a slot is therefore never read.
+struct HnSetScratch {
+  uint8_t *d_out = nullptr;
+};
+
+HnSetScratch *handdec_set_scratch_new(int *status, std::string *err) {
+  auto *S = new HnSetScratch();
+  if (hipMalloc((void **)&S->d_out, kHnSlabBytes) != hipSuccess) {
+    (void)hipGetLastError();
+    delete S;
+    *status = MI355_ERR_OUT_OF_MEMORY;
+    *err = "hipMalloc(handdec set results)";
+    return nullptr;
+  }
+  *status = MI355_OK;
+  return S;
+}
+
+void handdec_set_scratch_free(HnSetScratch *S) {
+  if (!S) return;
+  if (S->d_out) (void)hipFree(S->d_out);
+  delete S;
+}
+
+size_t handdec_set_block_bytes() { return kHnSlabBytes; }
+
+int handdec_launch_set(HnSetScratch *S, hipStream_t stream, const HnTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
+                       std::string *err) {
+  *kernel_launches = 0;
+  if (!S || !tensors || n < 1 || n > kHnSetMax) { *err = "handdec: bad launch set"; return MI355_ERR_INVALID_ARG; }
+  int decoder[kHnSetMax];
+  uint32_t rows[kHnSetMax], block[kHnSetMax], kp_slot[kHnSetMax];
+  uint64_t totals[4];
+  for (int i = 0; i < n; i++) { decoder[i] = tensors[i].decoder; rows[i] = tensors[i].rows; }
+  const int rc = handdec_set_plan(n, decoder, rows, block, kp_slot, totals);
+  if (rc) { *err = "handdec: bad launch set"; return rc; }
+  if (totals[3] == 0) return MI355_OK;   // no job has rows: nothing to launch, nothing to copy
+  const size_t bytes = (size_t)totals[3];   // <= kHnSlabBytes: n <= kHnSetMax
+  if (!h_block || h_block_bytes < bytes) { *err = "handdec: the pinned result block is too small for the set"; return MI355_ERR_INVALID_ARG; }
+  HnPalmTable palm = {};
+  HnLandmarkTable lm = {};
+  for (int i = 0; i < n; i++) {
+    if (!rows[i]) continue;   // no rows: no block
+    const HnTensor &t = tensors[i];
+    if (t.decoder == 0) {
+      HnPalmJob &J = palm.job[block[i]];   // block[i] < palm blocks <= kHnSetMax
+      J.data = t.data;
+      J.N = t.rows;
+      J.slot = (uint32_t)i;
+      J.p = t.p;
+    } else {
+      HnLandmarkJob &J = lm.job[block[i]];
+      J.data = t.data;
+      J.scores = t.scores;
+      J.H = t.rows;
+      J.slot = (uint32_t)i;
+      J.D = t.D;
+      J.num_scores = t.scores ? t.num_scores : 0u;
+      J.kp_slot = kp_slot[i];
+      J.p = t.p;
+    }
+  }
+  uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out);
+  mi355_hand_det *d_dets = reinterpret_cast<mi355_hand_det *>(S->d_out + kHnCountsBytes);
+  mi355_hand_keypoints *d_kps = reinterpret_cast<mi355_hand_keypoints *>(S->d_out + kHnCountsBytes + dets_bytes((uint32_t)n));
+  if (totals[0]) {
+    hipLaunchKernelGGL(handdec_palm_jobs_kernel, dim3((uint32_t)totals[0]), dim3(kPalmThreads), 0, stream, palm, d_dets, d_n);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { *err = std::string("handdec palm jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+    (*kernel_launches)++;
+  }
+  if (totals[1]) {
+    hipLaunchKernelGGL(handdec_landmark_jobs_kernel, dim3((uint32_t)totals[1]), dim3(kThreads), 0, stream, lm, d_dets, d_kps, d_n);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { *err = std::string("handdec landmark jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+    (*kernel_launches)++;
+  }
+  const hipError_t e = hipMemcpyAsync(h_block, S->d_out, bytes, hipMemcpyDeviceToHost, stream);
+  if (e != hipSuccess) { *err = std::string("handdec set D2H: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+  return MI355_OK;
+}
+
+// tensor i of a set of n (its decoder, rows and kp_slot as the plan gave them) out of the set's pinned block; h_block may be null
+// when no job of the set had rows
+void handdec_set_result(const void *h_block, int n, int i, int decoder, uint32_t rows, uint32_t kp_slot, mi355_hand_det *dets, mi355_hand_keypoints *kps,
+                        uint32_t *n_hands) {
+  *n_hands = 0;
+  if (!h_block || !rows) return;   // a job without rows had no block: its slot holds nothing of this set
+  const uint8_t *h = static_cast<const uint8_t *>(h_block);
+  const uint32_t c = reinterpret_cast<const uint32_t *>(h)[i];
+  const uint32_t m = c < MI355_HAND_MAX ? c : MI355_HAND_MAX;
+  *n_hands = m;
+  if (!m) return;
+  std::memcpy(dets, h + kHnCountsBytes + dets_bytes((uint32_t)i), (size_t)m * sizeof(mi355_hand_det));
+  if (decoder == 1) std::memcpy(kps, h + kHnCountsBytes + dets_bytes((uint32_t)n) + kps_bytes(kp_slot), (size_t)m * sizeof(mi355_hand_keypoints));
+}
+
 }  // namespace mi355
 
 using namespace mi355;
@@ -690,6 +865,10 @@ int mi355_selftest_handdec_check(int decoder, size_t tensor_pitch_bytes, int n_t
   const int rc = handdec_check_args(decoder, tensor_pitch_bytes, n_tensors, rows, kps_dim, score_pitch_bytes, num_scores, &why);
   if (rc) return rc;
   return handdec_check_params(decoder, max_hands, frame_width, frame_height, &why);
+}
+
+int mi355_selftest_handdec_set_plan(int n_jobs, const int *decoder, const uint32_t *rows, uint32_t *block, uint32_t *kp_slot, uint64_t totals[4]) {
+  return handdec_set_plan(n_jobs, decoder, rows, block, kp_slot, totals);
 }
 
 }  // extern "C"

@@ -335,6 +335,26 @@ size_t yolodec_set_result_bytes(uint64_t records);  // the pinned block a set wi
 // the NMS launch, counts and records into h_block (nothing launched or copied if no tensor has a candidate)
 int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
                        std::string *err);
+// launch sets of the video group's hand-decoder queue (handdec.hip): palm and landmark tensors of independent instances, job tables
+constexpr int kHnSetMax = MI355_HANDDEC_SET_MAX;
+constexpr size_t kHnCountsBytes = 128;  // a result block: kHnSetMax counts (by job), n x MI355_HAND_MAX box records (by job), then
+                                        // MI355_HAND_MAX keypoint records per landmark job (by kp_slot)
+struct HnTensor { int decoder; const float *data; uint32_t rows, D; const float *scores; uint32_t num_scores; mi355_hand_params p; };   // decoder 0: palm, 1: landmarks
+struct HnSetScratch;  // the result slab of one set, on the device; nothing in it is cleared between sets
+// the checks of the hand decoders' entry points that need no device; *why names the refusal
+int handdec_check_args(int decoder, size_t tensor_pitch_bytes, int n_tensors, uint32_t rows, uint32_t kps_dim, size_t score_pitch_bytes, uint32_t num_scores,
+                       const char **why);
+int handdec_check_params(int decoder, uint32_t max_hands, int32_t frame_width, int32_t frame_height, const char **why);
+int handdec_set_plan(int n_jobs, const int *decoder, const uint32_t *rows, uint32_t *block, uint32_t *kp_slot, uint64_t totals[4]);
+HnSetScratch *handdec_set_scratch_new(int *status, std::string *err);
+void handdec_set_scratch_free(HnSetScratch *S);
+size_t handdec_set_block_bytes();  // the pinned block a set's results are copied to: the slab's maximum, one size
+// n <= kHnSetMax checked tensors on `stream`: the palm launch, the landmark launch (each only if it has a job with rows), then the
+// slab's used prefix into h_block (nothing launched or copied if no tensor has rows)
+int handdec_launch_set(HnSetScratch *S, hipStream_t stream, const HnTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
+                       std::string *err);
+void handdec_set_result(const void *h_block, int n, int i, int decoder, uint32_t rows, uint32_t kp_slot, mi355_hand_det *dets, mi355_hand_keypoints *kps,
+                        uint32_t *n_hands);
 int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, int channel, int kind, float *out, int *w, int *h);
 int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint32_t device_rate);
 int hrtf_setup(mi355_ctx *ctx, int channels, int block_len, int steps);

@@ -122,6 +122,7 @@ class HandParams(C.Structure):
 
 
 HAND_MAX = 10   # MI355_HAND_MAX: records per tensor in the outputs
+HANDDEC_SET_MAX = 32   # MI355_HANDDEC_SET_MAX: tensors per launch set of the group's hand-decoder queue
 KP_VISIBILITY = {"UNKNOWN": 0, "VISIBLE": 1, "OCCLUDED": 2}   # mi355_kp_visibility
 # mi355_hand_det and mi355_hand_keypoints as numpy records
 HAND_DET = np.dtype([("xmin", "<f4"), ("ymin", "<f4"), ("xmax", "<f4"), ("ymax", "<f4"), ("rotation", "<f4"), ("rotation_od", "<f4"), ("confidence", "<f4"),
@@ -345,6 +346,12 @@ def load_library():
         "mi355_group_wait_yolodec": (i, [vp, C.c_uint64, vp, C.POINTER(C.c_uint32)]),
         "mi355_group_yolodec_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "mi355_selftest_yolodec_set_plan": (i, [i, C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 5 + [C.POINTER(C.c_uint64)] * 4),
+        "mi355_group_set_handdec_rendezvous": (i, [vp, i, C.c_uint]),
+        "mi355_group_submit_handdec_palm": (i, [vp, vp, vp, C.c_uint32, C.POINTER(HandParams), C.POINTER(C.c_uint64)]),
+        "mi355_group_submit_handdec_landmarks": (i, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(HandParams), C.POINTER(C.c_uint64)]),
+        "mi355_group_wait_handdec": (i, [vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32)]),
+        "mi355_group_handdec_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_handdec_set_plan": (i, [i, C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 3 + [C.POINTER(C.c_uint64)]),
         "mi355_selftest_mixer_plan": (i, [i] + [C.POINTER(C.c_uint32)] * 4 + [C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint32)] * 4 + [C.c_uint32]
                                       + [C.POINTER(C.c_uint32)] * 3),
         "mi355_agroup_create_mixer": (vp, [i, i, C.POINTER(C.c_int)]),
@@ -507,6 +514,7 @@ class Group:
             raise Mi355Error(st.value, "mi355_group_create")
         self._rounds = {}
         self._yolodec_caps = {}   # ticket -> the capacity its submit asked for (wait_yolodec sizes the result by it)
+        self._handdec_landmarks = set()   # the landmark tickets (wait_handdec returns keypoint records for them)
 
     def _ck(self, rc):
         if rc != 0:
@@ -658,10 +666,60 @@ class Group:
         self._ck(self.L.mi355_group_yolodec_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
+    # ---- handdetectiontensordec / handlandmarktensordec tensors of independent elements
+    def set_handdec_rendezvous(self, expected_streams, linger_us):
+        self._ck(self.L.mi355_group_set_handdec_rendezvous(self.h, expected_streams, linger_us))
+
+    def submit_handdec_palm(self, ctx, d_tensor, num_rows, params):
+        """One device palm tensor ([num_rows, 8] float32) of stream `ctx`; params: (confidence_thr, nms_iou_thr, max_hands[, frame_width,
+        frame_height]), a HandParams, or None for a null pointer; returns the ticket."""
+        p = None if params is None else _hand_params(params)[0]
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_handdec_palm(self.h, None if ctx is None else ctx.h, d_tensor, num_rows, p, C.byref(t)))
+        return t.value
+
+    def submit_handdec_landmarks(self, ctx, d_landmarks, num_hands, kps_dim, params, d_scores=None, num_scores=0):
+        """One device landmark tensor ([num_hands, 21 * kps_dim] float32) of stream `ctx`, with its num_scores device scores or None;
+        params as submit_handdec_palm; returns the ticket."""
+        p = None if params is None else _hand_params(params)[0]
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_handdec_landmarks(self.h, None if ctx is None else ctx.h, d_landmarks, num_hands, kps_dim, d_scores, num_scores, p,
+                                                             C.byref(t)))
+        self._handdec_landmarks.add(t.value)
+        return t.value
+
+    def wait_handdec(self, ticket):
+        """The tensor's hands as Context.handdec_palm_device / handdec_landmarks_device return them for one tensor: a HAND_DET record
+        array for a palm ticket, (HAND_DET records, HAND_KP records) for a landmark ticket."""
+        landmarks = ticket in self._handdec_landmarks
+        dets, kps = np.zeros(HAND_MAX, HAND_DET), np.zeros(HAND_MAX, HAND_KP)
+        n = C.c_uint32(0)
+        self._ck(self.L.mi355_group_wait_handdec(self.h, ticket, dets.ctypes.data, kps.ctypes.data, C.byref(n)))
+        self._handdec_landmarks.discard(ticket)
+        return (dets[:n.value].copy(), kps[:n.value].copy()) if landmarks else dets[:n.value].copy()
+
+    def handdec_stats(self):
+        """(tensors launched, launch sets, tensors in the largest set, kernel launches)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.L.mi355_group_handdec_stats(self.h, c))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
     def close(self):
         if self.h:
             self.L.mi355_group_destroy(self.h)
             self.h = None
+
+
+def selftest_handdec_set_plan(decoders, rows):
+    """mi355_selftest_handdec_set_plan (host only): the layout of one hand-decoder launch set. Returns (status, block, kp_slot,
+    totals); decoders: 0 (palm) / 1 (landmarks) per job."""
+    L = load_library()
+    n = len(decoders)
+    m = max(n, 1)
+    dec, r = (C.c_int * m)(*decoders), (C.c_uint32 * m)(*rows)
+    block, kp_slot, totals = (C.c_uint32 * m)(), (C.c_uint32 * m)(), (C.c_uint64 * 4)()
+    rc = L.mi355_selftest_handdec_set_plan(n, dec, r, block, kp_slot, totals)
+    return rc, list(block)[:n], list(kp_slot)[:n], list(totals)
 
 
 def selftest_yolodec_set_plan(layouts, num_fields, num_candidates, max_dets):

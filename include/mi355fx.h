@@ -1043,7 +1043,7 @@ int mi355_selftest_handdec_check(int decoder, size_t tensor_pitch_bytes, int n_t
  *           a null n_dets or a null dets otherwise: MI355_ERR_INVALID_ARG, the result stays collectable). A result is collected
  *           once. Tickets are one sequence per group: a ticket that is unknown, already collected or another queue's is
  *           MI355_ERR_INVALID_ARG here and stays collectable where it belongs; mi355_group_wait, _order_after, _wait_compare,
- *           _wait_colordetect and _wait_hsvdetect refuse a decoder ticket likewise.
+ *           _wait_colordetect, _wait_hsvdetect and _wait_handdec refuse a decoder ticket likewise.
  *   set_yolodec_rendezvous : as set_hsvdetect_rendezvous, counted over pending tensors only. The other queues' rendezvous, streams
  *           and stats and this queue's do not touch each other.
  *   At most MI355_YOLODEC_SET_MAX tensors share a launch set; more go out as consecutive sets. Per set: the V8 score launch if a V8
@@ -1072,6 +1072,65 @@ int mi355_group_yolodec_stats(mi355_group *group, uint64_t stats[4]);
 int mi355_selftest_yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates,
                                     const uint32_t *max_dets, uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset,
                                     uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]);
+
+/* The hand decoders across independent element instances. The reference elements receive one tensor per buffer per instance
+ * (analytics/analytics/src/hand/handdetectiontensordec/imp.rs, hand/handlandmarktensordec/imp.rs: transform_ip); a process with N
+ * camera pipelines, each with a palm decoder and a landmark decoder, makes 2 N lone calls per frame period, each a parameter
+ * upload, a launch, a download and a synchronisation around a kernel of 5 - 15 us. submit_handdec_palm /
+ * submit_handdec_landmarks queue one device tensor of stream `ctx` and whatever is pending goes out as at most TWO launches over job
+ * tables in the kernel arguments (one block per tensor), on the queue's own HIP stream, with NO upload and ONE download of all counts
+ * and records. Members are fully independent: each tensor has its own decoder, shape (N; H, D, scores) and settings. After
+ * wait_handdec, dets, kps and *n_hands hold exactly what mi355_handdec_palm_tensors_device(ctx, d_tensor, N * 32, 1, N, p, dets,
+ * n_hands) / mi355_handdec_landmarks_tensors_device(ctx, d_landmarks, H * 21 * D * 4, 1, H, D, d_scores, num_scores * 4, num_scores,
+ * p, dets, kps, n_hands) would have returned, byte for byte: the job kernels run the lone kernels' own body (one device function,
+ * one LDS layout).
+ *   submit : never blocks; the checks and status codes are those of the lone entry points with n_tensors = 1 and a pitch equal to
+ *           the tensor, i.e. what mi355_selftest_handdec_check(decoder, rows * row bytes, 1, rows, kps_dim, num_scores * 4,
+ *           num_scores, max_hands, frame_width, frame_height) reports (palm rows 0..4096, hands 0..1024, kps_dim 2..16, scores
+ *           0..1024, max_hands 1..8 / 1..10, the frame size both positive or both zero); a null group, ctx, p or ticket, or a null
+ *           or misaligned tensor (or misaligned scores) with rows > 0: MI355_ERR_INVALID_ARG. d_scores == NULL: no scores, and
+ *           num_scores is ignored. A refused submit queues nothing. Rows = 0 is accepted, gets a ticket and yields 0 hands. The
+ *           settings are copied at submit. The tensor and the scores are read after what ctx's HIP stream held at the call (an
+ *           event recorded on that stream when it holds work); they are read until wait_handdec for the ticket has returned.
+ *   wait   : launches what is pending if the tensor has not gone out (rendezvous first), then waits for its launch set; the
+ *           group's lock is not held meanwhile. Writes *n_hands (at most MI355_HAND_MAX) and the first *n_hands records of dets
+ *           and, for a landmark ticket, of kps; records from *n_hands on are not touched, as in the lone form. dets and n_hands
+ *           must not be null, kps must not be null for a landmark ticket (MI355_ERR_INVALID_ARG, the result stays collectable);
+ *           kps is ignored for a palm ticket. A result is collected once. Tickets are one sequence per group: a ticket that is
+ *           unknown, already collected or another queue's is MI355_ERR_INVALID_ARG here and stays collectable where it belongs;
+ *           mi355_group_wait, _order_after, _wait_compare, _wait_colordetect, _wait_hsvdetect and _wait_yolodec refuse a hand
+ *           ticket likewise.
+ *   set_handdec_rendezvous : as set_hsvdetect_rendezvous, counted over pending hand tensors only. The other queues' rendezvous,
+ *           streams and stats and this queue's do not touch each other.
+ *   At most MI355_HANDDEC_SET_MAX tensors share a launch set; more go out as consecutive sets in submission order. Per set: the palm
+ *   launch if a palm tensor has rows, the landmark launch likewise, one device-to-host copy of the set's result slab - 32 counts
+ *   (128 bytes, by job), n_jobs x MI355_HAND_MAX mi355_hand_det (by job), n_landmark_jobs x MI355_HAND_MAX mi355_hand_keypoints (by
+ *   the running index among landmark jobs). A set whose tensors all have 0 rows launches and copies nothing; a tensor without rows
+ *   gets no block and its count is 0 on the host. Consecutive sets share the device slab (ordered on the queue's stream) and nothing
+ *   in it is cleared between sets: every block writes its count on every path. Every set in flight has a pinned block of its own,
+ *   and results move out of it when the set is collected. flush, wait_all and destroy cover this queue as they cover the others. A
+ *   launch that fails is reported to the call that caused it and, once, to each tensor's own wait.
+ *   handdec_stats : {tensors launched, launch sets, tensors in the largest set, kernel launches}.
+ *   mi355_selftest_handdec_set_plan : host only, no device: the layout of one set, which the queue itself uses. Jobs keep submit
+ *           order; decoder[j] is 0 (palm) or 1 (landmarks). block[j] = the running count of the earlier jobs of j's own decoder
+ *           with rows > 0 - the block of j's launch that decodes it - or UINT32_MAX for a job without rows; kp_slot[j] = the
+ *           running count of the earlier landmark jobs, or UINT32_MAX for a palm job. totals = {palm blocks, landmark blocks,
+ *           landmark jobs, bytes copied = 128 + 640 n_jobs + 2880 landmark jobs, or 0 when no job has rows}. Refused
+ *           (MI355_ERR_INVALID_ARG): n_jobs outside 0..MI355_HANDDEC_SET_MAX, null arrays with n_jobs > 0, null totals, a decoder
+ *           that is neither 0 nor 1; rows above the decoder's limit (4096 / 1024): MI355_ERR_UNSUPPORTED. */
+#define MI355_HANDDEC_SET_MAX 32 /* tensors per launch set */
+int mi355_group_set_handdec_rendezvous(mi355_group *group, int expected_streams, unsigned linger_us);
+int mi355_group_submit_handdec_palm(mi355_group *group, mi355_ctx *ctx, const float *d_tensor, uint32_t num_rows,
+                                    const mi355_hand_params *p, uint64_t *ticket);
+int mi355_group_submit_handdec_landmarks(mi355_group *group, mi355_ctx *ctx, const float *d_landmarks, uint32_t num_hands,
+                                         uint32_t kps_dim, const float *d_scores, uint32_t num_scores, const mi355_hand_params *p,
+                                         uint64_t *ticket);
+int mi355_group_wait_handdec(mi355_group *group, uint64_t ticket, mi355_hand_det *dets, mi355_hand_keypoints *kps, uint32_t *n_hands);
+/* {tensors launched, launch sets, tensors in the largest set, kernel launches} */
+int mi355_group_handdec_stats(mi355_group *group, uint64_t stats[4]);
+/* host only, no device: the layout of one launch set */
+int mi355_selftest_handdec_set_plan(int n_jobs, const int *decoder, const uint32_t *rows, uint32_t *block, uint32_t *kp_slot,
+                                    uint64_t totals[4]);
 
 /* ---------------------------------------------------------------- agingradio
  * Replaces AgingRadio::process::<f32|f64> (audio/audiofx/src/agingradio/imp.rs:94-136): per pair of frames

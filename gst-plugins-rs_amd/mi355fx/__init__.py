@@ -115,6 +115,29 @@ def _yolo_params(params):
     return arr, len(params)
 
 
+YOLOX_LEVELS_MAX = 8   # MI355_YOLOX_LEVELS_MAX
+
+
+class YoloxLevel(C.Structure):
+    """mi355_yolox_level: one level of a YOLOX head - tensor 0's reg [4][h][w], obj [1][h][w] and cls [C][h][w] maps (tensor i's at
+    pointer + i * pitch), the level's shape and its stride."""
+    _fields_ = [("reg", C.c_void_p), ("obj", C.c_void_p), ("cls", C.c_void_p), ("reg_pitch_bytes", C.c_size_t), ("obj_pitch_bytes", C.c_size_t),
+                ("cls_pitch_bytes", C.c_size_t), ("h", C.c_uint32), ("w", C.c_uint32), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def _yolox_levels(levels):
+    """YoloxLevel objects, or tuples (reg, obj, cls, reg_pitch, obj_pitch, cls_pitch, h, w, stride[, reserved]) -> a ctypes array."""
+    arr = (YoloxLevel * max(len(levels), 1))()
+    for k, q in enumerate(levels):
+        arr[k] = q if isinstance(q, YoloxLevel) else YoloxLevel(*q)
+    return arr
+
+
+def yolox_candidates(levels):
+    """A = the sum of h * w over the levels (YoloxLevel objects or the tuples _yolox_levels takes)."""
+    return sum((q.h * q.w) if isinstance(q, YoloxLevel) else (q[6] * q[7]) for q in levels)
+
+
 class HandParams(C.Structure):
     """mi355_hand_params: the settings of one handdetectiontensordec / handlandmarktensordec instance; frame 0, 0: no frame size."""
     _fields_ = [("confidence_threshold", C.c_float), ("nms_iou_threshold", C.c_float), ("max_hands", C.c_uint32), ("frame_width", C.c_int32),
@@ -335,6 +358,11 @@ def load_library():
         "mi355_yolodec_tensor": (i, [vp, vp, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "mi355_yolodec_tensors_device": (i, [vp, vp, sz, i, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "mi355_selftest_yolodec_check": (i, [sz, i, i, C.c_uint32, C.c_uint32]),
+        "mi355_yolox_head_decode_device": (i, [vp, C.POINTER(YoloxLevel), i, i, C.c_uint32, vp, sz]),
+        "mi355_yolox_head_dets_device": (i, [vp, C.POINTER(YoloxLevel), i, i, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "mi355_yolox_head_dets": (i, [vp, C.POINTER(YoloxLevel), i, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "mi355_yolox_input_frames_device": (i, [vp, vp, sz, sz, i, C.c_uint32, C.c_uint32, vp, sz]),
+        "mi355_selftest_yolox_head_check": (i, [C.POINTER(YoloxLevel), i, i, C.c_uint32, sz]),
         "mi355_handdec_palm_tensor": (i, [vp, vp, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
         "mi355_handdec_palm_tensors_device": (i, [vp, vp, sz, i, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
         "mi355_handdec_landmarks_tensor": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(HandParams), vp, vp, C.POINTER(C.c_uint32)]),
@@ -720,6 +748,14 @@ def selftest_handdec_set_plan(decoders, rows):
     block, kp_slot, totals = (C.c_uint32 * m)(), (C.c_uint32 * m)(), (C.c_uint64 * 4)()
     rc = L.mi355_selftest_handdec_set_plan(n, dec, r, block, kp_slot, totals)
     return rc, list(block)[:n], list(kp_slot)[:n], list(totals)
+
+
+def selftest_yolox_head_check(levels, n_tensors, num_classes, out_pitch_bytes, n_levels=None):
+    """mi355_selftest_yolox_head_check (host only): the status the shape checks of the YOLOX head entry points give. levels: as
+    Context.yolox_head_decode_device takes them, or None; the pointers are never dereferenced. n_levels: default len(levels)."""
+    L = load_library()
+    n = (0 if levels is None else len(levels)) if n_levels is None else n_levels
+    return L.mi355_selftest_yolox_head_check(None if levels is None else _yolox_levels(levels), n, n_tensors, num_classes, out_pitch_bytes)
 
 
 def selftest_yolodec_set_plan(layouts, num_fields, num_candidates, max_dets):
@@ -1639,6 +1675,50 @@ class Context:
                                                      dets.ctypes.data, cap, n))
         out = [dets[t * cap:t * cap + min(n[t], cap)].copy() for t in range(n_tensors)]
         return (out, [n[t] for t in range(n_tensors)]) if return_counts else out
+
+    # ---- yoloxinference's head decode and input tensor (analytics/burn/src/yoloxinference: yolox_burn/model/head.rs, imp.rs)
+    def yolox_head_decode_device(self, levels, n_tensors, num_classes, d_out, out_pitch_bytes):
+        """The decoded [A, 5 + C] float32 tensor of every head at d_out + i * out_pitch_bytes; levels: YoloxLevel objects or tuples
+        (reg, obj, cls, reg_pitch, obj_pitch, cls_pitch, h, w, stride) of device pointers. One launch, asynchronous."""
+        self._ck(self.L.mi355_yolox_head_decode_device(self.h, _yolox_levels(levels), len(levels), n_tensors, num_classes, d_out, out_pitch_bytes))
+
+    def yolox_head_dets_device(self, levels, n_tensors, num_classes, params, max_dets=None, return_counts=False):
+        """One YOLO_DET record array per head, straight from the device head maps (levels as above); params: one
+        (box_thr, class_thr, iou_thr) triple per tensor. max_dets: default A, never truncated. One synchronisation."""
+        cap = yolox_candidates(levels) if max_dets is None else max_dets
+        p, n_p = _yolo_params(params)
+        if n_p != n_tensors:
+            raise ValueError("yolox_head_dets_device: one settings triple per tensor")
+        dets = np.zeros(max(n_tensors * cap, 1), YOLO_DET)
+        n = (C.c_uint32 * max(n_tensors, 1))()
+        self._ck(self.L.mi355_yolox_head_dets_device(self.h, _yolox_levels(levels), len(levels), n_tensors, num_classes, p, dets.ctypes.data, cap, n))
+        out = [dets[t * cap:t * cap + min(n[t], cap)].copy() for t in range(n_tensors)]
+        return (out, [n[t] for t in range(n_tensors)]) if return_counts else out
+
+    def yolox_head_dets(self, levels, params, max_dets=None, return_count=False):
+        """The kept boxes of one head held in host memory; levels: (reg, obj, cls, stride) per level, float32 arrays of shape
+        (4, h, w), (1, h, w) or (h, w), and (C, h, w); params: (box_thr, class_thr, iou_thr)."""
+        keep, lv, C_ = [], [], None
+        for reg, obj, cls, stride in levels:
+            reg, obj, cls = (np.ascontiguousarray(a, dtype=np.float32) for a in (reg, obj, cls))
+            h, w = reg.shape[-2:]
+            if reg.shape != (4, h, w) or obj.size != h * w or cls.ndim != 3 or cls.shape[1:] != (h, w) or C_ not in (None, cls.shape[0]):
+                raise ValueError("yolox_head_dets: reg (4, h, w), obj (1, h, w), cls (C, h, w) per level, one C")
+            C_ = cls.shape[0]
+            keep += [reg, obj, cls]
+            lv.append(YoloxLevel(reg.ctypes.data, obj.ctypes.data, cls.ctypes.data, 0, 0, 0, h, w, stride, 0))
+        cap = yolox_candidates(lv) if max_dets is None else max_dets
+        p, _ = _yolo_params(params)
+        dets = np.zeros(max(cap, 1), YOLO_DET)
+        n = C.c_uint32(0)
+        self._ck(self.L.mi355_yolox_head_dets(self.h, _yolox_levels(lv), len(lv), C_ or 0, p, dets.ctypes.data, cap, C.byref(n)))
+        out = dets[:min(n.value, cap)].copy()
+        return (out, n.value) if return_count else out
+
+    def yolox_input_frames_device(self, d_frames, frame_pitch, stride, n_frames, width, height, d_out, out_pitch_bytes):
+        """RGB u8 frames (row stride `stride`, frame i at d_frames + i * frame_pitch) -> [3][H][W] float32 per frame at
+        d_out + i * out_pitch_bytes, unscaled. One launch, asynchronous."""
+        self._ck(self.L.mi355_yolox_input_frames_device(self.h, d_frames, frame_pitch, stride, n_frames, width, height, d_out, out_pitch_bytes))
 
     # ---- handdetectiontensordec / handlandmarktensordec (analytics/analytics/src/hand)
     def handdec_palm(self, tensor, params, return_count=False):

@@ -943,6 +943,57 @@ int mi355_yolodec_tensors_device(mi355_ctx *ctx, const float *d_tensors, size_t 
                                  uint32_t max_dets, uint32_t *n_dets);
 int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates);
 
+/* ---------------------------------------------------------------- yoloxinference: head decode and input tensor (csrc/yolox_head.hip)
+ * Replaces the two in-tree loops of `yoloxinference` around the network. The head decode is Head::forward / Head::decode
+ * (analytics/burn/src/yoloxinference/yolox_burn/model/head.rs:23-34, :74-85, :89-122): from the per-level convolution outputs
+ * reg_out, obj_out, cls_out - sigmoid, concatenation, flatten, transpose, then the grid / stride / exp decode - to the [1, A, 5 + C]
+ * tensor that yoloxtensordec reads, or straight to its detections. The contract is DESIGN 4.13. Per tensor there are n_levels levels
+ * in order (the reference fixes 3 with strides 8, 16, 32, head.rs:16); candidate a = (sum of the earlier levels' h * w) + y * w + x
+ * (:84, :97-109: x is the fast index). Row a of the decoded tensor: (reg0 + x) * s, (reg1 + y) * s - an f32 add, then an f32
+ * multiply, unfused (:114); exp(reg2) * s, exp(reg3) * s (:116); sigmoid(obj) (:75); sigmoid(cls[c]), c = 0..C-1. Detections are
+ * DEFINED BY COMPOSITION: exactly what mi355_yolodec_tensors_device(..., MI355_YOLO_X, 5 + C, A, ...) returns for that tensor -
+ * same records, same order, candidate = a; the class is the last of equal maxima of the SIGMOID values.
+ * One stated deviation (as 4.12 a): exp and sigmoid come from burn's backend, whose source is not in the reference tree - RESTATED
+ * WITHOUT SOURCE, PARITY UNPINNED. exp(x) is the f64 exponential of the f32 argument rounded once to f32 (overflow: inf);
+ * sigmoid(x) is 1 / (1 + exp(-x)) evaluated in f64 from the f32 argument and rounded once (0 from about -104 down, exactly 1 from
+ * about 17.4 up). A NaN in gives a NaN out; its sign and payload are the hardware's and outside the contract.
+ *   level      device pointers to tensor 0's maps; tensor i's map is at (char *)p + i * pitch. reg [4][h][w], obj [1][h][w],
+ *              cls [C][h][w], contiguous NCHW f32. The three maps of a level MAY LIE IN ONE ALLOCATION - obj = reg + 4 h w,
+ *              cls = reg + 5 h w, equal pitches: the engine's fused [5 + C, h, w] output. Nothing is written to them.
+ *   _head_decode_device  materialises [A, 5 + C] per tensor at d_out + i * out_pitch_bytes: one launch, asynchronous on the
+ *                        context's stream. For callers who want the reference's tensor as it is.
+ *   _head_dets_device    the fused form: p, dets, max_dets, n_dets exactly as in mi355_yolodec_tensors_device (own settings per
+ *                        tensor, counts even above the capacity). Two launches, one synchronisation and one download per call,
+ *                        whatever n_tensors is; no decoded tensor exists anywhere. A candidate is dropped on sigmoid(obj) <
+ *                        box_confidence_threshold (yolotensordec/imp.rs:332) before any of its class values is read.
+ *   _head_dets           the host form: the same struct with HOST pointers, one tensor, pitches ignored; synchronous.
+ *   _input_frames_device the element's input (yoloxinference/imp.rs:439-447 packs the strided RGB frame, :533-539 converts and
+ *                        permutes, no scaling): out[c][y][x] = (f32) in[y * stride + 3 x + c], [3][H][W] f32 per frame at
+ *                        d_out + i * out_pitch_bytes, frame i at d_frames + i * frame_pitch (ignored for one frame). Exact. One
+ *                        launch, asynchronous. n_frames 1..1024, width and height 1..65536 (above: MI355_ERR_UNSUPPORTED),
+ *                        stride >= 3 * width, d_out 4-byte aligned, out pitch >= 3 H W 4 and a multiple of 4.
+ *   MI355_ERR_INVALID_ARG: null pointers, n_levels < 1, n_tensors < 1, num_classes < 1, h, w or stride 0, reserved != 0, pointers
+ *   not 4-byte aligned, a pitch below its map or no multiple of 4. MI355_ERR_UNSUPPORTED: n_levels > 8, 5 + C > 1029, A > 65536,
+ *   stride > 65536, n_tensors > 1024. Scratch is the context's decoder scratch (yolodec) and grows to the largest shape seen.
+ *   mi355_selftest_yolox_head_check : host only, no device: the status the shape checks of _head_decode_device give. The struct's
+ *              pointers are checked for null and alignment only, never dereferenced. */
+#define MI355_YOLOX_LEVELS_MAX 8
+typedef struct mi355_yolox_level {
+  const float *reg, *obj, *cls;      /* tensor i's map at (char *)p + i * pitch; reg [4][h][w], obj [1][h][w], cls [C][h][w] */
+  size_t reg_pitch_bytes, obj_pitch_bytes, cls_pitch_bytes;
+  uint32_t h, w, stride, reserved;   /* reserved 0 */
+} mi355_yolox_level;
+int mi355_yolox_head_decode_device(mi355_ctx *ctx, const mi355_yolox_level *levels, int n_levels, int n_tensors, uint32_t num_classes,
+                                   float *d_out, size_t out_pitch_bytes);
+int mi355_yolox_head_dets_device(mi355_ctx *ctx, const mi355_yolox_level *levels, int n_levels, int n_tensors, uint32_t num_classes,
+                                 const mi355_yolo_params *p, mi355_yolo_det *dets, uint32_t max_dets, uint32_t *n_dets);
+int mi355_yolox_head_dets(mi355_ctx *ctx, const mi355_yolox_level *levels, int n_levels, uint32_t num_classes,
+                          const mi355_yolo_params *p, mi355_yolo_det *dets, uint32_t max_dets, uint32_t *n_dets);
+int mi355_yolox_input_frames_device(mi355_ctx *ctx, const uint8_t *d_frames, size_t frame_pitch, size_t stride, int n_frames,
+                                    uint32_t width, uint32_t height, float *d_out, size_t out_pitch_bytes);
+int mi355_selftest_yolox_head_check(const mi355_yolox_level *levels, int n_levels, int n_tensors, uint32_t num_classes,
+                                    size_t out_pitch_bytes);
+
 /* ---------------------------------------------------------------- handdetectiontensordec / handlandmarktensordec (csrc/handdec.hip)
  * Replaces the decode loops of the two hand decoders: extract_hands_from_palm_detection with is_valid_palm_candidate_normalized
  * and apply_nms_to_palm_candidates (analytics/analytics/src/hand/handdetectiontensordec/imp.rs:89-335), extract_hands with

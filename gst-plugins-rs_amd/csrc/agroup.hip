@@ -4,7 +4,7 @@
 // (audio/audiofx/src/audioecho/imp.rs:205-227), ebur128level's (audio/audiofx/src/ebur128level/imp.rs:682-745), audioloudnorm's
 // sink_chain -> drain_full_frames -> State::process per 100 ms frame (audio/audiofx/src/audioloudnorm/imp.rs:1545-1586, :226-268).
 // One such buffer is a few thousand samples: on a GPU a single instance is launch- and round-trip-bound (one context per
-// instance: echo 0.22 ms per 32-instance interval where one CPU core needs 0.17; audioloudnorm 54x real time against 86x), while
+// instance: echo 0.22 ms per 32-instance interval where one CPU core needs 0.17; audioloudnorm 57x real time against 86x), while
 // the `_batch` kernels of this library advance hundreds of streams per launch (echo 0.014 ms, loudnorm 1,658x aggregate). Those
 // entry points need one caller that owns all streams; a process full of independent elements has none. An agroup is that caller:
 //   * members = element instances of ONE kind and configuration on one device (a transcoding farm's N identical pipelines);

@@ -94,7 +94,7 @@ struct mi355_ctx {
   void *ebur128 = nullptr;     // mi355::Ebur128State (ebur128_kernels.hip)
   void *hrtf = nullptr;        // mi355::HrtfState (hrtf_kernels.hip)
   void *sofa = nullptr;        // mi355::SofaState (sofa_kernels.hip)
-  void *loudnorm = nullptr;    // mi355::LoudNormState (loudnorm.hip)
+  void *loudnorm = nullptr;    // mi355::LoudNormLone (loudnorm.hip): a LoudNormBatch of one stream and the element's adapter
   void *loudnorm_batch = nullptr;  // mi355::LoudNormBatch (loudnorm.hip): n streams in lock step
   void *dssim_cache = nullptr; // mi355::DssimCache (dssim_kernels.hip)
   void *rounded = nullptr;     // mi355::RoundedMask (roundedcorners.hip): the element's alpha plane, device-resident

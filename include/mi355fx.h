@@ -560,7 +560,10 @@ int mi355_ebur128_true_peak(mi355_ctx *ctx, unsigned channel, double *out);
  *   setup : State::new(settings, info) with the four properties (loudness-target [LUFS], loudness-range-target [LU],
  *           max-true-peak [dbTP], offset [LU]; imp.rs:37-40).
  *   push  : sink_chain -> adapter.push + drain_full_frames: every complete frame (3 s first, then 100 ms) is processed;
- *           `out` receives *out_frames frames (0 while the first 3 s are still being collected).
+ *           `out` receives *out_frames frames (0 while the first 3 s are still being collected). A frame that does not
+ *           fit the rest of `out` is refused ("output buffer too small") before it changes anything - no meter has seen
+ *           it -: it and what was pushed after it stay in the adapter, the frames delivered before it in the same call
+ *           have left it and are counted in *out_frames. push again (0 frames will do) with room for the rest.
  *   drain : drain() at EOS / flush: the final frame (up to 3 s of latency comes out) or, with less than 3 s in total,
  *           the linear-gain path; *eos = 1 when there was nothing at all to drain (FlowError::Eos, :289-293).
  *           out_capacity_frames >= 30*19200 + pending frames covers every case. */

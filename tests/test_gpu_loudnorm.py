@@ -1,30 +1,33 @@
 """GPU parity tests for audioloudnorm through the C ABI against the CPU oracle.
 
-The State machine (gain history, limiter states) is transcribed on the host; the per-sample loops and the peak search
-run as kernels. Everything in-tree is f64 and unfused, so the samples must be BIT-IDENTICAL to the oracle as long
-as the two loudness meters agree; the meters (device vs oracle) agree to ~1e-9 LU (tests/test_gpu_ebur128.py), which
+The gain history is kept on the host; the per-sample loops and the limiter with its peak search run as kernels, for a
+single context (a batch of one stream behind loudnorm_push / _drain) as for a batch. Everything in-tree is f64 and
+unfused, so the samples must be BIT-IDENTICAL to the oracle as long as the two loudness meters agree; the meters (device vs oracle) agree to ~1e-9 LU (tests/test_gpu_ebur128.py), which
 enters the samples only through pow(10, x/20) of the gain history: tolerance 1e-9 relative, and bit-exact is asserted
-where no meter-dependent gain is involved (linear path excluded: offset depends on the global loudness)."""
+where no meter-dependent gain is involved (linear path excluded: offset depends on the global loudness).
+What a single context gives is, in addition, what it gave when it still ran a host-driven limiter of its own: the hashes of
+tests/golden/loudnorm_lone_parent.json (tests/loudnorm_streams.py)."""
 import numpy as np
 import pytest
 
+import loudnorm_streams as LS
+from loudnorm_streams import RATE, tone as _tone
+
 pytestmark = pytest.mark.gpu
 
-RATE = 192000
 
-
-def _tone(seconds, ch, amp=0.02, f=440.0):
-    t = np.arange(int(seconds * RATE)) / RATE
-    return np.stack([amp * np.sin(2 * np.pi * (f + 3 * c) * t) for c in range(ch)], 1)
-
-
-def _both(ctx, oracle, x, chunk, **kw):
+def _both(ctx, oracle, name, x=None):
+    """stream `name` of tests/loudnorm_streams.py through the context and the oracle -> (input, context's output, oracle's output);
+    the context's output is asserted to be the one recorded in tests/golden/loudnorm_lone_parent.json on the way"""
+    st = LS.get(name)
+    if x is None:
+        x = st.make()
     ch = x.shape[1]
-    ln = oracle.LoudNorm(ch, **kw)
-    ctx.loudnorm_setup(ch, **kw)
+    ln = oracle.LoudNorm(ch, **st.kw)
+    ctx.loudnorm_setup(ch, **st.kw)
     got, exp = [], []
-    for k in range(0, len(x), chunk):
-        g, e = ctx.loudnorm_push(x[k:k + chunk]), ln.push(x[k:k + chunk])
+    for part in st.parts(x):
+        g, e = ctx.loudnorm_push(part), ln.push(part)
         assert g.size == e.size
         got.append(g); exp.append(e)
     g, e = ctx.loudnorm_drain(), ln.drain()
@@ -32,7 +35,9 @@ def _both(ctx, oracle, x, chunk, **kw):
     if g is not None:
         assert g.size == e.size
         got.append(g); exp.append(e)
-    return np.concatenate(got), np.concatenate(exp)
+    got = np.concatenate(got)
+    LS.check(name, x, got)
+    return x, got, np.concatenate(exp)
 
 
 def _close(got, exp):
@@ -44,14 +49,7 @@ def _close(got, exp):
 def test_limiter_heavy_stream_matches_oracle(ctx, oracle, ch):
     """Bursts far above the ceiling in every limiter situation: isolated, rising series (attack restarts), falling
     series (sustain), a burst inside the release window, one in the first 10 ms, one near the very end."""
-    x = _tone(7.3, ch)
-    rng = np.random.default_rng(ch)
-    for start, n, k in ((0.001, 40, 80.0), (3.5, 2000, 60.0), (3.52, 300, 90.0), (3.56, 100, 40.0), (3.7, 50, 30.0), (4.4, 10, 70.0),
-                        (4.41, 10, 75.0), (4.42, 10, 85.0), (5.9, 500, 55.0), (7.28, 100, 65.0)):
-        i = int(start * RATE)
-        x[i:i + n] *= k
-    x += 1e-4 * rng.standard_normal(x.shape)
-    got, exp = _both(ctx, oracle, x, 123457)
+    x, got, exp = _both(ctx, oracle, "limiter_heavy/%dch" % ch)
     assert got.size == x.size
     assert np.abs(got).max() <= 10 ** (-2.0 / 20)
     assert _close(got, exp) <= 1e-9
@@ -60,23 +58,19 @@ def test_limiter_heavy_stream_matches_oracle(ctx, oracle, ch):
 def test_quiet_then_loud_gain_tracking(ctx, oracle):
     """Silence (below -70 LUFS: above_threshold stays false), then programme material: exercises the delta history,
     the gaussian smoothing and the 1.0058 creep (imp.rs:560-575)."""
-    x = np.concatenate([_tone(3.4, 2, amp=1e-6), _tone(4.0, 2, amp=0.2), _tone(1.1, 2, amp=0.01)])
-    got, exp = _both(ctx, oracle, x, 96000)
+    x, got, exp = _both(ctx, oracle, "quiet_then_loud")
     assert _close(got, exp) <= 1e-9
 
 
 def test_short_stream_linear_path_and_empty(ctx, oracle):
-    x = _tone(1.3, 2, amp=0.05)
-    got, exp = _both(ctx, oracle, x, 50000)
+    x, got, exp = _both(ctx, oracle, "short_stream")
     assert got.size == x.size and _close(got, exp) <= 1e-9
     ctx.loudnorm_setup(2)
     assert ctx.loudnorm_drain() is None   # FlowError::Eos
 
 
 def test_settings_and_exactly_three_seconds(ctx, oracle):
-    x = _tone(3.0, 1, amp=0.3)
-    x[int(2.95 * RATE)] = 0.999
-    got, exp = _both(ctx, oracle, x, 192000, loudness_target=-16.0, loudness_range_target=11.0, max_true_peak=-1.0, offset=0.5)
+    x, got, exp = _both(ctx, oracle, "exactly_three_seconds")
     assert got.size == x.size
     assert np.abs(got).max() <= 10 ** (-1.0 / 20)
     assert _close(got, exp) <= 1e-9
@@ -91,16 +85,6 @@ def test_not_negotiated(ctx):
 
 
 # ------------------------------------------------------------------ batches of streams (round 3)
-
-def _burst_stream(seed, seconds, ch):
-    """programme material with limiter work in it: a tone at a per-stream level with bursts far above the ceiling"""
-    rng = np.random.default_rng(seed)
-    x = _tone(seconds, ch, amp=0.01 * (1 + seed % 5), f=300.0 + 37 * seed)
-    for _ in range(6):
-        i = int(rng.uniform(0.0, seconds - 0.05) * RATE)
-        x[i:i + int(rng.integers(10, 3000))] *= rng.uniform(20.0, 90.0)
-    return x + 1e-4 * rng.standard_normal(x.shape)
-
 
 def _run_batch(ctx, streams, ch, **kw):
     """feeds the batch the way drain_full_frames does: whole frames, then the rest at drain"""
@@ -125,13 +109,13 @@ def test_batch_equals_separate_streams_and_oracle(ctx, oracle, ch, seconds):
     single-stream context BIT FOR BIT (same expressions, same meters) and the oracle's within the meters' 1e-9."""
     import mi355fx
     S = 5
-    streams = [_burst_stream(10 * ch + s, seconds, ch) for s in range(S)]
-    streams[3] = _tone(seconds, ch, amp=1e-6)           # below -70 LUFS throughout: above_threshold never set
+    streams = LS.batch_streams(ch, seconds)
+    assert len(streams) == S
     got = _run_batch(ctx, streams, ch)
     assert got.shape == (S, int(seconds * RATE) * ch)
     for s in range(S):
         with mi355fx.Context(0) as c1:
-            single, exp = _both(c1, oracle, streams[s], 200000)
+            _, single, exp = _both(c1, oracle, "batch_single/%dch/%d" % (ch, s), streams[s])
         assert (got[s] == single).all(), (s, int((got[s] != single).sum()))
         assert _close(got[s], exp) <= 1e-9
         assert np.abs(got[s]).max() <= 10 ** (-2.0 / 20)
@@ -157,11 +141,60 @@ def test_batch_argument_checks(ctx):
     assert ctx.loudnorm_batch_frame_size() == 0
 
 
+def test_single_state_and_batch_share_a_context(ctx):
+    """One context holds a single-stream state and a batch of two at once, calls interleaved frame by frame: each gives, bit for
+    bit, what a fresh context that ran only it gives. Mono, 3 s + 2.5 frames (3 s is the smallest first frame there is), one
+    burst above the ceiling in the second inner frame of every stream."""
+    import mi355fx
+    F, N0 = 19200, 3 * RATE
+    n = N0 + 2 * F + F // 2
+    xs = []
+    for k in range(3):
+        x = _tone((n + 1) / RATE, 1, amp=0.02 * (k + 1), f=330.0 + 50 * k)[:n]
+        i = N0 + F + 3000 + 2500 * k
+        x[i:i + 40 + 10 * k] *= 60.0
+        xs.append(x)
+    lone, rows = xs[0], xs[1:]
+    cuts = [0, N0, N0 + F, N0 + 2 * F]
+
+    def run(c, with_lone, with_batch):
+        out_l, out_b = [], []
+        if with_lone:
+            c.loudnorm_setup(1)
+        if with_batch:
+            c.loudnorm_setup_batch(2, 1)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            if with_lone:
+                out_l.append(c.loudnorm_push(lone[a:b]))
+            if with_batch:
+                assert c.loudnorm_batch_frame_size() == b - a
+                out_b.append(c.loudnorm_process_batch(np.stack([r[a:b].reshape(-1) for r in rows])))
+        if with_lone:
+            out_l.append(c.loudnorm_push(lone[cuts[-1]:]))
+        if with_batch:
+            out_b.append(c.loudnorm_process_batch(np.stack([r[cuts[-1]:].reshape(-1) for r in rows]), final=True))
+        if with_lone:
+            out_l.append(c.loudnorm_drain())
+        c.loudnorm_teardown()
+        return (np.concatenate(out_l) if with_lone else None), (np.concatenate(out_b, axis=1) if with_batch else None)
+
+    both_l, both_b = run(ctx, True, True)
+    with mi355fx.Context(0) as c1:
+        only_l, _ = run(c1, True, False)
+    with mi355fx.Context(0) as c2:
+        _, only_b = run(c2, False, True)
+    assert both_l.size == n and both_b.shape == (2, n)
+    ceiling = 10 ** (-2.0 / 20)
+    assert 0.5 * ceiling < np.abs(both_l[N0 + F:N0 + 2 * F]).max() <= ceiling   # the burst came out, held at the ceiling
+    assert (both_l == only_l).all(), int((both_l != only_l).sum())
+    assert (both_b == only_b).all(), int((both_b != only_b).sum())
+
+
 # ------------------------------------------------------------------ the case table (tests/loudnorm_cases.py)
 #
 # Every case is pinned on the CPU first (tests/test_loudnorm_cpu.py): the oracle equals an independent restatement of imp.rs bit
-# for bit there, and the limiter branches the case reaches are known by name. Here the host state machine over ln_detect_kernel /
-# ln_envelope_kernel and lnb_limiter_kernel run the same streams. The "grid" cases keep every delta at exactly 1.0 (input below
+# for bit there, and the limiter branches the case reaches are known by name. Here lnb_limiter_kernel runs the same streams, as the
+# one stream of a single context and as one of a batch of four. The "grid" cases keep every delta at exactly 1.0 (input below
 # -70 LUFS, the gain is the +60 dB offset: no meter reading enters a sample), so they are asserted BIT-IDENTICAL to the oracle; the
 # programme cases at the meters' 1e-9.
 
@@ -182,7 +215,9 @@ def _case_single(oracle, case):
         g, e = c1.loudnorm_drain(), ln.drain()
         assert g is not None and e is not None and g.size == e.size
         got.append(g); exp.append(e)
-    return np.concatenate(got), np.concatenate(exp)
+    got = np.concatenate(got)
+    LS.check("case/" + case.name, case.x, got)
+    return got, np.concatenate(exp)
 
 
 def _fillers(case):
@@ -202,8 +237,8 @@ def _fillers(case):
 
 @pytest.mark.parametrize("name", LC.names())
 def test_case_table_single_stream_and_batch(ctx, oracle, name):
-    """loudnorm_push / loudnorm_drain (host state machine over ln_detect_kernel / ln_envelope_kernel) against the oracle, then
-    loudnorm_process_batch (lnb_limiter_kernel) holding the case as stream 2 of 4, bit-identical to the single-stream context"""
+    """loudnorm_push / loudnorm_drain (lnb_limiter_kernel for the one stream of a single context) against the oracle and the
+    recorded hashes, then loudnorm_process_batch holding the case as stream 2 of 4, bit-identical to the single-stream context"""
     case = LC.get(name)
     try:
         single, exp = _case_single(oracle, case)

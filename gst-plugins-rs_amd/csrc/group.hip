@@ -26,7 +26,9 @@
 // hsvdetector frames (submit_hsvdetect: frames of independent instances - own size, strides, formats, settings - as at most two
 // launches over a job table, hsv_kernels.hip), decoder tensors (submit_yolodec: tensors of independent yolov8tensordec2 /
 // yoloxtensordec instances - own shape, layout, settings - as at most three launches over job tables and one download,
-// yolodec.hip) and hand tensors (submit_handdec_palm / _landmarks: tensors of independent handdetectiontensordec /
+// yolodec.hip; submit_yolox_head: the raw head maps of independent yoloxinference instances are members of the SAME queue - a
+// YdTensor of the kind MI355_YOLO_X_HEAD with the submit's copy of its levels - and cost a set one upload of their level tables
+// and two launches more, yolox_head.hip) and hand tensors (submit_handdec_palm / _landmarks: tensors of independent handdetectiontensordec /
 // handlandmarktensordec instances - own shape and settings - as at most two launches over job tables, no upload and one download,
 // handdec.hip). A fifth kind is a struct beside CdKind / HdKind / YdKind / HnKind - payload, result, kSetMax, its names, ensure,
 // plan, its pinned block (if any), launch, result, failed, destroy - a SetQueue<Kind> member of mi355_group, a line in
@@ -301,9 +303,10 @@ struct YdSlot { uint32_t num_candidates, max_dets; uint64_t det_offset; };
 struct YdKind {
   using Payload = YdTensor;
   using Result = YdOut;
-  struct Plan { YdTensor tensors[kYdSetMax]; uint64_t det_off[kYdSetMax], totals[6]; };
+  struct Plan { YdTensor tensors[kYdSetMax]; uint64_t det_off[kYdSetMax], totals[8]; };
   struct SetData {
-    YdBlock block{nullptr, 0};   // the set's own results until it is collected (h == nullptr: no tensor had a candidate)
+    // the set's own results until it is collected, and behind them the tables of its heads (h == nullptr: no member had a candidate)
+    YdBlock block{nullptr, 0};
     std::vector<YdSlot> slots;   // its tensors, by job (as the set's tickets are)
   };
   static constexpr int kSetMax = kYdSetMax;
@@ -311,6 +314,9 @@ struct YdKind {
   hipStream_t stream = nullptr;
   YdSetScratch *scratch = nullptr;
   std::vector<YdBlock> blocks;  // free pinned result blocks
+  // the heads among the members (mi355_group_yolox_head_stats): heads launched, sets that held one, table uploads, head kernel launches
+  uint64_t n_heads = 0, n_head_sets = 0, n_head_uploads = 0, n_head_launches = 0;
+  int last_head_counts[3] = {0, 0, 0};   // of the set `launch` has just sent out; counted by `launched`, i.e. once the set stands
 
   // flush, wait_all and destroy launch for this queue only once the scratch exists: a stream alone (the scratch could not be made)
   // has accepted nothing
@@ -326,15 +332,19 @@ struct YdKind {
   }
   // the set's layout, before anything is taken for it: the plan the launch itself uses says how large the set's block has to be
   int plan(const QItem<YdTensor> *take, size_t n, Plan *p, std::string *err) const {
-    int layout[kYdSetMax];
+    int layout[kYdSetMax], n_levels[kYdSetMax];
     uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], n_blocks[kYdSetMax];
+    uint32_t lv_h[kYdSetMax * MI355_YOLOX_LEVELS_MAX], lv_w[kYdSetMax * MI355_YOLOX_LEVELS_MAX], lv_first[kYdSetMax * MI355_YOLOX_LEVELS_MAX];
     uint64_t key_off[kYdSetMax], box_off[kYdSetMax];
+    size_t n_lv = 0;
     for (size_t i = 0; i < n; i++) {
       const YdTensor &t = p->tensors[i] = take[i].p;
       layout[i] = t.layout; F[i] = t.num_fields; N[i] = t.num_candidates; cap[i] = t.max_dets;
+      n_levels[i] = t.head ? t.head->n_levels : 0;   // 1..8: checked at submit
+      for (int l = 0; l < n_levels[i]; l++, n_lv++) { lv_h[n_lv] = t.head->lv[l].h; lv_w[n_lv] = t.head->lv[l].w; }
     }
     for (uint64_t &t : p->totals) t = 0;
-    const int rc = yolodec_set_plan((int)n, layout, F, N, cap, first, n_blocks, key_off, box_off, p->det_off, p->totals);
+    const int rc = yolodec_mixed_set_plan((int)n, layout, F, N, cap, n_levels, lv_h, lv_w, N, first, n_blocks, key_off, box_off, p->det_off, lv_first, p->totals);
     if (rc) *err = "group: bad decoder set";
     return rc;
   }
@@ -344,7 +354,7 @@ struct YdKind {
   // that is large enough, else a new one - and a free one that is too small makes room, or the pool would keep every size it saw.
   bool take_block(const Plan &p, SetData *d) {
     if (!p.totals[2]) return true;
-    const size_t bytes = yolodec_set_result_bytes(p.totals[5]);
+    const size_t bytes = yolodec_set_block_bytes(p.totals[5], p.totals[7]);
     for (size_t i = 0; i < blocks.size(); i++)
       if (blocks[i].bytes >= bytes) {
         d->block = blocks[i];
@@ -367,9 +377,14 @@ struct YdKind {
   }
   int launch(const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
     for (size_t i = 0; i < n; i++) d->slots.push_back(YdSlot{p.tensors[i].num_candidates, p.tensors[i].max_dets, p.det_off[i]});
-    return yolodec_launch_set(scratch, stream, p.tensors, (int)n, d->block.h, d->block.bytes, launches, err);
+    return yolodec_launch_set(scratch, stream, p.tensors, (int)n, d->block.h, d->block.bytes, launches, last_head_counts, err);
   }
-  void launched(const GroupCore *, const Plan &, size_t) const {}
+  void launched(const GroupCore *, const Plan &, size_t) {
+    n_heads += (uint64_t)last_head_counts[0];
+    n_head_sets += last_head_counts[0] ? 1 : 0;
+    n_head_uploads += (uint64_t)last_head_counts[1];
+    n_head_launches += (uint64_t)last_head_counts[2];
+  }
   // counts and records MOVE out of the pinned block: a later, larger set cannot overwrite what an earlier ticket has not collected
   void result(const SetData &d, size_t i, YdOut *o) const {
     const uint32_t *h_n = static_cast<const uint32_t *>(d.block.h);
@@ -1389,7 +1404,24 @@ int mi355_group_submit_yolodec(mi355_group *g, mi355_ctx *ctx, const float *d_te
   if (rc) return fail(g, rc, why);
   if (num_candidates && (!d_tensor || (uintptr_t)d_tensor % 4 != 0)) return fail(g, MI355_ERR_INVALID_ARG, "yolodec: null or misaligned tensors");
   // a tensor without a candidate is not read: it does not make the set wait for its stream (the model's last kernel, an upload)
-  return g->yd.submit(g, ctx, YdTensor{d_tensor, layout, num_fields, num_candidates, max_dets, *p}, num_candidates != 0, ticket);
+  return g->yd.submit(g, ctx, YdTensor{d_tensor, layout, num_fields, num_candidates, max_dets, *p, nullptr}, num_candidates != 0, ticket);
+}
+
+int mi355_group_submit_yolox_head(mi355_group *g, mi355_ctx *ctx, const mi355_yolox_level *levels, int n_levels, uint32_t num_classes, const mi355_yolo_params *p,
+                                  uint32_t max_dets, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !p || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context, settings or ticket");
+  const char *why = nullptr;
+  uint32_t A = 0;
+  int rc = yolox_head_check_shape(levels, n_levels, 1, num_classes, &A, &why);
+  if (!rc) rc = yolox_head_check_maps(levels, n_levels, &why);
+  if (rc) return fail(g, rc, why);
+  // a member of the decoder queue as a tensor is: 5 + C fields, A candidates (at least one: the maps are always read)
+  auto head = std::make_shared<YdHead>();
+  for (int l = 0; l < n_levels; l++) head->lv[l] = levels[l];
+  head->n_levels = n_levels;
+  return g->yd.submit(g, ctx, YdTensor{nullptr, MI355_YOLO_X_HEAD, 5 + num_classes, A, max_dets, *p, std::move(head)}, true, ticket);
 }
 
 int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *dets, uint32_t *n_dets) {
@@ -1425,6 +1457,17 @@ int mi355_group_yolodec_stats(mi355_group *g, uint64_t stats[4]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
   g->yd.stats(stats);
+  return MI355_OK;
+}
+
+int mi355_group_yolox_head_stats(mi355_group *g, uint64_t stats[4]) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  const YdKind &k = g->yd.kind;
+  stats[0] = k.n_heads;
+  stats[1] = k.n_head_sets;
+  stats[2] = k.n_head_uploads;
+  stats[3] = k.n_head_launches;
   return MI355_OK;
 }
 

@@ -324,17 +324,37 @@ int yolodec_check_args(size_t tensor_pitch_bytes, int n_tensors, int layout, uin
 // launch sets of the video group's decoder queue (yolodec.hip): tensors of independent instances, job tables
 constexpr int kYdSetMax = MI355_YOLODEC_SET_MAX;
 constexpr size_t kYdCountsBytes = 128;  // a result block: kYdSetMax kept counts (by job), then the jobs' records at their det_offset
-struct YdTensor { const float *data; int layout; uint32_t num_fields, num_candidates, max_dets; mi355_yolo_params p; };
-struct YdSetScratch;  // counters (zero between sets), keys, kept boxes and positions, results, on the device
+// A member is a decoded tensor (layout MI355_YOLO_V8 / MI355_YOLO_X: data) or the raw head maps of one yoloxinference tensor (layout
+// MI355_YOLO_X_HEAD: head; data is null, num_fields = 5 + C, num_candidates = A, the sum of the levels' h * w).
+struct YdHead { mi355_yolox_level lv[MI355_YOLOX_LEVELS_MAX]; int n_levels; };   // the submit's copy of the level structs
+// (a tensor member carries no levels: its `head` is empty, and copying it through the queue costs what it did)
+struct YdTensor { const float *data; int layout; uint32_t num_fields, num_candidates, max_dets; mi355_yolo_params p; std::shared_ptr<const YdHead> head; };
+struct YdSetScratch;  // counters (zero between sets), keys, kept boxes and positions, results, the head members' tables, on the device
 int yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, uint32_t *first_block,
                      uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]);
+// the shape checks of the YOLOX head entry points (yolox_head.hip): everything but the map pointers and pitches; *A_out: the candidates
+int yolox_head_check_shape(const mi355_yolox_level *lv, int n_levels, int n_tensors, uint32_t C, uint32_t *A_out, const char **why);
+// the map pointers of checked levels (pitches are not looked at: one tensor)
+int yolox_head_check_maps(const mi355_yolox_level *lv, int n_levels, const char **why);
+// The layout of one set that may hold head members (mi355_selftest_yolox_head_set_plan; yolodec_launch_set lays the set out with it).
+// kind: MI355_YOLO_V8 / _X / _X_HEAD per job. A head job reads its n_levels[j] and that many entries of level_h / level_w (the head
+// jobs' levels one after the other) and ignores num_candidates[j]; candidates[j] is its A (a tensor job's N). level_first_block: per
+// level, in the order of level_h, the running sum of ceil(h w / 256) within the job. totals: the six of yolodec_set_plan (a head
+// counts as a job with a candidate), then the head score blocks and the level jobs.
+int yolodec_mixed_set_plan(int n_jobs, const int *kind, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, const int *n_levels,
+                           const uint32_t *level_h, const uint32_t *level_w, uint32_t *candidates, uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset,
+                           uint64_t *box_offset, uint64_t *det_offset, uint32_t *level_first_block, uint64_t totals[8]);
 YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err);
 void yolodec_set_scratch_free(YdSetScratch *S);
-size_t yolodec_set_result_bytes(uint64_t records);  // the pinned block a set with that many records (totals[5]) is copied to
-// n <= kYdSetMax checked tensors on `stream`: the V8 score launch, the X score launch (each only if it has a job with a candidate),
-// the NMS launch, counts and records into h_block (nothing launched or copied if no tensor has a candidate)
+size_t yolodec_set_result_bytes(uint64_t records);  // the counts and that many records (totals[5]): what a set's download writes
+// the pinned block of a set: its results, and behind them the tables of its head members (level_jobs = totals[7]; 0: none)
+size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs);
+// n <= kYdSetMax checked members on `stream`: the head tables' upload (only if the set holds a head), the V8 score launch, the X
+// score launch (each only if it has a job with a candidate), the head score launch, the tensors' NMS launch, the heads' NMS launch,
+// counts and records into h_block (nothing launched or copied if no member has a candidate). head_counts: {heads, table uploads,
+// head kernel launches} of this set.
 int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
-                       std::string *err);
+                       int head_counts[3], std::string *err);
 // launch sets of the video group's hand-decoder queue (handdec.hip): palm and landmark tensors of independent instances, job tables
 constexpr int kHnSetMax = MI355_HANDDEC_SET_MAX;
 constexpr size_t kHnCountsBytes = 128;  // a result block: kHnSetMax counts (by job), n x MI355_HAND_MAX box records (by job), then

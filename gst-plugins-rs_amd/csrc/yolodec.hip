@@ -384,6 +384,65 @@ int yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, 
   return MI355_OK;
 }
 
+// the layout of one set that may hold heads (mi355_selftest_yolox_head_set_plan; yolodec_launch_set lays the set out with it): a
+// tensor job gets what yolodec_set_plan gives it, a head job is a job of A candidates whose tiles run level by level in a launch of
+// the heads' own
+int yolodec_mixed_set_plan(int n_jobs, const int *kind, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, const int *n_levels,
+                           const uint32_t *level_h, const uint32_t *level_w, uint32_t *candidates, uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset,
+                           uint64_t *box_offset, uint64_t *det_offset, uint32_t *level_first_block, uint64_t totals[8]) {
+  if (n_jobs < 0 || n_jobs > kYdSetMax || !totals) return MI355_ERR_INVALID_ARG;
+  if (n_jobs > 0 && (!kind || !num_fields || !num_candidates || !max_dets || !candidates || !first_block || !blocks || !key_offset || !box_offset || !det_offset))
+    return MI355_ERR_INVALID_ARG;
+  size_t at = 0;   // levels read so far
+  for (int j = 0; j < n_jobs; j++) {
+    const char *why = nullptr;
+    if (kind[j] != MI355_YOLO_X_HEAD) {
+      if (const int rc = yolodec_check_args((size_t)num_fields[j] * num_candidates[j] * 4, 1, kind[j], num_fields[j], num_candidates[j], &why)) return rc;
+      candidates[j] = num_candidates[j];
+      continue;
+    }
+    if (!n_levels || !level_h || !level_w || !level_first_block) return MI355_ERR_INVALID_ARG;
+    mi355_yolox_level lv[MI355_YOLOX_LEVELS_MAX] = {};
+    for (int l = 0; l < n_levels[j] && l < MI355_YOLOX_LEVELS_MAX; l++) {
+      lv[l].h = level_h[at + (size_t)l];
+      lv[l].w = level_w[at + (size_t)l];
+      lv[l].stride = 1;   // no part of the layout
+    }
+    if (const int rc = yolox_head_check_shape(lv, n_levels[j], 1, num_fields[j] < 5 ? 0 : num_fields[j] - 5, &candidates[j], &why)) return rc;
+    at += (size_t)n_levels[j];
+  }
+  uint64_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // V8 blocks, X blocks, jobs with a candidate, keys, boxes, records, head blocks, level jobs
+  at = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    const uint32_t N = candidates[j];
+    if (kind[j] == MI355_YOLO_X_HEAD) {
+      first_block[j] = (uint32_t)t[6];
+      uint32_t b = 0;
+      for (int l = 0; l < n_levels[j]; l++, at++) {
+        level_first_block[at] = b;
+        b += (level_h[at] * level_w[at] + kScoreThreads - 1) / kScoreThreads;
+      }
+      blocks[j] = b;
+      t[6] += b;
+      t[7] += (uint64_t)n_levels[j];
+    } else {
+      uint64_t &layout_blocks = t[kind[j] == MI355_YOLO_V8 ? 0 : 1];
+      blocks[j] = (N + kScoreThreads - 1) / kScoreThreads;
+      first_block[j] = (uint32_t)layout_blocks;   // at most 32 * 256 blocks
+      layout_blocks += blocks[j];
+    }
+    if (N) t[2]++;
+    key_offset[j] = t[3];
+    t[3] += pow2_at_least(N);
+    box_offset[j] = t[4];
+    t[4] += N;
+    det_offset[j] = t[5];
+    t[5] += max_dets[j] < N ? max_dets[j] : N;
+  }
+  for (int k = 0; k < 8; k++) totals[k] = t[k];
+  return MI355_OK;
+}
+
 // scratch of one queue; grows to the largest set seen
 struct YdSetScratch {
   uint32_t *d_count = nullptr;   // [kYdSetMax] survivors; zero between sets
@@ -392,7 +451,8 @@ struct YdSetScratch {
   float4 *d_kbox = nullptr;
   uint32_t *d_ksrc = nullptr;
   uint8_t *d_out = nullptr;      // [kYdSetMax] counts (kYdCountsBytes), then the jobs' records at their det_offset
-  size_t key_elems = 0, kbox_elems = 0, ksrc_elems = 0, out_bytes = 0;
+  YhTable *d_table = nullptr;    // the head members' tables of the set that runs; made with the first set that holds a head
+  size_t key_elems = 0, kbox_elems = 0, ksrc_elems = 0, out_bytes = 0, tables = 0;
 };
 
 YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err) {
@@ -415,6 +475,7 @@ void yolodec_set_scratch_free(YdSetScratch *S) {
   if (S->d_kbox) (void)hipFree(S->d_kbox);
   if (S->d_ksrc) (void)hipFree(S->d_ksrc);
   if (S->d_out) (void)hipFree(S->d_out);
+  if (S->d_table) (void)hipFree(S->d_table);
   delete S;
 }
 
@@ -432,21 +493,38 @@ static bool set_grow(T **p, size_t *have, size_t want) {
 
 size_t yolodec_set_result_bytes(uint64_t records) { return kYdCountsBytes + (size_t)records * sizeof(mi355_yolo_det); }
 
+// where the head tables stand in a set's pinned block: behind its results, which the download writes
+static size_t set_table_offset(uint64_t records) { return (yolodec_set_result_bytes(records) + 63) / 64 * 64; }
+
+size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs) {
+  return level_jobs ? set_table_offset(records) + yh_table_bytes(level_jobs) : yolodec_set_result_bytes(records);
+}
+
 int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
-                       std::string *err) {
+                       int head_counts[3], std::string *err) {
   *kernel_launches = 0;
+  head_counts[0] = head_counts[1] = head_counts[2] = 0;
   if (!S || !tensors || n < 1 || n > kYdSetMax) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
-  int layout[kYdSetMax];
+  int layout[kYdSetMax], n_levels[kYdSetMax];
   uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], blocks[kYdSetMax];
-  uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax], totals[6];
-  for (int i = 0; i < n; i++) { layout[i] = tensors[i].layout; F[i] = tensors[i].num_fields; N[i] = tensors[i].num_candidates; cap[i] = tensors[i].max_dets; }
-  const int rc = yolodec_set_plan(n, layout, F, N, cap, first, blocks, key_off, box_off, det_off, totals);
+  uint32_t lv_h[kYhLevelJobsMax], lv_w[kYhLevelJobsMax], lv_first[kYhLevelJobsMax];
+  uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax], totals[8];
+  size_t n_lv = 0;
+  for (int i = 0; i < n; i++) {
+    layout[i] = tensors[i].layout; F[i] = tensors[i].num_fields; N[i] = tensors[i].num_candidates; cap[i] = tensors[i].max_dets;
+    if (layout[i] == MI355_YOLO_X_HEAD && !tensors[i].head) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
+    n_levels[i] = layout[i] == MI355_YOLO_X_HEAD ? tensors[i].head->n_levels : 0;
+    if (n_levels[i] < 0 || n_levels[i] > MI355_YOLOX_LEVELS_MAX) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
+    for (int l = 0; l < n_levels[i]; l++, n_lv++) { lv_h[n_lv] = tensors[i].head->lv[l].h; lv_w[n_lv] = tensors[i].head->lv[l].w; }
+  }
+  const int rc = yolodec_mixed_set_plan(n, layout, F, N, cap, n_levels, lv_h, lv_w, N, first, blocks, key_off, box_off, det_off, lv_first, totals);
   if (rc) { *err = "yolodec: bad launch set"; return rc; }
   if (totals[2] == 0) return MI355_OK;   // no job has a candidate: nothing to launch, nothing to copy
-  const size_t bytes = yolodec_set_result_bytes(totals[5]);
-  if (!h_block || h_block_bytes < bytes) { *err = "yolodec: the pinned result block is too small for the set"; return MI355_ERR_INVALID_ARG; }
+  const size_t bytes = yolodec_set_result_bytes(totals[5]), table_bytes = yh_table_bytes(totals[7]);
+  if (!h_block || h_block_bytes < yolodec_set_block_bytes(totals[5], totals[7])) { *err = "yolodec: the pinned block is too small for the set"; return MI355_ERR_INVALID_ARG; }
   if (!set_grow(&S->d_keys, &S->key_elems, (size_t)totals[3]) || !set_grow(&S->d_kbox, &S->kbox_elems, (size_t)totals[4]) ||
-      !set_grow(&S->d_ksrc, &S->ksrc_elems, (size_t)totals[4]) || !set_grow(&S->d_out, &S->out_bytes, bytes)) {
+      !set_grow(&S->d_ksrc, &S->ksrc_elems, (size_t)totals[4]) || !set_grow(&S->d_out, &S->out_bytes, bytes) ||
+      (table_bytes && !set_grow(&S->d_table, &S->tables, (size_t)1))) {
     *err = "hipMalloc(yolodec set scratch)";
     return MI355_ERR_OUT_OF_MEMORY;
   }
@@ -455,10 +533,49 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
     S->count_zero = true;
   }
   YdJobTable score[2] = {}, nms = {};
+  YhTable *heads = table_bytes ? reinterpret_cast<YhTable *>(static_cast<uint8_t *>(h_block) + set_table_offset(totals[5])) : nullptr;
+  uint32_t n_heads = 0, n_level_jobs = 0;
   uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out);
   mi355_yolo_det *d_dets = reinterpret_cast<mi355_yolo_det *>(S->d_out + kYdCountsBytes);
   for (int i = 0; i < n; i++) {
     if (!N[i]) continue;   // no candidate: no job
+    if (layout[i] == MI355_YOLO_X_HEAD) {
+      YhHeadJob &H = heads->head[n_heads];
+      H.count = S->d_count + i;
+      H.keys = S->d_keys + key_off[i];
+      H.kbox = S->d_kbox + box_off[i];
+      H.ksrc = S->d_ksrc + box_off[i];
+      H.dets = d_dets + det_off[i];
+      H.n_dets = d_n + i;
+      H.A = N[i];
+      H.C = F[i] - 5;
+      H.key_cap = pow2_at_least(N[i]);
+      H.max_dets = cap[i];
+      H.first_level = n_level_jobs;
+      H.n_levels = (uint32_t)n_levels[i];
+      H.p = tensors[i].p;
+      H.pad = 0;
+      uint32_t a = 0;
+      for (int l = 0; l < MI355_YOLOX_LEVELS_MAX; l++) {
+        H.start[l] = a;   // A from n_levels on
+        if (l >= n_levels[i]) continue;
+        const mi355_yolox_level &v = tensors[i].head->lv[l];
+        YhLevelJob &L = heads->level[n_level_jobs];
+        L.reg = v.reg;
+        L.obj = v.obj;
+        L.cls = v.cls;
+        L.w = v.w;
+        L.hw = v.h * v.w;
+        L.first_cand = a;
+        L.first_block = first[i] + lv_first[n_level_jobs];   // the level jobs of a set are in the order of the plan's levels
+        L.head = n_heads;
+        L.stride = (float)v.stride;   // <= 65536: exact
+        a += L.hw;
+        n_level_jobs++;
+      }
+      n_heads++;
+      continue;
+    }
     YdJob J;
     J.data = tensors[i].data;
     J.count = S->d_count + i;
@@ -479,20 +596,35 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
     T.job[T.n_jobs++] = J;
     nms.job[nms.n_jobs++] = J;
   }
-  S->count_zero = false;   // true again only once the NMS launch has been enqueued behind the score launches
+  hipError_t e = hipSuccess;
+  if (n_heads) {
+    // the tables of all heads of the set, one copy: what the launches below read stands in device memory behind it
+    e = hipMemcpyAsync(S->d_table, heads, table_bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) { *err = std::string("yolodec set head tables H2D: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+    head_counts[1] = 1;
+  }
+  S->count_zero = false;   // true again only once the NMS launches have been enqueued behind the score launches
   for (int l = 0; l < 2; l++) {
     if (!score[l].n_jobs) continue;
     const dim3 grid((uint32_t)totals[l]);
     if (l == 0) hipLaunchKernelGGL(yolodec_score_jobs_kernel<0>, grid, dim3(kScoreThreads), 0, stream, score[l]);
     else hipLaunchKernelGGL(yolodec_score_jobs_kernel<1>, grid, dim3(kScoreThreads), 0, stream, score[l]);
-    const hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) { *err = std::string("yolodec score jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
     (*kernel_launches)++;
   }
-  hipLaunchKernelGGL(yolodec_nms_jobs_kernel, dim3((uint32_t)nms.n_jobs), dim3(kNmsThreads), 0, stream, nms);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { *err = std::string("yolodec nms jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
-  (*kernel_launches)++;
+  if (nms.n_jobs) {
+    hipLaunchKernelGGL(yolodec_nms_jobs_kernel, dim3((uint32_t)nms.n_jobs), dim3(kNmsThreads), 0, stream, nms);
+    e = hipGetLastError();
+    if (e != hipSuccess) { *err = std::string("yolodec nms jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+    (*kernel_launches)++;
+  }
+  if (n_heads) {
+    // (a launch of their own: merged into the tensors' NMS kernel, the head loader's registers would be every tensor job's)
+    if (const int hrc = yolox_head_launch_jobs(stream, S->d_table, n_heads, n_level_jobs, (uint32_t)totals[6], &head_counts[2], err)) return hrc;
+    *kernel_launches += head_counts[2];
+    head_counts[0] = (int)n_heads;
+  }
   S->count_zero = true;
   e = hipMemcpyAsync(h_block, S->d_out, bytes, hipMemcpyDeviceToHost, stream);
   if (e != hipSuccess) { *err = std::string("yolodec set D2H: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
@@ -553,6 +685,14 @@ int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int l
 int mi355_selftest_yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets,
                                     uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]) {
   return yolodec_set_plan(n_jobs, layout, num_fields, num_candidates, max_dets, first_block, blocks, key_offset, box_offset, det_offset, totals);
+}
+
+int mi355_selftest_yolox_head_set_plan(int n_jobs, const int *kind, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets,
+                                       const int *n_levels, const uint32_t *level_h, const uint32_t *level_w, uint32_t *candidates, uint32_t *first_block,
+                                       uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint32_t *level_first_block,
+                                       uint64_t totals[8]) {
+  return yolodec_mixed_set_plan(n_jobs, kind, num_fields, num_candidates, max_dets, n_levels, level_h, level_w, candidates, first_block, blocks, key_offset, box_offset,
+                                det_offset, level_first_block, totals);
 }
 
 }  // extern "C"

@@ -307,4 +307,39 @@ mi355_yolo_det *yolodec_d_dets(YoloDecState *s, uint32_t T);
 // results down, one synchronisation, the caller's arrays filled
 int yolodec_download(mi355_ctx *ctx, YoloDecState *s, uint32_t T, mi355_yolo_det *dets, uint32_t max_dets, uint32_t *n_dets);
 
+// ---- the head members of a decoder launch set (the video group's decoder queue): yolodec_launch_set builds the two tables in the
+// set's pinned block and uploads them in one copy; the job kernels of yolox_head.hip read them from device memory (32 heads x 8
+// levels do not fit the kernel arguments). A level job is one level of one head; every field a block reads is block-uniform.
+struct YhHeadJob {
+  uint32_t *count;              // the head's survivor counter; zero on entry to the score launch, left at zero by the NMS launch
+  unsigned long long *keys;     // key_cap entries
+  float4 *kbox;                 // A entries
+  uint32_t *ksrc;               // A entries
+  mi355_yolo_det *dets;         // min(max_dets, A) records
+  uint32_t *n_dets;
+  uint32_t A, C, key_cap, max_dets;
+  uint32_t first_level, n_levels;   // its level jobs: level[first_level .. first_level + n_levels)
+  mi355_yolo_params p;
+  uint32_t pad;
+  uint32_t start[MI355_YOLOX_LEVELS_MAX];   // first candidate of level l; A from n_levels on
+};
+struct YhLevelJob {
+  const float *reg, *obj, *cls;
+  uint32_t w, hw;               // hw = h * w
+  uint32_t first_cand;          // candidate index of the level's element 0
+  uint32_t first_block;         // its first tile in the head score launch; tiles are 256 candidates of this level
+  uint32_t head;                // index into YhTable::head
+  float stride;
+};
+constexpr int kYhLevelJobsMax = kYdSetMax * MI355_YOLOX_LEVELS_MAX;
+struct YhTable {
+  YhHeadJob head[kYdSetMax];
+  YhLevelJob level[kYhLevelJobsMax];   // in first_block order; the upload ends behind the last one used
+};
+static_assert(sizeof(YhHeadJob) == 120 && sizeof(YhLevelJob) == 48, "the head tables have no padding holes");
+inline size_t yh_table_bytes(uint64_t level_jobs) { return level_jobs ? offsetof(YhTable, level) + (size_t)level_jobs * sizeof(YhLevelJob) : 0; }
+// the two launches over uploaded tables: the score launch (grid = score_blocks, the level jobs' tiles), the NMS launch (a block per head)
+int yolox_head_launch_jobs(hipStream_t stream, const YhTable *d_table, uint32_t n_heads, uint32_t n_level_jobs, uint32_t score_blocks, int *kernel_launches,
+                           std::string *err);
+
 }  // namespace mi355

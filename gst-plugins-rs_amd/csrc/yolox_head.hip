@@ -27,11 +27,15 @@
 //                             reads by whole waves, row pieces of 128 bytes out.
 //   yolox_input_kernel        RGB u8 -> [3][H][W] f32: one lane takes 4 pixels of a row (12 bytes as three dwords where the row
 //                             piece is aligned, as the 3-byte hsvfilter kernel does) and stores one float4 per plane.
-// The device functions (locate, head_score_tile, HeadBoxes) take what a job table would hold, so a job-table wrapper for the video
-// group's decoder queue stays thin.
+//   yolox_head_score_jobs_kernel, yolox_head_nms_jobs_kernel
+//                             the job-table forms for the video group's decoder queue (group.hip; the set is laid out and launched
+//                             by yolodec_launch_set): heads of independent instances in two launches per set. A tile is 256
+//                             candidates of one level and its block reads that level's job, so there is no scan of the levels and
+//                             no per-lane level table; the candidate's work is score_cand / best_class / reg_box, as above.
 #include "yolodec_device.hpp"
 
 #include <cstring>
+#include <string>
 
 namespace mi355 {
 
@@ -164,6 +168,26 @@ __device__ __forceinline__ void best_class(const float *__restrict__ col, size_t
   bits_out = __float_as_uint(sm);
 }
 
+// element i of a level with the planes obj[hw], cls[C][hw]: does the candidate stay, and if so its class and confidence. Shared by
+// the lone kernel and the job-table kernel.
+__device__ __forceinline__ bool score_cand(const float *__restrict__ obj, const float *__restrict__ cls, uint32_t hw, uint32_t i, uint32_t C,
+                                           const mi355_yolo_params &P, uint32_t &best_cls, uint32_t &conf_bits) {
+  const float so = sigmoid_c(obj[i]);
+  if (so < P.box_confidence_threshold) return false;   // yolotensordec/imp.rs:332, before any class plane is touched
+  uint32_t sc_bits = 0;
+  best_class(cls + i, (size_t)hw, C, best_cls, sc_bits);
+  const float sc = __uint_as_float(sc_bits);
+  conf_bits = __float_as_uint(so * sc);
+  return !(sc < P.class_confidence_threshold);
+}
+
+// element i of a level with the planes reg[4][hw] at grid position (gx, gy) and stride s: its box
+__device__ __forceinline__ Box reg_box(const float *__restrict__ reg, uint32_t hw, uint32_t i, float gx, float gy, float s) {
+  const float *__restrict__ r = reg + i;
+  const float r0 = r[0], r1 = r[(size_t)hw], r2 = r[(size_t)2 * hw], r3 = r[(size_t)3 * hw];
+  return centre_box((r0 + gx) * s, (r1 + gy) * s, exp_c(r2) * s, exp_c(r3) * s);
+}
+
 // the score work of the 256-candidate tile of tensor t that starts at candidate c0, by the whole block: survivors are appended to
 // keys[0 .. key_pitch) behind *count
 __device__ __forceinline__ void head_score_tile(const HeadMaps &H, uint32_t t, uint32_t A, const mi355_yolo_params &P, uint32_t c0, uint32_t *__restrict__ count,
@@ -173,15 +197,7 @@ __device__ __forceinline__ void head_score_tile(const HeadMaps &H, uint32_t t, u
   uint32_t best_cls = 0, conf_bits = 0;
   if (keep) {
     const Cand k = locate(H, t, a);
-    const float so = sigmoid_c(k.obj[k.i]);
-    if (so < P.box_confidence_threshold) keep = false;   // yolotensordec/imp.rs:332, before any class plane is touched
-    if (keep) {
-      uint32_t sc_bits = 0;
-      best_class(k.cls + k.i, (size_t)k.hw, H.C, best_cls, sc_bits);
-      const float sc = __uint_as_float(sc_bits);
-      if (sc < P.class_confidence_threshold) keep = false;
-      conf_bits = __float_as_uint(so * sc);
-    }
+    keep = score_cand(k.obj, k.cls, k.hw, k.i, H.C, P, best_cls, conf_bits);
   }
   append_keys(keep, make_key(best_cls, conf_bits, a), count, keys, key_pitch);
 }
@@ -200,9 +216,7 @@ struct HeadBoxes {
   uint32_t t;
   __device__ __forceinline__ Box operator()(uint32_t a) const {
     const Cand k = locate(H, t, a);
-    const float *__restrict__ r = k.reg + k.i;
-    const float r0 = r[0], r1 = r[(size_t)k.hw], r2 = r[(size_t)2 * k.hw], r3 = r[(size_t)3 * k.hw];
-    return centre_box((r0 + k.gx) * k.s, (r1 + k.gy) * k.s, exp_c(r2) * k.s, exp_c(r3) * k.s);
+    return reg_box(k.reg, k.hw, k.i, k.gx, k.gy, k.s);
   }
 };
 
@@ -217,6 +231,59 @@ __global__ __launch_bounds__(kNmsThreads) void yolox_head_nms_kernel(const HeadM
   const HeadBoxes boxes = {H, t};
   nms_block(boxes, H.C, A, params[t].iou_threshold, count + t, keys + (size_t)t * key_pitch, kbox + (size_t)t * A, ksrc + (size_t)t * A,
             dets + (size_t)t * max_dets, max_dets, n_dets + t, lds_keys, S);
+}
+
+// ---- job-table forms (the video group's decoder queue): the heads of independent instances - own levels, C, settings, scratch - in
+// one launch set. The tables (YhTable, yolodec_device.hpp) are in device memory; a level's fields come with its job, so nothing
+// scans the levels per lane as locate does.
+
+// One flat grid over the tiles of the level jobs; a tile is 256 candidates of ONE level. The level job is the last one whose first
+// tile is at or before this block: a binary search on blockIdx.x alone, block-uniform, before anything else. (A two-step form - the
+// head among 32 first blocks in one load, then the level among the head's 8: three dependent loads for up to ten - measured the same
+// and was dropped)
+__global__ __launch_bounds__(kScoreThreads) void yolox_head_score_jobs_kernel(const YhTable *__restrict__ T, uint32_t n_level_jobs) {
+  uint32_t lo = 0, hi = n_level_jobs;   // level[lo].first_block <= blockIdx.x throughout: level[0].first_block is 0
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (T->level[mid].first_block <= blockIdx.x) lo = mid;
+    else hi = mid;
+  }
+  const YhLevelJob *__restrict__ L = T->level + lo;
+  const YhHeadJob *__restrict__ J = T->head + L->head;
+  const uint32_t hw = L->hw, i = (blockIdx.x - L->first_block) * kScoreThreads + (uint32_t)threadIdx.x;
+  const mi355_yolo_params P = J->p;
+  bool keep = i < hw;   // (a grid larger than the plan's total: no lane of the last level's surplus tiles stays)
+  uint32_t best_cls = 0, conf_bits = 0;
+  if (keep) keep = score_cand(L->obj, L->cls, hw, i, J->C, P, best_cls, conf_bits);
+  append_keys(keep, make_key(best_cls, conf_bits, L->first_cand + i), J->count, J->keys, (size_t)J->key_cap);
+}
+
+// the box loader nms_block takes: the survivor's level from the head's prefix sums (held in registers: every index is a constant),
+// then that level job's fields
+struct HeadJobBoxes {
+  const YhLevelJob *__restrict__ level;   // the head's first level job
+  uint32_t start[kLv];
+  __device__ __forceinline__ Box operator()(uint32_t a) const {
+    uint32_t l = 0;
+#pragma unroll
+    for (int k = 1; k < kLv; k++) l += a >= start[k] ? 1u : 0u;   // start[k] = A > a from n_levels on
+    const YhLevelJob *__restrict__ L = level + l;
+    const uint32_t w = L->w, i = a - L->first_cand, y = i / w;
+    return reg_box(L->reg, L->hw, i, (float)(i - y * w), (float)y, L->stride);
+  }
+};
+
+// one block per head
+__global__ __launch_bounds__(kNmsThreads) void yolox_head_nms_jobs_kernel(const YhTable *__restrict__ T, uint32_t n_heads) {
+  __shared__ unsigned long long lds_keys[kLdsSortKeys];
+  __shared__ NmsShared S;
+  if (blockIdx.x >= n_heads) return;
+  const YhHeadJob *__restrict__ J = T->head + blockIdx.x;
+  HeadJobBoxes boxes;
+  boxes.level = T->level + J->first_level;
+#pragma unroll
+  for (int k = 0; k < kLv; k++) boxes.start[k] = J->start[k];
+  nms_block(boxes, J->C, J->A, J->p.iou_threshold, J->count, J->keys, J->kbox, J->ksrc, J->dets, J->max_dets, J->n_dets, lds_keys, S);
 }
 
 // field f of the decoded row (f is wave-uniform in the kernel below)
@@ -298,10 +365,9 @@ __global__ __launch_bounds__(256) void yolox_input_kernel(const uint8_t *__restr
 
 }  // namespace
 
-// the checks that need no device (every entry point; mi355_selftest_yolox_head_check). device: the pitches count and n_tensors may
-// exceed 1; with_out: out_pitch_bytes is the pitch of the materialised tensor. *A_out: the candidates of one tensor.
-static int yolox_head_check_args(const mi355_yolox_level *lv, int n_levels, int n_tensors, uint32_t C, bool device, bool with_out, size_t out_pitch_bytes,
-                                 uint32_t *A_out, const char **why) {
+// the checks of the level shapes (every entry point, the group's submit and its set plan): everything but the map pointers and
+// pitches. *A_out: the candidates of one tensor.
+int yolox_head_check_shape(const mi355_yolox_level *lv, int n_levels, int n_tensors, uint32_t C, uint32_t *A_out, const char **why) {
   *why = nullptr;
   if (!lv) *why = "yolox_head: null levels";
   else if (n_levels < 1) *why = "yolox_head: n_levels must be at least 1";
@@ -324,20 +390,41 @@ static int yolox_head_check_args(const mi355_yolox_level *lv, int n_levels, int 
     else if (hw > kMaxCandidates || (A += hw) > kMaxCandidates) *why = "yolox_head: more than 65536 candidates";
     if (*why) return MI355_ERR_UNSUPPORTED;
   }
-  for (int l = 0; l < n_levels; l++) {
-    const uint64_t hw = (uint64_t)lv[l].h * lv[l].w;
-    if (!lv[l].reg || !lv[l].obj || !lv[l].cls) *why = "yolox_head: a null map";
-    else if ((uintptr_t)lv[l].reg % 4 != 0 || (uintptr_t)lv[l].obj % 4 != 0 || (uintptr_t)lv[l].cls % 4 != 0) *why = "yolox_head: a map is not 4-byte aligned";
-    else if (device && (lv[l].reg_pitch_bytes % 4 != 0 || lv[l].obj_pitch_bytes % 4 != 0 || lv[l].cls_pitch_bytes % 4 != 0 || lv[l].reg_pitch_bytes < 4 * hw * 4 ||
-                        lv[l].obj_pitch_bytes < hw * 4 || lv[l].cls_pitch_bytes < (uint64_t)C * hw * 4))
-      *why = "yolox_head: a map pitch is smaller than the map or no multiple of 4";
-    if (*why) return MI355_ERR_INVALID_ARG;
-  }
-  if (with_out && (out_pitch_bytes % 4 != 0 || out_pitch_bytes < A * (5 + (uint64_t)C) * 4)) {
+  if (A_out) *A_out = (uint32_t)A;
+  return MI355_OK;
+}
+
+// the maps of one level of a checked shape; device: the pitches count
+static int check_level_maps(const mi355_yolox_level &lv, bool device, uint32_t C, const char **why) {
+  const uint64_t hw = (uint64_t)lv.h * lv.w;
+  if (!lv.reg || !lv.obj || !lv.cls) *why = "yolox_head: a null map";
+  else if ((uintptr_t)lv.reg % 4 != 0 || (uintptr_t)lv.obj % 4 != 0 || (uintptr_t)lv.cls % 4 != 0) *why = "yolox_head: a map is not 4-byte aligned";
+  else if (device && (lv.reg_pitch_bytes % 4 != 0 || lv.obj_pitch_bytes % 4 != 0 || lv.cls_pitch_bytes % 4 != 0 || lv.reg_pitch_bytes < 4 * hw * 4 ||
+                      lv.obj_pitch_bytes < hw * 4 || lv.cls_pitch_bytes < (uint64_t)C * hw * 4))
+    *why = "yolox_head: a map pitch is smaller than the map or no multiple of 4";
+  return *why ? MI355_ERR_INVALID_ARG : MI355_OK;
+}
+
+int yolox_head_check_maps(const mi355_yolox_level *lv, int n_levels, const char **why) {
+  *why = nullptr;
+  for (int l = 0; l < n_levels; l++)
+    if (const int rc = check_level_maps(lv[l], false, 0, why)) return rc;
+  return MI355_OK;
+}
+
+// the checks that need no device (every entry point; mi355_selftest_yolox_head_check). device: the pitches count and n_tensors may
+// exceed 1; with_out: out_pitch_bytes is the pitch of the materialised tensor. *A_out: the candidates of one tensor.
+static int yolox_head_check_args(const mi355_yolox_level *lv, int n_levels, int n_tensors, uint32_t C, bool device, bool with_out, size_t out_pitch_bytes,
+                                 uint32_t *A_out, const char **why) {
+  uint32_t A = 0;
+  if (const int rc = yolox_head_check_shape(lv, n_levels, n_tensors, C, &A, why)) return rc;
+  for (int l = 0; l < n_levels; l++)
+    if (const int rc = check_level_maps(lv[l], device, C, why)) return rc;
+  if (with_out && (out_pitch_bytes % 4 != 0 || out_pitch_bytes < (uint64_t)A * (5 + (uint64_t)C) * 4)) {
     *why = "yolox_head: output pitch is smaller than the tensor or no multiple of 4";
     return MI355_ERR_INVALID_ARG;
   }
-  if (A_out) *A_out = (uint32_t)A;
+  if (A_out) *A_out = A;
   return MI355_OK;
 }
 
@@ -376,6 +463,24 @@ static int head_dets_run(mi355_ctx *ctx, YoloDecState *s, const HeadMaps &H, uin
                      yolodec_d_dets(s, T), max_dets, yolodec_d_counts(s));
   if ((rc = check_hip(ctx, hipGetLastError(), "yolox_head nms launch"))) return rc;
   return yolodec_download(ctx, s, T, dets, max_dets, n_dets);
+}
+
+// the head members of a decoder launch set (yolodec_launch_set): the tables are on the device behind what `stream` holds
+int yolox_head_launch_jobs(hipStream_t stream, const YhTable *d_table, uint32_t n_heads, uint32_t n_level_jobs, uint32_t score_blocks, int *kernel_launches,
+                           std::string *err) {
+  if (!d_table || n_heads < 1 || n_heads > (uint32_t)kYdSetMax || n_level_jobs < n_heads || n_level_jobs > (uint32_t)kYhLevelJobsMax || score_blocks < n_level_jobs) {
+    *err = "yolox_head: bad job tables";
+    return MI355_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(yolox_head_score_jobs_kernel, dim3(score_blocks), dim3(kScoreThreads), 0, stream, d_table, n_level_jobs);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { *err = std::string("yolox_head score jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+  (*kernel_launches)++;
+  hipLaunchKernelGGL(yolox_head_nms_jobs_kernel, dim3(n_heads), dim3(kNmsThreads), 0, stream, d_table, n_heads);
+  e = hipGetLastError();
+  if (e != hipSuccess) { *err = std::string("yolox_head nms jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+  (*kernel_launches)++;
+  return MI355_OK;
 }
 
 }  // namespace mi355

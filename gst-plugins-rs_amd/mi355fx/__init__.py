@@ -100,6 +100,7 @@ class YoloParams(C.Structure):
 
 
 YOLO_LAYOUT = {"V8": 0, "X": 1}   # mi355_yolo_layout
+YOLO_X_HEAD = 2   # MI355_YOLO_X_HEAD: a head member's kind in selftest_yolox_head_set_plan (no layout of the entry points)
 # mi355_yolo_det as a numpy record
 YOLO_DET = np.dtype([("xmin", "<f4"), ("ymin", "<f4"), ("xmax", "<f4"), ("ymax", "<f4"), ("x", "<i4"), ("y", "<i4"), ("width", "<i4"),
                      ("height", "<i4"), ("class_id", "<u4"), ("confidence", "<f4"), ("candidate", "<u4"), ("reserved", "<u4")])
@@ -374,6 +375,10 @@ def load_library():
         "mi355_group_wait_yolodec": (i, [vp, C.c_uint64, vp, C.POINTER(C.c_uint32)]),
         "mi355_group_yolodec_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "mi355_selftest_yolodec_set_plan": (i, [i, C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 5 + [C.POINTER(C.c_uint64)] * 4),
+        "mi355_group_submit_yolox_head": (i, [vp, vp, C.POINTER(YoloxLevel), i, C.c_uint32, C.POINTER(YoloParams), C.c_uint32, C.POINTER(C.c_uint64)]),
+        "mi355_group_yolox_head_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_yolox_head_set_plan": (i, [i, C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 3 + [C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 5 +
+                                               [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
         "mi355_group_set_handdec_rendezvous": (i, [vp, i, C.c_uint]),
         "mi355_group_submit_handdec_palm": (i, [vp, vp, vp, C.c_uint32, C.POINTER(HandParams), C.POINTER(C.c_uint64)]),
         "mi355_group_submit_handdec_landmarks": (i, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(HandParams), C.POINTER(C.c_uint64)]),
@@ -689,9 +694,28 @@ class Group:
         return dets[:min(n.value, cap)].copy(), n.value
 
     def yolodec_stats(self):
-        """(tensors launched, launch sets, tensors in the largest set, kernel launches)."""
+        """(tensors launched, launch sets, tensors in the largest set, kernel launches); a head counts as a tensor."""
         c = (C.c_uint64 * 4)()
         self._ck(self.L.mi355_group_yolodec_stats(self.h, c))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
+    def submit_yolox_head(self, ctx, levels, num_classes, params, max_dets=None, n_levels=None):
+        """The raw head maps of one tensor of stream `ctx` as a member of the decoder queue (levels: as Context.yolox_head_dets_device
+        takes them, or None for a null pointer; the pitches are ignored; max_dets: default A); returns the ticket, which
+        wait_yolodec collects."""
+        n = (0 if levels is None else len(levels)) if n_levels is None else n_levels
+        cap = (0 if levels is None else yolox_candidates(levels)) if max_dets is None else max_dets
+        p = None if params is None else _yolo_params(params)[0]
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_yolox_head(self.h, None if ctx is None else ctx.h, None if levels is None else _yolox_levels(levels), n, num_classes, p, cap,
+                                                      C.byref(t)))
+        self._yolodec_caps[t.value] = cap
+        return t.value
+
+    def yolox_head_stats(self):
+        """(heads launched, launch sets that held a head, level-table uploads, head kernel launches)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.L.mi355_group_yolox_head_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
     # ---- handdetectiontensordec / handlandmarktensordec tensors of independent elements
@@ -770,6 +794,35 @@ def selftest_yolodec_set_plan(layouts, num_fields, num_candidates, max_dets):
     key, box, det, totals = (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * 6)()
     rc = L.mi355_selftest_yolodec_set_plan(n, lay, F, N, cap, first, blocks, key, box, det, totals)
     return rc, list(first)[:n], list(blocks)[:n], list(key)[:n], list(box)[:n], list(det)[:n], list(totals)
+
+
+def selftest_yolox_head_set_plan(kinds, num_fields, num_candidates, max_dets, level_shapes):
+    """mi355_selftest_yolox_head_set_plan (host only): the layout of one decoder launch set that may hold heads. kinds: "V8" / "X" /
+    YOLO_X_HEAD or ints; level_shapes: per job a list of (h, w) - a head job's levels, anything empty for a tensor job - or None for
+    null level arrays. Returns (status, candidates, first_block, blocks, key_offset, box_offset, det_offset, level_first_block,
+    totals); level_first_block is per job, as level_shapes is."""
+    L = load_library()
+    n = len(kinds)
+    m = max(n, 1)
+    kind = (C.c_int * m)(*[YOLO_LAYOUT.get(v, v) for v in kinds])
+    F, N, cap = (C.c_uint32 * m)(*num_fields), (C.c_uint32 * m)(*num_candidates), (C.c_uint32 * m)(*max_dets)
+    if level_shapes is None:
+        nl = lh = lw = lfirst = None
+        counts = [0] * n
+    else:
+        counts = [len(q) for q in level_shapes]
+        flat = [hw for q in level_shapes for hw in q]
+        k = max(len(flat), 1)
+        nl = (C.c_int * m)(*counts)
+        lh, lw, lfirst = (C.c_uint32 * k)(*[q[0] for q in flat]), (C.c_uint32 * k)(*[q[1] for q in flat]), (C.c_uint32 * k)()
+    cand, first, blocks = (C.c_uint32 * m)(), (C.c_uint32 * m)(), (C.c_uint32 * m)()
+    key, box, det, totals = (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * 8)()
+    rc = L.mi355_selftest_yolox_head_set_plan(n, kind, F, N, cap, nl, lh, lw, cand, first, blocks, key, box, det, lfirst, totals)
+    per_job, at = [], 0
+    for c in counts:
+        per_job.append([] if lfirst is None else list(lfirst[at: at + c]))
+        at += c
+    return rc, list(cand)[:n], list(first)[:n], list(blocks)[:n], list(key)[:n], list(box)[:n], list(det)[:n], per_job, list(totals)
 
 
 class AudioGroup:

@@ -1082,7 +1082,7 @@ int mi355_selftest_handdec_check(int decoder, size_t tensor_pitch_bytes, int n_t
  * all launch, synchronisation and copy latency. submit_yolodec queues one device tensor of stream `ctx` and whatever is
  * pending goes out as at most THREE launches over job tables in the kernel arguments, on the queue's own HIP stream, with ONE
  * download of all counts and records. Members are fully independent: each tensor has its own shape (F, N), layout, three settings
- * and output capacity. After wait_yolodec, dets and *n_dets hold exactly what mi355_yolodec_tensors_device(ctx, d_tensor,
+ * and output capacity (raw yoloxinference head maps are members too: submit_yolox_head below). After wait_yolodec, dets and *n_dets hold exactly what mi355_yolodec_tensors_device(ctx, d_tensor,
  * F * N * 4, 1, layout, F, N, p, dets, max_dets, n_dets) would have returned, byte for byte: the tie rule (ascending candidate
  * index) makes the result independent of the order in which survivors were appended.
  *   submit : never blocks; the checks and status codes are those of mi355_yolodec_tensors_device with n_tensors = 1 and a pitch of
@@ -1097,7 +1097,7 @@ int mi355_selftest_handdec_check(int decoder, size_t tensor_pitch_bytes, int n_t
  *           a null n_dets or a null dets otherwise: MI355_ERR_INVALID_ARG, the result stays collectable). A result is collected
  *           once. Tickets are one sequence per group: a ticket that is unknown, already collected or another queue's is
  *           MI355_ERR_INVALID_ARG here and stays collectable where it belongs; mi355_group_wait, _order_after, _wait_compare,
- *           _wait_colordetect, _wait_hsvdetect and _wait_handdec refuse a decoder ticket likewise.
+ *           _wait_colordetect, _wait_hsvdetect and _wait_handdec refuse a decoder ticket - a tensor's or a head's - likewise.
  *   set_yolodec_rendezvous : as set_hsvdetect_rendezvous, counted over pending tensors only. The other queues' rendezvous, streams
  *           and stats and this queue's do not touch each other.
  *   At most MI355_YOLODEC_SET_MAX tensors share a launch set; more go out as consecutive sets. Per set: the V8 score launch if a V8
@@ -1126,6 +1126,49 @@ int mi355_group_yolodec_stats(mi355_group *group, uint64_t stats[4]);
 int mi355_selftest_yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates,
                                     const uint32_t *max_dets, uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset,
                                     uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]);
+
+/* yoloxinference's raw head maps as members of the decoder queue. A process with N `yoloxinference ! yoloxtensordec`
+ * pipelines makes N lone mi355_yolox_head_dets_device calls per frame period; submit_yolox_head queues the head maps of ONE tensor of
+ * stream `ctx` instead. A head is one more kind of member of the queue above, not a queue of its own: its ticket comes from the same
+ * sequence and is collected with mi355_group_wait_yolodec into the same records; set_yolodec_rendezvous counts pending heads and
+ * tensors together; MI355_YOLODEC_SET_MAX caps heads plus tensors per set; yolodec_stats counts a head as a tensor (its kernel
+ * launches among the set's); flush, wait_all, destroy and the failure reporting cover it as they cover a tensor; the other queues'
+ * wait functions refuse its ticket as they refuse a tensor's. After wait_yolodec, dets and *n_dets hold exactly what
+ * mi355_yolox_head_dets_device(ctx, levels, n_levels, 1, C, p, dets, max_dets, n_dets) would have returned, byte for byte.
+ *   submit : never blocks. Refused with the status of mi355_yolox_head_dets_device for one tensor: the shape checks of
+ *           mi355_selftest_yolox_head_check(levels, n_levels, 1, C, ...) and its null or misaligned maps; the pitches are ignored
+ *           (one tensor), there is no output pitch. A null group, ctx, p or ticket: MI355_ERR_INVALID_ARG. A refused submit queues
+ *           nothing. The level structs and the settings are copied at submit. The maps are read after what ctx's HIP stream held at
+ *           the call (the event of submit_yolodec) and until wait_yolodec for the ticket has returned; the three maps of a level may
+ *           lie in one allocation. The queue keeps room for min(max_dets, A) records.
+ *   Per set that holds a head: the tables of its heads and their levels (one level job per level of a head: the three planes, w,
+ *   h w, first candidate, first tile, stride, head) are built in the set's pinned block, behind its results, and go to the device in
+ *   ONE host-to-device copy; then TWO launches more than the set's tensors cost - the head score launch, one flat grid over the level
+ *   jobs' tiles of 256 candidates of one level each, and the head NMS launch, one block per head - and the set's one download. A set
+ *   of heads alone: one upload, two launches, one download. A set without a head uploads nothing and launches what it did before.
+ *   yolox_head_stats : {heads launched, launch sets that held a head, level-table uploads, head kernel launches}.
+ *   mi355_selftest_yolox_head_set_plan : host only, no device: the layout of one set that may hold heads, which the queue itself
+ *           uses. kind[j]: MI355_YOLO_V8, MI355_YOLO_X or MI355_YOLO_X_HEAD (valid only here). A tensor job gets exactly what
+ *           mi355_selftest_yolodec_set_plan gives it. A head job has num_fields = 5 + C, ignores num_candidates[j] and reads
+ *           n_levels[j] and that many entries of level_h / level_w (the head jobs' levels one after the other; n_levels of a tensor
+ *           job is not read): candidates[j] = A = the sum of h w (a tensor job's N), blocks[j] = the sum of ceil(h w / 256),
+ *           first_block[j] = the running sum of blocks over the earlier head jobs, level_first_block (indexed as level_h) = the
+ *           running sum of ceil(h w / 256) within the job. key_offset, box_offset and det_offset follow the old rules with N = A,
+ *           over all jobs in submit order. totals = the old six (a head counts among the jobs with N > 0), head blocks, level jobs.
+ *           Refused (MI355_ERR_INVALID_ARG): n_jobs outside 0..MI355_YOLODEC_SET_MAX, null arrays with n_jobs > 0 (the four level
+ *           arrays only with a head job), null totals; a tensor job as in the old plan; a head job returns the status
+ *           mi355_selftest_yolox_head_check gives its shape. */
+#define MI355_YOLO_X_HEAD 2 /* a member kind of the queue's plan; no mi355_yolo_layout of the lone entry points or of submit_yolodec */
+int mi355_group_submit_yolox_head(mi355_group *group, mi355_ctx *ctx, const mi355_yolox_level *levels, int n_levels,
+                                  uint32_t num_classes, const mi355_yolo_params *p, uint32_t max_dets, uint64_t *ticket);
+/* {heads launched, launch sets that held a head, level-table uploads, head kernel launches} */
+int mi355_group_yolox_head_stats(mi355_group *group, uint64_t stats[4]);
+/* host only, no device: the layout of one launch set that may hold heads */
+int mi355_selftest_yolox_head_set_plan(int n_jobs, const int *kind, const uint32_t *num_fields, const uint32_t *num_candidates,
+                                       const uint32_t *max_dets, const int *n_levels, const uint32_t *level_h,
+                                       const uint32_t *level_w, uint32_t *candidates, uint32_t *first_block, uint32_t *blocks,
+                                       uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset,
+                                       uint32_t *level_first_block, uint64_t totals[8]);
 
 /* The hand decoders across independent element instances. The reference elements receive one tensor per buffer per instance
  * (analytics/analytics/src/hand/handdetectiontensordec/imp.rs, hand/handlandmarktensordec/imp.rs: transform_ip); a process with N

@@ -19,20 +19,23 @@
 //   * results are the two element launches', bit for bit (same arithmetic, same table);
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
-// Five more queues live beside the filter batches, each with its own HIP stream, pending list, rendezvous and stats, and none
-// touching another: videocompare pairs (submit_compare: its own code - classes, lanes, collection per lane) and four SET QUEUES,
-// which are one protocol written once (SetQueue<Kind>: submit's tail, flush in sets of up to 32 in submission order, the
-// lingering wait, collect-once results, retire, stats, destroy) with four kinds: colordetect frames (submit_colordetect),
-// hsvdetector frames (submit_hsvdetect: frames of independent instances - own size, strides, formats, settings - as at most two
+// Five more queues live beside the filter batches, each with its own HIP stream(s), pending list, rendezvous and stats, and none
+// touching another. They are SET QUEUES: one protocol written once (SetQueue<Kind>: submit's tail, flush in sets of up to 32 of
+// one class in submission order, each set dealt out to the kind's lanes, the lingering wait, collect-once results per lane,
+// retire, stats, destroy) with five kinds: videocompare pairs (submit_compare: the one kind with classes - algorithm, geometry,
+// format, Dssim form - and lanes: a set's pairs, sorted by reference frame, go out as contiguous shares on up to 16 streams),
+// colordetect frames (submit_colordetect), hsvdetector frames (submit_hsvdetect: frames of independent instances - own size, strides, formats, settings - as at most two
 // launches over a job table, hsv_kernels.hip), decoder tensors (submit_yolodec: tensors of independent yolov8tensordec2 /
 // yoloxtensordec instances - own shape, layout, settings - as at most three launches over job tables and one download,
 // yolodec.hip; submit_yolox_head: the raw head maps of independent yoloxinference instances are members of the SAME queue - a
 // YdTensor of the kind MI355_YOLO_X_HEAD with the submit's copy of its levels - and cost a set one upload of their level tables
 // and two launches more, yolox_head.hip) and hand tensors (submit_handdec_palm / _landmarks: tensors of independent handdetectiontensordec /
 // handlandmarktensordec instances - own shape and settings - as at most two launches over job tables, no upload and one download,
-// handdec.hip). A fifth kind is a struct beside CdKind / HdKind / YdKind / HnKind - payload, result, kSetMax, its names, ensure,
-// plan, its pinned block (if any), launch, result, failed, destroy - a SetQueue<Kind> member of mi355_group, a line in
-// for_each_set_queue and its entry points; nothing of the protocol is written again.
+// handdec.hip). A further kind is a struct beside CmpKind / CdKind / HdKind / YdKind / HnKind - payload, result, kSetMax, its
+// names, ensure, plan, the size of its pinned block (if any), launch, result, failed, destroy; OneLane, or its own same_class /
+// split / lanes - a SetQueue<Kind> member of mi355_group, a line in for_each_set_queue (the detector queues: what wait_all and the
+// foreign-ticket refusal reach) and its entry points; nothing of the protocol is written again. The filter batches alone are
+// their own code: one frame per stream and batch, the non-batchable path and order_after are not this protocol.
 // The group has ONE mutex, ticket sequence, event free list and last_error (GroupCore); every queue uses those. Tickets are one
 // sequence; a wait entry refuses a ticket of another queue.
 // No persistent kernel: nothing here can hang the GPU waiting for the host, a launch is a launch.
@@ -74,29 +77,6 @@ struct Batch {
   int waiters;  // threads inside hipEventSynchronize(done) right now: the event is not recycled under them
   std::shared_ptr<void> table_ref;  // the table its launches read (see Desc)
 };
-
-// ---- videocompare across independent element instances (mi355_group_submit_compare): one (reference frame, frame) pair per submit
-struct CmpDesc {
-  mi355_ctx *ctx;
-  const uint8_t *ref, *frame;
-  int width, height, stride, format, algo, translucent, fast;   // fast: MI355_FLAG_DSSIM_FAST of the submitting context
-  uint64_t ticket;
-  hipEvent_t ready;  // recorded on ctx->stream at submit (nullptr: the stream held nothing)
-};
-struct CmpResult { int status; double distance; uint64_t hashes[2]; };
-struct CmpBatch {
-  uint64_t seq;
-  std::vector<uint64_t> tickets;
-  int algo, width, height;
-  int lane;        // which of the compare queue's streams carries it (batches of one lane finish in seq order)
-  hipEvent_t done;
-  int waiters;
-  void *h_block;  // pinned: Dssim [n][15] doubles / Blockhash [2 n] u64 (reference hashes, then frame hashes)
-  bool collected = false;  // its values are in cmp_results (the event and the block are recycled once nobody waits inside it)
-};
-constexpr int kCmpMaxBatch = 32;                      // pairs per launch set (a Dssim pair keeps 44 MB of maps until its batch is reduced)
-constexpr int kCmpMaxLanes = 16;                      // HIP streams the pairs of one launch set are dealt out to
-constexpr size_t kCmpBlockBytes = 64 * 15 * 8 + 1024; // one pinned result block
 
 // ---- what every queue of a group shares: ONE lock, ticket sequence, event free list and last_error
 struct GroupCore {
@@ -157,15 +137,79 @@ Waited wait_seq_unlocking(std::deque<S> &sets, uint64_t seq, std::unique_lock<st
   return Waited::kDone;
 }
 
-// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its four kinds
+// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its five kinds
 // A kind is what differs between the queues: what is submitted (Payload), what a wait takes (Result), what a launch reads (Plan),
-// what a set in flight owns (SetData), how a set is launched and read back, and the resources of first use. The protocol is below.
+// what a set in flight owns (SetData: its pinned `block` and what `result` needs besides), how a set is launched and read back, how
+// large its block has to be, the resources of first use - and which pending items may share a launch set (same_class) and how
+// what was taken is dealt out to the kind's streams (split: parts, each with a lane). The protocol is below.
 
 template <class Payload>
 struct QItem {
   Payload p;
   uint64_t ticket;
   hipEvent_t ready;  // recorded on the submitting context's stream (nullptr: the stream held nothing, or nothing will be read)
+};
+
+// items [begin, end) of what a flush took, as one launch on the stream of `lane`
+struct Part { int lane; size_t begin, end; };
+
+// A pinned result block, and a kind's free list of them. Sets' results may differ in size by orders of magnitude (the decoder's:
+// min(max_dets, N) records per tensor), so blocks are sized: `take` hands out a free one that is large enough, else a new one -
+// and a free one that is too small makes room, or the pool would keep every size it saw. Where every request has one size (the
+// other kinds) that is pop-or-allocate: a launch set allocates only when more sets are in flight than ever before.
+struct PinnedBlock { void *h = nullptr; size_t bytes = 0; };
+struct BlockPool {
+  std::vector<PinnedBlock> free;
+  static bool alloc(size_t bytes, PinnedBlock *b) {
+    const size_t want = (bytes + 4095) / 4096 * 4096;
+    if (hipHostMalloc(&b->h, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *b = PinnedBlock{}; return false; }
+    b->bytes = want;
+    return true;
+  }
+  bool take(size_t bytes, PinnedBlock *b) {
+    for (size_t i = 0; i < free.size(); i++)
+      if (free[i].bytes >= bytes) {
+        *b = free[i];
+        free.erase(free.begin() + (std::ptrdiff_t)i);
+        return true;
+      }
+    if (!free.empty()) {
+      (void)hipHostFree(free.back().h);
+      free.pop_back();
+    }
+    return alloc(bytes, b);
+  }
+  void give(PinnedBlock *b) {
+    if (b->h) free.push_back(*b);
+    *b = PinnedBlock{};
+  }
+  // the blocks of first use: the sets a stream of submits has in flight before anybody collects
+  bool prefill(size_t n, size_t bytes) {
+    while (free.size() < n) {
+      PinnedBlock b;
+      if (!alloc(bytes, &b)) return false;
+      free.push_back(b);
+    }
+    return true;
+  }
+  void destroy() {
+    for (PinnedBlock &b : free) (void)hipHostFree(b.h);
+    free.clear();
+  }
+};
+
+// What the kinds with ONE stream share: everything pending is one class, and what a flush took is one part on lane 0.
+template <class Payload>
+struct OneLane {
+  static constexpr int kLanesMax = 1;
+  hipStream_t stream = nullptr;
+  int lanes() const { return 1; }
+  hipStream_t lane_stream(int) const { return stream; }
+  static bool same_class(const Payload &, const Payload &) { return true; }
+  int split(std::vector<QItem<Payload>> &all, Part *parts) const {
+    parts[0] = Part{0, 0, all.size()};
+    return 1;
+  }
 };
 
 int queue_stream(GroupCore *g, hipStream_t *stream, const char *name) {
@@ -188,34 +232,24 @@ int device_cus(int device) {
 // palette comes back through the set's pinned block. Consecutive sets on the queue's stream share the device scratch.
 struct CdOut { int status, n_colors; uint8_t rgb[255 * 3]; };
 constexpr int kCdBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
-struct CdKind {
+struct CdKind : OneLane<CdFrame> {
   using Payload = CdFrame;
   using Result = CdOut;
   struct Plan { CdFrame frames[kCdSetMax]; };
-  struct SetData { void *h_block = nullptr; };  // pinned: the set's results (colordetect_set_result) until it is collected
+  struct SetData { PinnedBlock block; };  // the set's results (colordetect_set_result) until it is collected
   static constexpr int kSetMax = kCdSetMax;
   static constexpr const char *kName = "colordetect", *kItem = "colordetect frame", *kWaitEntry = "mi355_group_wait_colordetect";
-  hipStream_t stream = nullptr;
   CdSetScratch *scratch = nullptr;
   int n_cu = 256;
-  std::vector<void *> blocks;  // free pinned result blocks, all of colordetect_set_block_bytes()
+  BlockPool blocks;  // all of colordetect_set_block_bytes()
 
   bool set_up() const { return scratch != nullptr; }
-  // stream, device scratch and the first pinned blocks: at the first submit, never inside a launch set. The blocks have one size,
-  // so four are made here - the sets a stream of submits has in flight before anybody collects - and a launch set allocates only
-  // when more sets are in flight than ever before.
+  // stream, device scratch and the first pinned blocks: at the first submit, never inside a launch set
   int ensure(GroupCore *g) {
     if (scratch) return MI355_OK;
     n_cu = device_cus(g->device);
     if (int rc = queue_stream(g, &stream, kName)) return rc;
-    while ((int)blocks.size() < kCdBlocksAtFirstUse) {
-      void *b = nullptr;
-      if (hipHostMalloc(&b, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the colordetect queue");
-      }
-      blocks.push_back(b);
-    }
+    if (!blocks.prefill(kCdBlocksAtFirstUse, colordetect_set_block_bytes())) return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the colordetect queue");
     int st = MI355_OK;
     std::string err;
     scratch = colordetect_set_scratch_new(stream, &st, &err);
@@ -225,46 +259,35 @@ struct CdKind {
     for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
     return MI355_OK;
   }
-  bool no_free_block(const Plan &) const { return blocks.empty(); }
-  bool take_block(const Plan &, SetData *d) {
-    if (!blocks.empty()) { d->h_block = blocks.back(); blocks.pop_back(); }
-    // (more sets in flight than ever before: one more block, kept from then on)
-    else if (hipHostMalloc(&d->h_block, colordetect_set_block_bytes(), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); d->h_block = nullptr; }
-    return d->h_block != nullptr;
-  }
-  static bool holds_block(const SetData &d) { return d.h_block != nullptr; }
-  void release(SetData *d) {
-    if (d->h_block) blocks.push_back(d->h_block);
-    d->h_block = nullptr;
-  }
-  int launch(const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
-    return colordetect_launch_set(scratch, stream, n_cu, p.frames, (int)n, d->h_block, launches, err);
+  size_t block_bytes(const Plan &) const { return colordetect_set_block_bytes(); }
+  int launch(int, const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
+    return colordetect_launch_set(scratch, stream, n_cu, p.frames, (int)n, d->block.h, launches, err);
   }
   void launched(const GroupCore *, const Plan &, size_t) const {}
   void result(const SetData &d, size_t i, CdOut *o) const {
     o->status = MI355_OK;
-    colordetect_set_result(d.h_block, (int)i, o->rgb, &o->n_colors);
+    colordetect_set_result(d.block.h, (int)i, o->rgb, &o->n_colors);
   }
   static void failed(const CdFrame &, int rc, CdOut *o) { o->status = rc; o->n_colors = 0; }
   static int status(const CdOut &o) { return o.status; }
   void destroy() {
     colordetect_set_scratch_free(scratch);
     (void)hipStreamDestroy(stream);
-    for (void *b : blocks) (void)hipHostFree(b);
+    blocks.destroy();
   }
 };
 
 // ---- hsvdetector across independent element instances (mi355_group_submit_hsvdetect): one device frame per submit, written in
 // place on the device - nothing comes back but the launch's status, so a set owns NO pinned block and the queue no scratch.
-struct HdKind {
+struct HdKind : OneLane<HdFrame> {
   using Payload = HdFrame;
   using Result = int;  // the status
   struct Plan { HdFrame frames[kHdSetMax]; };
-  struct SetData {};
+  struct SetData { PinnedBlock block; };  // (never taken: block_bytes is 0)
   static constexpr int kSetMax = kHdSetMax;
   static constexpr const char *kName = "hsvdetector", *kItem = "hsvdetector frame", *kWaitEntry = "mi355_group_wait_hsvdetect";
-  hipStream_t stream = nullptr;
   int n_cu = 256;
+  BlockPool blocks;  // (stays empty)
 
   bool set_up() const { return stream != nullptr; }
   // the queue's stream is all it has, so first use is keyed on it: at the first submit, never inside a launch set
@@ -277,11 +300,8 @@ struct HdKind {
     for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
     return MI355_OK;
   }
-  bool no_free_block(const Plan &) const { return false; }
-  bool take_block(const Plan &, SetData *) const { return true; }
-  static bool holds_block(const SetData &) { return false; }
-  void release(SetData *) const {}
-  int launch(const Plan &p, size_t n, SetData *, int *launches, std::string *err) { return hsvdetect_launch_set(stream, n_cu, p.frames, (int)n, launches, err); }
+  size_t block_bytes(const Plan &) const { return 0; }
+  int launch(int, const Plan &p, size_t n, SetData *, int *launches, std::string *err) { return hsvdetect_launch_set(stream, n_cu, p.frames, (int)n, launches, err); }
   // what the element behind finds on-die, as the lone entry records it: every destination with a pixel, once the set has gone out
   void launched(const GroupCore *g, const Plan &p, size_t n) const {
     for (size_t i = 0; i < n; i++) {
@@ -298,22 +318,20 @@ struct HdKind {
 // ---- yolov8tensordec2 / yoloxtensordec across independent element instances (mi355_group_submit_yolodec): one device tensor per
 // submit; its kept count and records come back through the set's pinned block. Consecutive sets share the device scratch.
 struct YdOut { int status; uint32_t n_dets, max_dets; std::vector<mi355_yolo_det> dets; };   // dets: the first min(n_dets, max_dets)
-struct YdBlock { void *h; size_t bytes; };   // a pinned result block
 struct YdSlot { uint32_t num_candidates, max_dets; uint64_t det_offset; };
-struct YdKind {
+struct YdKind : OneLane<YdTensor> {
   using Payload = YdTensor;
   using Result = YdOut;
   struct Plan { YdTensor tensors[kYdSetMax]; uint64_t det_off[kYdSetMax], totals[8]; };
   struct SetData {
     // the set's own results until it is collected, and behind them the tables of its heads (h == nullptr: no member had a candidate)
-    YdBlock block{nullptr, 0};
+    PinnedBlock block;
     std::vector<YdSlot> slots;   // its tensors, by job (as the set's tickets are)
   };
   static constexpr int kSetMax = kYdSetMax;
   static constexpr const char *kName = "decoder", *kItem = "decoder tensor", *kWaitEntry = "mi355_group_wait_yolodec";
-  hipStream_t stream = nullptr;
   YdSetScratch *scratch = nullptr;
-  std::vector<YdBlock> blocks;  // free pinned result blocks
+  BlockPool blocks;  // sized by the sets' results
   // the heads among the members (mi355_group_yolox_head_stats): heads launched, sets that held one, table uploads, head kernel launches
   uint64_t n_heads = 0, n_head_sets = 0, n_head_uploads = 0, n_head_launches = 0;
   int last_head_counts[3] = {0, 0, 0};   // of the set `launch` has just sent out; counted by `launched`, i.e. once the set stands
@@ -349,33 +367,8 @@ struct YdKind {
     return rc;
   }
   // a set without a candidate has nothing to copy: it takes no block (and still gets its event and its set)
-  bool no_free_block(const Plan &p) const { return p.totals[2] && blocks.empty(); }
-  // The sets' results differ in size by orders of magnitude (min(max_dets, N) records per tensor), so blocks are sized: a free one
-  // that is large enough, else a new one - and a free one that is too small makes room, or the pool would keep every size it saw.
-  bool take_block(const Plan &p, SetData *d) {
-    if (!p.totals[2]) return true;
-    const size_t bytes = yolodec_set_block_bytes(p.totals[5], p.totals[7]);
-    for (size_t i = 0; i < blocks.size(); i++)
-      if (blocks[i].bytes >= bytes) {
-        d->block = blocks[i];
-        blocks.erase(blocks.begin() + (std::ptrdiff_t)i);
-        return true;
-      }
-    if (!blocks.empty()) {
-      (void)hipHostFree(blocks.back().h);
-      blocks.pop_back();
-    }
-    const size_t want = (bytes + 4095) / 4096 * 4096;
-    if (hipHostMalloc(&d->block.h, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); d->block.h = nullptr; return false; }
-    d->block.bytes = want;
-    return true;
-  }
-  static bool holds_block(const SetData &d) { return d.block.h != nullptr; }
-  void release(SetData *d) {
-    if (d->block.h) blocks.push_back(d->block);
-    d->block = YdBlock{nullptr, 0};
-  }
-  int launch(const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
+  size_t block_bytes(const Plan &p) const { return p.totals[2] ? yolodec_set_block_bytes(p.totals[5], p.totals[7]) : 0; }
+  int launch(int, const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
     for (size_t i = 0; i < n; i++) d->slots.push_back(YdSlot{p.tensors[i].num_candidates, p.tensors[i].max_dets, p.det_off[i]});
     return yolodec_launch_set(scratch, stream, p.tensors, (int)n, d->block.h, d->block.bytes, launches, last_head_counts, err);
   }
@@ -402,7 +395,7 @@ struct YdKind {
   void destroy() {
     yolodec_set_scratch_free(scratch);
     (void)hipStreamDestroy(stream);
-    for (YdBlock &b : blocks) (void)hipHostFree(b.h);
+    blocks.destroy();
   }
 };
 
@@ -412,33 +405,25 @@ struct YdKind {
 struct HnOut { int status, decoder; uint32_t n_hands; std::vector<mi355_hand_det> dets; std::vector<mi355_hand_keypoints> kps; };   // the first n_hands
 struct HnSlot { int decoder; uint32_t rows, kp_slot; };
 constexpr int kHnBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
-struct HnKind {
+struct HnKind : OneLane<HnTensor> {
   using Payload = HnTensor;
   using Result = HnOut;
   struct Plan { HnTensor tensors[kHnSetMax]; uint32_t kp_slot[kHnSetMax]; uint64_t totals[4]; };
   struct SetData {
-    void *h_block = nullptr;     // pinned: the set's own results until it is collected (nullptr: no tensor had rows)
+    PinnedBlock block;           // the set's own results until it is collected (h == nullptr: no tensor had rows)
     std::vector<HnSlot> slots;   // its tensors, by job (as the set's tickets are)
   };
   static constexpr int kSetMax = kHnSetMax;
   static constexpr const char *kName = "hand decoder", *kItem = "hand tensor", *kWaitEntry = "mi355_group_wait_handdec";
-  hipStream_t stream = nullptr;
   HnSetScratch *scratch = nullptr;
-  std::vector<void *> blocks;  // free pinned result blocks, all of handdec_set_block_bytes()
+  BlockPool blocks;  // all of handdec_set_block_bytes()
 
   bool set_up() const { return scratch != nullptr; }
   // stream, device slab and the first pinned blocks: at the first submit, never inside a launch set
   int ensure(GroupCore *g) {
     if (scratch) return MI355_OK;
     if (int rc = queue_stream(g, &stream, kName)) return rc;
-    while ((int)blocks.size() < kHnBlocksAtFirstUse) {
-      void *b = nullptr;
-      if (hipHostMalloc(&b, handdec_set_block_bytes(), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the hand decoder queue");
-      }
-      blocks.push_back(b);
-    }
+    if (!blocks.prefill(kHnBlocksAtFirstUse, handdec_set_block_bytes())) return fail(g, MI355_ERR_OUT_OF_MEMORY, "group: no pinned result blocks for the hand decoder queue");
     int st = MI355_OK;
     std::string err;
     scratch = handdec_set_scratch_new(&st, &err);
@@ -457,22 +442,10 @@ struct HnKind {
     return rc;
   }
   // a set without a row has nothing to copy: it takes no block (and still gets its event and its set)
-  bool no_free_block(const Plan &p) const { return p.totals[3] && blocks.empty(); }
-  bool take_block(const Plan &p, SetData *d) {
-    if (!p.totals[3]) return true;
-    if (!blocks.empty()) { d->h_block = blocks.back(); blocks.pop_back(); }
-    // (more sets in flight than ever before: one more block, kept from then on)
-    else if (hipHostMalloc(&d->h_block, handdec_set_block_bytes(), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); d->h_block = nullptr; }
-    return d->h_block != nullptr;
-  }
-  static bool holds_block(const SetData &d) { return d.h_block != nullptr; }
-  void release(SetData *d) {
-    if (d->h_block) blocks.push_back(d->h_block);
-    d->h_block = nullptr;
-  }
-  int launch(const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
+  size_t block_bytes(const Plan &p) const { return p.totals[3] ? handdec_set_block_bytes() : 0; }
+  int launch(int, const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
     for (size_t i = 0; i < n; i++) d->slots.push_back(HnSlot{p.tensors[i].decoder, p.tensors[i].rows, p.kp_slot[i]});
-    return handdec_launch_set(scratch, stream, p.tensors, (int)n, d->h_block, d->h_block ? handdec_set_block_bytes() : 0, launches, err);
+    return handdec_launch_set(scratch, stream, p.tensors, (int)n, d->block.h, d->block.h ? handdec_set_block_bytes() : 0, launches, err);
   }
   void launched(const GroupCore *, const Plan &, size_t) const {}
   // count and records MOVE out of the pinned block: the block is free for a later set once this one is collected
@@ -482,7 +455,7 @@ struct HnKind {
     mi355_hand_keypoints kps[MI355_HAND_MAX];
     o->status = MI355_OK;
     o->decoder = sl.decoder;
-    handdec_set_result(d.h_block, (int)d.slots.size(), (int)i, sl.decoder, sl.rows, sl.kp_slot, dets, kps, &o->n_hands);
+    handdec_set_result(d.block.h, (int)d.slots.size(), (int)i, sl.decoder, sl.rows, sl.kp_slot, dets, kps, &o->n_hands);
     o->dets.assign(dets, dets + o->n_hands);
     if (sl.decoder == 1) o->kps.assign(kps, kps + o->n_hands);
   }
@@ -491,7 +464,129 @@ struct HnKind {
   void destroy() {
     handdec_set_scratch_free(scratch);
     (void)hipStreamDestroy(stream);
-    for (void *b : blocks) (void)hipHostFree(b);
+    blocks.destroy();
+  }
+};
+
+// ---- videocompare across independent element instances (mi355_group_submit_compare): one (reference frame, frame) pair per
+// submit; its distance (and Blockhash's two hashes) come back through the part's pinned block. The one kind with classes and lanes:
+// a launch set holds pairs of one class, and its pairs are dealt out to `n_lanes` contexts (streams) - the Dssim kernels are
+// VALU-bound at ~80 % busy when one runs alone, and a second stream's launches fill its tails and launch boundaries (32 4K pairs:
+// 1.48 k comparisons/s on one stream, 1.84 k over eight); what the dispatcher removes is the per-comparison host round trip, not
+// the overlap.
+struct CmpPair {
+  const uint8_t *ref, *frame;
+  int width, height, stride, format, algo, translucent, fast;   // translucent, fast: the submitting context's Dssim settings
+};
+struct CmpResult { int status; double distance; uint64_t hashes[2]; };
+constexpr int kCmpMaxBatch = 32;                      // pairs per launch set (a Dssim pair keeps 44 MB of maps until its batch is reduced)
+constexpr int kCmpMaxLanes = 16;                      // HIP streams the pairs of one launch set are dealt out to
+constexpr size_t kCmpBlockBytes = 64 * 15 * 8 + 1024; // one pinned result block
+struct CmpKind {
+  using Payload = CmpPair;
+  using Result = CmpResult;
+  struct Plan { CmpPair first; const uint8_t *refs[kCmpMaxBatch], *frames[kCmpMaxBatch]; };
+  struct SetData {
+    PinnedBlock block;           // Dssim [n][15] doubles / Blockhash [2 n] u64 (reference hashes, then frame hashes)
+    int algo = 0, width = 0, height = 0, n = 0;
+    std::vector<double> scores;  // Dssim: the part's n distances, reduced from the block when its first result is taken
+  };
+  static constexpr int kSetMax = kCmpMaxBatch, kLanesMax = kCmpMaxLanes;
+  static constexpr const char *kName = "compare", *kItem = "pair";   // (no kWaitEntry: no other entry refuses a pair's ticket by name)
+  mi355_ctx *alane[kCmpMaxLanes] = {nullptr};        // a context (stream, Dssim scratch) per lane
+  int n_lanes = 8;
+  uint32_t *d_hash_sums[kCmpMaxLanes] = {nullptr};   // Blockhash scratch per lane: [2 kCmpMaxBatch][64] u32 + [2 kCmpMaxBatch] u64
+  BlockPool blocks;  // all of kCmpBlockBytes
+
+  bool set_up() const { return alane[0] != nullptr; }
+  int lanes() const { return n_lanes; }
+  hipStream_t lane_stream(int lane) const { return alane[lane] ? alane[lane]->stream : nullptr; }
+  // the lane contexts and their Blockhash scratch: at the first submit, all of them or none
+  int ensure(GroupCore *g) {
+    if (set_up()) return MI355_OK;
+    int st = MI355_OK;
+    for (int l = 0; l < n_lanes && !st; l++) {
+      alane[l] = mi355_ctx_create(g->device, &st);
+      if (!alane[l] && !st) st = MI355_ERR_HIP;
+      if (!st && hipMalloc((void **)&d_hash_sums[l], (size_t)2 * kCmpMaxBatch * (64 * 4 + 8)) != hipSuccess) { (void)hipGetLastError(); st = MI355_ERR_OUT_OF_MEMORY; }
+    }
+    if (!st) return MI355_OK;
+    free_lanes();
+    return fail(g, st, "group: no contexts for the compare queue");
+  }
+  void free_lanes() {
+    for (int l = 0; l < kCmpMaxLanes; l++) {
+      if (d_hash_sums[l]) (void)hipFree(d_hash_sums[l]);
+      if (alane[l]) mi355_ctx_destroy(alane[l]);
+      d_hash_sums[l] = nullptr; alane[l] = nullptr;
+    }
+  }
+  static bool same_class(const CmpPair &a, const CmpPair &b) {
+    return a.algo == b.algo && a.width == b.width && a.height == b.height && a.stride == b.stride && a.format == b.format && a.translucent == b.translucent && a.fast == b.fast;
+  }
+  // pairs that share a reference frame next to each other (videocompare with several pads: the reference is hashed once), then
+  // contiguous shares for the lanes
+  int split(std::vector<QItem<CmpPair>> &all, Part *parts) const {
+    std::stable_sort(all.begin(), all.end(), [](const QItem<CmpPair> &a, const QItem<CmpPair> &b) { return (uintptr_t)a.p.ref < (uintptr_t)b.p.ref; });
+    const int total = (int)all.size();
+    const int shares = total < n_lanes ? total : n_lanes;
+    int n_parts = 0, begin = 0;
+    for (int lane = 0; lane < shares; lane++) {
+      int end = (int)((long long)total * (lane + 1) / shares);
+      // a reference frame is not split over two lanes
+      while (end < total && end > begin && all[end].p.ref == all[end - 1].p.ref) end++;
+      if (end <= begin) continue;
+      parts[n_parts++] = Part{lane, (size_t)begin, (size_t)end};
+      begin = end;
+    }
+    return n_parts;
+  }
+  int plan(const QItem<CmpPair> *take, size_t n, Plan *p, std::string *) const {
+    p->first = take[0].p;   // a part holds pairs of one class only (same_class)
+    for (size_t i = 0; i < n; i++) { p->refs[i] = take[i].p.ref; p->frames[i] = take[i].p.frame; }
+    return MI355_OK;
+  }
+  size_t block_bytes(const Plan &) const { return kCmpBlockBytes; }
+  int launch(int lane, const Plan &p, size_t n, SetData *d, int *, std::string *err) {
+    const CmpPair &c = p.first;
+    mi355_ctx *a = alane[lane];
+    PixFmt fmt;
+    (void)pixfmt_of(c.format, &fmt);
+    d->algo = c.algo; d->width = c.width; d->height = c.height; d->n = (int)n;
+    int rc = MI355_OK;
+    if (c.algo == MI355_HASH_DSSIM) {
+      a->dssim_translucent = c.translucent;
+      a->dssim_fast = c.fast;
+      rc = dssim_compare_pairs_enqueue(a, p.refs, p.frames, (int)n, c.stride, c.width, c.height, fmt.pixel_stride, (double *)d->block.h);
+    } else {
+      const uint8_t *both[2 * kCmpMaxBatch];
+      std::copy(p.refs, p.refs + n, both);
+      std::copy(p.frames, p.frames + n, both + n);
+      unsigned long long *d_hashes = (unsigned long long *)(d_hash_sums[lane] + (size_t)2 * kCmpMaxBatch * 64);
+      rc = blockhash_enqueue(a, both, 2 * (int)n, c.stride, c.width, c.height, fmt.pixel_stride, d_hash_sums[lane], d_hashes);
+      if (!rc && hipMemcpyAsync(d->block.h, d_hashes, (size_t)2 * n * 8, hipMemcpyDeviceToHost, a->stream) != hipSuccess) rc = MI355_ERR_HIP;
+    }
+    if (rc) *err = a->last_error;
+    return rc;
+  }
+  void launched(const GroupCore *, const Plan &, size_t) const {}
+  void result(SetData &d, size_t i, CmpResult *o) const {
+    if (d.algo == MI355_HASH_DSSIM) {
+      if (d.scores.empty()) {
+        d.scores.resize((size_t)d.n);
+        dssim_scores_from_slots(d.width, d.height, (const double *)d.block.h, d.n, d.scores.data());
+      }
+      *o = CmpResult{MI355_OK, d.scores[i], {0, 0}};
+    } else {
+      const uint64_t *h = (const uint64_t *)d.block.h;
+      *o = CmpResult{MI355_OK, mi355_videocompare_distance(MI355_HASH_BLOCKHASH, h[i], h[d.n + i]), {h[i], h[d.n + i]}};
+    }
+  }
+  static void failed(const CmpPair &, int rc, CmpResult *o) { *o = CmpResult{rc, 0.0, {0, 0}}; }
+  static int status(const CmpResult &o) { return o.status; }
+  void destroy() {
+    free_lanes();
+    blocks.destroy();
   }
 };
 
@@ -500,15 +595,20 @@ template <class Kind>
 struct SetQueue {
   using Item = QItem<typename Kind::Payload>;
   using Result = typename Kind::Result;
+  using Payload = typename Kind::Payload;
   struct Set {
-    uint64_t seq;  // launch order on the queue's stream: set n is done => every set before it is
+    uint64_t seq;  // launch order: set n of a lane is done => every earlier set of that lane is
     std::vector<uint64_t> tickets;
+    int lane;      // which of the kind's streams carries it
     hipEvent_t done;
     int waiters;
     typename Kind::SetData data;
     bool collected = false;
   };
-  Kind kind;                     // the queue's own stream, scratch and blocks: made at the first submit (Kind::ensure)
+  // where a ticket stands: still pending (its payload), in a set in flight (the set and its index there), or collected (its result)
+  struct Standing { const Payload *pending = nullptr; const Set *set = nullptr; size_t index = 0; const Result *result = nullptr; };
+  static_assert(Kind::kLanesMax <= 32, "retire_done keeps the lanes in a mask");
+  Kind kind;                     // the queue's own streams, scratch and blocks: made at the first submit (Kind::ensure)
   std::vector<Item> pending;
   std::deque<Set> sets;          // launched, oldest first
   std::unordered_map<uint64_t, uint64_t> where;   // ticket -> seq
@@ -528,6 +628,22 @@ struct SetQueue {
   // is `ticket` an item of this queue that has not been collected?
   bool owns(uint64_t ticket) const { return where.count(ticket) || results.count(ticket) || is_pending(ticket); }
 
+  // for an entry point that has to know something of the item before a refusal that must leave it collectable
+  Standing find(uint64_t ticket) const {
+    Standing st;
+    for (const Item &d : pending)
+      if (d.ticket == ticket) st.pending = &d.p;
+    auto w = where.find(ticket);
+    if (w != where.end())
+      for (const Set &s : sets)
+        if (s.seq == w->second)
+          for (size_t i = 0; i < s.tickets.size(); i++)
+            if (s.tickets[i] == ticket) { st.set = &s; st.index = i; }
+    auto r = results.find(ticket);
+    if (r != results.end()) st.result = &r->second;
+    return st;
+  }
+
   // what an entry point that serves another queue says to a ticket this queue owns
   static std::string foreign_refusal() { return std::string("group: a ") + Kind::kItem + "'s ticket (" + Kind::kWaitEntry + " collects it)"; }
 
@@ -540,7 +656,7 @@ struct SetQueue {
       kind.result(s.data, i, &results[s.tickets[i]]);
       where.erase(s.tickets[i]);
     }
-    kind.release(&s.data);
+    kind.blocks.give(&s.data.block);
   }
 
   // collected sets nobody waits inside leave: the event goes back to the free list
@@ -555,72 +671,90 @@ struct SetQueue {
     }
   }
 
-  // finished sets are collected without a waiter (the queue's stream is in order: the first unfinished set ends the search)
+  // finished sets are collected without a waiter (a lane's stream is in order: its first unfinished set ends the search there;
+  // the lanes finish independently)
   void retire_done(GroupCore *g) {
+    unsigned unfinished = 0;   // lanes, as bits
     for (Set &s : sets) {
-      if (s.collected) continue;
-      if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); break; }
+      if (s.collected || (unfinished >> s.lane & 1u)) continue;
+      if (hipEventQuery(s.done) != hipSuccess) { (void)hipGetLastError(); unfinished |= 1u << s.lane; continue; }
       collect(s);
     }
     retire(g);
   }
 
-  // launches the pending items in submission order, kSetMax to a set (all of them, or up to the set that carries `until`), as
-  // consecutive sets on the queue's stream. A set that fails is told to each ticket it carried, once, through `results`; the
-  // flush goes on to the next set and returns the first failure.
+  // Launches the pending items (all of them, or up to the set that carries `until`). A take is, in submission order, the items of
+  // the front item's class, up to kSetMax; what it passes over keeps its order. The kind deals the take out as parts, each a set
+  // on its lane's stream, behind the `ready` events of its own items only. A part that fails is told to each ticket it carried,
+  // once, through `results`; the flush goes on and returns the first failure. The stats count per take, and what stood.
   int flush_locked(GroupCore *g, uint64_t until = 0) {
     bool reached = false;
     int first_rc = MI355_OK;
     while (!pending.empty() && !reached) {
-      const size_t n = std::min(pending.size(), (size_t)Kind::kSetMax);
-      std::vector<Item> take(pending.begin(), pending.begin() + (std::ptrdiff_t)n);
-      pending.erase(pending.begin(), pending.begin() + (std::ptrdiff_t)n);
-      int launches = 0;
-      std::string err;
-      typename Kind::Plan plan;
-      typename Kind::SetData data;
-      int rc = kind.plan(take.data(), n, &plan, &err);
-      hipEvent_t done = take_event(g);
-      if (!rc) {
-        if (kind.no_free_block(plan)) retire_done(g);   // (a finished set nobody has collected gives its block back)
-        if (!kind.take_block(plan, &data) || !done) { rc = MI355_ERR_HIP; err = std::string("group: no event or pinned block for a ") + Kind::kName + " set"; }
+      std::vector<Item> all, keep;
+      for (Item &d : pending) {
+        if (all.empty() || ((int)all.size() < Kind::kSetMax && Kind::same_class(all.front().p, d.p))) all.push_back(std::move(d));
+        else keep.push_back(std::move(d));
       }
-      for (const Item &d : take)
-        if (!rc && d.ready && hipStreamWaitEvent(kind.stream, d.ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = std::string("hipStreamWaitEvent(") + Kind::kItem + ")"; }
-      if (!rc) rc = kind.launch(plan, n, &data, &launches, &err);
-      if (!rc && hipEventRecord(done, kind.stream) != hipSuccess) { rc = MI355_ERR_HIP; err = std::string("hipEventRecord(") + Kind::kName + " set)"; }
-      for (const Item &d : take)
-        if (d.ready) g->events.push_back(d.ready);
-      if (rc) {
-        (void)hipGetLastError();
-        if (done) g->events.push_back(done);
-        if (Kind::holds_block(data)) {
-          // what did go out may still write the block: it is free again only behind the queue's stream
-          (void)hipStreamSynchronize(kind.stream);
-          (void)hipGetLastError();
-          kind.release(&data);
+      pending.swap(keep);
+      Part parts[Kind::kLanesMax];
+      const int n_parts = kind.split(all, parts);
+      size_t stood = 0;
+      for (int k = 0; k < n_parts; k++) {
+        const Item *take = all.data() + parts[k].begin;
+        const size_t n = parts[k].end - parts[k].begin;
+        const int lane = parts[k].lane;
+        const hipStream_t stream = kind.lane_stream(lane);
+        int launches = 0;
+        std::string err;
+        typename Kind::Plan plan;
+        typename Kind::SetData data;
+        int rc = kind.plan(take, n, &plan, &err);
+        hipEvent_t done = take_event(g);
+        if (!rc) {
+          const size_t bytes = kind.block_bytes(plan);   // (0: this set has nothing to copy back)
+          if (bytes && kind.blocks.free.empty()) retire_done(g);   // (a finished set nobody has collected gives its block back)
+          if ((bytes && !kind.blocks.take(bytes, &data.block)) || !done) { rc = MI355_ERR_HIP; err = std::string("group: no event or pinned block for a ") + Kind::kName + " set"; }
         }
-        g->last_error = std::string("group: ") + Kind::kName + " launch failed: " + err;
-        if (results.size() > 65536) results.clear();
-        for (const Item &d : take) Kind::failed(d.p, rc, &results[d.ticket]);   // told to the item's own wait, once
-        if (!first_rc) first_rc = rc;
-        continue;
+        for (size_t i = 0; i < n; i++)
+          if (!rc && take[i].ready && hipStreamWaitEvent(stream, take[i].ready, 0) != hipSuccess) { rc = MI355_ERR_HIP; err = std::string("hipStreamWaitEvent(") + Kind::kItem + ")"; }
+        if (!rc) rc = kind.launch(lane, plan, n, &data, &launches, &err);
+        if (!rc && hipEventRecord(done, stream) != hipSuccess) { rc = MI355_ERR_HIP; err = std::string("hipEventRecord(") + Kind::kName + " set)"; }
+        for (size_t i = 0; i < n; i++)
+          if (take[i].ready) g->events.push_back(take[i].ready);
+        if (rc) {
+          (void)hipGetLastError();
+          if (done) g->events.push_back(done);
+          if (data.block.h) {
+            // what did go out may still write the block: it is free again only behind the lane's stream
+            (void)hipStreamSynchronize(stream);
+            (void)hipGetLastError();
+            kind.blocks.give(&data.block);
+          }
+          g->last_error = std::string("group: ") + Kind::kName + " launch failed: " + err;
+          if (results.size() > 65536) results.clear();
+          for (size_t i = 0; i < n; i++) Kind::failed(take[i].p, rc, &results[take[i].ticket]);   // told to the item's own wait, once
+          if (!first_rc) first_rc = rc;
+          continue;
+        }
+        kind.launched(g, plan, n);
+        Set s{next_seq++, {}, lane, done, 0, std::move(data)};
+        for (size_t i = 0; i < n; i++) { s.tickets.push_back(take[i].ticket); where[take[i].ticket] = s.seq; reached |= until != 0 && take[i].ticket == until; }
+        sets.push_back(std::move(s));
+        stood += n;
+        n_launches += (uint64_t)launches;
       }
-      kind.launched(g, plan, n);
-      Set s{next_seq++, {}, done, 0, std::move(data)};
-      for (const Item &d : take) { s.tickets.push_back(d.ticket); where[d.ticket] = s.seq; reached |= until != 0 && d.ticket == until; }
-      sets.push_back(std::move(s));
-      n_items += n;
+      if (!stood) continue;
+      n_items += stood;
       n_sets++;
-      if (n > n_largest) n_largest = n;
-      n_launches += (uint64_t)launches;
+      if (stood > n_largest) n_largest = stood;
     }
     cv.notify_all();
     return first_rc;
   }
 
-  // host wait for the set of `ticket`, and with it - the queue's stream being in order - for every earlier one; `lk` owns g->mu on
-  // entry and on return, not while waiting
+  // host wait for the set of `ticket`, and with it - its lane's stream being in order - for every earlier one of that lane; `lk`
+  // owns g->mu on entry and on return, not while waiting
   int wait_unlocking(GroupCore *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
     auto it = where.find(ticket);
     if (it == where.end()) return MI355_OK;  // collected already (or failed: `results` has it)
@@ -628,18 +762,25 @@ struct SetQueue {
     const Waited w = wait_seq_unlocking(sets, seq, lk);
     if (w == Waited::kNothing) return MI355_OK;
     if (w == Waited::kFailed) return fail(g, MI355_ERR_HIP, std::string("hipEventSynchronize(group ") + Kind::kName + " set)");
+    // (the set itself is still here: none retires while somebody waits inside it, and the lock has been held since)
+    int lane = -1;
+    for (const Set &s : sets)
+      if (s.seq == seq) lane = s.lane;
     for (Set &s : sets)
-      if (s.seq <= seq) collect(s);
+      if (s.lane == lane && s.seq <= seq) collect(s);
     retire(g);
     return MI355_OK;
   }
 
-  // waits for every set launched so far (their results stay collectable)
+  // waits for every set launched so far: for each lane's last uncollected one (their results stay collectable)
   int wait_all_unlocking(GroupCore *g, std::unique_lock<std::mutex> &lk) {
-    uint64_t last = 0;
+    uint64_t last[Kind::kLanesMax] = {0};
     for (const Set &s : sets)
-      if (!s.collected) last = s.tickets.front();
-    return last ? wait_unlocking(g, lk, last) : MI355_OK;
+      if (!s.collected) last[s.lane] = s.tickets.front();
+    for (uint64_t t : last)
+      if (t)
+        if (int rc = wait_unlocking(g, lk, t)) return rc;
+    return MI355_OK;
   }
 
   void set_rendezvous(int expected_streams, unsigned linger) {
@@ -697,18 +838,18 @@ struct SetQueue {
     out[3] = n_launches;
   }
 
-  // The queue's part of mi355_group_destroy (takes g->mu itself): items still pending are launched and waited for, as pairs are -
-  // their buffers belong to callers who may free them once destroy returns, and a detector's destination is complete by then.
+  // The queue's part of mi355_group_destroy (takes g->mu itself): items still pending are launched and waited for - their buffers
+  // belong to callers who may free them once destroy returns, and a detector's destination is complete by then.
   void destroy(GroupCore *g) {
-    if (!kind.stream) return;
+    if (!kind.lane_stream(0)) return;
     if (kind.set_up()) {
       std::lock_guard<std::mutex> lk(g->mu);
       (void)flush_locked(g);
     }
-    (void)hipStreamSynchronize(kind.stream);
+    for (int l = 0; l < kind.lanes(); l++) (void)hipStreamSynchronize(kind.lane_stream(l));
     for (Set &s : sets) {
       (void)hipEventDestroy(s.done);
-      kind.release(&s.data);
+      kind.blocks.give(&s.data.block);
     }
     sets.clear();
     for (Item &d : pending)
@@ -732,26 +873,9 @@ struct mi355_group : GroupCore {
   // table references of retired batches: dropping the last reference to a table frees 64 MiB behind a device-wide wait, which
   // does not belong under `mu` - the entry points empty this list into a local one that dies after they have unlocked (Locked)
   std::vector<std::shared_ptr<void>> dead_refs;
-  // ---- compare queue (videocompare's Dssim / Blockhash): its own context + stream, independent of the filter batches above
-  // The pairs of a launch set are dealt out to `n_lanes` contexts (streams): the Dssim kernels are VALU-bound at ~80 % busy when
-  // one runs alone, and a second stream's launches fill its tails and launch boundaries (32 4K pairs: 1.48 k comparisons/s on one
-  // stream, 1.84 k over eight) - what the dispatcher removes is the per-comparison host round trip, not the overlap.
-  mi355_ctx *alane[kCmpMaxLanes] = {nullptr};
-  int n_lanes = 8;
-  mi355_ctx *actx = nullptr;                 // = alane[0], created at the first compare submit
-  std::vector<CmpDesc> cmp_pending;
-  std::deque<CmpBatch> cmp_batches;          // launched, oldest first
-  std::unordered_map<uint64_t, uint64_t> cmp_where;      // ticket -> seq
-  std::unordered_map<uint64_t, CmpResult> cmp_results;   // finished, not yet collected by mi355_group_wait_compare
-  std::vector<void *> cmp_blocks;            // free pinned result blocks
-  uint32_t *d_hash_sums[kCmpMaxLanes] = {nullptr};   // Blockhash scratch per lane: [2 kCmpMaxBatch][64] u32 + [2 kCmpMaxBatch] u64
-  uint64_t next_cmp_seq = 1;
-  uint64_t n_cmp_pairs = 0, n_cmp_batches = 0, n_cmp_largest = 0;
-  int expected_streams = 0;                  // rendezvous: a waiter lingers until this many pairs are pending ...
-  unsigned linger_us = 0;                    // ... or this long (mi355_group_set_rendezvous)
-  std::condition_variable cv;                // "a compare batch has been launched"
-  // ---- the four set queues: each its own stream (and scratch, and blocks), created at its first submit, independent of the
-  // two queues above and of each other
+  // ---- the five set queues: each its own streams (and scratch, and blocks), created at its first submit, independent of the
+  // filter batches above and of each other
+  SetQueue<CmpKind> cmp; // videocompare pairs (Dssim / Blockhash)
   SetQueue<CdKind> cd;   // colordetect frames
   SetQueue<HdKind> hd;   // hsvdetector frames
   SetQueue<YdKind> yd;   // decoder tensors
@@ -896,154 +1020,10 @@ int wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
   return MI355_OK;
 }
 
-// ------------------------------------------------------------------ compare queue
+// ------------------------------------------------------------------ the detector queues, where an entry point names them all
 
-void *cmp_take_block(mi355_group *g) {
-  if (!g->cmp_blocks.empty()) { void *b = g->cmp_blocks.back(); g->cmp_blocks.pop_back(); return b; }
-  void *b = nullptr;
-  if (hipHostMalloc(&b, kCmpBlockBytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  return b;
-}
-
-bool cmp_same_class(const CmpDesc &a, const CmpDesc &b) {
-  return a.algo == b.algo && a.width == b.width && a.height == b.height && a.stride == b.stride && a.format == b.format && a.translucent == b.translucent && a.fast == b.fast;
-}
-
-// a finished batch: values from its pinned block into cmp_results (once). g->mu held.
-void cmp_collect(mi355_group *g, CmpBatch &b) {
-  if (b.collected) return;
-  b.collected = true;
-  const int n = (int)b.tickets.size();
-  if (b.algo == MI355_HASH_DSSIM) {
-    std::vector<double> v((size_t)n);
-    dssim_scores_from_slots(b.width, b.height, (const double *)b.h_block, n, v.data());
-    for (int i = 0; i < n; i++) g->cmp_results[b.tickets[i]] = CmpResult{MI355_OK, v[i], {0, 0}};
-  } else {
-    const uint64_t *h = (const uint64_t *)b.h_block;
-    for (int i = 0; i < n; i++)
-      g->cmp_results[b.tickets[i]] = CmpResult{MI355_OK, mi355_videocompare_distance(MI355_HASH_BLOCKHASH, h[i], h[n + i]), {h[i], h[n + i]}};
-  }
-  for (uint64_t t : b.tickets) g->cmp_where.erase(t);
-}
-
-// collected batches nobody waits inside leave from the front: event and pinned block back to their free lists. g->mu held.
-void cmp_retire(mi355_group *g) {
-  for (auto it = g->cmp_batches.begin(); it != g->cmp_batches.end();) {
-    if (it->collected && it->waiters == 0) {
-      g->cmp_blocks.push_back(it->h_block);
-      g->events.push_back(it->done);
-      it = g->cmp_batches.erase(it);
-    } else {
-      ++it;
-    }
-  }
-}
-
-// launches the pending pairs, class by class (all of them, or up to the batch that carries `until`): the pairs of a class are
-// dealt out to the lanes in contiguous shares (pairs that share a reference frame stay together). g->mu held.
-int cmp_flush_locked(mi355_group *g, uint64_t until = 0) {
-  bool reached = false;
-  int first_rc = MI355_OK;
-  while (!g->cmp_pending.empty() && !reached) {
-    std::vector<CmpDesc> all, keep;
-    const CmpDesc first = g->cmp_pending.front();
-    for (const CmpDesc &d : g->cmp_pending) {
-      if ((int)all.size() < kCmpMaxBatch && cmp_same_class(first, d)) all.push_back(d);
-      else keep.push_back(d);
-    }
-    g->cmp_pending.swap(keep);
-    // pairs that share a reference frame next to each other (videocompare with several pads: the reference is hashed once)
-    std::stable_sort(all.begin(), all.end(), [](const CmpDesc &a, const CmpDesc &b) { return (uintptr_t)a.ref < (uintptr_t)b.ref; });
-    const int total = (int)all.size();
-    const int lanes = total < g->n_lanes ? total : g->n_lanes;
-    PixFmt fmt;
-    (void)pixfmt_of(first.format, &fmt);
-    int begin = 0;
-    for (int lane = 0; lane < lanes; lane++) {
-      int end = (int)((long long)total * (lane + 1) / lanes);
-      // a reference frame is not split over two lanes
-      while (end < total && end > begin && all[end].ref == all[end - 1].ref) end++;
-      if (end <= begin) continue;
-      std::vector<CmpDesc> take(all.begin() + begin, all.begin() + end);
-      begin = end;
-      const int n = (int)take.size();
-      mi355_ctx *a = g->alane[lane];
-      int rc = MI355_OK;
-      hipEvent_t done = take_event(g);
-      void *block = cmp_take_block(g);
-      if (!done || !block) rc = MI355_ERR_HIP;
-      for (const CmpDesc &d : take)
-        if (!rc && d.ready && hipStreamWaitEvent(a->stream, d.ready, 0) != hipSuccess) rc = MI355_ERR_HIP;
-      std::vector<const uint8_t *> refs((size_t)n), frames((size_t)n);
-      for (int i = 0; i < n; i++) { refs[i] = take[i].ref; frames[i] = take[i].frame; }
-      if (!rc && first.algo == MI355_HASH_DSSIM) {
-        a->dssim_translucent = first.translucent;
-        a->dssim_fast = first.fast;   // a batch holds pairs of one form only (cmp_same_class)
-        rc = dssim_compare_pairs_enqueue(a, refs.data(), frames.data(), n, first.stride, first.width, first.height, fmt.pixel_stride, (double *)block);
-      } else if (!rc) {
-        std::vector<const uint8_t *> both(refs);
-        both.insert(both.end(), frames.begin(), frames.end());
-        unsigned long long *d_hashes = (unsigned long long *)(g->d_hash_sums[lane] + (size_t)2 * kCmpMaxBatch * 64);
-        rc = blockhash_enqueue(a, both.data(), 2 * n, first.stride, first.width, first.height, fmt.pixel_stride, g->d_hash_sums[lane], d_hashes);
-        if (!rc && hipMemcpyAsync(block, d_hashes, (size_t)2 * n * 8, hipMemcpyDeviceToHost, a->stream) != hipSuccess) rc = MI355_ERR_HIP;
-      }
-      if (!rc && hipEventRecord(done, a->stream) != hipSuccess) rc = MI355_ERR_HIP;
-      if (rc) {
-        (void)hipGetLastError();
-        if (done) g->events.push_back(done);
-        if (block) g->cmp_blocks.push_back(block);
-        g->last_error = a->last_error.empty() ? "group: compare launch failed" : a->last_error;
-        if (g->cmp_results.size() > 65536) g->cmp_results.clear();   // (results nobody ever collected)
-        for (const CmpDesc &d : take) g->cmp_results[d.ticket] = CmpResult{rc, 0.0, {0, 0}};   // told to the pair's own wait, once
-        if (!first_rc) first_rc = rc;
-        continue;
-      }
-      CmpBatch b{g->next_cmp_seq++, {}, first.algo, first.width, first.height, lane, done, 0, block};
-      for (const CmpDesc &d : take) { b.tickets.push_back(d.ticket); g->cmp_where[d.ticket] = b.seq; reached |= until != 0 && d.ticket == until; }
-      g->cmp_batches.push_back(std::move(b));
-    }
-    for (const CmpDesc &d : all)
-      if (d.ready) g->events.push_back(d.ready);
-    g->n_cmp_pairs += (uint64_t)total;
-    g->n_cmp_batches++;
-    if ((uint64_t)total > g->n_cmp_largest) g->n_cmp_largest = (uint64_t)total;
-  }
-  g->cv.notify_all();
-  return first_rc;
-}
-
-// finished batches are collected without a waiter (their results stay in cmp_results until asked for)
-void cmp_retire_done(mi355_group *g) {
-  for (CmpBatch &b : g->cmp_batches) {
-    if (b.collected) continue;
-    if (hipEventQuery(b.done) != hipSuccess) { (void)hipGetLastError(); continue; }   // (the lanes finish independently)
-    cmp_collect(g, b);
-  }
-  cmp_retire(g);
-}
-
-// host wait for the batch of `ticket`; `lk` owns g->mu on entry and on return, not while waiting
-int cmp_wait_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk, uint64_t ticket) {
-  auto it = g->cmp_where.find(ticket);
-  if (it == g->cmp_where.end()) return MI355_OK;  // collected already (or failed: cmp_results has it)
-  const uint64_t seq = it->second;
-  const Waited w = wait_seq_unlocking(g->cmp_batches, seq, lk);
-  if (w == Waited::kNothing) return MI355_OK;
-  if (w == Waited::kFailed) return fail(g, MI355_ERR_HIP, "hipEventSynchronize(group compare batch)");
-  // a lane's stream is in order: everything of that lane up to this batch is done (the batch itself is still here: none
-  // retires while somebody waits inside it)
-  int lane = -1;
-  for (const CmpBatch &b : g->cmp_batches)
-    if (b.seq == seq) lane = b.lane;
-  for (CmpBatch &b : g->cmp_batches)
-    if (b.lane == lane && b.seq <= seq) cmp_collect(g, b);
-  cmp_retire(g);
-  return MI355_OK;
-}
-
-// ------------------------------------------------------------------ the set queues, where an entry point names them all
-
-// f(queue) for each, in the order flush, wait_all and destroy go through them
+// f(queue) for each of the four detector queues, in the order flush, wait_all and destroy go through them. The compare queue is
+// not among them: flush and destroy name it themselves, and wait_all and the foreign-ticket refusal below do not reach pairs.
 template <class F>
 void for_each_set_queue(mi355_group *g, F &&f) {
   f(g->cd);
@@ -1090,22 +1070,7 @@ void mi355_group_destroy(mi355_group *g) {
     (void)wait_all_unlocking(g, L.lk);
   }
   (void)hipStreamSynchronize(g->stream);
-  if (g->actx) {
-    // pairs still pending are launched and waited for: their frames belong to callers who may free them once this returns
-    {
-      Locked L(g);
-      (void)cmp_flush_locked(g);
-    }
-    for (int l = 0; l < kCmpMaxLanes; l++)
-      if (g->alane[l]) (void)hipStreamSynchronize(g->alane[l]->stream);
-    for (CmpBatch &b : g->cmp_batches) { (void)hipEventDestroy(b.done); (void)hipHostFree(b.h_block); }
-    g->cmp_batches.clear();
-    for (void *b : g->cmp_blocks) (void)hipHostFree(b);
-    for (int l = 0; l < kCmpMaxLanes; l++) {
-      if (g->d_hash_sums[l]) (void)hipFree(g->d_hash_sums[l]);
-      if (g->alane[l]) mi355_ctx_destroy(g->alane[l]);
-    }
-  }
+  if (g->cmp.kind.set_up()) g->cmp.destroy(g);
   for_each_set_queue(g, [&](auto &q) { q.destroy(g); });
   for (Batch &b : g->batches) (void)hipEventDestroy(b.done);   // (normally none left: wait_all retired them)
   for (Desc &d : g->pending)
@@ -1185,7 +1150,7 @@ int mi355_group_flush(mi355_group *g) {
   Locked L(g);
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
   const int rc = flush_locked(g);
-  const int rc2 = g->actx ? cmp_flush_locked(g) : MI355_OK;
+  const int rc2 = g->cmp.kind.set_up() ? g->cmp.flush_locked(g) : MI355_OK;
   int first = rc ? rc : rc2;
   for_each_set_queue(g, [&](auto &q) {   // every queue that has been set up is launched; the first failure is the answer
     const int r = q.kind.set_up() ? q.flush_locked(g) : MI355_OK;
@@ -1199,16 +1164,15 @@ int mi355_group_flush(mi355_group *g) {
 int mi355_group_set_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
   if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  g->expected_streams = expected_streams;
-  g->linger_us = linger_us;
+  g->cmp.set_rendezvous(expected_streams, linger_us);
   return MI355_OK;
 }
 
 int mi355_group_set_compare_lanes(mi355_group *g, int lanes) {
   if (!g || lanes < 1 || lanes > kCmpMaxLanes) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  if (g->actx) return fail(g, MI355_ERR_INVALID_ARG, "group: the compare queue's streams exist already (set the lanes before the first submit_compare)");
-  g->n_lanes = lanes;
+  if (g->cmp.kind.set_up()) return fail(g, MI355_ERR_INVALID_ARG, "group: the compare queue's streams exist already (set the lanes before the first submit_compare)");
+  g->cmp.kind.n_lanes = lanes;
   return MI355_OK;
 }
 
@@ -1224,67 +1188,18 @@ int mi355_group_submit_compare(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_
     return fail(g, MI355_ERR_UNSUPPORTED, "group: pairs are batched for hash-algorithm dssim and blockhash; the resize hashes go through their context");
   if (algo == MI355_HASH_BLOCKHASH && (width % 8 != 0 || height % 8 != 0))
     return fail(g, MI355_ERR_UNSUPPORTED, "group: blockhash batches take frames of 8 x 8 whole blocks (the any-size path goes through its context)");
-  if (ctx->device != g->device) return fail(g, MI355_ERR_INVALID_ARG, "group: context of another device");
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  if (!g->actx) {
-    int st = MI355_OK;
-    for (int l = 0; l < g->n_lanes && !st; l++) {
-      g->alane[l] = mi355_ctx_create(g->device, &st);
-      if (!g->alane[l] && !st) st = MI355_ERR_HIP;
-      if (!st && hipMalloc((void **)&g->d_hash_sums[l], (size_t)2 * kCmpMaxBatch * (64 * 4 + 8)) != hipSuccess) { (void)hipGetLastError(); st = MI355_ERR_OUT_OF_MEMORY; }
-    }
-    if (st) {
-      for (int l = 0; l < kCmpMaxLanes; l++) {
-        if (g->d_hash_sums[l]) (void)hipFree(g->d_hash_sums[l]);
-        if (g->alane[l]) mi355_ctx_destroy(g->alane[l]);
-        g->d_hash_sums[l] = nullptr; g->alane[l] = nullptr;
-      }
-      return fail(g, st, "group: no contexts for the compare queue");
-    }
-    g->actx = g->alane[0];
-  }
-  cmp_retire_done(g);
-  CmpDesc d{};
-  d.ctx = ctx; d.ref = d_ref; d.frame = d_frame; d.width = width; d.height = height; d.stride = stride; d.format = format; d.algo = algo;
-  d.translucent = ctx->dssim_translucent;
-  d.fast = ctx->dssim_fast;
-  // the pair starts after what the stream's own context holds now (an upload)
-  if (int rc = record_ready(g, ctx, &d.ready)) return rc;
-  d.ticket = g->next_ticket++;
-  if (ticket) *ticket = d.ticket;
-  g->cmp_pending.push_back(d);
-  // everybody is here (rendezvous), or a launch set is full: go. The pair has been accepted whatever that launch does (a failure
-  // is told to the waits of the pairs it carried).
-  const int full = g->expected_streams > 0 && g->expected_streams < kCmpMaxBatch ? g->expected_streams : kCmpMaxBatch;
-  if ((int)g->cmp_pending.size() >= full) (void)cmp_flush_locked(g);
-  return MI355_OK;
+  // the pair starts after what the stream's own context holds now (an upload); a caller may leave the ticket to flush
+  uint64_t t = 0;
+  const int rc = g->cmp.submit(g, ctx, CmpPair{d_ref, d_frame, width, height, stride, format, algo, ctx->dssim_translucent, ctx->dssim_fast}, true, &t);
+  if (!rc && ticket) *ticket = t;
+  return rc;
 }
 
 int mi355_group_wait_compare(mi355_group *g, uint64_t ticket, double *distance, uint64_t hashes[2]) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
-  std::unique_lock<std::mutex> &lk = L.lk;
-  if (ticket == 0 || ticket >= g->next_ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: unknown ticket");
-  if (int rc = refuse_set_queue_ticket(g, ticket)) return rc;
-  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  auto is_pending = [&]() { for (const CmpDesc &d : g->cmp_pending) if (d.ticket == ticket) return true; return false; };
-  if (is_pending()) {
-    // rendezvous: the other streams of this interval are about to submit - linger for them (bounded), then launch what is there
-    if (g->expected_streams > 0 && g->linger_us > 0) {
-      const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(g->linger_us);
-      while (is_pending() && (int)g->cmp_pending.size() < g->expected_streams) {
-        if (g->cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
-      }
-    }
-    if (is_pending()) (void)cmp_flush_locked(g, ticket);   // (a failure of this pair's own launch is in cmp_results)
-  }
-  int rc = cmp_wait_unlocking(g, lk, ticket);
-  if (rc) return rc;
-  auto r = g->cmp_results.find(ticket);
-  if (r == g->cmp_results.end()) return fail(g, MI355_ERR_INVALID_ARG, "group: this pair's result has been collected already (or the ticket is not a pair's)");
-  const CmpResult res = r->second;
-  g->cmp_results.erase(r);
-  if (res.status) return fail(g, res.status, "group: the launch that carried this pair failed");
+  CmpResult res;
+  if (int rc = g->cmp.wait(g, L.lk, ticket, &res)) return rc;
   if (distance) *distance = res.distance;
   if (hashes) { hashes[0] = res.hashes[0]; hashes[1] = res.hashes[1]; }
   return MI355_OK;
@@ -1293,9 +1208,9 @@ int mi355_group_wait_compare(mi355_group *g, uint64_t ticket, double *distance, 
 int mi355_group_compare_stats(mi355_group *g, uint64_t stats[3]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(g->mu);
-  stats[0] = g->n_cmp_pairs;
-  stats[1] = g->n_cmp_batches;
-  stats[2] = g->n_cmp_largest;
+  uint64_t all[4];   // (the compare queue reports no launch column)
+  g->cmp.stats(all);
+  std::copy(all, all + 3, stats);
   return MI355_OK;
 }
 
@@ -1432,18 +1347,8 @@ int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *de
     // Only a tensor submitted with max_dets == 0 has no records to take. The refusal leaves the result collectable, so the
     // capacity is looked up wherever the tensor stands - pending, in a set in flight, or collected into `results` - and not by
     // taking the result out first. (A ticket that is not this queue's has no capacity here and is refused below.)
-    SetQueue<YdKind> &q = g->yd;
-    uint32_t cap = 0;
-    for (const auto &d : q.pending)
-      if (d.ticket == ticket) cap = d.p.max_dets;
-    auto w = q.where.find(ticket);
-    if (w != q.where.end())
-      for (const auto &s : q.sets)
-        if (s.seq == w->second)
-          for (size_t i = 0; i < s.tickets.size(); i++)
-            if (s.tickets[i] == ticket) cap = s.data.slots[i].max_dets;
-    auto r = q.results.find(ticket);
-    if (r != q.results.end()) cap = r->second.max_dets;
+    const auto at = g->yd.find(ticket);
+    const uint32_t cap = at.pending ? at.pending->max_dets : at.set ? at.set->data.slots[at.index].max_dets : at.result ? at.result->max_dets : 0;
     if (cap) return fail(g, MI355_ERR_INVALID_ARG, "group: null records for a tensor submitted with max_dets > 0");
   }
   YdOut res;
@@ -1512,18 +1417,8 @@ int mi355_group_wait_handdec(mi355_group *g, uint64_t ticket, mi355_hand_det *de
     // Only a palm ticket has no keypoint records to take. The refusal leaves the result collectable, so the decoder is looked up
     // wherever the tensor stands - pending, in a set in flight, or collected into `results` - and not by taking the result out
     // first. (A ticket that is not this queue's has no decoder here and is refused below.)
-    SetQueue<HnKind> &q = g->hn;
-    int decoder = 0;
-    for (const auto &d : q.pending)
-      if (d.ticket == ticket) decoder = d.p.decoder;
-    auto w = q.where.find(ticket);
-    if (w != q.where.end())
-      for (const auto &s : q.sets)
-        if (s.seq == w->second)
-          for (size_t i = 0; i < s.tickets.size(); i++)
-            if (s.tickets[i] == ticket) decoder = s.data.slots[i].decoder;
-    auto r = q.results.find(ticket);
-    if (r != q.results.end()) decoder = r->second.decoder;
+    const auto at = g->hn.find(ticket);
+    const int decoder = at.pending ? at.pending->decoder : at.set ? at.set->data.slots[at.index].decoder : at.result ? at.result->decoder : 0;
     if (decoder == 1) return fail(g, MI355_ERR_INVALID_ARG, "group: null keypoint records for a landmark tensor");
   }
   HnOut res;

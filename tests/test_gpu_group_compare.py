@@ -103,6 +103,39 @@ def test_dssim_pairs_against_the_restatement_and_shared_reference(mi355lib):
         c.close()
 
 
+@pytest.mark.parametrize("lanes", [3, 1])
+def test_an_unsplit_reference_leaves_a_lane_empty(mi355lib, lanes):
+    """Four pairs over three lanes, three of them on one reference frame: the launch set's pairs are sorted by reference and dealt
+    out in contiguous shares, and a reference is never split over two lanes - so the shared reference's three pairs take the
+    second share as well and one lane gets nothing. The shared reference is allocated first so that its address sorts first (shares
+    {3 shared} {} {other}); an allocator that orders the addresses the other way gives {other} {3 shared} {}: valid shares too, and
+    the same assertions hold. One lane: the same values from one share of four."""
+    import mi355fx
+    w, h = 64, 48
+    rng = np.random.default_rng(21)
+    c = mi355fx.Context(0)
+    g = mi355fx.Group(0)
+    g.set_compare_lanes(lanes)
+    try:
+        shared, other = _frame(rng, w, h), _frame(rng, w, h)
+        d_shared = _upload(c, shared)                                       # first: the lower address
+        d_other = _upload(c, other)
+        d_frames = [_upload(c, _noisy(rng, other, 25))] + [_upload(c, _noisy(rng, shared, amp)) for amp in (4, 30, 80)]
+        d_refs = [d_other, d_shared, d_shared, d_shared]                    # submitted: other, shared, shared, shared
+        exp = [_own_dssim(c, r, f, w, h) for r, f in zip(d_refs, d_frames)]
+        assert len(set(exp)) == 4 and all(v > 0.0 for v in exp)
+        tk = [g.submit_compare(c, r, f, w * 4, w, h, "RGBA", 5) for r, f in zip(d_refs, d_frames)]
+        assert g.compare_stats() == (0, 0, 0)                               # nothing goes before a wait
+        for i in reversed(range(4)):
+            assert g.wait_compare(tk[i])[0] == exp[i], i
+        assert g.compare_stats() == (4, 1, 4)                               # one launch set, whatever its shares
+        for d in [d_shared, d_other] + d_frames:
+            c.free(d)
+    finally:
+        g.close()
+        c.close()
+
+
 def test_blockhash_pairs_and_mixed_classes_in_one_queue(mi355lib, oracle):
     """Blockhash pairs (RGBA and RGB), Dssim pairs of two sizes, all pending at once: each class gets its own launch sequence."""
     import mi355fx

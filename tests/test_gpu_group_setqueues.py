@@ -1,13 +1,16 @@
-"""The set-queue protocol of the dispatcher's three detector queues (csrc/group.hip: colordetect, hsvdetector, decoder), one
-script per path the per-queue files leave open, each run for every kind through a small adaptor: sets collected out of order (Q1),
-more sets in flight than the blocks of first use (Q2), flush (Q3), a wait for a ticket in the middle of the pending list (Q4) and
-all three kinds in one group (Q5). One thread, no rendezvous: every step is deterministic.
+"""The set-queue protocol of the dispatcher (csrc/group.hip, SetQueue<Kind>) for four of its kinds - colordetect, hsvdetector,
+decoder and the videocompare pairs (the hand decoder's queue is the subject of its own file) - one script per path the per-queue files leave open,
+each run for every kind through a small adaptor: sets collected out of order (Q1), more sets in flight than the blocks of first
+use (Q2), flush (Q3), a wait for a ticket in the middle of the pending list (Q4) and all kinds in one group (Q5). One thread, no
+rendezvous: every step is deterministic. The compare queue is the kind with lanes: a launch set goes out as up to eight parts on
+eight streams, and what Q1 collects in reverse it collects per lane.
 
 The bar is `==` against the lone entry on the same Context and the same device bytes (Context.colordetect_frames_device,
-Context.hsvdetect_frames_device, Context.yolodec_device with one tensor), computed once per item of this module. Items differ by
-seed, so a result handed to the wrong ticket is seen. The stats' launches column follows each kind's launch rule: colordetect one
-histogram and one MMCQ launch per set; hsvdetector one launch for a set of vector-class frames (all frames here are packed, aligned
-and on the dial); decoder one score launch per layout present and one NMS launch."""
+Context.hsvdetect_frames_device, Context.yolodec_device with one tensor, Context.dssim_create_image_device +
+dssim_compare_frames_device), computed once per item of this module. Items differ by seed, so a result handed to the wrong ticket
+is seen. The stats' launches column follows each kind's launch rule: colordetect one histogram and one MMCQ launch per set;
+hsvdetector one launch for a set of vector-class frames (all frames here are packed, aligned and on the dial); decoder one score
+launch per layout present and one NMS launch; the compare queue reports none."""
 import numpy as np
 import pytest
 
@@ -172,7 +175,62 @@ class Yolodec:
             self.c.free(it[0])
 
 
-KINDS = {"colordetect": Colordetect, "hsvdetect": Hsvdetect, "yolodec": Yolodec}
+class Compare:
+    """Dssim pairs of one class (one size, one format, the exact form), so that launch sets are the contiguous runs of the pending
+    list the scripts' stats expect; classes are test_gpu_group_compare.py's subject. A set's pairs go out over the group's default
+    eight lanes, so a script that collects out of order collects per lane. The compare queue reports no launch column:
+    compare_stats() has three figures, shown here with a launch count of 0."""
+    name = "compare"
+
+    def __init__(self, c):
+        self.c, self.items, self._lone = c, [], {}
+        for i in range(N_ITEMS):
+            rng = np.random.default_rng(4000 + i)
+            a = np.kron(rng.integers(0, 256, (H // 8, W // 8, 4), dtype=np.uint8), np.ones((8, 8, 1), np.uint8)).reshape(H, W * 4)   # a frame of its own ...
+            amp = 2 + 3 * (i % 29)
+            b = np.clip(a.astype(int) + rng.integers(-amp, amp + 1, a.shape), 0, 255).astype(np.uint8)                                 # ... and a noisy copy
+            a[:, 3::4] = b[:, 3::4] = 255
+            pair = []
+            for host in (a, b):
+                d = c.alloc(host.nbytes)
+                c.h2d(d, np.ascontiguousarray(host).reshape(-1))
+                pair.append(d)
+            self.items.append(tuple(pair))
+
+    def reset(self):
+        pass
+
+    def submit(self, g, i):
+        d_ref, d_frame = self.items[i]
+        return g.submit_compare(self.c, d_ref, d_frame, W * 4, W, H, "RGBA", 5)
+
+    def wait(self, g, i, ticket):
+        return g.wait_compare(ticket)[0]
+
+    def lone(self, i):
+        if i not in self._lone:
+            d_ref, d_frame = self.items[i]
+            x = self.c.dssim_create_image_device(d_ref, W * 4, W, H)
+            self._lone[i] = self.c.dssim_compare_frames_device(x, [d_frame], W * 4, W, H)[0]
+            self.c.dssim_free_image(x)
+        return self._lone[i]
+
+    def key(self, result):
+        return result
+
+    def stats(self, g):
+        return g.compare_stats() + (0,)
+
+    def launches(self, idx):
+        return 0
+
+    def free(self):
+        for it in self.items:
+            self.c.free(it[0])
+            self.c.free(it[1])
+
+
+KINDS = {"colordetect": Colordetect, "hsvdetect": Hsvdetect, "yolodec": Yolodec, "compare": Compare}
 
 
 @pytest.fixture(scope="module")
@@ -302,22 +360,23 @@ def test_q4_wait_for_a_ticket_in_the_middle_of_the_pending_list(pools, kind):
         g.close()
 
 
-def test_q5_all_three_kinds_in_one_group(pools):
+def test_q5_all_kinds_in_one_group(pools):
     import mi355fx
     kinds = [pools(k) for k in KINDS]
+    nk = len(kinds)
     n = SET_MAX + 1                                                                   # two sets each: a full one and one of one
     g = mi355fx.Group(0)
     try:
         tk = {}
         for i in range(n):
-            for a in kinds:                                                           # interleaved: cd, hd, yd, cd, hd, yd, ...
+            for a in kinds:                                                           # interleaved: cd, hd, yd, cmp, cd, hd, yd, cmp, ...
                 tk[a.name, i] = a.submit(g, i)
-        assert len(set(tk.values())) == 3 * n                                         # one ticket sequence
+        assert len(set(tk.values())) == nk * n                                        # one ticket sequence
         for a in kinds:
             assert a.stats(g) == (SET_MAX, 1, SET_MAX, a.launches(range(SET_MAX)))
         # items from the last to the first, the kinds rotating: never the order of submission
         for i in reversed(range(n)):
-            for a in (kinds[(i + 2) % 3], kinds[i % 3], kinds[(i + 1) % 3]):
+            for a in (kinds[(i + 2 + j) % nk] for j in range(nk)):
                 assert a.wait(g, i, tk[a.name, i]) == a.lone(i), (a.name, i)
         for a in kinds:
             assert a.stats(g) == (n, 2, SET_MAX, a.launches(range(SET_MAX)) + a.launches([SET_MAX])), a.name   # each queue counts only its own

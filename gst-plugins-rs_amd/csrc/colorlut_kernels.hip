@@ -1212,127 +1212,169 @@ int lut_upload(mi355_ctx *ctx, int is3d, size_t size, const float *table, const 
   return MI355_OK;
 }
 
-template <int NT, int P4, int S_CONST, int HSV = kNoHsv>
-static int launch_lds_variant(mi355_ctx *ctx, const uint4 *src, uint4 *dst, size_t n_groups, const HsvK &hk = HsvK{}) {
-  auto kern = colorlut3d_lds_kernel<NT, P4, S_CONST, HSV>;
-  const LutDevice &L = ctx->lut;
-  const size_t lds = L.lds_bytes;
-  int rc = check_hip(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                     "hipFuncSetAttribute(max dynamic LDS)");
-  if (rc) return rc;
-  // one block per CU (the plane takes the CU's whole LDS); small inputs use fewer blocks so that a
-  // block always has at least 1024 pixels to amortise its plane stagings
-  size_t grid = (size_t)ctx->n_cu;
-  const size_t min_blocks = (n_groups + 255) / 256;
-  if (grid > min_blocks) grid = min_blocks;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, ctx->stream, src, dst, n_groups, (const float *)L.d_planar,
-                     (const uint32_t *)L.d_axis, L.lds_Sy, L.lds_Sz, (uint32_t)L.planar_plane_floats,
-                     (L.lds_all_resident ? 1 : 0) | (ctx->lut_stagger << 8), hk);
-  return check_hip(ctx, hipGetLastError(), "colorlut3d_lds kernel launch");
-}
+// ---- host dispatch of the interpolating kernels
+// The frames of one call, as the entry points receive them.
+struct LutFrames {
+  const uint8_t *src; size_t src_pitch; int src_stride;
+  uint8_t *dst; size_t dst_pitch; int dst_stride;
+  int n_frames, width, height;
+  unsigned long long pixels() const { return (unsigned long long)width * height * n_frames; }
+};
 
-template <int NT, int P4>
-static int launch_lean_variant(mi355_ctx *ctx, const uint4 *src, uint4 *dst, size_t n_groups) {
-  const LutDevice &L = ctx->lut;
-  const size_t lds = L.lds_bytes;
-  const void *k33 = (const void *)colorlut3d_lean_kernel<NT, P4, 33>, *k0 = (const void *)colorlut3d_lean_kernel<NT, P4, 0>;
-  int rc = check_hip(ctx, hipFuncSetAttribute(L.size == 33 ? k33 : k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(max dynamic LDS)");
-  if (rc) return rc;
-  size_t grid = (size_t)ctx->n_cu;
-  const size_t min_blocks = (n_groups + 255) / 256;
-  if (grid > min_blocks) grid = min_blocks;
-  if (grid < 1) grid = 1;
-  if (L.size == 33)
-    hipLaunchKernelGGL((colorlut3d_lean_kernel<NT, P4, 33>), dim3((unsigned)grid), dim3(NT), lds, ctx->stream, src, dst, n_groups, (const float *)L.d_planar,
-                       (const uint32_t *)L.d_axis, L.lds_Sy, L.lds_Sz, (uint32_t)L.planar_plane_floats, L.lds_all_resident ? 1 : 0);
-  else
-    hipLaunchKernelGGL((colorlut3d_lean_kernel<NT, P4, 0>), dim3((unsigned)grid), dim3(NT), lds, ctx->stream, src, dst, n_groups, (const float *)L.d_planar,
-                       (const uint32_t *)L.d_axis, L.lds_Sy, L.lds_Sz, (uint32_t)L.planar_plane_floats, L.lds_all_resident ? 1 : 0);
-  return check_hip(ctx, hipGetLastError(), "colorlut3d_lean kernel launch");
-}
-
-// Is the RGBA8 3D LDS kernel applicable to this geometry? (contiguous rows and frames, 16 B aligned)
-static bool lds3d_rgba_applicable(const mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, const uint8_t *d_dst,
-                                  size_t dst_pitch, int dst_stride, int n_frames, int width, int height, size_t *n_groups) {
-  const LutDevice &L = ctx->lut;
-  if (!(L.is3d && L.lds_ok) || ctx->force_generic) return false;
-  const size_t row_bytes = (size_t)width * 4;
-  const bool contiguous = (size_t)src_stride == row_bytes && (size_t)dst_stride == row_bytes &&
-                          (n_frames == 1 || (src_pitch == row_bytes * (size_t)height && dst_pitch == row_bytes * (size_t)height));
-  const size_t total_bytes = row_bytes * (size_t)height * (size_t)n_frames;
-  if (!(contiguous && ((uintptr_t)d_src % 16 == 0) && ((uintptr_t)d_dst % 16 == 0) && (total_bytes % 16 == 0))) return false;
+// THE packed-geometry test of the flat kernels, for pixels of `bpp` bytes: rows and frames back to back, both bases 16-byte
+// aligned, the total a whole number of 16-byte groups (*n_groups).
+static bool packed_geom(const LutFrames &F, int bpp, size_t *n_groups) {
+  const size_t row_bytes = (size_t)F.width * (size_t)bpp;
+  const bool contiguous = (size_t)F.src_stride == row_bytes && (size_t)F.dst_stride == row_bytes &&
+                          (F.n_frames == 1 || (F.src_pitch == row_bytes * (size_t)F.height && F.dst_pitch == row_bytes * (size_t)F.height));
+  const size_t total_bytes = row_bytes * (size_t)F.height * (size_t)F.n_frames;
+  if (!contiguous || (uintptr_t)F.src % 16 != 0 || (uintptr_t)F.dst % 16 != 0 || total_bytes % 16 != 0) return false;
   *n_groups = total_bytes / 16;
   return true;
 }
 
-template <int NT, int P4, int S_CONST, int HSV, bool LATE_LOAD = false>
-static int launch_pipe_variant(mi355_ctx *ctx, const uint4 *src, uint4 *dst, size_t n_groups, const HsvK &hk) {
-  auto kern = hsv_colorlut3d_pipe_kernel<NT, P4, S_CONST, HSV, LATE_LOAD>;
-  const LutDevice &L = ctx->lut;
-  const size_t lds = L.lds_bytes;
-  int rc = check_hip(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                     "hipFuncSetAttribute(max dynamic LDS)");
-  if (rc) return rc;
+// one block per CU (the plane takes the CU's whole LDS); small inputs use fewer blocks so that a block always has at least
+// 1024 pixels to amortise its plane stagings
+static unsigned grid_block_per_cu(const mi355_ctx *ctx, size_t n_groups) {
   size_t grid = (size_t)ctx->n_cu;
   const size_t min_blocks = (n_groups + 255) / 256;
   if (grid > min_blocks) grid = min_blocks;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, ctx->stream, src, dst, n_groups, (const float *)L.d_planar,
-                     (const uint32_t *)L.d_axis, L.lds_Sy, L.lds_Sz, (uint32_t)L.planar_plane_floats, L.lds_all_resident ? 1 : 0, hk);
-  return check_hip(ctx, hipGetLastError(), "hsv_colorlut3d_pipe kernel launch");
+  return grid < 1 ? 1u : (unsigned)grid;
+}
+// blocks per CU limited by the LDS image (four at most); a few hundred pixels per lane amortise the table staging
+static unsigned grid_by_lds_image(const mi355_ctx *ctx, size_t lds_bytes, size_t n_groups, size_t nt) {
+  size_t per_cu = kLdsBytes / (lds_bytes ? lds_bytes : 1);
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 4) per_cu = 4;
+  const size_t grid = (size_t)ctx->n_cu * per_cu, max_blocks = (n_groups + nt - 1) / nt;
+  return (unsigned)(grid > max_blocks ? max_blocks : grid);
+}
+// launches `kern` with `lds` bytes of dynamic LDS, which it first allows the kernel to have
+template <class Kernel, class... Args>
+static int launch_lds(mi355_ctx *ctx, Kernel kern, const char *what, unsigned grid, int nt, size_t lds, Args... args) {
+  int rc = check_hip(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(max dynamic LDS)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3((unsigned)nt), lds, ctx->stream, args...);
+  return check_hip(ctx, hipGetLastError(), what);
+}
+
+// The three-pass whole-plane RGBA8 kernels take the same arguments up to the plane size; `tail` is what each adds.
+template <class Kernel, class... Tail>
+static int launch_plane(mi355_ctx *ctx, Kernel kern, const char *what, int nt, const uint4 *src, uint4 *dst, size_t n_groups, Tail... tail) {
+  const LutDevice &L = ctx->lut;
+  return launch_lds(ctx, kern, what, grid_block_per_cu(ctx, n_groups), nt, L.lds_bytes, src, dst, n_groups, (const float *)L.d_planar, (const uint32_t *)L.d_axis,
+                    L.lds_Sy, L.lds_Sz, (uint32_t)L.planar_plane_floats, tail...);
+}
+// (each of the three has a form with the strides of the 33^3 LUT as constants)
+template <int NT, int P4, int HSV = kNoHsv>
+static int launch_lds_variant(mi355_ctx *ctx, const uint4 *src, uint4 *dst, size_t n_groups, const HsvK &hk = HsvK{}) {
+  const int flags = (ctx->lut.lds_all_resident ? 1 : 0) | (ctx->lut_stagger << 8);
+  auto go = [&](auto kern) { return launch_plane(ctx, kern, "colorlut3d_lds kernel launch", NT, src, dst, n_groups, flags, hk); };
+  return ctx->lut.size == 33 ? go(colorlut3d_lds_kernel<NT, P4, 33, HSV>) : go(colorlut3d_lds_kernel<NT, P4, 0, HSV>);
+}
+template <int NT, int P4>
+static int launch_lean_variant(mi355_ctx *ctx, const uint4 *src, uint4 *dst, size_t n_groups) {
+  auto go = [&](auto kern) { return launch_plane(ctx, kern, "colorlut3d_lean kernel launch", NT, src, dst, n_groups, ctx->lut.lds_all_resident ? 1 : 0); };
+  return ctx->lut.size == 33 ? go(colorlut3d_lean_kernel<NT, P4, 33>) : go(colorlut3d_lean_kernel<NT, P4, 0>);
+}
+template <int NT, int P4, int HSV, bool LATE_LOAD = false>
+static int launch_pipe_variant(mi355_ctx *ctx, const uint4 *src, uint4 *dst, size_t n_groups, const HsvK &hk) {
+  auto go = [&](auto kern) { return launch_plane(ctx, kern, "hsv_colorlut3d_pipe kernel launch", NT, src, dst, n_groups, ctx->lut.lds_all_resident ? 1 : 0, hk); };
+  return ctx->lut.size == 33 ? go(hsv_colorlut3d_pipe_kernel<NT, P4, 33, HSV, LATE_LOAD>) : go(hsv_colorlut3d_pipe_kernel<NT, P4, 0, HSV, LATE_LOAD>);
+}
+
+// Is the RGBA8 3D LDS kernel applicable to this geometry? (packed)
+static bool lds3d_rgba_applicable(const mi355_ctx *ctx, const LutFrames &F, size_t *n_groups) {
+  return ctx->lut.is3d && ctx->lut.lds_ok && !ctx->force_generic && packed_geom(F, 4, n_groups);
 }
 
 template <int HSV>
 static int launch_fused_variant(mi355_ctx *ctx, const uint4 *s, uint4 *d, size_t n_groups, const HsvK &hk) {
-  const bool s33 = ctx->lut.size == 33;
   // MI355_FLAG_FUSED_VARIANT 1: software-pipelined kernel (hsv of the next tile under the plane DMA). Measured on
   // 8x4K: 0.316 ms smooth / 0.476 ms noise at 1024x2 vs 0.330 / 0.435 ms for the inline kernel at 1024x3; the
   // 1024x3 pipelined tiling spills at the 128-VGPR cap (0.49 ms), so the inline kernel stays the default.
-  if (ctx->fused_variant == 1)
-    return s33 ? launch_pipe_variant<1024, 2, 33, HSV>(ctx, s, d, n_groups, hk) : launch_pipe_variant<1024, 2, 0, HSV>(ctx, s, d, n_groups, hk);
-  return s33 ? launch_lds_variant<1024, 3, 33, HSV>(ctx, s, d, n_groups, hk) : launch_lds_variant<1024, 3, 0, HSV>(ctx, s, d, n_groups, hk);
+  if (ctx->fused_variant == 1) return launch_pipe_variant<1024, 2, HSV>(ctx, s, d, n_groups, hk);
+  return launch_lds_variant<1024, 3, HSV>(ctx, s, d, n_groups, hk);
 }
 
-// hsvfilter followed by colorlut on RGBA frames. One fused launch when the 3D LDS kernel applies; otherwise the
-// two element kernels back to back (copy src -> dst, hsvfilter in place on dst, colorlut dst -> dst; every colorlut
+// ---- the brick route: ONE statement of "brick kernel with 32 or 64 sets, block-shared cache, or on to the three-pass kernel"
+// for the three places that reach the brick-cache kernel. What differs between them is a member of BrickSite, stated where the
+// route is called.
+struct BrickSite {
+  int fmt64;                      // pixel format as brick_launch takes it: 0 RGBA8, 1 RGBA64_LE, 2 RGBA64_BE
+  const mi355_hsv_settings *hs;   // the fused hsvfilter -> colorlut form, or nullptr
+  bool admitted;                  // MI355_FLAG_LUT_VARIANT (and what else the site asks) admits the brick kernel
+  bool three_pass_ok;             // the site's three-pass kernel takes this geometry: where the watch's level 2 goes
+  bool build;                     // a table build is in progress (table_ensure)
+  bool shared_cache;              // the block-shared cache is a candidate: MI355_FLAG_BRICK_SETS 512 and level 1 of the watch
+  bool sets_verbatim;             // a pinned MI355_FLAG_BRICK_SETS reaches brick_launch as it is (and 48 is named); otherwise 32 unless 64
+  const char *name32, *name48, *name64;  // last_kernel by the sets launched (the site's suffix: none, <HSV>, <RGBA64>)
+};
+
+// true: the launch has been served (or has failed) and *rc is its status. false: it goes on to the site's three-pass kernel
+// (not admitted, not the brick kernel's geometry, or level 2 of the content watch).
+static bool brick_route(mi355_ctx *ctx, const LutFrames &F, const BrickSite &S, int *rc) {
+  if (!S.admitted || ctx->force_generic ||
+      !brick_applicable(ctx->lut.brick, F.src, F.src_pitch, F.src_stride, F.dst, F.dst_pitch, F.dst_stride, F.n_frames, F.width, F.height, S.fmt64 ? 8 : 4))
+    return false;
+  BrickLut &B = ctx->lut.brick;
+  auto shared_cache = [&]() { return shared_launch(ctx, B, F.src, F.src_stride, F.dst, F.dst_stride, F.n_frames, F.width, F.height); };
+  // MI355_FLAG_BRICK_SETS = 512: the block-shared cache (round 4), pinned
+  if (S.shared_cache && ctx->brick_sets == 512 && shared_applicable(ctx, F.width, F.dst_stride, F.n_frames, F.height)) {
+    brick_mark_unwatched(B);
+    ctx->lut.last_kernel = "colorlut3d_shared_kernel";
+    *rc = shared_cache();
+    return true;
+  }
+  // MI355_FLAG_BRICK_SETS pins the cache geometry; 0 lets the content watch pick (and leave for the three-pass kernel)
+  const bool pinned = ctx->lut_variant == 7 || !S.three_pass_ok || ctx->brick_sets != 0;
+  // a table build runs over the all-colours frame, which is as hostile to the brick cache as noise: three-pass kernel
+  // when it applies, and no entry in the stream's content watch either way
+  const bool watched = !pinned && !S.build;
+  // level 1 of the watch is the block-shared cache where the launch is large enough for one
+  bool small = false;
+  const bool shared1 = S.shared_cache && watched && shared_applicable(ctx, F.width, F.dst_stride, F.n_frames, F.height, &small);
+  int level = pinned ? (ctx->brick_sets == 64 ? 1 : 0) : (S.build ? 2 : brick_choose(B, shared1 && small ? 1 : 0));
+  if (level == 2 && !S.three_pass_ok) level = 1;
+  if (level == 2 || !watched) brick_mark_unwatched(B);
+  if (level == 2) return false;
+  const int sets = S.sets_verbatim && pinned && ctx->brick_sets ? ctx->brick_sets : (level ? 64 : 32);
+  const bool shared = shared1 && level == 1;
+  ctx->lut.last_kernel = shared ? "colorlut3d_shared_kernel" : (sets == 64 ? S.name64 : (sets == 48 ? S.name48 : S.name32));
+  *rc = watched ? brick_before_launch(ctx, B, level) : MI355_OK;
+  if (*rc) return true;
+  *rc = shared ? shared_cache() : brick_launch(ctx, B, F.src, F.src_stride, F.dst, F.dst_stride, F.n_frames, F.width, F.height, S.hs, sets, S.fmt64);
+  if (!*rc && watched) *rc = brick_after_launch(ctx, B, F.pixels(), level, shared1);
+  return true;
+}
+
+// hsvfilter followed by colorlut on RGBA frames. One fused launch when the brick kernel or the 3D LDS kernel applies; otherwise
+// the two element kernels back to back (copy src -> dst, hsvfilter in place on dst, colorlut dst -> dst; every colorlut
 // kernel reads a pixel before it writes the same pixel, so in-place is safe).
-static int launch_colorlut_compute(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst, size_t dst_pitch,
-                                  int dst_stride, int n_frames, int width, int height, int format);
+static int launch_colorlut_compute(mi355_ctx *ctx, const LutFrames &F, int format);
 
 // `plain`: the colorlut half of the unfused fallback uses the compute kernel directly (table builds)
-static int launch_hsv_colorlut_compute(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst,
-                                       size_t dst_pitch, int dst_stride, int n_frames, int width, int height,
-                                       const mi355_hsv_settings &hs, bool plain) {
+// (Both compute functions are reached through launch_colorlut / launch_hsv_colorlut and table_ensure only: a LUT is loaded and F is not empty.)
+static int launch_hsv_colorlut_compute(mi355_ctx *ctx, const LutFrames &F, const mi355_hsv_settings &hs, bool plain) {
   const LutDevice &L = ctx->lut;
-  if (!L.loaded) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "No LUT configured");
-  if (n_frames <= 0 || width <= 0 || height <= 0) return MI355_OK;
   size_t n_groups = 0;
-  const bool three_pass_ok = lds3d_rgba_applicable(ctx, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, &n_groups);
-  const int lv = ctx->lut_variant;
-  if (!ctx->force_generic && lv != 3 && lv != 1 && lv != 2 && ctx->fused_variant == 0 &&
-      brick_applicable(ctx->lut.brick, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height)) {
-    BrickLut &B = ctx->lut.brick;
-    const bool build = ctx->lut.building_table;
-    const bool pinned = lv == 7 || !three_pass_ok || ctx->brick_sets != 0;
-    int level = pinned ? (ctx->brick_sets == 64 ? 1 : 0) : (build ? 2 : brick_choose(B));
-    if (level == 2 && !three_pass_ok) level = 1;
-    if (level == 2 || build || pinned) brick_mark_unwatched(B);
-    if (level < 2) {
-      const int sets = pinned && ctx->brick_sets ? ctx->brick_sets : (level ? 64 : 32);
-      ctx->lut.last_kernel = sets == 64 ? "colorlut3d_brick_kernel<HSV> (64 sets)" : (sets == 48 ? "colorlut3d_brick_kernel<HSV> (48 sets)" : "colorlut3d_brick_kernel<HSV>");
-      int rc = (build || pinned) ? MI355_OK : brick_before_launch(ctx, B, level);
-      if (rc) return rc;
-      rc = brick_launch(ctx, B, d_src, src_stride, d_dst, dst_stride, n_frames, width, height, &hs, sets);
-      if (rc || build || pinned) return rc;
-      return brick_after_launch(ctx, B, (unsigned long long)width * height * n_frames, level);
-    }
-  }
+  int rc;
+  const bool three_pass_ok = lds3d_rgba_applicable(ctx, F, &n_groups);
+  const int v = ctx->lut_variant;
+  BrickSite site{};
+  site.hs = &hs;
+  site.admitted = v != 1 && v != 2 && v != 3 && ctx->fused_variant == 0;  // every variant but the three-pass ones: 8 and 9 reach the brick kernel here, not in the plain form
+  site.three_pass_ok = three_pass_ok;
+  site.build = L.building_table;  // read by the two RGBA8 forms
+  site.shared_cache = false;      // the block-shared cache has no fused form
+  site.sets_verbatim = true;      // BRICK_SETS 48 (and 512, which brick_launch takes for 32) as it is
+  site.name32 = "colorlut3d_brick_kernel<HSV>"; site.name48 = "colorlut3d_brick_kernel<HSV> (48 sets)"; site.name64 = "colorlut3d_brick_kernel<HSV> (64 sets)";
+  if (brick_route(ctx, F, site, &rc)) return rc;
   if (three_pass_ok) {
     ctx->lut.last_kernel = "colorlut3d_lds_kernel<HSV>";
     const HsvK hk{hs.hue_shift, hs.saturation_mul, hs.saturation_off, hs.value_mul, hs.value_off};
-    const uint4 *s = (const uint4 *)d_src;
-    uint4 *d = (uint4 *)d_dst;
+    const uint4 *s = (const uint4 *)F.src;
+    uint4 *d = (uint4 *)F.dst;
     switch (hsv_variant_for(hs, false)) {
       case -1: return launch_fused_variant<-1>(ctx, s, d, n_groups, hk);
       case 0: return launch_fused_variant<0>(ctx, s, d, n_groups, hk);
@@ -1345,208 +1387,86 @@ static int launch_hsv_colorlut_compute(mi355_ctx *ctx, const uint8_t *d_src, siz
   }
   PixFmt fmt;
   pixfmt_of(MI355_FMT_RGBA, &fmt);
-  if (d_src != d_dst) {
-    for (int f = 0; f < n_frames; f++) {
-      int rc = check_hip(ctx, hipMemcpy2DAsync(d_dst + (size_t)f * dst_pitch, (size_t)dst_stride, d_src + (size_t)f * src_pitch, (size_t)src_stride,
-                                               (size_t)width * 4, (size_t)height, hipMemcpyDeviceToDevice, ctx->stream),
-                         "hsv+colorlut: device copy");
+  if (F.src != F.dst) {
+    for (int f = 0; f < F.n_frames; f++) {
+      rc = check_hip(ctx, hipMemcpy2DAsync(F.dst + (size_t)f * F.dst_pitch, (size_t)F.dst_stride, F.src + (size_t)f * F.src_pitch, (size_t)F.src_stride,
+                                           (size_t)F.width * 4, (size_t)F.height, hipMemcpyDeviceToDevice, ctx->stream),
+                     "hsv+colorlut: device copy");
       if (rc) return rc;
     }
   }
-  int rc = launch_hsvfilter_compute(ctx, d_dst, n_frames, dst_pitch, width, height, dst_stride, fmt, hs);
+  rc = launch_hsvfilter_compute(ctx, F.dst, F.n_frames, F.dst_pitch, F.width, F.height, F.dst_stride, fmt, hs);
   if (rc) return rc;
-  if (plain) return launch_colorlut_compute(ctx, d_dst, dst_pitch, dst_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, MI355_FMT_RGBA);
-  return launch_colorlut(ctx, d_dst, dst_pitch, dst_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, MI355_FMT_RGBA);
+  if (plain) return launch_colorlut_compute(ctx, LutFrames{F.dst, F.dst_pitch, F.dst_stride, F.dst, F.dst_pitch, F.dst_stride, F.n_frames, F.width, F.height}, MI355_FMT_RGBA);
+  return launch_colorlut(ctx, F.dst, F.dst_pitch, F.dst_stride, F.dst, F.dst_pitch, F.dst_stride, F.n_frames, F.width, F.height, MI355_FMT_RGBA);
 }
 
-static int launch_colorlut_compute(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst,
-                    size_t dst_pitch, int dst_stride, int n_frames, int width, int height, int format) {
+// ---- the routes of launch_colorlut_compute, one function each
+static int launch_1d_rgba8(mi355_ctx *ctx, const LutFrames &F, size_t n_vec) {
+  constexpr int NT = 512;
   const LutDevice &L = ctx->lut;
-  if (!L.loaded) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "No LUT configured");
-  if (n_frames <= 0 || width <= 0 || height <= 0) return MI355_OK;
+  ctx->lut.last_kernel = "colorlut1d_lds_kernel";
+  return launch_lds(ctx, colorlut1d_lds_kernel<NT>, "colorlut1d_lds kernel launch", grid_by_lds_image(ctx, L.lds_bytes, n_vec, NT), NT, L.lds_bytes,
+                    (const uint4 *)F.src, (uint4 *)F.dst, n_vec, (const uint32_t *)L.d_axis, (uint32_t)(L.lds_bytes / 4));
+}
+
+static int launch_three_pass_rgba8(mi355_ctx *ctx, const LutFrames &F, size_t n_groups) {
+  ctx->lut.last_kernel = "colorlut3d_lds_kernel";
+  const uint4 *s = (const uint4 *)F.src;
+  uint4 *d = (uint4 *)F.dst;
+  constexpr int NT = 1024, P4 = 3;
+  // lean-state kernel (2 registers per pixel, 32 pixels per lane). Measured on 8x4K: 0.243-0.258 ms smooth /
+  // 0.440 ms noise vs 0.249-0.253 / 0.402 ms for the default: the larger tile amortises staging and barriers, the
+  // three extra axis reads per pixel and pass give it back. Not the default.
+  if (ctx->lut_variant == 2) return launch_lean_variant<1024, 8>(ctx, s, d, n_groups);
+  // MI355_FLAG_LUT_VARIANT 1: next tile's pixels prefetched before the last pass
+  if (ctx->lut_variant == 1) return launch_pipe_variant<NT, P4, kNoHsv, true>(ctx, s, d, n_groups, HsvK{});
+  return launch_lds_variant<NT, P4>(ctx, s, d, n_groups);
+}
+
+static int launch_three_pass_rgba64(mi355_ctx *ctx, const LutFrames &F, size_t n_groups, bool le) {
+  constexpr int NT = 1024, P2 = 4;
+  const LutDevice &L = ctx->lut;
+  ctx->lut.last_kernel = "colorlut3d_lds64_kernel";
+  Lut64K k64;
+  for (int c = 0; c < 3; c++) { k64.scale[c] = L.scale[c]; k64.offset[c] = L.offset[c]; }
+  k64.sm1 = (float)L.size - 1.0f;
+  k64.sy4 = 4u * (uint32_t)L.lds_Sy; k64.sz4 = 4u * (uint32_t)L.lds_Sz; k64.plane_base = kAxisTableBytes; k64.S = L.size;
+  auto go = [&](auto kern) {
+    return launch_lds(ctx, kern, "colorlut3d_lds64 kernel launch", grid_block_per_cu(ctx, n_groups), NT, kAxisTableBytes + 4 * L.planar_plane_floats,
+                      (const uint4 *)F.src, (uint4 *)F.dst, n_groups, (const float *)L.d_planar, (const uint32_t *)L.d_axis, (uint32_t)L.planar_plane_floats, k64);
+  };
+  return le ? go(colorlut3d_lds64_kernel<NT, P2, true>) : go(colorlut3d_lds64_kernel<NT, P2, false>);
+}
+
+static int launch_1d_rgba64(mi355_ctx *ctx, const LutFrames &F, size_t n_groups, bool le) {
+  constexpr int NT = 512;
+  const LutDevice &L = ctx->lut;
+  ctx->lut.last_kernel = "colorlut1d_lds64_kernel";
+  Lut1d64K k1;
+  for (int c = 0; c < 3; c++) { k1.scale[c] = L.scale[c]; k1.offset[c] = L.offset[c]; }
+  k1.sm1 = (float)L.size - 1.0f;
+  k1.table_bytes = ((uint32_t)L.size + 1u) * 4u;
+  auto go = [&](auto kern) {
+    return launch_lds(ctx, kern, "colorlut1d_lds64 kernel launch", grid_by_lds_image(ctx, L.lds_bytes, n_groups, NT), NT, L.lds_bytes, (const uint4 *)F.src,
+                      (uint4 *)F.dst, n_groups, (const uint32_t *)L.d_axis, (uint32_t)(L.lds_bytes / 4), k1);
+  };
+  return le ? go(colorlut1d_lds64_kernel<NT, true>) : go(colorlut1d_lds64_kernel<NT, false>);
+}
+
+// any geometry, any LUT, straight from the cells as the reference stores them
+static int launch_rows(mi355_ctx *ctx, const LutFrames &F, int format) {
+  const LutDevice &L = ctx->lut;
   LutK k;
   for (int c = 0; c < 3; c++) { k.scale[c] = L.scale[c]; k.offset[c] = L.offset[c]; }
   k.size = L.size;
-
-  const bool rgba8 = (format == MI355_FMT_RGBA);
-  if (rgba8 && !L.is3d && L.lds_ok && !ctx->force_generic) {
-    const size_t row_bytes = (size_t)width * 4;
-    const bool contiguous = (size_t)src_stride == row_bytes && (size_t)dst_stride == row_bytes &&
-                            (n_frames == 1 || (src_pitch == row_bytes * (size_t)height && dst_pitch == row_bytes * (size_t)height));
-    const size_t total_bytes = row_bytes * (size_t)height * (size_t)n_frames;
-    if (contiguous && ((uintptr_t)d_src % 16 == 0) && ((uintptr_t)d_dst % 16 == 0) && (total_bytes % 16 == 0)) {
-      constexpr int NT = 512;
-      ctx->lut.last_kernel = "colorlut1d_lds_kernel";
-      auto kern = colorlut1d_lds_kernel<NT>;
-      int rc = check_hip(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes),
-                         "hipFuncSetAttribute(max dynamic LDS)");
-      if (rc) return rc;
-      const size_t n_vec = total_bytes / 16;
-      // blocks per CU limited by the LDS image; a few hundred pixels per lane amortise the table staging
-      size_t per_cu = kLdsBytes / (L.lds_bytes ? L.lds_bytes : 1);
-      if (per_cu < 1) per_cu = 1;
-      if (per_cu > 4) per_cu = 4;
-      size_t grid = (size_t)ctx->n_cu * per_cu;
-      const size_t max_blocks = (n_vec + NT - 1) / NT;
-      if (grid > max_blocks) grid = max_blocks;
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), L.lds_bytes, ctx->stream, (const uint4 *)d_src, (uint4 *)d_dst, n_vec,
-                         (const uint32_t *)L.d_axis, (uint32_t)(L.lds_bytes / 4));
-      return check_hip(ctx, hipGetLastError(), "colorlut1d_lds kernel launch");
-    }
-  }
-  {
-    size_t n_groups = 0;
-    // MI355_FLAG_LUT_VARIANT among the interpolating kernels: 0 / 6 = brick-cache kernel with the content watch handing
-    // noise-like streams to the three-pass whole-plane kernel (brick_choose); 7 = brick kernel only; 3 = three-pass only;
-    // 1 / 2 = the three-pass kernel's late-prefetch / lean-state experiments.
-    const int v = ctx->lut_variant;
-    const bool three_pass_ok = rgba8 && lds3d_rgba_applicable(ctx, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, &n_groups);
-    if (rgba8 && !ctx->force_generic && (v == 0 || v == 6 || v == 7 || v == 4 || v == 5) &&
-        brick_applicable(ctx->lut.brick, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height)) {
-      BrickLut &B = ctx->lut.brick;
-      // a table build runs over the all-colours frame, which is as hostile to the brick cache as noise: three-pass kernel
-      // when it applies, and no entry in the stream's content watch either way
-      const bool build = ctx->lut.building_table;
-      // MI355_FLAG_BRICK_SETS = 512: the block-shared cache (round 4), pinned
-      if (ctx->brick_sets == 512 && shared_applicable(ctx, width, dst_stride, n_frames, height)) {
-        brick_mark_unwatched(B);
-        ctx->lut.last_kernel = "colorlut3d_shared_kernel";
-        return shared_launch(ctx, B, d_src, src_stride, d_dst, dst_stride, n_frames, width, height);
-      }
-      // MI355_FLAG_BRICK_SETS pins the cache geometry; 0 lets the content watch pick (and leave for the three-pass kernel)
-      const bool pinned = v == 7 || !three_pass_ok || ctx->brick_sets != 0;
-      // level 1 of the watch is the block-shared cache where the launch is large enough for one
-      bool small = false;
-      const bool shared1 = !pinned && !build && shared_applicable(ctx, width, dst_stride, n_frames, height, &small);
-      int level = pinned ? (ctx->brick_sets == 64 ? 1 : 0) : (build ? 2 : brick_choose(B, shared1 && small ? 1 : 0));
-      if (level == 2 && !three_pass_ok) level = 1;
-      if (level == 2 || build || pinned) brick_mark_unwatched(B);
-      if (level < 2) {
-        const int sets = pinned && ctx->brick_sets ? ctx->brick_sets : (level ? 64 : 32);
-        const bool shared = shared1 && level == 1;
-        ctx->lut.last_kernel = shared ? "colorlut3d_shared_kernel" : (sets == 64 ? "colorlut3d_brick_kernel (64 sets)" : (sets == 48 ? "colorlut3d_brick_kernel (48 sets)" : "colorlut3d_brick_kernel"));
-        int rc = (build || pinned) ? MI355_OK : brick_before_launch(ctx, B, level);
-        if (rc) return rc;
-        rc = shared ? shared_launch(ctx, B, d_src, src_stride, d_dst, dst_stride, n_frames, width, height)
-                    : brick_launch(ctx, B, d_src, src_stride, d_dst, dst_stride, n_frames, width, height, nullptr, sets);
-        if (rc || build || pinned) return rc;
-        return brick_after_launch(ctx, B, (unsigned long long)width * height * n_frames, level, shared1);
-      }
-    }
-    if (three_pass_ok) {
-      ctx->lut.last_kernel = "colorlut3d_lds_kernel";
-      const uint4 *s = (const uint4 *)d_src;
-      uint4 *d = (uint4 *)d_dst;
-      constexpr int NT = 1024, P4 = 3;
-      // lean-state kernel (2 registers per pixel, 32 pixels per lane). Measured on 8x4K: 0.243-0.258 ms smooth /
-      // 0.440 ms noise vs 0.249-0.253 / 0.402 ms for the default: the larger tile amortises staging and barriers, the
-      // three extra axis reads per pixel and pass give it back. Not the default.
-      if (ctx->lut_variant == 2) return launch_lean_variant<1024, 8>(ctx, s, d, n_groups);
-      if (ctx->lut_variant == 1)  // MI355_FLAG_LUT_VARIANT: next tile's pixels prefetched before the last pass
-        return L.size == 33 ? launch_pipe_variant<NT, P4, 33, kNoHsv, true>(ctx, s, d, n_groups, HsvK{})
-                            : launch_pipe_variant<NT, P4, 0, kNoHsv, true>(ctx, s, d, n_groups, HsvK{});
-      if (L.size == 33) return launch_lds_variant<NT, P4, 33>(ctx, s, d, n_groups);
-      return launch_lds_variant<NT, P4, 0>(ctx, s, d, n_groups);
-    }
-  }
-
-  // RGBA64 with a 3D LUT: the brick-cache kernel (round 3: coordinates computed instead of tabled) under the same content
-  // watch as RGBA8 - noise-like streams go on to the three-pass 16-bit kernel below
-  if ((format == MI355_FMT_RGBA64_LE || format == MI355_FMT_RGBA64_BE) && L.is3d && !ctx->force_generic && ctx->lut_variant != 3 &&
-      brick_applicable(ctx->lut.brick, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, 8)) {
-    BrickLut &B = ctx->lut.brick;
-    const size_t row_bytes64 = (size_t)width * 8;
-    const bool three_pass64_ok = L.lds_ok && (size_t)src_stride == row_bytes64 && (size_t)dst_stride == row_bytes64 &&
-                                 (n_frames == 1 || (src_pitch == row_bytes64 * (size_t)height && dst_pitch == row_bytes64 * (size_t)height));
-    const bool pinned = ctx->lut_variant == 7 || !three_pass64_ok || ctx->brick_sets != 0;
-    int level = pinned ? (ctx->brick_sets == 64 ? 1 : 0) : brick_choose(B);
-    if (level == 2 && !three_pass64_ok) level = 1;
-    if (level == 2 || pinned) brick_mark_unwatched(B);
-    if (level < 2) {
-      const int sets = pinned && ctx->brick_sets == 64 ? 64 : (level ? 64 : 32);
-      ctx->lut.last_kernel = sets == 64 ? "colorlut3d_brick_kernel<RGBA64> (64 sets)" : "colorlut3d_brick_kernel<RGBA64>";
-      int rc = pinned ? MI355_OK : brick_before_launch(ctx, B, level);
-      if (rc) return rc;
-      rc = brick_launch(ctx, B, d_src, src_stride, d_dst, dst_stride, n_frames, width, height, nullptr, sets, format == MI355_FMT_RGBA64_LE ? 1 : 2);
-      if (rc || pinned) return rc;
-      return brick_after_launch(ctx, B, (unsigned long long)width * height * n_frames, level);
-    }
-  }
-
-  if ((format == MI355_FMT_RGBA64_LE || format == MI355_FMT_RGBA64_BE) && L.is3d && L.lds_ok && !ctx->force_generic) {
-    const size_t row_bytes = (size_t)width * 8;
-    const bool contiguous = (size_t)src_stride == row_bytes && (size_t)dst_stride == row_bytes &&
-                            (n_frames == 1 || (src_pitch == row_bytes * (size_t)height && dst_pitch == row_bytes * (size_t)height));
-    const size_t total_bytes = row_bytes * (size_t)height * (size_t)n_frames;
-    if (contiguous && ((uintptr_t)d_src % 16 == 0) && ((uintptr_t)d_dst % 16 == 0) && (total_bytes % 16 == 0)) {
-      constexpr int NT = 1024, P2 = 4;
-      ctx->lut.last_kernel = "colorlut3d_lds64_kernel";
-      Lut64K k64;
-      for (int c = 0; c < 3; c++) { k64.scale[c] = L.scale[c]; k64.offset[c] = L.offset[c]; }
-      k64.sm1 = (float)L.size - 1.0f;
-      k64.sy4 = 4u * (uint32_t)L.lds_Sy; k64.sz4 = 4u * (uint32_t)L.lds_Sz; k64.plane_base = kAxisTableBytes; k64.S = L.size;
-      const size_t n_groups = total_bytes / 16;
-      size_t grid = (size_t)ctx->n_cu;
-      const size_t min_blocks = (n_groups + 255) / 256;
-      if (grid > min_blocks) grid = min_blocks;
-      if (grid < 1) grid = 1;
-      const size_t lds = kAxisTableBytes + 4 * L.planar_plane_floats;
-      const bool le = format == MI355_FMT_RGBA64_LE;
-      auto kle = colorlut3d_lds64_kernel<NT, P2, true>;
-      auto kbe = colorlut3d_lds64_kernel<NT, P2, false>;
-      int rc = check_hip(ctx, hipFuncSetAttribute(le ? (const void *)kle : (const void *)kbe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                         "hipFuncSetAttribute(max dynamic LDS)");
-      if (rc) return rc;
-      if (le) hipLaunchKernelGGL(kle, dim3((unsigned)grid), dim3(NT), lds, ctx->stream, (const uint4 *)d_src, (uint4 *)d_dst, n_groups,
-                                 (const float *)L.d_planar, (const uint32_t *)L.d_axis, (uint32_t)L.planar_plane_floats, k64);
-      else hipLaunchKernelGGL(kbe, dim3((unsigned)grid), dim3(NT), lds, ctx->stream, (const uint4 *)d_src, (uint4 *)d_dst, n_groups,
-                              (const float *)L.d_planar, (const uint32_t *)L.d_axis, (uint32_t)L.planar_plane_floats, k64);
-      return check_hip(ctx, hipGetLastError(), "colorlut3d_lds64 kernel launch");
-    }
-  }
-
-  if ((format == MI355_FMT_RGBA64_LE || format == MI355_FMT_RGBA64_BE) && !L.is3d && L.lds_ok && !ctx->force_generic) {
-    const size_t row_bytes = (size_t)width * 8;
-    const bool contiguous = (size_t)src_stride == row_bytes && (size_t)dst_stride == row_bytes &&
-                            (n_frames == 1 || (src_pitch == row_bytes * (size_t)height && dst_pitch == row_bytes * (size_t)height));
-    const size_t total_bytes = row_bytes * (size_t)height * (size_t)n_frames;
-    if (contiguous && ((uintptr_t)d_src % 16 == 0) && ((uintptr_t)d_dst % 16 == 0) && (total_bytes % 16 == 0)) {
-      constexpr int NT = 512;
-      ctx->lut.last_kernel = "colorlut1d_lds64_kernel";
-      Lut1d64K k1;
-      for (int c = 0; c < 3; c++) { k1.scale[c] = L.scale[c]; k1.offset[c] = L.offset[c]; }
-      k1.sm1 = (float)L.size - 1.0f;
-      k1.table_bytes = ((uint32_t)L.size + 1u) * 4u;
-      const bool le = format == MI355_FMT_RGBA64_LE;
-      auto kle = colorlut1d_lds64_kernel<NT, true>;
-      auto kbe = colorlut1d_lds64_kernel<NT, false>;
-      int rc = check_hip(ctx, hipFuncSetAttribute(le ? (const void *)kle : (const void *)kbe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes),
-                         "hipFuncSetAttribute(max dynamic LDS)");
-      if (rc) return rc;
-      const size_t n_groups = total_bytes / 16;
-      size_t per_cu = kLdsBytes / (L.lds_bytes ? L.lds_bytes : 1);
-      if (per_cu < 1) per_cu = 1;
-      if (per_cu > 4) per_cu = 4;
-      size_t grid = (size_t)ctx->n_cu * per_cu;
-      const size_t max_blocks = (n_groups + NT - 1) / NT;
-      if (grid > max_blocks) grid = max_blocks;
-      if (le) hipLaunchKernelGGL(kle, dim3((unsigned)grid), dim3(NT), L.lds_bytes, ctx->stream, (const uint4 *)d_src, (uint4 *)d_dst, n_groups,
-                                 (const uint32_t *)L.d_axis, (uint32_t)(L.lds_bytes / 4), k1);
-      else hipLaunchKernelGGL(kbe, dim3((unsigned)grid), dim3(NT), L.lds_bytes, ctx->stream, (const uint4 *)d_src, (uint4 *)d_dst, n_groups,
-                              (const uint32_t *)L.d_axis, (uint32_t)(L.lds_bytes / 4), k1);
-      return check_hip(ctx, hipGetLastError(), "colorlut1d_lds64 kernel launch");
-    }
-  }
-
   ctx->lut.last_kernel = "colorlut_rows_kernel";
-  const size_t total = (size_t)width * (size_t)height * (size_t)n_frames;
-  size_t blocks = (total + 255) / 256;
-  const size_t cap = (size_t)ctx->n_cu * 8;
-  if (blocks > cap) blocks = cap;
+  const size_t total = (size_t)F.width * (size_t)F.height * (size_t)F.n_frames;
+  const size_t blocks = std::min((total + 255) / 256, (size_t)ctx->n_cu * 8);
   dim3 g((unsigned)blocks), b(256);
-#define MI355_ROWS(IS3D, B16, LE)                                                                               \
-  hipLaunchKernelGGL((colorlut_rows_kernel<IS3D, B16, LE>), g, b, 0, ctx->stream, d_src, src_pitch, src_stride, \
-                     d_dst, dst_pitch, dst_stride, n_frames, width, height, (const float *)L.d_cells, k)
+#define MI355_ROWS(IS3D, B16, LE)                                                                                   \
+  hipLaunchKernelGGL((colorlut_rows_kernel<IS3D, B16, LE>), g, b, 0, ctx->stream, F.src, F.src_pitch, F.src_stride, \
+                     F.dst, F.dst_pitch, F.dst_stride, F.n_frames, F.width, F.height, (const float *)L.d_cells, k)
   if (format == MI355_FMT_RGBA) {
     if (L.is3d) MI355_ROWS(true, false, true); else MI355_ROWS(false, false, true);
   } else if (format == MI355_FMT_RGBA64_LE) {
@@ -1560,6 +1480,63 @@ static int launch_colorlut_compute(mi355_ctx *ctx, const uint8_t *d_src, size_t 
   return check_hip(ctx, hipGetLastError(), "colorlut rows kernel launch");
 }
 
+// The interpolating ("compute") kernels: the routes in the order they are tried, each one condition and one call. A route that
+// does not take the launch leaves it to the next; MI355_FLAG_FORCE_GENERIC 1 closes all but the last.
+//   1  1D LUT, RGBA8, packed: colorlut1d_lds_kernel (no flag pins it)
+//   2  3D LUT, RGBA8, rows padded or not: the brick route. MI355_FLAG_LUT_VARIANT 0 / 6 = brick-cache kernel with the content
+//      watch handing noise-like streams to route 3 (brick_choose); 7 = brick kernel only; 4 / 5 come here when the table path
+//      has refused the geometry. MI355_FLAG_BRICK_SETS 32 / 48 / 64 pins the cache geometry, 512 the block-shared cache
+//   3  3D LUT, RGBA8, packed: the three-pass whole-plane kernel. LUT_VARIANT 3 = this route only (8 / 9 too, where the table path
+//      has refused the launch); 1 / 2 = its late-prefetch / lean-state experiments
+//   4  3D LUT, RGBA64, rows padded or not: the brick route (round 3: coordinates computed instead of tabled) under the same content
+//      watch - noise-like streams go on to route 5. Every LUT_VARIANT but 3; 7 = brick kernel only; BRICK_SETS 64 pins 64 sets,
+//      every other value but 0 pins 32
+//   5  3D LUT, RGBA64, packed: colorlut3d_lds64_kernel. LUT_VARIANT 3 = this route only
+//   6  1D LUT, RGBA64, packed: colorlut1d_lds64_kernel
+//   7  everything else: colorlut_rows_kernel. FORCE_GENERIC 1 = this route only
+static int launch_colorlut_compute(mi355_ctx *ctx, const LutFrames &F, int format) {
+  const LutDevice &L = ctx->lut;
+  const bool rgba8 = format == MI355_FMT_RGBA, rgba64 = format == MI355_FMT_RGBA64_LE || format == MI355_FMT_RGBA64_BE, le = format == MI355_FMT_RGBA64_LE;
+  const bool lds = L.lds_ok && !ctx->force_generic;  // the LUT has an LDS image and the flat kernels may use it
+  const int v = ctx->lut_variant;
+  size_t n_groups = 0;
+  int rc;
+
+  if (rgba8 && !L.is3d && lds && packed_geom(F, 4, &n_groups)) return launch_1d_rgba8(ctx, F, n_groups);
+
+  const bool three_pass_ok = rgba8 && lds3d_rgba_applicable(ctx, F, &n_groups);
+  BrickSite site8{};
+  site8.admitted = v == 0 || v == 4 || v == 5 || v == 6 || v == 7;  // not 8 / 9: a geometry the table path refuses goes past the brick kernel in this form (routes 3, 7)
+  site8.three_pass_ok = three_pass_ok;
+  site8.build = L.building_table;  // read by the two RGBA8 forms
+  site8.shared_cache = true;       // plain RGBA8 only: BRICK_SETS 512, level 1 of the watch, min_level / shared1 in brick_choose / brick_after_launch
+  site8.sets_verbatim = true;      // BRICK_SETS 48 reaches brick_launch as 48 and is named "(48 sets)"
+  site8.name32 = "colorlut3d_brick_kernel"; site8.name48 = "colorlut3d_brick_kernel (48 sets)"; site8.name64 = "colorlut3d_brick_kernel (64 sets)";
+  if (rgba8 && brick_route(ctx, F, site8, &rc)) return rc;
+
+  if (three_pass_ok) return launch_three_pass_rgba8(ctx, F, n_groups);
+
+  const bool packed64 = rgba64 && packed_geom(F, 8, &n_groups);
+  BrickSite site64{};
+  site64.fmt64 = le ? 1 : 2;
+  site64.admitted = L.is3d && v != 3;  // every variant but the three-pass one
+  // The test here used to be contiguity alone. Behind brick_applicable (which brick_route asks first) that is the full packed test:
+  // it has required both bases 16-byte aligned and strides that are multiples of 16 B, and with stride == row bytes the total
+  // is stride * height * frames, a multiple of 16 too.
+  site64.three_pass_ok = packed64 && L.lds_ok;
+  site64.build = false;            // RGBA64 does not read building_table (no table is built from RGBA64)
+  site64.shared_cache = false;     // RGBA8 only
+  site64.sets_verbatim = false;    // BRICK_SETS 48 (and 32, 512) launches 32 sets
+  site64.name32 = site64.name48 = "colorlut3d_brick_kernel<RGBA64>"; site64.name64 = "colorlut3d_brick_kernel<RGBA64> (64 sets)";
+  if (rgba64 && brick_route(ctx, F, site64, &rc)) return rc;
+
+  if (packed64 && L.is3d && lds) return launch_three_pass_rgba64(ctx, F, n_groups, le);
+
+  if (packed64 && !L.is3d && lds) return launch_1d_rgba64(ctx, F, n_groups, le);
+
+  return launch_rows(ctx, F, format);
+}
+
 
 // geometry test shared by the table path and the auto-selector: RGBA8 frames on 16-byte-aligned storage, either packed
 // (rows and frames back to back: one flat array of pixel groups) or with padded rows (strides that are multiples of 16 B,
@@ -1569,24 +1546,20 @@ struct Rgba8Geom {
   unsigned sw4 = 0, dw4 = 0;  // row strides in 16-byte groups
   bool packed = false;
 };
-static bool rgba8_geom(const uint8_t *d_src, size_t src_pitch, int src_stride, const uint8_t *d_dst, size_t dst_pitch, int dst_stride, int n_frames,
-                       int width, int height, Rgba8Geom *g) {
-  const size_t row_bytes = (size_t)width * 4;
-  if (((uintptr_t)d_src % 16 != 0) || ((uintptr_t)d_dst % 16 != 0)) return false;
-  const bool packed = (size_t)src_stride == row_bytes && (size_t)dst_stride == row_bytes &&
-                      (n_frames == 1 || (src_pitch == row_bytes * (size_t)height && dst_pitch == row_bytes * (size_t)height));
-  const size_t total_bytes = row_bytes * (size_t)height * (size_t)n_frames;
-  if (packed) {
-    if (total_bytes % 16 != 0) return false;
-    g->n_vec = total_bytes / 16;
+static bool rgba8_geom(const LutFrames &F, Rgba8Geom *g) {
+  const size_t row_bytes = (size_t)F.width * 4;
+  if (((uintptr_t)F.src % 16 != 0) || ((uintptr_t)F.dst % 16 != 0)) return false;
+  if (packed_geom(F, 4, &g->n_vec)) {
     g->sw4 = g->dw4 = (unsigned)(row_bytes / 16);
     g->packed = true;
     return true;
   }
-  // padded rows: only what the tiled kernel takes (whole 16-byte groups per row, width >= 128)
+  // padded rows: only what the tiled kernel takes (whole 16-byte groups per row, width >= 128; this also refuses rows back to
+  // back whose total is no whole number of groups: their width is no multiple of 4)
+  const int width = F.width, src_stride = F.src_stride, dst_stride = F.dst_stride;
   if (width % 4 != 0 || width < 128 || (size_t)src_stride < row_bytes || (size_t)dst_stride < row_bytes || src_stride % 16 != 0 || dst_stride % 16 != 0) return false;
-  if (n_frames != 1 && (src_pitch != (size_t)src_stride * (size_t)height || dst_pitch != (size_t)dst_stride * (size_t)height)) return false;
-  g->n_vec = total_bytes / 16;
+  if (F.n_frames != 1 && (F.src_pitch != (size_t)src_stride * (size_t)F.height || F.dst_pitch != (size_t)dst_stride * (size_t)F.height)) return false;
+  g->n_vec = row_bytes * (size_t)F.height * (size_t)F.n_frames / 16;
   g->sw4 = (unsigned)src_stride / 16;
   g->dw4 = (unsigned)dst_stride / 16;
   g->packed = false;
@@ -1722,8 +1695,8 @@ static int table_ensure(mi355_ctx *ctx, int which, int morton, const mi355_hsv_s
     hipLaunchKernelGGL(table_domain_kernel, dim3(kTableEntries / 256), dim3(256), 0, ctx->stream, tab, morton);
     L.building_table = true;
     const char *serving = L.last_kernel;
-    const int r = which == 0 ? launch_colorlut_compute(ctx, t, 0, 4096 * 4, t, 0, 4096 * 4, 1, 4096, 4096, MI355_FMT_RGBA)
-                             : launch_hsv_colorlut_compute(ctx, t, 0, 4096 * 4, t, 0, 4096 * 4, 1, 4096, 4096, *hs, true);
+    const LutFrames all{t, 0, 4096 * 4, t, 0, 4096 * 4, 1, 4096, 4096};
+    const int r = which == 0 ? launch_colorlut_compute(ctx, all, MI355_FMT_RGBA) : launch_hsv_colorlut_compute(ctx, all, *hs, true);
     L.building_table = false;
     L.last_kernel = serving;
     return r;
@@ -1737,17 +1710,7 @@ static int table_ensure(mi355_ctx *ctx, int which, int morton, const mi355_hsv_s
 
 // `sub`: which kernel reads a Morton table - the gather kernels or the LDS-cached one (colorlut_window.hip)
 enum TableKernel { kTableGather = 0, kTableWindow = 1, kTableEither = 2 };
-template <class Compute, class Ensure, class Table>
-static int auto_launch(mi355_ctx *ctx, AutoPick &A, size_t n_vec, Compute &&compute, Ensure &&ensure, Table &&table);
 static int launch_table_gather(mi355_ctx *ctx, const uint32_t *t, const uint8_t *d_src, uint8_t *d_dst, const Rgba8Geom &geo, int width, size_t rows, int morton);
-static int launch_table_raw(mi355_ctx *ctx, const uint32_t *t, const uint8_t *d_src, uint8_t *d_dst, const Rgba8Geom &geo, int width, size_t rows, int morton,
-                            TableKernel sub = kTableGather, int *last_sub = nullptr);
-static int launch_table(mi355_ctx *ctx, int which, const uint8_t *d_src, uint8_t *d_dst, const Rgba8Geom &geo, int width, size_t rows, int morton,
-                        const mi355_hsv_settings *hs, TableKernel sub = kTableGather) {
-  int rc = table_ensure(ctx, which, morton, hs);
-  if (rc) return rc;
-  return launch_table_raw(ctx, ctx->lut.d_table[which], d_src, d_dst, geo, width, rows, morton, sub, &ctx->lut.last_sub[which]);
-}
 
 // Both kernels read the same table and give the same bytes; which is faster depends on WHERE THE PIXELS COME FROM: the gather
 // kernel wins when its input was just written by the previous launch and is still on-die (Infinity Cache; behind hsvfilter
@@ -1758,7 +1721,7 @@ static int launch_table(mi355_ctx *ctx, int which, const uint8_t *d_src, uint8_t
 // (BENCH_r05 content_sweep.amp4: 35.3 k instead of 37.6 k). The provenance is known exactly (note_written / recently_written):
 // kTableEither is that rule now, with no state, no probes and nothing to settle.
 static int launch_table_raw(mi355_ctx *ctx, const uint32_t *t, const uint8_t *d_src, uint8_t *d_dst, const Rgba8Geom &geo, int width, size_t rows, int morton,
-                            TableKernel sub, int *last_sub) {
+                            TableKernel sub, int *last_sub = nullptr) {
   const bool window_ok = morton && sub != kTableGather && width % 4 == 0 && window_applicable(ctx, (unsigned)width / 4, geo.dw4, rows);
   const size_t src_bytes = (size_t)geo.sw4 * 16 * rows;
   const bool window = window_ok && (sub == kTableWindow || !recently_written(ctx->device, d_src, src_bytes));
@@ -1865,58 +1828,59 @@ constexpr size_t kAutoMinVec = 16384;
 // MI355_FLAG_LUT_VARIANT values that pin a table kernel: 4 linear index, 5 Morton index (gather kernels), 8 Morton index
 // through the LDS-cached kernel (colorlut_window.hip) where the launch is large enough for it
 // 9 = Morton table, the kernel that reads it chosen by measurement as in auto
-static bool table_variant(int v) { return v == 4 || v == 5 || v == 8 || v == 9; }
+bool table_variant(int v) { return v == 4 || v == 5 || v == 8 || v == 9; }
 static TableKernel table_variant_kernel(int v) { return v == 8 ? kTableWindow : (v == 9 ? kTableEither : kTableGather); }
 
-int launch_colorlut(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst,
-                    size_t dst_pitch, int dst_stride, int n_frames, int width, int height, int format) {
-  LutDevice &L = ctx->lut;
-  if (!L.loaded) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "No LUT configured");
-  if (n_frames <= 0 || width <= 0 || height <= 0) return MI355_OK;
-  Rgba8Geom geo;
-  const bool table_ok = format == MI355_FMT_RGBA && !ctx->force_generic &&
-                        rgba8_geom(d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, &geo);
-  const size_t n_vec = geo.n_vec;
-  const int v = ctx->lut_variant;
-  auto compute = [&]() { return launch_colorlut_compute(ctx, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, format); };
-  if (table_ok && table_variant(v))
-    return launch_table(ctx, 0, d_src, d_dst, geo, width, (size_t)n_frames * height, v == 4 ? 0 : 1, nullptr, table_variant_kernel(v));
-  if (!table_ok || v != 0 || n_vec < kAutoMinVec) return compute();
-  return auto_launch(ctx, L.pick[0], n_vec, compute, [&]() { return table_ensure(ctx, 0, 1, nullptr); },
-                     [&]() { return launch_table(ctx, 0, d_src, d_dst, geo, width, (size_t)n_frames * height, 1, nullptr, kTableEither); });
+// The front of the three entry points that can serve a launch from a memoised table (colorlut, hsvfilter -> colorlut, hsvfilter).
+// table_ok: the table kernels take this format and geometry. pin: > 0 a flag pins the table kernel, 0 the measured choice,
+// < 0 the arithmetic kernel. ensure() makes the table current (building it if nobody has it), table() launches the kernel that
+// reads it, compute() the arithmetic one: the callables of auto_launch.
+// A table that depends on settings (seen != nullptr) is only built for settings that have been the same for kStableCalls
+// consecutive calls of the measured choice; `have`: the table the context holds is already the one these settings need.
+// (Settings that change with every call - a hue shift animated by a controller - never settle and keep the arithmetic kernel. Round 6
+// measured the alternative for large launches, a table built per call: 0.219 ms per 8 x 4K against 0.19 - the build is the fused
+// arithmetic over ALL 2^24 colours, the one frame on which every cache of the arithmetic kernels misses: profiles/r06_fused_animated_probe.txt)
+template <class Compute, class Ensure, class Table>
+static int table_front(mi355_ctx *ctx, AutoPick &A, bool table_ok, size_t n_vec, int pin, Settled *seen, const mi355_hsv_settings *hs, int bgr, bool have,
+                       Compute &&compute, Ensure &&ensure, Table &&table) {
+  if (table_ok && pin > 0) {
+    const int rc = ensure();
+    return rc ? rc : table();
+  }
+  if (!table_ok || pin < 0 || n_vec < kAutoMinVec) return compute();
+  const bool settled = !seen || seen->note(*hs, bgr);
+  if (!have && !settled) return compute();
+  if (!have && A.learn > 2) {  // the table kernel's time belongs to the old table only loosely: measure it again
+    A.t_table = 0.0;
+    A.learn = 2;
+  }
+  return auto_launch(ctx, A, n_vec, compute, ensure, table);
 }
 
-// The fused entry point: hsvfilter -> colorlut is also a function of the colour alone, so the same memoisation applies
-// with a table built by the fused compute path under the call's hsv settings. A table is only built for settings that
-// have been the same for kStableCalls consecutive calls (an animated property would otherwise rebuild it every buffer).
-constexpr unsigned kStableCalls = 8;
-int launch_hsv_colorlut(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst,
-                        size_t dst_pitch, int dst_stride, int n_frames, int width, int height,
-                        const mi355_hsv_settings &hs) {
+// colorlut (hs == nullptr: table 0 of the loaded LUT) and the fused entry point (table 1): hsvfilter -> colorlut is also a function
+// of the colour alone, so the same memoisation applies with a table built by the fused compute path under the call's hsv
+// settings, once they have settled.
+static int lut_front(mi355_ctx *ctx, const LutFrames &F, int format, const mi355_hsv_settings *hs) {
   LutDevice &L = ctx->lut;
   if (!L.loaded) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "No LUT configured");
-  if (n_frames <= 0 || width <= 0 || height <= 0) return MI355_OK;
+  if (F.n_frames <= 0 || F.width <= 0 || F.height <= 0) return MI355_OK;
+  const int which = hs ? 1 : 0, v = ctx->lut_variant, morton = v == 4 ? 0 : 1;
+  const TableKernel sub = table_variant(v) ? table_variant_kernel(v) : kTableEither;
   Rgba8Geom geo;
-  const bool table_ok = !ctx->force_generic && rgba8_geom(d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, &geo);
-  const size_t n_vec = geo.n_vec;
-  const int v = ctx->lut_variant;
-  auto compute = [&]() { return launch_hsv_colorlut_compute(ctx, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, hs, false); };
-  if (table_ok && table_variant(v))
-    return launch_table(ctx, 1, d_src, d_dst, geo, width, (size_t)n_frames * height, v == 4 ? 0 : 1, &hs, table_variant_kernel(v));
-  if (!table_ok || v != 0 || n_vec < kAutoMinVec) return compute();
-  if (same_hs(hs, L.seen_hs)) { if (L.seen_stable < kStableCalls) L.seen_stable++; }
-  else { L.seen_hs = hs; L.seen_stable = 0; }
-  const bool have = L.table_ref[1] && L.table_morton[1] == 1 && same_hs(L.table_hs, hs);
-  // (Settings that change with every call - a hue shift animated by a controller - never settle and keep the arithmetic kernel. Round 6
-  // measured the alternative for large launches, a table built per call: 0.219 ms per 8 x 4K against 0.19 - the build is the fused
-  // arithmetic over ALL 2^24 colours, the one frame on which every cache of the arithmetic kernels misses: profiles/r06_fused_animated_probe.txt)
-  if (!have && L.seen_stable < kStableCalls) return compute();
-  if (!have && L.pick[1].learn > 2) {  // the table kernel's time belongs to the old table only loosely: measure it again
-    L.pick[1].t_table = 0.0;
-    L.pick[1].learn = 2;
-  }
-  return auto_launch(ctx, L.pick[1], n_vec, compute, [&]() { return table_ensure(ctx, 1, 1, &hs); },
-                     [&]() { return launch_table(ctx, 1, d_src, d_dst, geo, width, (size_t)n_frames * height, 1, &hs, kTableEither); });
+  const bool table_ok = format == MI355_FMT_RGBA && !ctx->force_generic && rgba8_geom(F, &geo);
+  const bool have = !hs || (L.table_ref[1] && L.table_morton[1] == 1 && same_hs(L.table_hs, *hs));
+  return table_front(ctx, L.pick[which], table_ok, geo.n_vec, table_variant(v) ? 1 : (v == 0 ? 0 : -1), hs ? &L.seen : nullptr, hs, 0, have,
+                     [&]() { return hs ? launch_hsv_colorlut_compute(ctx, F, *hs, false) : launch_colorlut_compute(ctx, F, format); },
+                     [&]() { return table_ensure(ctx, which, morton, hs); },
+                     [&]() { return launch_table_raw(ctx, L.d_table[which], F.src, F.dst, geo, F.width, (size_t)F.n_frames * F.height, morton, sub, &L.last_sub[which]); });
+}
+int launch_colorlut(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst,
+                    size_t dst_pitch, int dst_stride, int n_frames, int width, int height, int format) {
+  return lut_front(ctx, LutFrames{d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height}, format, nullptr);
+}
+int launch_hsv_colorlut(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst,
+                        size_t dst_pitch, int dst_stride, int n_frames, int width, int height, const mi355_hsv_settings &hs) {
+  return lut_front(ctx, LutFrames{d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height}, MI355_FMT_RGBA, &hs);
 }
 
 // ---- frames of several streams in one launch (group.hip)
@@ -2013,27 +1977,12 @@ int launch_hsvfilter(mi355_ctx *ctx, uint8_t *d_data, int n_frames, size_t frame
   // mode 0 (default): only settings that need the GENERIC arithmetic (3x slower than the FAST kernels) are candidates
   const bool candidate = ctx->hsv_table_mode == 1 || ctx->hsv_table_mode == 2 || (ctx->hsv_table_mode == 0 && hsv_variant_for(hs, false, true) < 0);
   const bool table_ok = candidate && !ctx->force_generic && fmt.pixel_stride == 4 && fmt.first == 0 &&
-                        rgba8_geom(d_data, frame_pitch, stride, d_data, frame_pitch, stride, n_frames, width, height, &geo);
-  const size_t n_vec = geo.n_vec;
-  T.last_table = false;
-  if (!table_ok) return compute();
-  const size_t rows = (size_t)n_frames * height;
-  if (ctx->hsv_table_mode == 2) {
-    int rc = hsv_table_ensure(ctx, fmt, hs);
-    T.last_table = true;
-    return rc ? rc : launch_table_raw(ctx, T.d_table, d_data, d_data, geo, width, rows, 1, kTableEither, nullptr);
-  }
-  if (n_vec < kAutoMinVec) return compute();
-  if (same_hs(hs, T.seen_hs) && fmt.bgr == T.seen_bgr) { if (T.seen_stable < kStableCalls) T.seen_stable++; }
-  else { T.seen_hs = hs; T.seen_bgr = fmt.bgr; T.seen_stable = 0; }
+                        rgba8_geom(LutFrames{d_data, frame_pitch, stride, d_data, frame_pitch, stride, n_frames, width, height}, &geo);
+  const int pin = ctx->hsv_table_mode == 2 ? 1 : 0;
+  T.last_table = table_ok && pin;  // (a pinned table counts as in use even when it could not be made)
   const bool have = T.valid && T.bgr == fmt.bgr && same_hs(T.hs, hs);
-  if (!have && T.seen_stable < kStableCalls) return compute();
-  if (!have && T.pick.learn > 2) {
-    T.pick.t_table = 0.0;
-    T.pick.learn = 2;
-  }
-  return auto_launch(ctx, T.pick, n_vec, compute, [&]() { return hsv_table_ensure(ctx, fmt, hs); },
-                     [&]() { T.last_table = true; return launch_table_raw(ctx, T.d_table, d_data, d_data, geo, width, rows, 1, kTableEither, nullptr); });
+  return table_front(ctx, T.pick, table_ok, geo.n_vec, pin, &T.seen, &hs, fmt.bgr, have, compute, [&]() { return hsv_table_ensure(ctx, fmt, hs); },
+                     [&]() { T.last_table = true; return launch_table_raw(ctx, T.d_table, d_data, d_data, geo, width, (size_t)n_frames * height, 1, kTableEither); });
 }
 
 }  // namespace mi355

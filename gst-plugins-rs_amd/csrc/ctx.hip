@@ -463,7 +463,7 @@ int mi355_colorlut_kernel_choice(mi355_ctx *ctx, int fused, int *table_in_use, d
   // times are kept per 16-byte group = 4 pixels
   if (table_in_use)
     *table_in_use = fused == 2 ? (ctx->hsv_table.last_table ? 1 : 0)
-                               : (ctx->lut_variant == 4 || ctx->lut_variant == 5 || ctx->lut_variant == 8 || ctx->lut_variant == 9 || (ctx->lut_variant == 0 && A.t_table > 0.0 && A.table));
+                               : (table_variant(ctx->lut_variant) || (ctx->lut_variant == 0 && A.t_table > 0.0 && A.table));
   if (ms_per_mpx_compute) *ms_per_mpx_compute = A.t_compute * 250000.0;
   if (ms_per_mpx_table) *ms_per_mpx_table = A.t_table * 250000.0;
   return MI355_OK;

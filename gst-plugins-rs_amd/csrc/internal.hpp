@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -19,6 +20,20 @@ namespace mi355 {
 // state (autopick.hpp) plus the two events that bracket a sampled launch (colorlut_kernels.hip: auto_launch).
 struct AutoPick : AutoPolicy {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+// "The settings (and, for hsvfilter alone, the byte order) have been the same for kStableCalls consecutive calls": what a memoised
+// table is built for - an animated property would otherwise rebuild 64 MiB every buffer (colorlut_kernels.hip: table_front).
+constexpr unsigned kStableCalls = 8;
+struct Settled {
+  mi355_hsv_settings hs{};  // settings of the previous call
+  int bgr = 0;              // ... and its byte order
+  unsigned stable = 0;      // for how many calls they have not changed
+  bool note(const mi355_hsv_settings &h, int b = 0) {  // counts this call; true once the settings have stayed
+    if (std::memcmp(&h, &hs, sizeof(h)) == 0 && b == bgr) { if (stable < kStableCalls) stable++; }
+    else { hs = h; bgr = b; stable = 0; }
+    return stable >= kStableCalls;
+  }
 };
 
 struct LutDevice {
@@ -42,8 +57,7 @@ struct LutDevice {
   std::string digest;                          // identifies the loaded LUT (contents, size, kind, domain) in table keys
   int table_morton[2] = {-1, -1};  // layout of the table: 0 linear, 1 Morton, -1 not built
   mi355_hsv_settings table_hs{};   // settings d_table[1] was built for
-  mi355_hsv_settings seen_hs{};    // settings of the previous fused call and for how many calls they have not changed
-  unsigned seen_stable = 0;
+  Settled seen;                    // the fused entry point's settings, call by call
   AutoPick pick[2];                // compute-kernel / table-kernel choice for the two entry points
   int last_sub[2] = {0, 0};        // which kernel read the table last: 0 gather, 1 LDS-cached (colorlut_window.hip) - by provenance of the input
   BrickLut brick;                  // brick form of a 3D LUT for the brick-cache interpolating kernel (colorlut_brick.hip)
@@ -60,9 +74,7 @@ struct HsvTable {
   bool valid = false;
   int bgr = 0;
   mi355_hsv_settings hs{};       // settings the table was built for
-  mi355_hsv_settings seen_hs{};  // settings of the previous call and for how many calls they (and the byte order) have not changed
-  int seen_bgr = 0;
-  unsigned seen_stable = 0;
+  Settled seen;                  // the settings and the byte order, call by call
   bool last_table = false;       // the last launch_hsvfilter call ran the table kernel
   AutoPick pick;
 };
@@ -181,6 +193,7 @@ int launch_colorlut(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int 
 int launch_hsv_colorlut(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride,
                         uint8_t *d_dst, size_t dst_pitch, int dst_stride, int n_frames, int width,
                         int height, const mi355_hsv_settings &hs);
+bool table_variant(int lut_variant);  // the MI355_FLAG_LUT_VARIANT values that pin a memoised-table kernel
 int lut_upload(mi355_ctx *ctx, int is3d, size_t size, const float *table, const float scale[3],
                const float offset[3]);
 void lut_release(mi355_ctx *ctx);

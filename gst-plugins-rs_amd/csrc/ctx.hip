@@ -283,20 +283,38 @@ int mi355_memcpy_d2h(mi355_ctx *ctx, void *host, const void *dptr, size_t bytes)
   return check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
 }
 
+}  // extern "C"
+
 /* ------------------------------------------------------------------ hsvfilter */
+
+namespace mi355 {
+// The argument checks of the device entry, shared with the group's hsvfilter queue (group.hip: mi355_group_submit_hsvfilter), so
+// that a frame the one accepts is a frame the other accepts. MI355_OK with an empty batch means "nothing to do".
+int hsvfilter_check_frames(const uint8_t *d_data, int n_frames, size_t frame_pitch, int width, int height, int stride, int format,
+                           const mi355_hsv_settings *settings, PixFmt *fmt, const char **why) {
+  if (!settings || !pixfmt_of(format, fmt)) { *why = "hsvfilter: bad settings/format"; return MI355_ERR_INVALID_ARG; }
+  if (n_frames < 0 || width < 0 || height < 0 || stride < 0) { *why = "hsvfilter: negative size"; return MI355_ERR_INVALID_ARG; }
+  if (n_frames == 0 || width == 0 || height == 0) return MI355_OK;
+  if (!d_data) { *why = "hsvfilter: null data"; return MI355_ERR_INVALID_ARG; }
+  if ((size_t)stride < (size_t)width * fmt->pixel_stride) { *why = "hsvfilter: stride smaller than width*pixel_stride"; return MI355_ERR_INVALID_ARG; }
+  if (n_frames > 1 && frame_pitch < (size_t)(height - 1) * (size_t)stride + (size_t)width * fmt->pixel_stride) {
+    *why = "hsvfilter: frame_pitch smaller than one frame (frames would overlap)";
+    return MI355_ERR_INVALID_ARG;
+  }
+  return MI355_OK;
+}
+}  // namespace mi355
+
+extern "C" {
 
 int mi355_hsvfilter_frames_device(mi355_ctx *ctx, uint8_t *d_data, int n_frames, size_t frame_pitch, int width,
                                   int height, int stride, int format, const mi355_hsv_settings *settings) {
   REQUIRE_CTX(ctx);
   PixFmt fmt;
-  if (!settings || !pixfmt_of(format, &fmt)) return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvfilter: bad settings/format");
-  if (n_frames < 0 || width < 0 || height < 0 || stride < 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvfilter: negative size");
+  const char *why = nullptr;
+  const int bad = hsvfilter_check_frames(d_data, n_frames, frame_pitch, width, height, stride, format, settings, &fmt, &why);
+  if (bad) return set_error(ctx, bad, why);
   if (n_frames == 0 || width == 0 || height == 0) return MI355_OK;
-  if (!d_data) return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvfilter: null data");
-  if ((size_t)stride < (size_t)width * fmt.pixel_stride)
-    return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvfilter: stride smaller than width*pixel_stride");
-  if (n_frames > 1 && frame_pitch < (size_t)(height - 1) * (size_t)stride + (size_t)width * fmt.pixel_stride)
-    return set_error(ctx, MI355_ERR_INVALID_ARG, "hsvfilter: frame_pitch smaller than one frame (frames would overlap)");
   BIND_DEVICE(ctx);
   const int rc = launch_hsvfilter(ctx, d_data, n_frames, frame_pitch, width, height, stride, fmt, *settings);
   if (rc == MI355_OK) note_written(ctx->device, d_data, (size_t)(n_frames - 1) * frame_pitch + (size_t)stride * (size_t)height);   // what the element behind finds on-die

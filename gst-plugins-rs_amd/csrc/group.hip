@@ -19,10 +19,10 @@
 //   * results are the two element launches', bit for bit (same arithmetic, same table);
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
-// Five more queues live beside the filter batches, each with its own HIP stream(s), pending list, rendezvous and stats, and none
+// Six more queues live beside the filter batches, each with its own HIP stream(s), pending list, rendezvous and stats, and none
 // touching another. They are SET QUEUES: one protocol written once (SetQueue<Kind>: submit's tail, flush in sets of up to 32 of
 // one class in submission order, each set dealt out to the kind's lanes, the lingering wait, collect-once results per lane,
-// retire, stats, destroy) with five kinds: videocompare pairs (submit_compare: the one kind with classes - algorithm, geometry,
+// retire, stats, destroy) with six kinds: videocompare pairs (submit_compare: the one kind with classes - algorithm, geometry,
 // format, Dssim form - and lanes: a set's pairs, sorted by reference frame, go out as contiguous shares on up to 16 streams),
 // colordetect frames (submit_colordetect), hsvdetector frames (submit_hsvdetect: frames of independent instances - own size, strides, formats, settings - as at most two
 // launches over a job table, hsv_kernels.hip), decoder tensors (submit_yolodec: tensors of independent yolov8tensordec2 /
@@ -31,7 +31,10 @@
 // YdTensor of the kind MI355_YOLO_X_HEAD with the submit's copy of its levels - and cost a set one upload of their level tables
 // and two launches more, yolox_head.hip) and hand tensors (submit_handdec_palm / _landmarks: tensors of independent handdetectiontensordec /
 // handlandmarktensordec instances - own shape and settings - as at most two launches over job tables, no upload and one download,
-// handdec.hip). A further kind is a struct beside CmpKind / CdKind / HdKind / YdKind / HnKind - payload, result, kSetMax, its
+// handdec.hip) and hsvfilter frames (submit_hsvfilter: frames of independent instances - own size, stride, format, settings -
+// filtered IN PLACE as at most two launches over a job table, hsv_kernels.hip; the one kind whose members must not share bytes
+// within a launch: its submit entry launches what is pending in front of a frame that overlaps a pending one, and the sets of the
+// queue's one stream run in order). A further kind is a struct beside CmpKind / CdKind / HdKind / YdKind / HnKind / HfKind - payload, result, kSetMax, its
 // names, ensure, plan, the size of its pinned block (if any), launch, result, failed, destroy; OneLane, or its own same_class /
 // split / lanes - a SetQueue<Kind> member of mi355_group, a line in for_each_set_queue (the detector queues: what wait_all and the
 // foreign-ticket refusal reach) and its entry points; nothing of the protocol is written again. The filter batches alone are
@@ -137,7 +140,7 @@ Waited wait_seq_unlocking(std::deque<S> &sets, uint64_t seq, std::unique_lock<st
   return Waited::kDone;
 }
 
-// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its five kinds
+// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its six kinds
 // A kind is what differs between the queues: what is submitted (Payload), what a wait takes (Result), what a launch reads (Plan),
 // what a set in flight owns (SetData: its pinned `block` and what `result` needs besides), how a set is launched and read back, how
 // large its block has to be, the resources of first use - and which pending items may share a launch set (same_class) and how
@@ -311,6 +314,45 @@ struct HdKind : OneLane<HdFrame> {
   }
   void result(const SetData &, size_t, int *o) const { *o = MI355_OK; }
   static void failed(const HdFrame &, int rc, int *o) { *o = rc; }
+  static int status(int o) { return o; }
+  void destroy() { (void)hipStreamDestroy(stream); }
+};
+
+// ---- hsvfilter across independent element instances (mi355_group_submit_hsvfilter): one device frame per submit, filtered in
+// place - as the detector's, a set owns NO pinned block and the queue no scratch. The first in-place kind: the frames of a set must
+// not overlap, which the submit entry sees to (it launches what is pending in front of a frame that overlaps a pending one).
+struct HfKind : OneLane<HfFrame> {
+  using Payload = HfFrame;
+  using Result = int;  // the status
+  struct Plan { HfFrame frames[kHfSetMax]; };
+  struct SetData { PinnedBlock block; };  // (never taken: block_bytes is 0)
+  static constexpr int kSetMax = kHfSetMax;
+  static constexpr const char *kName = "hsvfilter", *kItem = "hsvfilter frame", *kWaitEntry = "mi355_group_wait_hsvfilter";
+  int n_cu = 256;
+  BlockPool blocks;  // (stays empty)
+
+  bool set_up() const { return stream != nullptr; }
+  // the queue's stream is all it has, so first use is keyed on it: at the first submit, never inside a launch set
+  int ensure(GroupCore *g) {
+    if (stream) return MI355_OK;
+    n_cu = device_cus(g->device);
+    return queue_stream(g, &stream, kName);
+  }
+  int plan(const QItem<HfFrame> *take, size_t n, Plan *p, std::string *) const {
+    for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
+    return MI355_OK;
+  }
+  size_t block_bytes(const Plan &) const { return 0; }
+  int launch(int, const Plan &p, size_t n, SetData *, int *launches, std::string *err) { return hsvfilter_launch_set(stream, n_cu, p.frames, (int)n, launches, err); }
+  // what the element behind finds on-die, as the lone entry records it: every frame with a pixel, once the set has gone out
+  void launched(const GroupCore *g, const Plan &p, size_t n) const {
+    for (size_t i = 0; i < n; i++) {
+      const HfFrame &f = p.frames[i];
+      if (f.width > 0 && f.height > 0) note_written(g->device, f.data, (size_t)f.stride * (size_t)f.height);
+    }
+  }
+  void result(const SetData &, size_t, int *o) const { *o = MI355_OK; }
+  static void failed(const HfFrame &, int rc, int *o) { *o = rc; }
   static int status(int o) { return o; }
   void destroy() { (void)hipStreamDestroy(stream); }
 };
@@ -873,13 +915,14 @@ struct mi355_group : GroupCore {
   // table references of retired batches: dropping the last reference to a table frees 64 MiB behind a device-wide wait, which
   // does not belong under `mu` - the entry points empty this list into a local one that dies after they have unlocked (Locked)
   std::vector<std::shared_ptr<void>> dead_refs;
-  // ---- the five set queues: each its own streams (and scratch, and blocks), created at its first submit, independent of the
+  // ---- the six set queues: each its own streams (and scratch, and blocks), created at its first submit, independent of the
   // filter batches above and of each other
   SetQueue<CmpKind> cmp; // videocompare pairs (Dssim / Blockhash)
   SetQueue<CdKind> cd;   // colordetect frames
   SetQueue<HdKind> hd;   // hsvdetector frames
   SetQueue<YdKind> yd;   // decoder tensors
   SetQueue<HnKind> hn;   // hand tensors (palm and landmarks)
+  SetQueue<HfKind> hf;   // hsvfilter frames (in place)
 };
 
 namespace {
@@ -1022,7 +1065,7 @@ int wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
 
 // ------------------------------------------------------------------ the detector queues, where an entry point names them all
 
-// f(queue) for each of the four detector queues, in the order flush, wait_all and destroy go through them. The compare queue is
+// f(queue) for each of the five detector and filter queues, in the order flush, wait_all and destroy go through them. The compare queue is
 // not among them: flush and destroy name it themselves, and wait_all and the foreign-ticket refusal below do not reach pairs.
 template <class F>
 void for_each_set_queue(mi355_group *g, F &&f) {
@@ -1030,6 +1073,7 @@ void for_each_set_queue(mi355_group *g, F &&f) {
   f(g->hd);
   f(g->yd);
   f(g->hn);
+  f(g->hf);
 }
 
 // A set queue's ticket presented to an entry point that serves another queue: refused (non-zero), and left collectable.
@@ -1300,6 +1344,73 @@ int mi355_group_hsvdetect_stats(mi355_group *g, uint64_t stats[4]) {
 int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_jobs, const uint64_t *units, uint32_t *first_block,
                                   uint32_t *blocks, uint32_t *total_blocks) {
   return hsvdetect_plan(n_cu, blocks_per_cu, units_per_block, n_jobs, units, first_block, blocks, total_blocks);
+}
+
+int mi355_group_set_hsvfilter_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
+  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  g->hf.set_rendezvous(expected_streams, linger_us);
+  return MI355_OK;
+}
+
+int mi355_group_submit_hsvfilter(mi355_group *g, mi355_ctx *ctx, uint8_t *d_data, int width, int height, int stride, int format,
+                                 const mi355_hsv_settings *settings, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context or ticket");
+  HfFrame f{};
+  const char *why = nullptr;
+  if (int rc = hsvfilter_check_frames(d_data, 1, 0, width, height, stride, format, settings, &f.fmt, &why)) return fail(g, rc, why);
+  f.data = d_data;
+  f.width = width;
+  f.height = height;
+  f.stride = stride;
+  f.s = *settings;
+  f.force_generic = ctx->force_generic;
+  // In place: a frame that shares bytes with a pending one must not share its launch. What is pending goes out first (sets of the
+  // queue's one stream run in order), so the two come out as if filtered one after the other. A failure of that launch is told to
+  // the waits of the frames it carried; this frame is queued whatever it did.
+  bool meets = false;
+  for (const auto &d : g->hf.pending) meets |= hsvfilter_frames_overlap(d.p, f);
+  if (meets) {
+    if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+    (void)g->hf.flush_locked(g);
+  }
+  // an empty frame touches nothing: it does not make the set wait for its stream
+  return g->hf.submit(g, ctx, f, width > 0 && height > 0, ticket);
+}
+
+int mi355_group_wait_hsvfilter(mi355_group *g, uint64_t ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  int status = MI355_OK;
+  return g->hf.wait(g, L.lk, ticket, &status);
+}
+
+int mi355_group_hsvfilter_stats(mi355_group *g, uint64_t stats[4]) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  g->hf.stats(stats);
+  return MI355_OK;
+}
+
+int mi355_selftest_hsvfilter_set_plan(int n_cu, const mi355_hsvfilter_plan_frame *frames, int n_frames, mi355_hsvfilter_plan_out *out, int *n_sets) {
+  if (n_cu < 1 || n_frames < 0 || !n_sets || (n_frames && (!frames || !out))) return MI355_ERR_INVALID_ARG;
+  std::vector<HfFrame> fr((size_t)n_frames);
+  for (int i = 0; i < n_frames; i++) {
+    const mi355_hsvfilter_plan_frame &p = frames[i];
+    HfFrame &f = fr[(size_t)i];
+    const char *why = nullptr;
+    // (a frame with a pixel has an address: null is what submit refuses, any other number is as good as another)
+    if (hsvfilter_check_frames((const uint8_t *)(uintptr_t)p.address, 1, 0, p.width, p.height, p.stride, p.format, &p.settings, &f.fmt, &why)) return MI355_ERR_INVALID_ARG;
+    f.data = (uint8_t *)(uintptr_t)p.address;
+    f.width = p.width;
+    f.height = p.height;
+    f.stride = p.stride;
+    f.s = p.settings;
+    f.force_generic = p.force_generic;
+  }
+  return hsvfilter_set_plan(n_cu, fr.data(), n_frames, out, n_sets);
 }
 
 int mi355_group_set_yolodec_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {

@@ -641,8 +641,9 @@ struct HdJobTable {
 static_assert(sizeof(HdJob) == 80, "HdJob has no padding holes");
 static_assert(sizeof(HdJobTable) <= 4096, "the job table is passed in the kernel arguments");
 
-// the job of block b: jobs are in first_block order and every job of a table has at least one block
-__device__ __forceinline__ int hsvdetect_job_of(const HdJobTable &T, uint32_t b) {
+// the job of block b: jobs are in first_block order and every job of a table has at least one block (HdJobTable, HfJobTable)
+template <class Table>
+__device__ __forceinline__ int hsvdetect_job_of(const Table &T, uint32_t b) {
   int j = 0;
   while (j + 1 < T.n_jobs && b >= T.job[j].first_block + T.job[j].blocks) j++;
   return j;
@@ -787,6 +788,290 @@ int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, in
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { *err = std::string(L.vector ? "hsvdetect jobs kernel launch: " : "hsvdetect rows jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
     (*kernel_launches)++;
+  }
+  return MI355_OK;
+}
+
+// ---------------------------------------------------------------- hsvfilter launch sets (the video group's filter queue)
+//
+// The same form for hsvfilter: frames of independent element instances - own size, stride, format (the ten 8-bit ones) and five
+// settings, which the reference lets change while playing (hsvfilter/imp.rs:127-156, snapshot per buffer :85) - filtered IN PLACE
+// in at most two launches over a job table in the kernel arguments.
+//   hsvfilter_jobs_kernel       the vector launch, four pixels per lane through hsvfilter_quad in its canonical instance <0, 1, 2, 3>:
+//                               one v_perm_b32 (in_sel) brings R, G, B to bytes 0-2 and the x / alpha byte to byte 3 (a 3-byte
+//                               format's byte 3 is the neighbour's byte: carried along, dropped by the re-pack), a second one
+//                               (out_sel) restores the order; the arithmetic reads byte values only, so it is that of the
+//                               <RPOS, GPOS, BPOS, NPOS> instance the lone entry picks. It carries every frame with a pixel whose
+//                               settings give a FAST variant (hsv_variant_for(s, force_generic, true) >= 0, wide shifts included) and
+//                               whose geometry is the lone entry's flat or rgb24 class: packed rows and, 4-byte formats, a 16-byte
+//                               aligned base and a byte count % 16 == 0, or, 3-byte formats, a 4-byte aligned base and a byte count
+//                               % 12 == 0. 4-byte frames with padded rows whose base and stride are multiples of 16 (the lone
+//                               rowpad class) are here too, addressed as (row, group) with the 1-3 pixel group at a row's end read
+//                               and written dword by dword: by the compiler's resource report that branch costs the kernel no
+//                               vector register and no scratch (49 VGPRs with and without it). The variant is a per-job
+//                               value: a block-uniform switch over the ten FAST instantiations (same report: no scratch, 8 waves
+//                               per SIMD as the lone flat kernel).
+//   hsvfilter_rows_jobs_kernel  the literal launch, one pixel per lane through hsvfilter_px<FAST / generic> with byte accesses, as
+//                               hsvfilter_rows_kernel: GENERIC settings, FORCE_GENERIC, unaligned bases, padded rows off the 16-byte
+//                               multiples (and all padded rows of 3-byte formats), pixel counts that do not fill whole groups. Kept
+//                               apart because IEEE division and fmodf would set the register budget of the kernel all aligned
+//                               frames run.
+// In place means order matters: two jobs of one launch never touch the same bytes. hsvfilter_set_build closes a set in front of a
+// frame whose byte range [data, data + (height - 1) stride + width pixel_stride) meets that of a frame already in it (ranges only:
+// conservative), and sets run one after the other on the queue's stream - overlapping frames come out as if filtered in order.
+enum : uint32_t { HF_PX3 = 1u, HF_BGR = 2u, HF_FIRST = 4u, HF_ROWPAD = 8u };
+struct HfJob {
+  uint8_t *data;
+  uint64_t units;                // vector launch: groups of four pixels (16 or 12 bytes); literal launch: pixels
+  HsvK k;
+  uint32_t in_sel, out_sel;      // vector launch: v_perm selectors into and out of the canonical word
+  int32_t width, stride;         // literal launch
+  int32_t variant;               // vector launch: the FAST variant (hsv_shift_of / hsv_sv_ident_of); literal launch: >= 0 FAST, -1 generic
+  uint32_t flags;                // HF_*: 12- or 16-byte groups (vector), pixel stride and byte positions (literal)
+  uint32_t first_block, blocks;  // its blocks in the 1-D grid (hsvdetect_plan)
+  uint32_t pad;
+};
+struct HfJobTable {
+  HfJob job[kHfSetMax];
+  int32_t n_jobs, pad;
+};
+static_assert(sizeof(HfJob) == 72, "HfJob has no padding holes");
+static_assert(sizeof(HfJobTable) == kHfSetMax * 72 + 8 && sizeof(HfJobTable) <= 4096, "the job table is passed in the kernel arguments");
+
+// the groups of one job's share through the FAST variant VARIANT
+template <int VARIANT>
+__device__ __forceinline__ void hsvfilter_job_groups(const HfJob &J, uint32_t rel, const HsvLds *lds) {
+  const HsvK k = J.k;
+  const uint32_t in_sel = J.in_sel, out_sel = J.out_sel;
+  const size_t n = J.units, stride = (size_t)J.blocks * 256;
+  if (J.flags & HF_PX3) {
+    Rgb24x4 *__restrict__ data = (Rgb24x4 *)J.data;
+    for (size_t i = (size_t)rel * 256 + threadIdx.x; i < n; i += stride) {
+      const Rgb24x4 v = data[i];
+      uint32_t p0 = __builtin_amdgcn_perm(v.d0, 0u, in_sel), p1 = __builtin_amdgcn_perm((v.d0 >> 24) | (v.d1 << 8), 0u, in_sel);
+      uint32_t p2 = __builtin_amdgcn_perm((v.d1 >> 16) | (v.d2 << 16), 0u, in_sel), p3 = __builtin_amdgcn_perm(v.d2 >> 8, 0u, in_sel);
+      hsvfilter_quad<VARIANT, 0, 1, 2, 3>(p0, p1, p2, p3, k, lds);
+      p0 = __builtin_amdgcn_perm(p0, 0u, out_sel); p1 = __builtin_amdgcn_perm(p1, 0u, out_sel);
+      p2 = __builtin_amdgcn_perm(p2, 0u, out_sel); p3 = __builtin_amdgcn_perm(p3, 0u, out_sel);
+      Rgb24x4 o;
+      o.d0 = (p0 & 0x00ffffffu) | (p1 << 24);
+      o.d1 = ((p1 >> 8) & 0x0000ffffu) | (p2 << 16);
+      o.d2 = ((p2 >> 16) & 0x000000ffu) | (p3 << 8);
+      data[i] = o;
+    }
+  } else if (J.flags & HF_ROWPAD) {
+    // padded rows, base and stride on 16-byte multiples: (row, group of four pixels); the last group of a row may hold 1-3 pixels
+    // and only those are read and written (hsvfilter_rowpad_kernel)
+    const uint32_t groups = ((uint32_t)J.width + 3u) >> 2;
+    for (size_t i = (size_t)rel * 256 + threadIdx.x; i < n; i += stride) {
+      const size_t row = i / groups;
+      const uint32_t g = (uint32_t)(i - row * groups);
+      uint8_t *at = J.data + row * (size_t)J.stride + (size_t)g * 16;
+      const int left = J.width - (int)(g * 4);
+      uint32_t px[4] = {0, 0, 0, 0};
+      if (left >= 4) {
+        const uint4 p = *(const uint4 *)at;
+        px[0] = p.x; px[1] = p.y; px[2] = p.z; px[3] = p.w;
+      } else {
+        for (int q = 0; q < left; q++) px[q] = ((const uint32_t *)at)[q];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) px[q] = __builtin_amdgcn_perm(px[q], 0u, in_sel);
+      hsvfilter_quad<VARIANT, 0, 1, 2, 3>(px[0], px[1], px[2], px[3], k, lds);
+#pragma unroll
+      for (int q = 0; q < 4; q++) px[q] = __builtin_amdgcn_perm(px[q], 0u, out_sel);
+      if (left >= 4) *(uint4 *)at = make_uint4(px[0], px[1], px[2], px[3]);
+      else
+        for (int q = 0; q < left; q++) ((uint32_t *)at)[q] = px[q];
+    }
+  } else {
+    uint4 *__restrict__ data = (uint4 *)J.data;
+    for (size_t i = (size_t)rel * 256 + threadIdx.x; i < n; i += stride) {
+      uint4 p = data[i];
+      p.x = __builtin_amdgcn_perm(p.x, 0u, in_sel); p.y = __builtin_amdgcn_perm(p.y, 0u, in_sel);
+      p.z = __builtin_amdgcn_perm(p.z, 0u, in_sel); p.w = __builtin_amdgcn_perm(p.w, 0u, in_sel);
+      hsvfilter_quad<VARIANT, 0, 1, 2, 3>(p.x, p.y, p.z, p.w, k, lds);
+      p.x = __builtin_amdgcn_perm(p.x, 0u, out_sel); p.y = __builtin_amdgcn_perm(p.y, 0u, out_sel);
+      p.z = __builtin_amdgcn_perm(p.z, 0u, out_sel); p.w = __builtin_amdgcn_perm(p.w, 0u, out_sel);
+      data[i] = p;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void hsvfilter_jobs_kernel(const HfJobTable T) {
+  const int j = hsvdetect_job_of(T, blockIdx.x);
+  const uint32_t rel = blockIdx.x - T.job[j].first_block;
+  if (blockIdx.x < T.job[j].first_block || rel >= T.job[j].blocks) return;  // a grid larger than the plan's total: the whole block leaves, before the barrier
+  __shared__ HsvLds lds;
+  hsv_lds_fill<0, 1, 2, 3>(&lds);
+  __syncthreads();
+  // the job, and with it the variant, is the block's: every wave takes the same case
+  switch (T.job[j].variant) {
+    case 0: hsvfilter_job_groups<0>(T.job[j], rel, &lds); break;
+    case 1: hsvfilter_job_groups<1>(T.job[j], rel, &lds); break;
+    case 2: hsvfilter_job_groups<2>(T.job[j], rel, &lds); break;
+    case 4: hsvfilter_job_groups<4>(T.job[j], rel, &lds); break;
+    case 5: hsvfilter_job_groups<5>(T.job[j], rel, &lds); break;
+    case 6: hsvfilter_job_groups<6>(T.job[j], rel, &lds); break;
+    case 8: hsvfilter_job_groups<8>(T.job[j], rel, &lds); break;
+    case 9: hsvfilter_job_groups<9>(T.job[j], rel, &lds); break;
+    case 12: hsvfilter_job_groups<12>(T.job[j], rel, &lds); break;
+    case 13: hsvfilter_job_groups<13>(T.job[j], rel, &lds); break;
+    default: break;  // (no other variant is ever put into a vector table)
+  }
+}
+
+template <bool FAST>
+__device__ __forceinline__ void hsvfilter_job_pixels(const HfJob &J, uint32_t rel, const uint32_t *sel_tab) {
+  const HsvK k = J.k;
+  const bool bgr = (J.flags & HF_BGR) != 0;
+  const size_t pixel_stride = (J.flags & HF_PX3) ? 3 : 4, first = (J.flags & HF_FIRST) ? 1 : 0;
+  const size_t total = J.units, width = (size_t)J.width, row_stride = (size_t)J.stride, stride = (size_t)J.blocks * 256;
+  uint8_t *__restrict__ data = J.data;
+  for (size_t i = (size_t)rel * 256 + threadIdx.x; i < total; i += stride) {
+    const size_t row = i / width;
+    const size_t col = i - row * width;
+    uint8_t *px = data + row * row_stride + col * pixel_stride + first;
+    const uint32_t c0 = px[0], c1 = px[1], c2 = px[2];
+    const uint32_t p = bgr ? (c2 | (c1 << 8) | (c0 << 16)) : (c0 | (c1 << 8) | (c2 << 16));
+    const uint32_t o = hsvfilter_px<FAST, 0, 1, 2, 3>(p, k, sel_tab);
+    const uint8_t orr = (uint8_t)(o & 0xff), og = (uint8_t)((o >> 8) & 0xff), ob = (uint8_t)((o >> 16) & 0xff);
+    px[0] = bgr ? ob : orr;
+    px[1] = og;
+    px[2] = bgr ? orr : ob;
+  }
+}
+
+__global__ __launch_bounds__(256) void hsvfilter_rows_jobs_kernel(const HfJobTable T) {
+  const int j = hsvdetect_job_of(T, blockIdx.x);
+  const uint32_t rel = blockIdx.x - T.job[j].first_block;
+  if (blockIdx.x < T.job[j].first_block || rel >= T.job[j].blocks) return;  // a grid larger than the plan's total
+  __shared__ uint32_t sel_tab[8];
+  if (threadIdx.x < 7) sel_tab[threadIdx.x] = hsv_sel_entry(threadIdx.x, 0, 1, 2, 3);
+  __syncthreads();
+  if (T.job[j].variant >= 0) hsvfilter_job_pixels<true>(T.job[j], rel, sel_tab);
+  else hsvfilter_job_pixels<false>(T.job[j], rel, sel_tab);
+}
+
+bool hsvfilter_frames_overlap(const HfFrame &a, const HfFrame &b) {
+  if (a.width <= 0 || a.height <= 0 || b.width <= 0 || b.height <= 0) return false;  // no pixel, no byte
+  const uintptr_t a0 = (uintptr_t)a.data, b0 = (uintptr_t)b.data;
+  const uintptr_t a1 = a0 + (size_t)(a.height - 1) * (size_t)a.stride + (size_t)a.width * (size_t)a.fmt.pixel_stride;
+  const uintptr_t b1 = b0 + (size_t)(b.height - 1) * (size_t)b.stride + (size_t)b.width * (size_t)b.fmt.pixel_stride;
+  return a0 < b1 && b0 < a1;
+}
+
+// The ONE builder of launch sets, for hsvfilter_launch_set and mi355_selftest_hsvfilter_set_plan alike: classifies the frames,
+// computes variants and selectors, closes a set at kHfSetMax frames and in front of a frame that overlaps one already in it, and
+// plans the blocks of each set's two launches. The frames' addresses are numbers here: nothing is dereferenced. `out` (per frame)
+// may be null.
+struct HfSet { HfJobTable vec, lit; uint32_t vec_blocks, lit_blocks; };
+static int hsvfilter_set_build(int n_cu, const HfFrame *frames, int n, std::vector<HfSet> *sets, mi355_hsvfilter_plan_out *out) {
+  sets->clear();
+  if (n_cu < 1 || n < 0 || (n && !frames)) return MI355_ERR_INVALID_ARG;
+  struct Slot { int frame; bool vector; int job; };
+  for (int begin = 0; begin < n;) {
+    int end = begin;
+    for (; end < n && end - begin < kHfSetMax; end++) {
+      bool meets = false;
+      for (int e = begin; e < end && !meets; e++) meets = hsvfilter_frames_overlap(frames[e], frames[end]);
+      if (meets) break;
+    }
+    sets->emplace_back();
+    HfSet &S = sets->back();
+    std::memset(&S, 0, sizeof(S));
+    uint64_t vec_units[kHfSetMax], lit_units[kHfSetMax];
+    Slot slot[kHfSetMax];
+    int n_slots = 0;
+    for (int i = begin; i < end; i++) {
+      const HfFrame &f = frames[i];
+      if (out) out[i] = mi355_hsvfilter_plan_out{(int32_t)sets->size() - 1, 0, -1, 0, 0, 0, 0};
+      if (f.width <= 0 || f.height <= 0) continue;  // no pixel: no job
+      const size_t row_bytes = (size_t)f.width * (size_t)f.fmt.pixel_stride, total_bytes = row_bytes * (size_t)f.height;
+      const bool packed = (size_t)f.stride == row_bytes;
+      const uintptr_t at = (uintptr_t)f.data;
+      const int wide_variant = hsv_variant_for(f.s, f.force_generic != 0, true);
+      const bool flat = f.fmt.pixel_stride == 4 ? packed && at % 16 == 0 && total_bytes % 16 == 0
+                                                : f.fmt.first == 0 && packed && at % 4 == 0 && total_bytes % 12 == 0;
+      const bool rowpad = !flat && f.fmt.pixel_stride == 4 && at % 16 == 0 && f.stride % 16 == 0;
+      const bool vector = wide_variant >= 0 && (flat || rowpad);
+      HfJobTable &T = vector ? S.vec : S.lit;
+      HfJob &J = T.job[T.n_jobs];
+      J.data = f.data;
+      J.k = HsvK{f.s.hue_shift, f.s.saturation_mul, f.s.saturation_off, f.s.value_mul, f.s.value_off};
+      J.width = f.width;
+      J.stride = f.stride;
+      J.flags = (f.fmt.pixel_stride == 3 ? HF_PX3 : 0u) | (f.fmt.bgr ? HF_BGR : 0u) | (f.fmt.first ? HF_FIRST : 0u);
+      if (vector) {
+        // canonical word: R, G, B at bytes 0, 1, 2, the x / alpha byte (3-byte formats: the word's spare byte) at byte 3. Selector
+        // bytes 4..7 pick from the first operand of v_perm_b32
+        const uint32_t rpos = (uint32_t)(f.fmt.first + (f.fmt.bgr ? 2 : 0)), gpos = (uint32_t)f.fmt.first + 1, bpos = (uint32_t)(f.fmt.first + (f.fmt.bgr ? 0 : 2));
+        const uint32_t npos = f.fmt.pixel_stride == 4 && f.fmt.first ? 0 : 3;
+        J.in_sel = (4 + rpos) | ((4 + gpos) << 8) | ((4 + bpos) << 16) | ((4 + npos) << 24);
+        J.out_sel = (4u << (8 * rpos)) | (5u << (8 * gpos)) | (6u << (8 * bpos)) | (7u << (8 * npos));
+        J.variant = wide_variant;
+        if (rowpad) J.flags |= HF_ROWPAD;
+        J.units = rowpad ? (uint64_t)(((uint32_t)f.width + 3u) / 4u) * (uint64_t)f.height : total_bytes / (f.fmt.pixel_stride == 4 ? 16 : 12);
+        vec_units[T.n_jobs] = J.units;
+      } else {
+        // one pixel per lane: the single-pixel FAST routine knows the narrow shift classes only (as the lone rows kernel's choice)
+        J.variant = hsv_variant_for(f.s, f.force_generic != 0, false);
+        J.units = (uint64_t)f.width * (uint64_t)f.height;
+        lit_units[T.n_jobs] = J.units;
+      }
+      slot[n_slots++] = Slot{i, vector, T.n_jobs};
+      T.n_jobs++;
+    }
+    // vector: two groups per lane and the cap of the lone grid_for(ctx, (n_vec + 1) / 2, 256, 64); literal: grid_for(ctx, total, 256, 32)
+    struct Launch { HfJobTable *T; const uint64_t *units; unsigned per_block; int per_cu; uint32_t *total; };
+    const Launch launches[2] = {{&S.vec, vec_units, 512, 64, &S.vec_blocks}, {&S.lit, lit_units, 256, 32, &S.lit_blocks}};
+    for (const Launch &L : launches) {
+      uint32_t first[kHfSetMax], blocks[kHfSetMax];
+      const int rc = hsvdetect_plan(n_cu, L.per_cu, L.per_block, L.T->n_jobs, L.units, first, blocks, L.total);
+      if (rc) return rc;
+      for (int j = 0; j < L.T->n_jobs; j++) { L.T->job[j].first_block = first[j]; L.T->job[j].blocks = blocks[j]; }
+    }
+    if (out)
+      for (int k = 0; k < n_slots; k++) {
+        const HfJob &J = (slot[k].vector ? S.vec : S.lit).job[slot[k].job];
+        mi355_hsvfilter_plan_out &o = out[slot[k].frame];
+        o.launch = slot[k].vector ? 1 : 2;
+        o.variant = J.variant;
+        o.first_block = J.first_block;
+        o.blocks = J.blocks;
+        o.units = J.units;
+      }
+    begin = end;
+  }
+  return MI355_OK;
+}
+
+int hsvfilter_set_plan(int n_cu, const HfFrame *frames, int n, mi355_hsvfilter_plan_out *out, int *n_sets) {
+  std::vector<HfSet> sets;
+  const int rc = hsvfilter_set_build(n_cu, frames, n, &sets, out);
+  if (!rc) *n_sets = (int)sets.size();
+  return rc;
+}
+
+int hsvfilter_launch_set(hipStream_t stream, int n_cu, const HfFrame *frames, int n, int *kernel_launches, std::string *err) {
+  *kernel_launches = 0;
+  if (!frames || n < 1 || n > kHfSetMax) { *err = "hsvfilter: bad launch set"; return MI355_ERR_INVALID_ARG; }
+  std::vector<HfSet> sets;
+  if (const int rc = hsvfilter_set_build(n_cu, frames, n, &sets, nullptr)) { *err = "hsvfilter: bad launch set"; return rc; }
+  // (one set, unless the caller handed over frames that overlap: then their sets, in order on the one stream)
+  for (const HfSet &S : sets) {
+    if (S.vec.n_jobs) {
+      hipLaunchKernelGGL(hsvfilter_jobs_kernel, dim3(S.vec_blocks), dim3(256), 0, stream, S.vec);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) { *err = std::string("hsvfilter jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+      (*kernel_launches)++;
+    }
+    if (S.lit.n_jobs) {
+      hipLaunchKernelGGL(hsvfilter_rows_jobs_kernel, dim3(S.lit_blocks), dim3(256), 0, stream, S.lit);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) { *err = std::string("hsvfilter rows jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+      (*kernel_launches)++;
+    }
   }
   return MI355_OK;
 }

@@ -286,6 +286,25 @@ int hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_
                    uint32_t *total_blocks);
 // n <= kHdSetMax checked frames on `stream`: the vector launch and / or the literal launch, whichever has a job with a pixel
 int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, int n, int *kernel_launches, std::string *err);
+// launch sets of the video group's hsvfilter queue (hsv_kernels.hip): frames of independent instances filtered in place, one job table
+constexpr int kHfSetMax = MI355_HSVFILTER_SET_MAX;
+struct HfFrame {
+  uint8_t *data;
+  int width, height, stride;
+  PixFmt fmt;
+  mi355_hsv_settings s;
+  int force_generic;  // the member's MI355_FLAG_FORCE_GENERIC at submit
+};
+// the checks of mi355_hsvfilter_frames_device for n_frames frames (ctx.hip; both entries call it); *why names the refusal
+int hsvfilter_check_frames(const uint8_t *d_data, int n_frames, size_t frame_pitch, int width, int height, int stride, int format,
+                           const mi355_hsv_settings *settings, PixFmt *fmt, const char **why);
+// do the byte ranges [data, data + (height - 1) stride + width pixel_stride) of two frames meet? (a frame without a pixel has no byte)
+bool hsvfilter_frames_overlap(const HfFrame &a, const HfFrame &b);
+// host only: the sets n frames go out in - a new one at kHfSetMax frames and in front of a frame that overlaps one of the set - and per
+// frame its set, launch (0 no pixel, 1 vector, 2 literal), variant, units and blocks; the builder hsvfilter_launch_set launches from
+int hsvfilter_set_plan(int n_cu, const HfFrame *frames, int n, mi355_hsvfilter_plan_out *out, int *n_sets);
+// n <= kHfSetMax checked frames on `stream`: the vector launch and / or the literal launch, whichever has a job with a pixel
+int hsvfilter_launch_set(hipStream_t stream, int n_cu, const HfFrame *frames, int n, int *kernel_launches, std::string *err);
 
 // agingradio (agingradio.hip): one job = one element instance's buffer. The host fills the table (alpha and the quantise factor
 // computed with its libm); the group (agroup.hip) submits one job per member, a context a table of one.

@@ -41,6 +41,7 @@ FLAG_WINDOW_ORDER = 17
 FLAG_WINDOW_STATS = 18
 FLAG_DSSIM_FAST = 19
 HSVDETECT_SET_MAX = 32   # MI355_HSVDETECT_SET_MAX: detector frames per launch set of a Group
+HSVFILTER_SET_MAX = 32   # MI355_HSVFILTER_SET_MAX: hsvfilter frames per launch set of a Group
 YOLODEC_SET_MAX = 32     # MI355_YOLODEC_SET_MAX: decoder tensors per launch set of a Group
 MIXER_FRAME_TILE = 64    # MI355_MIXER_FRAME_TILE: frames per block of the mixer kernel
 
@@ -48,6 +49,18 @@ MIXER_FRAME_TILE = 64    # MI355_MIXER_FRAME_TILE: frames per block of the mixer
 class HsvSettings(C.Structure):
     _fields_ = [("hue_shift", C.c_float), ("saturation_mul", C.c_float), ("saturation_off", C.c_float),
                 ("value_mul", C.c_float), ("value_off", C.c_float)]
+
+
+class HsvFilterPlanFrame(C.Structure):
+    """mi355_hsvfilter_plan_frame: one frame as mi355_selftest_hsvfilter_set_plan takes it; the address is a number."""
+    _fields_ = [("address", C.c_uint64), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("format", C.c_int32),
+                ("settings", HsvSettings), ("force_generic", C.c_int32)]
+
+
+class HsvFilterPlanOut(C.Structure):
+    """mi355_hsvfilter_plan_out: where the builder puts a frame (launch: 0 no pixel, 1 vector, 2 literal)."""
+    _fields_ = [("set", C.c_int32), ("launch", C.c_int32), ("variant", C.c_int32), ("first_block", C.c_uint32), ("blocks", C.c_uint32),
+                ("reserved", C.c_uint32), ("units", C.c_uint64)]
 
 
 class AgingRadioSettings(C.Structure):
@@ -321,6 +334,11 @@ def load_library():
         "mi355_group_hsvdetect_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "mi355_selftest_hsvdetect_plan": (i, [i, i, C.c_uint, i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32)]),
+        "mi355_group_set_hsvfilter_rendezvous": (i, [vp, i, C.c_uint]),
+        "mi355_group_submit_hsvfilter": (i, [vp, vp, u8p, i, i, i, i, C.POINTER(HsvSettings), C.POINTER(C.c_uint64)]),
+        "mi355_group_wait_hsvfilter": (i, [vp, C.c_uint64]),
+        "mi355_group_hsvfilter_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_hsvfilter_set_plan": (i, [i, C.POINTER(HsvFilterPlanFrame), i, C.POINTER(HsvFilterPlanOut), C.POINTER(C.c_int)]),
         "mi355_agroup_create_echo": (vp, [i, i, sz, C.POINTER(C.c_int)]),
         "mi355_agroup_create_ebur128": (vp, [i, i, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_create_loudnorm": (vp, [i, i, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int)]),
@@ -667,6 +685,28 @@ class Group:
         self._ck(self.L.mi355_group_hsvdetect_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
+    # ---- hsvfilter frames of independent elements, in place
+    def set_hsvfilter_rendezvous(self, expected_streams, linger_us):
+        self._ck(self.L.mi355_group_set_hsvfilter_rendezvous(self.h, expected_streams, linger_us))
+
+    def submit_hsvfilter(self, ctx, d_data, width, height, stride, fmt, settings):
+        """One device frame of stream `ctx`, filtered in place (settings: the five floats, or None for a null pointer; fmt: a name
+        or the enum's int); returns the ticket."""
+        s = None if settings is None else C.byref(HsvSettings(*[float(v) for v in settings]))
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_hsvfilter(self.h, ctx.h, d_data, width, height, stride, FMT.get(fmt, fmt), s, C.byref(t)))
+        return t.value
+
+    def wait_hsvfilter(self, ticket):
+        """Returns once the frame holds what Context.hsvfilter_frames_device would have left."""
+        self._ck(self.L.mi355_group_wait_hsvfilter(self.h, ticket))
+
+    def hsvfilter_stats(self):
+        """(frames launched, launch sets, frames in the largest set, kernel launches)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.L.mi355_group_hsvfilter_stats(self.h, c))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
     # ---- yolov8tensordec2 / yoloxtensordec tensors of independent elements
     def set_yolodec_rendezvous(self, expected_streams, linger_us):
         self._ck(self.L.mi355_group_set_yolodec_rendezvous(self.h, expected_streams, linger_us))
@@ -760,6 +800,25 @@ class Group:
         if self.h:
             self.L.mi355_group_destroy(self.h)
             self.h = None
+
+
+def selftest_hsvfilter_set_plan(frames, n_cu=256):
+    """mi355_selftest_hsvfilter_set_plan (host only): what the hsvfilter queue's builder makes of frames in submission order.
+    frames: (address, width, height, stride, fmt, settings[, force_generic]) each, the address a number that is never dereferenced,
+    fmt a name or the enum's int; or None for null arrays. Returns (status, n_sets, [dict(set, launch, variant, units, first_block,
+    blocks)])."""
+    L = load_library()
+    n_sets = C.c_int(-1)
+    if frames is None:
+        return L.mi355_selftest_hsvfilter_set_plan(n_cu, None, 1, None, C.byref(n_sets)), n_sets.value, []
+    n = len(frames)
+    m = max(n, 1)
+    fr, out = (HsvFilterPlanFrame * m)(), (HsvFilterPlanOut * m)()
+    for k, f in enumerate(frames):
+        fr[k] = HsvFilterPlanFrame(f[0], f[1], f[2], f[3], FMT.get(f[4], f[4]), HsvSettings(*[float(v) for v in f[5]]), int(f[6]) if len(f) > 6 else 0)
+    rc = L.mi355_selftest_hsvfilter_set_plan(n_cu, fr, n, out, C.byref(n_sets))
+    return rc, n_sets.value, [dict(set=o.set, launch=o.launch, variant=o.variant, units=int(o.units), first_block=o.first_block, blocks=o.blocks)
+                              for o in list(out)[:n]]
 
 
 def selftest_handdec_set_plan(decoders, rows):

@@ -6,7 +6,13 @@
  * Added by the shim: propose_allocation offers pinned buffers (gst_mi355_propose_pinned_pool); and when the DIRECT
  * downstream peer is this shim's colorlut on RGBA frames (custom query "mi355-fuse-hsv"), the element leaves the pixels
  * alone and tags the buffer with its settings snapshot (GstMi355HsvMeta): colorlut then runs the fused
- * hsvfilter -> colorlut kernel - one upload, one launch, one download for the pair instead of two PCIe round trips. */
+ * hsvfilter -> colorlut kernel - one upload, one launch, one download for the pair instead of two PCIe round trips.
+ * With MI355_GROUP_MEMBERS=n (n >= 2) in the environment the n instances of the process hand the buffers that lie in this
+ * project's device memory to the device's dispatcher instead (mi355_group_submit_hsvfilter): the frames of an interval - each with
+ * its own size, format and settings snapshot - share at most two launches. Mapped buffers, the deferral to
+ * colorlut and the unset environment are unchanged. */
+#include <stdlib.h>
+
 #include "gstmi355common.h"
 
 GST_DEBUG_CATEGORY_STATIC(gst_hsv_filter_debug);
@@ -22,6 +28,8 @@ struct _GstHsvFilter {
   mi355_ctx *ctx;             /* created in start(), destroyed in stop() */
   gint fuse_checked;          /* the peer has been asked since the last (re)negotiation / relink / reconfigure (atomic) */
   gboolean fuse;              /* downstream is our colorlut: defer the filter to its fused kernel */
+  /* MI355_GROUP_MEMBERS=n: the process's dispatcher (mi355_group_shared), held between start and stop */
+  mi355_group *group;
 };
 
 G_DEFINE_TYPE(GstHsvFilter, gst_hsv_filter, GST_TYPE_VIDEO_FILTER)
@@ -70,11 +78,16 @@ static gboolean gst_hsv_filter_start(GstBaseTransform *trans) {
     GST_ELEMENT_ERROR(self, LIBRARY, INIT, ("No MI355X context"), ("%s", mi355_status_string(status)));
     return FALSE;
   }
+  const char *members = g_getenv("MI355_GROUP_MEMBERS");
+  if (members && atoi(members) >= 2 && (self->group = mi355_group_shared(0, &status)))
+    (void)mi355_group_set_hsvfilter_rendezvous(self->group, atoi(members), 2000); /* every instance submits + waits at once; a straggler is waited for 2 ms */
   return TRUE;
 }
 
 static gboolean gst_hsv_filter_stop(GstBaseTransform *trans) {
   GstHsvFilter *self = GST_HSV_FILTER(trans);
+  if (self->group) mi355_group_release(self->group);
+  self->group = NULL;
   if (self->ctx) mi355_ctx_destroy(self->ctx);
   self->ctx = NULL;
   return TRUE;
@@ -129,6 +142,55 @@ static gboolean gst_hsv_filter_peer_fuses(GstHsvFilter *self) {
   return ok;
 }
 
+/* does the downstream colorlut run this frame's filter in its fused kernel? Asked once per (re)negotiation / relink */
+static gboolean gst_hsv_filter_defers(GstHsvFilter *self, int fmt) {
+  if (!g_atomic_int_get(&self->fuse_checked)) {
+    g_atomic_int_set(&self->fuse_checked, TRUE);  /* (set first: a relink while we ask clears it again) */
+    self->fuse = fmt == MI355_FMT_RGBA && gst_hsv_filter_peer_fuses(self);
+    GST_INFO_OBJECT(self, "hsvfilter %s", self->fuse ? "deferred to the downstream colorlut (fused kernel)" : "runs its own kernel");
+  }
+  return self->fuse;
+}
+
+/* GstBaseTransformClass::transform_ip, in front of GstVideoFilter's (which maps the buffer): with MI355_GROUP_MEMBERS set, a buffer
+ * of our device memory is filtered where it lies, in the launch set it shares with the other instances' frames of this interval -
+ * no host copy. Anything else - no group, a mapped buffer, a frame deferred to colorlut - chains up to transform_frame_ip below. */
+static GstFlowReturn gst_hsv_filter_transform_ip(GstBaseTransform *trans, GstBuffer *buf) {
+  GstHsvFilter *self = GST_HSV_FILTER(trans);
+  GstVideoFilter *vf = GST_VIDEO_FILTER(trans);
+  mi355_buf *b = self->group ? gst_mi355_buffer_peek_device(buf) : NULL;
+  const int fmt = b && vf->negotiated ? gst_mi355_format(GST_VIDEO_INFO_FORMAT(&vf->in_info)) : -1;
+  if (fmt < 0 || gst_hsv_filter_defers(self, fmt)) return GST_BASE_TRANSFORM_CLASS(gst_hsv_filter_parent_class)->transform_ip(trans, buf);
+  mi355_hsv_settings s;
+  g_mutex_lock(&self->lock);
+  s = self->settings;
+  g_mutex_unlock(&self->lock);
+  const GstVideoInfo *ii = &vf->in_info;
+  uint8_t *d = mi355_buf_device_ptr(b, self->ctx, MI355_MAP_READ | MI355_MAP_WRITE);
+  if (!d) {
+    GST_ERROR_OBJECT(self, "mi355_buf_device_ptr: %s", mi355_ctx_last_error(self->ctx));
+    return GST_FLOW_ERROR;
+  }
+  /* the frame joins whatever the other instances have pending; the bytes are the lone call's */
+  uint64_t ticket = 0;
+  const char *failed = "mi355_group_submit_hsvfilter";
+  int rc = mi355_group_submit_hsvfilter(self->group, self->ctx, d + GST_VIDEO_INFO_PLANE_OFFSET(ii, 0), GST_VIDEO_INFO_WIDTH(ii), GST_VIDEO_INFO_HEIGHT(ii),
+                                        GST_VIDEO_INFO_PLANE_STRIDE(ii, 0), fmt, &s, &ticket);
+  if (rc == MI355_OK) {
+    failed = "mi355_group_wait_hsvfilter";
+    rc = mi355_group_wait_hsvfilter(self->group, ticket);
+  }
+  if (rc != MI355_OK) {
+    GST_ERROR_OBJECT(self, "%s: %s", failed, mi355_group_last_error(self->group));
+    return GST_FLOW_ERROR;
+  }
+  if (mi355_buf_commit(b, self->ctx) != MI355_OK) {
+    GST_ERROR_OBJECT(self, "mi355_buf_commit: %s", mi355_ctx_last_error(self->ctx));
+    return GST_FLOW_ERROR;
+  }
+  return GST_FLOW_OK;
+}
+
 /* VideoFilterImpl::transform_frame_ip (imp.rs:323-376): the base class hands a writable frame (AlwaysInPlace). */
 static GstFlowReturn gst_hsv_filter_transform_frame_ip(GstVideoFilter *filter, GstVideoFrame *frame) {
   GstHsvFilter *self = GST_HSV_FILTER(filter);
@@ -138,12 +200,7 @@ static GstFlowReturn gst_hsv_filter_transform_frame_ip(GstVideoFilter *filter, G
   g_mutex_unlock(&self->lock);
   const int fmt = gst_mi355_format(GST_VIDEO_FRAME_FORMAT(frame));
   if (fmt < 0) return GST_FLOW_NOT_NEGOTIATED; /* the reference's match ends in unreachable!() (imp.rs:374) */
-  if (!g_atomic_int_get(&self->fuse_checked)) {
-    g_atomic_int_set(&self->fuse_checked, TRUE);  /* (set first: a relink while we ask clears it again) */
-    self->fuse = fmt == MI355_FMT_RGBA && gst_hsv_filter_peer_fuses(self);
-    GST_INFO_OBJECT(self, "hsvfilter %s", self->fuse ? "deferred to the downstream colorlut (fused kernel)" : "runs its own kernel");
-  }
-  if (self->fuse) {
+  if (gst_hsv_filter_defers(self, fmt)) {
     /* the settings of THIS frame travel with it; colorlut applies them in the fused launch */
     return gst_buffer_add_mi355_hsv_meta(frame->buffer, &s) ? GST_FLOW_OK : GST_FLOW_ERROR;
   }
@@ -195,6 +252,7 @@ static void gst_hsv_filter_class_init(GstHsvFilterClass *klass) {
   trans->stop = gst_hsv_filter_stop;
   trans->propose_allocation = gst_hsv_filter_propose_allocation;
   trans->src_event = gst_hsv_filter_src_event;
+  trans->transform_ip = gst_hsv_filter_transform_ip; /* GstVideoFilter's transform_ip is reached by chaining up */
   trans->passthrough_on_same_caps = FALSE;     /* imp.rs:318 */
   trans->transform_ip_on_passthrough = FALSE;  /* imp.rs:319 */
   vfilter->set_info = gst_hsv_filter_set_info;

@@ -390,6 +390,78 @@ int mi355_group_hsvdetect_stats(mi355_group *group, uint64_t stats[4]);
 int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_jobs, const uint64_t *units,
                                   uint32_t *first_block, uint32_t *blocks, uint32_t *total_blocks);
 
+/* hsvfilter across independent element instances. The five properties of the element change while playing
+ * (video/hsv/src/hsvfilter/imp.rs:127-156) and are snapshotted per buffer (:85): 32 cameras with a hue shift each, or one camera
+ * whose shift is animated, are 32 lone launches per frame period. submit_hsvfilter queues one device frame of stream `ctx`, filtered
+ * IN PLACE, and whatever is pending goes out as at most TWO launches over a job table in the kernel arguments, on the queue's own
+ * HIP stream. Members are fully independent: each frame has its own size, stride, format (the ten 8-bit ones, MI355_FMT_RGBX ...
+ * MI355_FMT_BGR) and five settings; no colorlut runs behind it. After wait_hsvfilter the frame's bytes are what
+ * mi355_hsvfilter_frames_device(ctx, d_data, 1, 0, width, height, stride, format, settings) would have left, byte for byte (the x /
+ * alpha byte of a 4-byte format unchanged), and no byte outside width * pixel_stride bytes of each of height rows has changed. The
+ * frame is recorded as recently written, as the lone entry records it: a colorlut behind it sees an on-die source.
+ *   submit : never blocks; the checks and status codes are those of mi355_hsvfilter_frames_device with n_frames = 1 (format -
+ *           MI355_FMT_RGBA64_* included -, settings pointer, negative sizes, null data with a non-empty frame, stride against line
+ *           bytes; a null ctx or a null ticket: MI355_ERR_INVALID_ARG). A refused submit queues nothing. A frame with width == 0 or
+ *           height == 0 is accepted, gets a ticket and writes nothing. The settings are copied and the member's
+ *           MI355_FLAG_FORCE_GENERIC is read at submit; MI355_FLAG_HSV_NT and the context's memoised hsv table play no part: the
+ *           group's kernels use plain loads and stores and compute. The frame is processed after what ctx's HIP stream held at the
+ *           call, and is read and written until wait_hsvfilter for the ticket has returned.
+ *   order  : in place means order matters: two frames of one launch never touch the same bytes. Overlap is judged on the byte
+ *           ranges [d_data, d_data + (height - 1) * stride + width * pixel_stride) - ranges only, conservative. A submit that
+ *           overlaps a frame still pending first launches what is pending, then queues; sets run in order on the queue's one
+ *           stream, so overlapping frames come out as if filtered one after the other in submission order. Frames that do not
+ *           overlap share a set, wherever they were carved from.
+ *   wait   : launches what is pending if the frame has not gone out (rendezvous first), then waits for its launch set; the
+ *           group's lock is not held meanwhile. A result is collected once. Tickets are one sequence per group: a ticket that is
+ *           unknown, already collected or another queue's is MI355_ERR_INVALID_ARG here and stays collectable where it belongs;
+ *           mi355_group_wait, _order_after, _wait_compare, _wait_colordetect, _wait_hsvdetect, _wait_yolodec and _wait_handdec
+ *           refuse an hsvfilter ticket likewise.
+ *   set_hsvfilter_rendezvous : as set_hsvdetect_rendezvous, counted over pending hsvfilter frames only. The other queues'
+ *           rendezvous, streams and stats and this queue's do not touch each other.
+ *   At most MI355_HSVFILTER_SET_MAX frames share a launch set; more go out as consecutive sets. flush, wait_all and destroy cover
+ *   this queue as they cover the others. A launch that fails is reported, once, to each frame's own wait.
+ *   The two launches: the vector launch (four pixels per lane, one v_perm_b32 into a canonical byte order and one out of it) carries
+ *   every frame whose settings give a FAST variant - hue_shift 0 or 1e-30 <= |hue_shift| <= 2^22, finite, FORCE_GENERIC off - and
+ *   whose geometry is the lone entry's flat or rgb24 class: packed rows and, 4-byte formats, a 16-byte aligned base and a byte count
+ *   that is a multiple of 16, or, 3-byte formats, a 4-byte aligned base and a byte count that is a multiple of 12 - or its rowpad
+ *   class: a 4-byte format with padded rows whose base and stride are multiples of 16 (units: ceil(width / 4) groups per row). The
+ *   literal launch (one pixel per lane, byte accesses; IEEE division and fmodf for the settings that need them) carries every other
+ *   frame: GENERIC settings, FORCE_GENERIC, unaligned bases, pixel counts that do not fill whole groups, padded rows off the
+ *   16-byte multiples and every padded row of a 3-byte format.
+ *   hsvfilter_stats : {frames launched, launch sets, frames in the largest set, kernel launches} - per set 0 launches when no frame
+ *           has a pixel, 1 when all frames are of one class, 2 when both classes occur.
+ *   mi355_selftest_hsvfilter_set_plan : host only, no device: what the builder the queue launches from makes of n_frames frames in
+ *           submission order. The addresses are numbers and are never dereferenced. Per frame: `set`, counted from 0 - a new set
+ *           begins at MI355_HSVFILTER_SET_MAX frames and in front of a frame that overlaps one of the current set; `launch`, 0 no
+ *           pixel, 1 vector, 2 literal; `variant`, vector: the FAST variant (bits 0-1 zero / positive / negative shift, bit 2
+ *           identity saturation and value settings, bit 3 wide shift with its sign in bit 0), literal: >= 0 if the single-pixel FAST
+ *           routine serves the settings (narrow shifts), -1 for the literal arithmetic, no pixel: -1; `units`, vector: groups of
+ *           four pixels, literal: pixels; `first_block` and `blocks`, its share of its launch's grid by
+ *           mi355_selftest_hsvdetect_plan's rule (vector: 512 units per block, 64 blocks per CU; literal: 256 and 32). *n_sets: the
+ *           sets. Refused (MI355_ERR_INVALID_ARG): n_cu < 1, n_frames < 0, null arrays with n_frames > 0, a null n_sets, and a
+ *           frame submit would refuse (format, negative sizes, stride below the line bytes of a frame with a pixel). */
+#define MI355_HSVFILTER_SET_MAX 32 /* frames per launch set */
+typedef struct mi355_hsvfilter_plan_frame {
+  uint64_t address;            /* the frame's first byte, as a number */
+  int32_t width, height, stride, format;
+  mi355_hsv_settings settings;
+  int32_t force_generic;       /* the member's MI355_FLAG_FORCE_GENERIC */
+} mi355_hsvfilter_plan_frame;
+typedef struct mi355_hsvfilter_plan_out {
+  int32_t set, launch, variant;
+  uint32_t first_block, blocks, reserved;
+  uint64_t units;
+} mi355_hsvfilter_plan_out;
+int mi355_group_set_hsvfilter_rendezvous(mi355_group *group, int expected_streams, unsigned linger_us);
+int mi355_group_submit_hsvfilter(mi355_group *group, mi355_ctx *ctx, uint8_t *d_data, int width, int height, int stride,
+                                 int format, const mi355_hsv_settings *settings, uint64_t *ticket);
+int mi355_group_wait_hsvfilter(mi355_group *group, uint64_t ticket);
+/* {frames launched, launch sets, frames in the largest set, kernel launches} */
+int mi355_group_hsvfilter_stats(mi355_group *group, uint64_t stats[4]);
+/* host only, no device: the sets, launches and blocks of n_frames frames */
+int mi355_selftest_hsvfilter_set_plan(int n_cu, const mi355_hsvfilter_plan_frame *frames, int n_frames,
+                                      mi355_hsvfilter_plan_out *out, int *n_sets);
+
 /* ---------------------------------------------------------------- many AUDIO element instances, few launches (csrc/agroup.hip)
  * rsaudioecho (audio/audiofx/src/audioecho/imp.rs:205-227), ebur128level (audio/audiofx/src/ebur128level/imp.rs:682-745) and
  * audioloudnorm (audio/audiofx/src/audioloudnorm/imp.rs:1545-1586) are one instance per stream and one buffer per call; the batch

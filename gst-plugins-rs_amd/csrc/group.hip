@@ -20,25 +20,31 @@
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
 // Six more queues live beside the filter batches, each with its own HIP stream(s), pending list, rendezvous and stats, and none
-// touching another. They are SET QUEUES: one protocol written once (SetQueue<Kind>: submit's tail, flush in sets of up to 32 of
+// touching another. They are SET QUEUES: one protocol written once - SetQueue<Kind>: submit's tail, flush in sets of up to 32 of
 // one class in submission order, each set dealt out to the kind's lanes, the lingering wait, collect-once results per lane,
-// retire, stats, destroy) with six kinds: videocompare pairs (submit_compare: the one kind with classes - algorithm, geometry,
-// format, Dssim form - and lanes: a set's pairs, sorted by reference frame, go out as contiguous shares on up to 16 streams),
-// colordetect frames (submit_colordetect), hsvdetector frames (submit_hsvdetect: frames of independent instances - own size, strides, formats, settings - as at most two
-// launches over a job table, hsv_kernels.hip), decoder tensors (submit_yolodec: tensors of independent yolov8tensordec2 /
-// yoloxtensordec instances - own shape, layout, settings - as at most three launches over job tables and one download,
-// yolodec.hip; submit_yolox_head: the raw head maps of independent yoloxinference instances are members of the SAME queue - a
-// YdTensor of the kind MI355_YOLO_X_HEAD with the submit's copy of its levels - and cost a set one upload of their level tables
-// and two launches more, yolox_head.hip) and hand tensors (submit_handdec_palm / _landmarks: tensors of independent handdetectiontensordec /
-// handlandmarktensordec instances - own shape and settings - as at most two launches over job tables, no upload and one download,
-// handdec.hip) and hsvfilter frames (submit_hsvfilter: frames of independent instances - own size, stride, format, settings -
-// filtered IN PLACE as at most two launches over a job table, hsv_kernels.hip; the one kind whose members must not share bytes
-// within a launch: its submit entry launches what is pending in front of a frame that overlaps a pending one, and the sets of the
-// queue's one stream run in order). A further kind is a struct beside CmpKind / CdKind / HdKind / YdKind / HnKind / HfKind - payload, result, kSetMax, its
-// names, ensure, plan, the size of its pinned block (if any), launch, result, failed, destroy; OneLane, or its own same_class /
-// split / lanes - a SetQueue<Kind> member of mi355_group, a line in for_each_set_queue (the detector queues: what wait_all and the
-// foreign-ticket refusal reach) and its entry points; nothing of the protocol is written again. The filter batches alone are
-// their own code: one frame per stream and batch, the non-batchable path and order_after are not this protocol.
+// retire, stats, destroy - with six kinds:
+//   * CmpKind, videocompare pairs (submit_compare). The one kind with classes (algorithm, geometry, format, Dssim form) and lanes:
+//     a set's pairs, sorted by reference frame, go out as contiguous shares on up to 16 streams.
+//   * CdKind, colordetect frames (submit_colordetect).
+//   * YdKind, decoder tensors (submit_yolodec): tensors of independent yolov8tensordec2 / yoloxtensordec instances - own shape,
+//     layout, settings - as at most three launches over job tables and one download, yolodec.hip. The raw head maps of independent
+//     yoloxinference instances (submit_yolox_head) are members of the SAME queue: a YdTensor of the kind MI355_YOLO_X_HEAD with
+//     the submit's copy of its levels; they cost a set one upload of their level tables and two launches more, yolox_head.hip.
+//   * HnKind, hand tensors (submit_handdec_palm / _landmarks): tensors of independent handdetectiontensordec /
+//     handlandmarktensordec instances - own shape and settings - as at most two launches over job tables, no upload and one
+//     download, handdec.hip.
+//   * HdKind and HfKind, hsvdetector and hsvfilter frames (submit_hsvdetect, submit_hsvfilter): frames of independent instances -
+//     own size, strides, formats, settings - as at most two launches over a job table, hsv_kernels.hip. Both are FrameKind<traits>:
+//     written on the device, nothing to bring back. hsvfilter works IN PLACE and is the one kind whose members must not share
+//     bytes within a launch: its submit entry launches what is pending in front of a frame that overlaps a pending one, and the
+//     sets of the queue's one stream run in order.
+// A further kind is a struct beside these - payload, result, kSetMax, its names, ensure, plan (PayloadPlan, if the launch reads
+// the payloads as they are), the size of its pinned block (if any), launch, result, failed, destroy; OneLane, or its own same_class
+// / split / lanes - or, for frames written on the device, the traits of a FrameKind. It is a SetQueue<Kind> member of mi355_group
+// and a line in for_each_queue_but_compare, which is how flush, wait_all, destroy and the foreign-ticket refusal reach it; its entry points
+// check their own arguments and take their rendezvous, stats and (status-only) wait bodies from queue_set_rendezvous, queue_stats
+// and queue_wait_status. Nothing of the protocol is written again. The filter batches alone are their own code: one frame per
+// stream and batch, the non-batchable path and order_after are not this protocol.
 // The group has ONE mutex, ticket sequence, event free list and last_error (GroupCore); every queue uses those. Tickets are one
 // sequence; a wait entry refuses a ticket of another queue.
 // No persistent kernel: nothing here can hang the GPU waiting for the host, a launch is a launch.
@@ -231,14 +237,23 @@ int device_cus(int device) {
   return n_cu > 0 ? n_cu : 256;
 }
 
+// What the kinds whose launch reads the payloads as they were submitted share (CdKind, FrameKind): the plan is a copy of them.
+template <class Payload, int N>
+struct PayloadPlan : OneLane<Payload> {
+  struct Plan { Payload frames[N]; };
+  int plan(const QItem<Payload> *take, size_t n, Plan *p, std::string *) const {
+    for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
+    return MI355_OK;
+  }
+};
+
 // ---- colordetect across independent element instances (mi355_group_submit_colordetect): one flat device plane per submit; its
 // palette comes back through the set's pinned block. Consecutive sets on the queue's stream share the device scratch.
 struct CdOut { int status, n_colors; uint8_t rgb[255 * 3]; };
 constexpr int kCdBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in flight before one more has to be allocated
-struct CdKind : OneLane<CdFrame> {
+struct CdKind : PayloadPlan<CdFrame, kCdSetMax> {
   using Payload = CdFrame;
   using Result = CdOut;
-  struct Plan { CdFrame frames[kCdSetMax]; };
   struct SetData { PinnedBlock block; };  // the set's results (colordetect_set_result) until it is collected
   static constexpr int kSetMax = kCdSetMax;
   static constexpr const char *kName = "colordetect", *kItem = "colordetect frame", *kWaitEntry = "mi355_group_wait_colordetect";
@@ -258,10 +273,6 @@ struct CdKind : OneLane<CdFrame> {
     scratch = colordetect_set_scratch_new(stream, &st, &err);
     return scratch ? MI355_OK : fail(g, st, "group: " + err);
   }
-  int plan(const QItem<CdFrame> *take, size_t n, Plan *p, std::string *) const {
-    for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
-    return MI355_OK;
-  }
   size_t block_bytes(const Plan &) const { return colordetect_set_block_bytes(); }
   int launch(int, const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
     return colordetect_launch_set(scratch, stream, n_cu, p.frames, (int)n, d->block.h, launches, err);
@@ -280,82 +291,61 @@ struct CdKind : OneLane<CdFrame> {
   }
 };
 
-// ---- hsvdetector across independent element instances (mi355_group_submit_hsvdetect): one device frame per submit, written in
-// place on the device - nothing comes back but the launch's status, so a set owns NO pinned block and the queue no scratch.
-struct HdKind : OneLane<HdFrame> {
-  using Payload = HdFrame;
-  using Result = int;  // the status
-  struct Plan { HdFrame frames[kHdSetMax]; };
-  struct SetData { PinnedBlock block; };  // (never taken: block_bytes is 0)
+// ---- frames written on the device, across independent element instances: one device frame per submit, and nothing comes back but
+// the launch's status - a set owns NO pinned block and the queue no scratch. Two kinds, each a few lines of traits (the frame, its
+// names, its launch-set function in hsv_kernels.hip and the bytes a frame's launch writes):
+//   HdKind  hsvdetector (mi355_group_submit_hsvdetect): source to destination.
+//   HfKind  hsvfilter (mi355_group_submit_hsvfilter): IN PLACE, so the frames of a set must not overlap, which the submit entry sees
+//           to (it launches what is pending in front of a frame that overlaps a pending one).
+struct HdTraits {
+  using Frame = HdFrame;
   static constexpr int kSetMax = kHdSetMax;
   static constexpr const char *kName = "hsvdetector", *kItem = "hsvdetector frame", *kWaitEntry = "mi355_group_wait_hsvdetect";
-  int n_cu = 256;
-  BlockPool blocks;  // (stays empty)
-
-  bool set_up() const { return stream != nullptr; }
-  // the queue's stream is all it has, so first use is keyed on it: at the first submit, never inside a launch set
-  int ensure(GroupCore *g) {
-    if (stream) return MI355_OK;
-    n_cu = device_cus(g->device);
-    return queue_stream(g, &stream, kName);
-  }
-  int plan(const QItem<HdFrame> *take, size_t n, Plan *p, std::string *) const {
-    for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
-    return MI355_OK;
-  }
-  size_t block_bytes(const Plan &) const { return 0; }
-  int launch(int, const Plan &p, size_t n, SetData *, int *launches, std::string *err) { return hsvdetect_launch_set(stream, n_cu, p.frames, (int)n, launches, err); }
-  // what the element behind finds on-die, as the lone entry records it: every destination with a pixel, once the set has gone out
-  void launched(const GroupCore *g, const Plan &p, size_t n) const {
-    for (size_t i = 0; i < n; i++) {
-      const HdFrame &f = p.frames[i];
-      if (f.width > 0 && f.height > 0) note_written(g->device, f.dst, (size_t)f.dst_stride * (size_t)f.height);
-    }
-  }
-  void result(const SetData &, size_t, int *o) const { *o = MI355_OK; }
-  static void failed(const HdFrame &, int rc, int *o) { *o = rc; }
-  static int status(int o) { return o; }
-  void destroy() { (void)hipStreamDestroy(stream); }
+  static constexpr auto kLaunchSet = hsvdetect_launch_set;
+  static const void *written(const HdFrame &f, size_t *bytes) { *bytes = (size_t)f.dst_stride * (size_t)f.height; return f.dst; }
 };
-
-// ---- hsvfilter across independent element instances (mi355_group_submit_hsvfilter): one device frame per submit, filtered in
-// place - as the detector's, a set owns NO pinned block and the queue no scratch. The first in-place kind: the frames of a set must
-// not overlap, which the submit entry sees to (it launches what is pending in front of a frame that overlaps a pending one).
-struct HfKind : OneLane<HfFrame> {
-  using Payload = HfFrame;
-  using Result = int;  // the status
-  struct Plan { HfFrame frames[kHfSetMax]; };
-  struct SetData { PinnedBlock block; };  // (never taken: block_bytes is 0)
+struct HfTraits {
+  using Frame = HfFrame;
   static constexpr int kSetMax = kHfSetMax;
   static constexpr const char *kName = "hsvfilter", *kItem = "hsvfilter frame", *kWaitEntry = "mi355_group_wait_hsvfilter";
+  static constexpr auto kLaunchSet = hsvfilter_launch_set;
+  static const void *written(const HfFrame &f, size_t *bytes) { *bytes = (size_t)f.stride * (size_t)f.height; return f.data; }
+};
+template <class T>
+struct FrameKind : PayloadPlan<typename T::Frame, T::kSetMax> {
+  using Payload = typename T::Frame;
+  using Result = int;  // the status
+  using Plan = typename PayloadPlan<Payload, T::kSetMax>::Plan;
+  struct SetData { PinnedBlock block; };  // (never taken: block_bytes is 0)
+  static constexpr int kSetMax = T::kSetMax;
+  static constexpr const char *kName = T::kName, *kItem = T::kItem, *kWaitEntry = T::kWaitEntry;
   int n_cu = 256;
   BlockPool blocks;  // (stays empty)
 
-  bool set_up() const { return stream != nullptr; }
+  bool set_up() const { return this->stream != nullptr; }
   // the queue's stream is all it has, so first use is keyed on it: at the first submit, never inside a launch set
   int ensure(GroupCore *g) {
-    if (stream) return MI355_OK;
+    if (this->stream) return MI355_OK;
     n_cu = device_cus(g->device);
-    return queue_stream(g, &stream, kName);
-  }
-  int plan(const QItem<HfFrame> *take, size_t n, Plan *p, std::string *) const {
-    for (size_t i = 0; i < n; i++) p->frames[i] = take[i].p;
-    return MI355_OK;
+    return queue_stream(g, &this->stream, kName);
   }
   size_t block_bytes(const Plan &) const { return 0; }
-  int launch(int, const Plan &p, size_t n, SetData *, int *launches, std::string *err) { return hsvfilter_launch_set(stream, n_cu, p.frames, (int)n, launches, err); }
-  // what the element behind finds on-die, as the lone entry records it: every frame with a pixel, once the set has gone out
+  int launch(int, const Plan &p, size_t n, SetData *, int *launches, std::string *err) { return T::kLaunchSet(this->stream, n_cu, p.frames, (int)n, launches, err); }
+  // what the element behind finds on-die, as the lone entry records it: what every frame with a pixel writes, once the set has gone out
   void launched(const GroupCore *g, const Plan &p, size_t n) const {
     for (size_t i = 0; i < n; i++) {
-      const HfFrame &f = p.frames[i];
-      if (f.width > 0 && f.height > 0) note_written(g->device, f.data, (size_t)f.stride * (size_t)f.height);
+      size_t bytes = 0;
+      const void *at = T::written(p.frames[i], &bytes);
+      if (p.frames[i].width > 0 && p.frames[i].height > 0) note_written(g->device, at, bytes);
     }
   }
   void result(const SetData &, size_t, int *o) const { *o = MI355_OK; }
-  static void failed(const HfFrame &, int rc, int *o) { *o = rc; }
+  static void failed(const Payload &, int rc, int *o) { *o = rc; }
   static int status(int o) { return o; }
-  void destroy() { (void)hipStreamDestroy(stream); }
+  void destroy() { (void)hipStreamDestroy(this->stream); }
 };
+using HdKind = FrameKind<HdTraits>;
+using HfKind = FrameKind<HfTraits>;
 
 // ---- yolov8tensordec2 / yoloxtensordec across independent element instances (mi355_group_submit_yolodec): one device tensor per
 // submit; its kept count and records come back through the set's pinned block. Consecutive sets share the device scratch.
@@ -1063,12 +1053,13 @@ int wait_all_unlocking(mi355_group *g, std::unique_lock<std::mutex> &lk) {
   return MI355_OK;
 }
 
-// ------------------------------------------------------------------ the detector queues, where an entry point names them all
+// ------------------------------------------------------------------ the set queues, where an entry point names them all
 
-// f(queue) for each of the five detector and filter queues, in the order flush, wait_all and destroy go through them. The compare queue is
-// not among them: flush and destroy name it themselves, and wait_all and the foreign-ticket refusal below do not reach pairs.
+// f(queue) for each set queue but the compare queue, in the order every walk goes through them. This is what wait_all and the
+// foreign-ticket refusal below reach: wait_all does not wait for pairs, and no other entry refuses a pair's ticket by name - the
+// one difference between the compare queue and the others here.
 template <class F>
-void for_each_set_queue(mi355_group *g, F &&f) {
+void for_each_queue_but_compare(mi355_group *g, F &&f) {
   f(g->cd);
   f(g->hd);
   f(g->yd);
@@ -1076,13 +1067,50 @@ void for_each_set_queue(mi355_group *g, F &&f) {
   f(g->hf);
 }
 
+// ... and for all six, the compare queue first: flush and destroy treat it as every other
+template <class F>
+void for_each_set_queue(mi355_group *g, F &&f) {
+  f(g->cmp);
+  for_each_queue_but_compare(g, f);
+}
+
 // A set queue's ticket presented to an entry point that serves another queue: refused (non-zero), and left collectable.
 int refuse_set_queue_ticket(mi355_group *g, uint64_t ticket) {
   std::string owner;
-  for_each_set_queue(g, [&](auto &q) {
+  for_each_queue_but_compare(g, [&](auto &q) {
     if (owner.empty() && q.owns(ticket)) owner = q.foreign_refusal();
   });
   return owner.empty() ? MI355_OK : fail(g, MI355_ERR_INVALID_ARG, owner);
+}
+
+// ---- the bodies the set queues' entry points share; `q` names the queue (a null group has none to take the address of)
+
+template <class Q>
+int queue_set_rendezvous(mi355_group *g, Q mi355_group::*q, int expected_streams, unsigned linger_us) {
+  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  (g->*q).set_rendezvous(expected_streams, linger_us);
+  return MI355_OK;
+}
+
+// {items launched, launch sets, items in the largest set, kernel launches}: the first `columns` of them
+template <class Q>
+int queue_stats(mi355_group *g, Q mi355_group::*q, uint64_t *stats, int columns = 4) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  uint64_t all[4];
+  (g->*q).stats(all);
+  std::copy(all, all + columns, stats);
+  return MI355_OK;
+}
+
+// the wait of a kind whose result is the launch's status alone (FrameKind)
+template <class Q>
+int queue_wait_status(mi355_group *g, Q mi355_group::*q, uint64_t ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  int status = MI355_OK;
+  return (g->*q).wait(g, L.lk, ticket, &status);
 }
 
 }  // namespace
@@ -1114,8 +1142,7 @@ void mi355_group_destroy(mi355_group *g) {
     (void)wait_all_unlocking(g, L.lk);
   }
   (void)hipStreamSynchronize(g->stream);
-  if (g->cmp.kind.set_up()) g->cmp.destroy(g);
-  for_each_set_queue(g, [&](auto &q) { q.destroy(g); });
+  for_each_set_queue(g, [&](auto &q) { q.destroy(g); });   // (a queue that was never set up has nothing: SetQueue::destroy)
   for (Batch &b : g->batches) (void)hipEventDestroy(b.done);   // (normally none left: wait_all retired them)
   for (Desc &d : g->pending)
     if (d.ready) (void)hipEventDestroy(d.ready);
@@ -1193,9 +1220,7 @@ int mi355_group_flush(mi355_group *g) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
   if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
-  const int rc = flush_locked(g);
-  const int rc2 = g->cmp.kind.set_up() ? g->cmp.flush_locked(g) : MI355_OK;
-  int first = rc ? rc : rc2;
+  int first = flush_locked(g);
   for_each_set_queue(g, [&](auto &q) {   // every queue that has been set up is launched; the first failure is the answer
     const int r = q.kind.set_up() ? q.flush_locked(g) : MI355_OK;
     if (!first) first = r;
@@ -1206,10 +1231,7 @@ int mi355_group_flush(mi355_group *g) {
 // ---------------------------------------------------------------- videocompare pairs (Dssim / Blockhash) of independent elements
 
 int mi355_group_set_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
-  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  g->cmp.set_rendezvous(expected_streams, linger_us);
-  return MI355_OK;
+  return queue_set_rendezvous(g, &mi355_group::cmp, expected_streams, linger_us);
 }
 
 int mi355_group_set_compare_lanes(mi355_group *g, int lanes) {
@@ -1249,23 +1271,14 @@ int mi355_group_wait_compare(mi355_group *g, uint64_t ticket, double *distance, 
   return MI355_OK;
 }
 
-int mi355_group_compare_stats(mi355_group *g, uint64_t stats[3]) {
-  if (!g || !stats) return MI355_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(g->mu);
-  uint64_t all[4];   // (the compare queue reports no launch column)
-  g->cmp.stats(all);
-  std::copy(all, all + 3, stats);
-  return MI355_OK;
-}
+// (the compare queue reports no launch column)
+int mi355_group_compare_stats(mi355_group *g, uint64_t stats[3]) { return queue_stats(g, &mi355_group::cmp, stats, 3); }
 
 // ---------------------------------------------------------------- the set queues' entry points: each checks its own arguments and
 // hands over to SetQueue<Kind> (submit's tail, the body of wait, stats)
 
 int mi355_group_set_colordetect_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
-  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  g->cd.set_rendezvous(expected_streams, linger_us);
-  return MI355_OK;
+  return queue_set_rendezvous(g, &mi355_group::cd, expected_streams, linger_us);
 }
 
 int mi355_group_submit_colordetect(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_data, size_t data_len, int format, int quality, int max_colors,
@@ -1291,18 +1304,10 @@ int mi355_group_wait_colordetect(mi355_group *g, uint64_t ticket, uint8_t palett
   return MI355_OK;
 }
 
-int mi355_group_colordetect_stats(mi355_group *g, uint64_t stats[4]) {
-  if (!g || !stats) return MI355_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(g->mu);
-  g->cd.stats(stats);
-  return MI355_OK;
-}
+int mi355_group_colordetect_stats(mi355_group *g, uint64_t stats[4]) { return queue_stats(g, &mi355_group::cd, stats); }
 
 int mi355_group_set_hsvdetect_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
-  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  g->hd.set_rendezvous(expected_streams, linger_us);
-  return MI355_OK;
+  return queue_set_rendezvous(g, &mi355_group::hd, expected_streams, linger_us);
 }
 
 int mi355_group_submit_hsvdetect(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_src, int src_stride, int src_format, uint8_t *d_dst, int dst_stride,
@@ -1327,19 +1332,9 @@ int mi355_group_submit_hsvdetect(mi355_group *g, mi355_ctx *ctx, const uint8_t *
   return g->hd.submit(g, ctx, f, width > 0 && height > 0, ticket);
 }
 
-int mi355_group_wait_hsvdetect(mi355_group *g, uint64_t ticket) {
-  if (!g) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  int status = MI355_OK;
-  return g->hd.wait(g, L.lk, ticket, &status);
-}
+int mi355_group_wait_hsvdetect(mi355_group *g, uint64_t ticket) { return queue_wait_status(g, &mi355_group::hd, ticket); }
 
-int mi355_group_hsvdetect_stats(mi355_group *g, uint64_t stats[4]) {
-  if (!g || !stats) return MI355_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(g->mu);
-  g->hd.stats(stats);
-  return MI355_OK;
-}
+int mi355_group_hsvdetect_stats(mi355_group *g, uint64_t stats[4]) { return queue_stats(g, &mi355_group::hd, stats); }
 
 int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_jobs, const uint64_t *units, uint32_t *first_block,
                                   uint32_t *blocks, uint32_t *total_blocks) {
@@ -1347,10 +1342,7 @@ int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_pe
 }
 
 int mi355_group_set_hsvfilter_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
-  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  g->hf.set_rendezvous(expected_streams, linger_us);
-  return MI355_OK;
+  return queue_set_rendezvous(g, &mi355_group::hf, expected_streams, linger_us);
 }
 
 int mi355_group_submit_hsvfilter(mi355_group *g, mi355_ctx *ctx, uint8_t *d_data, int width, int height, int stride, int format,
@@ -1380,19 +1372,9 @@ int mi355_group_submit_hsvfilter(mi355_group *g, mi355_ctx *ctx, uint8_t *d_data
   return g->hf.submit(g, ctx, f, width > 0 && height > 0, ticket);
 }
 
-int mi355_group_wait_hsvfilter(mi355_group *g, uint64_t ticket) {
-  if (!g) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  int status = MI355_OK;
-  return g->hf.wait(g, L.lk, ticket, &status);
-}
+int mi355_group_wait_hsvfilter(mi355_group *g, uint64_t ticket) { return queue_wait_status(g, &mi355_group::hf, ticket); }
 
-int mi355_group_hsvfilter_stats(mi355_group *g, uint64_t stats[4]) {
-  if (!g || !stats) return MI355_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(g->mu);
-  g->hf.stats(stats);
-  return MI355_OK;
-}
+int mi355_group_hsvfilter_stats(mi355_group *g, uint64_t stats[4]) { return queue_stats(g, &mi355_group::hf, stats); }
 
 int mi355_selftest_hsvfilter_set_plan(int n_cu, const mi355_hsvfilter_plan_frame *frames, int n_frames, mi355_hsvfilter_plan_out *out, int *n_sets) {
   if (n_cu < 1 || n_frames < 0 || !n_sets || (n_frames && (!frames || !out))) return MI355_ERR_INVALID_ARG;
@@ -1414,10 +1396,7 @@ int mi355_selftest_hsvfilter_set_plan(int n_cu, const mi355_hsvfilter_plan_frame
 }
 
 int mi355_group_set_yolodec_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
-  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  g->yd.set_rendezvous(expected_streams, linger_us);
-  return MI355_OK;
+  return queue_set_rendezvous(g, &mi355_group::yd, expected_streams, linger_us);
 }
 
 int mi355_group_submit_yolodec(mi355_group *g, mi355_ctx *ctx, const float *d_tensor, int layout, uint32_t num_fields, uint32_t num_candidates,
@@ -1469,12 +1448,7 @@ int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *de
   return MI355_OK;
 }
 
-int mi355_group_yolodec_stats(mi355_group *g, uint64_t stats[4]) {
-  if (!g || !stats) return MI355_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(g->mu);
-  g->yd.stats(stats);
-  return MI355_OK;
-}
+int mi355_group_yolodec_stats(mi355_group *g, uint64_t stats[4]) { return queue_stats(g, &mi355_group::yd, stats); }
 
 int mi355_group_yolox_head_stats(mi355_group *g, uint64_t stats[4]) {
   if (!g || !stats) return MI355_ERR_INVALID_ARG;
@@ -1488,10 +1462,7 @@ int mi355_group_yolox_head_stats(mi355_group *g, uint64_t stats[4]) {
 }
 
 int mi355_group_set_handdec_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
-  if (!g || expected_streams < 0) return MI355_ERR_INVALID_ARG;
-  Locked L(g);
-  g->hn.set_rendezvous(expected_streams, linger_us);
-  return MI355_OK;
+  return queue_set_rendezvous(g, &mi355_group::hn, expected_streams, linger_us);
 }
 
 // the two submits' common part: the lone entry points' checks for one tensor at a pitch equal to the tensor, in their order
@@ -1540,12 +1511,7 @@ int mi355_group_wait_handdec(mi355_group *g, uint64_t ticket, mi355_hand_det *de
   return MI355_OK;
 }
 
-int mi355_group_handdec_stats(mi355_group *g, uint64_t stats[4]) {
-  if (!g || !stats) return MI355_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(g->mu);
-  g->hn.stats(stats);
-  return MI355_OK;
-}
+int mi355_group_handdec_stats(mi355_group *g, uint64_t stats[4]) { return queue_stats(g, &mi355_group::hn, stats); }
 
 int mi355_group_wait(mi355_group *g, uint64_t ticket) {
   if (!g) return MI355_ERR_INVALID_ARG;
@@ -1595,7 +1561,7 @@ int mi355_group_wait_all(mi355_group *g) {
   int rc = flush_locked(g);
   if (rc) return rc;
   if ((rc = wait_all_unlocking(g, lk))) return rc;
-  for_each_set_queue(g, [&](auto &q) {   // each queue that has been set up, in turn; the first failure ends it
+  for_each_queue_but_compare(g, [&](auto &q) {   // each queue that has been set up, in turn; the first failure ends it
     if (rc || !q.kind.set_up()) return;
     if (!(rc = q.flush_locked(g))) rc = q.wait_all_unlocking(g, lk);
   });

@@ -240,18 +240,6 @@ __global__ __launch_bounds__(256) void hsvfilter_rgb24x16_kernel(uint4 *__restri
   }
 }
 
-template <int VARIANT>
-static void launch_rgb24x16(mi355_ctx *ctx, uint4 *d, size_t n_chunks, const HsvK &k, int bgr, int grid) {
-  if (bgr) hipLaunchKernelGGL((hsvfilter_rgb24x16_kernel<VARIANT, true>), dim3(grid), dim3(256), 0, ctx->stream, d, n_chunks, k);
-  else hipLaunchKernelGGL((hsvfilter_rgb24x16_kernel<VARIANT, false>), dim3(grid), dim3(256), 0, ctx->stream, d, n_chunks, k);
-}
-
-template <int VARIANT>
-static void launch_rgb24(mi355_ctx *ctx, Rgb24x4 *d, size_t n_grp, const HsvK &k, int bgr, int grid) {
-  if (bgr) hipLaunchKernelGGL((hsvfilter_rgb24_kernel<VARIANT, true>), dim3(grid), dim3(256), 0, ctx->stream, d, n_grp, k);
-  else hipLaunchKernelGGL((hsvfilter_rgb24_kernel<VARIANT, false>), dim3(grid), dim3(256), 0, ctx->stream, d, n_grp, k);
-}
-
 // General kernel: any stride / pixel stride (3 or 4) / triple offset / alignment, one pixel per lane, byte
 // accesses. Only `line[..width*pixel_stride]` of each row is touched (hsvfilter/imp.rs:94-97).
 template <bool FAST>
@@ -289,64 +277,83 @@ static int grid_for(mi355_ctx *ctx, size_t work_items, int block, int blocks_per
   return (int)blocks;
 }
 
-template <int VARIANT>
-static void launch_flat(mi355_ctx *ctx, uint4 *d, size_t n_vec, const HsvK &k, int first, int bgr, int grid) {
-  dim3 g(grid), b(256);
+// ---- run-time value -> template argument, each conversion written once. A launcher nests the helpers it needs around its ONE
+// hipLaunchKernelGGL line; f is a generic lambda and gets std::integral_constant / std::bool_constant values.
+
+// the variant number of hsv_variant_for: -1 = GENERIC, the nine narrow FAST classes by number, every other number is 13
+template <class F>
+static void with_variant(int variant, F &&f) {
+  switch (variant) {
+    case -1: f(std::integral_constant<int, -1>{}); break;
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 9: f(std::integral_constant<int, 9>{}); break;
+    case 12: f(std::integral_constant<int, 12>{}); break;
+    default: f(std::integral_constant<int, 13>{}); break;
+  }
+}
+
+// a two-way choice: the 3-byte formats' byte order, the detector's offset class, the rows kernels' FAST
+template <class F>
+static void with_flag(bool on, F &&f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// the byte order of a 4-byte format: f(FIRST, BGR), FIRST = 0 (RGBx, BGRx) or 1 (xRGB, xBGR)
+template <class F>
+static void with_byte_order(int first, int bgr, F &&f) {
+  if (first == 0 && !bgr) f(std::integral_constant<int, 0>{}, std::false_type{});
+  else if (first == 0 && bgr) f(std::integral_constant<int, 0>{}, std::true_type{});
+  else if (first == 1 && !bgr) f(std::integral_constant<int, 1>{}, std::false_type{});
+  else f(std::integral_constant<int, 1>{}, std::true_type{});
+}
+
+static void launch_flat(mi355_ctx *ctx, int variant, uint4 *d, size_t n_vec, const HsvK &k, int first, int bgr, int grid) {
   const int nt = ctx->hsv_nt;
-  if (first == 0 && !bgr) hipLaunchKernelGGL((hsvfilter_flat_kernel<VARIANT, 0, false>), g, b, 0, ctx->stream, d, n_vec, k, nt);
-  else if (first == 0 && bgr) hipLaunchKernelGGL((hsvfilter_flat_kernel<VARIANT, 0, true>), g, b, 0, ctx->stream, d, n_vec, k, nt);
-  else if (first == 1 && !bgr) hipLaunchKernelGGL((hsvfilter_flat_kernel<VARIANT, 1, false>), g, b, 0, ctx->stream, d, n_vec, k, nt);
-  else hipLaunchKernelGGL((hsvfilter_flat_kernel<VARIANT, 1, true>), g, b, 0, ctx->stream, d, n_vec, k, nt);
+  with_variant(variant, [&](auto V) { with_byte_order(first, bgr, [&](auto FIRST, auto BGR) {
+    hipLaunchKernelGGL((hsvfilter_flat_kernel<V, FIRST, BGR>), dim3(grid), dim3(256), 0, ctx->stream, d, n_vec, k, nt);
+  }); });
 }
 
-template <int VARIANT>
-static void launch_flat_multi(hipStream_t stream, const MultiFramePtrs &frames, int n_frames, size_t n_vec, const HsvK &k, int first, int bgr, int grid_x) {
-  dim3 g(grid_x, n_frames), b(256);
-  if (first == 0 && !bgr) hipLaunchKernelGGL((hsvfilter_flat_multi_kernel<VARIANT, 0, false>), g, b, 0, stream, frames, n_vec, k);
-  else if (first == 0 && bgr) hipLaunchKernelGGL((hsvfilter_flat_multi_kernel<VARIANT, 0, true>), g, b, 0, stream, frames, n_vec, k);
-  else if (first == 1 && !bgr) hipLaunchKernelGGL((hsvfilter_flat_multi_kernel<VARIANT, 1, false>), g, b, 0, stream, frames, n_vec, k);
-  else hipLaunchKernelGGL((hsvfilter_flat_multi_kernel<VARIANT, 1, true>), g, b, 0, stream, frames, n_vec, k);
-}
-
-template <int VARIANT>
-static void launch_strided(mi355_ctx *ctx, uint8_t *d, int n_frames, size_t frame_pitch, int width, int height, int stride, const HsvK &k,
+static void launch_strided(mi355_ctx *ctx, int variant, uint8_t *d, int n_frames, size_t frame_pitch, int width, int height, int stride, const HsvK &k,
                            int first, int bgr, int grid) {
-  if ((n_frames == 1 || frame_pitch == (size_t)stride * (size_t)height) && (size_t)n_frames * (size_t)height < (1u << 31)) {
-    // padded rows only: the batch is one tall picture
-    const unsigned rows_total = (unsigned)n_frames * (unsigned)height, gx = ((unsigned)(width + 3) / 4 + 63) / 64;
-    unsigned gy = (rows_total + 3) / 4;
-    const unsigned cap = (unsigned)ctx->n_cu * (unsigned)ctx->hsv_blocks_per_cu / (gx ? gx : 1) + 1;
-    if (gy > cap) gy = cap;
-    if (gy > 65535) gy = 65535;
-    dim3 g2(gx, gy), b2(256);
-    if (first == 0 && !bgr) hipLaunchKernelGGL((hsvfilter_rowpad_kernel<VARIANT, 0, false>), g2, b2, 0, ctx->stream, d, rows_total, width, stride, k);
-    else if (first == 0 && bgr) hipLaunchKernelGGL((hsvfilter_rowpad_kernel<VARIANT, 0, true>), g2, b2, 0, ctx->stream, d, rows_total, width, stride, k);
-    else if (first == 1 && !bgr) hipLaunchKernelGGL((hsvfilter_rowpad_kernel<VARIANT, 1, false>), g2, b2, 0, ctx->stream, d, rows_total, width, stride, k);
-    else hipLaunchKernelGGL((hsvfilter_rowpad_kernel<VARIANT, 1, true>), g2, b2, 0, ctx->stream, d, rows_total, width, stride, k);
-    return;
-  }
-  dim3 g(grid), b(256);
-  if (first == 0 && !bgr) hipLaunchKernelGGL((hsvfilter_strided_kernel<VARIANT, 0, false>), g, b, 0, ctx->stream, d, n_frames, frame_pitch, width, height, stride, k);
-  else if (first == 0 && bgr) hipLaunchKernelGGL((hsvfilter_strided_kernel<VARIANT, 0, true>), g, b, 0, ctx->stream, d, n_frames, frame_pitch, width, height, stride, k);
-  else if (first == 1 && !bgr) hipLaunchKernelGGL((hsvfilter_strided_kernel<VARIANT, 1, false>), g, b, 0, ctx->stream, d, n_frames, frame_pitch, width, height, stride, k);
-  else hipLaunchKernelGGL((hsvfilter_strided_kernel<VARIANT, 1, true>), g, b, 0, ctx->stream, d, n_frames, frame_pitch, width, height, stride, k);
+  // padded rows only: the batch is one tall picture, for the rowpad kernel and its (gx, gy) grid; else the strided kernel on `grid`
+  const bool tall = (n_frames == 1 || frame_pitch == (size_t)stride * (size_t)height) && (size_t)n_frames * (size_t)height < (1u << 31);
+  const unsigned rows_total = (unsigned)n_frames * (unsigned)height, gx = ((unsigned)(width + 3) / 4 + 63) / 64;
+  unsigned gy = (rows_total + 3) / 4;
+  const unsigned cap = (unsigned)ctx->n_cu * (unsigned)ctx->hsv_blocks_per_cu / (gx ? gx : 1) + 1;
+  if (gy > cap) gy = cap;
+  if (gy > 65535) gy = 65535;
+  with_variant(variant, [&](auto V) {
+    if (tall) {
+      with_byte_order(first, bgr, [&](auto FIRST, auto BGR) {
+        hipLaunchKernelGGL((hsvfilter_rowpad_kernel<V, FIRST, BGR>), dim3(gx, gy), dim3(256), 0, ctx->stream, d, rows_total, width, stride, k);
+      });
+    } else {
+      with_byte_order(first, bgr, [&](auto FIRST, auto BGR) {
+        hipLaunchKernelGGL((hsvfilter_strided_kernel<V, FIRST, BGR>), dim3(grid), dim3(256), 0, ctx->stream, d, n_frames, frame_pitch, width, height, stride, k);
+      });
+    }
+  });
 }
 
-// Calls F<VARIANT>(args...) for the run-time variant number (hsv_variant_for).
-#define MI355_HSV_VARIANT_SWITCH(variant, F, ...)   \
-  switch (variant) {                                \
-    case -1: F<-1>(__VA_ARGS__); break;             \
-    case 0: F<0>(__VA_ARGS__); break;               \
-    case 1: F<1>(__VA_ARGS__); break;               \
-    case 2: F<2>(__VA_ARGS__); break;               \
-    case 4: F<4>(__VA_ARGS__); break;               \
-    case 5: F<5>(__VA_ARGS__); break;               \
-    case 6: F<6>(__VA_ARGS__); break;               \
-    case 8: F<8>(__VA_ARGS__); break;               \
-    case 9: F<9>(__VA_ARGS__); break;               \
-    case 12: F<12>(__VA_ARGS__); break;             \
-    default: F<13>(__VA_ARGS__); break;             \
-  }
+static void launch_rgb24x16(mi355_ctx *ctx, int variant, uint4 *d, size_t n_chunks, const HsvK &k, int bgr, int grid) {
+  with_variant(variant, [&](auto V) { with_flag(bgr != 0, [&](auto BGR) {
+    hipLaunchKernelGGL((hsvfilter_rgb24x16_kernel<V, BGR>), dim3(grid), dim3(256), 0, ctx->stream, d, n_chunks, k);
+  }); });
+}
+
+static void launch_rgb24(mi355_ctx *ctx, int variant, Rgb24x4 *d, size_t n_grp, const HsvK &k, int bgr, int grid) {
+  with_variant(variant, [&](auto V) { with_flag(bgr != 0, [&](auto BGR) {
+    hipLaunchKernelGGL((hsvfilter_rgb24_kernel<V, BGR>), dim3(grid), dim3(256), 0, ctx->stream, d, n_grp, k);
+  }); });
+}
 
 int launch_hsvfilter_compute(mi355_ctx *ctx, uint8_t *d_data, int n_frames, size_t frame_pitch, int width,
                      int height, int stride, const PixFmt &fmt, const mi355_hsv_settings &s) {
@@ -362,34 +369,32 @@ int launch_hsvfilter_compute(mi355_ctx *ctx, uint8_t *d_data, int n_frames, size
     // (one stream's buffer) are 10-15 % faster than with one group per lane (tools/r03_single_frame_launch.py)
     const int grid = grid_for(ctx, (n_vec + 1) / 2, 256, ctx->hsv_blocks_per_cu);
     uint4 *d = (uint4 *)d_data;
-    MI355_HSV_VARIANT_SWITCH(variant, launch_flat, ctx, d, n_vec, k, fmt.first, fmt.bgr, grid)
+    launch_flat(ctx, variant, d, n_vec, k, fmt.first, fmt.bgr, grid);
   } else if (fmt.pixel_stride == 4 && ((uintptr_t)d_data % 16 == 0) && stride % 16 == 0 && (n_frames == 1 || frame_pitch % 16 == 0)) {
     const size_t n_grp = (size_t)((width + 3) / 4) * (size_t)height * (size_t)n_frames;
     const int grid = grid_for(ctx, (n_grp + 1) / 2, 256, ctx->hsv_blocks_per_cu);
-    MI355_HSV_VARIANT_SWITCH(variant, launch_strided, ctx, d_data, n_frames, frame_pitch, width, height, stride, k, fmt.first, fmt.bgr, grid)
+    launch_strided(ctx, variant, d_data, n_frames, frame_pitch, width, height, stride, k, fmt.first, fmt.bgr, grid);
   } else if (fmt.pixel_stride == 3 && fmt.first == 0 && packed_rows && ((uintptr_t)d_data % 4 == 0) && (total_bytes % 12 == 0)) {
     // whole 3 KB chunks (1024 pixels) through the coalescing kernel when the base is 16-byte aligned, the rest 12 bytes per lane
     const size_t n_chunks = ((uintptr_t)d_data % 16 == 0) ? total_bytes / 3072 : 0;
     if (n_chunks) {
       const int grid = grid_for(ctx, n_chunks * 64, 256, ctx->hsv_blocks_per_cu / 2);
-      MI355_HSV_VARIANT_SWITCH(variant, launch_rgb24x16, ctx, (uint4 *)d_data, n_chunks, k, fmt.bgr, grid)
+      launch_rgb24x16(ctx, variant, (uint4 *)d_data, n_chunks, k, fmt.bgr, grid);
     }
     const size_t n_grp = (total_bytes - n_chunks * 3072) / 12;
     if (n_grp) {
       const int grid = grid_for(ctx, n_grp, 256, ctx->hsv_blocks_per_cu);
       Rgb24x4 *d = (Rgb24x4 *)(d_data + n_chunks * 3072);
-      MI355_HSV_VARIANT_SWITCH(variant, launch_rgb24, ctx, d, n_grp, k, fmt.bgr, grid)
+      launch_rgb24(ctx, variant, d, n_grp, k, fmt.bgr, grid);
     }
   } else {
     const size_t total = (size_t)width * (size_t)height * (size_t)n_frames;
     const int grid = grid_for(ctx, total, 256, 32);
     // one pixel per lane: the single-pixel FAST routine knows the narrow shift classes only
-    if (hsv_variant_for(s, ctx->force_generic, false) >= 0)
-      hipLaunchKernelGGL((hsvfilter_rows_kernel<true>), dim3(grid), dim3(256), 0, ctx->stream, d_data, n_frames,
+    with_flag(hsv_variant_for(s, ctx->force_generic, false) >= 0, [&](auto FAST) {
+      hipLaunchKernelGGL((hsvfilter_rows_kernel<FAST>), dim3(grid), dim3(256), 0, ctx->stream, d_data, n_frames,
                          frame_pitch, width, height, stride, fmt.pixel_stride, fmt.first, fmt.bgr, k);
-    else
-      hipLaunchKernelGGL((hsvfilter_rows_kernel<false>), dim3(grid), dim3(256), 0, ctx->stream, d_data, n_frames,
-                         frame_pitch, width, height, stride, fmt.pixel_stride, fmt.first, fmt.bgr, k);
+    });
   }
   return check_hip(ctx, hipGetLastError(), "hsvfilter kernel launch");
 }
@@ -403,6 +408,11 @@ bool hsvfilter_multi_applicable(const uint8_t *const *frames, int n_frames, int 
     if (!frames[f] || (uintptr_t)frames[f] % 16 != 0) return false;
   return true;
 }
+static void launch_flat_multi(hipStream_t stream, int variant, const MultiFramePtrs &frames, int n_frames, size_t n_vec, const HsvK &k, int first, int bgr, int grid_x) {
+  with_variant(variant, [&](auto V) { with_byte_order(first, bgr, [&](auto FIRST, auto BGR) {
+    hipLaunchKernelGGL((hsvfilter_flat_multi_kernel<V, FIRST, BGR>), dim3(grid_x, n_frames), dim3(256), 0, stream, frames, n_vec, k);
+  }); });
+}
 int launch_hsvfilter_multi(mi355_ctx *ctx, hipStream_t stream, uint8_t *const *frames, int n_frames, int width, int height, const PixFmt &fmt,
                            const mi355_hsv_settings &s) {
   const HsvK k{s.hue_shift, s.saturation_mul, s.saturation_off, s.value_mul, s.value_off};
@@ -413,7 +423,7 @@ int launch_hsvfilter_multi(mi355_ctx *ctx, hipStream_t stream, uint8_t *const *f
   // the same total grid as one launch over n contiguous frames would get, split evenly over the frames
   int gx = grid_for(ctx, ((size_t)n_frames * n_vec + 1) / 2, 256, ctx->hsv_blocks_per_cu) / n_frames;
   if (gx < 1) gx = 1;
-  MI355_HSV_VARIANT_SWITCH(variant, launch_flat_multi, stream, ptrs, n_frames, n_vec, k, fmt.first, fmt.bgr, gx)
+  launch_flat_multi(stream, variant, ptrs, n_frames, n_vec, k, fmt.first, fmt.bgr, gx);
   return check_hip(ctx, hipGetLastError(), "hsvfilter multi-frame kernel launch");
 }
 
@@ -580,19 +590,9 @@ int launch_hsvdetect(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int
     const uint32_t sel = hsvdetect_out_sel(in_pos, dst_alpha_first, dst_bgr);
     const size_t n_vec = total / 4;
     const int fgrid = grid_for(ctx, (n_vec + 1) / 2, 256, 64);   // two groups per lane, as the hsvfilter kernels (one-frame launches)
-    dim3 g(fgrid), b(256);
-    const uint4 *sp = (const uint4 *)d_src;
-    uint4 *dp = (uint4 *)d_dst;
-#define MI355_DET_LAUNCH(F, B)                                                                                              \
-    do {                                                                                                                    \
-      if (neg) hipLaunchKernelGGL((hsvdetect_flat_kernel<F, B, true>), g, b, 0, ctx->stream, sp, dp, n_vec, k, sel);       \
-      else hipLaunchKernelGGL((hsvdetect_flat_kernel<F, B, false>), g, b, 0, ctx->stream, sp, dp, n_vec, k, sel);          \
-    } while (0)
-    if (sfmt.first == 0 && !sfmt.bgr) MI355_DET_LAUNCH(0, false);
-    else if (sfmt.first == 0 && sfmt.bgr) MI355_DET_LAUNCH(0, true);
-    else if (sfmt.first == 1 && !sfmt.bgr) MI355_DET_LAUNCH(1, false);
-    else MI355_DET_LAUNCH(1, true);
-#undef MI355_DET_LAUNCH
+    with_byte_order(sfmt.first, sfmt.bgr, [&](auto FIRST, auto BGR) { with_flag(neg, [&](auto NEG) {
+      hipLaunchKernelGGL((hsvdetect_flat_kernel<FIRST, BGR, NEG>), dim3(fgrid), dim3(256), 0, ctx->stream, (const uint4 *)d_src, (uint4 *)d_dst, n_vec, k, sel);
+    }); });
     return check_hip(ctx, hipGetLastError(), "hsvdetect flat kernel launch");
   }
   if (path == HSVDET_RGB24) {
@@ -600,10 +600,9 @@ int launch_hsvdetect(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int
     const uint32_t sel = hsvdetect_out_sel(in_pos, dst_alpha_first, dst_bgr);
     const size_t n_grp = total / 4;
     const int fgrid = grid_for(ctx, n_grp, 256, 64);
-    if (sfmt.bgr && neg) hipLaunchKernelGGL((hsvdetect_rgb24_kernel<true, true>), dim3(fgrid), dim3(256), 0, ctx->stream, (const Rgb24x4 *)d_src, (uint4 *)d_dst, n_grp, k, sel);
-    else if (sfmt.bgr) hipLaunchKernelGGL((hsvdetect_rgb24_kernel<true, false>), dim3(fgrid), dim3(256), 0, ctx->stream, (const Rgb24x4 *)d_src, (uint4 *)d_dst, n_grp, k, sel);
-    else if (neg) hipLaunchKernelGGL((hsvdetect_rgb24_kernel<false, true>), dim3(fgrid), dim3(256), 0, ctx->stream, (const Rgb24x4 *)d_src, (uint4 *)d_dst, n_grp, k, sel);
-    else hipLaunchKernelGGL((hsvdetect_rgb24_kernel<false, false>), dim3(fgrid), dim3(256), 0, ctx->stream, (const Rgb24x4 *)d_src, (uint4 *)d_dst, n_grp, k, sel);
+    with_flag(sfmt.bgr != 0, [&](auto BGR) { with_flag(neg, [&](auto NEG) {
+      hipLaunchKernelGGL((hsvdetect_rgb24_kernel<BGR, NEG>), dim3(fgrid), dim3(256), 0, ctx->stream, (const Rgb24x4 *)d_src, (uint4 *)d_dst, n_grp, k, sel);
+    }); });
     return check_hip(ctx, hipGetLastError(), "hsvdetect rgb24 kernel launch");
   }
   const int grid = grid_for(ctx, total, 256, 32);
@@ -617,7 +616,8 @@ int launch_hsvdetect(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int
 //
 // Frames of independent element instances - each with its own geometry, formats and settings - in at most two launches over a
 // job table. The table travels in the kernel arguments (no upload, no lifetime); a block's job index comes from blockIdx alone,
-// so the search and every job field are scalar and the path choices below are the same for all waves of a block.
+// so the search and every job field are scalar and the path choices below are the same for all waves of a block. The host side is
+// hsvdetect_launch_set: it sorts the frames into the two tables of a JobSet, which plans and launches them (hsvfilter's sets too).
 //   hsvdetect_jobs_kernel       the jobs the lone entry gives to hsvdetect_flat_kernel or hsvdetect_rgb24_kernel: four pixels per
 //                               lane through hsvdetect_quad. One v_perm_b32 brings a job's byte order to R,G,B,0; the arithmetic
 //                               reads byte values only, so it is that of the <RPOS, GPOS, BPOS> instance the lone entry picks.
@@ -739,18 +739,61 @@ int hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_
   return MI355_OK;
 }
 
+// A launch set: the two job tables (HdJobTable, HfJobTable) that hsvdetect_launch_set and hsvfilter_set_build classify frames into
+// and fill, and their grids. Planned and launched here, for both elements.
+//   kVec  four pixels per lane: 512 units per block (two groups per lane), 64 blocks per CU - the lone grid_for(ctx, (n_vec + 1) / 2, 256, 64)
+//   kLit  one pixel per lane, literally: 256 units per block, 32 blocks per CU - the lone grid_for(ctx, total, 256, 32)
+namespace {  // (host only, this file only)
+enum { kVec = 0, kLit = 1 };
+template <class Table>
+struct JobSet {
+  typedef void (*Kernel)(const Table);
+  Table table[2];
+  uint32_t blocks[2];
+
+  // first_block / blocks of every job, by hsvdetect_plan over the jobs' own units; a table with a job has at least one block
+  int plan(int n_cu) {
+    constexpr int kMax = (int)(sizeof(Table::job) / sizeof(Table::job[0]));
+    static_assert(kMax <= kHdSetMax, "hsvdetect_plan takes up to kHdSetMax jobs");
+    const unsigned per_block[2] = {512, 256};
+    const int per_cu[2] = {64, 32};
+    for (int h = 0; h < 2; h++) {
+      Table &T = table[h];
+      uint64_t units[kMax];
+      uint32_t first[kMax], n[kMax];
+      for (int j = 0; j < T.n_jobs; j++) units[j] = T.job[j].units;
+      const int rc = hsvdetect_plan(n_cu, per_cu[h], per_block[h], T.n_jobs, units, first, n, &blocks[h]);
+      if (rc || (T.n_jobs && !blocks[h])) return rc ? rc : MI355_ERR_INVALID_ARG;
+      for (int j = 0; j < T.n_jobs; j++) { T.job[j].first_block = first[j]; T.job[j].blocks = n[j]; }
+    }
+    return MI355_OK;
+  }
+
+  // whichever table has a job goes out on `stream`; *kernel_launches counts on. what[h]: the launch's name in the error text
+  int launch(hipStream_t stream, const Kernel (&kernel)[2], const char *const (&what)[2], int *kernel_launches, std::string *err) const {
+    for (int h = 0; h < 2; h++) {
+      if (!table[h].n_jobs) continue;
+      hipLaunchKernelGGL(kernel[h], dim3(blocks[h]), dim3(256), 0, stream, table[h]);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) { *err = std::string(what[h]) + hipGetErrorString(e); return MI355_ERR_HIP; }
+      (*kernel_launches)++;
+    }
+    return MI355_OK;
+  }
+};
+}  // namespace
+
 int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, int n, int *kernel_launches, std::string *err) {
   *kernel_launches = 0;
   if (!frames || n < 1 || n > kHdSetMax) { *err = "hsvdetector: bad launch set"; return MI355_ERR_INVALID_ARG; }
-  HdJobTable vec{}, lit{};
-  uint64_t vec_units[kHdSetMax], lit_units[kHdSetMax];
+  JobSet<HdJobTable> S{};
   for (int i = 0; i < n; i++) {
     const HdFrame &f = frames[i];
     if (f.width <= 0 || f.height <= 0) continue;  // no pixel: no job
     const size_t total = (size_t)f.width * (size_t)f.height;
     const HsvDetPath path = hsvdetect_path(f.force_generic, f.src, 0, f.src_stride, f.sfmt, f.dst, 0, f.dst_stride, 1, f.width, f.height, f.s);
-    HdJobTable &T = path == HSVDET_ROWS ? lit : vec;
-    HdJob &J = T.job[T.n_jobs];
+    HdJobTable &T = S.table[path == HSVDET_ROWS ? kLit : kVec];
+    HdJob &J = T.job[T.n_jobs++];
     J.src = f.src;
     J.dst = f.dst;
     J.width = f.width;
@@ -761,7 +804,6 @@ int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, in
               (f.dst_alpha_first ? HD_OUT_ALPHA_FIRST : 0u) | (f.dst_bgr ? HD_OUT_BGR : 0u) | (f.sfmt.first ? HD_IN_FIRST : 0u);
     if (path == HSVDET_ROWS) {
       J.units = total;
-      lit_units[T.n_jobs] = J.units;
     } else {
       // canonical word: R, G, B at bytes 0, 1, 2 and a zero (selector 0x0c) - the lone kernels' selector with in_pos = {0, 1, 2}
       const int rpos = f.sfmt.first + (f.sfmt.bgr ? 2 : 0), gpos = f.sfmt.first + 1, bpos = f.sfmt.first + (f.sfmt.bgr ? 0 : 2);
@@ -769,27 +811,10 @@ int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, in
       J.in_sel = (uint32_t)(4 + rpos) | ((uint32_t)(4 + gpos) << 8) | ((uint32_t)(4 + bpos) << 16) | (0x0cu << 24);
       J.out_sel = hsvdetect_out_sel(canon, f.dst_alpha_first, f.dst_bgr);
       J.units = total / 4;
-      vec_units[T.n_jobs] = J.units;
     }
-    T.n_jobs++;
   }
-  struct Launch { HdJobTable *T; const uint64_t *units; unsigned per_block; int per_cu; bool vector; };
-  // vector: two groups per lane and the cap of the lone grid_for(ctx, (n_vec + 1) / 2, 256, 64); literal: grid_for(ctx, total, 256, 32)
-  const Launch launches[2] = {{&vec, vec_units, 512, 64, true}, {&lit, lit_units, 256, 32, false}};
-  for (const Launch &L : launches) {
-    HdJobTable &T = *L.T;
-    if (!T.n_jobs) continue;
-    uint32_t first[kHdSetMax], blocks[kHdSetMax], total_blocks = 0;
-    const int rc = hsvdetect_plan(n_cu, L.per_cu, L.per_block, T.n_jobs, L.units, first, blocks, &total_blocks);
-    if (rc || !total_blocks) { *err = "hsvdetector: bad launch set"; return rc ? rc : MI355_ERR_INVALID_ARG; }
-    for (int j = 0; j < T.n_jobs; j++) { T.job[j].first_block = first[j]; T.job[j].blocks = blocks[j]; }
-    if (L.vector) hipLaunchKernelGGL(hsvdetect_jobs_kernel, dim3(total_blocks), dim3(256), 0, stream, T);
-    else hipLaunchKernelGGL(hsvdetect_rows_jobs_kernel, dim3(total_blocks), dim3(256), 0, stream, T);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { *err = std::string(L.vector ? "hsvdetect jobs kernel launch: " : "hsvdetect rows jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
-    (*kernel_launches)++;
-  }
-  return MI355_OK;
+  if (const int rc = S.plan(n_cu)) { *err = "hsvdetector: bad launch set"; return rc; }
+  return S.launch(stream, {hsvdetect_jobs_kernel, hsvdetect_rows_jobs_kernel}, {"hsvdetect jobs kernel launch: ", "hsvdetect rows jobs kernel launch: "}, kernel_launches, err);
 }
 
 // ---------------------------------------------------------------- hsvfilter launch sets (the video group's filter queue)
@@ -819,6 +844,7 @@ int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, in
 // In place means order matters: two jobs of one launch never touch the same bytes. hsvfilter_set_build closes a set in front of a
 // frame whose byte range [data, data + (height - 1) stride + width pixel_stride) meets that of a frame already in it (ranges only:
 // conservative), and sets run one after the other on the queue's stream - overlapping frames come out as if filtered in order.
+// The host side is that builder and the detector's JobSet: hsvfilter_launch_set builds, then launches each set.
 enum : uint32_t { HF_PX3 = 1u, HF_BGR = 2u, HF_FIRST = 4u, HF_ROWPAD = 8u };
 struct HfJob {
   uint8_t *data;
@@ -961,15 +987,14 @@ bool hsvfilter_frames_overlap(const HfFrame &a, const HfFrame &b) {
   return a0 < b1 && b0 < a1;
 }
 
-// The ONE builder of launch sets, for hsvfilter_launch_set and mi355_selftest_hsvfilter_set_plan alike: classifies the frames,
-// computes variants and selectors, closes a set at kHfSetMax frames and in front of a frame that overlaps one already in it, and
-// plans the blocks of each set's two launches. The frames' addresses are numbers here: nothing is dereferenced. `out` (per frame)
-// may be null.
-struct HfSet { HfJobTable vec, lit; uint32_t vec_blocks, lit_blocks; };
+// The ONE builder of launch sets, for hsvfilter_launch_set and mi355_selftest_hsvfilter_set_plan alike: closes a set at kHfSetMax
+// frames and in front of a frame that overlaps one already in it, classifies each set's frames into its two tables with their
+// variants and selectors, and has JobSet plan the blocks. The frames' addresses are numbers here: nothing is dereferenced. `out` (per
+// frame) may be null.
+typedef JobSet<HfJobTable> HfSet;
 static int hsvfilter_set_build(int n_cu, const HfFrame *frames, int n, std::vector<HfSet> *sets, mi355_hsvfilter_plan_out *out) {
   sets->clear();
   if (n_cu < 1 || n < 0 || (n && !frames)) return MI355_ERR_INVALID_ARG;
-  struct Slot { int frame; bool vector; int job; };
   for (int begin = 0; begin < n;) {
     int end = begin;
     for (; end < n && end - begin < kHfSetMax; end++) {
@@ -980,9 +1005,6 @@ static int hsvfilter_set_build(int n_cu, const HfFrame *frames, int n, std::vect
     sets->emplace_back();
     HfSet &S = sets->back();
     std::memset(&S, 0, sizeof(S));
-    uint64_t vec_units[kHfSetMax], lit_units[kHfSetMax];
-    Slot slot[kHfSetMax];
-    int n_slots = 0;
     for (int i = begin; i < end; i++) {
       const HfFrame &f = frames[i];
       if (out) out[i] = mi355_hsvfilter_plan_out{(int32_t)sets->size() - 1, 0, -1, 0, 0, 0, 0};
@@ -995,8 +1017,8 @@ static int hsvfilter_set_build(int n_cu, const HfFrame *frames, int n, std::vect
                                                 : f.fmt.first == 0 && packed && at % 4 == 0 && total_bytes % 12 == 0;
       const bool rowpad = !flat && f.fmt.pixel_stride == 4 && at % 16 == 0 && f.stride % 16 == 0;
       const bool vector = wide_variant >= 0 && (flat || rowpad);
-      HfJobTable &T = vector ? S.vec : S.lit;
-      HfJob &J = T.job[T.n_jobs];
+      HfJobTable &T = S.table[vector ? kVec : kLit];
+      HfJob &J = T.job[T.n_jobs++];
       J.data = f.data;
       J.k = HsvK{f.s.hue_shift, f.s.saturation_mul, f.s.saturation_off, f.s.value_mul, f.s.value_off};
       J.width = f.width;
@@ -1012,35 +1034,21 @@ static int hsvfilter_set_build(int n_cu, const HfFrame *frames, int n, std::vect
         J.variant = wide_variant;
         if (rowpad) J.flags |= HF_ROWPAD;
         J.units = rowpad ? (uint64_t)(((uint32_t)f.width + 3u) / 4u) * (uint64_t)f.height : total_bytes / (f.fmt.pixel_stride == 4 ? 16 : 12);
-        vec_units[T.n_jobs] = J.units;
       } else {
         // one pixel per lane: the single-pixel FAST routine knows the narrow shift classes only (as the lone rows kernel's choice)
         J.variant = hsv_variant_for(f.s, f.force_generic != 0, false);
         J.units = (uint64_t)f.width * (uint64_t)f.height;
-        lit_units[T.n_jobs] = J.units;
       }
-      slot[n_slots++] = Slot{i, vector, T.n_jobs};
-      T.n_jobs++;
+      if (out) { out[i].launch = 1 + (vector ? kVec : kLit); out[i].variant = J.variant; out[i].units = J.units; }
     }
-    // vector: two groups per lane and the cap of the lone grid_for(ctx, (n_vec + 1) / 2, 256, 64); literal: grid_for(ctx, total, 256, 32)
-    struct Launch { HfJobTable *T; const uint64_t *units; unsigned per_block; int per_cu; uint32_t *total; };
-    const Launch launches[2] = {{&S.vec, vec_units, 512, 64, &S.vec_blocks}, {&S.lit, lit_units, 256, 32, &S.lit_blocks}};
-    for (const Launch &L : launches) {
-      uint32_t first[kHfSetMax], blocks[kHfSetMax];
-      const int rc = hsvdetect_plan(n_cu, L.per_cu, L.per_block, L.T->n_jobs, L.units, first, blocks, L.total);
-      if (rc) return rc;
-      for (int j = 0; j < L.T->n_jobs; j++) { L.T->job[j].first_block = first[j]; L.T->job[j].blocks = blocks[j]; }
+    if (const int rc = S.plan(n_cu)) return rc;
+    int next[2] = {0, 0};   // a table's jobs are in the order of their frames
+    for (int i = begin; out && i < end; i++) {
+      if (!out[i].launch) continue;
+      const HfJob &J = S.table[out[i].launch - 1].job[next[out[i].launch - 1]++];
+      out[i].first_block = J.first_block;
+      out[i].blocks = J.blocks;
     }
-    if (out)
-      for (int k = 0; k < n_slots; k++) {
-        const HfJob &J = (slot[k].vector ? S.vec : S.lit).job[slot[k].job];
-        mi355_hsvfilter_plan_out &o = out[slot[k].frame];
-        o.launch = slot[k].vector ? 1 : 2;
-        o.variant = J.variant;
-        o.first_block = J.first_block;
-        o.blocks = J.blocks;
-        o.units = J.units;
-      }
     begin = end;
   }
   return MI355_OK;
@@ -1059,20 +1067,8 @@ int hsvfilter_launch_set(hipStream_t stream, int n_cu, const HfFrame *frames, in
   std::vector<HfSet> sets;
   if (const int rc = hsvfilter_set_build(n_cu, frames, n, &sets, nullptr)) { *err = "hsvfilter: bad launch set"; return rc; }
   // (one set, unless the caller handed over frames that overlap: then their sets, in order on the one stream)
-  for (const HfSet &S : sets) {
-    if (S.vec.n_jobs) {
-      hipLaunchKernelGGL(hsvfilter_jobs_kernel, dim3(S.vec_blocks), dim3(256), 0, stream, S.vec);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) { *err = std::string("hsvfilter jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
-      (*kernel_launches)++;
-    }
-    if (S.lit.n_jobs) {
-      hipLaunchKernelGGL(hsvfilter_rows_jobs_kernel, dim3(S.lit_blocks), dim3(256), 0, stream, S.lit);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) { *err = std::string("hsvfilter rows jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
-      (*kernel_launches)++;
-    }
-  }
+  for (const HfSet &S : sets)
+    if (const int rc = S.launch(stream, {hsvfilter_jobs_kernel, hsvfilter_rows_jobs_kernel}, {"hsvfilter jobs kernel launch: ", "hsvfilter rows jobs kernel launch: "}, kernel_launches, err)) return rc;
   return MI355_OK;
 }
 

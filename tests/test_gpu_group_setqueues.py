@@ -1,15 +1,16 @@
-"""The set-queue protocol of the dispatcher (csrc/group.hip, SetQueue<Kind>) for four of its kinds - colordetect, hsvdetector,
-decoder and the videocompare pairs (the hand decoder's queue is the subject of its own file) - one script per path the per-queue files leave open,
+"""The set-queue protocol of the dispatcher (csrc/group.hip, SetQueue<Kind>) for five of its kinds - colordetect, hsvdetector,
+hsvfilter, decoder and the videocompare pairs (the hand decoder's queue is the subject of its own file) - one script per path the per-queue files leave open,
 each run for every kind through a small adaptor: sets collected out of order (Q1), more sets in flight than the blocks of first
 use (Q2), flush (Q3), a wait for a ticket in the middle of the pending list (Q4) and all kinds in one group (Q5). One thread, no
 rendezvous: every step is deterministic. The compare queue is the kind with lanes: a launch set goes out as up to eight parts on
 eight streams, and what Q1 collects in reverse it collects per lane.
 
 The bar is `==` against the lone entry on the same Context and the same device bytes (Context.colordetect_frames_device,
-Context.hsvdetect_frames_device, Context.yolodec_device with one tensor, Context.dssim_create_image_device +
+Context.hsvdetect_frames_device, Context.hsvfilter_frames_device, Context.yolodec_device with one tensor, Context.dssim_create_image_device +
 dssim_compare_frames_device), computed once per item of this module. Items differ by seed, so a result handed to the wrong ticket
 is seen. The stats' launches column follows each kind's launch rule: colordetect one histogram and one MMCQ launch per set;
-hsvdetector one launch for a set of vector-class frames (all frames here are packed, aligned and on the dial); decoder one score
+hsvdetector and hsvfilter one launch for a set of vector-class frames (all frames here are packed and aligned, the detector's on the
+dial, the filter's with finite settings and a hue shift within +-360); decoder one score
 launch per layout present and one NMS launch; the compare queue reports none."""
 import numpy as np
 import pytest
@@ -130,6 +131,67 @@ class Hsvdetect:
             self.c.free(p)
 
 
+class Hsvfilter:
+    """The result of a frame is what its slice holds after the wait: frames are filtered IN PLACE, each in a slice of its own of one
+    arena, so no two overlap. reset() puts the source bytes back into the group's arena; the lone entry filters a second arena that
+    holds the same bytes. The 3-byte formats fill the first three quarters of their slice; the rest must come back untouched."""
+    name = "hsvfilter"
+    FMTS = ("RGBx", "xRGB", "BGRx", "xBGR", "RGBA", "ARGB", "BGRA", "ABGR", "RGB", "BGR")
+
+    def __init__(self, c):
+        self.c, self._lone = c, None
+        self.fb = W * H * 4
+        n = N_ITEMS * self.fb
+        self.src = np.random.default_rng(5000).integers(0, 256, n, dtype=np.uint8)
+        self.dg, self.dl = c.alloc(n), c.alloc(n)
+        c.h2d(self.dl, self.src)
+        self.reset()
+
+    def _args(self, i, arena):
+        fmt = self.FMTS[i % 10]
+        ident = i % 4 == 0                                                            # identity saturation / value: the other variants
+        st = ((0.0, 90.0, -120.0, 360.0, -360.0, 45.5, -0.25)[i % 7],) + ((1.0, 0.0, 1.0, 0.0) if ident else
+                                                                           (0.5 + 0.25 * (i % 5), 0.1 * (i % 3 - 1), 0.6 + 0.2 * (i % 3), 0.05 * (i % 4 - 1)))
+        return arena + i * self.fb, W, H, W * (3 if fmt in ("RGB", "BGR") else 4), fmt, st
+
+    def reset(self):
+        self.c.h2d(self.dg, self.src)
+
+    def submit(self, g, i):
+        return g.submit_hsvfilter(self.c, *self._args(i, self.dg))
+
+    def wait(self, g, i, ticket):
+        g.wait_hsvfilter(ticket)
+        got = np.zeros(self.fb, np.uint8)
+        self.c.d2h(got, self.dg + i * self.fb)
+        return got.tobytes()
+
+    def lone(self, i):
+        if self._lone is None:
+            for k in range(N_ITEMS):
+                d, w, h, stride, fmt, st = self._args(k, self.dl)
+                self.c.hsvfilter_frames_device(d, 1, 0, w, h, stride, fmt, st)
+            self.c.synchronize()
+            all_ = np.zeros(N_ITEMS * self.fb, np.uint8)
+            self.c.d2h(all_, self.dl)
+            assert (all_ != self.src).any()
+            self._lone = [all_[k * self.fb: (k + 1) * self.fb].tobytes() for k in range(N_ITEMS)]
+        return self._lone[i]
+
+    def key(self, result):
+        return result
+
+    def stats(self, g):
+        return g.hsvfilter_stats()
+
+    def launches(self, idx):
+        return 1
+
+    def free(self):
+        for p in (self.dg, self.dl):
+            self.c.free(p)
+
+
 class Yolodec:
     name = "yolodec"
 
@@ -230,7 +292,7 @@ class Compare:
             self.c.free(it[1])
 
 
-KINDS = {"colordetect": Colordetect, "hsvdetect": Hsvdetect, "yolodec": Yolodec, "compare": Compare}
+KINDS = {"colordetect": Colordetect, "hsvdetect": Hsvdetect, "hsvfilter": Hsvfilter, "yolodec": Yolodec, "compare": Compare}
 
 
 @pytest.fixture(scope="module")
@@ -369,7 +431,7 @@ def test_q5_all_kinds_in_one_group(pools):
     try:
         tk = {}
         for i in range(n):
-            for a in kinds:                                                           # interleaved: cd, hd, yd, cmp, cd, hd, yd, cmp, ...
+            for a in kinds:                                                           # interleaved: cd, hd, hf, yd, cmp, cd, hd, hf, yd, cmp, ...
                 tk[a.name, i] = a.submit(g, i)
         assert len(set(tk.values())) == nk * n                                        # one ticket sequence
         for a in kinds:

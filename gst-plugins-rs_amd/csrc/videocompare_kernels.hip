@@ -410,8 +410,9 @@ int launch_imghash(mi355_ctx *ctx, const uint8_t *d_frames, size_t frame_pitch, 
   std::vector<float> wts;
   ih_weights(height, rh, &vw, &wts);
   ih_weights(width, rw, &hw, &wts);
-  // scratch (slot 1): weights | tmp [n_frames][rh][width] f32 | hashes
-  const size_t wbytes = (wts.size() * 4 + 15) & ~(size_t)15, tbytes = (size_t)n_frames * rh * width * 4;
+  // scratch (slot 1): weights | tmp [n_frames][rh][width] f32 | hashes (u64: tmp's bytes are rounded up to 8, an odd
+  // n_frames * rh * width would leave the array 4 bytes off its alignment)
+  const size_t wbytes = (wts.size() * 4 + 15) & ~(size_t)15, tbytes = ((size_t)n_frames * rh * width * 4 + 7) & ~(size_t)7;
   const size_t need = wbytes + tbytes + (size_t)n_frames * 8;
   if (ctx->d_stage_bytes[1] < need) {
     if (ctx->d_stage[1]) (void)hipFree(ctx->d_stage[1]);

@@ -8,6 +8,8 @@ import threading
 import numpy as np
 import pytest
 
+import videocompare_cases as V
+
 pytestmark = pytest.mark.gpu
 
 
@@ -164,6 +166,40 @@ def test_blockhash_pairs_and_mixed_classes_in_one_queue(mi355lib, oracle):
         assert g.compare_stats()[1] == 4   # blockhash RGBA 640x480 / dssim 128x96 / blockhash RGB 320x240 / dssim 322x246
         for j in jobs:
             c.free(j[6]); c.free(j[7])
+    finally:
+        g.close()
+        c.close()
+
+
+@pytest.mark.parametrize("name,w,h,stride,off,k_ref,k_frame", V.GROUP_CASES, ids=[c[0] for c in V.GROUP_CASES])
+def test_blockhash_pairs_take_the_lone_contexts_routes(mi355lib, oracle, name, w, h, stride, off, k_ref, k_frame):
+    """blockhash_enqueue chooses the sum kernel frame by frame (tests/videocompare_cases.py, GROUP_CASES): a padded stride, a second
+    frame 4 bytes past a 16-byte boundary (one pair then mixes the vector and the bytes kernel), a narrow frame. Three pairs in one
+    launch set, on poisoned rows; (dist, h0, h1) == the oracle's hashes, their Hamming distance, the lone context's hashes."""
+    import mi355fx
+    c = mi355fx.Context(0)
+    g = mi355fx.Group(0)
+    try:
+        frames = V.random_frames("group-" + name, 6, w, h, 4)
+        exp = [oracle.blockhash(f, w, h, w * 4, 4) for f in frames]
+        ptrs = []
+        for k, f in enumerate(frames):
+            lead = off if k % 2 else 0
+            buf = V.pack(f[None], w, h, 4, stride, stride * h, lead)
+            d = c.alloc(buf.size + 16)
+            c.h2d(d, buf)
+            ptrs.append((d, lead))
+            assert V.route(w, h, 4, stride, None, (d + lead) % 16, 1, False) == (k_frame if k % 2 else k_ref)
+        own = [c.videocompare_hash_frames_device(d + lead, stride * h, stride, 1, w, h, "RGBA")[0] for d, lead in ptrs]
+        assert own == exp
+        tk = [g.submit_compare(c, ptrs[2 * p][0], ptrs[2 * p + 1][0] + ptrs[2 * p + 1][1], stride, w, h, "RGBA", 4) for p in range(3)]
+        for p in (2, 0, 1):
+            dist, h0, h1 = g.wait_compare(tk[p])
+            assert (h0, h1) == (exp[2 * p], exp[2 * p + 1])
+            assert dist == float(bin(h0 ^ h1).count("1")) == oracle.hash_distance(h0, h1) and dist > 0
+        assert g.compare_stats() == (3, 1, 3)
+        for d, _ in ptrs:
+            c.free(d)
     finally:
         g.close()
         c.close()

@@ -354,7 +354,7 @@ struct YdSlot { uint32_t num_candidates, max_dets; uint64_t det_offset; };
 struct YdKind : OneLane<YdTensor> {
   using Payload = YdTensor;
   using Result = YdOut;
-  struct Plan { YdTensor tensors[kYdSetMax]; uint64_t det_off[kYdSetMax], totals[8]; };
+  struct Plan { YdTensor tensors[kYdSetMax]; YdSetPlan set; };
   struct SetData {
     // the set's own results until it is collected, and behind them the tables of its heads (h == nullptr: no member had a candidate)
     PinnedBlock block;
@@ -382,27 +382,16 @@ struct YdKind : OneLane<YdTensor> {
   }
   // the set's layout, before anything is taken for it: the plan the launch itself uses says how large the set's block has to be
   int plan(const QItem<YdTensor> *take, size_t n, Plan *p, std::string *err) const {
-    int layout[kYdSetMax], n_levels[kYdSetMax];
-    uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], n_blocks[kYdSetMax];
-    uint32_t lv_h[kYdSetMax * MI355_YOLOX_LEVELS_MAX], lv_w[kYdSetMax * MI355_YOLOX_LEVELS_MAX], lv_first[kYdSetMax * MI355_YOLOX_LEVELS_MAX];
-    uint64_t key_off[kYdSetMax], box_off[kYdSetMax];
-    size_t n_lv = 0;
-    for (size_t i = 0; i < n; i++) {
-      const YdTensor &t = p->tensors[i] = take[i].p;
-      layout[i] = t.layout; F[i] = t.num_fields; N[i] = t.num_candidates; cap[i] = t.max_dets;
-      n_levels[i] = t.head ? t.head->n_levels : 0;   // 1..8: checked at submit
-      for (int l = 0; l < n_levels[i]; l++, n_lv++) { lv_h[n_lv] = t.head->lv[l].h; lv_w[n_lv] = t.head->lv[l].w; }
-    }
-    for (uint64_t &t : p->totals) t = 0;
-    const int rc = yolodec_mixed_set_plan((int)n, layout, F, N, cap, n_levels, lv_h, lv_w, N, first, n_blocks, key_off, box_off, p->det_off, lv_first, p->totals);
+    for (size_t i = 0; i < n; i++) p->tensors[i] = take[i].p;
+    const int rc = yolodec_plan_set(p->tensors, (int)n, &p->set);
     if (rc) *err = "group: bad decoder set";
     return rc;
   }
   // a set without a candidate has nothing to copy: it takes no block (and still gets its event and its set)
-  size_t block_bytes(const Plan &p) const { return p.totals[2] ? yolodec_set_block_bytes(p.totals[5], p.totals[7]) : 0; }
+  size_t block_bytes(const Plan &p) const { return p.set.totals[2] ? yolodec_set_block_bytes(p.set.totals[5], p.set.totals[7]) : 0; }
   int launch(int, const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
-    for (size_t i = 0; i < n; i++) d->slots.push_back(YdSlot{p.tensors[i].num_candidates, p.tensors[i].max_dets, p.det_off[i]});
-    return yolodec_launch_set(scratch, stream, p.tensors, (int)n, d->block.h, d->block.bytes, launches, last_head_counts, err);
+    for (size_t i = 0; i < n; i++) d->slots.push_back(YdSlot{p.tensors[i].num_candidates, p.tensors[i].max_dets, p.set.det_off[i]});
+    return yolodec_launch_set(scratch, stream, p.tensors, (int)n, p.set, d->block.h, d->block.bytes, launches, last_head_counts, err);
   }
   void launched(const GroupCore *, const Plan &, size_t) {
     n_heads += (uint64_t)last_head_counts[0];
@@ -440,7 +429,7 @@ constexpr int kHnBlocksAtFirstUse = 4;  // pinned result blocks = launch sets in
 struct HnKind : OneLane<HnTensor> {
   using Payload = HnTensor;
   using Result = HnOut;
-  struct Plan { HnTensor tensors[kHnSetMax]; uint32_t kp_slot[kHnSetMax]; uint64_t totals[4]; };
+  struct Plan { HnTensor tensors[kHnSetMax]; HnSetPlan set; };
   struct SetData {
     PinnedBlock block;           // the set's own results until it is collected (h == nullptr: no tensor had rows)
     std::vector<HnSlot> slots;   // its tensors, by job (as the set's tickets are)
@@ -463,21 +452,16 @@ struct HnKind : OneLane<HnTensor> {
   }
   // the set's layout, by the plan the launch itself uses: which tensors have a block, the landmark tensors' keypoint slots
   int plan(const QItem<HnTensor> *take, size_t n, Plan *p, std::string *err) const {
-    int decoder[kHnSetMax];
-    uint32_t rows[kHnSetMax], block[kHnSetMax];
-    for (size_t i = 0; i < n; i++) {
-      const HnTensor &t = p->tensors[i] = take[i].p;
-      decoder[i] = t.decoder; rows[i] = t.rows;
-    }
-    const int rc = handdec_set_plan((int)n, decoder, rows, block, p->kp_slot, p->totals);
+    for (size_t i = 0; i < n; i++) p->tensors[i] = take[i].p;
+    const int rc = handdec_plan_set(p->tensors, (int)n, &p->set);
     if (rc) *err = "group: bad hand decoder set";
     return rc;
   }
   // a set without a row has nothing to copy: it takes no block (and still gets its event and its set)
-  size_t block_bytes(const Plan &p) const { return p.totals[3] ? handdec_set_block_bytes() : 0; }
+  size_t block_bytes(const Plan &p) const { return p.set.totals[3] ? handdec_set_block_bytes() : 0; }
   int launch(int, const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
-    for (size_t i = 0; i < n; i++) d->slots.push_back(HnSlot{p.tensors[i].decoder, p.tensors[i].rows, p.kp_slot[i]});
-    return handdec_launch_set(scratch, stream, p.tensors, (int)n, d->block.h, d->block.h ? handdec_set_block_bytes() : 0, launches, err);
+    for (size_t i = 0; i < n; i++) d->slots.push_back(HnSlot{p.tensors[i].decoder, p.tensors[i].rows, p.set.kp_slot[i]});
+    return handdec_launch_set(scratch, stream, p.tensors, (int)n, p.set, d->block.h, d->block.h ? handdec_set_block_bytes() : 0, launches, err);
   }
   void launched(const GroupCore *, const Plan &, size_t) const {}
   // count and records MOVE out of the pinned block: the block is free for a later set once this one is collected

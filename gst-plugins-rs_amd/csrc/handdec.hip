@@ -38,9 +38,11 @@
 //   handdec_palm_jobs_kernel / handdec_landmark_jobs_kernel  the same two bodies (palm_decode, landmark_decode) over a job table in the
 //                            kernel arguments: block b decodes job b - its own tensor, shape and settings - into the result slab of a
 //                            launch set of the video group's hand-decoder queue (handdec_launch_set, group.hip). No upload per set.
+// total_key and its inverse, cast_i32, Box, kPadKey and the wave-aggregated append_keys are decode_device.hpp's, shared with the YOLO
+// decoders; the key layout (score | index), the IoU, the in-wave register sort and select_hands are this file's own.
+#include "decode_device.hpp"
 #include "internal.hpp"
 
-#include <climits>
 #include <cstddef>
 #include <cstring>
 
@@ -53,7 +55,6 @@ constexpr int kThreads = 256;        // landmarks: a wave per hand, few hands
 constexpr int kWaves = kThreads / 64;
 constexpr uint32_t kMaxRows = 4096, kMaxHands = 1024, kMaxDim = 16, kMaxTensors = 1024, kMaxScores = 1024;
 constexpr uint32_t kPalmMaxHands = 8, kLandmarkMaxHands = MI355_HAND_MAX;
-constexpr unsigned long long kPadKey = ~0ull;   // above every real key
 
 constexpr float kFracPi2 = 1.57079632679489661923f;   // f32::consts::FRAC_PI_2
 constexpr float kPalmMinRr = 0.06f, kPalmMaxRr = 1.40f, kPalmMinVisible = 0.5f, kPalmMinSpan = 0.15f, kPalmMaxSpan = 1.60f;
@@ -66,31 +67,13 @@ static_assert(offsetof(mi355_hand_keypoints, confidences) == 172 && offsetof(mi3
 
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));   // a 16-byte load from a 4-byte aligned address
 
-struct Box { float xmin, ymin, xmax, ymax; };
-
-// f32::total_cmp's key: the order of the result as i32 is the total order (this file's copy of yolodec.hip's)
-__device__ __forceinline__ int32_t total_key(uint32_t bits) {
-  const int32_t s = (int32_t)bits;
-  return s ^ (int32_t)((uint32_t)(s >> 31) >> 1);
-}
 // ascending key order is the output order: score descending, then index ascending
 __device__ __forceinline__ unsigned long long make_key(uint32_t score_bits, uint32_t index) {
   const uint32_t asc = (uint32_t)total_key(score_bits) ^ 0x80000000u;
   return ((unsigned long long)(~asc) << 32) | (unsigned long long)index;
 }
 __device__ __forceinline__ uint32_t key_index(unsigned long long k) { return (uint32_t)k; }
-__device__ __forceinline__ uint32_t key_score_bits(unsigned long long k) {
-  const int32_t s = (int32_t)((~(uint32_t)(k >> 32)) ^ 0x80000000u);
-  return (uint32_t)(s ^ (int32_t)((uint32_t)(s >> 31) >> 1));   // the key map is its own inverse
-}
-
-// Rust's `as i32`: toward zero, saturating, NaN -> 0
-__device__ __forceinline__ int32_t cast_i32(float f) {
-  if (f != f) return 0;
-  if (f >= 2147483648.0f) return INT_MAX;
-  if (f <= -2147483648.0f) return INT_MIN;
-  return (int32_t)f;
-}
+__device__ __forceinline__ uint32_t key_score_bits(unsigned long long k) { return total_key_bits((~(uint32_t)(k >> 32)) ^ 0x80000000u); }
 
 __device__ __forceinline__ bool finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
@@ -165,20 +148,6 @@ __device__ __forceinline__ void oriented_od(const Box &b, float rotation, const 
   d.height = h;
   d.rotation_od = rotation + (-kFracPi2);
   d.has_od = 1;
-}
-
-// called by every lane of the wave: the survivors' keys go to keys[old count ...), one LDS atomic for the wave
-template <typename T>
-__device__ __forceinline__ void append_keys(bool keep, T key, uint32_t *count, T *keys, uint32_t cap) {
-  const unsigned long long m = __ballot(keep);
-  if (m == 0) return;   // wave-uniform
-  const int lane = (int)__lane_id();
-  const int leader = __ffsll((long long)m) - 1;
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
-  base = (uint32_t)__shfl((int)base, leader);
-  const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  if (keep && at < cap) keys[at] = key;   // always inside: the counter starts at zero and a row is appended once
 }
 
 // the bitonic steps j = j0, j0 / 2, ... 1 (j0 <= 32) of stage k for element i, whose partners i ^ j all lie in the wave: in registers
@@ -522,24 +491,15 @@ __global__ __launch_bounds__(kThreads) void handdec_landmark_jobs_kernel(const H
 
 // scratch of one context; grows to the largest call seen
 struct HandDecState {
-  mi355_hand_params *d_params = nullptr, *h_params = nullptr;
-  size_t d_params_n = 0, h_params_n = 0;
-  uint8_t *d_out = nullptr, *h_out = nullptr;   // [tensors] counts (padded to 64 bytes), [tensors][MI355_HAND_MAX] dets, then keypoint records
-  size_t d_out_bytes = 0, h_out_bytes = 0;
-  float *d_stage = nullptr, *d_stage_scores = nullptr;   // the host forms' tensor and scores
-  size_t stage_floats = 0, stage_score_floats = 0;
+  DeviceBuf<mi355_hand_params> d_params;
+  PinnedBuf<mi355_hand_params> h_params;
+  DeviceBuf<uint8_t> d_out;      // [tensors] counts (padded to 64 bytes), [tensors][MI355_HAND_MAX] dets, then keypoint records
+  PinnedBuf<uint8_t> h_out;
+  DeviceBuf<float> d_stage, d_stage_scores;   // the host forms' tensor and scores
 };
 
 void handdec_release(mi355_ctx *ctx) {
-  auto *s = static_cast<HandDecState *>(ctx->handdec);
-  if (!s) return;
-  if (s->d_params) (void)hipFree(s->d_params);
-  if (s->h_params) (void)hipHostFree(s->h_params);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->h_out) (void)hipHostFree(s->h_out);
-  if (s->d_stage) (void)hipFree(s->d_stage);
-  if (s->d_stage_scores) (void)hipFree(s->d_stage_scores);
-  delete s;
+  delete static_cast<HandDecState *>(ctx->handdec);
   ctx->handdec = nullptr;
 }
 
@@ -578,19 +538,6 @@ int handdec_check_params(int decoder, uint32_t max_hands, int32_t frame_width, i
   return *why ? MI355_ERR_INVALID_ARG : MI355_OK;
 }
 
-template <typename T>
-static int grow(mi355_ctx *ctx, T **p, size_t *have, size_t want, const char *what, bool host = false) {
-  if (*have >= want && *p) return MI355_OK;
-  if (*p) (void)(host ? hipHostFree(*p) : hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  const hipError_t e = host ? hipHostMalloc((void **)p, want * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)p, want * sizeof(T));
-  const int rc = check_hip(ctx, e, what);
-  if (rc) { *p = nullptr; return rc; }
-  *have = want;
-  return MI355_OK;
-}
-
 static size_t counts_bytes(uint32_t T) { return ((size_t)T * sizeof(uint32_t) + 63) / 64 * 64; }
 static size_t dets_bytes(uint32_t T) { return (size_t)T * MI355_HAND_MAX * sizeof(mi355_hand_det); }
 static size_t kps_bytes(uint32_t T) { return (size_t)T * MI355_HAND_MAX * sizeof(mi355_hand_keypoints); }
@@ -599,11 +546,11 @@ static int handdec_scratch(mi355_ctx *ctx, uint32_t T, bool landmarks, HandDecSt
   auto *s = static_cast<HandDecState *>(ctx->handdec);
   if (!s) ctx->handdec = s = new HandDecState();
   int rc = MI355_OK;
-  if ((rc = grow(ctx, &s->d_params, &s->d_params_n, (size_t)T, "hipMalloc(handdec params)"))) return rc;
-  if ((rc = grow(ctx, &s->h_params, &s->h_params_n, (size_t)T, "hipHostMalloc(handdec params)", true))) return rc;
+  if ((rc = check_hip(ctx, s->d_params.reserve((size_t)T), "hipMalloc(handdec params)"))) return rc;
+  if ((rc = check_hip(ctx, s->h_params.reserve((size_t)T), "hipHostMalloc(handdec params)"))) return rc;
   const size_t bytes = counts_bytes(T) + dets_bytes(T) + (landmarks ? kps_bytes(T) : 0);
-  if ((rc = grow(ctx, &s->d_out, &s->d_out_bytes, bytes, "hipMalloc(handdec results)"))) return rc;
-  if ((rc = grow(ctx, &s->h_out, &s->h_out_bytes, bytes, "hipHostMalloc(handdec results)", true))) return rc;
+  if ((rc = check_hip(ctx, s->d_out.reserve(bytes), "hipMalloc(handdec results)"))) return rc;
+  if ((rc = check_hip(ctx, s->h_out.reserve(bytes), "hipHostMalloc(handdec results)"))) return rc;
   *out = s;
   return MI355_OK;
 }
@@ -613,26 +560,26 @@ static int handdec_run(mi355_ctx *ctx, HandDecState *s, bool landmarks, const fl
                        const float *d_scores, size_t score_pitch_bytes, uint32_t num_scores, const mi355_hand_params *p, mi355_hand_det *dets,
                        mi355_hand_keypoints *kps, uint32_t *n_hands) {
   int rc = MI355_OK;
-  std::memcpy(s->h_params, p, (size_t)T * sizeof(mi355_hand_params));
-  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_params, s->h_params, (size_t)T * sizeof(mi355_hand_params), hipMemcpyHostToDevice, ctx->stream), "handdec params H2D")))
+  std::memcpy(s->h_params.p, p, (size_t)T * sizeof(mi355_hand_params));
+  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_params.p, s->h_params.p, (size_t)T * sizeof(mi355_hand_params), hipMemcpyHostToDevice, ctx->stream), "handdec params H2D")))
     return rc;
   __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
-  uint32_t *d_n = reinterpret_cast<uint32_t *>(s->d_out);
-  mi355_hand_det *d_dets = reinterpret_cast<mi355_hand_det *>(s->d_out + counts_bytes(T));
-  mi355_hand_keypoints *d_kps = reinterpret_cast<mi355_hand_keypoints *>(s->d_out + counts_bytes(T) + dets_bytes(T));
+  uint32_t *d_n = reinterpret_cast<uint32_t *>(s->d_out.p);
+  mi355_hand_det *d_dets = reinterpret_cast<mi355_hand_det *>(s->d_out.p + counts_bytes(T));
+  mi355_hand_keypoints *d_kps = reinterpret_cast<mi355_hand_keypoints *>(s->d_out.p + counts_bytes(T) + dets_bytes(T));
   if (landmarks)
     hipLaunchKernelGGL(handdec_landmark_kernel, dim3(T), dim3(kThreads), 0, ctx->stream, d_tensors, pitch_bytes / 4, rows, D, d_scores, score_pitch_bytes / 4,
-                       d_scores ? num_scores : 0u, s->d_params, d_dets, d_kps, d_n);
+                       d_scores ? num_scores : 0u, s->d_params.p, d_dets, d_kps, d_n);
   else
-    hipLaunchKernelGGL(handdec_palm_kernel, dim3(T), dim3(kPalmThreads), 0, ctx->stream, d_tensors, pitch_bytes / 4, rows, s->d_params, d_dets, d_n);
+    hipLaunchKernelGGL(handdec_palm_kernel, dim3(T), dim3(kPalmThreads), 0, ctx->stream, d_tensors, pitch_bytes / 4, rows, s->d_params.p, d_dets, d_n);
   if ((rc = check_hip(ctx, hipGetLastError(), "handdec launch"))) return rc;
   const size_t bytes = counts_bytes(T) + dets_bytes(T) + (landmarks ? kps_bytes(T) : 0);
-  if ((rc = check_hip(ctx, hipMemcpyAsync(s->h_out, s->d_out, bytes, hipMemcpyDeviceToHost, ctx->stream), "handdec D2H"))) return rc;
+  if ((rc = check_hip(ctx, hipMemcpyAsync(s->h_out.p, s->d_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream), "handdec D2H"))) return rc;
   __atomic_fetch_add(&ctx->n_d2h, 1ull, __ATOMIC_RELAXED);
   if ((rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))) return rc;
-  const uint32_t *h_n = reinterpret_cast<const uint32_t *>(s->h_out);
-  const mi355_hand_det *h_dets = reinterpret_cast<const mi355_hand_det *>(s->h_out + counts_bytes(T));
-  const mi355_hand_keypoints *h_kps = reinterpret_cast<const mi355_hand_keypoints *>(s->h_out + counts_bytes(T) + dets_bytes(T));
+  const uint32_t *h_n = reinterpret_cast<const uint32_t *>(s->h_out.p);
+  const mi355_hand_det *h_dets = reinterpret_cast<const mi355_hand_det *>(s->h_out.p + counts_bytes(T));
+  const mi355_hand_keypoints *h_kps = reinterpret_cast<const mi355_hand_keypoints *>(s->h_out.p + counts_bytes(T) + dets_bytes(T));
   for (uint32_t t = 0; t < T; t++) {
     const uint32_t n = h_n[t] < MI355_HAND_MAX ? h_n[t] : MI355_HAND_MAX;
     n_hands[t] = n;
@@ -667,7 +614,7 @@ constexpr size_t kHnSlabBytes = kHnCountsBytes + (size_t)kHnSetMax * MI355_HAND_
 static_assert(kHnCountsBytes >= kHnSetMax * sizeof(uint32_t) && kHnCountsBytes % 8 == 0, "the counts come first and the records behind them stay aligned");
 static_assert(kHnSlabBytes == 128 + 32 * 640 + 32 * 2880, "the slab's maximum: pinned blocks are of one size");
 
-// the layout of one set (mi355_selftest_handdec_set_plan; handdec_launch_set fills its tables with it)
+// the layout of one set (mi355_selftest_handdec_set_plan; handdec_plan_set plans the queue's sets with it)
 int handdec_set_plan(int n_jobs, const int *decoder, const uint32_t *rows, uint32_t *block, uint32_t *kp_slot, uint64_t totals[4]) {
   if (n_jobs < 0 || n_jobs > kHnSetMax || !totals) return MI355_ERR_INVALID_ARG;
   if (n_jobs > 0 && (!decoder || !rows || !block || !kp_slot)) return MI355_ERR_INVALID_ARG;
@@ -691,13 +638,12 @@ int handdec_set_plan(int n_jobs, const int *decoder, const uint32_t *rows, uint3
 // early return, the selected hands otherwise) and exactly that many records; a job without rows has no block and its count is 0 on
 // the host (the queue never reads its slot). What an earlier set left in a slot is therefore never read.
 struct HnSetScratch {
-  uint8_t *d_out = nullptr;
+  DeviceBuf<uint8_t> d_out;
 };
 
 HnSetScratch *handdec_set_scratch_new(int *status, std::string *err) {
   auto *S = new HnSetScratch();
-  if (hipMalloc((void **)&S->d_out, kHnSlabBytes) != hipSuccess) {
-    (void)hipGetLastError();
+  if (S->d_out.reserve(kHnSlabBytes) != hipSuccess) {
     delete S;
     *status = MI355_ERR_OUT_OF_MEMORY;
     *err = "hipMalloc(handdec set results)";
@@ -707,53 +653,54 @@ HnSetScratch *handdec_set_scratch_new(int *status, std::string *err) {
   return S;
 }
 
-void handdec_set_scratch_free(HnSetScratch *S) {
-  if (!S) return;
-  if (S->d_out) (void)hipFree(S->d_out);
-  delete S;
-}
+void handdec_set_scratch_free(HnSetScratch *S) { delete S; }
 
 size_t handdec_set_block_bytes() { return kHnSlabBytes; }
 
-int handdec_launch_set(HnSetScratch *S, hipStream_t stream, const HnTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
-                       std::string *err) {
+// the one place a set's members become the plan's arrays
+int handdec_plan_set(const HnTensor *tensors, int n, HnSetPlan *out) {
+  for (uint64_t &t : out->totals) t = 0;
+  if (!tensors || n < 0 || n > kHnSetMax) return MI355_ERR_INVALID_ARG;
+  int decoder[kHnSetMax];
+  uint32_t rows[kHnSetMax];
+  for (int i = 0; i < n; i++) { decoder[i] = tensors[i].decoder; rows[i] = tensors[i].rows; }
+  return handdec_set_plan(n, decoder, rows, out->block, out->kp_slot, out->totals);
+}
+
+int handdec_launch_set(HnSetScratch *S, hipStream_t stream, const HnTensor *tensors, int n, const HnSetPlan &P, void *h_block, size_t h_block_bytes,
+                       int *kernel_launches, std::string *err) {
   *kernel_launches = 0;
   if (!S || !tensors || n < 1 || n > kHnSetMax) { *err = "handdec: bad launch set"; return MI355_ERR_INVALID_ARG; }
-  int decoder[kHnSetMax];
-  uint32_t rows[kHnSetMax], block[kHnSetMax], kp_slot[kHnSetMax];
-  uint64_t totals[4];
-  for (int i = 0; i < n; i++) { decoder[i] = tensors[i].decoder; rows[i] = tensors[i].rows; }
-  const int rc = handdec_set_plan(n, decoder, rows, block, kp_slot, totals);
-  if (rc) { *err = "handdec: bad launch set"; return rc; }
+  const uint64_t *totals = P.totals;
   if (totals[3] == 0) return MI355_OK;   // no job has rows: nothing to launch, nothing to copy
   const size_t bytes = (size_t)totals[3];   // <= kHnSlabBytes: n <= kHnSetMax
   if (!h_block || h_block_bytes < bytes) { *err = "handdec: the pinned result block is too small for the set"; return MI355_ERR_INVALID_ARG; }
   HnPalmTable palm = {};
   HnLandmarkTable lm = {};
   for (int i = 0; i < n; i++) {
-    if (!rows[i]) continue;   // no rows: no block
     const HnTensor &t = tensors[i];
+    if (!t.rows) continue;   // no rows: no block
     if (t.decoder == 0) {
-      HnPalmJob &J = palm.job[block[i]];   // block[i] < palm blocks <= kHnSetMax
+      HnPalmJob &J = palm.job[P.block[i]];   // block[i] < palm blocks <= kHnSetMax
       J.data = t.data;
       J.N = t.rows;
       J.slot = (uint32_t)i;
       J.p = t.p;
     } else {
-      HnLandmarkJob &J = lm.job[block[i]];
+      HnLandmarkJob &J = lm.job[P.block[i]];
       J.data = t.data;
       J.scores = t.scores;
       J.H = t.rows;
       J.slot = (uint32_t)i;
       J.D = t.D;
       J.num_scores = t.scores ? t.num_scores : 0u;
-      J.kp_slot = kp_slot[i];
+      J.kp_slot = P.kp_slot[i];
       J.p = t.p;
     }
   }
-  uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out);
-  mi355_hand_det *d_dets = reinterpret_cast<mi355_hand_det *>(S->d_out + kHnCountsBytes);
-  mi355_hand_keypoints *d_kps = reinterpret_cast<mi355_hand_keypoints *>(S->d_out + kHnCountsBytes + dets_bytes((uint32_t)n));
+  uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out.p);
+  mi355_hand_det *d_dets = reinterpret_cast<mi355_hand_det *>(S->d_out.p + kHnCountsBytes);
+  mi355_hand_keypoints *d_kps = reinterpret_cast<mi355_hand_keypoints *>(S->d_out.p + kHnCountsBytes + dets_bytes((uint32_t)n));
   if (totals[0]) {
     hipLaunchKernelGGL(handdec_palm_jobs_kernel, dim3((uint32_t)totals[0]), dim3(kPalmThreads), 0, stream, palm, d_dets, d_n);
     const hipError_t e = hipGetLastError();
@@ -766,7 +713,7 @@ int handdec_launch_set(HnSetScratch *S, hipStream_t stream, const HnTensor *tens
     if (e != hipSuccess) { *err = std::string("handdec landmark jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
     (*kernel_launches)++;
   }
-  const hipError_t e = hipMemcpyAsync(h_block, S->d_out, bytes, hipMemcpyDeviceToHost, stream);
+  const hipError_t e = hipMemcpyAsync(h_block, S->d_out.p, bytes, hipMemcpyDeviceToHost, stream);
   if (e != hipSuccess) { *err = std::string("handdec set D2H: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
   return MI355_OK;
 }
@@ -815,10 +762,10 @@ int mi355_handdec_palm_tensor(mi355_ctx *ctx, const float *data, uint32_t num_ro
   if ((rc = check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice"))) return rc;
   HandDecState *s = nullptr;
   if ((rc = handdec_scratch(ctx, 1, false, &s))) return rc;
-  if ((rc = grow(ctx, &s->d_stage, &s->stage_floats, bytes / 4, "hipMalloc(handdec staging)"))) return rc;
-  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage, data, bytes, hipMemcpyHostToDevice, ctx->stream), "handdec H2D"))) return rc;
+  if ((rc = check_hip(ctx, s->d_stage.reserve(bytes / 4), "hipMalloc(handdec staging)"))) return rc;
+  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage.p, data, bytes, hipMemcpyHostToDevice, ctx->stream), "handdec H2D"))) return rc;
   __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
-  return handdec_run(ctx, s, false, s->d_stage, bytes, 1, num_rows, 0, nullptr, 0, 0, p, dets, nullptr, n_hands);
+  return handdec_run(ctx, s, false, s->d_stage.p, bytes, 1, num_rows, 0, nullptr, 0, 0, p, dets, nullptr, n_hands);
 }
 
 int mi355_handdec_landmarks_tensors_device(mi355_ctx *ctx, const float *d_landmarks, size_t tensor_pitch_bytes, int n_tensors, uint32_t num_hands, uint32_t kps_dim,
@@ -848,15 +795,15 @@ int mi355_handdec_landmarks_tensor(mi355_ctx *ctx, const float *landmarks, uint3
   if ((rc = check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice"))) return rc;
   HandDecState *s = nullptr;
   if ((rc = handdec_scratch(ctx, 1, true, &s))) return rc;
-  if ((rc = grow(ctx, &s->d_stage, &s->stage_floats, bytes / 4, "hipMalloc(handdec staging)"))) return rc;
-  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage, landmarks, bytes, hipMemcpyHostToDevice, ctx->stream), "handdec H2D"))) return rc;
+  if ((rc = check_hip(ctx, s->d_stage.reserve(bytes / 4), "hipMalloc(handdec staging)"))) return rc;
+  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage.p, landmarks, bytes, hipMemcpyHostToDevice, ctx->stream), "handdec H2D"))) return rc;
   __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
   if (have_scores) {
-    if ((rc = grow(ctx, &s->d_stage_scores, &s->stage_score_floats, (size_t)num_scores, "hipMalloc(handdec score staging)"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage_scores, scores, score_bytes, hipMemcpyHostToDevice, ctx->stream), "handdec scores H2D"))) return rc;
+    if ((rc = check_hip(ctx, s->d_stage_scores.reserve((size_t)num_scores), "hipMalloc(handdec score staging)"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage_scores.p, scores, score_bytes, hipMemcpyHostToDevice, ctx->stream), "handdec scores H2D"))) return rc;
     __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
   }
-  return handdec_run(ctx, s, true, s->d_stage, bytes, 1, num_hands, kps_dim, have_scores ? s->d_stage_scores : nullptr, score_bytes, num_scores, p, dets, kps, n_hands);
+  return handdec_run(ctx, s, true, s->d_stage.p, bytes, 1, num_hands, kps_dim, have_scores ? s->d_stage_scores.p : nullptr, score_bytes, num_scores, p, dets, kps, n_hands);
 }
 
 int mi355_selftest_handdec_check(int decoder, size_t tensor_pitch_bytes, int n_tensors, uint32_t rows, uint32_t kps_dim, size_t score_pitch_bytes, uint32_t num_scores,

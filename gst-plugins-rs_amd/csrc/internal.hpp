@@ -168,6 +168,42 @@ bool recently_written(int device, const void *p, size_t bytes);
 void forget_written(int device, const void *p, size_t bytes);   // a host copy has replaced that range
 int check_hip(mi355_ctx *ctx, hipError_t e, const char *what);
 
+// An owning, grow-only buffer of n elements of T: in device memory, or (PINNED) in pinned host memory. Scratch that grows to the
+// largest shape seen: the decoders' (yolodec.hip, handdec.hip) is made of these.
+template <typename T, bool PINNED>
+struct GrowBuf {
+  T *p = nullptr;
+  size_t n = 0;   // elements held; 0 when p is null
+  GrowBuf() = default;
+  GrowBuf(const GrowBuf &) = delete;
+  GrowBuf &operator=(const GrowBuf &) = delete;
+  ~GrowBuf() { release(); }
+  void release() {
+    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    n = 0;
+  }
+  // Nothing if the buffer already holds `want` elements. Otherwise the old allocation is freed and one of `want` elements made: the
+  // contents are NOT kept, and *fresh (if given) is set - whatever the buffer held is gone, also when the allocation fails, which
+  // leaves the buffer empty and the runtime's last error cleared.
+  // (hipFree waits for the device: work still running on a stream has finished with the old allocation)
+  hipError_t reserve(size_t want, bool *fresh = nullptr) {
+    if (n >= want && p) return hipSuccess;
+    release();
+    if (fresh) *fresh = true;
+    const hipError_t e = PINNED ? hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, want * sizeof(T));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return e;
+    }
+    n = want;
+    return hipSuccess;
+  }
+};
+template <typename T> using DeviceBuf = GrowBuf<T, false>;
+template <typename T> using PinnedBuf = GrowBuf<T, true>;
+
 // kernel launchers (asynchronous on ctx->stream)
 int launch_hsvfilter(mi355_ctx *ctx, uint8_t *d_data, int n_frames, size_t frame_pitch, int width,
                      int height, int stride, const PixFmt &fmt, const mi355_hsv_settings &s);
@@ -362,31 +398,41 @@ struct YdHead { mi355_yolox_level lv[MI355_YOLOX_LEVELS_MAX]; int n_levels; };  
 // (a tensor member carries no levels: its `head` is empty, and copying it through the queue costs what it did)
 struct YdTensor { const float *data; int layout; uint32_t num_fields, num_candidates, max_dets; mi355_yolo_params p; std::shared_ptr<const YdHead> head; };
 struct YdSetScratch;  // counters (zero between sets), keys, kept boxes and positions, results, the head members' tables, on the device
-int yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, uint32_t *first_block,
-                     uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]);
 // the shape checks of the YOLOX head entry points (yolox_head.hip): everything but the map pointers and pitches; *A_out: the candidates
 int yolox_head_check_shape(const mi355_yolox_level *lv, int n_levels, int n_tensors, uint32_t C, uint32_t *A_out, const char **why);
 // the map pointers of checked levels (pitches are not looked at: one tensor)
 int yolox_head_check_maps(const mi355_yolox_level *lv, int n_levels, const char **why);
-// The layout of one set that may hold head members (mi355_selftest_yolox_head_set_plan; yolodec_launch_set lays the set out with it).
-// kind: MI355_YOLO_V8 / _X / _X_HEAD per job. A head job reads its n_levels[j] and that many entries of level_h / level_w (the head
-// jobs' levels one after the other) and ignores num_candidates[j]; candidates[j] is its A (a tensor job's N). level_first_block: per
-// level, in the order of level_h, the running sum of ceil(h w / 256) within the job. totals: the six of yolodec_set_plan (a head
-// counts as a job with a candidate), then the head score blocks and the level jobs.
+// The layout of one set (mi355_selftest_yolox_head_set_plan and, without heads, mi355_selftest_yolodec_set_plan; yolodec_plan_set
+// plans the queue's sets with it). kind: MI355_YOLO_V8 / _X / _X_HEAD per job. A head job reads its n_levels[j] and that many entries
+// of level_h / level_w (the head jobs' levels one after the other) and ignores num_candidates[j]; candidates[j] is its A (a tensor
+// job's N; may be num_candidates itself). level_first_block: per level, in the order of level_h, the running sum of ceil(h w / 256)
+// within the job. The four level arrays may be null when no job is a head. totals: V8 score blocks, X score blocks, jobs with a
+// candidate (a head counts as one), keys, boxes, records, then the head score blocks and the level jobs.
 int yolodec_mixed_set_plan(int n_jobs, const int *kind, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, const int *n_levels,
                            const uint32_t *level_h, const uint32_t *level_w, uint32_t *candidates, uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset,
                            uint64_t *box_offset, uint64_t *det_offset, uint32_t *level_first_block, uint64_t totals[8]);
+// the plan of one set of the queue: what yolodec_mixed_set_plan writes, by job (level_first_block: by level, the heads' levels one
+// after the other). Made ONCE per set: it sizes the set's pinned block and yolodec_launch_set lays the set out with it.
+struct YdSetPlan {
+  uint32_t candidates[kYdSetMax], first_block[kYdSetMax], blocks[kYdSetMax];
+  uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax];
+  uint32_t level_first_block[kYdSetMax * MI355_YOLOX_LEVELS_MAX];
+  uint64_t totals[8];
+};
+// the plan of n members (zeroed totals on a refusal): a head member without its levels, or with fewer than 0 or more than
+// MI355_YOLOX_LEVELS_MAX of them, is MI355_ERR_INVALID_ARG; the rest are yolodec_mixed_set_plan's refusals
+int yolodec_plan_set(const YdTensor *tensors, int n, YdSetPlan *out);
 YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err);
 void yolodec_set_scratch_free(YdSetScratch *S);
 size_t yolodec_set_result_bytes(uint64_t records);  // the counts and that many records (totals[5]): what a set's download writes
 // the pinned block of a set: its results, and behind them the tables of its head members (level_jobs = totals[7]; 0: none)
 size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs);
-// n <= kYdSetMax checked members on `stream`: the head tables' upload (only if the set holds a head), the V8 score launch, the X
-// score launch (each only if it has a job with a candidate), the head score launch, the tensors' NMS launch, the heads' NMS launch,
-// counts and records into h_block (nothing launched or copied if no member has a candidate). head_counts: {heads, table uploads,
-// head kernel launches} of this set.
-int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
-                       int head_counts[3], std::string *err);
+// n <= kYdSetMax members and their plan (yolodec_plan_set) on `stream`: the head tables' upload (only if the set holds a head), the
+// V8 score launch, the X score launch (each only if it has a job with a candidate), the head score launch, the tensors' NMS launch,
+// the heads' NMS launch, counts and records into h_block (nothing launched or copied if no member has a candidate). head_counts:
+// {heads, table uploads, head kernel launches} of this set.
+int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, const YdSetPlan &plan, void *h_block, size_t h_block_bytes,
+                       int *kernel_launches, int head_counts[3], std::string *err);
 // launch sets of the video group's hand-decoder queue (handdec.hip): palm and landmark tensors of independent instances, job tables
 constexpr int kHnSetMax = MI355_HANDDEC_SET_MAX;
 constexpr size_t kHnCountsBytes = 128;  // a result block: kHnSetMax counts (by job), n x MI355_HAND_MAX box records (by job), then
@@ -397,14 +443,22 @@ struct HnSetScratch;  // the result slab of one set, on the device; nothing in i
 int handdec_check_args(int decoder, size_t tensor_pitch_bytes, int n_tensors, uint32_t rows, uint32_t kps_dim, size_t score_pitch_bytes, uint32_t num_scores,
                        const char **why);
 int handdec_check_params(int decoder, uint32_t max_hands, int32_t frame_width, int32_t frame_height, const char **why);
+// the layout of one set (mi355_selftest_handdec_set_plan; handdec_plan_set plans the queue's sets with it)
 int handdec_set_plan(int n_jobs, const int *decoder, const uint32_t *rows, uint32_t *block, uint32_t *kp_slot, uint64_t totals[4]);
+// the plan of one set of the queue: what handdec_set_plan writes, by job. Made ONCE per set: it says whether the set takes a pinned
+// block, handdec_launch_set fills its tables with it, and the results are read by its kp_slot.
+struct HnSetPlan {
+  uint32_t block[kHnSetMax], kp_slot[kHnSetMax];
+  uint64_t totals[4];
+};
+int handdec_plan_set(const HnTensor *tensors, int n, HnSetPlan *out);   // zeroed totals on a refusal
 HnSetScratch *handdec_set_scratch_new(int *status, std::string *err);
 void handdec_set_scratch_free(HnSetScratch *S);
 size_t handdec_set_block_bytes();  // the pinned block a set's results are copied to: the slab's maximum, one size
-// n <= kHnSetMax checked tensors on `stream`: the palm launch, the landmark launch (each only if it has a job with rows), then the
-// slab's used prefix into h_block (nothing launched or copied if no tensor has rows)
-int handdec_launch_set(HnSetScratch *S, hipStream_t stream, const HnTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
-                       std::string *err);
+// n <= kHnSetMax checked tensors and their plan (handdec_plan_set) on `stream`: the palm launch, the landmark launch (each only if it
+// has a job with rows), then the slab's used prefix into h_block (nothing launched or copied if no tensor has rows)
+int handdec_launch_set(HnSetScratch *S, hipStream_t stream, const HnTensor *tensors, int n, const HnSetPlan &plan, void *h_block, size_t h_block_bytes,
+                       int *kernel_launches, std::string *err);
 void handdec_set_result(const void *h_block, int n, int i, int decoder, uint32_t rows, uint32_t kp_slot, mi355_hand_det *dets, mi355_hand_keypoints *kps,
                         uint32_t *n_hands);
 int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, int channel, int kind, float *out, int *w, int *h);

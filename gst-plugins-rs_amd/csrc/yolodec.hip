@@ -178,7 +178,7 @@ struct YdJob {
   mi355_yolo_det *dets;         // min(max_dets, N) records
   uint32_t *n_dets;
   uint32_t F, N, key_cap, max_dets;
-  uint32_t first_block, blocks; // its tiles in the score launch of its layout (yolodec_set_plan)
+  uint32_t first_block, blocks; // its tiles in the score launch of its layout (yolodec_mixed_set_plan)
   int32_t layout;
   mi355_yolo_params p;
 };
@@ -215,18 +215,7 @@ __global__ __launch_bounds__(kNmsThreads) void yolodec_nms_jobs_kernel(const YdJ
 }  // namespace
 
 void yolodec_release(mi355_ctx *ctx) {
-  auto *s = static_cast<YoloDecState *>(ctx->yolodec);
-  if (!s) return;
-  if (s->d_count) (void)hipFree(s->d_count);
-  if (s->d_params) (void)hipFree(s->d_params);
-  if (s->h_params) (void)hipHostFree(s->h_params);
-  if (s->d_keys) (void)hipFree(s->d_keys);
-  if (s->d_kbox) (void)hipFree(s->d_kbox);
-  if (s->d_ksrc) (void)hipFree(s->d_ksrc);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->h_out) (void)hipHostFree(s->h_out);
-  if (s->d_stage) (void)hipFree(s->d_stage);
-  delete s;
+  delete static_cast<YoloDecState *>(ctx->yolodec);
   ctx->yolodec = nullptr;
 }
 
@@ -248,75 +237,54 @@ int yolodec_check_args(size_t tensor_pitch_bytes, int n_tensors, int layout, uin
   return MI355_OK;
 }
 
-template <typename T>
-static int grow(mi355_ctx *ctx, T **p, size_t *have, size_t want, const char *what, bool host = false) {
-  if (*have >= want && *p) return MI355_OK;
-  if (*p) (void)(host ? hipHostFree(*p) : hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  const hipError_t e = host ? hipHostMalloc((void **)p, want * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)p, want * sizeof(T));
-  const int rc = check_hip(ctx, e, what);
-  if (rc) { *p = nullptr; return rc; }
-  *have = want;
-  return MI355_OK;
-}
-
 static size_t out_counts_bytes(uint32_t T) { return ((size_t)T * sizeof(uint32_t) + 63) / 64 * 64; }
 
 int yolodec_scratch(mi355_ctx *ctx, uint32_t T, uint32_t N, uint32_t max_dets, YoloDecState **out) {
   auto *s = static_cast<YoloDecState *>(ctx->yolodec);
   if (!s) ctx->yolodec = s = new YoloDecState();
-  int rc = MI355_OK;
-  if (s->tensors < T) {
-    if (s->d_count) (void)hipFree(s->d_count);
-    if (s->d_params) (void)hipFree(s->d_params);
-    if (s->h_params) (void)hipHostFree(s->h_params);
-    s->d_count = nullptr;
-    s->d_params = s->h_params = nullptr;
-    s->tensors = 0;
-    s->count_zero = false;
-    if ((rc = check_hip(ctx, hipMalloc((void **)&s->d_count, (size_t)T * sizeof(uint32_t)), "hipMalloc(yolodec counters)"))) return rc;
-    if ((rc = check_hip(ctx, hipMalloc((void **)&s->d_params, (size_t)T * sizeof(mi355_yolo_params)), "hipMalloc(yolodec settings)"))) return rc;
-    if ((rc = check_hip(ctx, hipHostMalloc((void **)&s->h_params, (size_t)T * sizeof(mi355_yolo_params), hipHostMallocDefault), "hipHostMalloc(yolodec settings)")))
-      return rc;
-    s->tensors = T;
-  }
+  bool fresh = false;
+  int rc = check_hip(ctx, s->d_count.reserve(T, &fresh), "hipMalloc(yolodec counters)");
+  if (fresh) s->count_zero = false;
+  if (rc) return rc;
+  // the settings are sized by the counters' T (>= this call's), whichever call set it: the three grow together
+  if ((rc = check_hip(ctx, s->d_params.reserve(s->d_count.n), "hipMalloc(yolodec settings)"))) return rc;
+  if ((rc = check_hip(ctx, s->h_params.reserve(s->d_count.n), "hipHostMalloc(yolodec settings)"))) return rc;
   const size_t key_pitch = pow2_at_least(N);
-  if ((rc = grow(ctx, &s->d_keys, &s->key_elems, (size_t)T * key_pitch, "hipMalloc(yolodec keys)"))) return rc;
-  if ((rc = grow(ctx, &s->d_kbox, &s->kbox_elems, (size_t)T * N, "hipMalloc(yolodec kept boxes)"))) return rc;
-  if ((rc = grow(ctx, &s->d_ksrc, &s->ksrc_elems, (size_t)T * N, "hipMalloc(yolodec kept positions)"))) return rc;
+  if ((rc = check_hip(ctx, s->d_keys.reserve((size_t)T * key_pitch), "hipMalloc(yolodec keys)"))) return rc;
+  if ((rc = check_hip(ctx, s->d_kbox.reserve((size_t)T * N), "hipMalloc(yolodec kept boxes)"))) return rc;
+  if ((rc = check_hip(ctx, s->d_ksrc.reserve((size_t)T * N), "hipMalloc(yolodec kept positions)"))) return rc;
   const size_t out_bytes = out_counts_bytes(T) + (size_t)T * max_dets * sizeof(mi355_yolo_det);
-  if ((rc = grow(ctx, &s->d_out, &s->d_out_bytes, out_bytes, "hipMalloc(yolodec results)"))) return rc;
-  if ((rc = grow(ctx, &s->h_out, &s->h_out_bytes, out_bytes, "hipHostMalloc(yolodec results)", true))) return rc;
+  if ((rc = check_hip(ctx, s->d_out.reserve(out_bytes), "hipMalloc(yolodec results)"))) return rc;
+  if ((rc = check_hip(ctx, s->h_out.reserve(out_bytes), "hipHostMalloc(yolodec results)"))) return rc;
   if (!s->count_zero) {
-    if ((rc = check_hip(ctx, hipMemsetAsync(s->d_count, 0, (size_t)s->tensors * sizeof(uint32_t), ctx->stream), "hipMemsetAsync(yolodec)"))) return rc;
+    if ((rc = check_hip(ctx, hipMemsetAsync(s->d_count.p, 0, s->d_count.n * sizeof(uint32_t), ctx->stream), "hipMemsetAsync(yolodec)"))) return rc;
     s->count_zero = true;
   }
   *out = s;
   return MI355_OK;
 }
 
-int yolodec_stage(mi355_ctx *ctx, YoloDecState *s, size_t floats) { return grow(ctx, &s->d_stage, &s->stage_floats, floats, "hipMalloc(yolodec staging)"); }
+int yolodec_stage(mi355_ctx *ctx, YoloDecState *s, size_t floats) { return check_hip(ctx, s->d_stage.reserve(floats), "hipMalloc(yolodec staging)"); }
 
 int yolodec_upload_params(mi355_ctx *ctx, YoloDecState *s, uint32_t T, const mi355_yolo_params *p) {
-  std::memcpy(s->h_params, p, (size_t)T * sizeof(mi355_yolo_params));
-  const int rc = check_hip(ctx, hipMemcpyAsync(s->d_params, s->h_params, (size_t)T * sizeof(mi355_yolo_params), hipMemcpyHostToDevice, ctx->stream), "yolodec settings H2D");
+  std::memcpy(s->h_params.p, p, (size_t)T * sizeof(mi355_yolo_params));
+  const int rc = check_hip(ctx, hipMemcpyAsync(s->d_params.p, s->h_params.p, (size_t)T * sizeof(mi355_yolo_params), hipMemcpyHostToDevice, ctx->stream), "yolodec settings H2D");
   if (rc) return rc;
   __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
   return MI355_OK;
 }
 
-mi355_yolo_det *yolodec_d_dets(YoloDecState *s, uint32_t T) { return reinterpret_cast<mi355_yolo_det *>(s->d_out + out_counts_bytes(T)); }
+mi355_yolo_det *yolodec_d_dets(YoloDecState *s, uint32_t T) { return reinterpret_cast<mi355_yolo_det *>(s->d_out.p + out_counts_bytes(T)); }
 
 int yolodec_download(mi355_ctx *ctx, YoloDecState *s, uint32_t T, mi355_yolo_det *dets, uint32_t max_dets, uint32_t *n_dets) {
   int rc = MI355_OK;
   const size_t bytes = out_counts_bytes(T) + (size_t)T * max_dets * sizeof(mi355_yolo_det);
-  if ((rc = check_hip(ctx, hipMemcpyAsync(s->h_out, s->d_out, bytes, hipMemcpyDeviceToHost, ctx->stream), "yolodec D2H"))) return rc;
+  if ((rc = check_hip(ctx, hipMemcpyAsync(s->h_out.p, s->d_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream), "yolodec D2H"))) return rc;
   __atomic_fetch_add(&ctx->n_d2h, 1ull, __ATOMIC_RELAXED);
   if ((rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))) return rc;
   s->count_zero = true;
-  const uint32_t *h_n = reinterpret_cast<const uint32_t *>(s->h_out);
-  const mi355_yolo_det *h_dets = reinterpret_cast<const mi355_yolo_det *>(s->h_out + out_counts_bytes(T));
+  const uint32_t *h_n = reinterpret_cast<const uint32_t *>(s->h_out.p);
+  const mi355_yolo_det *h_dets = reinterpret_cast<const mi355_yolo_det *>(s->h_out.p + out_counts_bytes(T));
   for (uint32_t t = 0; t < T; t++) {
     n_dets[t] = h_n[t];
     const uint32_t w = h_n[t] < max_dets ? h_n[t] : max_dets;
@@ -337,56 +305,25 @@ static int yolodec_run(mi355_ctx *ctx, YoloDecState *s, const float *d_tensors, 
   s->count_zero = false;   // true again only once the NMS kernel has been enqueued behind the score kernel
   if (layout == MI355_YOLO_V8)
     hipLaunchKernelGGL(yolodec_score_kernel<0>, grid, dim3(kScoreThreads), 0, ctx->stream, reinterpret_cast<const uint32_t *>(d_tensors), pitch_dwords, F, N,
-                       s->d_params, s->d_count, s->d_keys, key_pitch);
+                       s->d_params.p, s->d_count.p, s->d_keys.p, key_pitch);
   else
     hipLaunchKernelGGL(yolodec_score_kernel<1>, grid, dim3(kScoreThreads), 0, ctx->stream, reinterpret_cast<const uint32_t *>(d_tensors), pitch_dwords, F, N,
-                       s->d_params, s->d_count, s->d_keys, key_pitch);
+                       s->d_params.p, s->d_count.p, s->d_keys.p, key_pitch);
   if ((rc = check_hip(ctx, hipGetLastError(), "yolodec score launch"))) return rc;
   if (layout == MI355_YOLO_V8)
-    hipLaunchKernelGGL(yolodec_nms_kernel<0>, dim3(T), dim3(kNmsThreads), 0, ctx->stream, d_tensors, pitch_dwords, F, N, s->d_params, s->d_count, s->d_keys, key_pitch,
-                       s->d_kbox, s->d_ksrc, d_dets, max_dets, d_n);
+    hipLaunchKernelGGL(yolodec_nms_kernel<0>, dim3(T), dim3(kNmsThreads), 0, ctx->stream, d_tensors, pitch_dwords, F, N, s->d_params.p, s->d_count.p, s->d_keys.p, key_pitch,
+                       s->d_kbox.p, s->d_ksrc.p, d_dets, max_dets, d_n);
   else
-    hipLaunchKernelGGL(yolodec_nms_kernel<1>, dim3(T), dim3(kNmsThreads), 0, ctx->stream, d_tensors, pitch_dwords, F, N, s->d_params, s->d_count, s->d_keys, key_pitch,
-                       s->d_kbox, s->d_ksrc, d_dets, max_dets, d_n);
+    hipLaunchKernelGGL(yolodec_nms_kernel<1>, dim3(T), dim3(kNmsThreads), 0, ctx->stream, d_tensors, pitch_dwords, F, N, s->d_params.p, s->d_count.p, s->d_keys.p, key_pitch,
+                       s->d_kbox.p, s->d_ksrc.p, d_dets, max_dets, d_n);
   if ((rc = check_hip(ctx, hipGetLastError(), "yolodec nms launch"))) return rc;
   return yolodec_download(ctx, s, T, dets, max_dets, n_dets);
 }
 
 // ---- launch sets of the video group's decoder queue
 
-// the layout of one set (mi355_selftest_yolodec_set_plan; yolodec_launch_set lays its scratch out with it)
-int yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, uint32_t *first_block,
-                     uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]) {
-  if (n_jobs < 0 || n_jobs > kYdSetMax || !totals) return MI355_ERR_INVALID_ARG;
-  if (n_jobs > 0 && (!layout || !num_fields || !num_candidates || !max_dets || !first_block || !blocks || !key_offset || !box_offset || !det_offset))
-    return MI355_ERR_INVALID_ARG;
-  for (int j = 0; j < n_jobs; j++) {
-    const char *why = nullptr;
-    const int rc = yolodec_check_args((size_t)num_fields[j] * num_candidates[j] * 4, 1, layout[j], num_fields[j], num_candidates[j], &why);
-    if (rc) return rc;
-  }
-  uint64_t t[6] = {0, 0, 0, 0, 0, 0};   // V8 blocks, X blocks, NMS blocks, keys, boxes, records
-  for (int j = 0; j < n_jobs; j++) {
-    const uint32_t N = num_candidates[j];
-    uint64_t &layout_blocks = t[layout[j] == MI355_YOLO_V8 ? 0 : 1];
-    blocks[j] = (N + kScoreThreads - 1) / kScoreThreads;
-    first_block[j] = (uint32_t)layout_blocks;   // at most 32 * 256 blocks
-    layout_blocks += blocks[j];
-    if (N) t[2]++;
-    key_offset[j] = t[3];
-    t[3] += pow2_at_least(N);
-    box_offset[j] = t[4];
-    t[4] += N;
-    det_offset[j] = t[5];
-    t[5] += max_dets[j] < N ? max_dets[j] : N;
-  }
-  for (int k = 0; k < 6; k++) totals[k] = t[k];
-  return MI355_OK;
-}
-
-// the layout of one set that may hold heads (mi355_selftest_yolox_head_set_plan; yolodec_launch_set lays the set out with it): a
-// tensor job gets what yolodec_set_plan gives it, a head job is a job of A candidates whose tiles run level by level in a launch of
-// the heads' own
+// the layout of one set (the two selftest exports; yolodec_plan_set plans the queue's sets with it): a tensor job's tiles run in the
+// score launch of its layout, a head job is a job of A candidates whose tiles run level by level in a launch of the heads' own
 int yolodec_mixed_set_plan(int n_jobs, const int *kind, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets, const int *n_levels,
                            const uint32_t *level_h, const uint32_t *level_w, uint32_t *candidates, uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset,
                            uint64_t *box_offset, uint64_t *det_offset, uint32_t *level_first_block, uint64_t totals[8]) {
@@ -445,20 +382,21 @@ int yolodec_mixed_set_plan(int n_jobs, const int *kind, const uint32_t *num_fiel
 
 // scratch of one queue; grows to the largest set seen
 struct YdSetScratch {
-  uint32_t *d_count = nullptr;   // [kYdSetMax] survivors; zero between sets
+  DeviceBuf<uint32_t> d_count;   // [kYdSetMax] survivors; zero between sets
   bool count_zero = false;       // false after the allocation or an interrupted set: cleared before the next launch
-  unsigned long long *d_keys = nullptr;
-  float4 *d_kbox = nullptr;
-  uint32_t *d_ksrc = nullptr;
-  uint8_t *d_out = nullptr;      // [kYdSetMax] counts (kYdCountsBytes), then the jobs' records at their det_offset
-  YhTable *d_table = nullptr;    // the head members' tables of the set that runs; made with the first set that holds a head
-  size_t key_elems = 0, kbox_elems = 0, ksrc_elems = 0, out_bytes = 0, tables = 0;
+  DeviceBuf<unsigned long long> d_keys;
+  DeviceBuf<float4> d_kbox;
+  DeviceBuf<uint32_t> d_ksrc;
+  DeviceBuf<uint8_t> d_out;      // [kYdSetMax] counts (kYdCountsBytes), then the jobs' records at their det_offset
+  DeviceBuf<YhTable> d_table;    // the head members' tables of the set that runs; made with the first set that holds a head
 };
 
 YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err) {
   auto *S = new YdSetScratch();
-  if (hipMalloc((void **)&S->d_count, (size_t)kYdSetMax * sizeof(uint32_t)) != hipSuccess) {
-    (void)hipGetLastError();
+  bool fresh = false;
+  const hipError_t e = S->d_count.reserve((size_t)kYdSetMax, &fresh);
+  if (fresh) S->count_zero = false;   // new counters hold anything
+  if (e != hipSuccess) {
     delete S;
     *status = MI355_ERR_OUT_OF_MEMORY;
     *err = "hipMalloc(yolodec set counters)";
@@ -468,28 +406,7 @@ YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err) {
   return S;
 }
 
-void yolodec_set_scratch_free(YdSetScratch *S) {
-  if (!S) return;
-  if (S->d_count) (void)hipFree(S->d_count);
-  if (S->d_keys) (void)hipFree(S->d_keys);
-  if (S->d_kbox) (void)hipFree(S->d_kbox);
-  if (S->d_ksrc) (void)hipFree(S->d_ksrc);
-  if (S->d_out) (void)hipFree(S->d_out);
-  if (S->d_table) (void)hipFree(S->d_table);
-  delete S;
-}
-
-// (hipFree waits for the device: a set still running on the queue's stream has finished with the old allocation)
-template <typename T>
-static bool set_grow(T **p, size_t *have, size_t want) {
-  if (*have >= want && *p) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc((void **)p, want * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-  *have = want;
-  return true;
-}
+void yolodec_set_scratch_free(YdSetScratch *S) { delete S; }
 
 size_t yolodec_set_result_bytes(uint64_t records) { return kYdCountsBytes + (size_t)records * sizeof(mi355_yolo_det); }
 
@@ -500,66 +417,76 @@ size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs) {
   return level_jobs ? set_table_offset(records) + yh_table_bytes(level_jobs) : yolodec_set_result_bytes(records);
 }
 
-int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, void *h_block, size_t h_block_bytes, int *kernel_launches,
-                       int head_counts[3], std::string *err) {
+// the one place a set's members become the plan's arrays
+int yolodec_plan_set(const YdTensor *tensors, int n, YdSetPlan *out) {
+  for (uint64_t &t : out->totals) t = 0;
+  if (!tensors || n < 0 || n > kYdSetMax) return MI355_ERR_INVALID_ARG;
+  int kind[kYdSetMax], n_levels[kYdSetMax];
+  uint32_t F[kYdSetMax], cap[kYdSetMax], lv_h[kYhLevelJobsMax], lv_w[kYhLevelJobsMax];
+  size_t n_lv = 0;
+  for (int i = 0; i < n; i++) {
+    const YdTensor &t = tensors[i];
+    kind[i] = t.layout; F[i] = t.num_fields; out->candidates[i] = t.num_candidates; cap[i] = t.max_dets;
+    if (kind[i] == MI355_YOLO_X_HEAD && !t.head) return MI355_ERR_INVALID_ARG;
+    n_levels[i] = kind[i] == MI355_YOLO_X_HEAD ? t.head->n_levels : 0;
+    if (n_levels[i] < 0 || n_levels[i] > MI355_YOLOX_LEVELS_MAX) return MI355_ERR_INVALID_ARG;
+    for (int l = 0; l < n_levels[i]; l++, n_lv++) { lv_h[n_lv] = t.head->lv[l].h; lv_w[n_lv] = t.head->lv[l].w; }
+  }
+  return yolodec_mixed_set_plan(n, kind, F, out->candidates, cap, n_levels, lv_h, lv_w, out->candidates, out->first_block, out->blocks, out->key_off, out->box_off,
+                                out->det_off, out->level_first_block, out->totals);
+}
+
+int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, const YdSetPlan &P, void *h_block, size_t h_block_bytes,
+                       int *kernel_launches, int head_counts[3], std::string *err) {
   *kernel_launches = 0;
   head_counts[0] = head_counts[1] = head_counts[2] = 0;
   if (!S || !tensors || n < 1 || n > kYdSetMax) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
-  int layout[kYdSetMax], n_levels[kYdSetMax];
-  uint32_t F[kYdSetMax], N[kYdSetMax], cap[kYdSetMax], first[kYdSetMax], blocks[kYdSetMax];
-  uint32_t lv_h[kYhLevelJobsMax], lv_w[kYhLevelJobsMax], lv_first[kYhLevelJobsMax];
-  uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax], totals[8];
-  size_t n_lv = 0;
-  for (int i = 0; i < n; i++) {
-    layout[i] = tensors[i].layout; F[i] = tensors[i].num_fields; N[i] = tensors[i].num_candidates; cap[i] = tensors[i].max_dets;
-    if (layout[i] == MI355_YOLO_X_HEAD && !tensors[i].head) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
-    n_levels[i] = layout[i] == MI355_YOLO_X_HEAD ? tensors[i].head->n_levels : 0;
-    if (n_levels[i] < 0 || n_levels[i] > MI355_YOLOX_LEVELS_MAX) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
-    for (int l = 0; l < n_levels[i]; l++, n_lv++) { lv_h[n_lv] = tensors[i].head->lv[l].h; lv_w[n_lv] = tensors[i].head->lv[l].w; }
-  }
-  const int rc = yolodec_mixed_set_plan(n, layout, F, N, cap, n_levels, lv_h, lv_w, N, first, blocks, key_off, box_off, det_off, lv_first, totals);
-  if (rc) { *err = "yolodec: bad launch set"; return rc; }
+  const uint64_t *totals = P.totals;
   if (totals[2] == 0) return MI355_OK;   // no job has a candidate: nothing to launch, nothing to copy
   const size_t bytes = yolodec_set_result_bytes(totals[5]), table_bytes = yh_table_bytes(totals[7]);
   if (!h_block || h_block_bytes < yolodec_set_block_bytes(totals[5], totals[7])) { *err = "yolodec: the pinned block is too small for the set"; return MI355_ERR_INVALID_ARG; }
-  if (!set_grow(&S->d_keys, &S->key_elems, (size_t)totals[3]) || !set_grow(&S->d_kbox, &S->kbox_elems, (size_t)totals[4]) ||
-      !set_grow(&S->d_ksrc, &S->ksrc_elems, (size_t)totals[4]) || !set_grow(&S->d_out, &S->out_bytes, bytes) ||
-      (table_bytes && !set_grow(&S->d_table, &S->tables, (size_t)1))) {
+  // (growing frees first, which waits for the device: a set still running on the queue's stream has finished with the old allocation)
+  if (S->d_keys.reserve((size_t)totals[3]) != hipSuccess || S->d_kbox.reserve((size_t)totals[4]) != hipSuccess ||
+      S->d_ksrc.reserve((size_t)totals[4]) != hipSuccess || S->d_out.reserve(bytes) != hipSuccess ||
+      (table_bytes && S->d_table.reserve((size_t)1) != hipSuccess)) {
     *err = "hipMalloc(yolodec set scratch)";
     return MI355_ERR_OUT_OF_MEMORY;
   }
   if (!S->count_zero) {
-    if (hipMemsetAsync(S->d_count, 0, (size_t)kYdSetMax * sizeof(uint32_t), stream) != hipSuccess) { *err = "hipMemsetAsync(yolodec set counters)"; return MI355_ERR_HIP; }
+    if (hipMemsetAsync(S->d_count.p, 0, (size_t)kYdSetMax * sizeof(uint32_t), stream) != hipSuccess) { *err = "hipMemsetAsync(yolodec set counters)"; return MI355_ERR_HIP; }
     S->count_zero = true;
   }
   YdJobTable score[2] = {}, nms = {};
   YhTable *heads = table_bytes ? reinterpret_cast<YhTable *>(static_cast<uint8_t *>(h_block) + set_table_offset(totals[5])) : nullptr;
   uint32_t n_heads = 0, n_level_jobs = 0;
-  uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out);
-  mi355_yolo_det *d_dets = reinterpret_cast<mi355_yolo_det *>(S->d_out + kYdCountsBytes);
+  uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out.p);
+  mi355_yolo_det *d_dets = reinterpret_cast<mi355_yolo_det *>(S->d_out.p + kYdCountsBytes);
   for (int i = 0; i < n; i++) {
-    if (!N[i]) continue;   // no candidate: no job
-    if (layout[i] == MI355_YOLO_X_HEAD) {
+    const YdTensor &t = tensors[i];
+    const uint32_t N = P.candidates[i];
+    if (!N) continue;   // no candidate: no job
+    if (t.layout == MI355_YOLO_X_HEAD) {
+      const int n_levels = t.head->n_levels;   // the plan stands: the head has its levels
       YhHeadJob &H = heads->head[n_heads];
-      H.count = S->d_count + i;
-      H.keys = S->d_keys + key_off[i];
-      H.kbox = S->d_kbox + box_off[i];
-      H.ksrc = S->d_ksrc + box_off[i];
-      H.dets = d_dets + det_off[i];
+      H.count = S->d_count.p + i;
+      H.keys = S->d_keys.p + P.key_off[i];
+      H.kbox = S->d_kbox.p + P.box_off[i];
+      H.ksrc = S->d_ksrc.p + P.box_off[i];
+      H.dets = d_dets + P.det_off[i];
       H.n_dets = d_n + i;
-      H.A = N[i];
-      H.C = F[i] - 5;
-      H.key_cap = pow2_at_least(N[i]);
-      H.max_dets = cap[i];
+      H.A = N;
+      H.C = t.num_fields - 5;
+      H.key_cap = pow2_at_least(N);
+      H.max_dets = t.max_dets;
       H.first_level = n_level_jobs;
-      H.n_levels = (uint32_t)n_levels[i];
-      H.p = tensors[i].p;
+      H.n_levels = (uint32_t)n_levels;
+      H.p = t.p;
       H.pad = 0;
       uint32_t a = 0;
       for (int l = 0; l < MI355_YOLOX_LEVELS_MAX; l++) {
         H.start[l] = a;   // A from n_levels on
-        if (l >= n_levels[i]) continue;
-        const mi355_yolox_level &v = tensors[i].head->lv[l];
+        if (l >= n_levels) continue;
+        const mi355_yolox_level &v = t.head->lv[l];
         YhLevelJob &L = heads->level[n_level_jobs];
         L.reg = v.reg;
         L.obj = v.obj;
@@ -567,7 +494,7 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
         L.w = v.w;
         L.hw = v.h * v.w;
         L.first_cand = a;
-        L.first_block = first[i] + lv_first[n_level_jobs];   // the level jobs of a set are in the order of the plan's levels
+        L.first_block = P.first_block[i] + P.level_first_block[n_level_jobs];   // the level jobs of a set are in the order of the plan's levels
         L.head = n_heads;
         L.stride = (float)v.stride;   // <= 65536: exact
         a += L.hw;
@@ -577,29 +504,29 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
       continue;
     }
     YdJob J;
-    J.data = tensors[i].data;
-    J.count = S->d_count + i;
-    J.keys = S->d_keys + key_off[i];
-    J.kbox = S->d_kbox + box_off[i];
-    J.ksrc = S->d_ksrc + box_off[i];
-    J.dets = d_dets + det_off[i];
+    J.data = t.data;
+    J.count = S->d_count.p + i;
+    J.keys = S->d_keys.p + P.key_off[i];
+    J.kbox = S->d_kbox.p + P.box_off[i];
+    J.ksrc = S->d_ksrc.p + P.box_off[i];
+    J.dets = d_dets + P.det_off[i];
     J.n_dets = d_n + i;
-    J.F = F[i];
-    J.N = N[i];
-    J.key_cap = pow2_at_least(N[i]);
-    J.max_dets = cap[i];
-    J.first_block = first[i];
-    J.blocks = blocks[i];
-    J.layout = layout[i];
-    J.p = tensors[i].p;
-    YdJobTable &T = score[layout[i] == MI355_YOLO_V8 ? 0 : 1];
+    J.F = t.num_fields;
+    J.N = N;
+    J.key_cap = pow2_at_least(N);
+    J.max_dets = t.max_dets;
+    J.first_block = P.first_block[i];
+    J.blocks = P.blocks[i];
+    J.layout = t.layout;
+    J.p = t.p;
+    YdJobTable &T = score[t.layout == MI355_YOLO_V8 ? 0 : 1];
     T.job[T.n_jobs++] = J;
     nms.job[nms.n_jobs++] = J;
   }
   hipError_t e = hipSuccess;
   if (n_heads) {
     // the tables of all heads of the set, one copy: what the launches below read stands in device memory behind it
-    e = hipMemcpyAsync(S->d_table, heads, table_bytes, hipMemcpyHostToDevice, stream);
+    e = hipMemcpyAsync(S->d_table.p, heads, table_bytes, hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) { *err = std::string("yolodec set head tables H2D: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
     head_counts[1] = 1;
   }
@@ -621,12 +548,12 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
   }
   if (n_heads) {
     // (a launch of their own: merged into the tensors' NMS kernel, the head loader's registers would be every tensor job's)
-    if (const int hrc = yolox_head_launch_jobs(stream, S->d_table, n_heads, n_level_jobs, (uint32_t)totals[6], &head_counts[2], err)) return hrc;
+    if (const int hrc = yolox_head_launch_jobs(stream, S->d_table.p, n_heads, n_level_jobs, (uint32_t)totals[6], &head_counts[2], err)) return hrc;
     *kernel_launches += head_counts[2];
     head_counts[0] = (int)n_heads;
   }
   S->count_zero = true;
-  e = hipMemcpyAsync(h_block, S->d_out, bytes, hipMemcpyDeviceToHost, stream);
+  e = hipMemcpyAsync(h_block, S->d_out.p, bytes, hipMemcpyDeviceToHost, stream);
   if (e != hipSuccess) { *err = std::string("yolodec set D2H: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
   return MI355_OK;
 }
@@ -672,9 +599,9 @@ int mi355_yolodec_tensor(mi355_ctx *ctx, const float *data, int layout, uint32_t
   YoloDecState *s = nullptr;
   if ((rc = yolodec_scratch(ctx, 1, num_candidates, max_dets, &s))) return rc;
   if ((rc = yolodec_stage(ctx, s, bytes / 4))) return rc;
-  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage, data, bytes, hipMemcpyHostToDevice, ctx->stream), "yolodec H2D"))) return rc;
+  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_stage.p, data, bytes, hipMemcpyHostToDevice, ctx->stream), "yolodec H2D"))) return rc;
   __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
-  return yolodec_run(ctx, s, s->d_stage, bytes, 1, layout, num_fields, num_candidates, p, dets, max_dets, n_dets);
+  return yolodec_run(ctx, s, s->d_stage.p, bytes, 1, layout, num_fields, num_candidates, p, dets, max_dets, n_dets);
 }
 
 int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates) {
@@ -684,7 +611,15 @@ int mi355_selftest_yolodec_check(size_t tensor_pitch_bytes, int n_tensors, int l
 
 int mi355_selftest_yolodec_set_plan(int n_jobs, const int *layout, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets,
                                     uint32_t *first_block, uint32_t *blocks, uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset, uint64_t totals[6]) {
-  return yolodec_set_plan(n_jobs, layout, num_fields, num_candidates, max_dets, first_block, blocks, key_offset, box_offset, det_offset, totals);
+  if (!totals) return MI355_ERR_INVALID_ARG;
+  // the mixed plan without level arrays: it refuses a head job with MI355_ERR_INVALID_ARG, in job order with the other refusals
+  uint32_t candidates[kYdSetMax];
+  uint64_t t[8];
+  const int rc = yolodec_mixed_set_plan(n_jobs, layout, num_fields, num_candidates, max_dets, nullptr, nullptr, nullptr, candidates, first_block, blocks, key_offset,
+                                        box_offset, det_offset, nullptr, t);
+  if (rc) return rc;
+  for (int k = 0; k < 6; k++) totals[k] = t[k];
+  return MI355_OK;
 }
 
 int mi355_selftest_yolox_head_set_plan(int n_jobs, const int *kind, const uint32_t *num_fields, const uint32_t *num_candidates, const uint32_t *max_dets,

@@ -1,12 +1,12 @@
 // yolodec_device.hpp - the device functions and the per-context scratch that the tensor decoders (yolodec.hip) and the YOLOX head
 // decoder (yolox_head.hip) share: the survivor key (11 bits class | 32 bits inverted total_cmp key of the confidence | 16 bits
-// candidate - ascending key order is the output order), the wave-aggregated append, and the NMS block - bitonic sort of the keys,
-// class runs, greedy NMS per run, records. What differs between the callers is where a candidate's box comes from: nms_block takes
-// a loader, `Box load(uint32_t candidate)`.
+// candidate - ascending key order is the output order) and the NMS block - bitonic sort of the keys, class runs, greedy NMS per run,
+// records. What differs between the callers is where a candidate's box comes from: nms_block takes a loader,
+// `Box load(uint32_t candidate)`. The primitives the hand decoders use as well (total_key and its inverse, cast_i32, Box, kPadKey,
+// pow2_at_least, the wave-aggregated append_keys) are in decode_device.hpp.
 #pragma once
+#include "decode_device.hpp"
 #include "internal.hpp"
-
-#include <climits>
 
 namespace mi355 {
 
@@ -18,16 +18,9 @@ constexpr int kNmsWaves = kNmsThreads / 64;
 constexpr int kLdsSortKeys = 4096;
 constexpr uint32_t kMaxFields = 1029, kMaxCandidates = 65536, kMaxTensors = 1024;
 constexpr int kMaxClasses = 1025;       // V8 at F = 1029
-constexpr unsigned long long kPadKey = ~0ull;   // class 2047: above every real key
 
 static_assert(sizeof(mi355_yolo_det) == 48, "mi355_yolo_det is 48 bytes");
 static_assert(sizeof(mi355_yolo_params) == 12, "mi355_yolo_params is three floats");
-
-// f32::total_cmp's key: the order of the result as i32 is the total order
-__device__ __forceinline__ int32_t total_key(uint32_t bits) {
-  const int32_t s = (int32_t)bits;
-  return s ^ (int32_t)((uint32_t)(s >> 31) >> 1);
-}
 
 __device__ __forceinline__ unsigned long long make_key(uint32_t cls, uint32_t conf_bits, uint32_t cand) {
   const uint32_t asc = (uint32_t)total_key(conf_bits) ^ 0x80000000u;   // unsigned, ascending with the confidence
@@ -35,11 +28,7 @@ __device__ __forceinline__ unsigned long long make_key(uint32_t cls, uint32_t co
 }
 __device__ __forceinline__ uint32_t key_class(unsigned long long k) { return (uint32_t)(k >> 48); }
 __device__ __forceinline__ uint32_t key_cand(unsigned long long k) { return (uint32_t)(k & 0xffffu); }
-__device__ __forceinline__ uint32_t key_conf_bits(unsigned long long k) {
-  const uint32_t t = (~(uint32_t)(k >> 16)) ^ 0x80000000u;   // total_key as u32
-  const int32_t s = (int32_t)t;
-  return (uint32_t)(s ^ (int32_t)((uint32_t)(s >> 31) >> 1));   // the key map is its own inverse
-}
+__device__ __forceinline__ uint32_t key_conf_bits(unsigned long long k) { return total_key_bits((~(uint32_t)(k >> 16)) ^ 0x80000000u); }
 
 // max_by's fold: a later element replaces the best unless it is smaller
 __device__ __forceinline__ void fold_class(uint32_t bits, uint32_t cls, int32_t &best_key, uint32_t &best_bits, uint32_t &best_cls) {
@@ -49,19 +38,6 @@ __device__ __forceinline__ void fold_class(uint32_t bits, uint32_t cls, int32_t 
     best_bits = bits;
     best_cls = cls;
   }
-}
-
-// called by every lane of the wave: the survivors' keys go to keys[old count ...), one atomic for the wave
-__device__ __forceinline__ void append_keys(bool keep, unsigned long long key, uint32_t *count, unsigned long long *keys, size_t key_pitch) {
-  const unsigned long long m = __ballot(keep);
-  if (m == 0) return;   // wave-uniform
-  const int lane = (int)__lane_id();
-  const int leader = __ffsll((long long)m) - 1;
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
-  base = (uint32_t)__shfl((int)base, leader);
-  const size_t at = (size_t)base + (size_t)__popcll(m & ((1ull << lane) - 1ull));
-  if (keep && at < key_pitch) keys[at] = key;   // always inside: the counter starts at zero and a candidate is appended once
 }
 
 // ascending bitonic sort of n2 keys (a power of two) by the whole block
@@ -84,8 +60,6 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long *K, uint32_t n2)
   }
 }
 
-struct Box { float xmin, ymin, xmax, ymax; };
-
 // imp.rs:318-323, :347-352: the corners of a centre / size box, unfused
 __device__ __forceinline__ Box centre_box(float x, float y, float w, float h) {
   Box r;
@@ -106,14 +80,6 @@ __device__ __forceinline__ float iou(const Box &b1, const Box &b2) {
   const float i_ymax = fminf(b1.ymax, b2.ymax);
   const float i_area = fmaxf(i_xmax - i_xmin + 1.0f, 0.0f) * fmaxf(i_ymax - i_ymin + 1.0f, 0.0f);
   return i_area / (b1_area + b2_area - i_area);
-}
-
-// Rust's `as i32`: toward zero, saturating, NaN -> 0
-__device__ __forceinline__ int32_t cast_i32(float f) {
-  if (f != f) return 0;
-  if (f >= 2147483648.0f) return INT_MAX;
-  if (f <= -2147483648.0f) return INT_MIN;
-  return (int32_t)f;
 }
 
 struct NmsShared {
@@ -270,29 +236,21 @@ __device__ __forceinline__ void nms_block(const LoadBox &load, uint32_t n_classe
   write_records(K, n_classes, kb, ks, S, out, max_dets, n_out);
 }
 
-inline uint32_t pow2_at_least(uint32_t n) {
-  uint32_t p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
 }  // namespace
 
 // scratch of one context; grows to the largest shape seen. Both decoders' calls use it: they run one after the other on the
 // context's stream and each leaves the counters at zero.
 struct YoloDecState {
-  uint32_t *d_count = nullptr;   // [tensors] survivors; zero between calls
-  mi355_yolo_params *d_params = nullptr, *h_params = nullptr;
-  uint32_t tensors = 0;
+  DeviceBuf<uint32_t> d_count;   // [tensors] survivors; zero between calls
+  DeviceBuf<mi355_yolo_params> d_params;   // as many as d_count holds, and as many in h_params
+  PinnedBuf<mi355_yolo_params> h_params;
   bool count_zero = false;       // false after an allocation or an interrupted call: cleared before the next launch
-  unsigned long long *d_keys = nullptr;
-  float4 *d_kbox = nullptr;
-  uint32_t *d_ksrc = nullptr;
-  size_t key_elems = 0, kbox_elems = 0, ksrc_elems = 0;
-  uint8_t *d_out = nullptr, *h_out = nullptr;   // [tensors] counts (padded to 64 bytes), then [tensors][max_dets] records
-  size_t d_out_bytes = 0, h_out_bytes = 0;
-  float *d_stage = nullptr;      // the host form's tensor
-  size_t stage_floats = 0;
+  DeviceBuf<unsigned long long> d_keys;
+  DeviceBuf<float4> d_kbox;
+  DeviceBuf<uint32_t> d_ksrc;
+  DeviceBuf<uint8_t> d_out;      // [tensors] counts (padded to 64 bytes), then [tensors][max_dets] records
+  PinnedBuf<uint8_t> h_out;
+  DeviceBuf<float> d_stage;      // the host form's tensor
 };
 
 // counters (zero on return, or cleared on the stream), settings, keys, kept boxes and positions, results for T tensors of N candidates
@@ -302,7 +260,7 @@ int yolodec_stage(mi355_ctx *ctx, YoloDecState *s, size_t floats);
 // the T settings to s->d_params on the context's stream
 int yolodec_upload_params(mi355_ctx *ctx, YoloDecState *s, uint32_t T, const mi355_yolo_params *p);
 // where the NMS launch writes: T counts, then T x max_dets records
-inline uint32_t *yolodec_d_counts(YoloDecState *s) { return reinterpret_cast<uint32_t *>(s->d_out); }
+inline uint32_t *yolodec_d_counts(YoloDecState *s) { return reinterpret_cast<uint32_t *>(s->d_out.p); }
 mi355_yolo_det *yolodec_d_dets(YoloDecState *s, uint32_t T);
 // results down, one synchronisation, the caller's arrays filled
 int yolodec_download(mi355_ctx *ctx, YoloDecState *s, uint32_t T, mi355_yolo_det *dets, uint32_t max_dets, uint32_t *n_dets);

@@ -456,10 +456,10 @@ static int head_dets_run(mi355_ctx *ctx, YoloDecState *s, const HeadMaps &H, uin
   if ((rc = yolodec_upload_params(ctx, s, T, p))) return rc;
   const size_t key_pitch = pow2_at_least(A);
   s->count_zero = false;   // true again only once the NMS kernel has been enqueued behind the score kernel
-  hipLaunchKernelGGL(yolox_head_score_kernel, dim3((A + kScoreThreads - 1) / kScoreThreads, T), dim3(kScoreThreads), 0, ctx->stream, H, A, s->d_params, s->d_count,
-                     s->d_keys, key_pitch);
+  hipLaunchKernelGGL(yolox_head_score_kernel, dim3((A + kScoreThreads - 1) / kScoreThreads, T), dim3(kScoreThreads), 0, ctx->stream, H, A, s->d_params.p, s->d_count.p,
+                     s->d_keys.p, key_pitch);
   if ((rc = check_hip(ctx, hipGetLastError(), "yolox_head score launch"))) return rc;
-  hipLaunchKernelGGL(yolox_head_nms_kernel, dim3(T), dim3(kNmsThreads), 0, ctx->stream, H, A, s->d_params, s->d_count, s->d_keys, key_pitch, s->d_kbox, s->d_ksrc,
+  hipLaunchKernelGGL(yolox_head_nms_kernel, dim3(T), dim3(kNmsThreads), 0, ctx->stream, H, A, s->d_params.p, s->d_count.p, s->d_keys.p, key_pitch, s->d_kbox.p, s->d_ksrc.p,
                      yolodec_d_dets(s, T), max_dets, yolodec_d_counts(s));
   if ((rc = check_hip(ctx, hipGetLastError(), "yolox_head nms launch"))) return rc;
   return yolodec_download(ctx, s, T, dets, max_dets, n_dets);
@@ -534,7 +534,7 @@ int mi355_yolox_head_dets(mi355_ctx *ctx, const mi355_yolox_level *levels, int n
   // the maps side by side in the staging buffer: per level reg, obj, cls - the engine's fused [5 + C, h, w] form
   if ((rc = yolodec_stage(ctx, s, (size_t)A * (5 + (size_t)num_classes)))) return rc;
   mi355_yolox_level dl[kLv];
-  float *at = s->d_stage;
+  float *at = s->d_stage.p;
   for (int l = 0; l < n_levels; l++) {
     const size_t hw = (size_t)levels[l].h * levels[l].w;
     const float *src[3] = {levels[l].reg, levels[l].obj, levels[l].cls};

@@ -93,18 +93,42 @@ def _mixed32():
     return layout, F, N, cap
 
 
-@pytest.mark.parametrize("case", ["empty", "one_v8", "one_x", "mixed32", "all_empty_tensors"])
-def test_plan_equals_its_restatement(case):
-    layout, F, N, cap = {
+CASES = ["empty", "one_v8", "one_x", "mixed32", "all_empty_tensors"]
+
+
+def _case(case):
+    return {
         "empty": ([], [], [], []),
         "one_v8": ([V8], [84], [8400], [100]),
         "one_x": ([X], [85], [8400], [9000]),
         "mixed32": _mixed32(),
         "all_empty_tensors": ([V8, X, V8], [6, 6, 6], [0, 0, 0], [0, 5, 0]),
     }[case]
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_plan_equals_its_restatement(case):
+    layout, F, N, cap = _case(case)
     rc, first, blocks, key, box, det, totals = _plan(layout, F, N, cap)
     assert rc == OK
     assert (first, blocks, key, box, det, totals) == restate(layout, N, cap)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_plan_is_the_mixed_plan_without_heads(case):
+    """mi355_selftest_yolodec_set_plan is a thin front of the plan the queue's launch uses (mi355_selftest_yolox_head_set_plan): on
+    jobs without a head both give the same five per-job arrays and the same first six totals, and the mixed plan's two head totals
+    are zero."""
+    import mi355fx
+    layout, F, N, cap = _case(case)
+    rc, first, blocks, key, box, det, totals = _plan(layout, F, N, cap)
+    assert rc == OK
+    for levels in ([[] for _ in layout], None):                               # empty level arrays, null level arrays
+        mrc, cand, mfirst, mblocks, mkey, mbox, mdet, _, mtotals = mi355fx.selftest_yolox_head_set_plan(layout, F, N, cap, levels)
+        assert mrc == OK
+        assert cand == N
+        assert (first, blocks, key, box, det) == (mfirst, mblocks, mkey, mbox, mdet)
+        assert totals == mtotals[:6] and mtotals[6:] == [0, 0]
 
 
 def test_plan_values_by_hand():
@@ -144,3 +168,24 @@ def test_plan_refusals(lib):
     assert f(-1, *full, totals) == ERR_INVALID_ARG
     assert f(0, *full, None) == ERR_INVALID_ARG
     assert f(0, *([None] * 9), totals) == OK and list(totals) == [0] * 6
+
+
+def test_plan_refuses_a_head_job_and_writes_nothing(lib):
+    """A job of kind MI355_YOLO_X_HEAD is no layout of this plan: MI355_ERR_INVALID_ARG, wherever it stands, and no output is touched."""
+    import mi355fx
+    assert mi355fx.YOLO_X_HEAD == 2
+    f = lib.mi355_selftest_yolodec_set_plan
+    f.restype = C.c_int
+    p32, p64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    f.argtypes = [C.c_int, C.POINTER(C.c_int), p32, p32, p32, p32, p32, p64, p64, p64, p64]
+    mark32, mark64 = 0xA5A5A5A5, 0xA5A5A5A5A5A5A5A5
+    for kinds in ([mi355fx.YOLO_X_HEAD], [V8, mi355fx.YOLO_X_HEAD, X]):
+        n = len(kinds)
+        lay, F, N, cap = (C.c_int * n)(*kinds), (C.c_uint32 * n)(*[85] * n), (C.c_uint32 * n)(*[8400] * n), (C.c_uint32 * n)(*[100] * n)
+        out32 = [(C.c_uint32 * n)(*[mark32] * n) for _ in range(2)]
+        out64 = [(C.c_uint64 * n)(*[mark64] * n) for _ in range(3)]
+        totals = (C.c_uint64 * 6)(*[mark64] * 6)
+        assert f(n, lay, F, N, cap, *out32, *out64, totals) == ERR_INVALID_ARG
+        assert all(list(a) == [mark32] * n for a in out32) and all(list(a) == [mark64] * n for a in out64)
+        assert list(totals) == [mark64] * 6
+        assert _plan(kinds, [85] * n, [8400] * n, [100] * n)[0] == ERR_INVALID_ARG

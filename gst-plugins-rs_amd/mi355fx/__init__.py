@@ -152,6 +152,38 @@ def yolox_candidates(levels):
     return sum((q.h * q.w) if isinstance(q, YoloxLevel) else (q[6] * q[7]) for q in levels)
 
 
+
+class YoloxNetConfig(C.Structure):
+    """mi355_yolox_net_config: depth, width, depthwise, num_classes of a YOLOX network; reserved 0."""
+    _fields_ = [("depth", C.c_double), ("width", C.c_double), ("depthwise", C.c_int32), ("num_classes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# the reference's six constructors (MI355_YOLOX_NET_NANO .. _X): (depth, width, depthwise)
+YOLOX_VARIANTS = {"nano": (0.33, 0.25, True), "tiny": (0.33, 0.375, False), "s": (0.33, 0.50, False), "m": (0.67, 0.75, False), "l": (1.0, 1.0, False),
+                  "x": (1.33, 1.25, False)}
+YOLOX_NET_MAX_FRAMES, YOLOX_NET_MAX_SIDE, YOLOX_NET_NAME_MAX = 64, 2048, 96
+YOLOX_OP = {"conv": 0, "dw": 1, "pool5": 2, "up2": 3, "focus": 4}   # kinds of mi355_selftest_yolox_net_op_device
+
+
+def yolox_net_config(depth, width, depthwise, num_classes, reserved=0):
+    return YoloxNetConfig(float(depth), float(width), int(depthwise), int(num_classes), int(reserved))
+
+
+class YoloxNetPlan(C.Structure):
+    """mi355_yolox_net_plan: what mi355_selftest_yolox_net_plan reports."""
+    _fields_ = [("status", C.c_int32), ("config_status", C.c_int32), ("frames_status", C.c_int32), ("size_status", C.c_int32), ("param_count", C.c_uint32),
+                ("launches", C.c_uint32), ("param_floats", C.c_uint64), ("arena_bytes", C.c_uint64), ("macs", C.c_uint64), ("level_h", C.c_uint32 * 3),
+                ("level_w", C.c_uint32 * 3)]
+
+
+class YoloxNetOp(C.Structure):
+    """mi355_yolox_net_op: one op on caller views (mi355_selftest_yolox_net_op_device)."""
+    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("silu", C.c_int32), ("n_frames", C.c_uint32), ("h_in", C.c_uint32),
+                ("w_in", C.c_uint32), ("tile", C.c_uint32), ("inp", C.c_void_p), ("in_c", C.c_uint32), ("in_off", C.c_uint32), ("in_ctot", C.c_uint32),
+                ("out_c", C.c_uint32), ("out", C.c_void_p), ("out_off", C.c_uint32), ("out_ctot", C.c_uint32), ("res_off", C.c_uint32),
+                ("res_ctot", C.c_uint32), ("res", C.c_void_p), ("weight", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p)]
+
+
 class HandParams(C.Structure):
     """mi355_hand_params: the settings of one handdetectiontensordec / handlandmarktensordec instance; frame 0, 0: no frame size."""
     _fields_ = [("confidence_threshold", C.c_float), ("nms_iou_threshold", C.c_float), ("max_hands", C.c_uint32), ("frame_width", C.c_int32),
@@ -382,6 +414,20 @@ def load_library():
         "mi355_yolox_head_dets": (i, [vp, C.POINTER(YoloxLevel), i, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "mi355_yolox_input_frames_device": (i, [vp, vp, sz, sz, i, C.c_uint32, C.c_uint32, vp, sz]),
         "mi355_selftest_yolox_head_check": (i, [C.POINTER(YoloxLevel), i, i, C.c_uint32, sz]),
+        "mi355_yolox_net_create": (i, [vp, C.POINTER(YoloxNetConfig), C.POINTER(vp)]),
+        "mi355_yolox_net_destroy": (None, [vp]),
+        "mi355_yolox_net_param_count": (i, [vp]),
+        "mi355_yolox_net_param_info": (i, [vp, i, C.c_char_p, sz, C.POINTER(C.c_uint32), C.POINTER(i)]),
+        "mi355_yolox_net_set_param": (i, [vp, i, vp, sz]),
+        "mi355_yolox_net_finalize": (i, [vp]),
+        "mi355_yolox_net_forward_device": (i, [vp, vp, sz, i, C.c_uint32, C.c_uint32, C.POINTER(YoloxLevel)]),
+        "mi355_yolox_net_launches": (i, [vp]),
+        "mi355_yolox_net_arena_info": (i, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mi355_yolox_infer_frames_device": (i, [vp, vp, sz, sz, i, C.c_uint32, C.c_uint32, vp, sz]),
+        "mi355_yolox_infer_dets_device": (i, [vp, vp, sz, sz, i, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "mi355_selftest_yolox_net_plan": (i, [C.POINTER(YoloxNetConfig), i, C.c_uint32, C.c_uint32, C.POINTER(YoloxNetPlan)]),
+        "mi355_selftest_yolox_net_param_info": (i, [C.POINTER(YoloxNetConfig), i, C.c_char_p, sz, C.POINTER(C.c_uint32), C.POINTER(i)]),
+        "mi355_selftest_yolox_net_op_device": (i, [vp, C.POINTER(YoloxNetOp)]),
         "mi355_handdec_palm_tensor": (i, [vp, vp, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
         "mi355_handdec_palm_tensors_device": (i, [vp, vp, sz, i, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
         "mi355_handdec_landmarks_tensor": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(HandParams), vp, vp, C.POINTER(C.c_uint32)]),
@@ -839,6 +885,116 @@ def selftest_yolox_head_check(levels, n_tensors, num_classes, out_pitch_bytes, n
     L = load_library()
     n = (0 if levels is None else len(levels)) if n_levels is None else n_levels
     return L.mi355_selftest_yolox_head_check(None if levels is None else _yolox_levels(levels), n, n_tensors, num_classes, out_pitch_bytes)
+
+
+def _yolox_param_table(fn, n=None):
+    """[(name, dims)] of a parameter enumeration: fn(index, name buffer, cap, dims, n_dims) -> status; n None: until the first refusal."""
+    out, k = [], 0
+    name, dims, nd = C.create_string_buffer(YOLOX_NET_NAME_MAX), (C.c_uint32 * 4)(), C.c_int(0)
+    while n is None or k < n:
+        rc = fn(k, name, YOLOX_NET_NAME_MAX, dims, C.byref(nd))
+        if rc != 0:
+            if n is None:
+                break
+            raise Mi355Error(rc, "yolox_net parameter %d" % k)
+        out.append((name.value.decode(), tuple(int(d) for d in dims[:nd.value])))
+        k += 1
+    return out
+
+
+def selftest_yolox_net_plan(config, n_frames, H, W):
+    """mi355_selftest_yolox_net_plan (host only) -> (status, YoloxNetPlan). config: a YoloxNetConfig or None."""
+    L = load_library()
+    plan = YoloxNetPlan()
+    rc = L.mi355_selftest_yolox_net_plan(None if config is None else C.byref(config), n_frames, H, W, C.byref(plan))
+    return rc, plan
+
+
+def selftest_yolox_net_params(config, n=None):
+    """The parameter table of a config without a device (mi355_selftest_yolox_net_param_info): [(name, dims)] in the net's order."""
+    L = load_library()
+    return _yolox_param_table(lambda k, name, cap, dims, nd: L.mi355_selftest_yolox_net_param_info(C.byref(config), k, name, cap, dims, nd), n)
+
+
+class YoloxNet:
+    """mi355_yolox_net: yoloxinference's network on one Context. Set every parameter (set_param / load), finalize(), then forward_device
+    or the two compositions. Destroy it (close) before its context."""
+
+    def __init__(self, ctx, config):
+        self.ctx, self.L, self.config = ctx, ctx.L, config
+        h = C.c_void_p()
+        self.h = None
+        ctx._ck(self.L.mi355_yolox_net_create(ctx.h, None if config is None else C.byref(config), C.byref(h)))
+        self.h = h.value
+        self.num_classes = int(config.num_classes)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mi355_yolox_net_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def param_count(self):
+        return int(self.L.mi355_yolox_net_param_count(self.h))
+
+    def params(self):
+        return _yolox_param_table(lambda k, name, cap, dims, nd: self.L.mi355_yolox_net_param_info(self.h, k, name, cap, dims, nd), self.param_count())
+
+    def set_param(self, index, values, n=None):
+        a = np.ascontiguousarray(values, dtype=np.float32)
+        self.ctx._ck(self.L.mi355_yolox_net_set_param(self.h, index, a.ctypes.data, a.size if n is None else n))
+
+    def load(self, arrays):
+        """arrays: {name: array} holding every parameter of params()."""
+        for k, (name, dims) in enumerate(self.params()):
+            self.set_param(k, np.asarray(arrays[name], dtype=np.float32).reshape(dims))
+
+    def finalize(self):
+        self.ctx._ck(self.L.mi355_yolox_net_finalize(self.h))
+
+    def launches(self):
+        return int(self.L.mi355_yolox_net_launches(self.h))
+
+    def arena_info(self):
+        """(arena bytes, device allocations made for activations so far)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self.ctx._ck(self.L.mi355_yolox_net_arena_info(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def forward_device(self, d_in, in_pitch_bytes, n_frames, H, W):
+        """-> the three YoloxLevel structs (device pointers into the net's memory, valid until the next forward). Asynchronous."""
+        lv = (YoloxLevel * 3)()
+        self.ctx._ck(self.L.mi355_yolox_net_forward_device(self.h, d_in, in_pitch_bytes, n_frames, H, W, lv))
+        return [lv[0], lv[1], lv[2]]
+
+    def read_levels(self, levels, n_frames):
+        """The raw maps of forward_device's levels read back: per level an array [n_frames, 5 + C, h, w] (reg 0:4, obj 4, cls 5:)."""
+        self.ctx.synchronize()
+        out = []
+        for lv in levels:
+            a = np.empty((n_frames, 5 + self.num_classes, lv.h, lv.w), np.float32)
+            assert lv.reg_pitch_bytes == a[0].nbytes and lv.obj == lv.reg + 16 * lv.h * lv.w and lv.cls == lv.reg + 20 * lv.h * lv.w
+            self.ctx.d2h(a, lv.reg)
+            out.append(a)
+        return out
+
+    def infer_frames_device(self, d_frames, frame_pitch, stride, n_frames, width, height, d_out, out_pitch_bytes):
+        self.ctx._ck(self.L.mi355_yolox_infer_frames_device(self.h, d_frames, frame_pitch, stride, n_frames, width, height, d_out, out_pitch_bytes))
+
+    def infer_dets_device(self, d_frames, frame_pitch, stride, n_frames, width, height, params, max_dets, return_counts=False):
+        p, n_p = _yolo_params(params)
+        if n_p != n_frames:
+            raise ValueError("yolox infer_dets_device: one settings triple per frame")
+        dets = np.zeros((n_frames, max(max_dets, 1)), YOLO_DET)
+        n = (C.c_uint32 * n_frames)()
+        self.ctx._ck(self.L.mi355_yolox_infer_dets_device(self.h, d_frames, frame_pitch, stride, n_frames, width, height, p, dets.ctypes.data, max_dets, n))
+        out = [dets[k, :min(n[k], max_dets)].copy() for k in range(n_frames)]
+        return (out, [int(v) for v in n]) if return_counts else out
 
 
 def selftest_yolodec_set_plan(layouts, num_fields, num_candidates, max_dets):
@@ -1831,6 +1987,14 @@ class Context:
         """RGB u8 frames (row stride `stride`, frame i at d_frames + i * frame_pitch) -> [3][H][W] float32 per frame at
         d_out + i * out_pitch_bytes, unscaled. One launch, asynchronous."""
         self._ck(self.L.mi355_yolox_input_frames_device(self.h, d_frames, frame_pitch, stride, n_frames, width, height, d_out, out_pitch_bytes))
+
+    def selftest_yolox_net_op(self, **fields):
+        """mi355_selftest_yolox_net_op_device (test only): one op of the network on caller views; kind: a YOLOX_OP name."""
+        op = YoloxNetOp()
+        fields["kind"] = YOLOX_OP[fields["kind"]]
+        for k, v in fields.items():
+            setattr(op, k, v)
+        self._ck(self.L.mi355_selftest_yolox_net_op_device(self.h, C.byref(op)))
 
     # ---- handdetectiontensordec / handlandmarktensordec (analytics/analytics/src/hand)
     def handdec_palm(self, tensor, params, return_count=False):

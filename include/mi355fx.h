@@ -1069,6 +1069,106 @@ int mi355_yolox_input_frames_device(mi355_ctx *ctx, const uint8_t *d_frames, siz
 int mi355_selftest_yolox_head_check(const mi355_yolox_level *levels, int n_levels, int n_tensors, uint32_t num_classes,
                                     size_t out_pitch_bytes);
 
+/* ---------------------------------------------------------------- yoloxinference: the network (csrc/yolox_net.hip)
+ * The f32 forward pass of Yolox::forward (analytics/burn/src/yoloxinference/yolox_burn/model/{blocks,bottleneck,darknet,pafpn,head,
+ * yolox}.rs) up to, but not including, Head::decode and the two sigmoids of head.rs:75: for each of the three levels (strides 8, 16,
+ * 32) the raw reg [4][h][w], obj [1][h][w] and cls [C][h][w] maps of reg_pred, obj_pred and cls_pred. The three maps of a level lie
+ * in one allocation, the fused [5 + C, h, w] form of mi355_yolox_level, so the levels a forward fills go straight into
+ * mi355_yolox_head_decode_device / _head_dets_device with n_tensors = n_frames. The contract is DESIGN 4.14.
+ * Stated deviation (as 4.13's): burn's backends own the summation order of a convolution and their exp, and their source is not in the
+ * reference tree - RESTATED WITHOUT SOURCE, PARITY UNPINNED. Ours is f32 throughout: f32 inputs, f32 fused multiply-add accumulation
+ * in ascending (input channel, tap row, tap column) order - in steps of 16 terms whose sums are added in ascending order - and no
+ * reduced-precision operand anywhere. BatchNorm (eps 1e-3, blocks.rs:114)
+ * is a per-channel epilogue acc * scale + shift with scale = gamma / sqrt(var + eps), shift = beta - mean * scale computed in f64 and
+ * rounded once to f32 at finalize; it is not folded into the weights. SiLU is x * (1 / (1 + exp(-x))) in f32. A Bottleneck's shortcut
+ * is added after the activation (bottleneck.rs:20-30). Max-pool padding never wins (-inf). The net is deterministic: no atomics, no
+ * split accumulation; the result of a frame does not depend on n_frames or on its position in the batch.
+ *   config     depth in {0.33, 0.67, 1.0, 1.33} and width in {0.25, 0.375, 0.5, 0.75, 1.0, 1.25} (darknet.rs:51-59), depthwise 0 / 1,
+ *              num_classes 1..1024, reserved 0; anything else MI355_ERR_INVALID_ARG (num_classes above 1024: MI355_ERR_UNSUPPORTED).
+ *              Channel counts are floor(n * width) in f64 (blocks.rs:12), block counts max(round(3 * depth), 1) (darknet.rs:62), three
+ *              times that in dark3 / dark4; shortcut is on in the backbone's C3 blocks but dark5's, off in the PAFPN's.
+ *   parameters enumerated in ONE fixed order: the modules in the order their structs declare them (Yolox: backbone, head; Pafpn:
+ *              backbone, lateral_conv0, c3_n3, c3_n4, c3_p3, c3_p4, reduce_conv1, bu_conv1, bu_conv2; CspDarknet: stem, dark2 .. dark5;
+ *              CspBlock: conv, c3, spp; CspBottleneck: conv1, conv2, conv3, m.0 ..; Bottleneck and SppBottleneck: conv1, conv2;
+ *              Head: stems.0 .. 2, cls_convs.0 .. 2 (conv0, conv1), reg_convs, cls_preds, reg_preds, obj_preds; a depthwise Conv:
+ *              dconv, pconv), and per BaseConv conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var; per prediction
+ *              layer weight, bias. Names are the state-dict names after the remapping of yolox.rs:255-272, e.g.
+ *              backbone.backbone.dark3.c3.m.0.conv2.conv.weight, head.cls_convs.1.conv0.conv.weight. Weights are [out][in / groups][k][k].
+ *   _set_param uploads parameter i from host memory (synchronous); n must be the parameter's element count. _finalize refuses
+ *              (INVALID_ARG) while a parameter is unset; after it the net is immutable and _set_param fails (INVALID_ARG).
+ *   _forward_device  d_in: [3][H][W] f32 per frame (what mi355_yolox_input_frames_device writes), frame i at (char *)d_in + i *
+ *              in_pitch_bytes. Fills levels[3] with pointers into memory the net owns, valid until the next forward or destroy; level
+ *              pitches are per frame. Asynchronous on the context's stream; no host synchronisation and no allocation once a shape
+ *              has been seen: the activation arena is one allocation planned per (n_frames, H, W) that grows to the largest shape seen.
+ *              H, W multiples of 32 (else INVALID_ARG; the pad template's rule, yoloxinference/imp.rs:239-247) and <= 2048, n_frames
+ *              1..64 (above: MI355_ERR_UNSUPPORTED). Before _finalize: MI355_ERR_NOT_CONFIGURED.
+ *   _launches  kernel launches of one forward (the length of the net's op list); _arena_info: the arena's bytes and how many device
+ *              allocations the net has made for activations and the compositions' input tensor since create.
+ *   _infer_frames_device / _infer_dets_device   DEFINED BY COMPOSITION: mi355_yolox_input_frames_device into a tensor the net owns,
+ *              _forward_device, then mi355_yolox_head_decode_device / mi355_yolox_head_dets_device on the same stream - the same
+ *              bytes as calling the three yourself. The second takes RGB frames and returns detections; nothing else crosses PCIe.
+ *   mi355_selftest_yolox_net_plan / _param_info : host only, no device: every check's status, the parameter table and the plan.
+ *   mi355_selftest_yolox_net_op_device : test only: ONE op of the list (kind 0 dense conv, 1 depthwise 3x3, 2 max-pool 5, 3 nearest
+ *              2x upsample, 4 the stem's dense conv over the Focus gather of an [3][2 h_in][2 w_in] frame) on caller views: base
+ *              pointer of channel 0 of the wider buffer, channel offset, channels of the wider buffer; frames are contiguous.
+ *              The dense kernel has two tile shapes (64 channels x 64 or x 16 pixels; a forward takes the narrow one where the wide
+ *              one would leave compute units without a block); every output is the same chain of 16-term steps under both, so the
+ *              choice changes no byte.
+ * A net belongs to the context it was created on and is destroyed before it. */
+typedef struct mi355_yolox_net mi355_yolox_net;
+typedef struct mi355_yolox_net_config {
+  double depth, width;
+  int32_t depthwise;
+  uint32_t num_classes;
+  uint32_t reserved;   /* 0 */
+} mi355_yolox_net_config;
+/* the reference's six constructors (yolox.rs:40-222) */
+#define MI355_YOLOX_NET_NANO(num_classes) {0.33, 0.25, 1, (num_classes), 0}
+#define MI355_YOLOX_NET_TINY(num_classes) {0.33, 0.375, 0, (num_classes), 0}
+#define MI355_YOLOX_NET_S(num_classes) {0.33, 0.50, 0, (num_classes), 0}
+#define MI355_YOLOX_NET_M(num_classes) {0.67, 0.75, 0, (num_classes), 0}
+#define MI355_YOLOX_NET_L(num_classes) {1.0, 1.0, 0, (num_classes), 0}
+#define MI355_YOLOX_NET_X(num_classes) {1.33, 1.25, 0, (num_classes), 0}
+#define MI355_YOLOX_NET_MAX_FRAMES 64
+#define MI355_YOLOX_NET_MAX_SIDE 2048
+#define MI355_YOLOX_NET_NAME_MAX 96   /* a name_cap that holds every parameter name */
+typedef struct mi355_yolox_net_plan {
+  int32_t status;                                     /* the first refusal of: config, frames, size */
+  int32_t config_status, frames_status, size_status;
+  uint32_t param_count, launches;
+  uint64_t param_floats, arena_bytes, macs;           /* macs: multiply-adds of one forward of n_frames frames */
+  uint32_t level_h[3], level_w[3];
+} mi355_yolox_net_plan;
+typedef struct mi355_yolox_net_op {
+  int32_t kind, k, stride, silu;                      /* k 1 / 3 (kind 0), stride 1 / 2 (kinds 0, 1) */
+  uint32_t n_frames, h_in, w_in, tile;                /* tile (dense conv): 0 as a forward chooses, 1 the 64 x 16 form, 4 the 64 x 64 form */
+  const float *in;
+  uint32_t in_c, in_off, in_ctot, out_c;
+  float *out;
+  uint32_t out_off, out_ctot, res_off, res_ctot;
+  const float *res;                                   /* null: no residual; out_c channels at the output's size */
+  const float *weight, *scale, *shift;                /* kinds 0, 1, 4: [out_c][in_c / groups][k][k], [out_c], [out_c] */
+} mi355_yolox_net_op;
+int mi355_yolox_net_create(mi355_ctx *ctx, const mi355_yolox_net_config *config, mi355_yolox_net **net_out);
+void mi355_yolox_net_destroy(mi355_yolox_net *net);
+int mi355_yolox_net_param_count(const mi355_yolox_net *net);
+int mi355_yolox_net_param_info(const mi355_yolox_net *net, int index, char *name, size_t name_cap, uint32_t dims[4], int *n_dims);
+int mi355_yolox_net_set_param(mi355_yolox_net *net, int index, const float *host, size_t n);
+int mi355_yolox_net_finalize(mi355_yolox_net *net);
+int mi355_yolox_net_forward_device(mi355_yolox_net *net, const float *d_in, size_t in_pitch_bytes, int n_frames, uint32_t H, uint32_t W,
+                                   mi355_yolox_level levels[3]);
+int mi355_yolox_net_launches(const mi355_yolox_net *net);
+int mi355_yolox_net_arena_info(const mi355_yolox_net *net, uint64_t *arena_bytes, uint64_t *allocations);
+int mi355_yolox_infer_frames_device(mi355_yolox_net *net, const uint8_t *d_frames, size_t frame_pitch, size_t stride, int n_frames,
+                                    uint32_t width, uint32_t height, float *d_out, size_t out_pitch_bytes);
+int mi355_yolox_infer_dets_device(mi355_yolox_net *net, const uint8_t *d_frames, size_t frame_pitch, size_t stride, int n_frames,
+                                  uint32_t width, uint32_t height, const mi355_yolo_params *p, mi355_yolo_det *dets, uint32_t max_dets,
+                                  uint32_t *n_dets);
+int mi355_selftest_yolox_net_plan(const mi355_yolox_net_config *config, int n_frames, uint32_t H, uint32_t W, mi355_yolox_net_plan *plan);
+int mi355_selftest_yolox_net_param_info(const mi355_yolox_net_config *config, int index, char *name, size_t name_cap, uint32_t dims[4],
+                                        int *n_dims);
+int mi355_selftest_yolox_net_op_device(mi355_ctx *ctx, const mi355_yolox_net_op *op);
+
 /* ---------------------------------------------------------------- handdetectiontensordec / handlandmarktensordec (csrc/handdec.hip)
  * Replaces the decode loops of the two hand decoders: extract_hands_from_palm_detection with is_valid_palm_candidate_normalized
  * and apply_nms_to_palm_candidates (analytics/analytics/src/hand/handdetectiontensordec/imp.rs:89-335), extract_hands with

@@ -23,11 +23,11 @@
 //                         the FIR stays for what does not (and can be pinned with MI355_FLAG_HRTF_METHOD).
 //   hrtf_mix_kernel     : channel-ordered sum into the interleaved stereo output (imp.rs:256-268 order)
 // HBM traffic per block is ~C*(frames+taps)*4 B in and frames*8 B out; the FIR is LDS-bound (1 LDS read per MAC).
+#include "audio_fft.hpp"
 #include "internal.hpp"
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -218,26 +218,7 @@ __global__ __launch_bounds__(256) void hrtf_fir_kernel(const float *__restrict__
 }
 
 // ---- overlap-save FFT form. grid (S, C); block 256; dynamic LDS: X[N], Z[N], twiddles[N/2] (float2)
-__device__ __forceinline__ float2 hrtf_cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ int hrtf_bitrev(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
-// in-place radix-2 decimation-in-time transform of buf[0..N) (input stored bit-reversed), all lanes of the block
-template <bool INVERSE>
-__device__ __forceinline__ void hrtf_fft_lds(float2 *buf, const float2 *tw, int N, int logN) {
-  for (int st = 1; st <= logN; st++) {
-    const int half = 1 << (st - 1);
-    __syncthreads();
-    for (int t = threadIdx.x; t < N / 2; t += 256) {
-      const int j = t & (half - 1), base = (t >> (st - 1)) << st;
-      float2 w = tw[j << (logN - st)];
-      if (INVERSE) w.y = -w.y;
-      const float2 a = buf[base + j], b = hrtf_cmul(buf[base + j + half], w);
-      buf[base + j] = make_float2(a.x + b.x, a.y + b.y);
-      buf[base + j + half] = make_float2(a.x - b.x, a.y - b.y);
-    }
-  }
-  __syncthreads();
-}
-
+// (cmul, bitrev and the transform in LDS are audio_fft.hpp's; its lanes stride by the block's 256 here)
 __device__ __forceinline__ void hrtf_fft_body(float2 *hsm, const float *__restrict__ x, const float *__restrict__ taps, const float *__restrict__ gain,
                                               float *__restrict__ partial, int S, int B, int L, int N, int logN, int s, int c) {
   float2 *X = hsm, *Z = hsm + N, *tw = hsm + 2 * N;
@@ -250,26 +231,26 @@ __device__ __forceinline__ void hrtf_fft_body(float2 *hsm, const float *__restri
     tw[i] = make_float2(cs, sn);
   }
   for (int i = threadIdx.x; i < N; i += 256) {
-    const int r = hrtf_bitrev(i, logN);
+    const int r = bitrev(i, logN);
     X[r] = make_float2(i < W ? xrow[i] : 0.0f, 0.0f);
     Z[r] = i < L ? make_float2(tp[i], tp[L + i]) : make_float2(0.0f, 0.0f);  // left ear in the real part, right ear in the imaginary
   }
-  hrtf_fft_lds<false>(X, tw, N, logN);
-  hrtf_fft_lds<false>(Z, tw, N, logN);
+  fft_lds<false, 256>(X, tw, N, logN);
+  fft_lds<false, 256>(Z, tw, N, logN);
   // Y = X Z back into X in bit-reversed order (every lane first reads its products, then all write)
   float2 y[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) {
     const int i = threadIdx.x + 256 * k;
-    if (i < N) y[k] = hrtf_cmul(X[i], Z[i]);
+    if (i < N) y[k] = cmul(X[i], Z[i]);
   }
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 16; k++) {
     const int i = threadIdx.x + 256 * k;
-    if (i < N) X[hrtf_bitrev(i, logN)] = y[k];
+    if (i < N) X[bitrev(i, logN)] = y[k];
   }
-  hrtf_fft_lds<true>(X, tw, N, logN);
+  fft_lds<true, 256>(X, tw, N, logN);
   const float g = gain[c * S + s] / (float)N;
   for (int i = threadIdx.x; i < B; i += 256) {  // overlap-save: window position pad + i holds output frame n0 + i
     const float2 v = X[pad + i];
@@ -358,14 +339,6 @@ __global__ __launch_bounds__(256) void hrtf_mix_jobs_kernel(const HrtfJobMember 
 
 // ------------------------------------------------------------------ host side
 
-static int hrtf_hip(hipError_t e, const char *what, std::string *err) {
-  if (e == hipSuccess) return MI355_OK;
-  (void)hipGetLastError();
-  *err = std::string(what) + ": " + hipGetErrorString(e);
-  return e == hipErrorOutOfMemory ? MI355_ERR_OUT_OF_MEMORY : MI355_ERR_HIP;
-}
-static int hrtf_fail(int status, const char *msg, std::string *err) { *err = msg; return status; }
-
 static void hrtf_free_processors(HrtfState *H) {
   for (int i = 0; i < 2; i++) { if (H->d_x[i]) (void)hipFree(H->d_x[i]); H->d_x[i] = nullptr; }
   float **fp[] = {&H->d_taps, &H->d_last_taps, &H->d_gain, &H->d_uvw, &H->d_partial, &H->d_in, &H->d_out};
@@ -426,12 +399,12 @@ static std::vector<float> resample_hrir(const float *h, uint32_t len, double rat
 
 // HrirSphere::new(bytes, device_rate) (imp.rs:84-94): parsed, resampled where the rates differ, uploaded. *out is a new sphere with one reference.
 static int hrtf_sphere_create(const unsigned char *bytes, size_t n, uint32_t device_rate, HrtfSphere **out, std::string *err) {
-  if (!bytes || n < 20 || std::memcmp(bytes, "HRIR", 4) != 0) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: not an HRIR sphere (bad magic)", err);
+  if (!bytes || n < 20 || std::memcmp(bytes, "HRIR", 4) != 0) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: not an HRIR sphere (bad magic)", err);
   const uint32_t rate = rd_u32(bytes + 4), file_len = rd_u32(bytes + 8), nv = rd_u32(bytes + 12), ni = rd_u32(bytes + 16);
-  if (file_len == 0) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: HRIR length is zero", err);
+  if (file_len == 0) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: HRIR length is zero", err);
   const size_t need = 20 + 4 * (size_t)ni + (size_t)nv * (12 + 8 * (size_t)file_len);
-  if (n < need) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: truncated HRIR sphere", err);
-  if (rate == 0 || device_rate == 0) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: zero sample rate", err);
+  if (n < need) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: truncated HRIR sphere", err);
+  if (rate == 0 || device_rate == 0) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: zero sample rate", err);
   const bool resample = rate != device_rate;
   const double ratio = (double)device_rate / (double)rate;
   uint32_t len = file_len;
@@ -442,7 +415,7 @@ static int hrtf_sphere_create(const unsigned char *bytes, size_t n, uint32_t dev
   std::vector<uint32_t> idx(ni);
   for (uint32_t i = 0; i < ni; i++) {
     idx[i] = rd_u32(bytes + 20 + 4 * (size_t)i);
-    if (idx[i] >= nv) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: face index out of range", err);
+    if (idx[i] >= nv) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: face index out of range", err);
   }
   std::vector<float> pos((size_t)nv * 3), hr((size_t)nv * 2 * len);
   size_t off = 20 + 4 * (size_t)ni;
@@ -463,12 +436,12 @@ static int hrtf_sphere_create(const unsigned char *bytes, size_t n, uint32_t dev
   }
   HrtfSphere *S = new HrtfSphere();
   int rc;
-  if ((rc = hrtf_hip(hipMalloc(&S->d_pos, pos.size() * 4 + 4), "hipMalloc(hrir positions)", err)) ||
-      (rc = hrtf_hip(hipMalloc(&S->d_idx, idx.size() * 4 + 4), "hipMalloc(hrir indices)", err)) ||
-      (rc = hrtf_hip(hipMalloc(&S->d_hrir, hr.size() * 4 + 4), "hipMalloc(hrir data)", err)) ||
-      (rc = hrtf_hip(hipMemcpy(S->d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice), "upload hrir positions", err)) ||
-      (!idx.empty() && (rc = hrtf_hip(hipMemcpy(S->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice), "upload hrir indices", err))) ||
-      (rc = hrtf_hip(hipMemcpy(S->d_hrir, hr.data(), hr.size() * 4, hipMemcpyHostToDevice), "upload hrir data", err))) {
+  if ((rc = audio_hip(hipMalloc(&S->d_pos, pos.size() * 4 + 4), "hipMalloc(hrir positions)", err)) ||
+      (rc = audio_hip(hipMalloc(&S->d_idx, idx.size() * 4 + 4), "hipMalloc(hrir indices)", err)) ||
+      (rc = audio_hip(hipMalloc(&S->d_hrir, hr.size() * 4 + 4), "hipMalloc(hrir data)", err)) ||
+      (rc = audio_hip(hipMemcpy(S->d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice), "upload hrir positions", err)) ||
+      (!idx.empty() && (rc = audio_hip(hipMemcpy(S->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice), "upload hrir indices", err))) ||
+      (rc = audio_hip(hipMemcpy(S->d_hrir, hr.data(), hr.size() * 4, hipMemcpyHostToDevice), "upload hrir data", err))) {
     hrtf_sphere_unref(S);
     return rc;
   }
@@ -494,10 +467,10 @@ int hrtf_load_sphere(mi355_ctx *ctx, const unsigned char *bytes, size_t n, uint3
 
 // HrtfProcessor::new per channel (imp.rs:662-680) for one instance: `method` is MI355_FLAG_HRTF_METHOD's value
 static int hrtf_state_setup(HrtfState *H, int method, int channels, int block_len, int steps, bool own_staging, std::string *err) {
-  if (!H || !H->sphere) return hrtf_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set", err);
+  if (!H || !H->sphere) return audio_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set", err);
   // (channels above 64: the element's caps stop there, and HrtfVecGain holds 64 channels' directions and gains)
-  if (channels < 1 || channels > 64 || block_len < 1 || steps < 1 || steps > 64) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: bad channels/block-length/interpolation-steps", err);
-  if ((size_t)block_len * (size_t)steps > (1u << 24)) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: block too large", err);
+  if (channels < 1 || channels > 64 || block_len < 1 || steps < 1 || steps > 64) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: bad channels/block-length/interpolation-steps", err);
+  if ((size_t)block_len * (size_t)steps > (1u << 24)) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: block too large", err);
   hrtf_free_processors(H);
   const size_t L = H->sphere->len, pad = L - 1, frames = (size_t)block_len * steps, C = (size_t)channels, S = (size_t)steps;
   const size_t T = block_len < 1024 ? (size_t)block_len : 1024;
@@ -506,7 +479,7 @@ static int hrtf_state_setup(HrtfState *H, int method, int channels, int block_le
   while ((size_t)fft_n < (size_t)block_len + pad) { fft_n <<= 1; fft_log++; }
   const bool fft_fits = fft_n <= 4096 && fft_n >= 512;
   const bool fir_fits = (T + pad + 2 * L) * 4 <= 160 * 1024;
-  if (!fft_fits && !fir_fits) return hrtf_fail(MI355_ERR_UNSUPPORTED, "hrtfrender: HRIR too long for the LDS (block + HRIR length above 4096 and FIR tile above 160 KB)", err);
+  if (!fft_fits && !fir_fits) return audio_fail(MI355_ERR_UNSUPPORTED, "hrtfrender: HRIR too long for the LDS (block + HRIR length above 4096 and FIR tile above 160 KB)", err);
   // method: 1 = FFT, 2 = FIR pinned; 0 = FFT from kHrtfFftMinTaps taps on, FIR below
   // measured, 64 sources, block 512 x 8 (ms per block, FFT / FIR): 64 taps 0.040 / 0.030, 256: 0.042 / 0.040, 512: 0.047 / 0.056,
   // 1024: 0.072 / 0.087, 2048: 0.128 / 0.156 (tools/bench_hrtf.py --method 1 / 2, r03)
@@ -514,17 +487,17 @@ static int hrtf_state_setup(HrtfState *H, int method, int channels, int block_le
   const bool use_fft = fft_fits && (method == 1 || !fir_fits || (method == 0 && L >= kHrtfFftMinTaps));
   int rc;
   for (int i = 0; i < 2; i++) {
-    if ((rc = hrtf_hip(hipMalloc(&H->d_x[i], C * (pad + frames) * 4 + 4), "hipMalloc(hrtf input rows)", err))) return rc;
-    if ((rc = hrtf_hip(hipMemset(H->d_x[i], 0, C * (pad + frames) * 4), "hipMemset(hrtf input rows)", err))) return rc;
+    if ((rc = audio_hip(hipMalloc(&H->d_x[i], C * (pad + frames) * 4 + 4), "hipMalloc(hrtf input rows)", err))) return rc;
+    if ((rc = audio_hip(hipMemset(H->d_x[i], 0, C * (pad + frames) * 4), "hipMemset(hrtf input rows)", err))) return rc;
   }
   struct { float **p; size_t n; } bufs[] = {{&H->d_taps, C * S * 2 * L}, {&H->d_last_taps, C * 2 * L}, {&H->d_gain, C * S}, {&H->d_uvw, C * S * 3},
                                             {&H->d_partial, C * frames * 2}, {&H->d_in, frames * C}, {&H->d_out, frames * 2}};
   for (auto &b : bufs) {
     if (!own_staging && (b.p == &H->d_in || b.p == &H->d_out)) continue;
-    if ((rc = hrtf_hip(hipMalloc(b.p, b.n * 4 + 4), "hipMalloc(hrtf state)", err))) return rc;
-    if ((rc = hrtf_hip(hipMemset(*b.p, 0, b.n * 4), "hipMemset(hrtf state)", err))) return rc;
+    if ((rc = audio_hip(hipMalloc(b.p, b.n * 4 + 4), "hipMalloc(hrtf state)", err))) return rc;
+    if ((rc = audio_hip(hipMemset(*b.p, 0, b.n * 4), "hipMemset(hrtf state)", err))) return rc;
   }
-  if ((rc = hrtf_hip(hipMalloc(&H->d_face, C * S * 4 + 4), "hipMalloc(hrtf faces)", err))) return rc;
+  if ((rc = audio_hip(hipMalloc(&H->d_face, C * S * 4 + 4), "hipMalloc(hrtf faces)", err))) return rc;
   H->channels = channels; H->steps = steps; H->block_len = block_len; H->cur = 0;
   H->fft_n = use_fft ? fft_n : 0; H->fft_log = use_fft ? fft_log : 0;
   H->prev_vec.assign(C * 3, 0.0f); H->prev_gain.assign(C, 0.0f); H->have_prev.assign(C, 0);
@@ -543,7 +516,7 @@ static int hrtf_state_reset(HrtfState *H, hipStream_t stream, std::string *err) 
   if (!H || !H->configured) return MI355_OK;
   const size_t row = (size_t)H->sphere->len - 1 + (size_t)H->block_len * H->steps;
   for (int i = 0; i < 2; i++) {
-    int rc = hrtf_hip(hipMemsetAsync(H->d_x[i], 0, (size_t)H->channels * row * 4, stream), "hipMemset(hrtf tails)", err);
+    int rc = audio_hip(hipMemsetAsync(H->d_x[i], 0, (size_t)H->channels * row * 4, stream), "hipMemset(hrtf tails)", err);
     if (rc) return rc;
   }
   return MI355_OK;
@@ -624,12 +597,12 @@ int hrtf_process_block_host(mi355_ctx *ctx, const float *in, float *out, const f
 }
 
 static int hrtf_state_last_lookup(HrtfState *H, hipStream_t stream, int *faces, float *uvw, std::string *err) {
-  if (!H || !H->configured) return hrtf_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)", err);
+  if (!H || !H->configured) return audio_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: not negotiated (setup not called)", err);
   const size_t n = (size_t)H->channels * H->steps;
-  int rc = hrtf_hip(hipStreamSynchronize(stream), "hrtf sync", err);
+  int rc = audio_hip(hipStreamSynchronize(stream), "hrtf sync", err);
   if (rc) return rc;
-  if (faces && (rc = hrtf_hip(hipMemcpy(faces, H->d_face, n * 4, hipMemcpyDeviceToHost), "hrtf faces D2H", err))) return rc;
-  if (uvw && (rc = hrtf_hip(hipMemcpy(uvw, H->d_uvw, n * 12, hipMemcpyDeviceToHost), "hrtf uvw D2H", err))) return rc;
+  if (faces && (rc = audio_hip(hipMemcpy(faces, H->d_face, n * 4, hipMemcpyDeviceToHost), "hrtf faces D2H", err))) return rc;
+  if (uvw && (rc = audio_hip(hipMemcpy(uvw, H->d_uvw, n * 12, hipMemcpyDeviceToHost), "hrtf uvw D2H", err))) return rc;
   return MI355_OK;
 }
 
@@ -677,7 +650,7 @@ static size_t hrtf_rows_offset(const HrtfGroup *G) { return (G->members.size() *
 HrtfGroup *hrtf_group_new(int n_members, std::string *err, int *status) {
   HrtfGroup *G = new HrtfGroup();
   G->members.resize((size_t)n_members);
-  *status = hrtf_hip(hipEventCreateWithFlags(&G->ev, hipEventDisableTiming), "hipEventCreate(hrtf group)", err);
+  *status = audio_hip(hipEventCreateWithFlags(&G->ev, hipEventDisableTiming), "hipEventCreate(hrtf group)", err);
   if (*status) { delete G; return nullptr; }
   return G;
 }
@@ -725,7 +698,7 @@ int hrtf_group_load_sphere(HrtfGroup *G, int m, const unsigned char *bytes, size
 }
 
 int hrtf_group_setup(HrtfGroup *G, int m, int channels, int block_len, int steps, int method, std::string *err) {
-  if (method < 0 || method > 2) return hrtf_fail(MI355_ERR_INVALID_ARG, "hrtfrender: method is 0 (by HRIR length), 1 (FFT) or 2 (FIR)", err);
+  if (method < 0 || method > 2) return audio_fail(MI355_ERR_INVALID_ARG, "hrtfrender: method is 0 (by HRIR length), 1 (FFT) or 2 (FIR)", err);
   return hrtf_state_setup(&G->members[(size_t)m], method, channels, block_len, steps, false, err);
 }
 
@@ -739,7 +712,7 @@ uint64_t hrtf_group_launches(const HrtfGroup *G) { return G->n_launches; }
 
 int hrtf_group_info(HrtfGroup *G, int m, uint32_t *hrir_len, int *fft_n, int *spheres_held, std::string *err) {
   const HrtfState &H = G->members[(size_t)m];
-  if (!H.sphere) return hrtf_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set", err);
+  if (!H.sphere) return audio_fail(MI355_ERR_NOT_CONFIGURED, "hrtfrender: impulse response not set", err);
   if (hrir_len) *hrir_len = H.sphere->len;
   if (fft_n) *fft_n = H.configured ? H.fft_n : -1;
   if (spheres_held) *spheres_held = (int)G->spheres.size();
@@ -751,16 +724,7 @@ int hrtf_group_last_lookup(HrtfGroup *G, int m, hipStream_t stream, int *faces, 
 }
 
 // the largest dynamic LDS a job kernel has been allowed so far (the attribute belongs to the function, not to a group)
-static std::mutex g_hrtf_attr_mu;
 static size_t g_hrtf_fir_lds = 0, g_hrtf_fft_lds = 0;
-
-static int hrtf_allow_lds(const void *fn, size_t *allowed, size_t lds, const char *what, std::string *err) {
-  std::lock_guard<std::mutex> lk(g_hrtf_attr_mu);
-  if (lds <= *allowed) return MI355_OK;
-  const int rc = hrtf_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), what, err);
-  if (!rc) *allowed = lds;
-  return rc;
-}
 
 // ONE launch set for the members in subs[0..n): tables up, prepare, at most one convolution launch per distinct transform size plus
 // one for the FIR rows, mix. Enqueued on `stream`; nothing is waited for but the pinned table block of the previous set.
@@ -771,18 +735,18 @@ int hrtf_group_run(HrtfGroup *G, hipStream_t stream, const HrtfSubmit *subs, int
   const size_t rows_off = hrtf_rows_offset(G);
   int rc;
   if (n_rows > G->row_cap) {
-    if ((rc = hrtf_hip(hipStreamSynchronize(stream), "hrtf group: sync", err))) return rc;
+    if ((rc = audio_hip(hipStreamSynchronize(stream), "hrtf group: sync", err))) return rc;
     if (G->h_tab) (void)hipHostFree(G->h_tab);
     if (G->d_tab) (void)hipFree(G->d_tab);
     G->h_tab = G->d_tab = nullptr; G->row_cap = 0;
     size_t cap = 64;
     while (cap < n_rows) cap *= 2;
     const size_t bytes = rows_off + cap * sizeof(HrtfJobRow);
-    if ((rc = hrtf_hip(hipHostMalloc((void **)&G->h_tab, bytes, hipHostMallocDefault), "hipHostMalloc(hrtf group tables)", err))) return rc;
-    if ((rc = hrtf_hip(hipMalloc((void **)&G->d_tab, bytes), "hipMalloc(hrtf group tables)", err))) return rc;
+    if ((rc = audio_hip(hipHostMalloc((void **)&G->h_tab, bytes, hipHostMallocDefault), "hipHostMalloc(hrtf group tables)", err))) return rc;
+    if ((rc = audio_hip(hipMalloc((void **)&G->d_tab, bytes), "hipMalloc(hrtf group tables)", err))) return rc;
     G->row_cap = cap;
   }
-  if ((rc = hrtf_hip(hipEventSynchronize(G->ev), "hipEventSynchronize(hrtf group tables)", err))) return rc;
+  if ((rc = audio_hip(hipEventSynchronize(G->ev), "hipEventSynchronize(hrtf group tables)", err))) return rc;
   HrtfJobMember *hm = (HrtfJobMember *)G->h_tab;
   HrtfJobRow *hr = (HrtfJobRow *)(G->h_tab + rows_off);
   size_t r = 0, fir_lds = 0;
@@ -819,25 +783,25 @@ int hrtf_group_run(HrtfGroup *G, hipStream_t stream, const HrtfSubmit *subs, int
   const HrtfJobMember *dm = (const HrtfJobMember *)G->d_tab;
   const HrtfJobRow *dr = (const HrtfJobRow *)(G->d_tab + rows_off);
   // (two copies, each of what this set fills: the member entries end where the rows' fixed offset begins only in a full group)
-  if ((rc = hrtf_hip(hipMemcpyAsync(G->d_tab, G->h_tab, (size_t)n * sizeof(HrtfJobMember), hipMemcpyHostToDevice, stream), "hrtf group: member table", err))) return rc;
-  if ((rc = hrtf_hip(hipMemcpyAsync(G->d_tab + rows_off, G->h_tab + rows_off, n_rows * sizeof(HrtfJobRow), hipMemcpyHostToDevice, stream), "hrtf group: row table", err))) return rc;
-  if ((rc = hrtf_hip(hipEventRecord(G->ev, stream), "hipEventRecord(hrtf group tables)", err))) return rc;
+  if ((rc = audio_hip(hipMemcpyAsync(G->d_tab, G->h_tab, (size_t)n * sizeof(HrtfJobMember), hipMemcpyHostToDevice, stream), "hrtf group: member table", err))) return rc;
+  if ((rc = audio_hip(hipMemcpyAsync(G->d_tab + rows_off, G->h_tab + rows_off, n_rows * sizeof(HrtfJobRow), hipMemcpyHostToDevice, stream), "hrtf group: row table", err))) return rc;
+  if ((rc = audio_hip(hipEventRecord(G->ev, stream), "hipEventRecord(hrtf group tables)", err))) return rc;
   hipLaunchKernelGGL(hrtf_prepare_jobs_kernel, dim3((unsigned)n_rows), dim3(256), 0, stream, dm, dr);
   G->n_launches++;
   for (int k = 0; k < n_fft; k++) {
     const size_t lds = (size_t)(2 * fft_sizes[k] + fft_sizes[k] / 2) * sizeof(float2);
-    if ((rc = hrtf_allow_lds((const void *)hrtf_fft_jobs_kernel, &g_hrtf_fft_lds, lds, "hipFuncSetAttribute(hrtf group fft LDS)", err))) return rc;
+    if ((rc = audio_allow_lds((const void *)hrtf_fft_jobs_kernel, &g_hrtf_fft_lds, lds, "hipFuncSetAttribute(hrtf group fft LDS)", err))) return rc;
     hipLaunchKernelGGL(hrtf_fft_jobs_kernel, dim3((unsigned)(n_rows * (size_t)fft_y[k])), dim3(256), lds, stream, dm, dr, fft_sizes[k], fft_y[k]);
     G->n_launches++;
   }
   if (fir_y) {
-    if ((rc = hrtf_allow_lds((const void *)hrtf_fir_jobs_kernel, &g_hrtf_fir_lds, fir_lds, "hipFuncSetAttribute(hrtf group fir LDS)", err))) return rc;
+    if ((rc = audio_allow_lds((const void *)hrtf_fir_jobs_kernel, &g_hrtf_fir_lds, fir_lds, "hipFuncSetAttribute(hrtf group fir LDS)", err))) return rc;
     hipLaunchKernelGGL(hrtf_fir_jobs_kernel, dim3((unsigned)(n_rows * (size_t)fir_y)), dim3(256), fir_lds, stream, dm, dr, fir_y);
     G->n_launches++;
   }
   hipLaunchKernelGGL(hrtf_mix_jobs_kernel, dim3((unsigned)mix_x, (unsigned)n), dim3(256), 0, stream, dm);
   G->n_launches++;
-  if ((rc = hrtf_hip(hipGetLastError(), "hrtf group kernel launch", err))) return rc;
+  if ((rc = audio_hip(hipGetLastError(), "hrtf group kernel launch", err))) return rc;
   for (int j = 0; j < n; j++) hrtf_advance(&G->members[(size_t)subs[j].member], subs[j].positions, subs[j].gains);
   return MI355_OK;
 }

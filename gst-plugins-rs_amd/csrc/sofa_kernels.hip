@@ -18,11 +18,11 @@
 // One workgroup per channel walks the B / P sub-blocks of a block: the 2P-point transforms run in LDS (radix-2, all lanes
 // of the workgroup on N/2 butterflies per stage, twiddles from an LDS table), the frequency-domain delay line (K spectra
 // per channel) lives in global memory (L2-resident: K * N * 8 B per channel), the two ears share X.
+#include "audio_fft.hpp"
 #include "internal.hpp"
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 namespace mi355 {
@@ -43,29 +43,7 @@ struct SofaState {
 };
 static SofaState *sofa_of(mi355_ctx *ctx) { return (SofaState *)ctx->sofa; }
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-// In-place radix-2 decimation-in-time FFT of buf[0..N) in LDS by all lanes of the workgroup. tw[k] = exp(-2 pi i k / N),
-// k < N/2. INVERSE: conjugated twiddles, no scaling. The caller has stored the input in bit-reversed order.
-template <bool INVERSE>
-__device__ __forceinline__ void fft_lds(float2 *buf, const float2 *tw, int N, int logN) {
-  for (int s = 1; s <= logN; s++) {
-    const int half = 1 << (s - 1);
-    __syncthreads();
-    for (int t = threadIdx.x; t < N / 2; t += blockDim.x) {
-      const int j = t & (half - 1), base = (t >> (s - 1)) << s;
-      float2 w = tw[j << (logN - s)];
-      if (INVERSE) w.y = -w.y;
-      const float2 a = buf[base + j], b = cmul(buf[base + j + half], w);
-      buf[base + j] = make_float2(a.x + b.x, a.y + b.y);
-      buf[base + j + half] = make_float2(a.x - b.x, a.y - b.y);
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ int bitrev(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
-
+// cmul, bitrev and the transform in LDS (fft_lds, its lanes striding by blockDim.x here) are audio_fft.hpp's.
 // The bodies below are shared by the lone kernels (one context, one instance) and the job-table kernels of a sofa agroup further
 // down: a member of a group computes what a lone context computes, bit for bit, because it runs the same statements.
 
@@ -79,7 +57,7 @@ __device__ __forceinline__ void sofa_filter_fft_body(float2 *sm, const float *__
     tw[i] = make_float2(c, s);
   }
   for (int i = threadIdx.x; i < N; i += blockDim.x) buf[bitrev(i, logN)] = make_float2(i < P ? taps[(size_t)ear * K * P + (size_t)k * P + i] : 0.0f, 0.0f);
-  fft_lds<false>(buf, tw, N, logN);
+  fft_lds<false, kLanesBlockDim>(buf, tw, N, logN);
   for (int i = threadIdx.x; i < N; i += blockDim.x) H[((size_t)ear * K + k) * N + i] = buf[i];
 }
 
@@ -107,7 +85,7 @@ __device__ __forceinline__ void sofa_convolve_body(float2 *sm, const float *__re
     }
     __syncthreads();
     for (int i = threadIdx.x; i < P; i += blockDim.x) pv[i] = in[(size_t)(j * P + i) * in_stride];
-    fft_lds<false>(X, tw, N, logN);
+    fft_lds<false, kLanesBlockDim>(X, tw, N, logN);
     for (int i = threadIdx.x; i < N; i += blockDim.x) F[(size_t)slot * N + i] = X[i];
     __syncthreads();
     // Y = sum_k X_{j-k} . H_k, partitions in ascending k (fixed order: deterministic)
@@ -122,8 +100,8 @@ __device__ __forceinline__ void sofa_convolve_body(float2 *sm, const float *__re
       Yl[bitrev(i, logN)] = al;
       Yr[bitrev(i, logN)] = ar;
     }
-    fft_lds<true>(Yl, tw, N, logN);
-    fft_lds<true>(Yr, tw, N, logN);
+    fft_lds<true, kLanesBlockDim>(Yl, tw, N, logN);
+    fft_lds<true, kLanesBlockDim>(Yr, tw, N, logN);
     for (int i = threadIdx.x; i < P; i += blockDim.x) {  // overlap-save: the last P samples are the valid ones
       out[(size_t)(j * P + i) * 2 + 0] = Yl[P + i].x * inv_n;
       out[(size_t)(j * P + i) * 2 + 1] = Yr[P + i].x * inv_n;
@@ -371,14 +349,6 @@ struct SofaGroup {
   uint64_t n_launches = 0;
 };
 
-static int sofa_hip(hipError_t e, const char *what, std::string *err) {
-  if (e == hipSuccess) return MI355_OK;
-  (void)hipGetLastError();
-  *err = std::string(what) + ": " + hipGetErrorString(e);
-  return e == hipErrorOutOfMemory ? MI355_ERR_OUT_OF_MEMORY : MI355_ERR_HIP;
-}
-static int sofa_fail(int status, const char *msg, std::string *err) { *err = msg; return status; }
-
 static size_t sofa_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 static size_t sofa_conv_offset(const SofaGroup *G) { return sofa_align16(G->members.size() * sizeof(SofaJobMember)); }
 static size_t sofa_filter_offset(const SofaGroup *G, size_t rows) { return sofa_conv_offset(G) + sofa_align16(rows * sizeof(SofaJobConv)); }
@@ -387,7 +357,7 @@ static size_t sofa_tab_bytes(const SofaGroup *G, size_t rows) { return sofa_filt
 SofaGroup *sofa_group_new(int n_members, std::string *err, int *status) {
   SofaGroup *G = new SofaGroup();
   G->members.resize((size_t)n_members);
-  *status = sofa_hip(hipEventCreateWithFlags(&G->ev, hipEventDisableTiming), "hipEventCreate(sofa group)", err);
+  *status = audio_hip(hipEventCreateWithFlags(&G->ev, hipEventDisableTiming), "hipEventCreate(sofa group)", err);
   if (*status) { delete G; return nullptr; }
   return G;
 }
@@ -413,15 +383,15 @@ void sofa_group_free(SofaGroup *G) {
 // will take part in need is allocated HERE, after the stream has drained (nothing in flight reads what is replaced): a launch set
 // allocates nothing.
 int sofa_group_setup(SofaGroup *G, int m, hipStream_t stream, int channels, int filter_len, int partition_len, int block_len, std::string *err) {
-  if (channels < 1 || channels > 64) return sofa_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad channel count", err);
-  if (filter_len < 1 || filter_len > (1 << 20)) return sofa_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad filter length", err);
+  if (channels < 1 || channels > 64) return audio_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad channel count", err);
+  if (filter_len < 1 || filter_len > (1 << 20)) return audio_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad filter length", err);
   if (partition_len < 1 || partition_len > 65535 || block_len < 1 || block_len > 65535)  // property ranges
-    return sofa_fail(MI355_ERR_INVALID_ARG, "sofalizer: partition / block length out of range", err);
-  if (block_len % partition_len != 0) return sofa_fail(MI355_ERR_INVALID_ARG, "Block Length is not multiple of Partition Length", err);  // :779-784
+    return audio_fail(MI355_ERR_INVALID_ARG, "sofalizer: partition / block length out of range", err);
+  if (block_len % partition_len != 0) return audio_fail(MI355_ERR_INVALID_ARG, "Block Length is not multiple of Partition Length", err);  // :779-784
   if ((partition_len & (partition_len - 1)) != 0 || partition_len < 8 || partition_len > 2048)
-    return sofa_fail(MI355_ERR_UNSUPPORTED, "sofalizer: partition length must be a power of two in 8..2048 (radix-2 transforms in LDS)", err);
+    return audio_fail(MI355_ERR_UNSUPPORTED, "sofalizer: partition length must be a power of two in 8..2048 (radix-2 transforms in LDS)", err);
   int rc;
-  if ((rc = sofa_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err))) return rc;
+  if ((rc = audio_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err))) return rc;
   SofaMember *M = &G->members[(size_t)m];
   sofa_member_free(M);
   M->channels = channels; M->filter_len = filter_len; M->P = partition_len; M->B = block_len;
@@ -432,8 +402,8 @@ int sofa_group_setup(SofaGroup *G, int m, hipStream_t stream, int channels, int 
   M->have_filter.assign((size_t)channels, 0);
   M->pending.assign((size_t)channels, std::vector<float>());
   const size_t C = (size_t)channels, K = (size_t)M->K, N = (size_t)M->N;
-#define MI355_SOFA_GALLOC(p, bytes, what) if ((rc = sofa_hip(hipMalloc((void **)&(p), (bytes)), what, err)) || \
-                                              (rc = sofa_hip(hipMemsetAsync((p), 0, (bytes), stream), what, err))) { sofa_member_free(M); return rc; }
+#define MI355_SOFA_GALLOC(p, bytes, what) if ((rc = audio_hip(hipMalloc((void **)&(p), (bytes)), what, err)) || \
+                                              (rc = audio_hip(hipMemsetAsync((p), 0, (bytes), stream), what, err))) { sofa_member_free(M); return rc; }
   MI355_SOFA_GALLOC(M->d_H, C * 2 * K * N * sizeof(float2), "hipMalloc(sofa group filter spectra)")
   MI355_SOFA_GALLOC(M->d_fdl, C * K * N * sizeof(float2), "hipMalloc(sofa group delay line)")
   MI355_SOFA_GALLOC(M->d_prev, C * (size_t)M->P * sizeof(float), "hipMalloc(sofa group history)")
@@ -450,11 +420,11 @@ int sofa_group_setup(SofaGroup *G, int m, hipStream_t stream, int channels, int 
     size_t cap = 64;
     while (cap < rows) cap *= 2;
     const size_t bytes = sofa_tab_bytes(G, cap);
-    if ((rc = sofa_hip(hipHostMalloc((void **)&G->h_tab, bytes, hipHostMallocDefault), "hipHostMalloc(sofa group tables)", err)) ||
-        (rc = sofa_hip(hipMalloc((void **)&G->d_tab, bytes), "hipMalloc(sofa group tables)", err))) { sofa_member_free(M); return rc; }
+    if ((rc = audio_hip(hipHostMalloc((void **)&G->h_tab, bytes, hipHostMallocDefault), "hipHostMalloc(sofa group tables)", err)) ||
+        (rc = audio_hip(hipMalloc((void **)&G->d_tab, bytes), "hipMalloc(sofa group tables)", err))) { sofa_member_free(M); return rc; }
     G->tab_rows = cap;
   }
-  if ((rc = sofa_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err))) { sofa_member_free(M); return rc; }
+  if ((rc = audio_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err))) { sofa_member_free(M); return rc; }
   M->configured = true;
   return MI355_OK;
 }
@@ -466,22 +436,22 @@ int sofa_group_setup(SofaGroup *G, int m, hipStream_t stream, int channels, int 
 int sofa_group_set_filter(SofaGroup *G, int m, hipStream_t stream, int channel, const float *left, const float *right, int delay_left, int delay_right,
                           std::string *err) {
   SofaMember *M = &G->members[(size_t)m];
-  if (!M->configured) return sofa_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
+  if (!M->configured) return audio_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
   if (channel < 0 || channel >= M->channels || !left || !right || delay_left < 0 || delay_right < 0)
-    return sofa_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad filter argument", err);
+    return audio_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad filter argument", err);
   const size_t KP = (size_t)M->K * M->P;
   size_t need = 0;
   for (const SofaMember &o : G->members) need += (size_t)o.n_pending * 2 * (size_t)o.K * (size_t)o.P;
   if (M->pending[(size_t)channel].empty()) need += 2 * KP;
   if (need > G->slab_floats) {
     int rc;
-    if ((rc = sofa_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err))) return rc;
+    if ((rc = audio_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err))) return rc;
     size_t cap = 4096;
     while (cap < need && cap < ((size_t)1 << 20)) cap *= 2;
     if (cap < need) cap = (need + 4095) & ~(size_t)4095;
     float *h = nullptr, *d = nullptr;
-    if ((rc = sofa_hip(hipHostMalloc((void **)&h, cap * sizeof(float), hipHostMallocDefault), "hipHostMalloc(sofa group taps)", err))) return rc;
-    if ((rc = sofa_hip(hipMalloc((void **)&d, cap * sizeof(float)), "hipMalloc(sofa group taps)", err))) { (void)hipHostFree(h); return rc; }
+    if ((rc = audio_hip(hipHostMalloc((void **)&h, cap * sizeof(float), hipHostMallocDefault), "hipHostMalloc(sofa group taps)", err))) return rc;
+    if ((rc = audio_hip(hipMalloc((void **)&d, cap * sizeof(float)), "hipMalloc(sofa group taps)", err))) { (void)hipHostFree(h); return rc; }
     if (G->h_slab) (void)hipHostFree(G->h_slab);
     if (G->d_slab) (void)hipFree(G->d_slab);
     G->h_slab = h; G->d_slab = d; G->slab_floats = cap;
@@ -499,23 +469,23 @@ int sofa_group_set_filter(SofaGroup *G, int m, hipStream_t stream, int channel, 
 
 int sofa_group_set_drop(SofaGroup *G, int m, hipStream_t stream, int channel, int drop, std::string *err) {
   SofaMember *M = &G->members[(size_t)m];
-  if (!M->configured) return sofa_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
-  if (channel < 0 || channel >= M->channels) return sofa_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad channel", err);
-  if (M->counter != 0) return sofa_fail(MI355_ERR_INVALID_ARG, "sofalizer: drop flags are fixed once a block has been processed (reset first)", err);
+  if (!M->configured) return audio_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
+  if (channel < 0 || channel >= M->channels) return audio_fail(MI355_ERR_INVALID_ARG, "sofalizer: bad channel", err);
+  if (M->counter != 0) return audio_fail(MI355_ERR_INVALID_ARG, "sofalizer: drop flags are fixed once a block has been processed (reset first)", err);
   M->drop[(size_t)channel] = drop ? 1 : 0;
-  int rc = sofa_hip(hipMemcpyAsync(M->d_drop, M->drop.data(), M->drop.size() * sizeof(int), hipMemcpyHostToDevice, stream), "hipMemcpyAsync(sofa group drop flags)", err);
+  int rc = audio_hip(hipMemcpyAsync(M->d_drop, M->drop.data(), M->drop.size() * sizeof(int), hipMemcpyHostToDevice, stream), "hipMemcpyAsync(sofa group drop flags)", err);
   if (rc) return rc;
-  return sofa_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err);   // (M->drop may change again at once)
+  return audio_hip(hipStreamSynchronize(stream), "sofa group: stream synchronize", err);   // (M->drop may change again at once)
 }
 
 // ChannelProcessor::reset of every channel (sofa/imp.rs:84-90, :123-127; flush-stop :846-853): the input history goes, the filters -
 // transformed and pending alike - stay. On the group's stream: after the member's last launch set, before its next.
 int sofa_group_reset(SofaGroup *G, int m, hipStream_t stream, std::string *err) {
   SofaMember *M = &G->members[(size_t)m];
-  if (!M->configured) return sofa_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
-  int rc = sofa_hip(hipMemsetAsync(M->d_fdl, 0, (size_t)M->channels * M->K * M->N * sizeof(float2), stream), "hipMemset(sofa group delay line)", err);
+  if (!M->configured) return audio_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
+  int rc = audio_hip(hipMemsetAsync(M->d_fdl, 0, (size_t)M->channels * M->K * M->N * sizeof(float2), stream), "hipMemset(sofa group delay line)", err);
   if (rc) return rc;
-  rc = sofa_hip(hipMemsetAsync(M->d_prev, 0, (size_t)M->channels * M->P * sizeof(float), stream), "hipMemset(sofa group history)", err);
+  rc = audio_hip(hipMemsetAsync(M->d_prev, 0, (size_t)M->channels * M->P * sizeof(float), stream), "hipMemset(sofa group history)", err);
   M->counter = 0;
   return rc;
 }
@@ -535,7 +505,7 @@ bool sofa_group_ready(const SofaGroup *G, int m) {
 
 int sofa_group_info(const SofaGroup *G, int m, int *partitions_K, int *fft_n, int *pending_filters, std::string *err) {
   const SofaMember &M = G->members[(size_t)m];
-  if (!M.configured) return sofa_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
+  if (!M.configured) return audio_fail(MI355_ERR_NOT_CONFIGURED, "sofalizer: not configured", err);
   if (partitions_K) *partitions_K = M.K;
   if (fft_n) *fft_n = M.N;
   if (pending_filters) *pending_filters = M.n_pending;
@@ -543,17 +513,7 @@ int sofa_group_info(const SofaGroup *G, int m, int *partitions_K, int *fft_n, in
 }
 
 // the largest dynamic LDS the job kernels have been allowed so far (the attribute belongs to the function, not to a group)
-static std::mutex g_sofa_attr_mu;
-static size_t g_sofa_conv_lds = 0, g_sofa_filter_lds = 0;
-
-static int sofa_allow_lds(const void *fn, size_t *allowed, size_t lds, const char *what, std::string *err) {
-  std::lock_guard<std::mutex> lk(g_sofa_attr_mu);
-  if (lds <= *allowed) return MI355_OK;
-  // partition 2048 needs 112 KiB, above the default limit: a refused request must not reach the launch
-  const int rc = sofa_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), what, err);
-  if (!rc) *allowed = lds;
-  return rc;
-}
+static size_t g_sofa_conv_lds = 0, g_sofa_filter_lds = 0;   // (partition 2048 needs 112 KiB, above the default limit)
 
 // ONE launch set for the members in subs[0..n): the pending filters of THESE members packed into the taps slab and uploaded once, the
 // table uploaded once, one filter-transform launch per distinct partition length among those filters, one convolution launch per
@@ -570,9 +530,9 @@ int sofa_group_run(SofaGroup *G, hipStream_t stream, const SofaSubmit *subs, int
     n_taps += (size_t)M.n_pending * 2 * (size_t)M.K * (size_t)M.P;
   }
   if (n_rows > G->tab_rows || n_filters > G->tab_rows || n_taps > G->slab_floats || (size_t)n > G->members.size())
-    return sofa_fail(MI355_ERR_INVALID_ARG, "sofa group: tables smaller than the launch set (internal)", err);
+    return audio_fail(MI355_ERR_INVALID_ARG, "sofa group: tables smaller than the launch set (internal)", err);
   int rc;
-  if ((rc = sofa_hip(hipEventSynchronize(G->ev), "hipEventSynchronize(sofa group tables)", err))) return rc;
+  if ((rc = audio_hip(hipEventSynchronize(G->ev), "hipEventSynchronize(sofa group tables)", err))) return rc;
   const size_t conv_off = sofa_conv_offset(G), filt_off = sofa_filter_offset(G, G->tab_rows);
   SofaJobMember *hm = (SofaJobMember *)G->h_tab;
   SofaJobConv *hc = (SofaJobConv *)(G->h_tab + conv_off);
@@ -621,17 +581,17 @@ int sofa_group_run(SofaGroup *G, hipStream_t stream, const SofaSubmit *subs, int
     }
   }
   conv_first[kClasses] = r; filt_first[kClasses] = f;
-  if (t && (rc = sofa_hip(hipMemcpyAsync(G->d_slab, G->h_slab, t * sizeof(float), hipMemcpyHostToDevice, stream), "sofa group: taps", err))) return rc;
+  if (t && (rc = audio_hip(hipMemcpyAsync(G->d_slab, G->h_slab, t * sizeof(float), hipMemcpyHostToDevice, stream), "sofa group: taps", err))) return rc;
   // (three copies at the most, each of what this set fills: the sections lie at fixed offsets)
-  if ((rc = sofa_hip(hipMemcpyAsync(G->d_tab, G->h_tab, (size_t)n * sizeof(SofaJobMember), hipMemcpyHostToDevice, stream), "sofa group: member table", err))) return rc;
-  if (r && (rc = sofa_hip(hipMemcpyAsync(G->d_tab + conv_off, G->h_tab + conv_off, r * sizeof(SofaJobConv), hipMemcpyHostToDevice, stream), "sofa group: row table", err))) return rc;
-  if (f && (rc = sofa_hip(hipMemcpyAsync(G->d_tab + filt_off, G->h_tab + filt_off, f * sizeof(SofaJobFilter), hipMemcpyHostToDevice, stream), "sofa group: filter table", err))) return rc;
-  if ((rc = sofa_hip(hipEventRecord(G->ev, stream), "hipEventRecord(sofa group tables)", err))) return rc;
+  if ((rc = audio_hip(hipMemcpyAsync(G->d_tab, G->h_tab, (size_t)n * sizeof(SofaJobMember), hipMemcpyHostToDevice, stream), "sofa group: member table", err))) return rc;
+  if (r && (rc = audio_hip(hipMemcpyAsync(G->d_tab + conv_off, G->h_tab + conv_off, r * sizeof(SofaJobConv), hipMemcpyHostToDevice, stream), "sofa group: row table", err))) return rc;
+  if (f && (rc = audio_hip(hipMemcpyAsync(G->d_tab + filt_off, G->h_tab + filt_off, f * sizeof(SofaJobFilter), hipMemcpyHostToDevice, stream), "sofa group: filter table", err))) return rc;
+  if ((rc = audio_hip(hipEventRecord(G->ev, stream), "hipEventRecord(sofa group tables)", err))) return rc;
   for (int k = 0; k < kClasses; k++) {
     const size_t cnt = filt_first[k + 1] - filt_first[k];
     if (!cnt) continue;
     const size_t N = (size_t)(16 << k), lds = (N + N / 2) * sizeof(float2);
-    if ((rc = sofa_allow_lds((const void *)sofa_filter_fft_jobs_kernel, &g_sofa_filter_lds, lds, "hipFuncSetAttribute(sofa group filter LDS)", err))) return rc;
+    if ((rc = audio_allow_lds((const void *)sofa_filter_fft_jobs_kernel, &g_sofa_filter_lds, lds, "hipFuncSetAttribute(sofa group filter LDS)", err))) return rc;
     hipLaunchKernelGGL(sofa_filter_fft_jobs_kernel, dim3((unsigned)(cnt * (size_t)filt_ky[k]), 2), dim3(256), lds, stream, df + filt_first[k], filt_ky[k]);
     G->n_launches++;
   }
@@ -639,13 +599,13 @@ int sofa_group_run(SofaGroup *G, hipStream_t stream, const SofaSubmit *subs, int
     const size_t cnt = conv_first[k + 1] - conv_first[k];
     if (!cnt) continue;
     const size_t N = (size_t)(16 << k), lds = (3 * N + N / 2) * sizeof(float2);
-    if ((rc = sofa_allow_lds((const void *)sofa_convolve_jobs_kernel, &g_sofa_conv_lds, lds, "hipFuncSetAttribute(sofa group convolve LDS)", err))) return rc;
+    if ((rc = audio_allow_lds((const void *)sofa_convolve_jobs_kernel, &g_sofa_conv_lds, lds, "hipFuncSetAttribute(sofa group convolve LDS)", err))) return rc;
     hipLaunchKernelGGL(sofa_convolve_jobs_kernel, dim3((unsigned)cnt), dim3(256), lds, stream, dc + conv_first[k]);
     G->n_launches++;
   }
   hipLaunchKernelGGL(sofa_mix_jobs_kernel, dim3((unsigned)mix_x, (unsigned)n), dim3(256), 0, stream, dm);
   G->n_launches++;
-  if ((rc = sofa_hip(hipGetLastError(), "sofa group kernel launch", err))) return rc;
+  if ((rc = audio_hip(hipGetLastError(), "sofa group kernel launch", err))) return rc;
   for (int j = 0; j < n; j++) {
     SofaMember &M = G->members[(size_t)subs[j].member];
     for (int c = 0; c < M.channels; c++)

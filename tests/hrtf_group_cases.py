@@ -77,6 +77,50 @@ def lone_context(mi355fx, synth, m, sphere=None):
     return ctx
 
 
+def extra_members():
+    """the members of the fixture's "extra" section (a reset after the first block; the device entry point), recorded later
+    than the rest (at the commit the section names): the smallest member once per method, and - its single tap leaves a reset
+    no tail to clear - one member per form whose tail a reset does clear"""
+    small = members()[3]
+    assert (small["len"], small["channels"]) == (1, 1)
+    fft = dict(small, method=1, transform=512, key="L1_C1_S8_B512_m1")
+    fir = dict(small, method=2, transform=0, key="L1_C1_S8_B512_m2")
+    return [fft, fir, members()[2], members()[7]]
+
+
+def lone_extra_crcs(mi355fx, synth, m):
+    """GUARD_BLOCKS blocks twice: through the host entry point with a reset after the first block, and through
+    hrtf_process_block_device on buffers the caller uploads and downloads itself"""
+    frames, C = m["steps"] * m["block"], m["channels"]
+    blocks = stream(m, GUARD_BLOCKS)
+    ctx = lone_context(mi355fx, synth, m)
+    try:
+        reset = []
+        for b, (x, p, g) in enumerate(blocks):
+            if b == 1:
+                ctx.hrtf_reset()
+            reset.append(crc(ctx.hrtf_process_block(x, p, g)))
+        n = ctx.hrtf_transform_size()
+    finally:
+        ctx.close()
+    ctx = lone_context(mi355fx, synth, m)
+    d_in, d_out = ctx.alloc(frames * C * 4), ctx.alloc(frames * 8)
+    try:
+        device = []
+        for (x, p, g) in blocks:
+            ctx.h2d(d_in, np.ascontiguousarray(x, np.float32))
+            ctx.hrtf_process_block_device(d_in, d_out, p, g)   # (returns without waiting; the copy below is on the same stream)
+            out = np.zeros(frames * 2, np.float32)
+            ctx.d2h(out, d_out)
+            device.append(crc(out))
+        faces, uvw = ctx.hrtf_last_lookup()
+        return {"transform": n, "reset": reset, "device": device, "faces": crc(faces.astype(np.int32)), "uvw": crc(uvw.astype(np.float32))}
+    finally:
+        ctx.free(d_in)
+        ctx.free(d_out)
+        ctx.close()
+
+
 def lone_crcs(mi355fx, synth, m):
     """CRC-32 of each of GUARD_BLOCKS output blocks of a lone context, and of the faces / weights of the last lookup"""
     ctx = lone_context(mi355fx, synth, m)

@@ -109,6 +109,66 @@ def lone_crcs(mi355fx, shape):
     return [crc(o) for o in lone_outputs(mi355fx, shape, schedule(shape))]
 
 
+# What the first guard does not reach, recorded later than the rest, at the commit the entry names (the "extra" section of
+# the fixture): a reset with a filter set behind it, two set_filter calls on one channel before the first block, and the device
+# entry point. n_blocks(shape) blocks each.
+EXTRA_SHAPES = [(2, 20, 8, 8), (2, 17, 16, 48), (6, 128, 64, 256)]
+
+
+def lone_reset_outputs(mi355fx, shape):
+    """schedule(shape) through the host entry point, with two additions: the first live channel's filter is set twice before the first
+    block (another pair first, the scheduled one last: only the last may count), and after the second block the context is reset
+    and that channel gets a third pair before the next block"""
+    sched = schedule(shape)
+    C, L, _, _ = shape
+    rng = np.random.default_rng(15485863 + 31 * C + L)
+    (la, ra), (lb, rb) = A.sofa_filters(rng, 2, L)
+    first = sched["filters"][0]
+    ctx = lone_context(mi355fx, shape, sched)
+    try:
+        ctx.sofa_set_filter(first[0], la, ra, 2, 3)
+        ctx.sofa_set_filter(*first)
+        outs = []
+        for b, (x, gains, changes) in enumerate(sched["blocks"]):
+            if b == 2:
+                ctx.sofa_reset()
+                ctx.sofa_set_filter(first[0], lb, rb, 1, 0)
+            for f in changes:
+                ctx.sofa_set_filter(*f)
+            outs.append(np.array(ctx.sofa_process_block(x, gains), np.float32).reshape(-1, 2).copy())
+        return outs
+    finally:
+        ctx.close()
+
+
+def lone_device_outputs(mi355fx, shape):
+    """schedule(shape) through sofa_process_block_device on buffers the caller uploads and downloads itself"""
+    sched = schedule(shape)
+    C, _, _, B = shape
+    ctx = lone_context(mi355fx, shape, sched)
+    d_in, d_out = ctx.alloc(B * C * 4), ctx.alloc(B * 8)
+    try:
+        outs = []
+        for (x, gains, changes) in sched["blocks"]:
+            for f in changes:
+                ctx.sofa_set_filter(*f)
+            ctx.h2d(d_in, np.ascontiguousarray(x, np.float32))
+            ctx.synchronize()
+            ctx.sofa_process_block_device(d_in, d_out, gains)   # (returns with d_out written)
+            out = np.zeros((B, 2), np.float32)
+            ctx.d2h(out, d_out)
+            outs.append(out)
+        return outs
+    finally:
+        ctx.free(d_in)
+        ctx.free(d_out)
+        ctx.close()
+
+
+def lone_extra_crcs(mi355fx, shape):
+    return {"reset": [crc(o) for o in lone_reset_outputs(mi355fx, shape)], "device": [crc(o) for o in lone_device_outputs(mi355fx, shape)]}
+
+
 def join(g, i, shape, sched):
     """member i of group g set up as lone_context sets a Context up"""
     g.sofa_setup(i, *shape)

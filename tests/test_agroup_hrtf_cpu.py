@@ -57,6 +57,28 @@ def test_guard_fixture_names_a_commit_and_covers_every_shape():
         assert len(e["out"]) == 3 and len(set(e["out"])) == 3
         for c in e["out"] + [e["faces"], e["uvw"]]:
             assert re.fullmatch(r"[0-9a-f]{8}", c)
+    # the "extra" section: a reset after the first block and the device entry point, recorded at a later commit than the rest
+    extra = doc["extra"]
+    assert re.fullmatch(r"[0-9a-f]{40}", extra["commit"]) and extra["commit"] != doc["commit"] and extra["blocks"] == H.GUARD_BLOCKS
+    ms = H.extra_members()
+    assert [m["key"] for m in ms] == ["L1_C1_S8_B512_m1", "L1_C1_S8_B512_m2", "L400_C2_S8_B512_m0", "L100_C3_S4_B77_m2"]
+    assert set(extra["shapes"]) == {m["key"] for m in ms}
+    smallest = min(H.members(), key=lambda m: (m["len"], m["channels"]))
+    for m in ms[:2]:                                                     # the smallest member, once per form
+        assert {k: m[k] for k in m if k not in ("key", "method", "transform")} == {k: smallest[k] for k in smallest if k not in ("key", "method", "transform")}
+    assert [(m["method"], m["transform"]) for m in ms[:2]] == [(1, 512), (2, 0)]
+    for m in ms:
+        e = extra["shapes"][m["key"]]
+        assert e["transform"] == m["transform"] == A.hrtf_expected_transform(m["len"], m["block"], m["method"])
+        for run in (e["reset"], e["device"]):
+            assert len(run) == H.GUARD_BLOCKS and len(set(run)) == len(run)
+        for c in e["reset"] + e["device"] + [e["faces"], e["uvw"]]:
+            assert re.fullmatch(r"[0-9a-f]{8}", c)
+        assert e["reset"][0] == e["device"][0] and e["reset"][2] == e["device"][2]   # a reset clears tails: heard in the block behind it alone
+        assert (e["reset"][1] != e["device"][1]) == (m["len"] > 1)                 # ... when the HRIR has a tail at all
+        if m["key"] in doc["shapes"]:
+            base = doc["shapes"][m["key"]]
+            assert e["device"] == base["out"] and (e["faces"], e["uvw"]) == (base["faces"], base["uvw"])
 
 
 def test_header_declares_the_new_names():

@@ -59,6 +59,20 @@ def test_guard_fixture_names_a_commit_and_covers_every_shape():
         assert len(e) == S.n_blocks(s) and len(set(e)) == len(e), s
         for c in e:
             assert re.fullmatch(r"[0-9a-f]{8}", c)
+    # the "extra" section: the reset / double set_filter run and the device entry point, recorded at a later commit than the rest
+    extra = doc["extra"]
+    assert re.fullmatch(r"[0-9a-f]{40}", extra["commit"]) and extra["commit"] != doc["commit"]
+    assert S.EXTRA_SHAPES == [(2, 20, 8, 8), (2, 17, 16, 48), (6, 128, 64, 256)] and set(S.EXTRA_SHAPES) <= set(shapes)
+    assert set(extra["shapes"]) == {S.key(s) for s in S.EXTRA_SHAPES}
+    for s in S.EXTRA_SHAPES:
+        e, base = extra["shapes"][S.key(s)], doc["shapes"][S.key(s)]
+        assert sorted(e) == ["device", "reset"], s
+        for run in e.values():
+            assert len(run) == S.n_blocks(s) >= 4 and len(set(run)) == len(run), s
+            assert all(re.fullmatch(r"[0-9a-f]{8}", c) for c in run)
+        assert e["device"] == base, s                                  # the device entry point computes what the host one does
+        assert e["reset"][:2] == base[:2], s                           # of two filters set before the first block only the last counts
+        assert not set(e["reset"][2:]) & set(base), s                  # ... and the reset and the filter behind it are heard
 
 
 def test_library_exports_the_new_names():

@@ -368,3 +368,47 @@ def test_lone_path_still_produces_the_parent_commits_bits(mi355lib, synth):
     assert doc["blocks"] == H.GUARD_BLOCKS
     for m in H.members():
         assert H.lone_crcs(mi355fx, synth, m) == doc["shapes"][m["key"]], m["key"]
+
+
+@pytest.mark.parametrize("m", H.extra_members(), ids=[m["key"] for m in H.extra_members()])
+def test_lone_reset_and_device_entry_still_produce_the_parent_commits_bits(mi355lib, synth, m):
+    """the fixture's "extra" section, recorded at the commit before audio_fft.hpp took over the two files' shared helpers: a reset after the first
+    of GUARD_BLOCKS blocks, and the device entry point"""
+    with open(H.CRC_FIXTURE) as f:
+        doc = json.load(f)
+    assert doc["extra"]["blocks"] == H.GUARD_BLOCKS
+    assert H.lone_extra_crcs(mi355fx, synth, m) == doc["extra"]["shapes"][m["key"]], m["key"]
+
+
+def test_lone_context_set_up_again_equals_a_fresh_one(mi355lib, synth):
+    first, second = SMALL, SMALL_FFT
+    sp = {m["key"]: H.sphere_bytes(synth, m) for m in (first, second)}
+    ctx = H.lone_context(mi355fx, synth, first, sp[first["key"]])
+    fresh = H.lone_context(mi355fx, synth, second, sp[second["key"]])
+    try:
+        for blk in H.stream(first, 2, seed=50):
+            ctx.hrtf_process_block(*blk)
+        # the same bytes again on the same context (a group shares spheres by content: here with itself), then another sphere and geometry
+        ctx.hrtf_load_sphere(sp[first["key"]], first["rate"])
+        assert ctx.hrtf_sphere_info()[0] == first["len"]
+        with pytest.raises(mi355fx.Mi355Error) as e:
+            ctx.hrtf_transform_size()                # a load takes the processors down: setup has to follow
+        assert e.value.status == mi355fx.ERR_NOT_CONFIGURED
+        ctx.hrtf_load_sphere(sp[second["key"]], second["rate"])
+        ctx.hrtf_load_sphere(sp[second["key"]], second["rate"])
+        ctx.hrtf_setup(second["channels"], second["block"], second["steps"])
+        assert ctx.hrtf_transform_size() == fresh.hrtf_transform_size() == second["transform"]
+        for b, blk in enumerate(H.stream(second, 3, seed=51)):
+            got, want = ctx.hrtf_process_block(*blk), fresh.hrtf_process_block(*blk)
+            assert got.any()
+            _same(got, want, b)
+        gf, gw = ctx.hrtf_last_lookup()
+        ff, fw = fresh.hrtf_last_lookup()
+        assert np.array_equal(gf, ff) and np.array_equal(gw, fw)
+        ctx.hrtf_teardown()
+        ctx.hrtf_teardown()                           # nothing left to trip over
+        ctx.hrtf_reset()                              # (a reset without processors is accepted and does nothing, as ever)
+    finally:
+        ctx.close()
+        ctx.close()
+        fresh.close()

@@ -352,3 +352,68 @@ def test_lone_path_unchanged(mi355lib, shape):
     with open(S.CRC_FIXTURE) as f:
         doc = json.load(f)
     assert S.lone_crcs(mi355fx, shape) == doc["shapes"][S.key(shape)], shape
+
+
+@pytest.mark.parametrize("shape", S.EXTRA_SHAPES, ids=[S.key(s) for s in S.EXTRA_SHAPES])
+def test_lone_reset_double_set_filter_and_device_entry_unchanged(mi355lib, shape):
+    """the fixture's "extra" section, recorded at the commit before audio_fft.hpp took over the two files' shared helpers: a reset after the second
+    block with a filter set behind it, two set_filter calls on one channel before the first block, and the device entry point"""
+    with open(S.CRC_FIXTURE) as f:
+        doc = json.load(f)
+    assert S.lone_extra_crcs(mi355fx, shape) == doc["extra"]["shapes"][S.key(shape)], shape
+
+
+# ---------------------------------------------------------------- 8: the life of a lone context
+
+def _lone_run(ctx, shape, seed, blocks):
+    """set `ctx` up as `shape` with seeded filters and run seeded blocks -> the outputs"""
+    C, L, P, B = shape
+    ctx.sofa_setup(*shape)
+    for c, (l, r) in enumerate(_filters(seed, shape)):
+        ctx.sofa_set_filter(c, l, r, c % 2, 1)
+    gains = np.linspace(0.3, 0.9, C).astype(np.float32)
+    return [ctx.sofa_process_block(_noise(seed + 1 + b, B, C), gains).copy() for b in range(blocks)]
+
+
+def test_lone_context_set_up_again_equals_a_fresh_one(mi355lib):
+    first, second = (2, 20, 8, 8), (1, 33, 16, 64)
+    ctx, fresh = mi355fx.Context(0), mi355fx.Context(0)
+    try:
+        _lone_run(ctx, first, 70, 2)
+        got = _lone_run(ctx, second, 80, 3)          # another geometry on the same context: nothing of the first may survive
+        want = _lone_run(fresh, second, 80, 3)
+        for b in range(3):
+            assert got[b].shape == (64, 2) and got[b].any()
+            S.same(got[b], want[b], b)
+        ctx.sofa_teardown()
+        assert "not configured" in _raises(mi355fx.ERR_NOT_CONFIGURED, ctx.sofa_reset)
+        ctx.sofa_teardown()                           # nothing left to trip over
+        S.same(_lone_run(ctx, second, 80, 1)[0], want[0])
+    finally:
+        ctx.close()
+        ctx.close()
+        fresh.close()
+
+
+def test_refused_lone_block_moves_no_state(mi355lib):
+    shape = (2, 17, 16, 48)
+    C, L, P, B = shape
+    flt = _filters(90, shape)
+    gains = np.array([0.8, 0.5], np.float32)
+    x = [_noise(91 + b, B, C) for b in range(2)]
+    ctx, never = mi355fx.Context(0), mi355fx.Context(0)
+    try:
+        for c in (ctx, never):
+            c.sofa_setup(*shape)
+            c.sofa_set_filter(0, *flt[0])
+        assert "no filter" in _raises(mi355fx.ERR_NOT_CONFIGURED, ctx.sofa_process_block, x[0], gains)   # channel 1 has none and is not dropped
+        assert "no filter" in _raises(mi355fx.ERR_NOT_CONFIGURED, ctx.sofa_process_block, x[1], gains)
+        ctx.sofa_set_drop(1, True)                    # the flags are still free: no block has run
+        ctx.sofa_set_drop(1, False)
+        for c in (ctx, never):
+            c.sofa_set_filter(1, *flt[1])
+        for b in range(2):
+            S.same(ctx.sofa_process_block(x[b], gains), never.sofa_process_block(x[b], gains), b)
+    finally:
+        ctx.close()
+        never.close()

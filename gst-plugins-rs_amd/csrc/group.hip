@@ -30,6 +30,9 @@
 //     layout, settings - as at most three launches over job tables and one download, yolodec.hip. The raw head maps of independent
 //     yoloxinference instances (submit_yolox_head) are members of the SAME queue: a YdTensor of the kind MI355_YOLO_X_HEAD with
 //     the submit's copy of its levels; they cost a set one upload of their level tables and two launches more, yolox_head.hip.
+//     RGB frames for a shared, finalized yoloxinference net (submit_yolox_infer) are members of the same queue too: a YdTensor of
+//     the kind MI355_YOLO_X_INFER. A set converts all of them in one launch and runs ONE forward per class (net, H, W) in an
+//     activation lane of the queue's own (yolox_net.hip: YxLanes); from the score launch on they are heads.
 //   * HnKind, hand tensors (submit_handdec_palm / _landmarks): tensors of independent handdetectiontensordec /
 //     handlandmarktensordec instances - own shape and settings - as at most two launches over job tables, no upload and one
 //     download, handdec.hip.
@@ -367,6 +370,14 @@ struct YdKind : OneLane<YdTensor> {
   // the heads among the members (mi355_group_yolox_head_stats): heads launched, sets that held one, table uploads, head kernel launches
   uint64_t n_heads = 0, n_head_sets = 0, n_head_uploads = 0, n_head_launches = 0;
   int last_head_counts[3] = {0, 0, 0};   // of the set `launch` has just sent out; counted by `launched`, i.e. once the set stands
+  // the infer members (mi355_group_yolox_infer_stats): frames, forwards (classes), frames of the largest forward, kernel launches of
+  // conversions and forwards; their lanes, made with the scratch and freed by destroy; the net (by serial) of every infer ticket
+  // that its wait has not taken yet (release_yolox_net refuses a net that one of them names)
+  uint64_t n_infer = 0, n_forwards = 0, n_largest_forward = 0, n_infer_launches = 0;
+  int last_infer_counts[4] = {0, 0, 0, 0};
+  YxLanes *net_lanes = nullptr;
+  int n_cu = 256;
+  std::unordered_map<uint64_t, uint64_t> infer_tickets;
 
   // flush, wait_all and destroy launch for this queue only once the scratch exists: a stream alone (the scratch could not be made)
   // has accepted nothing
@@ -377,6 +388,8 @@ struct YdKind : OneLane<YdTensor> {
     if (int rc = queue_stream(g, &stream, kName)) return rc;
     int st = MI355_OK;
     std::string err;
+    if (!net_lanes) net_lanes = yolox_lanes_new();
+    n_cu = device_cus(g->device);
     scratch = yolodec_set_scratch_new(&st, &err);
     return scratch ? MI355_OK : fail(g, st, "group: " + err);
   }
@@ -388,16 +401,20 @@ struct YdKind : OneLane<YdTensor> {
     return rc;
   }
   // a set without a candidate has nothing to copy: it takes no block (and still gets its event and its set)
-  size_t block_bytes(const Plan &p) const { return p.set.totals[2] ? yolodec_set_block_bytes(p.set.totals[5], p.set.totals[7]) : 0; }
+  size_t block_bytes(const Plan &p) const { return p.set.totals[2] ? yolodec_set_block_bytes(p.set.totals[5], p.set.totals[7], p.set.infer_totals[1]) : 0; }
   int launch(int, const Plan &p, size_t n, SetData *d, int *launches, std::string *err) {
     for (size_t i = 0; i < n; i++) d->slots.push_back(YdSlot{p.tensors[i].num_candidates, p.tensors[i].max_dets, p.set.det_off[i]});
-    return yolodec_launch_set(scratch, stream, p.tensors, (int)n, p.set, d->block.h, d->block.bytes, launches, last_head_counts, err);
+    return yolodec_launch_set(scratch, stream, p.tensors, (int)n, p.set, d->block.h, d->block.bytes, launches, last_head_counts, err, net_lanes, n_cu, last_infer_counts);
   }
   void launched(const GroupCore *, const Plan &, size_t) {
     n_heads += (uint64_t)last_head_counts[0];
     n_head_sets += last_head_counts[0] ? 1 : 0;
     n_head_uploads += (uint64_t)last_head_counts[1];
     n_head_launches += (uint64_t)last_head_counts[2];
+    n_infer += (uint64_t)last_infer_counts[0];
+    n_forwards += (uint64_t)last_infer_counts[1];
+    n_largest_forward = std::max(n_largest_forward, (uint64_t)last_infer_counts[2]);
+    n_infer_launches += (uint64_t)last_infer_counts[3];
   }
   // counts and records MOVE out of the pinned block: a later, larger set cannot overwrite what an earlier ticket has not collected
   void result(const SetData &d, size_t i, YdOut *o) const {
@@ -415,6 +432,7 @@ struct YdKind : OneLane<YdTensor> {
   static int status(const YdOut &o) { return o.status; }
   void destroy() {
     yolodec_set_scratch_free(scratch);
+    yolox_lanes_free(net_lanes);   // (the queue's stream has been waited for)
     (void)hipStreamDestroy(stream);
     blocks.destroy();
   }
@@ -1413,6 +1431,63 @@ int mi355_group_submit_yolox_head(mi355_group *g, mi355_ctx *ctx, const mi355_yo
   return g->yd.submit(g, ctx, YdTensor{nullptr, MI355_YOLO_X_HEAD, 5 + num_classes, A, max_dets, *p, std::move(head)}, true, ticket);
 }
 
+int mi355_group_submit_yolox_infer(mi355_group *g, mi355_ctx *ctx, mi355_yolox_net *net, const uint8_t *d_frame, size_t stride, uint32_t width, uint32_t height,
+                                   const mi355_yolo_params *p, uint32_t max_dets, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !net || !p || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context, net, settings or ticket");
+  // the lone call's checks for one frame, in its order; only what _finalize froze is read of the net
+  const char *why = nullptr;
+  if (const int rc = yolox_net_check_size(height, width, &why)) return fail(g, rc, why);
+  YxNetInfo info;
+  yolox_net_info(net, &info);
+  if (!info.finalized) return fail(g, MI355_ERR_NOT_CONFIGURED, "yolox_net: inference before finalize");
+  if (stride < (size_t)3 * width) return fail(g, MI355_ERR_INVALID_ARG, "yolox_input: stride below the row or frame pitch below the frame");
+  if (!d_frame) return fail(g, MI355_ERR_INVALID_ARG, "yolox_input: null frames, or null or misaligned output");
+  if (info.device != ctx->device) return fail(g, MI355_ERR_INVALID_ARG, "group: the net's context is on another device than the member's");
+  // ... and its last: the head's shape checks of the three levels (a frame of more than 65536 candidates is refused there)
+  mi355_yolox_level lv[3] = {};
+  for (int l = 0; l < 3; l++) lv[l].h = height >> (3 + l), lv[l].w = width >> (3 + l), lv[l].stride = 8u << l;
+  uint32_t A = 0;
+  if (const int rc = yolox_head_check_shape(lv, 3, 1, info.num_classes, &A, &why)) return fail(g, rc, why);
+  auto infer = std::make_shared<YdInfer>(YdInfer{net, info.serial, d_frame, stride, width, height});
+  const int rc = g->yd.submit(g, ctx, YdTensor{nullptr, MI355_YOLO_X_INFER, 5 + info.num_classes, A, max_dets, *p, nullptr, std::move(infer)}, true, ticket);
+  if (!rc) g->yd.kind.infer_tickets[*ticket] = info.serial;
+  return rc;
+}
+
+int mi355_group_release_yolox_net(mi355_group *g, const mi355_yolox_net *net) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!net) return fail(g, MI355_ERR_INVALID_ARG, "group: null net");
+  YxNetInfo info;
+  yolox_net_info(net, &info);
+  YdKind &k = g->yd.kind;
+  for (auto it = k.infer_tickets.begin(); it != k.infer_tickets.end();) {
+    if (!g->yd.owns(it->first)) { it = k.infer_tickets.erase(it); continue; }   // (a result nobody collected and the queue dropped)
+    if (it->second == info.serial) return fail(g, MI355_ERR_INVALID_ARG, "group: a ticket that names this net is pending or uncollected");
+    ++it;
+  }
+  if (!k.net_lanes) return MI355_OK;   // the queue has never been used
+  if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+  // every set that named the net has been collected, so it has finished; the wait is for what the stream may hold behind it
+  if (hipStreamSynchronize(k.stream) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipStreamSynchronize(decoder queue)"); }
+  (void)yolox_lanes_release(k.net_lanes, info.serial);
+  return MI355_OK;
+}
+
+int mi355_group_yolox_infer_stats(mi355_group *g, uint64_t stats[6]) {
+  if (!g || !stats) return MI355_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  const YdKind &k = g->yd.kind;
+  stats[0] = k.n_infer;
+  stats[1] = k.n_forwards;
+  stats[2] = k.n_largest_forward;
+  stats[3] = k.n_infer_launches;
+  yolox_lanes_stats(k.net_lanes, &stats[4], &stats[5]);
+  return MI355_OK;
+}
+
 int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *dets, uint32_t *n_dets) {
   if (!g) return MI355_ERR_INVALID_ARG;
   Locked L(g);
@@ -1426,7 +1501,9 @@ int mi355_group_wait_yolodec(mi355_group *g, uint64_t ticket, mi355_yolo_det *de
     if (cap) return fail(g, MI355_ERR_INVALID_ARG, "group: null records for a tensor submitted with max_dets > 0");
   }
   YdOut res;
-  if (int rc = g->yd.wait(g, L.lk, ticket, &res)) return rc;
+  const int rc = g->yd.wait(g, L.lk, ticket, &res);
+  if (!g->yd.owns(ticket)) g->yd.kind.infer_tickets.erase(ticket);   // taken, or told its failure: no longer names a net
+  if (rc) return rc;
   *n_dets = res.n_dets;
   if (dets && !res.dets.empty()) std::memcpy(dets, res.dets.data(), res.dets.size() * sizeof(mi355_yolo_det));
   return MI355_OK;

@@ -387,6 +387,26 @@ int mixer_launch(MixerTablesBuf *B, hipStream_t stream, const MixerCall *calls, 
 void mixer_release(mi355_ctx *ctx);
 void yolodec_release(mi355_ctx *ctx);
 void handdec_release(mi355_ctx *ctx);
+// yoloxinference's network as a member of the decoder queue (yolox_net.hip): what a submit reads of a net (frozen by _finalize, but
+// for `finalized` itself), the plan of a set's infer members (mi355_selftest_yolox_infer_set_plan; yolodec_plan_set plans the queue's
+// sets with it) and the queue's activation lanes, one per class key (net serial, H, W)
+struct YxNetInfo { uint64_t serial; int device; bool finalized; uint32_t num_classes; int launches; };
+void yolox_net_info(const mi355_yolox_net *net, YxNetInfo *out);
+int yolox_net_check_size(uint32_t H, uint32_t W, const char **why);
+int yolox_infer_set_plan(int n_jobs, const int *kind, const uint64_t *net_key, const uint32_t *height, const uint32_t *width, int32_t *class_of,
+                         uint32_t *frame_in_class, uint32_t *conv_first_block, uint32_t *conv_blocks, uint32_t *class_frames, uint64_t totals[3]);
+struct YxLanes;
+YxLanes *yolox_lanes_new();
+void yolox_lanes_free(YxLanes *S);   // frees every lane
+void yolox_lanes_stats(const YxLanes *S, uint64_t *alive, uint64_t *allocations);
+int yolox_lanes_release(YxLanes *S, uint64_t serial);   // frees the lanes of that net (hipFree waits for the device); how many
+// the lane of (net, H, W) planned for n_frames and grown to hold them (no allocation once it has seen the largest count): its input
+// tensor [n_frames][3][H][W] and frame 0's maps with the bytes from frame to frame
+int yolox_lanes_prepare(YxLanes *S, const mi355_yolox_net *net, uint32_t n_frames, uint32_t H, uint32_t W, float **d_input, mi355_yolox_level levels[3],
+                        std::string *err);
+// one forward of the lane as prepared, from its input tensor, on `stream`
+int yolox_lanes_forward(YxLanes *S, const mi355_yolox_net *net, uint32_t n_frames, uint32_t H, uint32_t W, hipStream_t stream, int n_cu, int *kernel_launches,
+                        std::string *err);
 // the checks of mi355_yolodec_tensors_device that need no device; *why names the refusal
 int yolodec_check_args(size_t tensor_pitch_bytes, int n_tensors, int layout, uint32_t num_fields, uint32_t num_candidates, const char **why);
 // launch sets of the video group's decoder queue (yolodec.hip): tensors of independent instances, job tables
@@ -396,7 +416,14 @@ constexpr size_t kYdCountsBytes = 128;  // a result block: kYdSetMax kept counts
 // MI355_YOLO_X_HEAD: head; data is null, num_fields = 5 + C, num_candidates = A, the sum of the levels' h * w).
 struct YdHead { mi355_yolox_level lv[MI355_YOLOX_LEVELS_MAX]; int n_levels; };   // the submit's copy of the level structs
 // (a tensor member carries no levels: its `head` is empty, and copying it through the queue costs what it did)
-struct YdTensor { const float *data; int layout; uint32_t num_fields, num_candidates, max_dets; mi355_yolo_params p; std::shared_ptr<const YdHead> head; };
+// An infer member (layout MI355_YOLO_X_INFER: infer; data and head are null, num_fields = 5 + C, num_candidates = A of the frame size)
+// is one RGB frame for a finalized net: the set converts it, runs it through one forward of its class (net, H, W) in a lane of the
+// queue's own, and from the score launch on it is a head of three levels in that lane's level buffers.
+struct YdInfer { const mi355_yolox_net *net; uint64_t serial; const uint8_t *frame; size_t stride; uint32_t width, height; };
+struct YdTensor {
+  const float *data; int layout; uint32_t num_fields, num_candidates, max_dets; mi355_yolo_params p; std::shared_ptr<const YdHead> head;
+  std::shared_ptr<const YdInfer> infer;
+};
 struct YdSetScratch;  // counters (zero between sets), keys, kept boxes and positions, results, the head members' tables, on the device
 // the shape checks of the YOLOX head entry points (yolox_head.hip): everything but the map pointers and pitches; *A_out: the candidates
 int yolox_head_check_shape(const mi355_yolox_level *lv, int n_levels, int n_tensors, uint32_t C, uint32_t *A_out, const char **why);
@@ -418,6 +445,10 @@ struct YdSetPlan {
   uint64_t key_off[kYdSetMax], box_off[kYdSetMax], det_off[kYdSetMax];
   uint32_t level_first_block[kYdSetMax * MI355_YOLOX_LEVELS_MAX];
   uint64_t totals[8];
+  // the infer members' side (yolox_infer_set_plan): classes, frames of a class, conversion blocks; infer_totals = {classes, frames, blocks}
+  int32_t class_of[kYdSetMax];
+  uint32_t frame_in_class[kYdSetMax], conv_first_block[kYdSetMax], conv_blocks[kYdSetMax], class_frames[kYdSetMax];
+  uint64_t infer_totals[3];
 };
 // the plan of n members (zeroed totals on a refusal): a head member without its levels, or with fewer than 0 or more than
 // MI355_YOLOX_LEVELS_MAX of them, is MI355_ERR_INVALID_ARG; the rest are yolodec_mixed_set_plan's refusals
@@ -426,13 +457,17 @@ YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err);
 void yolodec_set_scratch_free(YdSetScratch *S);
 size_t yolodec_set_result_bytes(uint64_t records);  // the counts and that many records (totals[5]): what a set's download writes
 // the pinned block of a set: its results, and behind them the tables of its head members (level_jobs = totals[7]; 0: none)
-size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs);
+// (infer_jobs = infer_totals[1]: the conversion jobs of the infer members ride behind the level jobs, in the same copy)
+size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs, uint64_t infer_jobs = 0);
 // n <= kYdSetMax members and their plan (yolodec_plan_set) on `stream`: the head tables' upload (only if the set holds a head), the
 // V8 score launch, the X score launch (each only if it has a job with a candidate), the head score launch, the tensors' NMS launch,
 // the heads' NMS launch, counts and records into h_block (nothing launched or copied if no member has a candidate). head_counts:
 // {heads, table uploads, head kernel launches} of this set.
+// A set with infer members takes the queue's lanes and the device's compute units: after the upload ONE conversion launch for all
+// infer members, then one forward per class, then the launches above. infer_counts: {frames, classes, frames of the largest class,
+// kernel launches of the conversion and the forwards} of this set.
 int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, const YdSetPlan &plan, void *h_block, size_t h_block_bytes,
-                       int *kernel_launches, int head_counts[3], std::string *err);
+                       int *kernel_launches, int head_counts[3], std::string *err, YxLanes *lanes = nullptr, int n_cu = 0, int infer_counts[4] = nullptr);
 // launch sets of the video group's hand-decoder queue (handdec.hip): palm and landmark tensors of independent instances, job tables
 constexpr int kHnSetMax = MI355_HANDDEC_SET_MAX;
 constexpr size_t kHnCountsBytes = 128;  // a result block: kHnSetMax counts (by job), n x MI355_HAND_MAX box records (by job), then

@@ -388,7 +388,8 @@ struct YdSetScratch {
   DeviceBuf<float4> d_kbox;
   DeviceBuf<uint32_t> d_ksrc;
   DeviceBuf<uint8_t> d_out;      // [kYdSetMax] counts (kYdCountsBytes), then the jobs' records at their det_offset
-  DeviceBuf<YhTable> d_table;    // the head members' tables of the set that runs; made with the first set that holds a head
+  DeviceBuf<uint8_t> d_table;    // the head members' tables (a YhTable) of the set that runs and, behind its level jobs, the infer members'
+                                 // conversion jobs: kYhUploadMax bytes, made with the first set that holds a head or an infer member
 };
 
 YdSetScratch *yolodec_set_scratch_new(int *status, std::string *err) {
@@ -413,42 +414,61 @@ size_t yolodec_set_result_bytes(uint64_t records) { return kYdCountsBytes + (siz
 // where the head tables stand in a set's pinned block: behind its results, which the download writes
 static size_t set_table_offset(uint64_t records) { return (yolodec_set_result_bytes(records) + 63) / 64 * 64; }
 
-size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs) {
-  return level_jobs ? set_table_offset(records) + yh_table_bytes(level_jobs) : yolodec_set_result_bytes(records);
+size_t yolodec_set_block_bytes(uint64_t records, uint64_t level_jobs, uint64_t infer_jobs) {
+  return level_jobs ? set_table_offset(records) + yh_upload_bytes(level_jobs, infer_jobs) : yolodec_set_result_bytes(records);
 }
 
 // the one place a set's members become the plan's arrays
 int yolodec_plan_set(const YdTensor *tensors, int n, YdSetPlan *out) {
   for (uint64_t &t : out->totals) t = 0;
   if (!tensors || n < 0 || n > kYdSetMax) return MI355_ERR_INVALID_ARG;
-  int kind[kYdSetMax], n_levels[kYdSetMax];
-  uint32_t F[kYdSetMax], cap[kYdSetMax], lv_h[kYhLevelJobsMax], lv_w[kYhLevelJobsMax];
+  for (uint64_t &t : out->infer_totals) t = 0;
+  int member[kYdSetMax], kind[kYdSetMax], n_levels[kYdSetMax];
+  uint32_t F[kYdSetMax], cap[kYdSetMax], lv_h[kYhLevelJobsMax], lv_w[kYhLevelJobsMax], in_h[kYdSetMax], in_w[kYdSetMax];
+  uint64_t net_key[kYdSetMax];
   size_t n_lv = 0;
   for (int i = 0; i < n; i++) {
     const YdTensor &t = tensors[i];
-    kind[i] = t.layout; F[i] = t.num_fields; out->candidates[i] = t.num_candidates; cap[i] = t.max_dets;
-    if (kind[i] == MI355_YOLO_X_HEAD && !t.head) return MI355_ERR_INVALID_ARG;
+    member[i] = t.layout; F[i] = t.num_fields; out->candidates[i] = t.num_candidates; cap[i] = t.max_dets;
+    net_key[i] = 0; in_h[i] = in_w[i] = 0;
+    if (member[i] == MI355_YOLO_X_HEAD && !t.head) return MI355_ERR_INVALID_ARG;
+    if (member[i] == MI355_YOLO_X_INFER) {
+      // the decode side of an infer member: a head of the three levels of its frame size
+      if (!t.infer) return MI355_ERR_INVALID_ARG;
+      net_key[i] = t.infer->serial; in_h[i] = t.infer->height; in_w[i] = t.infer->width;
+      kind[i] = MI355_YOLO_X_HEAD;
+      n_levels[i] = 3;
+      for (int l = 0; l < 3; l++, n_lv++) { lv_h[n_lv] = in_h[i] >> (3 + l); lv_w[n_lv] = in_w[i] >> (3 + l); }
+      continue;
+    }
+    kind[i] = member[i];
     n_levels[i] = kind[i] == MI355_YOLO_X_HEAD ? t.head->n_levels : 0;
     if (n_levels[i] < 0 || n_levels[i] > MI355_YOLOX_LEVELS_MAX) return MI355_ERR_INVALID_ARG;
     for (int l = 0; l < n_levels[i]; l++, n_lv++) { lv_h[n_lv] = t.head->lv[l].h; lv_w[n_lv] = t.head->lv[l].w; }
   }
+  if (const int rc = yolox_infer_set_plan(n, member, net_key, in_h, in_w, out->class_of, out->frame_in_class, out->conv_first_block, out->conv_blocks, out->class_frames,
+                                          out->infer_totals))
+    return rc;
   return yolodec_mixed_set_plan(n, kind, F, out->candidates, cap, n_levels, lv_h, lv_w, out->candidates, out->first_block, out->blocks, out->key_off, out->box_off,
                                 out->det_off, out->level_first_block, out->totals);
 }
 
 int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tensors, int n, const YdSetPlan &P, void *h_block, size_t h_block_bytes,
-                       int *kernel_launches, int head_counts[3], std::string *err) {
+                       int *kernel_launches, int head_counts[3], std::string *err, YxLanes *lanes, int n_cu, int infer_counts[4]) {
   *kernel_launches = 0;
   head_counts[0] = head_counts[1] = head_counts[2] = 0;
+  if (infer_counts) infer_counts[0] = infer_counts[1] = infer_counts[2] = infer_counts[3] = 0;
   if (!S || !tensors || n < 1 || n > kYdSetMax) { *err = "yolodec: bad launch set"; return MI355_ERR_INVALID_ARG; }
   const uint64_t *totals = P.totals;
   if (totals[2] == 0) return MI355_OK;   // no job has a candidate: nothing to launch, nothing to copy
-  const size_t bytes = yolodec_set_result_bytes(totals[5]), table_bytes = yh_table_bytes(totals[7]);
-  if (!h_block || h_block_bytes < yolodec_set_block_bytes(totals[5], totals[7])) { *err = "yolodec: the pinned block is too small for the set"; return MI355_ERR_INVALID_ARG; }
+  const uint32_t n_classes = (uint32_t)P.infer_totals[0], n_infer = (uint32_t)P.infer_totals[1];
+  if (n_infer && (!lanes || !infer_counts)) { *err = "yolodec: a set with infer members and no lanes"; return MI355_ERR_INVALID_ARG; }
+  const size_t bytes = yolodec_set_result_bytes(totals[5]), table_bytes = yh_upload_bytes(totals[7], n_infer);
+  if (!h_block || h_block_bytes < yolodec_set_block_bytes(totals[5], totals[7], n_infer)) { *err = "yolodec: the pinned block is too small for the set"; return MI355_ERR_INVALID_ARG; }
   // (growing frees first, which waits for the device: a set still running on the queue's stream has finished with the old allocation)
   if (S->d_keys.reserve((size_t)totals[3]) != hipSuccess || S->d_kbox.reserve((size_t)totals[4]) != hipSuccess ||
       S->d_ksrc.reserve((size_t)totals[4]) != hipSuccess || S->d_out.reserve(bytes) != hipSuccess ||
-      (table_bytes && S->d_table.reserve((size_t)1) != hipSuccess)) {
+      (table_bytes && S->d_table.reserve(kYhUploadMax) != hipSuccess)) {
     *err = "hipMalloc(yolodec set scratch)";
     return MI355_ERR_OUT_OF_MEMORY;
   }
@@ -458,15 +478,50 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
   }
   YdJobTable score[2] = {}, nms = {};
   YhTable *heads = table_bytes ? reinterpret_cast<YhTable *>(static_cast<uint8_t *>(h_block) + set_table_offset(totals[5])) : nullptr;
-  uint32_t n_heads = 0, n_level_jobs = 0;
+  const YhTable *d_heads = reinterpret_cast<const YhTable *>(S->d_table.p);
+  YxConvJob *conv = n_infer ? reinterpret_cast<YxConvJob *>(reinterpret_cast<uint8_t *>(heads) + yx_conv_offset(totals[7])) : nullptr;
+  const YxConvJob *d_conv = n_infer ? reinterpret_cast<const YxConvJob *>(S->d_table.p + yx_conv_offset(totals[7])) : nullptr;
+  // the lanes of the set's classes, before anything is enqueued: a lane that grows frees first, which waits for the device
+  const YdInfer *class_first[kYdSetMax] = {};
+  float *class_input[kYdSetMax] = {};
+  mi355_yolox_level class_lv[kYdSetMax][3];
+  for (int i = 0; i < n && n_infer; i++) {
+    const int c = P.class_of[i];
+    if (c < 0 || class_first[c]) continue;
+    class_first[c] = tensors[i].infer.get();
+    if (const int lrc = yolox_lanes_prepare(lanes, class_first[c]->net, P.class_frames[c], class_first[c]->height, class_first[c]->width, &class_input[c], class_lv[c], err))
+      return lrc;
+  }
+  uint32_t n_heads = 0, n_level_jobs = 0, n_conv = 0;
   uint32_t *d_n = reinterpret_cast<uint32_t *>(S->d_out.p);
   mi355_yolo_det *d_dets = reinterpret_cast<mi355_yolo_det *>(S->d_out.p + kYdCountsBytes);
   for (int i = 0; i < n; i++) {
     const YdTensor &t = tensors[i];
     const uint32_t N = P.candidates[i];
     if (!N) continue;   // no candidate: no job
-    if (t.layout == MI355_YOLO_X_HEAD) {
-      const int n_levels = t.head->n_levels;   // the plan stands: the head has its levels
+    if (t.layout == MI355_YOLO_X_HEAD || t.layout == MI355_YOLO_X_INFER) {
+      mi355_yolox_level own[3];
+      if (t.layout == MI355_YOLO_X_INFER) {
+        // its frame of its class's lane: the conversion writes the input tensor there, the forward the level buffers
+        const int c = P.class_of[i];
+        const uint32_t f = P.frame_in_class[i];
+        const YdInfer &I = *t.infer;
+        YxConvJob &K = conv[n_conv++];
+        K.src = I.frame;
+        K.dst = class_input[c] + (size_t)f * 3 * I.height * I.width;
+        K.stride = I.stride;
+        K.W = I.width;
+        K.H = I.height;
+        K.first_block = P.conv_first_block[i];
+        K.pad = 0;
+        for (int l = 0; l < 3; l++) {
+          own[l] = class_lv[c][l];
+          const size_t at = (size_t)f * (own[l].reg_pitch_bytes / 4);
+          own[l].reg += at, own[l].obj += at, own[l].cls += at;
+        }
+      }
+      const mi355_yolox_level *lv = t.layout == MI355_YOLO_X_INFER ? own : t.head->lv;
+      const int n_levels = t.layout == MI355_YOLO_X_INFER ? 3 : t.head->n_levels;   // the plan stands: the head has its levels
       YhHeadJob &H = heads->head[n_heads];
       H.count = S->d_count.p + i;
       H.keys = S->d_keys.p + P.key_off[i];
@@ -486,7 +541,7 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
       for (int l = 0; l < MI355_YOLOX_LEVELS_MAX; l++) {
         H.start[l] = a;   // A from n_levels on
         if (l >= n_levels) continue;
-        const mi355_yolox_level &v = t.head->lv[l];
+        const mi355_yolox_level &v = lv[l];
         YhLevelJob &L = heads->level[n_level_jobs];
         L.reg = v.reg;
         L.obj = v.obj;
@@ -530,6 +585,20 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
     if (e != hipSuccess) { *err = std::string("yolodec set head tables H2D: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
     head_counts[1] = 1;
   }
+  if (n_infer) {
+    // every infer member's frame in one launch, then one forward per class: the level buffers the head launches below read
+    int made = 0;
+    if (const int crc = yolox_input_launch_jobs(stream, d_conv, n_conv, (uint32_t)P.infer_totals[2], &made, err)) return crc;
+    for (uint32_t c = 0; c < n_classes; c++) {
+      if (const int frc = yolox_lanes_forward(lanes, class_first[c]->net, P.class_frames[c], class_first[c]->height, class_first[c]->width, stream, n_cu, &made, err))
+        return frc;
+      if ((int)P.class_frames[c] > infer_counts[2]) infer_counts[2] = (int)P.class_frames[c];
+    }
+    infer_counts[0] = (int)n_infer;
+    infer_counts[1] = (int)n_classes;
+    infer_counts[3] = made;
+    *kernel_launches += made;
+  }
   S->count_zero = false;   // true again only once the NMS launches have been enqueued behind the score launches
   for (int l = 0; l < 2; l++) {
     if (!score[l].n_jobs) continue;
@@ -548,7 +617,7 @@ int yolodec_launch_set(YdSetScratch *S, hipStream_t stream, const YdTensor *tens
   }
   if (n_heads) {
     // (a launch of their own: merged into the tensors' NMS kernel, the head loader's registers would be every tensor job's)
-    if (const int hrc = yolox_head_launch_jobs(stream, S->d_table.p, n_heads, n_level_jobs, (uint32_t)totals[6], &head_counts[2], err)) return hrc;
+    if (const int hrc = yolox_head_launch_jobs(stream, d_heads, n_heads, n_level_jobs, (uint32_t)totals[6], &head_counts[2], err)) return hrc;
     *kernel_launches += head_counts[2];
     head_counts[0] = (int)n_heads;
   }

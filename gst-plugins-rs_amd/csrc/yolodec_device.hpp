@@ -296,6 +296,26 @@ struct YhTable {
 };
 static_assert(sizeof(YhHeadJob) == 120 && sizeof(YhLevelJob) == 48, "the head tables have no padding holes");
 inline size_t yh_table_bytes(uint64_t level_jobs) { return level_jobs ? offsetof(YhTable, level) + (size_t)level_jobs * sizeof(YhLevelJob) : 0; }
+// A conversion job of the decoder queue's infer members (yolox_input_jobs_kernel): one RGB frame of a member - its own base pointer
+// and stride - into frame `frame_in_class` of its class's lane input tensor, [3][H][W] f32. The jobs of a set stand behind its level
+// jobs, in the same upload, in first_block order.
+struct YxConvJob {
+  const uint8_t *src;
+  float *dst;
+  unsigned long long stride;   // bytes from row to row of src
+  uint32_t W, H;               // multiples of 32
+  uint32_t first_block;        // its first block in the conversion launch; a block is 256 lanes of 4 pixels
+  uint32_t pad;
+};
+static_assert(sizeof(YxConvJob) == 40, "the conversion jobs have no padding holes");
+// where the conversion jobs stand in the uploaded bytes, and the bytes of the upload (0: the set has neither a head nor an infer member)
+inline size_t yx_conv_offset(uint64_t level_jobs) { return (yh_table_bytes(level_jobs ? level_jobs : 1) + 15) / 16 * 16; }
+inline size_t yh_upload_bytes(uint64_t level_jobs, uint64_t conv_jobs) {
+  return conv_jobs ? yx_conv_offset(level_jobs) + (size_t)conv_jobs * sizeof(YxConvJob) : yh_table_bytes(level_jobs);
+}
+constexpr size_t kYhUploadMax = (sizeof(YhTable) + 15) / 16 * 16 + (size_t)kYdSetMax * sizeof(YxConvJob);
+// the conversion launch over uploaded jobs: one flat grid of total_blocks
+int yolox_input_launch_jobs(hipStream_t stream, const YxConvJob *d_jobs, uint32_t n_jobs, uint32_t total_blocks, int *kernel_launches, std::string *err);
 // the two launches over uploaded tables: the score launch (grid = score_blocks, the level jobs' tiles), the NMS launch (a block per head)
 int yolox_head_launch_jobs(hipStream_t stream, const YhTable *d_table, uint32_t n_heads, uint32_t n_level_jobs, uint32_t score_blocks, int *kernel_launches,
                            std::string *err);

@@ -27,6 +27,8 @@
 //                             reads by whole waves, row pieces of 128 bytes out.
 //   yolox_input_kernel        RGB u8 -> [3][H][W] f32: one lane takes 4 pixels of a row (12 bytes as three dwords where the row
 //                             piece is aligned, as the 3-byte hsvfilter kernel does) and stores one float4 per plane.
+//   yolox_input_jobs_kernel   the job-table form of yolox_input_kernel for the decoder queue's infer members: one flat grid over the
+//                             frames of independent instances, each with its own pointer, stride, size and destination.
 //   yolox_head_score_jobs_kernel, yolox_head_nms_jobs_kernel
 //                             the job-table forms for the video group's decoder queue (group.hip; the set is laid out and launched
 //                             by yolodec_launch_set): heads of independent instances in two launches per set. A tile is 256
@@ -363,6 +365,49 @@ __global__ __launch_bounds__(256) void yolox_input_kernel(const uint8_t *__restr
   }
 }
 
+// The job-table form of yolox_input_kernel for the decoder queue's infer members: one flat grid over the conversion blocks of all
+// jobs, a block 256 lanes of 4 pixels of ONE job. The job is the last one whose first block is at or before this block: a binary
+// search on blockIdx.x alone, block-uniform, as yolox_head_score_jobs_kernel finds its level job. W is a multiple of 32, so a group
+// of 4 pixels never meets a row's end and every store is one aligned float4 (the lane's input tensor is an allocation's start plus
+// whole frames); the byte path stays: a member's base pointer and stride are its own.
+__global__ __launch_bounds__(256) void yolox_input_jobs_kernel(const YxConvJob *__restrict__ jobs, uint32_t n_jobs, uint32_t total_blocks) {
+  if (blockIdx.x >= total_blocks) return;   // a grid larger than the plan's total
+  uint32_t lo = 0, hi = n_jobs;   // jobs[lo].first_block <= blockIdx.x throughout: jobs[0].first_block is 0
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (jobs[mid].first_block <= blockIdx.x) lo = mid;
+    else hi = mid;
+  }
+  const YxConvJob *__restrict__ J = jobs + lo;
+  const uint32_t W = J->W, Hh = J->H, groups_per_row = W >> 2;
+  const uint32_t g = (blockIdx.x - J->first_block) * 256 + (uint32_t)threadIdx.x;
+  if (g >= groups_per_row * Hh) return;   // <= 2048 * 512 groups; the last block's tail, and the blocks of a job with more blocks than its frame has
+  const uint32_t y = g / groups_per_row, x0 = (g - y * groups_per_row) * 4;
+  const uint8_t *__restrict__ src = J->src + (size_t)y * J->stride + (size_t)3 * x0;
+  uint32_t d0 = 0, d1 = 0, d2 = 0;   // the 12 bytes of the group, little-endian
+  if (((uintptr_t)src & 3) == 0) {
+    const uint32_t *__restrict__ s4 = reinterpret_cast<const uint32_t *>(src);
+    d0 = s4[0];
+    d1 = s4[1];
+    d2 = s4[2];
+  } else {
+#pragma unroll
+    for (uint32_t b = 0; b < 12; b++) {
+      const uint32_t v = (uint32_t)src[b] << (8 * (b & 3));
+      if (b < 4) d0 |= v;
+      else if (b < 8) d1 |= v;
+      else d2 |= v;
+    }
+  }
+  const uint32_t p[4] = {d0, (d0 >> 24) | (d1 << 8), (d1 >> 16) | (d2 << 16), d2 >> 8};   // pixel j: c0 | c1 << 8 | c2 << 16
+  const size_t plane = (size_t)W * Hh;
+  float *__restrict__ dst = J->dst + (size_t)y * W + x0;
+#pragma unroll
+  for (int c = 0; c < 3; c++)
+    *reinterpret_cast<float4 *>(dst + (size_t)c * plane) = make_float4((float)((p[0] >> (8 * c)) & 0xffu), (float)((p[1] >> (8 * c)) & 0xffu),
+                                                                        (float)((p[2] >> (8 * c)) & 0xffu), (float)((p[3] >> (8 * c)) & 0xffu));
+}
+
 }  // namespace
 
 // the checks of the level shapes (every entry point, the group's submit and its set plan): everything but the map pointers and
@@ -479,6 +524,19 @@ int yolox_head_launch_jobs(hipStream_t stream, const YhTable *d_table, uint32_t 
   hipLaunchKernelGGL(yolox_head_nms_jobs_kernel, dim3(n_heads), dim3(kNmsThreads), 0, stream, d_table, n_heads);
   e = hipGetLastError();
   if (e != hipSuccess) { *err = std::string("yolox_head nms jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+  (*kernel_launches)++;
+  return MI355_OK;
+}
+
+// the infer members of a decoder launch set (yolodec_launch_set): the jobs are on the device behind what `stream` holds
+int yolox_input_launch_jobs(hipStream_t stream, const YxConvJob *d_jobs, uint32_t n_jobs, uint32_t total_blocks, int *kernel_launches, std::string *err) {
+  if (!d_jobs || n_jobs < 1 || n_jobs > (uint32_t)kYdSetMax || total_blocks < n_jobs || (uintptr_t)d_jobs % 8 != 0) {
+    *err = "yolox_input: bad conversion jobs";
+    return MI355_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(yolox_input_jobs_kernel, dim3(total_blocks), dim3(256), 0, stream, d_jobs, n_jobs, total_blocks);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { *err = std::string("yolox_input jobs kernel launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
   (*kernel_launches)++;
   return MI355_OK;
 }

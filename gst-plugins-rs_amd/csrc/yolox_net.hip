@@ -22,11 +22,15 @@
 //   yolox_dw_kernel             depthwise 3 x 3 (groups = C), one lane per output value.
 //   yolox_pool5_kernel          max-pool 5 x 5, stride 1, pad 2 with -inf; SPP's 9 and 13 are the cascade 5∘5 and 5∘5∘5 (max is exact).
 //   yolox_up2_kernel            nearest 2x: out[y][x] = in[y / 2][x / 2], written into the concat destination.
+// A forward is split from the state it plans into (YxLane: arena, input tensor, cached plan, allocation count): the entry points run
+// the net's own lane on its context's stream; the video group's decoder queue runs lanes of its own, one per (net serial, H, W), on
+// its stream (YxLanes; mi355_group_submit_yolox_infer), reading nothing of the net but what _finalize froze.
 // Epilogue of the convolutions: acc * scale + shift per channel (BatchNorm; a prediction layer has scale 1, shift bias), optional SiLU
 // x * (1 / (1 + exp(-x))), optional residual added AFTER the activation (bottleneck.rs:20-30).
 #include "internal.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <map>
@@ -613,14 +617,11 @@ hipError_t launch_op(hipStream_t stream, int kind, const ConvArgs &A, uint32_t k
 
 using namespace mi355;
 
-struct mi355_yolox_net {
-  mi355_ctx *ctx = nullptr;
-  NetDef def;
-  std::vector<char> is_set;
-  std::vector<float> host_small;          // the host copy of every 1-d parameter (BatchNorm, biases), at host_off
-  std::vector<size_t> host_off;
-  bool finalized = false;
-  float *d_params = nullptr, *d_ss = nullptr;   // the parameter store; scale [channels] then shift [channels]
+// What a forward plans into and writes: the arena of the activations, the input tensor of the compositions, the plan of the last
+// shape. A net has one of its own (the lone entry points, on its context's stream); the video group's decoder queue keeps its own,
+// one per (net, H, W), and runs them on the queue's stream (YxLanes below) - a forward touches nothing of the net but what
+// _finalize froze.
+struct YxLane {
   float *d_arena = nullptr, *d_input = nullptr;
   size_t arena_floats = 0, input_floats = 0;
   uint64_t allocations = 0;
@@ -628,6 +629,24 @@ struct mi355_yolox_net {
   uint32_t plan_n = 0, plan_h = 0, plan_w = 0;
   std::vector<size_t> offset;
   size_t plan_floats = 0;
+  void release() {
+    for (float *p : {d_arena, d_input})
+      if (p) (void)hipFree(p);   // waits for the device: a forward still running has finished with them
+    d_arena = d_input = nullptr;
+    arena_floats = input_floats = 0;
+  }
+};
+
+struct mi355_yolox_net {
+  mi355_ctx *ctx = nullptr;
+  uint64_t serial = 0;                    // given at create, never again: what the queue's lanes are keyed on (an address comes back)
+  NetDef def;
+  std::vector<char> is_set;
+  std::vector<float> host_small;          // the host copy of every 1-d parameter (BatchNorm, biases), at host_off
+  std::vector<size_t> host_off;
+  bool finalized = false;
+  float *d_params = nullptr, *d_ss = nullptr;   // the parameter store; scale [channels] then shift [channels]
+  YxLane lane;                            // the lone entry points'
 };
 
 static int param_info_of(const NetDef &N, int index, char *name, size_t name_cap, uint32_t dims[4], int *n_dims) {
@@ -643,14 +662,222 @@ static int param_info_of(const NetDef &N, int index, char *name, size_t name_cap
 }
 
 // the view's first channel in frame 0 and the floats from frame to frame
-static float *view_ptr(const mi355_yolox_net *net, const View &v, uint32_t H, uint32_t W, unsigned long long *pitch) {
-  const BufDef &b = net->def.bufs[v.buf];
+static float *view_ptr(const NetDef &N, const YxLane &lane, const View &v, uint32_t H, uint32_t W, unsigned long long *pitch) {
+  const BufDef &b = N.bufs[v.buf];
   const size_t hw = (size_t)(H / b.ds) * (W / b.ds);
   *pitch = (unsigned long long)b.C * hw;
-  return net->d_arena + net->offset[v.buf] + (size_t)v.off * hw;
+  return lane.d_arena + lane.offset[v.buf] + (size_t)v.off * hw;
 }
 
+// ---- a forward, split from the state it plans into: (net, lane, stream, n_cu). Shapes are checked by the callers.
+
+// the lane's plan for (n, H, W), and an arena that holds it: grows to the largest shape seen (hipFree waits for the device)
+static hipError_t lane_plan(const NetDef &N, YxLane *lane, uint32_t n, uint32_t H, uint32_t W) {
+  if (lane->plan_n != n || lane->plan_h != H || lane->plan_w != W) {
+    plan_arena(N, n, H, W, &lane->offset, &lane->plan_floats);
+    lane->plan_n = n, lane->plan_h = H, lane->plan_w = W;
+  }
+  if (lane->plan_floats > lane->arena_floats) {
+    if (lane->d_arena) (void)hipFree(lane->d_arena);
+    lane->d_arena = nullptr;
+    lane->arena_floats = 0;
+    if (const hipError_t e = hipMalloc((void **)&lane->d_arena, lane->plan_floats * 4)) return e;
+    lane->arena_floats = lane->plan_floats;
+    lane->allocations++;
+  }
+  return hipSuccess;
+}
+
+// the lane's input tensor, for `want` floats
+static hipError_t lane_input(YxLane *lane, size_t want) {
+  if (want <= lane->input_floats) return hipSuccess;
+  if (lane->d_input) (void)hipFree(lane->d_input);
+  lane->d_input = nullptr;
+  lane->input_floats = 0;
+  if (const hipError_t e = hipMalloc((void **)&lane->d_input, want * 4)) return e;
+  lane->input_floats = want;
+  lane->allocations++;
+  return hipSuccess;
+}
+
+// the launches of one forward of the planned lane: d_in [n][3][H][W] at in_pitch floats from frame to frame
+static hipError_t lane_run(const mi355_yolox_net *net, const YxLane &lane, hipStream_t stream, uint32_t n_cu, const float *d_in, unsigned long long in_pitch, uint32_t n,
+                           uint32_t H, uint32_t W) {
+  const NetDef &N = net->def;
+  for (const OpDef &op : N.ops) {
+    ConvArgs A{};
+    const BufDef &bi = N.bufs[op.in.buf], &bo = N.bufs[op.out.buf];
+    A.hi = H / bi.ds, A.wi = W / bi.ds, A.ho = H / bo.ds, A.wo = W / bo.ds;
+    if (op.in.buf == 0) {
+      A.in = d_in;
+      A.in_pitch = in_pitch;
+    } else {
+      A.in = view_ptr(N, lane, op.in, H, W, &A.in_pitch);
+    }
+    A.out = view_ptr(N, lane, op.out, H, W, &A.out_pitch);
+    if (op.has_res) A.res = view_ptr(N, lane, op.res, H, W, &A.res_pitch);
+    A.cin = op.in.C, A.cout = op.out.C;
+    uint32_t k = 0;
+    if (op.conv >= 0) {
+      const ConvDef &c = N.convs[op.conv];
+      A.w = net->d_params + N.params[c.w].off;
+      A.scale = net->d_ss + c.ss;
+      A.shift = net->d_ss + N.ss_channels + c.ss;
+      A.stride = c.stride, A.silu = op.silu ? 1 : 0;
+      A.cin = c.cin;
+      k = c.k;
+    }
+    if (op.kind == kOpFocus) A.hi = A.ho, A.wi = A.wo;   // the gathered [12][H / 2][W / 2] input
+    if (const hipError_t e = launch_op(stream, op.kind, A, k, n, n_cu)) return e;
+  }
+  return hipSuccess;
+}
+
+// frame 0's maps of the planned lane, and the bytes from frame to frame
+static void lane_levels(const NetDef &N, const YxLane &lane, uint32_t H, uint32_t W, mi355_yolox_level levels[3]) {
+  for (int l = 0; l < 3; l++) {
+    unsigned long long pitch = 0;
+    const View all{N.level_buf[l], 0, 5 + N.cfg.num_classes};
+    float *p = view_ptr(N, lane, all, H, W, &pitch);
+    const size_t hw = (size_t)(H >> (3 + l)) * (W >> (3 + l));
+    mi355_yolox_level &lv = levels[l];
+    lv.reg = p, lv.obj = p + 4 * hw, lv.cls = p + 5 * hw;
+    lv.reg_pitch_bytes = lv.obj_pitch_bytes = lv.cls_pitch_bytes = (size_t)pitch * 4;
+    lv.h = H >> (3 + l), lv.w = W >> (3 + l), lv.stride = 8u << l, lv.reserved = 0;
+  }
+}
+
+// ---- the net as a member of the video group's decoder queue (group.hip, yolodec.hip): what the queue reads of a net,
+// the plan of a set's infer members, and the queue's own lanes
+namespace mi355 {
+
+void yolox_net_info(const mi355_yolox_net *net, YxNetInfo *out) {
+  out->serial = net->serial;
+  out->device = net->ctx->device;
+  out->finalized = net->finalized;
+  out->num_classes = net->def.cfg.num_classes;
+  out->launches = (int)net->def.ops.size();
+}
+
+int yolox_net_check_size(uint32_t H, uint32_t W, const char **why) { return check_size(H, W, why); }
+
+// the one place a set's infer members become classes, frames of a class and conversion blocks
+int yolox_infer_set_plan(int n_jobs, const int *kind, const uint64_t *net_key, const uint32_t *height, const uint32_t *width, int32_t *class_of,
+                         uint32_t *frame_in_class, uint32_t *conv_first_block, uint32_t *conv_blocks, uint32_t *class_frames, uint64_t totals[3]) {
+  if (n_jobs < 0 || n_jobs > kYdSetMax || !totals) return MI355_ERR_INVALID_ARG;
+  if (n_jobs > 0 && (!kind || !net_key || !height || !width || !class_of || !frame_in_class || !conv_first_block || !conv_blocks || !class_frames))
+    return MI355_ERR_INVALID_ARG;
+  for (int j = 0; j < n_jobs; j++) {
+    if (kind[j] < MI355_YOLO_V8 || kind[j] > MI355_YOLO_X_INFER) return MI355_ERR_INVALID_ARG;
+    const char *why = nullptr;
+    if (kind[j] == MI355_YOLO_X_INFER)
+      if (const int rc = check_size(height[j], width[j], &why)) return rc;
+  }
+  int first_of[kYdSetMax];   // the first job of each class
+  uint32_t classes = 0, frames = 0, blocks = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    conv_first_block[j] = blocks;
+    if (kind[j] != MI355_YOLO_X_INFER) {
+      class_of[j] = -1;
+      frame_in_class[j] = 0;
+      conv_blocks[j] = 0;
+      continue;
+    }
+    uint32_t c = 0;
+    while (c < classes && !(net_key[first_of[c]] == net_key[j] && height[first_of[c]] == height[j] && width[first_of[c]] == width[j])) c++;
+    if (c == classes) {
+      first_of[classes++] = j;
+      class_frames[c] = 0;
+    }
+    class_of[j] = (int32_t)c;
+    frame_in_class[j] = class_frames[c]++;
+    conv_blocks[j] = (uint32_t)(((uint64_t)(width[j] / 4) * height[j] + 255) / 256);   // one lane takes 4 pixels; <= 4096 blocks a frame
+    blocks += conv_blocks[j];
+    frames++;
+  }
+  totals[0] = classes, totals[1] = frames, totals[2] = blocks;
+  return MI355_OK;
+}
+
+// The queue's lanes: one per class key (net serial, H, W), never per net - the head launches of a set run after ALL of its forwards,
+// so two classes of one net in a set would overwrite each other's level buffers in a shared lane.
+struct YxLaneKey {
+  uint64_t serial;
+  uint32_t H, W;
+  bool operator<(const YxLaneKey &o) const { return serial != o.serial ? serial < o.serial : H != o.H ? H < o.H : W < o.W; }
+};
+struct YxLanes {
+  std::map<YxLaneKey, YxLane> lanes;
+  uint64_t allocations = 0;   // made for lanes since the store exists, released lanes' included
+};
+
+YxLanes *yolox_lanes_new() { return new YxLanes(); }
+
+void yolox_lanes_free(YxLanes *S) {
+  if (!S) return;
+  for (auto &kv : S->lanes) kv.second.release();
+  delete S;
+}
+
+void yolox_lanes_stats(const YxLanes *S, uint64_t *alive, uint64_t *allocations) {
+  *alive = S ? (uint64_t)S->lanes.size() : 0;
+  *allocations = S ? S->allocations : 0;
+}
+
+int yolox_lanes_release(YxLanes *S, uint64_t serial) {
+  int n = 0;
+  for (auto it = S->lanes.begin(); it != S->lanes.end();) {
+    if (it->first.serial != serial) { ++it; continue; }
+    it->second.release();
+    it = S->lanes.erase(it);
+    n++;
+  }
+  return n;
+}
+
+int yolox_lanes_prepare(YxLanes *S, const mi355_yolox_net *net, uint32_t n_frames, uint32_t H, uint32_t W, float **d_input, mi355_yolox_level levels[3],
+                        std::string *err) {
+  const char *why = nullptr;
+  int rc = MI355_OK;
+  if (!S || !net || !net->finalized) { *err = "yolox_net: no lanes, or a net that is not finalized"; return MI355_ERR_INVALID_ARG; }
+  if ((rc = check_frames((int)n_frames, &why)) || (rc = check_size(H, W, &why))) { *err = why; return rc; }
+  YxLane &lane = S->lanes[YxLaneKey{net->serial, H, W}];
+  const uint64_t before = lane.allocations;
+  hipError_t e = lane_input(&lane, (size_t)3 * H * W * n_frames);
+  if (e == hipSuccess) e = lane_plan(net->def, &lane, n_frames, H, W);
+  S->allocations += lane.allocations - before;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *err = "hipMalloc(yolox_net lane)";
+    return MI355_ERR_OUT_OF_MEMORY;
+  }
+  *d_input = lane.d_input;
+  lane_levels(net->def, lane, H, W, levels);
+  return MI355_OK;
+}
+
+int yolox_lanes_forward(YxLanes *S, const mi355_yolox_net *net, uint32_t n_frames, uint32_t H, uint32_t W, hipStream_t stream, int n_cu, int *kernel_launches,
+                        std::string *err) {
+  auto it = S->lanes.find(YxLaneKey{net->serial, H, W});
+  if (it == S->lanes.end() || it->second.plan_n != n_frames || it->second.plan_h != H || it->second.plan_w != W) {
+    *err = "yolox_net: a forward of a lane that is not prepared for it";
+    return MI355_ERR_INVALID_ARG;
+  }
+  const YxLane &lane = it->second;
+  const hipError_t e = lane_run(net, lane, stream, (uint32_t)n_cu, lane.d_input, (unsigned long long)3 * H * W, n_frames, H, W);
+  if (e != hipSuccess) { *err = std::string("yolox_net lane launch: ") + hipGetErrorString(e); return MI355_ERR_HIP; }
+  *kernel_launches += (int)net->def.ops.size();
+  return MI355_OK;
+}
+
+}  // namespace mi355
+
 extern "C" {
+
+int mi355_selftest_yolox_infer_set_plan(int n_jobs, const int *kind, const uint64_t *net_key, const uint32_t *height, const uint32_t *width, int32_t *class_of,
+                                        uint32_t *frame_in_class, uint32_t *conv_first_block, uint32_t *conv_blocks, uint32_t *class_frames, uint64_t totals[3]) {
+  return yolox_infer_set_plan(n_jobs, kind, net_key, height, width, class_of, frame_in_class, conv_first_block, conv_blocks, class_frames, totals);
+}
 
 int mi355_yolox_net_create(mi355_ctx *ctx, const mi355_yolox_net_config *config, mi355_yolox_net **net_out) {
   if (!ctx) return MI355_ERR_INVALID_ARG;
@@ -661,6 +888,8 @@ int mi355_yolox_net_create(mi355_ctx *ctx, const mi355_yolox_net_config *config,
   if (rc) return set_error(ctx, rc, why);
   std::unique_ptr<mi355_yolox_net> net(new mi355_yolox_net);
   net->ctx = ctx;
+  static std::atomic<uint64_t> next_serial{1};
+  net->serial = next_serial.fetch_add(1);
   if (!build_def(*config, &net->def)) return set_error(ctx, MI355_ERR_UNSUPPORTED, "yolox_net: the config's channel counts do not fit the model");
   const NetDef &N = net->def;
   net->is_set.assign(N.params.size(), 0);
@@ -685,8 +914,9 @@ int mi355_yolox_net_create(mi355_ctx *ctx, const mi355_yolox_net_config *config,
 void mi355_yolox_net_destroy(mi355_yolox_net *net) {
   if (!net) return;
   if (net->ctx) (void)hipSetDevice(net->ctx->device);
-  for (float *p : {net->d_params, net->d_ss, net->d_arena, net->d_input})
+  for (float *p : {net->d_params, net->d_ss})
     if (p) (void)hipFree(p);   // waits for the device: a forward still running has finished with them
+  net->lane.release();
   delete net;
 }
 
@@ -755,56 +985,10 @@ int mi355_yolox_net_forward_device(mi355_yolox_net *net, const float *d_in, size
   if (in_pitch_bytes % 4 != 0 || (n_frames > 1 && in_pitch_bytes < (size_t)3 * H * W * 4))
     return set_error(ctx, MI355_ERR_INVALID_ARG, "yolox_net: input pitch is smaller than the tensor or no multiple of 4");
   if ((rc = check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice"))) return rc;
-  const NetDef &N = net->def;
   const uint32_t n = (uint32_t)n_frames;
-  if (net->plan_n != n || net->plan_h != H || net->plan_w != W) {
-    plan_arena(N, n, H, W, &net->offset, &net->plan_floats);
-    net->plan_n = n, net->plan_h = H, net->plan_w = W;
-  }
-  if (net->plan_floats > net->arena_floats) {   // grows to the largest shape seen (hipFree waits for the device)
-    if (net->d_arena) (void)hipFree(net->d_arena);
-    net->d_arena = nullptr;
-    net->arena_floats = 0;
-    if ((rc = check_hip(ctx, hipMalloc((void **)&net->d_arena, net->plan_floats * 4), "hipMalloc(yolox_net arena)"))) return rc;
-    net->arena_floats = net->plan_floats;
-    net->allocations++;
-  }
-  for (const OpDef &op : N.ops) {
-    ConvArgs A{};
-    const BufDef &bi = N.bufs[op.in.buf], &bo = N.bufs[op.out.buf];
-    A.hi = H / bi.ds, A.wi = W / bi.ds, A.ho = H / bo.ds, A.wo = W / bo.ds;
-    if (op.in.buf == 0) {
-      A.in = d_in;
-      A.in_pitch = in_pitch_bytes / 4;
-    } else {
-      A.in = view_ptr(net, op.in, H, W, &A.in_pitch);
-    }
-    A.out = view_ptr(net, op.out, H, W, &A.out_pitch);
-    if (op.has_res) A.res = view_ptr(net, op.res, H, W, &A.res_pitch);
-    A.cin = op.in.C, A.cout = op.out.C;
-    uint32_t k = 0;
-    if (op.conv >= 0) {
-      const ConvDef &c = N.convs[op.conv];
-      A.w = net->d_params + N.params[c.w].off;
-      A.scale = net->d_ss + c.ss;
-      A.shift = net->d_ss + N.ss_channels + c.ss;
-      A.stride = c.stride, A.silu = op.silu ? 1 : 0;
-      A.cin = c.cin;
-      k = c.k;
-    }
-    if (op.kind == kOpFocus) A.hi = A.ho, A.wi = A.wo;   // the gathered [12][H / 2][W / 2] input
-    if ((rc = check_hip(ctx, launch_op(ctx->stream, op.kind, A, k, n, (uint32_t)ctx->n_cu), "yolox_net launch"))) return rc;
-  }
-  for (int l = 0; l < 3; l++) {
-    unsigned long long pitch = 0;
-    const View all{N.level_buf[l], 0, 5 + N.cfg.num_classes};
-    float *p = view_ptr(net, all, H, W, &pitch);
-    const size_t hw = (size_t)(H >> (3 + l)) * (W >> (3 + l));
-    mi355_yolox_level &lv = levels[l];
-    lv.reg = p, lv.obj = p + 4 * hw, lv.cls = p + 5 * hw;
-    lv.reg_pitch_bytes = lv.obj_pitch_bytes = lv.cls_pitch_bytes = (size_t)pitch * 4;
-    lv.h = H >> (3 + l), lv.w = W >> (3 + l), lv.stride = 8u << l, lv.reserved = 0;
-  }
+  if ((rc = check_hip(ctx, lane_plan(net->def, &net->lane, n, H, W), "hipMalloc(yolox_net arena)"))) return rc;
+  if ((rc = check_hip(ctx, lane_run(net, net->lane, ctx->stream, (uint32_t)ctx->n_cu, d_in, in_pitch_bytes / 4, n, H, W), "yolox_net launch"))) return rc;
+  lane_levels(net->def, net->lane, H, W, levels);
   return MI355_OK;
 }
 
@@ -812,8 +996,8 @@ int mi355_yolox_net_launches(const mi355_yolox_net *net) { return net ? (int)net
 
 int mi355_yolox_net_arena_info(const mi355_yolox_net *net, uint64_t *arena_bytes, uint64_t *allocations) {
   if (!net) return MI355_ERR_INVALID_ARG;
-  if (arena_bytes) *arena_bytes = (uint64_t)net->arena_floats * 4;
-  if (allocations) *allocations = net->allocations;
+  if (arena_bytes) *arena_bytes = (uint64_t)net->lane.arena_floats * 4;
+  if (allocations) *allocations = net->lane.allocations;
   return MI355_OK;
 }
 
@@ -827,16 +1011,9 @@ static int infer_levels(mi355_yolox_net *net, const uint8_t *d_frames, size_t fr
   if (!net->finalized) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "yolox_net: inference before finalize");
   if ((rc = check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice"))) return rc;
   const size_t frame_floats = (size_t)3 * width * height, want = frame_floats * (size_t)n_frames;
-  if (want > net->input_floats) {
-    if (net->d_input) (void)hipFree(net->d_input);
-    net->d_input = nullptr;
-    net->input_floats = 0;
-    if ((rc = check_hip(ctx, hipMalloc((void **)&net->d_input, want * 4), "hipMalloc(yolox_net input)"))) return rc;
-    net->input_floats = want;
-    net->allocations++;
-  }
-  if ((rc = mi355_yolox_input_frames_device(ctx, d_frames, frame_pitch, stride, n_frames, width, height, net->d_input, frame_floats * 4))) return rc;
-  return mi355_yolox_net_forward_device(net, net->d_input, frame_floats * 4, n_frames, height, width, levels);
+  if ((rc = check_hip(ctx, lane_input(&net->lane, want), "hipMalloc(yolox_net input)"))) return rc;
+  if ((rc = mi355_yolox_input_frames_device(ctx, d_frames, frame_pitch, stride, n_frames, width, height, net->lane.d_input, frame_floats * 4))) return rc;
+  return mi355_yolox_net_forward_device(net, net->lane.d_input, frame_floats * 4, n_frames, height, width, levels);
 }
 
 int mi355_yolox_infer_frames_device(mi355_yolox_net *net, const uint8_t *d_frames, size_t frame_pitch, size_t stride, int n_frames, uint32_t width,

@@ -113,6 +113,7 @@ class YoloParams(C.Structure):
 
 
 YOLO_LAYOUT = {"V8": 0, "X": 1}   # mi355_yolo_layout
+YOLO_X_INFER = 3  # MI355_YOLO_X_INFER: an infer member's kind in selftest_yolox_infer_set_plan (no layout of the entry points)
 YOLO_X_HEAD = 2   # MI355_YOLO_X_HEAD: a head member's kind in selftest_yolox_head_set_plan (no layout of the entry points)
 # mi355_yolo_det as a numpy record
 YOLO_DET = np.dtype([("xmin", "<f4"), ("ymin", "<f4"), ("xmax", "<f4"), ("ymax", "<f4"), ("x", "<i4"), ("y", "<i4"), ("width", "<i4"),
@@ -443,6 +444,11 @@ def load_library():
         "mi355_group_yolox_head_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "mi355_selftest_yolox_head_set_plan": (i, [i, C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 3 + [C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 5 +
                                                [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+        "mi355_group_submit_yolox_infer": (i, [vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.POINTER(YoloParams), C.c_uint32, C.POINTER(C.c_uint64)]),
+        "mi355_group_release_yolox_net": (i, [vp, vp]),
+        "mi355_group_yolox_infer_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_yolox_infer_set_plan": (i, [i, C.POINTER(C.c_int), C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint32)] * 2 + [C.POINTER(C.c_int32)] +
+                                                [C.POINTER(C.c_uint32)] * 4 + [C.POINTER(C.c_uint64)]),
         "mi355_group_set_handdec_rendezvous": (i, [vp, i, C.c_uint]),
         "mi355_group_submit_handdec_palm": (i, [vp, vp, vp, C.c_uint32, C.POINTER(HandParams), C.POINTER(C.c_uint64)]),
         "mi355_group_submit_handdec_landmarks": (i, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(HandParams), C.POINTER(C.c_uint64)]),
@@ -804,6 +810,29 @@ class Group:
         self._ck(self.L.mi355_group_yolox_head_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
+    def submit_yolox_infer(self, ctx, net, d_frame, stride, width, height, params, max_dets=None):
+        """One RGB device frame of stream `ctx` for the finalized YoloxNet `net` as a member of the decoder queue (net: a YoloxNet, a
+        raw handle, or None for a null pointer; params: (box_thr, class_thr, iou_thr), a YoloParams, or None for a null pointer;
+        max_dets: default A of the frame size); returns the ticket, which wait_yolodec collects."""
+        cap = sum((height >> (3 + l)) * (width >> (3 + l)) for l in range(3)) if max_dets is None else max_dets
+        p = None if params is None else _yolo_params(params)[0]
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_yolox_infer(self.h, None if ctx is None else ctx.h, getattr(net, "h", net), d_frame, stride, width, height, p, cap,
+                                                       C.byref(t)))
+        self._yolodec_caps[t.value] = cap
+        return t.value
+
+    def release_yolox_net(self, net):
+        """Frees the queue's activation lanes of `net`; refused while a ticket that names it is pending or uncollected."""
+        self._ck(self.L.mi355_group_release_yolox_net(self.h, getattr(net, "h", net)))
+
+    def yolox_infer_stats(self):
+        """(frames launched, forwards launched, frames in the largest forward, kernel launches of conversions and forwards, lanes
+        alive, device allocations made for lanes since create)."""
+        c = (C.c_uint64 * 6)()
+        self._ck(self.L.mi355_group_yolox_infer_stats(self.h, c))
+        return tuple(int(v) for v in c)
+
     # ---- handdetectiontensordec / handlandmarktensordec tensors of independent elements
     def set_handdec_rendezvous(self, expected_streams, linger_us):
         self._ck(self.L.mi355_group_set_handdec_rendezvous(self.h, expected_streams, linger_us))
@@ -1038,6 +1067,23 @@ def selftest_yolox_head_set_plan(kinds, num_fields, num_candidates, max_dets, le
         per_job.append([] if lfirst is None else list(lfirst[at: at + c]))
         at += c
     return rc, list(cand)[:n], list(first)[:n], list(blocks)[:n], list(key)[:n], list(box)[:n], list(det)[:n], per_job, list(totals)
+
+
+def selftest_yolox_infer_set_plan(kinds, net_keys, heights, widths, null=()):
+    """mi355_selftest_yolox_infer_set_plan (host only): the infer side of one decoder launch set. kinds: "V8" / "X" / YOLO_X_HEAD /
+    YOLO_X_INFER or ints; null: names of arguments passed as null pointers (kind, net_key, height, width, class_of, frame_in_class,
+    conv_first_block, conv_blocks, class_frames, totals). Returns (status, class_of, frame_in_class, conv_first_block, conv_blocks,
+    class_frames, totals); class_frames holds one entry per class."""
+    L = load_library()
+    n = len(kinds)
+    m = max(n, 1)
+    a = {"kind": (C.c_int * m)(*[YOLO_LAYOUT.get(v, v) for v in kinds]), "net_key": (C.c_uint64 * m)(*net_keys), "height": (C.c_uint32 * m)(*heights),
+         "width": (C.c_uint32 * m)(*widths), "class_of": (C.c_int32 * m)(), "frame_in_class": (C.c_uint32 * m)(), "conv_first_block": (C.c_uint32 * m)(),
+         "conv_blocks": (C.c_uint32 * m)(), "class_frames": (C.c_uint32 * m)(), "totals": (C.c_uint64 * 3)()}
+    rc = L.mi355_selftest_yolox_infer_set_plan(n, *[None if k in null else v for k, v in a.items()])
+    totals = list(a["totals"])
+    return (rc, list(a["class_of"])[:n], list(a["frame_in_class"])[:n], list(a["conv_first_block"])[:n], list(a["conv_blocks"])[:n],
+            list(a["class_frames"])[:int(totals[0]) if rc == 0 else 0], totals)
 
 
 class AudioGroup:

@@ -1342,6 +1342,61 @@ int mi355_selftest_yolox_head_set_plan(int n_jobs, const int *kind, const uint32
                                        uint64_t *key_offset, uint64_t *box_offset, uint64_t *det_offset,
                                        uint32_t *level_first_block, uint64_t totals[8]);
 
+/* yoloxinference's network as a member of the decoder queue. A process with N `yoloxinference ! yoloxtensordec`
+ * pipelines that share one finalized net makes N lone mi355_yolox_infer_dets_device calls of ONE frame per frame period, the worst
+ * case of that call (88 - 160 dependent launches over grids that do not fill the device). submit_yolox_infer queues one RGB frame of
+ * stream `ctx` for `net` instead, and a set runs ONE forward per (net, frame size) over all of its frames. An infer member is one
+ * more kind of member of the queue above, not a queue of its own: its ticket comes from the group's one sequence and is collected
+ * with mi355_group_wait_yolodec into mi355_yolo_det records; set_yolodec_rendezvous counts it with tensors and heads;
+ * MI355_YOLODEC_SET_MAX caps the three kinds together (so a forward never exceeds 32 frames, within MI355_YOLOX_NET_MAX_FRAMES);
+ * yolodec_stats counts it as a tensor, its launches among the set's; yolox_head_stats counts it as a head, which it is from the
+ * score launch on; flush, wait_all, destroy, the failure reporting and the other queues' refusal of its ticket cover it as they
+ * cover a head. After wait_yolodec, dets and *n_dets hold exactly what mi355_yolox_infer_dets_device(net, d_frame, 0, stride, 1,
+ * width, height, p, dets, max_dets, n_dets) would have returned, byte for byte, the count above the capacity included: a frame's
+ * maps depend neither on the frame count nor on its place in the batch, the tile choice changes no byte, the conversion is exact
+ * and the head job kernels are byte-equal to the lone ones.
+ *   submit : never blocks. Refused with the status the lone call gives one frame: H, W multiples of 32 (MI355_ERR_INVALID_ARG) and
+ *           at most 2048 (MI355_ERR_UNSUPPORTED), MI355_ERR_NOT_CONFIGURED before _finalize, stride < 3 * width and a null frame
+ *           (MI355_ERR_INVALID_ARG). MI355_ERR_INVALID_ARG also: a null group, ctx, net, p or ticket, and a net whose context is on
+ *           another device than ctx. A refused submit queues nothing. The settings are copied at submit. The frame is read after
+ *           what ctx's HIP stream held at the call (the event of submit_yolodec) and until wait_yolodec for the ticket has returned.
+ *           The net must stay alive until every ticket that names it is collected. The queue keeps room for min(max_dets, A)
+ *           records, A = the sum over l = 0..2 of (H >> (3 + l)) (W >> (3 + l)).
+ *   A net shared by many threads: submit reads only what _finalize froze. The queue never touches the net's own arena, input tensor
+ *           or plan: it runs forwards in activation LANES of its own, on the queue's stream, one per class key (net, H, W) - not per
+ *           net: the head launches of a set run after all of its forwards, so two sizes of one net in a set need their own level
+ *           buffers. The owner may go on making lone _forward_device / _infer_* calls between a submit and its wait. A lane grows to
+ *           the largest frame count seen and is then reused without allocation; consecutive sets reuse it in stream order.
+ *   Per set: the infer members fall into classes by (net, H, W), numbered by first appearance in submit order, their frames in submit
+ *           order. The conversion jobs ride in the set's pinned block behind the head tables, in the same ONE host-to-device copy;
+ *           then ONE conversion launch for all infer members of all classes (yolox_input_jobs_kernel: one flat grid over the jobs'
+ *           blocks of 256 lanes of 4 pixels), then per class one forward of class_frames frames (mi355_yolox_net_launches(net)
+ *           launches), then the set's launches as before - the head score and head NMS launches cover submitted heads and infer
+ *           members together - and its one download. A set of k classes of infer members alone: one upload,
+ *           1 + the sum of launches(net_c) + 2 launches, one download.
+ *   release_yolox_net : waits for the queue's stream and frees the lanes of `net`. MI355_ERR_INVALID_ARG: null arguments, or a
+ *           ticket that names the net is pending or uncollected (it stays collectable). mi355_group_destroy frees every lane. Lanes
+ *           are keyed on a serial number a net gets at create, never on its address.
+ *   yolox_infer_stats : {frames launched, forwards launched (classes), frames in the largest forward, kernel launches of conversions
+ *           and forwards, lanes alive, device allocations made for lanes since create}.
+ *   mi355_selftest_yolox_infer_set_plan : host only, no device: the infer side of one set's layout, which the queue itself uses.
+ *           kind[j]: MI355_YOLO_V8, _X, _X_HEAD or MI355_YOLO_X_INFER. An infer job reads net_key[j] (any number that tells nets
+ *           apart), height[j], width[j]: class_of[j] = its class, frame_in_class[j] = its position among the class's frames,
+ *           conv_blocks[j] = ceil((W / 4) H / 256). Another job reads none of the three: class_of[j] = -1, conv_blocks[j] = 0.
+ *           conv_first_block[j] = the running sum of conv_blocks over the earlier jobs, for every job. class_frames[c]: the frames
+ *           of class c. totals = {classes, infer frames, conversion blocks}. The decode side of an infer job is what
+ *           mi355_selftest_yolox_head_set_plan gives a head job of the levels (H/8, W/8), (H/16, W/16), (H/32, W/32) with 5 + C
+ *           fields. Refused (MI355_ERR_INVALID_ARG): n_jobs outside 0..MI355_YOLODEC_SET_MAX, null arrays with n_jobs > 0, null
+ *           totals, a kind outside 0..3; an infer job of a size the net refuses returns that status. */
+#define MI355_YOLO_X_INFER 3 /* a member kind of the queue's plan only, as MI355_YOLO_X_HEAD is */
+int mi355_group_submit_yolox_infer(mi355_group *group, mi355_ctx *ctx, mi355_yolox_net *net, const uint8_t *d_frame, size_t stride,
+                                   uint32_t width, uint32_t height, const mi355_yolo_params *p, uint32_t max_dets, uint64_t *ticket);
+int mi355_group_release_yolox_net(mi355_group *group, const mi355_yolox_net *net);
+int mi355_group_yolox_infer_stats(mi355_group *group, uint64_t stats[6]);
+int mi355_selftest_yolox_infer_set_plan(int n_jobs, const int *kind, const uint64_t *net_key, const uint32_t *height,
+                                        const uint32_t *width, int32_t *class_of, uint32_t *frame_in_class,
+                                        uint32_t *conv_first_block, uint32_t *conv_blocks, uint32_t *class_frames, uint64_t totals[3]);
+
 /* The hand decoders across independent element instances. The reference elements receive one tensor per buffer per instance
  * (analytics/analytics/src/hand/handdetectiontensordec/imp.rs, hand/handlandmarktensordec/imp.rs: transform_ip); a process with N
  * camera pipelines, each with a palm decoder and a landmark decoder, makes 2 N lone calls per frame period, each a parameter

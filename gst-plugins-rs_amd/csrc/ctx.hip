@@ -1026,6 +1026,16 @@ int mi355_selftest_dssim_cbrt(mi355_ctx *ctx, uint32_t lo_bits, uint32_t hi_bits
   return dssim_cbrt_selftest(ctx, lo_bits, hi_bits, mismatches);
 }
 
+int mi355_selftest_dssim_plan(int width, int height, int n_cu, mi355_dssim_plan *plan) { return dssim_plan(width, height, n_cu, plan); }
+
+int mi355_selftest_dssim_compare_detail(mi355_ctx *ctx, const mi355_dssim_image *original, const mi355_dssim_image *modified, int scale, float *map,
+                                        double *slots, double *dssim) {
+  REQUIRE_CTX(ctx);
+  if (!original || !modified || !dssim || scale < 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: bad argument");
+  BIND_DEVICE(ctx);
+  return dssim_compare(ctx, original, modified, dssim, scale, map, slots);
+}
+
 int mi355_dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *image, int scale, int channel, int kind, float *out, int *width, int *height) {
   REQUIRE_CTX(ctx);
   if (!image) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: null image");

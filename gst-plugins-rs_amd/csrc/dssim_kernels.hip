@@ -186,6 +186,15 @@ constexpr int kPpl = (kTw * kTh) / kNt;            // tile pixels per lane in th
 static_assert((kTw * kTh) % kNt == 0 && kOwners <= kNt && kNt % 64 == 0 && kNt >= 256, "tile geometry");
 constexpr int kRw = kTw + 2 * kHalo, kRh = kTh + 2 * kHalo;  // 40 x 24 region
 
+// Is tile (tx, ty) of a w x h scale INTERIOR for a kernel with this halo: does its region - the tile plus `halo` cells on every side -
+// lie inside the image? The host's restatement (dssim_plan) of the block-uniform test the three tile kernels make on their own x0, y0
+// (region kRw x kRh for halo kHalo, kCw x kChh for halo kCh). The kernels do not call it: sharing it as a __host__ __device__ inline
+// changed their register allocation, and their code is kept as it was.
+static inline bool dssim_tile_interior(int tx, int ty, int w, int h, int halo) {
+  const int x0 = tx * kTw - halo, y0 = ty * kTh - halo;
+  return x0 >= 0 && y0 >= 0 && x0 + (kTw + 2 * halo) <= w && y0 + (kTh + 2 * halo) <= h;
+}
+
 struct DssimSrc {          // source of the scale's linear RGB
   const uint8_t *u8; int stride, channels; const float *lut;   // scale 0: packed sRGB(A) bytes + gamma table
   int pattern;                                                  // translucent pixels: 1 = over the crate's coloured pattern, 0 = over black
@@ -900,10 +909,66 @@ void dssim_release(mi355_ctx *ctx) {
   ctx->dssim_cache = nullptr;
 }
 
-static unsigned dssim_grid(mi355_ctx *ctx, size_t n) {
+// The geometry of an image, shared by every launch sequence below and by dssim_plan:
+// the grid of a 256-lane grid-stride kernel over n elements: one block per 256, at most 8 per CU
+static unsigned dssim_grid_blocks(int n_cu, size_t n) {
   size_t b = (n + 255) / 256;
-  const size_t cap = (size_t)ctx->n_cu * 8;
+  const size_t cap = (size_t)n_cu * 8;
   return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+static unsigned dssim_grid(mi355_ctx *ctx, size_t n) { return dssim_grid_blocks(ctx->n_cu, n); }
+// the scale chain: halved while both sides are >= 8 (downsample() -> None below that), at most kDssimScales; returns their number
+static int dssim_scale_chain(int width, int height, int *ws, int *hs) {
+  int ns = 0;
+  for (int w = width, h = height; ns < kDssimScales; ) {
+    ws[ns] = w; hs[ns] = h; ns++;
+    if (w < 8 || h < 8) break;
+    w /= 2; h /= 2;
+  }
+  return ns;
+}
+static unsigned dssim_tile_count(int w, int h) { return (unsigned)(((w + kTw - 1) / kTw) * ((h + kTh - 1) / kTh)); }
+// scales served by the launch that starts at scale k: scales 0 and 1 on their own, the small ones up to three per launch
+static int dssim_launch_jobs(int k, int ns) { return k < 2 ? 1 : (ns - k < 3 ? ns - k : 3); }
+// first[] of that launch: blocks [first[j], first[j + 1]) belong to job j (scale k + j), empty ranges behind the last job; returns the grid
+static unsigned dssim_launch_first(int k, int count, const unsigned *tiles, unsigned *first) {
+  unsigned total = 0;
+  for (int j = 0; j < 3; j++) {
+    first[j] = total;
+    if (j < count) total += tiles[k + j];
+  }
+  first[3] = total;
+  return total;
+}
+
+int dssim_plan(int width, int height, int n_cu, mi355_dssim_plan *plan) {
+  if (!plan || width <= 0 || height <= 0 || n_cu <= 0) return MI355_ERR_INVALID_ARG;
+  mi355_dssim_plan P = {};
+  P.tile_w = kTw; P.tile_h = kTh; P.tile_lanes = kNt; P.scale_halo = kHalo; P.compare_halo = kCh;
+  int ws[kDssimScales], hs[kDssimScales];
+  const int ns = P.n_scales = dssim_scale_chain(width, height, ws, hs);
+  for (int k = 0; k < ns; k++) {
+    P.w[k] = ws[k]; P.h[k] = hs[k];
+    P.tiles[k] = dssim_tile_count(ws[k], hs[k]);
+    const int tiles_x = (ws[k] + kTw - 1) / kTw;
+    for (unsigned t = 0; t < P.tiles[k]; t++) {
+      const int tx = (int)(t % (unsigned)tiles_x), ty = (int)(t / (unsigned)tiles_x);
+      P.interior_scale[k] += dssim_tile_interior(tx, ty, ws[k], hs[k], kHalo);
+      P.interior_compare[k] += dssim_tile_interior(tx, ty, ws[k], hs[k], kCh);
+    }
+    const size_t n = (size_t)ws[k] * hs[k];
+    P.downsample_blocks[k] = k ? dssim_grid_blocks(n_cu, n) : 0;
+    P.absdev_blocks[k] = dssim_grid_blocks(n_cu, n);
+  }
+  for (int k = 0; k < ns; ) {
+    const int l = P.n_launches++, count = dssim_launch_jobs(k, ns);
+    P.launch_scale[l] = k; P.launch_jobs[l] = count;
+    (void)dssim_launch_first(k, count, P.tiles, P.launch_first[l]);
+    k += count;
+  }
+  P.avg_blocks = P.sum_blocks = (unsigned)ns;
+  *plan = P;
+  return MI355_OK;
 }
 
 static int dssim_scratch(mi355_ctx *ctx, int slot, size_t bytes, void **out) {
@@ -965,12 +1030,8 @@ void dssim_free_image(mi355_ctx *ctx, mi355_dssim_image *img) {
 int dssim_create_image(mi355_ctx *ctx, const uint8_t *d_frame, int stride, int width, int height, int channels, mi355_dssim_image **out) {
   *out = nullptr;
   // scale geometry
-  int ws[kDssimScales], hs[kDssimScales], ns = 0;
-  for (int w = width, h = height; ns < kDssimScales; ) {
-    ws[ns] = w; hs[ns] = h; ns++;
-    if (w < 8 || h < 8) break;  // downsample() -> None
-    w /= 2; h /= 2;
-  }
+  int ws[kDssimScales], hs[kDssimScales];
+  const int ns = dssim_scale_chain(width, height, ws, hs);
   size_t planes_px = 0;
   for (int k = 0; k < ns; k++) planes_px += (size_t)ws[k] * hs[k];
   mi355_dssim_image *img = new mi355_dssim_image();
@@ -1021,18 +1082,13 @@ int dssim_create_image(mi355_ctx *ctx, const uint8_t *d_frame, int stride, int w
     for (int c = 0; c < 3; c++) { j.O.img[c] = s.img[c]; j.O.mu[c] = s.mu[c]; j.O.sq[c] = s.sq[c]; }
     return j;
   };
-  auto tiles_of = [&](int k) { return (unsigned)(((img->s[k].w + kTw - 1) / kTw) * ((img->s[k].h + kTh - 1) / kTh)); };
+  unsigned tiles[kDssimScales];
+  for (int k = 0; k < ns; k++) tiles[k] = dssim_tile_count(ws[k], hs[k]);
   for (int k = 0; k < ns; ) {
     DssimScaleJobs J;
-    const int count = k < 2 ? 1 : (ns - k < 3 ? ns - k : 3);
-    unsigned total = 0;
-    for (int j = 0; j < 3; j++) {
-      J.first[j] = total;
-      if (j < count) { J.job[j] = job_of(k + j); total += tiles_of(k + j); }
-      else J.job[j] = J.job[0];
-    }
-    J.first[3] = total;
-    for (int j = count; j < 3; j++) J.first[j] = total;  // empty ranges
+    const int count = dssim_launch_jobs(k, ns);
+    const unsigned total = dssim_launch_first(k, count, tiles, J.first);
+    for (int j = 0; j < 3; j++) J.job[j] = j < count ? job_of(k + j) : J.job[0];
     hipLaunchKernelGGL(dssim_scale_fused_kernel, dim3(total), dim3(kNt), 0, ctx->stream, J);
     k += count;
   }
@@ -1059,9 +1115,10 @@ int dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *img, int scale, i
 }
 
 // Dssim::compare -> the f64 value. One fused kernel per scale + two tiny reductions; a single D2H/sync at the end.
-int dssim_compare(mi355_ctx *ctx, const mi355_dssim_image *a, const mi355_dssim_image *b, double *out) {
+int dssim_compare(mi355_ctx *ctx, const mi355_dssim_image *a, const mi355_dssim_image *b, double *out, int map_scale, float *map_out, double *slots_out) {
   if (a->n_scales != b->n_scales || a->s[0].w != b->s[0].w || a->s[0].h != b->s[0].h)
     return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: images differ in size");
+  if (map_scale >= a->n_scales) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: the images have no such scale");
   // scratch: the SSIM maps of all scales, the two families of block partials, the result slots
   DssimRed R;
   R.n_scales = a->n_scales;
@@ -1070,7 +1127,7 @@ int dssim_compare(mi355_ctx *ctx, const mi355_dssim_image *a, const mi355_dssim_
   unsigned tiles[kDssimScales];
   for (int k = 0; k < a->n_scales; k++) {
     const size_t n = (size_t)a->s[k].w * a->s[k].h;
-    tiles[k] = (unsigned)(((a->s[k].w + kTw - 1) / kTw) * ((a->s[k].h + kTh - 1) / kTh));
+    tiles[k] = dssim_tile_count(a->s[k].w, a->s[k].h);
     R.n[k] = n;
     R.n_a[k] = tiles[k];
     R.first_b[k] = n_pb;
@@ -1114,6 +1171,13 @@ int dssim_compare(mi355_ctx *ctx, const mi355_dssim_image *a, const mi355_dssim_
   if ((rc = check_hip(ctx, hipMemcpyAsync(slots, d_slots, sizeof(double) * 3 * a->n_scales, hipMemcpyDeviceToHost, ctx->stream), "dssim: scores D2H"))) return rc;
   if ((rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "dssim: sync"))) return rc;
   *out = dssim_value_of(a, slots);
+  if (map_scale >= 0) {
+    if (slots_out) for (int j = 0; j < 3; j++) slots_out[j] = slots[3 * map_scale + j];
+    if (map_out) {
+      if ((rc = check_hip(ctx, hipMemcpyAsync(map_out, R.map[map_scale], R.n[map_scale] * sizeof(float), hipMemcpyDeviceToHost, ctx->stream), "dssim: map D2H"))) return rc;
+      if ((rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "dssim: sync"))) return rc;
+    }
+  }
   return MI355_OK;
 }
 
@@ -1133,13 +1197,9 @@ static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a,
                                      int stride, int width, int height, int channels, double *out, double *h_slots, int map_scale = -1, float *map_out = nullptr) {
   mi355_dssim_image geometry;   // scale sizes only (pairs: there is no image yet)
   if (!a) {
-    int ns0 = 0;
-    for (int w = width, h = height; ns0 < kDssimScales; ) {
-      geometry.s[ns0].w = w; geometry.s[ns0].h = h; ns0++;
-      if (w < 8 || h < 8) break;
-      w /= 2; h /= 2;
-    }
-    geometry.n_scales = ns0;
+    int ws[kDssimScales], hs[kDssimScales];
+    geometry.n_scales = dssim_scale_chain(width, height, ws, hs);
+    for (int k = 0; k < geometry.n_scales; k++) { geometry.s[k].w = ws[k]; geometry.s[k].h = hs[k]; }
     a = &geometry;
   }
   if (a->s[0].w != width || a->s[0].h != height) return set_error(ctx, MI355_ERR_INVALID_ARG, "dssim: frame and image differ in size");
@@ -1152,7 +1212,7 @@ static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a,
   unsigned tiles[kDssimScales];
   for (int k = 0; k < ns; k++) {
     const size_t n = (size_t)a->s[k].w * a->s[k].h;
-    tiles[k] = (unsigned)(((a->s[k].w + kTw - 1) / kTw) * ((a->s[k].h + kTh - 1) / kTh));
+    tiles[k] = dssim_tile_count(a->s[k].w, a->s[k].h);
     R.n[k] = n;
     R.n_a[k] = tiles[k];
     R.first_b[k] = n_pb;
@@ -1212,7 +1272,7 @@ static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a,
       }
       for (int k = 0; k < ns; ) {
         DssimFastJobs J;
-        const int count = k < 2 ? 1 : (ns - k < 3 ? ns - k : 3);
+        const int count = dssim_launch_jobs(k, ns);
         unsigned total = 0;
         for (int j = 0; j < 3; j++) {
           J.first[j] = total;
@@ -1261,15 +1321,9 @@ static int dssim_compare_frames_impl(mi355_ctx *ctx, const mi355_dssim_image *a,
     };
     for (int k = 0; k < ns; ) {
       DssimFusedJobs J;
-      const int count = k < 2 ? 1 : (ns - k < 3 ? ns - k : 3);
-      unsigned total = 0;
-      for (int j = 0; j < 3; j++) {
-        J.first[j] = total;
-        if (j < count) { J.job[j] = job_of(k + j); total += tiles[k + j]; }
-        else J.job[j] = J.job[0];
-      }
-      J.first[3] = total;
-      for (int j = count; j < 3; j++) J.first[j] = total;
+      const int count = dssim_launch_jobs(k, ns);
+      const unsigned total = dssim_launch_first(k, count, tiles, J.first);
+      for (int j = 0; j < 3; j++) J.job[j] = j < count ? job_of(k + j) : J.job[0];
       hipLaunchKernelGGL(dssim_hash_compare_kernel, dim3(total), dim3(kNt), 0, ctx->stream, J);
       k += count;
     }
@@ -1310,13 +1364,9 @@ int dssim_compare_pairs(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint
 // ... and the values once the copy has landed
 void dssim_scores_from_slots(int width, int height, const double *h_slots, int n_pairs, double *out) {
   mi355_dssim_image g;
-  int ns = 0;
-  for (int w = width, h = height; ns < kDssimScales; ) {
-    g.s[ns].w = w; g.s[ns].h = h; ns++;
-    if (w < 8 || h < 8) break;
-    w /= 2; h /= 2;
-  }
-  g.n_scales = ns;
+  int ws[kDssimScales], hs[kDssimScales];
+  g.n_scales = dssim_scale_chain(width, height, ws, hs);
+  for (int k = 0; k < g.n_scales; k++) { g.s[k].w = ws[k]; g.s[k].h = hs[k]; }
   for (int f = 0; f < n_pairs; f++) out[f] = dssim_value_of(&g, h_slots + (size_t)f * 3 * kDssimScales);
 }
 

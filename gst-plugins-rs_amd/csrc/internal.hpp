@@ -267,7 +267,11 @@ int loudnorm_process_batch(mi355_ctx *ctx, const double *data, size_t stream_str
 void loudnorm_batch_release(mi355_ctx *ctx);
 int dssim_create_image(mi355_ctx *ctx, const uint8_t *d_frame, int stride, int width, int height, int channels, mi355_dssim_image **out);
 void dssim_free_image(mi355_ctx *ctx, mi355_dssim_image *img);
-int dssim_compare(mi355_ctx *ctx, const mi355_dssim_image *a, const mi355_dssim_image *b, double *out);
+// map_scale >= 0 (mi355_selftest_dssim_compare_detail): the SSIM map of that scale goes to map_out and its [sum, avg, dev] slots to
+// slots_out (host; either may be null) behind the value
+int dssim_compare(mi355_ctx *ctx, const mi355_dssim_image *a, const mi355_dssim_image *b, double *out, int map_scale = -1, float *map_out = nullptr,
+                  double *slots_out = nullptr);
+int dssim_plan(int width, int height, int n_cu, mi355_dssim_plan *plan);   // host only (mi355_selftest_dssim_plan)
 int dssim_compare_frames(mi355_ctx *ctx, const mi355_dssim_image *a, const uint8_t *const *d_frames, int n_frames, int stride, int width, int height,
                          int channels, double *out);
 int dssim_compare_pairs_enqueue(mi355_ctx *ctx, const uint8_t *const *d_refs, const uint8_t *const *d_frames, int n_pairs, int stride, int width, int height,

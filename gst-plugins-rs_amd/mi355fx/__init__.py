@@ -63,6 +63,15 @@ class HsvFilterPlanOut(C.Structure):
                 ("reserved", C.c_uint32), ("units", C.c_uint64)]
 
 
+class DssimPlan(C.Structure):
+    """mi355_dssim_plan: the exact Dssim engine's geometry of one frame size (mi355_selftest_dssim_plan)."""
+    _fields_ = [("tile_w", C.c_int32), ("tile_h", C.c_int32), ("tile_lanes", C.c_int32), ("scale_halo", C.c_int32), ("compare_halo", C.c_int32),
+                ("n_scales", C.c_int32), ("w", C.c_int32 * 5), ("h", C.c_int32 * 5),
+                ("tiles", C.c_uint32 * 5), ("interior_scale", C.c_uint32 * 5), ("interior_compare", C.c_uint32 * 5),
+                ("n_launches", C.c_int32), ("launch_scale", C.c_int32 * 3), ("launch_jobs", C.c_int32 * 3), ("launch_first", (C.c_uint32 * 4) * 3),
+                ("downsample_blocks", C.c_uint32 * 5), ("absdev_blocks", C.c_uint32 * 5), ("avg_blocks", C.c_uint32), ("sum_blocks", C.c_uint32)]
+
+
 class AgingRadioSettings(C.Structure):
     """mi355_agingradio_settings: agingradio's Settings as transform_ip snapshots them (lowpass-freq goes to setup)."""
     _fields_ = [("white_noise_ampl", C.c_float), ("clicks_prob", C.c_float), ("bits_to_quantize", C.c_float),
@@ -474,6 +483,8 @@ def load_library():
         "mi355_dssim_compare_pairs_device": (i, [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, i, i, C.POINTER(C.c_double)]),
         "mi355_dssim_pair_map_device": (i, [vp, vp, vp, i, i, i, i, i, f32p, C.POINTER(i), C.POINTER(i)]),
         "mi355_selftest_dssim_cbrt": (i, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_dssim_plan": (i, [i, i, i, C.POINTER(DssimPlan)]),
+        "mi355_selftest_dssim_compare_detail": (i, [vp, vp, vp, i, f32p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "mi355_dssim_image_plane": (i, [vp, vp, i, i, i, f32p, C.POINTER(i), C.POINTER(i)]),
         "mi355_sofa_setup": (i, [vp, i, i, i, i]),
         "mi355_sofa_set_filter": (i, [vp, i, f32p, f32p, i, i]),
@@ -894,6 +905,24 @@ def selftest_hsvfilter_set_plan(frames, n_cu=256):
     rc = L.mi355_selftest_hsvfilter_set_plan(n_cu, fr, n, out, C.byref(n_sets))
     return rc, n_sets.value, [dict(set=o.set, launch=o.launch, variant=o.variant, units=int(o.units), first_block=o.first_block, blocks=o.blocks)
                               for o in list(out)[:n]]
+
+
+def selftest_dssim_plan(width, height, n_cu=256):
+    """mi355_selftest_dssim_plan (host only): the exact Dssim engine's geometry of a width x height frame on n_cu compute units.
+    Returns (status, dict): tile = (tile_w, tile_h, tile_lanes, scale_halo, compare_halo); scales = [(w, h)]; tiles, interior_scale,
+    interior_compare, downsample_blocks, absdev_blocks per scale; launches = [(first scale, jobs, first[0..3])]; avg_blocks,
+    sum_blocks. The dict is None when the status is not 0."""
+    L = load_library()
+    p = DssimPlan()
+    rc = L.mi355_selftest_dssim_plan(width, height, n_cu, C.byref(p))
+    if rc:
+        return rc, None
+    ns = p.n_scales
+    return rc, dict(tile=(p.tile_w, p.tile_h, p.tile_lanes, p.scale_halo, p.compare_halo), scales=[(p.w[k], p.h[k]) for k in range(ns)],
+                    tiles=list(p.tiles)[:ns], interior_scale=list(p.interior_scale)[:ns], interior_compare=list(p.interior_compare)[:ns],
+                    downsample_blocks=list(p.downsample_blocks)[:ns], absdev_blocks=list(p.absdev_blocks)[:ns],
+                    launches=[(p.launch_scale[l], p.launch_jobs[l], tuple(p.launch_first[l])) for l in range(p.n_launches)],
+                    avg_blocks=p.avg_blocks, sum_blocks=p.sum_blocks)
 
 
 def selftest_handdec_set_plan(decoders, rows):
@@ -1824,6 +1853,15 @@ class Context:
         v = C.c_double(0)
         self._ck(self.L.mi355_dssim_compare(self.h, a, b, C.byref(v)))
         return v.value
+
+    def selftest_dssim_compare_detail(self, a, b, scale):
+        """dssim_compare(a, b) with the insides of one scale: (value, (h, w) float32 SSIM map, [sum, avg, dev])."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._ck(self.L.mi355_dssim_image_plane(self.h, a, scale, 0, 0, None, C.byref(w), C.byref(h)))
+        m = np.full((h.value, w.value), np.nan, np.float32)
+        slots, v = (C.c_double * 3)(), C.c_double(0)
+        self._ck(self.L.mi355_selftest_dssim_compare_detail(self.h, a, b, scale, m.ctypes.data_as(C.POINTER(C.c_float)), slots, C.byref(v)))
+        return v.value, m, list(slots)
 
     # ---- sofalizer
     def sofa_setup(self, channels, filter_len, partition_length=64, block_length=256):

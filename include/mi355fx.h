@@ -731,6 +731,33 @@ int mi355_dssim_pair_map_device(mi355_ctx *ctx, const uint8_t *d_ref, const uint
  * Halley iteration with the range-restricted division the kernels use against the same iteration with the compiler's IEEE
  * division; *mismatches = how many differ in any bit (0 over (216/24389, 2], the whole domain of the conversion). */
 int mi355_selftest_dssim_cbrt(mi355_ctx *ctx, uint32_t lo_bits, uint32_t hi_bits, uint64_t *mismatches);
+/* Test-only entries of the exact engine (tests/dssim_cases.py holds the model they are compared with).
+ *   mi355_selftest_dssim_plan : host only, no device: what the engine's host code and kernels make of a width x height frame on a
+ *           device of n_cu compute units, from the functions and constants the launches themselves use. tile_w x tile_h: the tile of
+ *           the three tile kernels (tile_lanes lanes per block); scale_halo / compare_halo: the halo of the scale and hash-compare
+ *           kernels / of the compare kernel. Scale k is w[k] x h[k] (halved while both sides are >= 8, at most 5 scales) in tiles[k]
+ *           tiles, of which interior_scale[k] / interior_compare[k] take the kernels' INTERIOR path (the tile plus its halo lies
+ *           inside the scale). Launch l of create_image / compare_frames serves launch_jobs[l] scales from launch_scale[l] on, job j
+ *           in blocks [launch_first[l][j], launch_first[l][j + 1]). downsample_blocks[k] (k >= 1) and absdev_blocks[k]: the grids of
+ *           the box chain and of the absolute-deviation reduction (capped at 8 n_cu); avg_blocks / sum_blocks: one block per scale.
+ *           MI355_ERR_INVALID_ARG for a null plan, width / height <= 0 or n_cu <= 0.
+ *   mi355_selftest_dssim_compare_detail : mi355_dssim_compare (same launches, same value in *dssim) that also copies out the f32
+ *           SSIM map of scale `scale` (map, w[scale] * h[scale] floats; may be NULL) and that scale's three f64 reduction slots
+ *           [sum of the map, avg = max(sum / len, 0) ^ (0.5 ^ scale), sum of |avg - map|] (slots; may be NULL). */
+typedef struct mi355_dssim_plan {
+  int32_t tile_w, tile_h, tile_lanes, scale_halo, compare_halo;
+  int32_t n_scales;
+  int32_t w[5], h[5];
+  uint32_t tiles[5], interior_scale[5], interior_compare[5];
+  int32_t n_launches;
+  int32_t launch_scale[3], launch_jobs[3];
+  uint32_t launch_first[3][4];
+  uint32_t downsample_blocks[5], absdev_blocks[5];
+  uint32_t avg_blocks, sum_blocks;
+} mi355_dssim_plan;
+int mi355_selftest_dssim_plan(int width, int height, int n_cu, mi355_dssim_plan *plan);
+int mi355_selftest_dssim_compare_detail(mi355_ctx *ctx, const mi355_dssim_image *original, const mi355_dssim_image *modified,
+                                        int scale, float *map, double *slots, double *dssim);
 /* Diagnostics: one f32 plane of the image (kind 0 = LAB plane, 1 = mu, 2 = img_sq_blur) copied to `out` (may be NULL
  * to query the scale's size only). */
 int mi355_dssim_image_plane(mi355_ctx *ctx, const mi355_dssim_image *image, int scale, int channel, int kind,

@@ -205,6 +205,46 @@ def test_blockhash_pairs_take_the_lone_contexts_routes(mi355lib, oracle, name, w
         c.close()
 
 
+def test_dssim_pairs_at_the_interior_thresholds_share_one_interval(mi355lib):
+    """The eight geometries around the interior thresholds of the Dssim tile kernels (tests/dssim_cases.py, GROUP_GEOMETRIES: one
+    column or row short of an interior tile, an interior tile that ends on the last column and row, one with a column and a row to
+    spare, for either halo), two pairs each on poisoned padded rows, all pending in one interval of the compare queue: every result
+    == the element's own create_image + compare_frames and agrees with the restatement."""
+    import mi355fx
+    import dssim_cases as T
+    assert len(T.GROUP_GEOMETRIES) == 8
+    c = mi355fx.Context(0)
+    g = mi355fx.Group(0)
+    try:
+        jobs, bufs = [], []
+        for geo in T.GROUP_GEOMETRIES:
+            cases = [k for k in geo.cases if k.layout == "rgba" and k.content in ("noise3", "noise40")]
+            assert len(cases) == 2
+            d_ref = _upload(c, cases[0].buffers()[0])
+            bufs.append(d_ref)
+            for k in cases:
+                d_mod = _upload(c, k.buffers()[1])
+                bufs.append(d_mod)
+                jobs.append((k, d_ref + k.lead, d_mod + k.lead))
+        own = []
+        for k, da, db in jobs:
+            x = c.dssim_create_image_device(da, k.stride, k.w, k.h, k.fmt)
+            own.append(c.dssim_compare_frames_device(x, [db], k.stride, k.w, k.h, k.fmt)[0])
+            c.dssim_free_image(x)
+        tk = [g.submit_compare(c, da, db, k.stride, k.w, k.h, k.fmt, 5) for k, da, db in jobs]
+        assert g.compare_stats() == (0, 0, 0)                               # all sixteen pending at the first wait
+        got = [g.wait_compare(t)[0] for t in reversed(tk)][::-1]
+        assert got == own
+        for (k, _, _), v in zip(jobs, got):
+            assert v > 0.0 and v == pytest.approx(T.reference(k)[0], rel=1e-9, abs=1e-13), k.id
+        assert g.compare_stats() == (16, 8, 2)                              # one launch sequence per geometry, two pairs each
+        for d in bufs:
+            c.free(d)
+    finally:
+        g.close()
+        c.close()
+
+
 def test_compare_errors_and_a_result_is_collected_once(mi355lib):
     import mi355fx
     rng = np.random.default_rng(2)

@@ -775,4 +775,29 @@ int mi355_selftest_colordetect_plan(int n_cu, int n_jobs, const uint64_t *n_samp
   return colordetect_plan(n_cu, n_jobs, n_samples, first_block, blocks, samples_per_block, total_blocks);
 }
 
+// test only: the MMCQ kernel on a histogram given by the caller instead of one counted from a frame, launched as
+// mi355_colordetect_histogram_device launches its second step
+int mi355_selftest_colordetect_mmcq(mi355_ctx *ctx, const uint32_t *bins, int max_colors, uint8_t *palette_rgb, int *n_colors, int *box) {
+  if (!ctx) return MI355_ERR_INVALID_ARG;
+  if (!bins || !palette_rgb || !n_colors || !box) return set_error(ctx, MI355_ERR_INVALID_ARG, "colordetect: null bins or result arrays");
+  if (max_colors < 2 || max_colors > 255) return set_error(ctx, MI355_ERR_INVALID_ARG, "colordetect: max_colors must be 2..255");
+  uint64_t all = 0;
+  for (int i = 0; i < kBins; i++) all += bins[i];
+  if (all > 0xffffffffull) return set_error(ctx, MI355_ERR_INVALID_ARG, "colordetect: more than 2^32 - 1 samples in the bins");
+  int ch = 0;
+  Layout L{};
+  (void)layout_of(MI355_FMT_RGBA, &ch, &L);
+  int rc = check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  if (rc) return rc;
+  ColorDetectState *s = nullptr;
+  if ((rc = colordetect_scratch(ctx, 1, &s))) return rc;
+  s->hist_zero = false;
+  if ((rc = check_hip(ctx, hipMemcpyAsync(s->d_hist, bins, kBins * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "colordetect bins H2D"))) return rc;
+  __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
+  if ((rc = colordetect_enqueue(ctx, s, nullptr, 0, 0, 1, ch, L, 1, max_colors, true))) return rc;
+  if ((rc = colordetect_collect(ctx, s, 1, palette_rgb, n_colors))) return rc;
+  std::memcpy(box, s->h_res[0].box, sizeof(s->h_res[0].box));
+  return MI355_OK;
+}
+
 }  // extern "C"

@@ -280,6 +280,7 @@ def load_library():
         "mi355_colordetect_frame": (i, [vp, u8p, sz, i, i, i, u8p, C.POINTER(C.c_int)]),
         "mi355_colordetect_frames_device": (i, [vp, vp, sz, sz, i, i, i, i, u8p, C.POINTER(C.c_int)]),
         "mi355_colordetect_histogram_device": (i, [vp, vp, sz, i, i, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+        "mi355_selftest_colordetect_mmcq": (i, [vp, vp, i, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_hsvfilter_frame_ip": (i, [vp, u8p, sz, i, i, i, C.POINTER(HsvSettings)]),
         "mi355_hsvfilter_frames_device": (i, [vp, u8p, i, sz, i, i, i, i, C.POINTER(HsvSettings)]),
         "mi355_hsvdetect_frame": (i, [vp, u8p, sz, i, i, u8p, sz, i, i, i, C.POINTER(HsvDetectSettings)]),
@@ -1753,6 +1754,17 @@ class Context:
                                                            hist.ctypes.data_as(C.POINTER(C.c_uint32)), box))
         b = tuple(box[k] for k in range(6))
         return hist, (None if b[0] < 0 else b)
+
+    def selftest_colordetect_mmcq(self, bins, max_colors):
+        """Test only: (palette, first box or None) of the MMCQ kernel run on 32768 bins given by the caller."""
+        h = np.ascontiguousarray(bins, dtype=np.uint32).reshape(-1)
+        assert h.size == 32768
+        pal = np.zeros(255 * 3, np.uint8)
+        n = C.c_int(0)
+        box = (C.c_int * 6)()
+        self._ck(self.L.mi355_selftest_colordetect_mmcq(self.h, h.ctypes.data, max_colors, pal.ctypes.data, C.byref(n), box))
+        b = tuple(box[k] for k in range(6))
+        return [tuple(int(x) for x in pal[3 * k:3 * k + 3]) for k in range(n.value)], (None if b[0] < 0 else b)
 
     # ---- videocompare
     HASH_ALGO = {"mean": 0, "gradient": 1, "vertgradient": 2, "doublegradient": 3, "blockhash": 4, "dssim": 5}

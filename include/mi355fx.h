@@ -994,13 +994,20 @@ int mi355_roundedcorners_append_device(mi355_ctx *ctx, uint8_t *d_frames, size_t
  *   mi355_colordetect_frames_device    n_frames device planes at d_frames + f * frame_pitch; palette_rgb holds n_frames x 255 x 3
  *                                      bytes and n_colors n_frames ints; one synchronisation per call.
  *   mi355_colordetect_histogram_device diagnostics: the 32768 bins ((r>>3)<<10 | (g>>3)<<5 | (b>>3)) of one device plane and the
- *                                      first box {r1, r2, g1, g2, b1, b2} (all -1 when no sample is kept); synchronous. */
+ *                                      first box {r1, r2, g1, g2, b1, b2} (all -1 when no sample is kept); synchronous.
+ *   mi355_selftest_colordetect_mmcq    test only: the palette of a histogram the caller supplies. The 32768 bins are copied into
+ *                                      the context's histogram scratch and colordetect_mmcq_kernel runs on them as it runs on a
+ *                                      counted frame; palette, *n_colors and the first box come back and the scratch is zero
+ *                                      again. Null pointers, max_colors outside 2..255 and bins that sum to more than 2^32 - 1
+ *                                      (more than a frame can hold) are MI355_ERR_INVALID_ARG; synchronous. */
 int mi355_colordetect_frame(mi355_ctx *ctx, const uint8_t *data, size_t data_len, int format, int quality, int max_colors,
                             uint8_t palette_rgb[255 * 3], int *n_colors);
 int mi355_colordetect_frames_device(mi355_ctx *ctx, const uint8_t *d_frames, size_t frame_pitch, size_t data_len, int n_frames,
                                     int format, int quality, int max_colors, uint8_t *palette_rgb, int *n_colors);
 int mi355_colordetect_histogram_device(mi355_ctx *ctx, const uint8_t *d_data, size_t data_len, int format, int quality,
                                        uint32_t hist[32768], int box[6]);
+int mi355_selftest_colordetect_mmcq(mi355_ctx *ctx, const uint32_t bins[32768], int max_colors, uint8_t palette_rgb[255 * 3],
+                                    int *n_colors, int box[6]);
 
 /* ---------------------------------------------------------------- yolov8tensordec2 / yoloxtensordec (csrc/yolodec.hip)
  * Replaces the decode loops of YoloTensorDec::transform_ip (analytics/analytics/src/yolotensordec/imp.rs:234-422, iou :480-489):

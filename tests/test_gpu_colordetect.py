@@ -117,6 +117,8 @@ def _frames(synth):
 
 @pytest.mark.parametrize("max_colors", [2, 3, 5, 8, 16, 64, 255])
 def test_palette_matches_restatement(ctx, synth, max_colors):
+    """Whole pictures. Which branches of the MMCQ they reach is accidental: the directed coverage, case by case and branch by
+    branch, lives in tests/test_gpu_colordetect_cases.py."""
     for name, frame in _frames(synth).items():
         for q in (1, 10):
             got = ctx.colordetect_frame(frame, "RGBA", q, max_colors)

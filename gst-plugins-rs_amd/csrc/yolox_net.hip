@@ -19,6 +19,15 @@
 //                               summation: the error grows with 16 + K / 16, not K), so a result depends on nothing but its own inputs. Both tails (Cout,
 //                               Cin k k, pixels) are guarded. MODE 1 folds the Focus gather (blocks.rs:176-211: top-left,
 //                               bottom-left, top-right, bottom-right, 3 channels each) into the input addressing of the stem.
+//   yolox_conv_mfma_kernel<K, MODE, TN>  the same convolution for a net of MI355_YOLOX_PRECISION_BF16: an implicit
+//                               GEMM on v_mfma_f32_16x16x32_bf16. A block takes 64 output channels x TN output pixels of one frame
+//                               (TN 64: four waves of 32 x 32; TN 16: four waves of 16 x 16 - the same bytes); the reduction goes
+//                               through LDS in steps of 32: a 64 x 32 tile of the weights packed to bf16 at _finalize
+//                               (yolox_pack_bf16_kernel: rows padded to 64, the reduction to 32, with zeros) and TN x 32 input
+//                               values gathered with the addressing above and rounded to bf16 (nearest, ties to even) on the way
+//                               into LDS, both laid out so that a lane's 8 consecutive k are one 16-byte read. Products are exact in
+//                               f32, accumulation is f32 in the accumulator registers, one instruction per output and step in
+//                               ascending order; the epilogue is conv_store, unchanged.
 //   yolox_dw_kernel             depthwise 3 x 3 (groups = C), one lane per output value.
 //   yolox_pool5_kernel          max-pool 5 x 5, stride 1, pad 2 with -inf; SPP's 9 and 13 are the cascade 5∘5 and 5∘5∘5 (max is exact).
 //   yolox_up2_kernel            nearest 2x: out[y][x] = in[y / 2][x / 2], written into the concat destination.
@@ -54,6 +63,8 @@ struct ConvArgs {
   unsigned long long res_pitch;
   const float *w, *scale, *shift;
   uint32_t cin, cout, hi, wi, ho, wo, stride, silu;
+  const unsigned short *wp;   // a BF16 net: the packed weights [cout padded to 64][kpad] bf16; null otherwise
+  uint32_t kpad;              // cin k k padded to 32
 };
 
 __device__ __forceinline__ float silu_f(float v) { return v * (1.0f / (1.0f + expf(-v))); }
@@ -212,6 +223,129 @@ __global__ __launch_bounds__(256) void yolox_up2_kernel(const float *__restrict_
   if (e >= Po * C) return;
   const uint32_t c = (uint32_t)(e / Po), p = (uint32_t)(e - (size_t)c * Po), y = p / (2 * w), x = p - y * (2 * w);
   out[(size_t)blockIdx.z * out_pitch + e] = in[(size_t)blockIdx.z * in_pitch + ((size_t)c * h + (y >> 1)) * w + (x >> 1)];
+}
+
+// ---- bf16 operands on the matrix cores (MI355_YOLOX_PRECISION_BF16)
+
+constexpr int kMK = 32, kMPitch = 40;   // the reduction step; bf16 values from row to row of a tile in LDS (80 B: 16-byte reads stay aligned)
+
+// f32 -> bf16, round to nearest, ties to even, on the bit pattern: finite values below 2^127 (the contract excludes the rest)
+__host__ __device__ __forceinline__ uint32_t bf16_rne(uint32_t bits) { return (bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16; }
+
+// one dense conv's weights [cout][ktot] f32 -> [rows][kpad] bf16, zeros in the padding; grid: groups of 256 values
+__global__ __launch_bounds__(256) void yolox_pack_bf16_kernel(const float *__restrict__ w, unsigned short *__restrict__ out, uint32_t cout, uint32_t ktot, uint32_t rows,
+                                                                 uint32_t kpad) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)rows * kpad) return;
+  const uint32_t r = (uint32_t)(e / kpad), c = (uint32_t)(e - (size_t)r * kpad);
+  out[e] = (r < cout && c < ktot) ? (unsigned short)bf16_rne(__float_as_uint(w[(size_t)r * ktot + c])) : (unsigned short)0;
+}
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// two activations -> two bf16 in one dword, the first in the low half: the hardware's conversion (v_cvt_pk_bf16_f32: round to nearest,
+// ties to even - for the values of the contract the bits of bf16_rne, which tests/test_gpu_yolox_net_bf16.py pins with planted ties)
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+  const bf16x2 r = __builtin_convertvector(f32x2{lo, hi}, bf16x2);
+  return __builtin_bit_cast(uint32_t, r);
+}
+
+// grid (pixel tiles, channel tiles, frames); 4 waves: TN 64 as 2 x 2 of 32 channels x 32 pixels, TN 16 as 4 x 1 of 16 x 16
+template <int K, int MODE, int TN>
+__global__ __launch_bounds__(256) void yolox_conv_mfma_kernel(const ConvArgs A) {
+  static_assert(TN == 64 || TN == 16, "tile");
+  constexpr int KPT = kMK * TN / 256;           // gathered values of a step per thread: 8 consecutive k of one pixel, or 2
+  constexpr int MI = TN == 64 ? 2 : 1, NI = MI;  // 16 x 16 tiles of a wave
+  __shared__ __attribute__((aligned(16))) unsigned short As[kTM][kMPitch];
+  __shared__ __attribute__((aligned(16))) unsigned short Bs[TN][kMPitch];
+  constexpr uint32_t KK = K * K;
+  constexpr int pad = (K - 1) / 2;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t P = A.ho * A.wo, p0 = blockIdx.x * TN, oc0 = blockIdx.y * kTM, f = blockIdx.z;
+  const uint32_t Ktot = A.cin * KK;
+  const float *__restrict__ in = A.in + (size_t)f * A.in_pitch;
+  // gather role: one pixel, KPT consecutive reduction indices
+  const uint32_t g_px = tid % TN, g_k = (tid / TN) * KPT;
+  const uint32_t gp = p0 + g_px;
+  const bool pv = gp < P;
+  const uint32_t oy = pv ? gp / A.wo : 0, ox = pv ? gp - oy * A.wo : 0;
+  const int iy0 = (int)(oy * A.stride) - pad, ix0 = (int)(ox * A.stride) - pad;
+  const uint32_t plane = A.hi * A.wi;
+  // weight role: 8 consecutive reduction indices of one channel, 16 bytes of the packed store (padded: no guard)
+  const unsigned short *__restrict__ wrow = A.wp + (size_t)(oc0 + (tid >> 2)) * A.kpad + (tid & 3) * 8;
+  auto fetch = [&](uint32_t k0, uint4 &ar, float (&br)[KPT]) {
+    ar = *reinterpret_cast<const uint4 *>(wrow + k0);
+    uint32_t kk = k0 + g_k;
+    uint32_t ci = kk / KK, tap = kk - ci * KK;
+#pragma unroll
+    for (int j = 0; j < KPT; j++) {
+      const int dy = (int)(tap / K), dx = (int)(tap - (tap / K) * K);
+      const int iy = iy0 + dy, ix = ix0 + dx;
+      // every load is issued, at the view's first value where the term is padding, and then zeroed: no branch around a load,
+      // so the step's loads are in flight together
+      const bool ok = kk < Ktot && pv && (unsigned)iy < A.hi && (unsigned)ix < A.wi;
+      size_t at;   // one 32-bit offset inside a plane (a side is at most 2048), one 64-bit multiply-add for the plane
+      if (MODE == 0) {
+        at = (size_t)ci * plane + ((uint32_t)iy * A.wi + (uint32_t)ix);
+      } else {   // Focus, as in yolox_conv_kernel
+        const uint32_t patch = ci / 3, c = ci - 3 * patch;
+        const uint32_t fy = 2 * (uint32_t)iy + (patch & 1), fx = 2 * (uint32_t)ix + (patch >> 1);
+        at = (size_t)c * (4 * plane) + (fy * (2 * A.wi) + fx);
+      }
+      float v = in[ok ? at : 0];
+      v = ok ? v : 0.0f;
+      br[j] = v;
+      kk++;
+      if (++tap == KK) tap = 0, ci++;
+    }
+  };
+  const uint32_t wm = TN == 64 ? wave >> 1 : wave, wn = TN == 64 ? wave & 1 : 0;   // the wave's place in the block's tile
+  const uint32_t fr = lane & 15, fk = (lane >> 4) * 8;                              // fragment row (A) or column (B); first k
+  f32x4 acc[MI][NI];
+#pragma unroll
+  for (int i = 0; i < MI; i++)
+#pragma unroll
+    for (int j = 0; j < NI; j++) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  uint4 ar;
+  float br[KPT];
+  fetch(0, ar, br);
+  for (uint32_t k0 = 0; k0 < Ktot; k0 += kMK) {
+    *reinterpret_cast<uint4 *>(&As[tid >> 2][(tid & 3) * 8]) = ar;
+    uint32_t pk[KPT / 2];
+#pragma unroll
+    for (int j = 0; j < KPT / 2; j++) pk[j] = pack_bf16x2(br[2 * j], br[2 * j + 1]);
+    if (KPT == 8) *reinterpret_cast<uint4 *>(&Bs[g_px][g_k]) = uint4{pk[0], pk[KPT > 2 ? 1 : 0], pk[KPT > 4 ? 2 : 0], pk[KPT > 6 ? 3 : 0]};
+    else *reinterpret_cast<uint32_t *>(&Bs[g_px][g_k]) = pk[0];
+    __syncthreads();
+    if (k0 + kMK < Ktot) fetch(k0 + kMK, ar, br);   // the next step's loads are in flight while this one is summed
+    bf16x8 af[MI], bf[NI];
+#pragma unroll
+    for (int i = 0; i < MI; i++) af[i] = *reinterpret_cast<const bf16x8 *>(&As[(wm * MI + i) * 16 + fr][fk]);
+#pragma unroll
+    for (int j = 0; j < NI; j++) bf[j] = *reinterpret_cast<const bf16x8 *>(&Bs[(wn * NI + j) * 16 + fr][fk]);
+#pragma unroll
+    for (int i = 0; i < MI; i++)
+#pragma unroll
+      for (int j = 0; j < NI; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+    __syncthreads();   // the tiles are written again
+  }
+  // accumulator register r of a lane: channel 4 (lane / 16) + r, pixel lane % 16 of the 16 x 16 tile
+#pragma unroll
+  for (int i = 0; i < MI; i++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const uint32_t oc = oc0 + (wm * MI + i) * 16 + (lane >> 4) * 4 + r;
+      if (oc >= A.cout) continue;
+      const float sc = A.scale[oc], sh = A.shift[oc];
+#pragma unroll
+      for (int j = 0; j < NI; j++) {
+        const uint32_t p = p0 + (wn * NI + j) * 16 + fr;
+        if (p < P) conv_store(A, f, oc, P, p, acc[i][j][r], sc, sh);
+      }
+    }
 }
 
 // ---- the definition of a net: what the config alone decides
@@ -588,14 +722,40 @@ void launch_conv(hipStream_t stream, int kind, const ConvArgs &A, uint32_t k, ui
   else hipLaunchKernelGGL((yolox_conv_kernel<1, 0, TPX>), grid, dim3(256), 0, stream, A);
 }
 
+template <int TN>
+void launch_conv_mfma(hipStream_t stream, int kind, const ConvArgs &A, uint32_t k, uint32_t n_frames) {
+  const uint32_t P = A.ho * A.wo;
+  const dim3 grid((P + TN - 1) / TN, (A.cout + kTM - 1) / kTM, n_frames);
+  if (kind == kOpFocus) hipLaunchKernelGGL((yolox_conv_mfma_kernel<3, 1, TN>), grid, dim3(256), 0, stream, A);
+  else if (k == 3) hipLaunchKernelGGL((yolox_conv_mfma_kernel<3, 0, TN>), grid, dim3(256), 0, stream, A);
+  else hipLaunchKernelGGL((yolox_conv_mfma_kernel<1, 0, TN>), grid, dim3(256), 0, stream, A);
+}
+
+// the bf16 store of one dense conv: rows and reduction length as packed
+uint32_t pack_rows(uint32_t cout) { return (cout + kTM - 1) / kTM * kTM; }
+uint32_t pack_kpad(uint32_t ktot) { return (ktot + kMK - 1) / kMK * kMK; }
+hipError_t launch_pack(hipStream_t stream, const float *w, unsigned short *out, uint32_t cout, uint32_t ktot) {
+  const uint32_t rows = pack_rows(cout), kpad = pack_kpad(ktot);
+  const size_t total = (size_t)rows * kpad;
+  hipLaunchKernelGGL(yolox_pack_bf16_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, w, out, cout, ktot, rows, kpad);
+  return hipGetLastError();
+}
+
 // n_cu: the device's compute units. A convolution with fewer than three 64 x 64 tiles for four CUs takes 64 x 16 tiles instead
 // (measured, DESIGN 4.14: one frame of YOLOX-s 3.85 -> 2.80 ms; at one or two tiles per CU the batches of 8 lose 5 % and 34 %).
 // Every output is the same chain of 16-term steps under either tile, so the choice changes no byte of the result.
-hipError_t launch_op(hipStream_t stream, int kind, const ConvArgs &A, uint32_t k, uint32_t n_frames, uint32_t n_cu) {
+// precision BF16 (A.wp set): the dense convolutions take the matrix-core kernel, under the same rule and with the same property (one
+// instruction per output and 32-term step under either tile); every other op runs the code it always ran.
+hipError_t launch_op(hipStream_t stream, int kind, const ConvArgs &A, uint32_t k, uint32_t n_frames, uint32_t n_cu, int precision) {
   const uint32_t P = A.ho * A.wo;
   if (kind == kOpConv || kind == kOpFocus) {
     const uint64_t wide_blocks = (uint64_t)((P + kTN - 1) / kTN) * ((A.cout + kTM - 1) / kTM) * n_frames;
-    if (wide_blocks * 4 < 3ull * n_cu) launch_conv<1>(stream, kind, A, k, n_frames);
+    const bool narrow = wide_blocks * 4 < 3ull * n_cu;
+    if (precision == MI355_YOLOX_PRECISION_BF16) {
+      if (!A.wp) return hipErrorInvalidValue;   // no packed weights: never the f32 kernel in their place
+      if (narrow) launch_conv_mfma<16>(stream, kind, A, k, n_frames);
+      else launch_conv_mfma<64>(stream, kind, A, k, n_frames);
+    } else if (narrow) launch_conv<1>(stream, kind, A, k, n_frames);
     else launch_conv<4>(stream, kind, A, k, n_frames);
   } else if (kind == kOpDw) {
     hipLaunchKernelGGL(yolox_dw_kernel, dim3((P + 255) / 256, A.cout, n_frames), dim3(256), 0, stream, A);
@@ -646,6 +806,9 @@ struct mi355_yolox_net {
   std::vector<size_t> host_off;
   bool finalized = false;
   float *d_params = nullptr, *d_ss = nullptr;   // the parameter store; scale [channels] then shift [channels]
+  int precision = MI355_YOLOX_PRECISION_F32;    // of the dense convolutions' operands; frozen by _finalize
+  unsigned short *d_wp = nullptr;               // a BF16 net: every dense conv's packed bf16 weights, conv c at wp_off[c]
+  std::vector<size_t> wp_off;
   YxLane lane;                            // the lone entry points'
 };
 
@@ -726,9 +889,10 @@ static hipError_t lane_run(const mi355_yolox_net *net, const YxLane &lane, hipSt
       A.stride = c.stride, A.silu = op.silu ? 1 : 0;
       A.cin = c.cin;
       k = c.k;
+      if (net->d_wp && !c.dw) A.wp = net->d_wp + net->wp_off[op.conv], A.kpad = pack_kpad(c.cin * c.k * c.k);
     }
     if (op.kind == kOpFocus) A.hi = A.ho, A.wi = A.wo;   // the gathered [12][H / 2][W / 2] input
-    if (const hipError_t e = launch_op(stream, op.kind, A, k, n, n_cu)) return e;
+    if (const hipError_t e = launch_op(stream, op.kind, A, k, n, n_cu, net->precision)) return e;
   }
   return hipSuccess;
 }
@@ -914,7 +1078,7 @@ int mi355_yolox_net_create(mi355_ctx *ctx, const mi355_yolox_net_config *config,
 void mi355_yolox_net_destroy(mi355_yolox_net *net) {
   if (!net) return;
   if (net->ctx) (void)hipSetDevice(net->ctx->device);
-  for (float *p : {net->d_params, net->d_ss})
+  for (void *p : {(void *)net->d_params, (void *)net->d_ss, (void *)net->d_wp})
     if (p) (void)hipFree(p);   // waits for the device: a forward still running has finished with them
   net->lane.release();
   delete net;
@@ -969,9 +1133,41 @@ int mi355_yolox_net_finalize(mi355_yolox_net *net) {
   if ((rc = check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice"))) return rc;
   if ((rc = check_hip(ctx, hipMemcpy(net->d_ss, ss.data(), ss.size() * 4, hipMemcpyHostToDevice), "yolox_net epilogue H2D"))) return rc;
   __atomic_fetch_add(&ctx->n_h2d, 1ull, __ATOMIC_RELAXED);
+  if (net->precision == MI355_YOLOX_PRECISION_BF16) {   // the dense convolutions' weights, rounded once, on the device (the host keeps none)
+    net->wp_off.assign(N.convs.size(), 0);
+    size_t total = 0;
+    for (size_t c = 0; c < N.convs.size(); c++) {
+      if (N.convs[c].dw) continue;
+      net->wp_off[c] = total;
+      total += (size_t)pack_rows(N.convs[c].cout) * pack_kpad(N.convs[c].cin * N.convs[c].k * N.convs[c].k);
+    }
+    if ((rc = check_hip(ctx, hipMalloc((void **)&net->d_wp, total * 2), "hipMalloc(yolox_net bf16 weights)"))) return rc;
+    hipError_t e = hipSuccess;
+    for (size_t c = 0; c < N.convs.size() && e == hipSuccess; c++) {
+      const ConvDef &cd = N.convs[c];
+      if (!cd.dw) e = launch_pack(ctx->stream, net->d_params + N.params[cd.w].off, net->d_wp + net->wp_off[c], cd.cout, cd.cin * cd.k * cd.k);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(net->d_wp);
+      net->d_wp = nullptr;
+      return check_hip(ctx, e, "yolox_net bf16 weight packing");
+    }
+  }
   net->finalized = true;
   return MI355_OK;
 }
+
+int mi355_yolox_net_set_precision(mi355_yolox_net *net, int precision) {
+  if (!net) return MI355_ERR_INVALID_ARG;
+  if (net->finalized) return set_error(net->ctx, MI355_ERR_INVALID_ARG, "yolox_net: the net is finalized and immutable");
+  if (precision != MI355_YOLOX_PRECISION_F32 && precision != MI355_YOLOX_PRECISION_BF16)
+    return set_error(net->ctx, MI355_ERR_INVALID_ARG, "yolox_net: precision is neither MI355_YOLOX_PRECISION_F32 nor _BF16");
+  net->precision = precision;
+  return MI355_OK;
+}
+
+int mi355_yolox_net_precision(const mi355_yolox_net *net) { return net ? net->precision : MI355_ERR_INVALID_ARG; }
 
 int mi355_yolox_net_forward_device(mi355_yolox_net *net, const float *d_in, size_t in_pitch_bytes, int n_frames, uint32_t H, uint32_t W,
                                    mi355_yolox_level levels[3]) {
@@ -1071,7 +1267,8 @@ int mi355_selftest_yolox_net_param_info(const mi355_yolox_net_config *config, in
   return param_info_of(cached, index, name, name_cap, dims, n_dims);
 }
 
-int mi355_selftest_yolox_net_op_device(mi355_ctx *ctx, const mi355_yolox_net_op *op) {
+// the checks of the one-op entries and the launch arguments of a checked op
+static int selftest_op_args(mi355_ctx *ctx, const mi355_yolox_net_op *op, ConvArgs *args, uint32_t *k_out) {
   if (!ctx) return MI355_ERR_INVALID_ARG;
   if (!op || !op->in || !op->out || (op->tile != 0 && op->tile != 1 && op->tile != 4)) return set_error(ctx, MI355_ERR_INVALID_ARG, "yolox_net op: null op or views, or a tile that is not 0, 1 or 4");
   const int kind = op->kind;
@@ -1087,7 +1284,8 @@ int mi355_selftest_yolox_net_op_device(mi355_ctx *ctx, const mi355_yolox_net_op 
   if (!is_conv && op->res) return set_error(ctx, MI355_ERR_INVALID_ARG, "yolox_net op: a residual needs a convolution");
   int rc = MI355_OK;
   if ((rc = check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice"))) return rc;
-  ConvArgs A{};
+  ConvArgs &A = *args;
+  A = ConvArgs{};
   const uint32_t k = kind == kOpConv ? (uint32_t)op->k : 3, stride = is_conv ? (uint32_t)op->stride : 1, padk = (k - 1) / 2;
   A.hi = op->h_in, A.wi = op->w_in;
   if (kind == kOpUp) A.ho = 2 * A.hi, A.wo = 2 * A.wi;
@@ -1104,7 +1302,35 @@ int mi355_selftest_yolox_net_op_device(mi355_ctx *ctx, const mi355_yolox_net_op 
   }
   A.w = op->weight, A.scale = op->scale, A.shift = op->shift;
   A.cin = kind == kOpFocus ? 12 : op->in_c, A.cout = op->out_c, A.stride = stride, A.silu = op->silu ? 1 : 0;
-  return check_hip(ctx, launch_op(ctx->stream, kind, A, k, op->n_frames, op->tile == 4 ? 0u : op->tile == 1 ? UINT32_MAX / 2 : (uint32_t)ctx->n_cu), "yolox_net op launch");
+  *k_out = k;
+  return MI355_OK;
+}
+
+// the n_cu that makes launch_op take the tile an op names
+static uint32_t selftest_op_cu(const mi355_ctx *ctx, const mi355_yolox_net_op *op) { return op->tile == 4 ? 0u : op->tile == 1 ? UINT32_MAX / 2 : (uint32_t)ctx->n_cu; }
+
+int mi355_selftest_yolox_net_op_device(mi355_ctx *ctx, const mi355_yolox_net_op *op) {
+  ConvArgs A{};
+  uint32_t k = 0;
+  if (const int rc = selftest_op_args(ctx, op, &A, &k)) return rc;
+  return check_hip(ctx, launch_op(ctx->stream, op->kind, A, k, op->n_frames, selftest_op_cu(ctx, op), MI355_YOLOX_PRECISION_F32), "yolox_net op launch");
+}
+
+int mi355_selftest_yolox_net_op_bf16_device(mi355_ctx *ctx, const mi355_yolox_net_op *op) {
+  ConvArgs A{};
+  uint32_t k = 0;
+  if (const int rc = selftest_op_args(ctx, op, &A, &k)) return rc;
+  if (op->kind != kOpConv && op->kind != kOpFocus) return set_error(ctx, MI355_ERR_INVALID_ARG, "yolox_net bf16 op: the kind is neither a dense conv nor the Focus stem");
+  const uint32_t ktot = A.cin * k * k;
+  unsigned short *d_wp = nullptr;
+  int rc = MI355_OK;
+  if ((rc = check_hip(ctx, hipMalloc((void **)&d_wp, (size_t)pack_rows(A.cout) * pack_kpad(ktot) * 2), "hipMalloc(yolox_net op bf16 weights)"))) return rc;
+  hipError_t e = launch_pack(ctx->stream, A.w, d_wp, A.cout, ktot);   // what _finalize runs per conv
+  A.wp = d_wp, A.kpad = pack_kpad(ktot);
+  if (e == hipSuccess) e = launch_op(ctx->stream, op->kind, A, k, op->n_frames, selftest_op_cu(ctx, op), MI355_YOLOX_PRECISION_BF16);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);   // the packed copy is this call's
+  (void)hipFree(d_wp);
+  return check_hip(ctx, e != hipSuccess ? e : es, "yolox_net bf16 op");
 }
 
 }  // extern "C"

@@ -172,6 +172,7 @@ class YoloxNetConfig(C.Structure):
 YOLOX_VARIANTS = {"nano": (0.33, 0.25, True), "tiny": (0.33, 0.375, False), "s": (0.33, 0.50, False), "m": (0.67, 0.75, False), "l": (1.0, 1.0, False),
                   "x": (1.33, 1.25, False)}
 YOLOX_NET_MAX_FRAMES, YOLOX_NET_MAX_SIDE, YOLOX_NET_NAME_MAX = 64, 2048, 96
+YOLOX_PRECISION = {"f32": 0, "bf16": 1}   # MI355_YOLOX_PRECISION_*
 YOLOX_OP = {"conv": 0, "dw": 1, "pool5": 2, "up2": 3, "focus": 4}   # kinds of mi355_selftest_yolox_net_op_device
 
 
@@ -439,6 +440,9 @@ def load_library():
         "mi355_selftest_yolox_net_plan": (i, [C.POINTER(YoloxNetConfig), i, C.c_uint32, C.c_uint32, C.POINTER(YoloxNetPlan)]),
         "mi355_selftest_yolox_net_param_info": (i, [C.POINTER(YoloxNetConfig), i, C.c_char_p, sz, C.POINTER(C.c_uint32), C.POINTER(i)]),
         "mi355_selftest_yolox_net_op_device": (i, [vp, C.POINTER(YoloxNetOp)]),
+        "mi355_yolox_net_set_precision": (i, [vp, i]),
+        "mi355_yolox_net_precision": (i, [vp]),
+        "mi355_selftest_yolox_net_op_bf16_device": (i, [vp, C.POINTER(YoloxNetOp)]),
         "mi355_handdec_palm_tensor": (i, [vp, vp, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
         "mi355_handdec_palm_tensors_device": (i, [vp, vp, sz, i, C.c_uint32, C.POINTER(HandParams), vp, C.POINTER(C.c_uint32)]),
         "mi355_handdec_landmarks_tensor": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(HandParams), vp, vp, C.POINTER(C.c_uint32)]),
@@ -1012,6 +1016,13 @@ class YoloxNet:
         """arrays: {name: array} holding every parameter of params()."""
         for k, (name, dims) in enumerate(self.params()):
             self.set_param(k, np.asarray(arrays[name], dtype=np.float32).reshape(dims))
+
+    def set_precision(self, precision):
+        """mi355_yolox_net_set_precision: "f32" (the default) / "bf16" or the enum's ints; before finalize() only."""
+        self.ctx._ck(self.L.mi355_yolox_net_set_precision(self.h, YOLOX_PRECISION.get(precision, precision)))
+
+    def precision(self):
+        return int(self.L.mi355_yolox_net_precision(self.h))
 
     def finalize(self):
         self.ctx._ck(self.L.mi355_yolox_net_finalize(self.h))
@@ -2091,6 +2102,15 @@ class Context:
         for k, v in fields.items():
             setattr(op, k, v)
         self._ck(self.L.mi355_selftest_yolox_net_op_device(self.h, C.byref(op)))
+
+    def selftest_yolox_net_op_bf16(self, **fields):
+        """mi355_selftest_yolox_net_op_bf16_device (test only): a dense conv ("conv") or the Focus stem ("focus") as a BF16 net runs it;
+        weight is f32 on the device."""
+        op = YoloxNetOp()
+        fields["kind"] = YOLOX_OP[fields["kind"]]
+        for k, v in fields.items():
+            setattr(op, k, v)
+        self._ck(self.L.mi355_selftest_yolox_net_op_bf16_device(self.h, C.byref(op)))
 
     # ---- handdetectiontensordec / handlandmarktensordec (analytics/analytics/src/hand)
     def handdec_palm(self, tensor, params, return_count=False):

@@ -1148,6 +1148,28 @@ int mi355_selftest_yolox_head_check(const mi355_yolox_level *levels, int n_level
  *              The dense kernel has two tile shapes (64 channels x 64 or x 16 pixels; a forward takes the narrow one where the wide
  *              one would leave compute units without a block); every output is the same chain of 16-term steps under both, so the
  *              choice changes no byte.
+ *   _set_precision   OPT-IN bf16 operands on the matrix cores. MI355_YOLOX_PRECISION_F32 (the default: everything above,
+ *              byte for byte) or MI355_YOLOX_PRECISION_BF16; allowed between _create and _finalize, before or after the _set_param
+ *              calls, any number of times - the last value holds. After _finalize, for an unknown value and for a null net:
+ *              MI355_ERR_INVALID_ARG. _precision returns the value (null net: MI355_ERR_INVALID_ARG). A BF16 net:
+ *                - every dense convolution (op kinds 0 and 4: the Focus stem and the nine prediction layers included) takes bf16
+ *                  operands: a weight is rounded once at _finalize (on the device, into a second store beside the f32 one; an F32 net
+ *                  allocates nothing new), an input activation as it is read; the pixel values 0 .. 255 are exact in bf16;
+ *                - both roundings are round to nearest, ties to even; products are exact in f32 and accumulation is f32; the order
+ *                  of accumulation inside a matrix instruction is the hardware's and is not pinned;
+ *                - the epilogue is the f32 one unchanged: fmaf(acc, scale, shift), SiLU, residual, scale and shift as above;
+ *                - activations stay f32 in the arena: views, arena plan, level buffers, depthwise, pool, upsample, head decode and
+ *                  input conversion run the code they always ran; _launches and _arena_info are those of the F32 net;
+ *                - deterministic: the same call twice gives the same bytes, a frame's maps depend neither on n_frames nor on its
+ *                  position, the tile choice changes no byte (one instruction per output and 32-term step under either tile); no
+ *                  atomics, no split accumulation;
+ *                - operands of magnitude >= 2^127, NaN and f32 subnormals are outside the specification.
+ *              The price, measured with the numpy restatement on the 40 seeded cases: the raw maps differ from the f64 maps by
+ *              0.5 % to 5.8 % of a level's RMS. Group members of a BF16 net inherit the mode; a net has one precision for life.
+ *   mi355_selftest_yolox_net_op_bf16_device : test only: op kinds 0 and 4 (others: MI355_ERR_INVALID_ARG) of the struct above under
+ *              BF16: `weight` is f32 on the device and is packed by the routine _finalize uses, then the kernel a BF16 forward
+ *              launches runs. tile: 0 as a forward chooses, 1 the 64 x 16 form, 4 the 64 x 64 form; anything else INVALID_ARG.
+ *              Synchronises the context's stream (the packed copy is the call's own).
  * A net belongs to the context it was created on and is destroyed before it. */
 typedef struct mi355_yolox_net mi355_yolox_net;
 typedef struct mi355_yolox_net_config {
@@ -1164,6 +1186,8 @@ typedef struct mi355_yolox_net_config {
 #define MI355_YOLOX_NET_L(num_classes) {1.0, 1.0, 0, (num_classes), 0}
 #define MI355_YOLOX_NET_X(num_classes) {1.33, 1.25, 0, (num_classes), 0}
 #define MI355_YOLOX_NET_MAX_FRAMES 64
+#define MI355_YOLOX_PRECISION_F32 0
+#define MI355_YOLOX_PRECISION_BF16 1
 #define MI355_YOLOX_NET_MAX_SIDE 2048
 #define MI355_YOLOX_NET_NAME_MAX 96   /* a name_cap that holds every parameter name */
 typedef struct mi355_yolox_net_plan {
@@ -1202,6 +1226,9 @@ int mi355_selftest_yolox_net_plan(const mi355_yolox_net_config *config, int n_fr
 int mi355_selftest_yolox_net_param_info(const mi355_yolox_net_config *config, int index, char *name, size_t name_cap, uint32_t dims[4],
                                         int *n_dims);
 int mi355_selftest_yolox_net_op_device(mi355_ctx *ctx, const mi355_yolox_net_op *op);
+int mi355_yolox_net_set_precision(mi355_yolox_net *net, int precision);
+int mi355_yolox_net_precision(const mi355_yolox_net *net);
+int mi355_selftest_yolox_net_op_bf16_device(mi355_ctx *ctx, const mi355_yolox_net_op *op);
 
 /* ---------------------------------------------------------------- handdetectiontensordec / handlandmarktensordec (csrc/handdec.hip)
  * Replaces the decode loops of the two hand decoders: extract_hands_from_palm_detection with is_valid_palm_candidate_normalized

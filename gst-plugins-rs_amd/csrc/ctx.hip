@@ -521,20 +521,43 @@ static int colorlut_bpp(int format) {
   return 0;
 }
 
+}  // extern "C"
+
+namespace mi355 {
+// The argument checks of the device entry, shared with the group's colorlut queue (group.hip: mi355_group_submit_colorlut), so that
+// a frame the one refuses is a frame the other refuses, with the same status and in the same order.
+int colorlut_check_frames(bool lut_loaded, const uint8_t *d_src, size_t src_pitch, int src_stride, const uint8_t *d_dst, size_t dst_pitch, int dst_stride,
+                          int n_frames, int width, int height, int format, int *bpp_out, const char **why) {
+  const int bpp = *bpp_out = colorlut_bpp(format);
+  if (!bpp) { *why = "colorlut: format must be RGBA, RGBA64_LE or RGBA64_BE"; return MI355_ERR_INVALID_ARG; }
+  if (!lut_loaded) { *why = "No LUT configured"; return MI355_ERR_NOT_CONFIGURED; }
+  if (n_frames < 0 || width < 0 || height < 0) { *why = "colorlut: negative size"; return MI355_ERR_INVALID_ARG; }
+  if (n_frames == 0 || width == 0 || height == 0) return MI355_OK;
+  if (!d_src || !d_dst) { *why = "colorlut: null data"; return MI355_ERR_INVALID_ARG; }
+  // (a negative stride is below any row's bytes: compared as signed first, where the cast would have let it through)
+  if (src_stride < 0 || dst_stride < 0 || (size_t)src_stride < (size_t)width * bpp || (size_t)dst_stride < (size_t)width * bpp) {
+    *why = "colorlut: stride smaller than row bytes";
+    return MI355_ERR_INVALID_ARG;
+  }
+  if (n_frames > 1 && (src_pitch < (size_t)(height - 1) * (size_t)src_stride + (size_t)width * bpp ||
+                       dst_pitch < (size_t)(height - 1) * (size_t)dst_stride + (size_t)width * bpp)) {
+    *why = "colorlut: frame pitch smaller than one frame (frames would overlap)";
+    return MI355_ERR_INVALID_ARG;
+  }
+  return MI355_OK;
+}
+}  // namespace mi355
+
+extern "C" {
+
 int mi355_colorlut_frames_device(mi355_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int src_stride, uint8_t *d_dst,
                                  size_t dst_pitch, int dst_stride, int n_frames, int width, int height, int format) {
   REQUIRE_CTX(ctx);
-  const int bpp = colorlut_bpp(format);
-  if (!bpp) return set_error(ctx, MI355_ERR_INVALID_ARG, "colorlut: format must be RGBA, RGBA64_LE or RGBA64_BE");
-  if (!ctx->lut.loaded) return set_error(ctx, MI355_ERR_NOT_CONFIGURED, "No LUT configured");
-  if (n_frames < 0 || width < 0 || height < 0) return set_error(ctx, MI355_ERR_INVALID_ARG, "colorlut: negative size");
+  int bpp = 0;
+  const char *why = nullptr;
+  const int bad = colorlut_check_frames(ctx->lut.loaded, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, format, &bpp, &why);
+  if (bad) return set_error(ctx, bad, why);
   if (n_frames == 0 || width == 0 || height == 0) return MI355_OK;
-  if (!d_src || !d_dst) return set_error(ctx, MI355_ERR_INVALID_ARG, "colorlut: null data");
-  if ((size_t)src_stride < (size_t)width * bpp || (size_t)dst_stride < (size_t)width * bpp)
-    return set_error(ctx, MI355_ERR_INVALID_ARG, "colorlut: stride smaller than row bytes");
-  if (n_frames > 1 && (src_pitch < (size_t)(height - 1) * (size_t)src_stride + (size_t)width * bpp ||
-                       dst_pitch < (size_t)(height - 1) * (size_t)dst_stride + (size_t)width * bpp))
-    return set_error(ctx, MI355_ERR_INVALID_ARG, "colorlut: frame pitch smaller than one frame (frames would overlap)");
   BIND_DEVICE(ctx);
   const int rc = launch_colorlut(ctx, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_frames, width, height, format);
   if (rc == MI355_OK) note_written(ctx->device, d_dst, (size_t)(n_frames - 1) * dst_pitch + (size_t)dst_stride * (size_t)height);

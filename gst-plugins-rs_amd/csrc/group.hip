@@ -19,10 +19,10 @@
 //   * results are the two element launches', bit for bit (same arithmetic, same table);
 //   * frames the batched kernels do not take (padded rows, 3-byte formats, no table) run through their context's own path,
 //     in order.
-// Six more queues live beside the filter batches, each with its own HIP stream(s), pending list, rendezvous and stats, and none
+// Seven more queues live beside the filter batches, each with its own HIP stream(s), pending list, rendezvous and stats, and none
 // touching another. They are SET QUEUES: one protocol written once - SetQueue<Kind>: submit's tail, flush in sets of up to 32 of
 // one class in submission order, each set dealt out to the kind's lanes, the lingering wait, collect-once results per lane,
-// retire, stats, destroy - with six kinds:
+// retire, stats, destroy - with seven kinds:
 //   * CmpKind, videocompare pairs (submit_compare). The one kind with classes (algorithm, geometry, format, Dssim form) and lanes:
 //     a set's pairs, sorted by reference frame, go out as contiguous shares on up to 16 streams.
 //   * CdKind, colordetect frames (submit_colordetect).
@@ -41,6 +41,9 @@
 //     written on the device, nothing to bring back. hsvfilter works IN PLACE and is the one kind whose members must not share
 //     bytes within a launch: its submit entry launches what is pending in front of a frame that overlaps a pending one, and the
 //     sets of the queue's one stream run in order.
+//   * ClKind, colorlut frames (submit_colorlut): a third FrameKind, source to destination - own size, strides, format and the LUT
+//     of the member's context - as at most two launches over a job table, colorlut_group.hip. Its submit entry launches what is
+//     pending in front of a frame that writes what a pending one reads or writes, or reads what a pending one writes.
 // A further kind is a struct beside these - payload, result, kSetMax, its names, ensure, plan (PayloadPlan, if the launch reads
 // the payloads as they are), the size of its pinned block (if any), launch, result, failed, destroy; OneLane, or its own same_class
 // / split / lanes - or, for frames written on the device, the traits of a FrameKind. It is a SetQueue<Kind> member of mi355_group
@@ -149,7 +152,7 @@ Waited wait_seq_unlocking(std::deque<S> &sets, uint64_t seq, std::unique_lock<st
   return Waited::kDone;
 }
 
-// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its six kinds
+// ------------------------------------------------------------------ the set queue (SetQueue<Kind>) and its seven kinds
 // A kind is what differs between the queues: what is submitted (Payload), what a wait takes (Result), what a launch reads (Plan),
 // what a set in flight owns (SetData: its pinned `block` and what `result` needs besides), how a set is launched and read back, how
 // large its block has to be, the resources of first use - and which pending items may share a launch set (same_class) and how
@@ -295,7 +298,7 @@ struct CdKind : PayloadPlan<CdFrame, kCdSetMax> {
 };
 
 // ---- frames written on the device, across independent element instances: one device frame per submit, and nothing comes back but
-// the launch's status - a set owns NO pinned block and the queue no scratch. Two kinds, each a few lines of traits (the frame, its
+// the launch's status - a set owns NO pinned block and the queue no scratch. Three kinds, each a few lines of traits (the frame, its
 // names, its launch-set function in hsv_kernels.hip and the bytes a frame's launch writes):
 //   HdKind  hsvdetector (mi355_group_submit_hsvdetect): source to destination.
 //   HfKind  hsvfilter (mi355_group_submit_hsvfilter): IN PLACE, so the frames of a set must not overlap, which the submit entry sees
@@ -313,6 +316,15 @@ struct HfTraits {
   static constexpr const char *kName = "hsvfilter", *kItem = "hsvfilter frame", *kWaitEntry = "mi355_group_wait_hsvfilter";
   static constexpr auto kLaunchSet = hsvfilter_launch_set;
   static const void *written(const HfFrame &f, size_t *bytes) { *bytes = (size_t)f.stride * (size_t)f.height; return f.data; }
+};
+// ClKind  colorlut (mi355_group_submit_colorlut): source to destination through the LUT the member's context held at submit
+//         (borrowed until the wait returns); a frame that meets a pending one launches what is pending first, as hsvfilter's does.
+struct ClTraits {
+  using Frame = ClFrame;
+  static constexpr int kSetMax = kClSetMax;
+  static constexpr const char *kName = "colorlut", *kItem = "colorlut frame", *kWaitEntry = "mi355_group_wait_colorlut";
+  static constexpr auto kLaunchSet = colorlut_launch_set;
+  static const void *written(const ClFrame &f, size_t *bytes) { *bytes = (size_t)f.dst_stride * (size_t)f.height; return f.dst; }
 };
 template <class T>
 struct FrameKind : PayloadPlan<typename T::Frame, T::kSetMax> {
@@ -349,6 +361,7 @@ struct FrameKind : PayloadPlan<typename T::Frame, T::kSetMax> {
 };
 using HdKind = FrameKind<HdTraits>;
 using HfKind = FrameKind<HfTraits>;
+using ClKind = FrameKind<ClTraits>;
 
 // ---- yolov8tensordec2 / yoloxtensordec across independent element instances (mi355_group_submit_yolodec): one device tensor per
 // submit; its kept count and records come back through the set's pinned block. Consecutive sets share the device scratch.
@@ -907,7 +920,7 @@ struct mi355_group : GroupCore {
   // table references of retired batches: dropping the last reference to a table frees 64 MiB behind a device-wide wait, which
   // does not belong under `mu` - the entry points empty this list into a local one that dies after they have unlocked (Locked)
   std::vector<std::shared_ptr<void>> dead_refs;
-  // ---- the six set queues: each its own streams (and scratch, and blocks), created at its first submit, independent of the
+  // ---- the seven set queues: each its own streams (and scratch, and blocks), created at its first submit, independent of the
   // filter batches above and of each other
   SetQueue<CmpKind> cmp; // videocompare pairs (Dssim / Blockhash)
   SetQueue<CdKind> cd;   // colordetect frames
@@ -915,6 +928,7 @@ struct mi355_group : GroupCore {
   SetQueue<YdKind> yd;   // decoder tensors
   SetQueue<HnKind> hn;   // hand tensors (palm and landmarks)
   SetQueue<HfKind> hf;   // hsvfilter frames (in place)
+  SetQueue<ClKind> cl;   // colorlut frames (each with its context's LUT)
 };
 
 namespace {
@@ -1067,9 +1081,10 @@ void for_each_queue_but_compare(mi355_group *g, F &&f) {
   f(g->yd);
   f(g->hn);
   f(g->hf);
+  f(g->cl);
 }
 
-// ... and for all six, the compare queue first: flush and destroy treat it as every other
+// ... and for all seven, the compare queue first: flush and destroy treat it as every other
 template <class F>
 void for_each_set_queue(mi355_group *g, F &&f) {
   f(g->cmp);
@@ -1395,6 +1410,76 @@ int mi355_selftest_hsvfilter_set_plan(int n_cu, const mi355_hsvfilter_plan_frame
     f.force_generic = p.force_generic;
   }
   return hsvfilter_set_plan(n_cu, fr.data(), n_frames, out, n_sets);
+}
+
+// One frame as the colorlut queue takes it, for the submit entry and the selftest alike: the lone entry's checks (ctx.hip), then the
+// queue's own - the element never works in place, so a frame whose own source and destination meet is refused.
+static int colorlut_frame_of(bool lut_loaded, const uint8_t *d_src, int src_stride, uint8_t *d_dst, int dst_stride, int width, int height, int format,
+                             ClFrame *f, const char **why) {
+  int bpp = 0;
+  if (int rc = colorlut_check_frames(lut_loaded, d_src, 0, src_stride, d_dst, 0, dst_stride, 1, width, height, format, &bpp, why)) return rc;
+  *f = ClFrame{};
+  f->src = d_src;
+  f->dst = d_dst;
+  f->src_stride = src_stride;
+  f->dst_stride = dst_stride;
+  f->width = width;
+  f->height = height;
+  f->format = format;
+  f->size = 2;
+  if (colorlut_frame_in_place(*f)) { *why = "colorlut: the frame's source and destination overlap"; return MI355_ERR_INVALID_ARG; }
+  return MI355_OK;
+}
+
+int mi355_group_set_colorlut_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {
+  return queue_set_rendezvous(g, &mi355_group::cl, expected_streams, linger_us);
+}
+
+int mi355_group_submit_colorlut(mi355_group *g, mi355_ctx *ctx, const uint8_t *d_src, int src_stride, uint8_t *d_dst, int dst_stride, int width, int height,
+                                int format, uint64_t *ticket) {
+  if (!g) return MI355_ERR_INVALID_ARG;
+  Locked L(g);
+  if (!ctx || !ticket) return fail(g, MI355_ERR_INVALID_ARG, "group: null context or ticket");
+  ClFrame f{};
+  const char *why = nullptr;
+  if (int rc = colorlut_frame_of(ctx->lut.loaded, d_src, src_stride, d_dst, dst_stride, width, height, format, &f, &why)) return fail(g, rc, why);
+  // the context's LUT, borrowed until the wait returns: the cells stay where mi355_colorlut_load put them
+  const LutDevice &lut = ctx->lut;
+  f.cells = lut.d_cells;
+  f.is3d = lut.is3d;
+  f.size = lut.size;
+  for (int c = 0; c < 3; c++) { f.scale[c] = lut.scale[c]; f.offset[c] = lut.offset[c]; }
+  f.force_generic = ctx->force_generic;
+  // A frame that writes what a pending one reads or writes, or reads what a pending one writes, must not share its launch. What is
+  // pending goes out first (sets of the queue's one stream run in order), so the frames come out as the lone calls in submission
+  // order. A failure of that launch is told to the waits of the frames it carried; this frame is queued whatever it did.
+  bool meets = false;
+  for (const auto &d : g->cl.pending) meets |= colorlut_frames_meet(d.p, f);
+  if (meets) {
+    if (hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return fail(g, MI355_ERR_HIP, "hipSetDevice"); }
+    (void)g->cl.flush_locked(g);
+  }
+  // an empty frame touches nothing: it does not make the set wait for its stream
+  return g->cl.submit(g, ctx, f, width > 0 && height > 0, ticket);
+}
+
+int mi355_group_wait_colorlut(mi355_group *g, uint64_t ticket) { return queue_wait_status(g, &mi355_group::cl, ticket); }
+
+int mi355_group_colorlut_stats(mi355_group *g, uint64_t stats[4]) { return queue_stats(g, &mi355_group::cl, stats); }
+
+int mi355_selftest_colorlut_set_plan(int n_cu, const mi355_colorlut_plan_frame *frames, int n_frames, mi355_colorlut_plan_out *out, int *n_sets) {
+  if (n_cu < 1 || n_frames < 0 || !n_sets || (n_frames && (!frames || !out))) return MI355_ERR_INVALID_ARG;
+  std::vector<ClFrame> fr((size_t)n_frames);
+  for (int i = 0; i < n_frames; i++) {
+    const mi355_colorlut_plan_frame &p = frames[i];
+    const char *why = nullptr;
+    // (a LUT is taken as loaded - the plan does not depend on it; a frame with a pixel has addresses: null is what submit refuses)
+    if (colorlut_frame_of(true, (const uint8_t *)(uintptr_t)p.src_address, p.src_stride, (uint8_t *)(uintptr_t)p.dst_address, p.dst_stride, p.width, p.height,
+                          p.format, &fr[(size_t)i], &why))
+      return MI355_ERR_INVALID_ARG;
+    fr[(size_t)i].force_generic = p.force_generic;
+  }
+  return colorlut_set_plan(n_cu, fr.data(), n_frames, out, n_sets);
 }
 
 int mi355_group_set_yolodec_rendezvous(mi355_group *g, int expected_streams, unsigned linger_us) {

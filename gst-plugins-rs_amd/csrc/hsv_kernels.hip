@@ -19,6 +19,7 @@
 #include "internal.hpp"
 #include "exact_math.hpp"
 #include "hsv_device.hpp"
+#include "job_set.hpp"
 
 namespace mi355 {
 
@@ -641,14 +642,6 @@ struct HdJobTable {
 static_assert(sizeof(HdJob) == 80, "HdJob has no padding holes");
 static_assert(sizeof(HdJobTable) <= 4096, "the job table is passed in the kernel arguments");
 
-// the job of block b: jobs are in first_block order and every job of a table has at least one block (HdJobTable, HfJobTable)
-template <class Table>
-__device__ __forceinline__ int hsvdetect_job_of(const Table &T, uint32_t b) {
-  int j = 0;
-  while (j + 1 < T.n_jobs && b >= T.job[j].first_block + T.job[j].blocks) j++;
-  return j;
-}
-
 __global__ __launch_bounds__(256) void hsvdetect_jobs_kernel(const HdJobTable T) {
   const int j = hsvdetect_job_of(T, blockIdx.x);
   const uint32_t rel = blockIdx.x - T.job[j].first_block;
@@ -739,50 +732,8 @@ int hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_per_block, int n_
   return MI355_OK;
 }
 
-// A launch set: the two job tables (HdJobTable, HfJobTable) that hsvdetect_launch_set and hsvfilter_set_build classify frames into
-// and fill, and their grids. Planned and launched here, for both elements.
-//   kVec  four pixels per lane: 512 units per block (two groups per lane), 64 blocks per CU - the lone grid_for(ctx, (n_vec + 1) / 2, 256, 64)
-//   kLit  one pixel per lane, literally: 256 units per block, 32 blocks per CU - the lone grid_for(ctx, total, 256, 32)
-namespace {  // (host only, this file only)
-enum { kVec = 0, kLit = 1 };
-template <class Table>
-struct JobSet {
-  typedef void (*Kernel)(const Table);
-  Table table[2];
-  uint32_t blocks[2];
-
-  // first_block / blocks of every job, by hsvdetect_plan over the jobs' own units; a table with a job has at least one block
-  int plan(int n_cu) {
-    constexpr int kMax = (int)(sizeof(Table::job) / sizeof(Table::job[0]));
-    static_assert(kMax <= kHdSetMax, "hsvdetect_plan takes up to kHdSetMax jobs");
-    const unsigned per_block[2] = {512, 256};
-    const int per_cu[2] = {64, 32};
-    for (int h = 0; h < 2; h++) {
-      Table &T = table[h];
-      uint64_t units[kMax];
-      uint32_t first[kMax], n[kMax];
-      for (int j = 0; j < T.n_jobs; j++) units[j] = T.job[j].units;
-      const int rc = hsvdetect_plan(n_cu, per_cu[h], per_block[h], T.n_jobs, units, first, n, &blocks[h]);
-      if (rc || (T.n_jobs && !blocks[h])) return rc ? rc : MI355_ERR_INVALID_ARG;
-      for (int j = 0; j < T.n_jobs; j++) { T.job[j].first_block = first[j]; T.job[j].blocks = n[j]; }
-    }
-    return MI355_OK;
-  }
-
-  // whichever table has a job goes out on `stream`; *kernel_launches counts on. what[h]: the launch's name in the error text
-  int launch(hipStream_t stream, const Kernel (&kernel)[2], const char *const (&what)[2], int *kernel_launches, std::string *err) const {
-    for (int h = 0; h < 2; h++) {
-      if (!table[h].n_jobs) continue;
-      hipLaunchKernelGGL(kernel[h], dim3(blocks[h]), dim3(256), 0, stream, table[h]);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) { *err = std::string(what[h]) + hipGetErrorString(e); return MI355_ERR_HIP; }
-      (*kernel_launches)++;
-    }
-    return MI355_OK;
-  }
-};
-}  // namespace
-
+// A launch set is a JobSet (job_set.hpp) over HdJobTable or HfJobTable: hsvdetect_launch_set and hsvfilter_set_build classify frames
+// into its two tables and fill them; it plans and launches them, for both elements, on the grid of kHsvJobGrid.
 int hsvdetect_launch_set(hipStream_t stream, int n_cu, const HdFrame *frames, int n, int *kernel_launches, std::string *err) {
   *kernel_launches = 0;
   if (!frames || n < 1 || n > kHdSetMax) { *err = "hsvdetector: bad launch set"; return MI355_ERR_INVALID_ARG; }

@@ -345,6 +345,32 @@ bool hsvfilter_frames_overlap(const HfFrame &a, const HfFrame &b);
 int hsvfilter_set_plan(int n_cu, const HfFrame *frames, int n, mi355_hsvfilter_plan_out *out, int *n_sets);
 // n <= kHfSetMax checked frames on `stream`: the vector launch and / or the literal launch, whichever has a job with a pixel
 int hsvfilter_launch_set(hipStream_t stream, int n_cu, const HfFrame *frames, int n, int *kernel_launches, std::string *err);
+// launch sets of the video group's colorlut queue (colorlut_group.hip): frames of independent instances, each with the LUT its context
+// held at submit (borrowed: the cells stay the context's), source to destination, one job table
+constexpr int kClSetMax = MI355_COLORLUT_SET_MAX;
+struct ClFrame {
+  const uint8_t *src;
+  uint8_t *dst;
+  int src_stride, dst_stride, width, height, format;
+  const float *cells;  // the LUT as the reference stores it (LutDevice::d_cells)
+  int is3d, size;
+  float scale[3], offset[3];
+  int force_generic;   // the member's MI355_FLAG_FORCE_GENERIC at submit
+};
+// the checks of mi355_colorlut_frames_device (ctx.hip; both entries call it), in its order; *bpp: bytes per pixel of the format; *why
+// names the refusal. MI355_OK with n_frames, width or height 0 means "nothing to do"
+int colorlut_check_frames(bool lut_loaded, const uint8_t *d_src, size_t src_pitch, int src_stride, const uint8_t *d_dst, size_t dst_pitch, int dst_stride,
+                          int n_frames, int width, int height, int format, int *bpp, const char **why);
+// do a frame's own source and destination byte ranges [p, p + (height - 1) stride + width bpp) meet? (no pixel: no byte)
+bool colorlut_frame_in_place(const ClFrame &f);
+// must `later` run after `earlier` has finished: its destination range meets earlier's source or destination, or its source meets
+// earlier's destination (ranges only: conservative). The one test of the submit entry and of the set builder
+bool colorlut_frames_meet(const ClFrame &earlier, const ClFrame &later);
+// host only: the sets n frames go out in - a new one at kClSetMax frames and in front of a frame that meets one of the set - and per
+// frame its set, launch (0 no pixel, 1 vector, 2 literal), geometry class, units and blocks; the builder colorlut_launch_set launches from
+int colorlut_set_plan(int n_cu, const ClFrame *frames, int n, mi355_colorlut_plan_out *out, int *n_sets);
+// n <= kClSetMax checked frames on `stream`: the vector launch and / or the literal launch, whichever has a job with a pixel
+int colorlut_launch_set(hipStream_t stream, int n_cu, const ClFrame *frames, int n, int *kernel_launches, std::string *err);
 
 // agingradio (agingradio.hip): one job = one element instance's buffer. The host fills the table (alpha and the quantise factor
 // computed with its libm); the group (agroup.hip) submits one job per member, a context a table of one.

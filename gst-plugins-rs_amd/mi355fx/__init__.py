@@ -42,6 +42,7 @@ FLAG_WINDOW_STATS = 18
 FLAG_DSSIM_FAST = 19
 HSVDETECT_SET_MAX = 32   # MI355_HSVDETECT_SET_MAX: detector frames per launch set of a Group
 HSVFILTER_SET_MAX = 32   # MI355_HSVFILTER_SET_MAX: hsvfilter frames per launch set of a Group
+COLORLUT_SET_MAX = 32    # MI355_COLORLUT_SET_MAX: colorlut frames per launch set of a Group
 YOLODEC_SET_MAX = 32     # MI355_YOLODEC_SET_MAX: decoder tensors per launch set of a Group
 MIXER_FRAME_TILE = 64    # MI355_MIXER_FRAME_TILE: frames per block of the mixer kernel
 
@@ -60,6 +61,18 @@ class HsvFilterPlanFrame(C.Structure):
 class HsvFilterPlanOut(C.Structure):
     """mi355_hsvfilter_plan_out: where the builder puts a frame (launch: 0 no pixel, 1 vector, 2 literal)."""
     _fields_ = [("set", C.c_int32), ("launch", C.c_int32), ("variant", C.c_int32), ("first_block", C.c_uint32), ("blocks", C.c_uint32),
+                ("reserved", C.c_uint32), ("units", C.c_uint64)]
+
+
+class ColorLutPlanFrame(C.Structure):
+    """mi355_colorlut_plan_frame: one frame as mi355_selftest_colorlut_set_plan takes it; the addresses are numbers."""
+    _fields_ = [("src_address", C.c_uint64), ("dst_address", C.c_uint64), ("src_stride", C.c_int32), ("dst_stride", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("format", C.c_int32), ("force_generic", C.c_int32)]
+
+
+class ColorLutPlanOut(C.Structure):
+    """mi355_colorlut_plan_out: where the builder puts a frame (launch: 0 no pixel, 1 vector, 2 literal; geometry: 1 flat, 2 rowpad)."""
+    _fields_ = [("set", C.c_int32), ("launch", C.c_int32), ("geometry", C.c_int32), ("first_block", C.c_uint32), ("blocks", C.c_uint32),
                 ("reserved", C.c_uint32), ("units", C.c_uint64)]
 
 
@@ -383,6 +396,11 @@ def load_library():
         "mi355_group_wait_hsvfilter": (i, [vp, C.c_uint64]),
         "mi355_group_hsvfilter_stats": (i, [vp, C.POINTER(C.c_uint64)]),
         "mi355_selftest_hsvfilter_set_plan": (i, [i, C.POINTER(HsvFilterPlanFrame), i, C.POINTER(HsvFilterPlanOut), C.POINTER(C.c_int)]),
+        "mi355_group_set_colorlut_rendezvous": (i, [vp, i, C.c_uint]),
+        "mi355_group_submit_colorlut": (i, [vp, vp, u8p, i, u8p, i, i, i, i, C.POINTER(C.c_uint64)]),
+        "mi355_group_wait_colorlut": (i, [vp, C.c_uint64]),
+        "mi355_group_colorlut_stats": (i, [vp, C.POINTER(C.c_uint64)]),
+        "mi355_selftest_colorlut_set_plan": (i, [i, C.POINTER(ColorLutPlanFrame), i, C.POINTER(ColorLutPlanOut), C.POINTER(C.c_int)]),
         "mi355_agroup_create_echo": (vp, [i, i, sz, C.POINTER(C.c_int)]),
         "mi355_agroup_create_ebur128": (vp, [i, i, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mi355_agroup_create_loudnorm": (vp, [i, i, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int)]),
@@ -775,6 +793,27 @@ class Group:
         self._ck(self.L.mi355_group_hsvfilter_stats(self.h, c))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
+    # ---- colorlut frames of independent elements, each through its context's LUT
+    def set_colorlut_rendezvous(self, expected_streams, linger_us):
+        self._ck(self.L.mi355_group_set_colorlut_rendezvous(self.h, expected_streams, linger_us))
+
+    def submit_colorlut(self, ctx, d_src, src_stride, d_dst, dst_stride, width, height, fmt):
+        """One device frame of stream `ctx`, source to destination through the LUT loaded in `ctx` (borrowed until the wait returns;
+        fmt: a name or the enum's int); returns the ticket."""
+        t = C.c_uint64(0)
+        self._ck(self.L.mi355_group_submit_colorlut(self.h, ctx.h, d_src, src_stride, d_dst, dst_stride, width, height, FMT.get(fmt, fmt), C.byref(t)))
+        return t.value
+
+    def wait_colorlut(self, ticket):
+        """Returns once the frame's destination holds what Context.colorlut_frames_device would have written."""
+        self._ck(self.L.mi355_group_wait_colorlut(self.h, ticket))
+
+    def colorlut_stats(self):
+        """(frames launched, launch sets, frames in the largest set, kernel launches)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.L.mi355_group_colorlut_stats(self.h, c))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
     # ---- yolov8tensordec2 / yoloxtensordec tensors of independent elements
     def set_yolodec_rendezvous(self, expected_streams, linger_us):
         self._ck(self.L.mi355_group_set_yolodec_rendezvous(self.h, expected_streams, linger_us))
@@ -909,6 +948,25 @@ def selftest_hsvfilter_set_plan(frames, n_cu=256):
         fr[k] = HsvFilterPlanFrame(f[0], f[1], f[2], f[3], FMT.get(f[4], f[4]), HsvSettings(*[float(v) for v in f[5]]), int(f[6]) if len(f) > 6 else 0)
     rc = L.mi355_selftest_hsvfilter_set_plan(n_cu, fr, n, out, C.byref(n_sets))
     return rc, n_sets.value, [dict(set=o.set, launch=o.launch, variant=o.variant, units=int(o.units), first_block=o.first_block, blocks=o.blocks)
+                              for o in list(out)[:n]]
+
+
+def selftest_colorlut_set_plan(frames, n_cu=256):
+    """mi355_selftest_colorlut_set_plan (host only): what the colorlut queue's builder makes of frames in submission order.
+    frames: (src_address, src_stride, dst_address, dst_stride, width, height, fmt[, force_generic]) each, the addresses numbers that
+    are never dereferenced, fmt a name or the enum's int; or None for null arrays. Returns (status, n_sets, [dict(set, launch,
+    geometry, units, first_block, blocks)])."""
+    L = load_library()
+    n_sets = C.c_int(-1)
+    if frames is None:
+        return L.mi355_selftest_colorlut_set_plan(n_cu, None, 1, None, C.byref(n_sets)), n_sets.value, []
+    n = len(frames)
+    m = max(n, 1)
+    fr, out = (ColorLutPlanFrame * m)(), (ColorLutPlanOut * m)()
+    for k, f in enumerate(frames):
+        fr[k] = ColorLutPlanFrame(f[0], f[2], f[1], f[3], f[4], f[5], FMT.get(f[6], f[6]), int(f[7]) if len(f) > 7 else 0)
+    rc = L.mi355_selftest_colorlut_set_plan(n_cu, fr, n, out, C.byref(n_sets))
+    return rc, n_sets.value, [dict(set=o.set, launch=o.launch, geometry=o.geometry, units=int(o.units), first_block=o.first_block, blocks=o.blocks)
                               for o in list(out)[:n]]
 
 

@@ -17,9 +17,15 @@
  * costs one upload, one launch and one download - DESIGN.md §6: 1.4 k frames/s at 4K, PCIe-bound, against 410 for two
  * synchronous elements. transform_frame stays as the synchronous fallback (no pipeline: mi355_pipe_create failed).
  * propose_allocation / decide_allocation put input and output buffers in pinned memory (d3d12colorlut/imp.rs:385-492 is
- * the reference's precedent for an element that brings its own memory). */
+ * the reference's precedent for an element that brings its own memory).
+ *
+ * With MI355_GROUP_MEMBERS=n (n >= 2) in the environment the n instances of the process hand the frames that lie in this project's
+ * device memory (and carry no deferred hsvfilter) to the device's dispatcher instead (mi355_group_submit_colorlut): the frames of an
+ * interval - each with its own size, format and LUT - share a launch set. The bytes are the lone call's; host buffers, the fused
+ * hand-over and the one-frame-deep pipeline are untouched. */
 #include "gstmi355common.h"
 #include "../gst-plugins-rs_amd/host/mi355fx_host.h"
+#include <stdlib.h>
 
 GST_DEBUG_CATEGORY_STATIC(gst_color_lut_debug);
 #define GST_CAT_DEFAULT gst_color_lut_debug
@@ -44,6 +50,8 @@ struct _GstColorLut {
   mi355_pipe *pipe;  /* asynchronous upload / compute / download pipeline of the library (NULL: synchronous fallback) */
   GQueue jobs;       /* ColorLutJob*, oldest first; streaming thread only */
   gboolean have_lut; /* State { lut: Option<CubeLut> } (imp.rs:55-58) */
+  /* MI355_GROUP_MEMBERS=n: the process's dispatcher (mi355_group_shared), held between start and stop */
+  mi355_group *group;
 };
 
 G_DEFINE_TYPE(GstColorLut, gst_color_lut, GST_TYPE_VIDEO_FILTER)
@@ -113,6 +121,9 @@ static gboolean gst_color_lut_start(GstBaseTransform *trans) {
     return FALSE;
   }
   self->have_lut = TRUE;
+  const char *members = g_getenv("MI355_GROUP_MEMBERS");
+  if (members && atoi(members) >= 2 && (self->group = mi355_group_shared(0, &status)))
+    (void)mi355_group_set_colorlut_rendezvous(self->group, atoi(members), 2000); /* every instance submits + waits at once; a straggler is waited for 2 ms */
   return TRUE;
 }
 
@@ -204,7 +215,14 @@ static GstFlowReturn gst_color_lut_generate_output(GstBaseTransform *trans, GstB
         if (drc == MI355_OK && dhsv)
           drc = mi355_hsv_colorlut_frames_device(self->ctx, d_src, GST_VIDEO_INFO_SIZE(ii), GST_VIDEO_INFO_PLANE_STRIDE(ii, 0), d_dst, GST_VIDEO_INFO_SIZE(oi),
                                                  GST_VIDEO_INFO_PLANE_STRIDE(oi, 0), 1, GST_VIDEO_INFO_WIDTH(ii), GST_VIDEO_INFO_HEIGHT(ii), &dhsv->settings);
-        else if (drc == MI355_OK)
+        else if (drc == MI355_OK && self->group) {
+          /* the frame joins whatever the other instances have pending; the LUT stays loaded until stop(), past the wait */
+          uint64_t ticket = 0;
+          drc = mi355_group_submit_colorlut(self->group, self->ctx, d_src, GST_VIDEO_INFO_PLANE_STRIDE(ii, 0), d_dst, GST_VIDEO_INFO_PLANE_STRIDE(oi, 0),
+                                            GST_VIDEO_INFO_WIDTH(ii), GST_VIDEO_INFO_HEIGHT(ii), dfmt, &ticket);
+          if (drc == MI355_OK) drc = mi355_group_wait_colorlut(self->group, ticket);
+          if (drc != MI355_OK) GST_ERROR_OBJECT(self, "colorlut through the group: %s", mi355_group_last_error(self->group));
+        } else if (drc == MI355_OK)
           drc = mi355_colorlut_frames_device(self->ctx, d_src, GST_VIDEO_INFO_SIZE(ii), GST_VIDEO_INFO_PLANE_STRIDE(ii, 0), d_dst, GST_VIDEO_INFO_SIZE(oi),
                                              GST_VIDEO_INFO_PLANE_STRIDE(oi, 0), 1, GST_VIDEO_INFO_WIDTH(ii), GST_VIDEO_INFO_HEIGHT(ii), dfmt);
         if (drc == MI355_OK) drc = mi355_buf_commit(bin, self->ctx);
@@ -331,6 +349,8 @@ static gboolean gst_color_lut_stop(GstBaseTransform *trans) {
   (void)color_lut_drain(self, FALSE);
   if (self->pipe) mi355_pipe_destroy(self->pipe);
   self->pipe = NULL;
+  if (self->group) mi355_group_release(self->group); /* (every frame has been waited for: the LUT is no longer borrowed) */
+  self->group = NULL;
   self->have_lut = FALSE;
   if (self->ctx) mi355_ctx_destroy(self->ctx);
   self->ctx = NULL;

@@ -462,6 +462,83 @@ int mi355_group_hsvfilter_stats(mi355_group *group, uint64_t stats[4]);
 int mi355_selftest_hsvfilter_set_plan(int n_cu, const mi355_hsvfilter_plan_frame *frames, int n_frames,
                                       mi355_hsvfilter_plan_out *out, int *n_sets);
 
+/* ---- colorlut frames of INDEPENDENT element instances (csrc/group.hip, csrc/colorlut_group.hip)
+ * colorlut is one instance per stream and one buffer per call (video/colorlut/src/colorlut/imp.rs:203-223): a process that grades 32
+ * cameras, each with its own .cube, makes 32 lone launches per frame period, and mi355_group_submit_chain / _fused batch only frames
+ * behind an hsvfilter that agree in size, settings and LUT. submit_colorlut queues one device frame of stream `ctx`, source to
+ * destination, and whatever is pending goes out as at most TWO launches over a job table in the kernel arguments, on the queue's
+ * own HIP stream. Members are fully independent: each frame has its own size, strides and format (MI355_FMT_RGBA, MI355_FMT_RGBA64_LE,
+ * MI355_FMT_RGBA64_BE) and the LUT that is loaded in `ctx` at the submit - 1D or 3D, any size and domain mi355_colorlut_load
+ * accepts. After wait_colorlut d_dst holds what mi355_colorlut_frames_device(ctx, d_src, 0, src_stride, d_dst, 0, dst_stride, 1, width,
+ * height, format) would have written, bit for bit (the alpha byte or word copied), and no byte of d_dst outside the width pixels of
+ * each of height rows has changed. The destination is recorded as recently written, as the lone entry records it.
+ *   submit : never blocks; the checks and status codes are those of mi355_colorlut_frames_device with n_frames = 1, in its order
+ *           (format; MI355_ERR_NOT_CONFIGURED without a LUT; negative sizes; null data with a pixel; a stride below the row bytes; a
+ *           null ctx or a null ticket: MI355_ERR_INVALID_ARG). One refusal is the queue's own: the element never works in place
+ *           (the note at mi355_colorlut_frames_device speaks of two different frames), so a frame whose own source and destination
+ *           byte ranges [p, p + (height - 1) * stride + width * bytes per pixel) meet is MI355_ERR_INVALID_ARG. A refused submit
+ *           queues nothing. A frame with width == 0 or height == 0 is accepted, gets a ticket and touches nothing. The frame is
+ *           processed after what ctx's HIP stream held at the call.
+ *   borrowing : between the submit and the return of wait_colorlut for its ticket the frame's bytes AND the context's LUT are
+ *           borrowed: no mi355_colorlut_load, no mi355_colorlut_unload and no mi355_ctx_destroy of `ctx` in between (the rule of
+ *           mi355_group_submit_chain). Only the LUT's cells, kind, size and domain are read: the member's MI355_FLAG_FORCE_GENERIC
+ *           is read at submit and sends its frame to the literal launch; MI355_FLAG_LUT_VARIANT, the compute / table choice, the
+ *           memoised tables, the brick and window kernels and the content watch play no part, and the queue never builds, reads
+ *           or measures a table.
+ *   order  : a submit whose destination range meets the source or the destination range of a frame still pending, or whose source
+ *           range meets a pending destination, first launches what is pending, then queues (ranges only: conservative - two
+ *           sub-pictures side by side in one padded picture count as meeting); sets run in order on the queue's one stream, so the
+ *           bytes are those of the lone calls in submission order. Frames that only share a SOURCE share a set.
+ *   wait   : launches what is pending if the frame has not gone out (rendezvous first), then waits for its launch set; the
+ *           group's lock is not held meanwhile. A result is collected once. Tickets are one sequence per group: a ticket that is
+ *           unknown, already collected or another queue's is MI355_ERR_INVALID_ARG here and stays collectable where it belongs;
+ *           mi355_group_wait, _order_after and the other queues' waits refuse a colorlut ticket likewise.
+ *   set_colorlut_rendezvous : as set_hsvdetect_rendezvous, counted over pending colorlut frames only.
+ *   At most MI355_COLORLUT_SET_MAX frames share a launch set; more go out as consecutive sets. flush, wait_all and destroy cover
+ *   this queue as they cover the others. A launch that fails is reported, once, to each frame's own wait.
+ *   The two launches: the vector launch (four pixels per lane, one 16-byte load and store; each block tables, for ITS job's domain
+ *   and size, the cell index and weight of the 256 byte values per axis in 6 KiB of LDS with the reference's own operations, and
+ *   gathers the eight cells of a pixel from the LUT in global memory) carries the MI355_FMT_RGBA frames of members without
+ *   FORCE_GENERIC whose geometry is flat - both sides packed, both bases and the byte count multiples of 16 - or rowpad - both bases
+ *   and both strides multiples of 16 (units: ceil(width / 4) groups per row). The literal launch (one pixel per lane, the arithmetic
+ *   of the lone FORCE_GENERIC route) carries every other frame: both RGBA64 orders, RGBA frames off the 16-byte grid, FORCE_GENERIC.
+ *   When it pays (measured, DESIGN 4.7.2: 32 members with 32 LUTs of 33^3, one thread, against 32 lone calls and their
+ *   synchronisations): the queue removes launches and synchronisations, not device work, and its vector kernel gathers eight cells
+ *   per pixel where the lone route reads a memoised table or LDS-cached bricks. It gains at 640x640 RGBA (3.3 x), at 1080p RGBA
+ *   (1.19 x; nothing separable when all members hold one LUT) and at 1080p RGBA64 (1.47 x); at 4K RGBA it LOSES (0.56 x: 1.56 ms
+ *   against 0.87 ms per interval). Leave 4K RGBA members on the lone entry.
+ *   colorlut_stats : {frames launched, launch sets, frames in the largest set, kernel launches} - per set 0 launches when no frame
+ *           has a pixel, 1 when all frames are of one class, 2 when both classes occur.
+ *   mi355_selftest_colorlut_set_plan : host only, no device: what the builder the queue launches from makes of n_frames frames in
+ *           submission order (no LUT is needed: the plan does not depend on it). The addresses are numbers and are never
+ *           dereferenced. Per frame: `set`, counted from 0 - a new set begins at MI355_COLORLUT_SET_MAX frames and in front of a
+ *           frame that meets one of the current set (the rule of `order`); `launch`, 0 no pixel, 1 vector, 2 literal; `geometry`,
+ *           vector: 1 flat, 2 rowpad, else 0; `units`, vector: groups of four pixels, literal: pixels; `first_block` and `blocks`,
+ *           its share of its launch's grid by mi355_selftest_hsvdetect_plan's rule (vector: 512 units per block, 16 blocks per CU;
+ *           literal: 256 and 8). *n_sets: the sets. Refused (MI355_ERR_INVALID_ARG): n_cu < 1, n_frames < 0, null arrays with
+ *           n_frames > 0, a null n_sets, and a frame submit would refuse (format, negative sizes, a null address with a pixel,
+ *           strides below the row bytes, own source and destination meeting). */
+#define MI355_COLORLUT_SET_MAX 32 /* frames per launch set */
+typedef struct mi355_colorlut_plan_frame {
+  uint64_t src_address, dst_address; /* the first bytes of source and destination, as numbers */
+  int32_t src_stride, dst_stride, width, height, format;
+  int32_t force_generic;             /* the member's MI355_FLAG_FORCE_GENERIC */
+} mi355_colorlut_plan_frame;
+typedef struct mi355_colorlut_plan_out {
+  int32_t set, launch, geometry;
+  uint32_t first_block, blocks, reserved;
+  uint64_t units;
+} mi355_colorlut_plan_out;
+int mi355_group_set_colorlut_rendezvous(mi355_group *group, int expected_streams, unsigned linger_us);
+int mi355_group_submit_colorlut(mi355_group *group, mi355_ctx *ctx, const uint8_t *d_src, int src_stride, uint8_t *d_dst,
+                                int dst_stride, int width, int height, int format, uint64_t *ticket);
+int mi355_group_wait_colorlut(mi355_group *group, uint64_t ticket);
+/* {frames launched, launch sets, frames in the largest set, kernel launches} */
+int mi355_group_colorlut_stats(mi355_group *group, uint64_t stats[4]);
+/* host only, no device: the sets, launches and blocks of n_frames frames */
+int mi355_selftest_colorlut_set_plan(int n_cu, const mi355_colorlut_plan_frame *frames, int n_frames,
+                                     mi355_colorlut_plan_out *out, int *n_sets);
+
 /* ---------------------------------------------------------------- many AUDIO element instances, few launches (csrc/agroup.hip)
  * rsaudioecho (audio/audiofx/src/audioecho/imp.rs:205-227), ebur128level (audio/audiofx/src/ebur128level/imp.rs:682-745) and
  * audioloudnorm (audio/audiofx/src/audioloudnorm/imp.rs:1545-1586) are one instance per stream and one buffer per call; the batch

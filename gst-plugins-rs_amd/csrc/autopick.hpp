@@ -16,6 +16,11 @@
 //     interpolating kernel for ever once a disturbance has flipped the choice (measured: 34 k frames/s instead of 41 k);
 //   * a decisive answer (the other kind at least twice as slow) sends its next probe straight to the longest period; a sample of
 //     the kind in use that differs from the previous one by more than 25 % (the content changed) brings the probe forward to now;
+//   * settled input - the launch reads what the launch before it wrote, still on-die (hsvfilter ! colorlut), and the table kind is
+//     in use: the samples of the kind in use thin out, n doubling with every sample that agrees with the one before (within the
+//     25 %) up to 1024 launches. Each sample puts two timestamp markers of ~5 us into the caller's stream and keeps two kernels'
+//     tails apart, and there it only repeats the previous one. A sample that differs by more than 25 % still brings the probe
+//     forward and returns n to its start, as does a change of the kind in use, of the launch size or of the input's provenance;
 //   * a change of launch size by more than 2x restarts the learning;
 //   * a LUT reload keeps what was learnt as the prior (lut_upload): the choice depends on the content, hardly on the LUT.
 #pragma once
@@ -51,6 +56,9 @@ struct AutoPolicy {
   double hysteresis_back = -1.0;
   bool smooth = false;
   bool last_probe = false;                // the launch decided last was a learning / probe launch (auto_decide)
+  // settled input (auto_decide): launches between two samples of the table kind in use, from auto_sample_every doubling up to
+  // kProbeMax while the samples agree; 0 = not climbing (the every-n-th cadence)
+  unsigned sample_period = 0, since_sample = 0;
 };
 
 struct AutoDecision {
@@ -83,13 +91,16 @@ inline void auto_complete(AutoPolicy &A, double ms) {
       // changed, and what is known about the OTHER kind is as old as its last probe - ask it again now, not in up to 1024 launches.
       A.probe_period = kProbeMin;
       A.since_probe = kProbeMin;
+      A.sample_period = 0;  // ... and watch the kind in use closely again
       regime = true;
+    } else if (in_use && before > 0.0 && A.sample_period) {
+      A.sample_period = A.sample_period * 2 > kProbeMax ? kProbeMax : A.sample_period * 2;  // it agrees with the one before: the next one may wait
     }
     if (A.t_compute > 0.0 && A.t_table > 0.0) {
       // hysteresis (3 % by default): measurements of near-equal kernels must not flip the choice back and forth
       const double back = A.hysteresis_back < 0.0 ? A.hysteresis : A.hysteresis_back;
       const bool table = A.t_table < A.t_compute * (A.table ? 1.0 + back : 1.0 - A.hysteresis);
-      if (table != A.table) { A.probe_period = kProbeMin; A.since_probe = 0; }
+      if (table != A.table) { A.probe_period = kProbeMin; A.since_probe = 0; A.sample_period = 0; }
       else if ((A.pending_probe || !both_before) && !regime) {
         // the answer stays: ask again later. A probe is two launches of the SLOWER kind (on uniform noise the table kernel takes three
         // times the interpolating one: the five probes of the 64 ... 1024 ladder cost BENCH_r05's 32-launch uniform leg 10 %), so a
@@ -104,13 +115,16 @@ inline void auto_complete(AutoPolicy &A, double ms) {
   A.pending_kind = -1;
 }
 
-// what this call runs (after the harvest step); updates the counters
-inline AutoDecision auto_decide(AutoPolicy &A, size_t n_vec) {
+// what this call runs (after the harvest step); updates the counters. settled: the launch reads what the launch before it wrote,
+// still on-die - there the provenance rule fixes which kernel reads the table (colorlut_kernels.hip: launch_table_raw) and a sample
+// of the table kind only repeats the one before until the content changes; see the header.
+inline AutoDecision auto_decide(AutoPolicy &A, size_t n_vec, bool settled = false) {
   if (A.vec && (n_vec > 2 * A.vec || 2 * n_vec < A.vec) && A.pending_kind < 0) {
     A.t_compute = A.t_table = 0.0;
     A.learn = 0;
     A.probe_period = kProbeMin;
     A.since_probe = 0;
+    A.sample_period = 0;
   }
   if (A.pending_kind < 0) A.vec = n_vec;
   AutoDecision D{0, false, false, false};
@@ -135,7 +149,17 @@ inline AutoDecision auto_decide(AutoPolicy &A, size_t n_vec) {
     }
     if (warming) { A.calls++; return D; }  // never measured: it is neither a sample of the kind in use nor a fair one of the other
   }
-  D.measure = A.pending_kind < 0 && (D.probe || (A.calls % auto_sample_every(n_vec)) == 0);
+  bool due;
+  if (settled && A.learn >= 4 && A.table && !D.probe) {
+    const unsigned base = auto_sample_every(n_vec);
+    if (A.sample_period < base) { A.sample_period = base; A.since_sample = base; }  // the first one now: the ladder needs two to compare
+    due = ++A.since_sample >= A.sample_period;
+  } else {
+    if (!D.probe) A.sample_period = 0;  // (a probe of the other kind is not the end of the settled run)
+    due = (A.calls % auto_sample_every(n_vec)) == 0;
+  }
+  D.measure = A.pending_kind < 0 && (D.probe || due);
+  if (D.measure && !D.probe) A.since_sample = 0;
   A.calls++;
   return D;
 }

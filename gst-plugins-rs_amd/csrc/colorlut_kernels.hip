@@ -1702,7 +1702,7 @@ static void auto_harvest(AutoPick &A) {
 }
 
 template <class Compute, class Ensure, class Table>
-static int auto_launch(mi355_ctx *ctx, AutoPick &A, size_t n_vec, Compute &&compute, Ensure &&ensure, Table &&table) {
+static int auto_launch(mi355_ctx *ctx, AutoPick &A, size_t n_vec, bool settled, Compute &&compute, Ensure &&ensure, Table &&table) {
   int rc;
   if (A.table_unavailable) return compute();
   if (!A.ev0) {
@@ -1710,7 +1710,7 @@ static int auto_launch(mi355_ctx *ctx, AutoPick &A, size_t n_vec, Compute &&comp
     if ((rc = check_hip(ctx, hipEventCreate(&A.ev1), "hipEventCreate"))) return rc;
   }
   auto_harvest(A);
-  const AutoDecision D = auto_decide(A, n_vec);
+  const AutoDecision D = auto_decide(A, n_vec, settled);
   if (D.kind == 1 && (rc = ensure())) {  // a table build stays outside the measurement
     // no memory for the 64 MiB table (or the build failed): this entry point stays on the compute kernel for good
     auto_give_up_table(A);
@@ -1745,7 +1745,7 @@ static TableKernel table_variant_kernel(int v) { return v == 8 ? kTableWindow : 
 // arithmetic over ALL 2^24 colours, the one frame on which every cache of the arithmetic kernels misses: profiles/r06_fused_animated_probe.txt)
 template <class Compute, class Ensure, class Table>
 static int table_front(mi355_ctx *ctx, AutoPick &A, bool table_ok, size_t n_vec, int pin, Settled *seen, const mi355_hsv_settings *hs, int bgr, bool have,
-                       Compute &&compute, Ensure &&ensure, Table &&table) {
+                       bool on_die, Compute &&compute, Ensure &&ensure, Table &&table) {
   if (table_ok && pin > 0) {
     const int rc = ensure();
     return rc ? rc : table();
@@ -1757,7 +1757,7 @@ static int table_front(mi355_ctx *ctx, AutoPick &A, bool table_ok, size_t n_vec,
     A.t_table = 0.0;
     A.learn = 2;
   }
-  return auto_launch(ctx, A, n_vec, compute, ensure, table);
+  return auto_launch(ctx, A, n_vec, on_die, compute, ensure, table);
 }
 
 // colorlut (hs == nullptr: table 0 of the loaded LUT) and the fused entry point (table 1): hsvfilter -> colorlut is also a function
@@ -1772,7 +1772,10 @@ static int lut_front(mi355_ctx *ctx, const LutFrames &F, int format, const mi355
   Rgba8Geom geo;
   const bool table_ok = format == MI355_FMT_RGBA && !ctx->force_generic && rgba8_geom(F, &geo);
   const bool have = !hs || (L.table_ref[1] && L.table_morton[1] == 1 && same_hs(L.table_hs, *hs));
-  return table_front(ctx, L.pick[which], table_ok, geo.n_vec, table_variant(v) ? 1 : (v == 0 ? 0 : -1), hs ? &L.seen : nullptr, hs, 0, have,
+  // the source lies inside what the previous launch wrote (the provenance rule of launch_table_raw: the gather kernel reads the
+  // table): the measured choice samples the table kind on the thinning cadence of autopick.hpp
+  const bool on_die = table_ok && recently_written(ctx->device, F.src, (size_t)geo.sw4 * 16 * (size_t)F.n_frames * (size_t)F.height);
+  return table_front(ctx, L.pick[which], table_ok, geo.n_vec, table_variant(v) ? 1 : (v == 0 ? 0 : -1), hs ? &L.seen : nullptr, hs, 0, have, on_die,
                      [&]() { return hs ? launch_hsv_colorlut_compute(ctx, F, *hs, false) : launch_colorlut_compute(ctx, F, format); },
                      [&]() { return table_ensure(ctx, which, morton, hs); },
                      [&]() { return launch_table_raw(ctx, L.d_table[which], F.src, F.dst, geo, F.width, (size_t)F.n_frames * F.height, morton, sub, &L.last_sub[which]); });
@@ -1884,7 +1887,7 @@ int launch_hsvfilter(mi355_ctx *ctx, uint8_t *d_data, int n_frames, size_t frame
   const int pin = ctx->hsv_table_mode == 2 ? 1 : 0;
   T.last_table = table_ok && pin;  // (a pinned table counts as in use even when it could not be made)
   const bool have = T.valid && T.bgr == fmt.bgr && same_hs(T.hs, hs);
-  return table_front(ctx, T.pick, table_ok, geo.n_vec, pin, &T.seen, &hs, fmt.bgr, have, compute, [&]() { return hsv_table_ensure(ctx, fmt, hs); },
+  return table_front(ctx, T.pick, table_ok, geo.n_vec, pin, &T.seen, &hs, fmt.bgr, have, false, compute, [&]() { return hsv_table_ensure(ctx, fmt, hs); },
                      [&]() { T.last_table = true; return launch_table_raw(ctx, T.d_table, d_data, d_data, geo, width, (size_t)n_frames * height, 1, kTableEither); });
 }
 
@@ -1927,13 +1930,20 @@ extern "C" int mi355_selftest_brickwatch(int n_calls, const double *miss0, const
 
 extern "C" int mi355_selftest_autopick(int n_calls, const uint64_t *n_vec, const double *ms_compute, const double *ms_table, int lag,
                                        int *kind_out, int *measured_out) {
+  return mi355_selftest_autopick_settled(n_calls, n_vec, ms_compute, ms_table, nullptr, lag, kind_out, measured_out);
+}
+
+// ... and with the input's provenance scripted too: settled[i] != 0 = call i reads what the launch before it wrote, still on-die
+// (null: never). tests/test_autopick_provenance_period.py
+extern "C" int mi355_selftest_autopick_settled(int n_calls, const uint64_t *n_vec, const double *ms_compute, const double *ms_table, const int *settled,
+                                               int lag, int *kind_out, int *measured_out) {
   if (n_calls < 0 || !n_vec || !ms_compute || !ms_table || !kind_out || lag < 0) return MI355_ERR_INVALID_ARG;
   mi355::AutoPolicy A;
   double pending_ms = 0.0;
   for (int i = 0; i < n_calls; i++) {
     const size_t nv = (size_t)n_vec[i];
     if (A.pending_kind >= 0 && A.calls - A.pending_call >= (unsigned)lag) mi355::auto_complete(A, pending_ms);
-    const mi355::AutoDecision D = mi355::auto_decide(A, nv);
+    const mi355::AutoDecision D = mi355::auto_decide(A, nv, settled && settled[i]);
     kind_out[i] = D.kind;
     if (measured_out) measured_out[i] = D.measure ? 1 : 0;
     if (D.measure) {

@@ -965,7 +965,7 @@ void retire_done(mi355_group *g) {
 
 bool same_class(const Desc &a, const Desc &b) {
   return a.batchable && b.batchable && a.fused == b.fused && a.width == b.width && a.height == b.height && a.stride == b.stride && a.format == b.format && a.table == b.table &&
-         std::memcmp(&a.hs, &b.hs, sizeof(a.hs)) == 0 && a.ctx->force_generic == b.ctx->force_generic;
+         std::memcmp(&a.hs, &b.hs, sizeof(a.hs)) == 0 && a.ctx->force_generic == b.ctx->force_generic && (a.ctx->hsv_nt == 2) == (b.ctx->hsv_nt == 2);
 }
 
 // launches what is pending, batch by batch - all of it, or (until != 0) only up to the batch that carries ticket `until`: what a
@@ -1376,6 +1376,7 @@ int mi355_group_submit_hsvfilter(mi355_group *g, mi355_ctx *ctx, uint8_t *d_data
   f.stride = stride;
   f.s = *settings;
   f.force_generic = ctx->force_generic;
+  f.hsv_nt = ctx->hsv_nt;
   // In place: a frame that shares bytes with a pending one must not share its launch. What is pending goes out first (sets of the
   // queue's one stream run in order), so the two come out as if filtered one after the other. A failure of that launch is told to
   // the waits of the frames it carried; this frame is queued whatever it did.

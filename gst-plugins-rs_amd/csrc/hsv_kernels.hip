@@ -39,11 +39,25 @@ __device__ __forceinline__ void hsvfilter_quad(uint32_t &a, uint32_t &b, uint32_
   }
 }
 
+// MI355_FLAG_HSV_NT = 2: a lane's 16 bytes as ONE global_store_dwordx4 that carries the system scope (sc0 sc1) and no nt bit. The L2
+// writes the line through as it takes it, so the kernel ends with no dirty backlog for its release to drain, and the line still
+// allocates in the memory-side Infinity Cache, where the launch behind finds it. The compiler has no spelling for this store: a
+// relaxed system-scope atomic gives the bits but is four dword stores, volatile gives them with a wait for every store. The
+// s_nop is the wait state a store of more than 8 bytes needs before a VALU instruction may overwrite its data registers - the
+// compiler inserts it behind its own stores and cannot see into this one. Ordered like any store: the kernel's end releases it.
+__device__ __forceinline__ void hsv_store_through(uint4 *at, const uint4 &p) {
+  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+  const u32x4_t o = {p.x, p.y, p.z, p.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 0" : : "v"(at), "v"(o) : "memory");
+}
+
 // Flat streaming kernel for 4-byte formats on contiguous storage (stride == width*4 and frames
 // back to back): each lane owns 16 B (4 pixels) per iteration -> global_load/store_dwordx4.
 // VARIANT: -1 = GENERIC arithmetic; otherwise FAST, see hsv_shift_of / hsv_sv_ident_of.
-// Plain loads and stores on purpose: with the non-temporal hint on both, this kernel alone is 5 % faster (0.086 against
-// 0.091 ms for the bare read-modify-write of 8 x 4K frames, tools/hsv_mem_probe.hip), but its output then bypasses the
+// nt (MI355_FLAG_HSV_NT): 2, the default, plain loads and write-through stores (hsv_store_through): 0.0823 against 0.0858 ms with
+// plain stores (0), the chain 44.9-45.7 k against 44.0-44.6 k frames/s, in turn on one box (profiles/r07_store_policy_ab.txt).
+// No non-temporal hint on purpose: with it on loads and stores (1) this kernel alone is 2-5 % faster than with plain ones (0.086
+// against 0.091 ms for the bare read-modify-write of 8 x 4K frames, tools/hsv_mem_probe.hip), but its output then bypasses the
 // Infinity Cache and the element behind it reads from HBM: colorlut 0.115 instead of 0.087 ms, the chain 38.5 k instead of
 // 44.4 k frames/s (r03, bench.py). One load in flight per lane: two measured the same or slower once the arithmetic had
 // shrunk (63 VGPRs, 8 waves per SIMD cover the latency).
@@ -56,7 +70,15 @@ __global__ __launch_bounds__(256) void hsvfilter_flat_kernel(uint4 *__restrict__
   hsv_lds_fill<RPOS, GPOS, BPOS, NPOS>(&lds);
   __syncthreads();
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  if (nt) {  // MI355_FLAG_HSV_NT (the A/B of bench.py: what the chain costs when this launch's output bypasses the Infinity Cache)
+  if (nt == 2) {  // MI355_FLAG_HSV_NT = 2: plain loads, write-through stores that stay in the Infinity Cache (hsv_store_through)
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
+      uint4 p = data[i];
+      hsvfilter_quad<VARIANT, RPOS, GPOS, BPOS, NPOS>(p.x, p.y, p.z, p.w, k, &lds);
+      hsv_store_through(data + i, p);
+    }
+    return;
+  }
+  if (nt) {  // MI355_FLAG_HSV_NT = 1 (the A/B of bench.py: what the chain costs when this launch's output bypasses the Infinity Cache)
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     u32x4_t *d4 = (u32x4_t *)data;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
@@ -77,9 +99,9 @@ __global__ __launch_bounds__(256) void hsvfilter_flat_kernel(uint4 *__restrict__
 
 // The flat kernel over up to kMultiFrames SEPARATE frames of one size (blockIdx.y = frame): the frames of different streams
 // batched into one launch by the group dispatcher (group.hip), so that a frame does not pay the ramp and the tail of a launch
-// of its own. Same arithmetic, same per-lane work.
+// of its own. Same arithmetic, same per-lane work; through != 0: the stores of MI355_FLAG_HSV_NT = 2, as the lone kernel's.
 template <int VARIANT, int FIRST, bool BGR>
-__global__ __launch_bounds__(256) void hsvfilter_flat_multi_kernel(MultiFramePtrs frames, size_t n_vec, HsvK k) {
+__global__ __launch_bounds__(256) void hsvfilter_flat_multi_kernel(MultiFramePtrs frames, size_t n_vec, HsvK k, int through) {
   constexpr int RPOS = FIRST + (BGR ? 2 : 0), GPOS = FIRST + 1, BPOS = FIRST + (BGR ? 0 : 2);
   constexpr int NPOS = FIRST == 0 ? 3 : 0;
   __shared__ HsvLds lds;
@@ -90,7 +112,8 @@ __global__ __launch_bounds__(256) void hsvfilter_flat_multi_kernel(MultiFramePtr
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     uint4 p = data[i];
     hsvfilter_quad<VARIANT, RPOS, GPOS, BPOS, NPOS>(p.x, p.y, p.z, p.w, k, &lds);
-    data[i] = p;
+    if (through) hsv_store_through(data + i, p);  // (the launch's: every wave takes the same side)
+    else data[i] = p;
   }
 }
 
@@ -409,9 +432,10 @@ bool hsvfilter_multi_applicable(const uint8_t *const *frames, int n_frames, int 
     if (!frames[f] || (uintptr_t)frames[f] % 16 != 0) return false;
   return true;
 }
-static void launch_flat_multi(hipStream_t stream, int variant, const MultiFramePtrs &frames, int n_frames, size_t n_vec, const HsvK &k, int first, int bgr, int grid_x) {
+static void launch_flat_multi(hipStream_t stream, int variant, const MultiFramePtrs &frames, int n_frames, size_t n_vec, const HsvK &k, int first, int bgr, int grid_x,
+                              int through) {
   with_variant(variant, [&](auto V) { with_byte_order(first, bgr, [&](auto FIRST, auto BGR) {
-    hipLaunchKernelGGL((hsvfilter_flat_multi_kernel<V, FIRST, BGR>), dim3(grid_x, n_frames), dim3(256), 0, stream, frames, n_vec, k);
+    hipLaunchKernelGGL((hsvfilter_flat_multi_kernel<V, FIRST, BGR>), dim3(grid_x, n_frames), dim3(256), 0, stream, frames, n_vec, k, through);
   }); });
 }
 int launch_hsvfilter_multi(mi355_ctx *ctx, hipStream_t stream, uint8_t *const *frames, int n_frames, int width, int height, const PixFmt &fmt,
@@ -424,7 +448,7 @@ int launch_hsvfilter_multi(mi355_ctx *ctx, hipStream_t stream, uint8_t *const *f
   // the same total grid as one launch over n contiguous frames would get, split evenly over the frames
   int gx = grid_for(ctx, ((size_t)n_frames * n_vec + 1) / 2, 256, ctx->hsv_blocks_per_cu) / n_frames;
   if (gx < 1) gx = 1;
-  launch_flat_multi(stream, variant, ptrs, n_frames, n_vec, k, fmt.first, fmt.bgr, gx);
+  launch_flat_multi(stream, variant, ptrs, n_frames, n_vec, k, fmt.first, fmt.bgr, gx, ctx->hsv_nt == 2);
   return check_hip(ctx, hipGetLastError(), "hsvfilter multi-frame kernel launch");
 }
 
@@ -806,7 +830,7 @@ struct HfJob {
   int32_t variant;               // vector launch: the FAST variant (hsv_shift_of / hsv_sv_ident_of); literal launch: >= 0 FAST, -1 generic
   uint32_t flags;                // HF_*: 12- or 16-byte groups (vector), pixel stride and byte positions (literal)
   uint32_t first_block, blocks;  // its blocks in the 1-D grid (hsvdetect_plan)
-  uint32_t pad;
+  uint32_t through;              // vector launch, flat 4-byte frames: the member's MI355_FLAG_HSV_NT was 2 at submit (hsv_store_through)
 };
 struct HfJobTable {
   HfJob job[kHfSetMax];
@@ -863,6 +887,7 @@ __device__ __forceinline__ void hsvfilter_job_groups(const HfJob &J, uint32_t re
     }
   } else {
     uint4 *__restrict__ data = (uint4 *)J.data;
+    const uint32_t through = J.through;
     for (size_t i = (size_t)rel * 256 + threadIdx.x; i < n; i += stride) {
       uint4 p = data[i];
       p.x = __builtin_amdgcn_perm(p.x, 0u, in_sel); p.y = __builtin_amdgcn_perm(p.y, 0u, in_sel);
@@ -870,7 +895,8 @@ __device__ __forceinline__ void hsvfilter_job_groups(const HfJob &J, uint32_t re
       hsvfilter_quad<VARIANT, 0, 1, 2, 3>(p.x, p.y, p.z, p.w, k, lds);
       p.x = __builtin_amdgcn_perm(p.x, 0u, out_sel); p.y = __builtin_amdgcn_perm(p.y, 0u, out_sel);
       p.z = __builtin_amdgcn_perm(p.z, 0u, out_sel); p.w = __builtin_amdgcn_perm(p.w, 0u, out_sel);
-      data[i] = p;
+      if (through) hsv_store_through(data + i, p);  // (the job's, so the block's)
+      else data[i] = p;
     }
   }
 }
@@ -983,6 +1009,7 @@ static int hsvfilter_set_build(int n_cu, const HfFrame *frames, int n, std::vect
         J.in_sel = (4 + rpos) | ((4 + gpos) << 8) | ((4 + bpos) << 16) | ((4 + npos) << 24);
         J.out_sel = (4u << (8 * rpos)) | (5u << (8 * gpos)) | (6u << (8 * bpos)) | (7u << (8 * npos));
         J.variant = wide_variant;
+        J.through = f.hsv_nt == 2;
         if (rowpad) J.flags |= HF_ROWPAD;
         J.units = rowpad ? (uint64_t)(((uint32_t)f.width + 3u) / 4u) * (uint64_t)f.height : total_bytes / (f.fmt.pixel_stride == 4 ? 16 : 12);
       } else {

@@ -137,7 +137,9 @@ struct mi355_ctx {
   bool window_stats_on = false; // MI355_FLAG_WINDOW_STATS: the LDS-cached kernels count {pixels, pixels past the cache, bricks installed} (three atomics per wave: off by default)
   unsigned long long *d_window_counters = nullptr;  // colorlut_window.hip: {pixels, pixels past the LDS cache, bricks installed} x 1024 slots
   int blockhash_any_size = 0;  // MI355_FLAG_BLOCKHASH_ANY_SIZE
-  int hsv_nt = 0;              // MI355_FLAG_HSV_NT: 1 = the flat hsvfilter kernel loads and stores with the non-temporal hint (measurement A/B)
+  int hsv_nt = 2;              // MI355_FLAG_HSV_NT: 2 = plain loads, write-through stores that stay in the Infinity Cache (hsv_kernels.hip:
+                               // hsv_store_through; the default by profiles/r07_store_policy_ab.txt), 0 = plain loads and stores, 1 = both
+                               // with the non-temporal hint (measurement A/B)
   mi355_hsv_settings group_fused_hs{};  // mi355_group_submit_fused: the settings of this stream's last fused submit ...
   unsigned group_fused_stable = 0;      // ... and how many submits in a row have carried them (a composed table is built for settings that stay)
   int hsv_blocks_per_cu = 64;  // grid cap of the flat hsvfilter kernel (tunable: MI355_FLAG_HSV_BLOCKS_PER_CU)
@@ -334,6 +336,7 @@ struct HfFrame {
   PixFmt fmt;
   mi355_hsv_settings s;
   int force_generic;  // the member's MI355_FLAG_FORCE_GENERIC at submit
+  int hsv_nt;         // the member's MI355_FLAG_HSV_NT at submit: 2 = write-through stores for a flat 4-byte frame (1 is the lone entry's A/B only)
 };
 // the checks of mi355_hsvfilter_frames_device for n_frames frames (ctx.hip; both entries call it); *why names the refusal
 int hsvfilter_check_frames(const uint8_t *d_data, int n_frames, size_t frame_pitch, int width, int height, int stride, int format,

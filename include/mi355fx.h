@@ -108,7 +108,7 @@ typedef enum mi355_flag {
   MI355_FLAG_BRICK_PRIO = 9, /* brick-cache kernel, how the waves of a block share work: bit 0 = waves lower their issue priority as they advance through their run, bit 1 = a wave that is done takes tiles from the run with most left (default 3) */
   MI355_FLAG_HRTF_METHOD = 12, /* hrtfrender convolution, read at mi355_hrtf_setup: 0 (default) = overlap-save FFT in LDS from 384-tap HRIRs on (the measured crossover), time-domain FIR below; 1 = FFT, 2 = FIR pinned (each only where it fits the LDS) */
   MI355_FLAG_BLOCKHASH_ANY_SIZE = 15, /* videocompare Blockhash on frames whose width or height is not a multiple of 8: 0 (default) = MI355_ERR_UNSUPPORTED, 1 = the crate's floating-point path (blockhash_slow: every pixel whole to block (floor(x / (w/8)), floor(y / (h/8))) in f32, block sums accumulated in pixel order - one lane per block, sequential by definition, 1-2 ms per 4K frame; restated from memory like the rest of the hash: parity unpinned) */
-  MI355_FLAG_HSV_NT = 14, /* hsvfilter on packed 4-byte frames: 1 = loads and stores carry the non-temporal hint. The kernel alone is ~5 % faster, but its output then bypasses the Infinity Cache and the element behind it reads from HBM (bench.py's `hsvfilter_nontemporal_ab` leg measures exactly that); default 0 */
+  MI355_FLAG_HSV_NT = 14, /* hsvfilter on packed 4-byte frames, how the flat kernels touch memory. 2 (default) = plain loads, write-through stores (system scope, no non-temporal bit): the kernel ends with no dirty L2 lines to drain and its output still allocates in the Infinity Cache, where the element behind it finds it; + 2.3 % on the hsvfilter ! colorlut chain against 0 = plain loads and stores (profiles/r07_store_policy_ab.txt). 1 = loads and stores carry the non-temporal hint: the kernel alone is 2-5 % faster than 0, but its output then bypasses the Infinity Cache and the element behind it reads from HBM (bench.py's `hsvfilter_nontemporal_ab` leg measures exactly that; lone entry only). The bytes are the same under all three */
   MI355_FLAG_WINDOW_ORDER = 17, /* LDS-cached table kernel: how its blocks share the picture: 1 (default) = aligned fronts (block b takes strip b % n_strips, layer b / n_strips; the blocks of a layer walk down side by side, so the chip streams a few bands of full rows), 0 = a contiguous share of the column-major step list each (round 4); A/B knob */
   MI355_FLAG_WINDOW_STATS = 18, /* 1 = the LDS-cached table kernels count pixels / pixels served past the cache / bricks installed for mi355_colorlut_window_stats (three atomics per wave; default 0) */
   MI355_FLAG_WINDOW_MIN_STEPS = 13, /* LDS-cached table kernel (LUT variants 0 / 8): smallest launch it serves, in 256 x 32 pixel steps per CU (default 3; 0 = any size - its first step per block runs on a cold cache, so small launches are faster through the gather kernels) */
@@ -204,6 +204,11 @@ int mi355_selftest_brickwatch(int n_calls, const double *miss0, const double *sl
  * readable `lag` calls later. kind_out[i] = 0 interpolating / 1 table, measured_out[i] (optional) = launch was bracketed. */
 int mi355_selftest_autopick(int n_calls, const uint64_t *n_vec, const double *ms_compute, const double *ms_table, int lag,
                             int *kind_out, int *measured_out);
+/* The same with the input's provenance scripted: settled[i] != 0 means call i reads what the launch before it wrote, still
+ * on-die (hsvfilter ! colorlut); there the samples of the table kind in use thin out to one per 1024 launches while they
+ * agree. settled == NULL is mi355_selftest_autopick. */
+int mi355_selftest_autopick_settled(int n_calls, const uint64_t *n_vec, const double *ms_compute, const double *ms_table, const int *settled,
+                                    int lag, int *kind_out, int *measured_out);
 /* Replaces transform_frame's body: transform_rgba / transform_rgba64::<LE>
  * (colorlut/imp.rs:203-223 -> :226-397). format in {RGBA, RGBA64_LE, RGBA64_BE}; src and dst are
  * plane 0 of two different frames with independent strides; rows = chunks(stride).take(height). */
@@ -403,8 +408,9 @@ int mi355_selftest_hsvdetect_plan(int n_cu, int blocks_per_cu, unsigned units_pe
  *           MI355_FMT_RGBA64_* included -, settings pointer, negative sizes, null data with a non-empty frame, stride against line
  *           bytes; a null ctx or a null ticket: MI355_ERR_INVALID_ARG). A refused submit queues nothing. A frame with width == 0 or
  *           height == 0 is accepted, gets a ticket and writes nothing. The settings are copied and the member's
- *           MI355_FLAG_FORCE_GENERIC is read at submit; MI355_FLAG_HSV_NT and the context's memoised hsv table play no part: the
- *           group's kernels use plain loads and stores and compute. The frame is processed after what ctx's HIP stream held at the
+ *           MI355_FLAG_FORCE_GENERIC is read at submit, and MI355_FLAG_HSV_NT for its value 2 (write-through stores for a packed,
+ *           aligned 4-byte frame); its value 1 and the context's memoised hsv table play no part: the
+ *           group's kernels otherwise use plain loads and stores and compute. The frame is processed after what ctx's HIP stream held at the
  *           call, and is read and written until wait_hsvfilter for the ticket has returned.
  *   order  : in place means order matters: two frames of one launch never touch the same bytes. Overlap is judged on the byte
  *           ranges [d_data, d_data + (height - 1) * stride + width * pixel_stride) - ranges only, conservative. A submit that
